@@ -1,8 +1,19 @@
 #!/usr/bin/env python
 """bench.py — SIMILAR TOP-K throughput of the MI355X-native vector_engine hot path.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline figure needs and nothing else: it builds the index once, runs W warmup steps, times
+EXACTLY K steps and prints the line (`value`, `ms_per_step` and the `roofline` figures of that very loop; the slots of the
+legs below stay null).  `--full` adds everything else the line can carry: the median over `--rebuilds` index rebuilds (default 3),
+the exactness certificate, the mirror legs, config 3 (`batched`), the concurrent callers, the CPU baseline, live PMC traffic,
+the isolated-kernel and read-ceiling probes, configs 2 and 5 and the SURVEY §8(f) legs (child runs), and at N > 1 the
+gather + merge timing and the one-process-handle leg.
+`--dump-outputs DIR` writes what the last timed step returned — rows.npy (float64), scores.npy (float32), counts.npy
+(float64), one row per query of the step — so that two builds can be compared output for output: corpus, queries and mask
+are generated from fixed seeds, the same for the same arguments.
 
 Workload (BASELINE.json `metric`): 10M x 768 f32 cosine brute-force TOP-100.  One "step" = one pass of the hot path over
 one batch of `--nq` synthetic queries (default 1: the HBM-bound single-query scan the roofline target is quoted on).  The
@@ -118,8 +129,13 @@ def parse():
     ap.add_argument("--streams", type=int, default=2,
                     help="HIP streams the steps are pipelined over (each stream runs whole steps in order; with 2 "
                          "the select/rescore/gather tail of one query overlaps the next query's scan)")
-    ap.add_argument("--rebuilds", type=int, default=3,
-                    help="index builds the timed loop is repeated over; value = the median (buffer placement moves one draw by several %%)")
+    ap.add_argument("--rebuilds", type=int, default=None,
+                    help="index builds the timed loop is repeated over; value = the median (buffer placement moves one draw by several %%); "
+                         "default 1, 3 with --full")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beside the headline loop (see the module docstring); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's rows / scores / counts to DIR/<name>.npy (float64 / float32)")
     ap.add_argument("--mask", type=float, default=1.0,
                     help="selectivity of a synthetic WHERE-predicate bitmap (config 5); 1.0 = no mask")
     ap.add_argument("--mirror", type=int, default=0, choices=[0, 1, 2],
@@ -386,7 +402,7 @@ def _child_json(cmd, timeout):
 def other_configs():
     """BASELINE.json configs 2 and 5 as child runs (each needs its own resident corpus: 3 GB and 61 GB).  Every child is this
     script on that workload: headline = the f32-corpus sweep, the library's default mirror sweep beside it — both come back."""
-    base = [sys.executable, os.path.abspath(__file__), "--no-cpu-baseline", "--no-other-configs", "--batched", "0", "--callers", "0",
+    base = [sys.executable, os.path.abspath(__file__), "--full", "--no-cpu-baseline", "--no-other-configs", "--batched", "0", "--callers", "0",
             "--legs", "i8", "--no-live-pmc", "--warmup", "3", "--rebuilds", "1"]
     runs = [("config2_1Mx768_cosine_top100", ["--rows", "1000000", "--steps", "200", "--rebuilds", "3"]),
             ("config5_10Mx1536_l2_top1000_mask1.0", ["--dim", "1536", "--metric", "euclidean", "--k", "1000", "--steps", "12"]),
@@ -767,8 +783,29 @@ def handle_child(args):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+def dump_outputs(path, rows, scores, counts, budget=(64 << 20) - 4096):  # (room for the three .npy headers)
+    """What the timed path returned in its last step, as float64 / float32 .npy files under `path`.  Above `budget` bytes a fixed,
+    seeded sample of the step's queries is written (and, should one query's list alone exceed it, the head of every list)."""
+    os.makedirs(path, exist_ok=True)
+    rows = np.asarray(rows).astype(np.float64)  # row ids < 2**53: exact
+    scores = np.asarray(scores).astype(np.float32)
+    counts = np.asarray(counts).astype(np.float64)
+    per_query = rows.shape[1] * (8 + 4) + 8
+    if rows.shape[0] * per_query > budget:
+        keep = max(1, budget // per_query)
+        sel = np.sort(np.random.default_rng(0x5EED0007).choice(rows.shape[0], keep, replace=False))
+        rows, scores, counts = rows[sel], scores[sel], counts[sel]
+    if rows.size * 12 > budget:
+        cols = max(1, (budget - 8 * rows.shape[0]) // (12 * rows.shape[0]))
+        rows, scores = rows[:, :cols], scores[:, :cols]
+    for name, a in (("rows", rows), ("scores", scores), ("counts", counts)):
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     args = parse()
+    if args.rebuilds is None:
+        args.rebuilds = 3 if args.full else 1
     if args.pmc_child:
         return pmc_child(args)
     if args.next_rows_child:
@@ -923,8 +960,8 @@ def main():
 
     default_workload = (args.rows == 10_000_000 and args.dim == 768 and args.k == 100 and args.nq == 1 and
                         args.metric == "cosine" and args.mask >= 1.0 and args.mirror == 0)
-    extras = world == 1 and not args.always_gather
-    leg_modes = [] if (args.no_mirror_legs or args.mirror != 0 or args.k > 4096 or args.nq != 1) else \
+    extras = args.full and world == 1 and not args.always_gather  # the legs of a full single-GPU run
+    leg_modes = [] if (not args.full or args.no_mirror_legs or args.mirror != 0 or args.k > 4096 or args.nq != 1) else \
         [m for m, nm in ((1, "i8"), (2, "bf16")) if nm in args.legs.split(",")]
 
     # ---- the headline: median over index rebuilds --------------------------------------------------------------------
@@ -946,6 +983,8 @@ def main():
                 batched_draws.setdefault(mode, []).append(
                     measure_batched(args, state["idx"], dev, metric, total_rows, torch, certify=(b == max(1, args.rebuilds) - 1)))
             state["idx"].set_mirror(args.mirror)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *last_out)  # (every rank holds the global top-k: rank 0 writes it)
     idx = state["idx"]
     med = int(np.argsort(draws)[len(draws) // 2])  # the median draw: `value`, `ms_per_step` AND the kernel time come from this one loop
     elapsed = float(draws[med])
@@ -954,7 +993,7 @@ def main():
     scan_ms, elem_bytes, cands = infos[med]["scan_ms"], infos[med]["elem_bytes"], [i["candidates"] for i in infos]
     scan_avg = float(np.mean(scan_ms)) if scan_ms else float("nan")
     hbm_bytes_per_row = (hbm0[0] + hbm0[1] + hbm0[2]) / max(local_rows, 1)
-    scan_alone = isolated_kernel_ms() if world == 1 else None
+    scan_alone = isolated_kernel_ms() if world == 1 and args.full else None
     # corpus sweeps per step, from the sweep the LIBRARY says it ran (nmn_search_stats.sweep_kind): the matrix-core sweeps serve a
     # whole pass of queries per corpus read, the VALU sweeps 4 (2 on the 8-bit mirror), the ring sweep and the large-k scan one
     def passes_of(sweep):
@@ -974,12 +1013,12 @@ def main():
     kernel_name = KERNEL_OF_SWEEP.get(sweep_name, sweep_name)
 
     # ---- read ceiling of this device: the scan's access pattern with the arithmetic removed ----
-    read_ceiling = idx.read_probe(3) if local_rows else None
+    read_ceiling = idx.read_probe(3) if local_rows and args.full else None
 
     # ---- parity of the last result ----
     parity = None
     q_last = q_host[(args.steps - 1) % n_query_sets][0]
-    if not args.no_parity:
+    if args.full and not args.no_parity:
         o_rows, o_scores, o_counts = last_out
         parity = certificate(idx, q_last, metric, o_rows.view(np.uint64), o_scores, o_counts, world, dev, mask_host)
 
@@ -988,7 +1027,7 @@ def main():
     if world > 1 or args.always_gather:
         s0 = state["searchers"][0]
         gm = []
-        for i in range(12):
+        for i in range(12 if args.full else 0):
             fence()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             with torch.cuda.stream(streams[0]):
@@ -1000,7 +1039,7 @@ def main():
         multi = {"rccl_ranks": rccl_ranks if backend == "nccl" else 0, "ranks": rccl_ranks,
                  "collective_backend": "nccl (RCCL over xGMI)" if backend == "nccl" else backend,
                  "rank_id_all_gather": "ranks 0..N-1 seen in order on every rank before the measurement",
-                 "rows_per_gpu": rows_per_gpu, "gather_plus_merge_ms": float(np.median(gm[2:])),
+                 "rows_per_gpu": rows_per_gpu, "gather_plus_merge_ms": float(np.median(gm[2:])) if gm else None,
                  "gather_bytes_per_rank": int(state["searchers"][0]._bufs["size"]), "host": "one process per GPU (torch.distributed)",
                  # how to read `value` across N: a query scans the WHOLE corpus, every GPU its shard.  Under weak scaling the corpus
                  # grows with N (10M rows per GPU), so queries/s staying level IS linear scaling — the quantity that grows with N is
@@ -1111,7 +1150,7 @@ def main():
         idx.set_mirror(args.mirror)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         ga = None
         if args.mask >= 1.0 and args.nq == 1:  # the resident index's answer to one of the baseline's queries, for the checker
             ga = (1,) + tuple(idx.search(q_host[1][0], args.k, metric))
@@ -1145,7 +1184,7 @@ def main():
     if world > 1 or args.always_gather:
         dist.barrier()  # every rank is done with its collectives before any of them tears the group down
         dist.destroy_process_group()
-    if rank == 0 and world > 1 and not args.no_handle_leg and multi is not None:
+    if rank == 0 and world > 1 and args.full and not args.no_handle_leg and multi is not None:
         # the same GPUs, ONE process, through the C ABI's nmn_sharded handle (its create runs the rank all-gather self-test)
         try:
             time.sleep(1.0)  # the other ranks are exiting and returning their HBM

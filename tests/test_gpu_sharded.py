@@ -84,7 +84,7 @@ def test_bench_two_ranks_control_flow_on_one_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, NMN_BENCH_DEVICE="0", NMN_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29517", os.path.join(root, "bench.py"), "--gpus", "2", "--rows", "300000", "--steps", "6",
+           "--master-port", "29517", os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--rows", "300000", "--steps", "6",
            "--warmup", "2"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=root)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

@@ -6,7 +6,7 @@ O=$R/gpurun_out/r02p
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 for NQ in 64 128; do
-  ARGS="--batched $NQ --steps 3 --warmup 1 --no-other-configs --no-cpu-baseline --callers 0 --no-f32-leg --no-live-pmc --no-parity"
+  ARGS="--full --batched $NQ --steps 3 --warmup 1 --no-other-configs --no-cpu-baseline --callers 0 --no-f32-leg --no-live-pmc --no-parity"
   timeout 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $O/f$NQ -o f -- python $R/bench.py $ARGS > $O/f$NQ.log 2>&1
   timeout 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $O/w$NQ -o w -- python $R/bench.py $ARGS > $O/w$NQ.log 2>&1
   F=$(find $O/f$NQ -name "*.db" | head -1); W=$(find $O/w$NQ -name "*.db" | head -1)

@@ -5,7 +5,7 @@
 # tools/variant_ab.sh "--dim 1536 --metric euclidean --k 1000 --steps 12 --mask 0.1" default pipe6
 R=${GRAFT_REPO_ROOT:-$(cd $(dirname $0)/.. && pwd)}
 ARGS=$1; shift
-COMMON="--no-cpu-baseline --no-other-configs --batched 0 --callers 0 --no-mirror-legs --no-live-pmc --warmup 3 --rebuilds 1"
+COMMON="--full --no-cpu-baseline --no-other-configs --batched 0 --callers 0 --no-mirror-legs --no-live-pmc --warmup 3 --rebuilds 1"
 for round in $(seq ${ROUNDS:-2}); do
   for v in "$@"; do
     if [ "$v" = default ]; then unset NEUMANN_GPU_LIB; else export NEUMANN_GPU_LIB=$R/neumann_amd/lib/variants/libneumann_gpu_$v.so; fi
