@@ -233,6 +233,14 @@ typedef struct nmn_engine_ivf nmn_engine_ivf; /* (IVFIndex, Vec<String> key_mapp
 void nmn_ivf_options_default(nmn_ivf_options* o);
 /* build_ivf_index (lib.rs:2641-2694): k-means (bit for bit) and list assignment on the GPU, see nmn_ivf_build */
 nmn_status nmn_engine_build_ivf_index(nmn_engine* e, const nmn_ivf_options* options, nmn_engine_ivf** out);
+/* build_ivf_index for any storage (IVFBuildOptions::{flat, pq, binary}, lib.rs:941-1000); storage NULL = Flat, see
+ * nmn_ivf_build_ex.  dim % pq_num_subspaces != 0: NMN_ERR_CONFIGURATION and no index (the reference panics). */
+nmn_status nmn_engine_build_ivf_index_ex(nmn_engine* e, const nmn_ivf_options* options, const nmn_ivf_storage* storage,
+                                         nmn_engine_ivf** out);
+/* estimate_ivf_memory (lib.rs:2821-2851): num_clusters x d x 4 + (Flat n x d x 4 | PQ n x M | Binary n x ceil(d / 64) x 8)
+ * + n x 8; 0 for an empty engine.  Host arithmetic, no device needed. */
+nmn_status nmn_engine_estimate_ivf_memory(nmn_engine* e, const nmn_ivf_options* options, const nmn_ivf_storage* storage,
+                                          uint64_t* out_bytes);
 void nmn_engine_ivf_free(nmn_engine_ivf* ivf);
 uint64_t nmn_engine_ivf_len(const nmn_engine_ivf* ivf);
 uint32_t nmn_engine_ivf_clusters(const nmn_engine_ivf* ivf);
@@ -272,7 +280,7 @@ nmn_status nmn_engine_load_index_binary(nmn_engine* e, const char* path, char* n
 nmn_strlist* nmn_engine_save_all_indices(nmn_engine* e, const char* dir, nmn_status* status);              /* 3944-3971 */
 nmn_strlist* nmn_engine_load_all_indices(nmn_engine* e, const char* dir, nmn_status* status);              /* 3980-3999 */
 /* The (IVFIndex, key_mapping) pair of build_ivf_index with its trained centroids and lists: a restart restores it
- * without k-means (the reference rebuilds: lib.rs:2641-2694). */
+ * without k-means (the reference rebuilds: lib.rs:2641-2694).  IVF-Flat only (PQ / Binary: NMN_ERR_CONFIGURATION). */
 nmn_status nmn_engine_ivf_save(nmn_engine_ivf* ivf, const char* path);
 nmn_status nmn_engine_ivf_load(nmn_engine* e, const char* path, nmn_engine_ivf** out);
 

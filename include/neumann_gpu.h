@@ -525,8 +525,48 @@ nmn_status nmn_ivf_search(nmn_ivf* ivf, const float* queries, uint32_t nq, uint3
  * it (those are scanned through a bitmap over the id-ordered rows meanwhile).  0: no copy (fewer than 4096 vectors, or no
  * HBM for it) — every probe goes through the bitmap.  Results are the same either way. */
 uint64_t nmn_ivf_list_major_rows(const nmn_ivf* ivf);
-/* The flat index holding the vectors (exhaustive search over the same rows, stats, ...). */
+/* The flat index holding the vectors (exhaustive search over the same rows, stats, ...).  NULL for a PQ / Binary index. */
 nmn_index* nmn_ivf_vectors(nmn_ivf* ivf);
+
+/* ---- IVF-PQ / IVF-Binary storage (tensor_store/src/ivf.rs:61-157, pq.rs, binary_quantization.rs) ---------------- */
+
+/* IVFStorage: how the vectors of the lists are kept.  PQ and Binary keep only codes in HBM — no f32 row stays on the device
+ * once nmn_ivf_build_ex returns.  Centroids and list assignment are Flat's (the same exact k-means and nearest-centroid
+ * sweep); a PQ index also trains a codebook on the residuals v - centroid[list(v)] (ivf.rs:235-249, pq.rs:114-169). */
+#define NMN_IVF_FLAT 0
+#define NMN_IVF_PQ 1
+#define NMN_IVF_BINARY 2
+#define NMN_BINARY_SIGN 0   /* BinaryThreshold::Sign:   bit i = v[i] > 0.0 */
+#define NMN_BINARY_MEAN 1   /* BinaryThreshold::Mean:   bit i = v[i] > sequential f32 sum / len */
+#define NMN_BINARY_MEDIAN 2 /* BinaryThreshold::Median: bit i = v[i] > the middle element (f64 midpoint of the two middle ones) */
+typedef struct nmn_ivf_storage {
+    int32_t kind;                   /* NMN_IVF_FLAT / NMN_IVF_PQ / NMN_IVF_BINARY */
+    uint32_t pq_num_subspaces;      /* PQConfig::num_subspaces (8); dim % it must be 0, else NMN_ERR_CONFIGURATION */
+    uint32_t pq_num_centroids;      /* PQConfig::num_centroids (256); K' = min(it, n) codewords per subspace */
+    nmn_kmeans_options pq_kmeans;   /* PQConfig::kmeans_config (KMeansConfig::default), separate from the IVF k-means */
+    int32_t binary_threshold;       /* NMN_BINARY_SIGN / _MEAN / _MEDIAN */
+} nmn_ivf_storage;
+/* IVFStorage::Flat, PQConfig::default and BinaryThreshold::Sign */
+void nmn_ivf_storage_default(nmn_ivf_storage* s);
+/* nmn_ivf_build for any storage (nmn_ivf_build == this with NMN_IVF_FLAT).  PQ: K' = min(pq_num_centroids, n) codewords per
+ * subspace, each subspace one exact k-means over the residuals' sub-vectors with storage->pq_kmeans.  A PQ / Binary index
+ * holds desc->capacity_rows codes, not rows. */
+nmn_status nmn_ivf_build_ex(const nmn_index_desc* desc, const float* rows_host, uint64_t n, uint32_t num_clusters,
+                            const nmn_kmeans_options* kmeans, const nmn_ivf_storage* storage, nmn_ivf** out);
+/* nmn_ivf_create for any storage: centroids (HOST, n_clusters x dim) and, for PQ, the codebook trained elsewhere (HOST,
+ * [M][K][dim / M] f32; nullable when K == 0) with K codewords per subspace.  K is ignored for Flat / Binary. */
+nmn_status nmn_ivf_create_ex(const nmn_index_desc* desc, const float* centroids, uint32_t n_clusters, const nmn_ivf_storage* storage,
+                             const float* pq_codebook, uint32_t K, nmn_ivf** out);
+int32_t nmn_ivf_storage_kind(const nmn_ivf* ivf);
+/* codewords per subspace of a PQ index (K'), 0 otherwise */
+uint32_t nmn_ivf_pq_codewords(const nmn_ivf* ivf);
+/* The PQ codebook, [M][K'][dim / M] f32, into HOST memory (NMN_ERR_CONFIGURATION for another kind). */
+nmn_status nmn_ivf_pq_codebook(nmn_ivf* ivf, float* out, uint64_t cap_floats);
+/* The codes in ID order into HOST memory: PQ M bytes per vector, Binary ceil(dim / 64) little-endian u64 words per vector
+ * (bit i of word i / 64 = component i above the threshold).  cap_bytes >= len x that; NMN_ERR_CONFIGURATION for Flat. */
+nmn_status nmn_ivf_codes(nmn_ivf* ivf, void* out, uint64_t cap_bytes);
+/* Device memory the index holds right now (vectors or codes, centroids, codebook, lists, search scratch). */
+uint64_t nmn_ivf_hbm_bytes(nmn_ivf* ivf);
 
 /* ---- persistence of the device layout ----------------------------------- */
 
@@ -545,7 +585,8 @@ nmn_status nmn_index_save(nmn_index* idx, const char* path);
 nmn_status nmn_index_load(const char* path, const nmn_index_desc* overrides, uint64_t max_file_bytes,
                           uint64_t max_entries, nmn_index** out);
 /* The same for an IVF index: trained centroids, the list of every vector (`assign[]`) and the vectors in id order, so a
- * restart neither re-runs k-means (tensor_store/src/ivf.rs:222-233) nor re-assigns a single vector. */
+ * restart neither re-runs k-means (tensor_store/src/ivf.rs:222-233) nor re-assigns a single vector.  IVF-Flat only: a PQ or
+ * Binary index returns NMN_ERR_CONFIGURATION (the reference's IVFIndexState drops the codebook too, ivf.rs:515-552). */
 nmn_status nmn_ivf_save(nmn_ivf* ivf, const char* path);
 nmn_status nmn_ivf_load(const char* path, const nmn_index_desc* overrides, uint64_t max_file_bytes, uint64_t max_entries,
                         nmn_ivf** out);

@@ -78,6 +78,16 @@ class KMeansOptions(C.Structure):
                 ("init_method", C.c_int32)]
 
 
+class IvfStorage(C.Structure):
+    """nmn_ivf_storage (IVFStorage, tensor_store/src/ivf.rs:150-157; PQConfig, pq.rs:40-85; BinaryThreshold)."""
+    _fields_ = [("kind", C.c_int32), ("pq_num_subspaces", C.c_uint32), ("pq_num_centroids", C.c_uint32),
+                ("pq_kmeans", KMeansOptions), ("binary_threshold", C.c_int32)]
+
+
+IVF_FLAT, IVF_PQ, IVF_BINARY = range(3)
+BINARY_SIGN, BINARY_MEAN, BINARY_MEDIAN = range(3)
+
+
 class PredOp(C.Structure):
     """nmn_pred_op: one step of a WHERE-predicate program (include/neumann_gpu.h, NMN_PRED_*)."""
     _fields_ = [("op", C.c_uint32), ("cmp", C.c_uint32), ("vkind", C.c_uint32), ("column", C.c_uint32),
@@ -156,6 +166,16 @@ SIGNATURES = {
     "nmn_ivf_cluster_sizes": (C.c_int32, [vp, vp]),
     "nmn_ivf_search": (C.c_int32, [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.POINTER(SearchStats)]),
     "nmn_ivf_vectors": (vp, [vp]),
+    "nmn_ivf_storage_default": (None, [C.POINTER(IvfStorage)]),
+    "nmn_ivf_build_ex": (C.c_int32, [C.POINTER(IndexDesc), vp, C.c_uint64, C.c_uint32, C.POINTER(KMeansOptions),
+                                     C.POINTER(IvfStorage), C.POINTER(vp)]),
+    "nmn_ivf_create_ex": (C.c_int32, [C.POINTER(IndexDesc), vp, C.c_uint32, C.POINTER(IvfStorage), vp, C.c_uint32,
+                                      C.POINTER(vp)]),
+    "nmn_ivf_storage_kind": (C.c_int32, [vp]),
+    "nmn_ivf_pq_codewords": (C.c_uint32, [vp]),
+    "nmn_ivf_pq_codebook": (C.c_int32, [vp, vp, C.c_uint64]),
+    "nmn_ivf_codes": (C.c_int32, [vp, vp, C.c_uint64]),
+    "nmn_ivf_hbm_bytes": (C.c_uint64, [vp]),
     "nmn_index_save": (C.c_int32, [vp, C.c_char_p]),
     "nmn_index_load": (C.c_int32, [C.c_char_p, C.POINTER(IndexDesc), C.c_uint64, C.c_uint64, C.POINTER(vp)]),
     "nmn_ivf_save": (C.c_int32, [vp, C.c_char_p]),

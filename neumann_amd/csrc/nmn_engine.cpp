@@ -1599,6 +1599,13 @@ void nmn_ivf_options_default(nmn_ivf_options* o) {  // IVFConfig::default + KMea
 }
 
 nmn_status nmn_engine_build_ivf_index(nmn_engine* e, const nmn_ivf_options* options, nmn_engine_ivf** out) {
+    return nmn_engine_build_ivf_index_ex(e, options, nullptr, out);
+}
+
+// build_ivf_index for IVFBuildOptions::{flat, pq, binary} (lib.rs:941-1000, 2641-2694): the same validation in the same order,
+// then nmn_ivf_build_ex (storage NULL = Flat)
+nmn_status nmn_engine_build_ivf_index_ex(nmn_engine* e, const nmn_ivf_options* options, const nmn_ivf_storage* storage,
+                                         nmn_engine_ivf** out) {
     if (!e || !out) return fail(NMN_ERR_INVALID_ARGUMENT, "null argument");
     *out = nullptr;
     nmn_ivf_options o;
@@ -1638,7 +1645,8 @@ nmn_status nmn_engine_build_ivf_index(nmn_engine* e, const nmn_ivf_options* opti
     ko.convergence_threshold = o.convergence_threshold;
     ko.seed = o.seed;
     ko.init_method = o.init_method == NMN_KMEANS_INIT_RANDOM ? 0 : 1;
-    nmn_status st = nmn_ivf_build(&d, rows.data(), n, (uint32_t)std::min<uint64_t>(o.num_clusters, UINT32_MAX), &ko, &res->index);
+    nmn_status st = nmn_ivf_build_ex(&d, rows.data(), n, (uint32_t)std::min<uint64_t>(o.num_clusters, UINT32_MAX), &ko, storage, &res->index);
+    if (st == NMN_ERR_CONFIGURATION) return fail(st, std::string("Configuration error: ") + nmn_last_error());  // (dim % M != 0: the reference panics)
     if (st != NMN_OK) return err_gpu(st);
     res->n_clusters = nmn_ivf_clusters(res->index);
     res->centroids.resize((size_t)res->n_clusters * dim);
@@ -1666,6 +1674,31 @@ nmn_status nmn_engine_ivf_cluster_sizes(nmn_engine_ivf* ivf, uint64_t* out) {
     if (!ivf->index) return NMN_OK;
     nmn_status st = nmn_ivf_cluster_sizes(ivf->index, out);
     return st == NMN_OK ? NMN_OK : err_gpu(st);
+}
+
+// estimate_ivf_memory (lib.rs:2821-2851): centroids C x d x 4 + the storage (Flat n x d x 4, PQ n x M, Binary n x ceil(d / 64) x 8)
+// + n x 8 of ids; 0 for an empty engine.  Host arithmetic only.
+nmn_status nmn_engine_estimate_ivf_memory(nmn_engine* e, const nmn_ivf_options* options, const nmn_ivf_storage* storage,
+                                          uint64_t* out_bytes) {
+    if (!e || !out_bytes) return fail(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    *out_bytes = 0;
+    nmn_ivf_options o;
+    if (options) o = *options;
+    else nmn_ivf_options_default(&o);
+    ReadLock g(e);
+    const uint64_t count = e->dflt.live;
+    if (count == 0) return NMN_OK;
+    uint64_t dim = 0;  // `get_embedding(&keys[0])`: the first key's vector
+    for (const auto& ent : e->dflt.slots)
+        if (ent.live) {
+            dim = ent.vec.size();
+            break;
+        }
+    uint64_t vector_bytes = count * dim * 4;
+    if (storage && storage->kind == NMN_IVF_PQ) vector_bytes = count * storage->pq_num_subspaces;
+    else if (storage && storage->kind == NMN_IVF_BINARY) vector_bytes = count * ((dim + 63) / 64) * 8;
+    *out_bytes = o.num_clusters * dim * 4 + vector_bytes + count * 8;
+    return NMN_OK;
 }
 
 // search_with_ivf / search_with_ivf_nprobe (lib.rs:2731-2812); nprobe == 0 = the index's own
@@ -3026,6 +3059,8 @@ nmn_strlist* nmn_engine_load_all_indices(nmn_engine* e, const char* dir, nmn_sta
 // | the IVF section (centroids, lists, vectors) — a restart restores the trained index without k-means
 nmn_status nmn_engine_ivf_save(nmn_engine_ivf* ivf, const char* path) {
     if (!ivf || !path) return fail(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (ivf->index && nmn_ivf_storage_kind(ivf->index) != NMN_IVF_FLAT)
+        return fail(NMN_ERR_CONFIGURATION, "Configuration error: IVF-PQ / IVF-Binary indexes cannot be saved (only IVF-Flat persists its device layout)");
     std::string o = "{\"nprobe\": " + std::to_string(ivf->nprobe) + ", \"dim\": " + std::to_string(ivf->dim) + ", \"trained\": " +
                     (ivf->index ? "true" : "false") + ", \"keys\": [";
     for (size_t i = 0; i < ivf->keys.size(); i++) {

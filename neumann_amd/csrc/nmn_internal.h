@@ -434,6 +434,20 @@ hipError_t launch_kmeans_update(const float* corpus, uint32_t ld, uint32_t dim, 
                                 const uint64_t* offsets, uint32_t k, float* new_centroids, hipStream_t s);
 hipError_t launch_kmeans_min_update(float* dist, const uint32_t* neg_bits, uint64_t n, hipStream_t s);
 
+// IVF-PQ / IVF-Binary storages (nmn_ivf_codec.hip).  segs: codec_seg_bytes() per (query, probed list), {list, first list-major
+// row, rows, first candidate}; scores: the negated distance of candidate j of query q at score_base[q] + j (large-k order).
+hipError_t launch_pq_residual(const float* rows, uint32_t ld_r, const float* cents, uint32_t ld_c, const uint32_t* assign, uint64_t n,
+                              uint32_t dim, uint32_t subdim, float* out, hipStream_t s);
+hipError_t launch_pq_encode(const float* res, uint64_t n, uint32_t M, uint32_t subdim, const float* cb, uint32_t K, uint8_t* codes,
+                            hipStream_t s);
+size_t codec_seg_bytes();
+hipError_t launch_pq_search(const float* queries, uint32_t dim, const float* cents, uint32_t ld_c, const void* segs, uint32_t np,
+                            uint32_t nq, uint32_t max_count, const float* cb, uint32_t K, uint32_t M, const uint8_t* codes,
+                            float* tables, const uint64_t* score_base, uint32_t* scores, hipStream_t s);
+hipError_t launch_bq_quantize(const float* rows, uint32_t ld, uint64_t n, uint32_t dim, int method, uint64_t* words, hipStream_t s);
+hipError_t launch_bq_search(const uint64_t* qwords, uint32_t dim, const void* segs, uint32_t np, uint32_t nq, uint32_t max_count,
+                            const uint64_t* codes, const uint64_t* score_base, uint32_t* scores, hipStream_t s);
+
 // synthetic data
 hipError_t launch_synth_fill(float* corpus, uint32_t ld, uint32_t dim, uint64_t seed, uint64_t global_row0,
                              uint64_t local_row0, uint64_t n, hipStream_t s);

@@ -267,6 +267,24 @@ struct nmn_ivf {
     std::vector<uint64_t> list_sizes;    // rows per cluster (host), for the selectivity hint of a probe
     uint64_t list_sizes_rows = 0;        // rows accounted for in list_sizes
     static constexpr size_t kMaxSlots = 64;
+    // ---- IVF-PQ / IVF-Binary (kind != NMN_IVF_FLAT): `vectors` and `cvec` stay null, the lists hold codes -----------------
+    int32_t kind = NMN_IVF_FLAT;
+    uint32_t pq_m = 0, pq_k = 0, pq_sub = 0;  // subspaces, codewords per subspace (K'), subspace dimension
+    int32_t bq_method = 0;                    // NMN_BINARY_*
+    uint32_t code_bytes = 0;                  // per vector: M (PQ) or 8 * ceil(dim / 64) (Binary)
+    uint64_t n_coded = 0, row_base = 0;       // vectors added; ids are row_base + [0, n_coded)
+    std::vector<uint8_t> codes_host;          // id order (nmn_ivf_codes; the source of every re-layout)
+    std::vector<float> codebook_host;         // [M][K'][pq_sub]
+    float* codebook = nullptr;                // device copy
+    uint8_t* lcodes = nullptr;                // device, LIST-MAJOR codes [cap][code_bytes] (order of perm_host)
+    // one coded search at a time owns the scratch below (searches of a PQ / Binary index are serialised; `add` holds rw exclusively)
+    std::mutex codec_mu;
+    struct Grow {
+        void* p = nullptr;
+        size_t cap = 0;
+    };
+    Grow cs_qraw, cs_qpad, cs_qinfo, cs_qstate, cs_cscores, cs_ckeys, cs_probe_rows, cs_probe_scores, cs_probe_count, cs_segs,
+        cs_base, cs_tables, cs_qwords, cs_scores, cs_keys, cs_rows, cs_rscores, cs_rcnt;
 };
 
 #define IVF_TRY(expr)                                         \
@@ -298,6 +316,13 @@ extern "C" nmn_status nmn_ivf_destroy(nmn_ivf* ivf) {
         if (sl->res_pin) (void)hipHostFree(sl->res_pin);
     }
     if (ivf->stream) (void)hipStreamDestroy(ivf->stream);
+    for (nmn_ivf::Grow* g : {&ivf->cs_qraw, &ivf->cs_qpad, &ivf->cs_qinfo, &ivf->cs_qstate, &ivf->cs_cscores, &ivf->cs_ckeys,
+                             &ivf->cs_probe_rows, &ivf->cs_probe_scores, &ivf->cs_probe_count, &ivf->cs_segs, &ivf->cs_base,
+                             &ivf->cs_tables, &ivf->cs_qwords, &ivf->cs_scores, &ivf->cs_keys, &ivf->cs_rows, &ivf->cs_rscores,
+                             &ivf->cs_rcnt})
+        if (g->p) (void)hipFree(g->p);
+    if (ivf->codebook) (void)hipFree(ivf->codebook);
+    if (ivf->lcodes) (void)hipFree(ivf->lcodes);
     if (ivf->cvec) nmn_index_destroy(ivf->cvec);
     if (ivf->vectors) nmn_index_destroy(ivf->vectors);
     if (ivf->centroids) nmn_index_destroy(ivf->centroids);
@@ -305,8 +330,9 @@ extern "C" nmn_status nmn_ivf_destroy(nmn_ivf* ivf) {
     return NMN_OK;
 }
 
-// allocate the index; `centroids` may be null (nmn_ivf_build trains them afterwards)
-static nmn_status ivf_new(const nmn_index_desc* desc, const float* centroids, uint32_t n_clusters, nmn_ivf** out) {
+// allocate the index; `centroids` may be null (nmn_ivf_build trains them afterwards).  coded: a PQ / Binary index — no flat
+// index of vectors (its lists hold codes, laid out by codec_layout), per-row device arrays sized by the codes instead.
+static nmn_status ivf_new(const nmn_index_desc* desc, const float* centroids, uint32_t n_clusters, nmn_ivf** out, bool coded = false) {
     *out = nullptr;
     if (n_clusters == 0) return set_error(NMN_ERR_INVALID_ARGUMENT, "an IVF index needs at least one centroid");
     nmn_ivf* ivf = new (std::nothrow) nmn_ivf();
@@ -315,12 +341,15 @@ static nmn_status ivf_new(const nmn_index_desc* desc, const float* centroids, ui
         nmn_ivf_destroy(ivf);
         return st;
     };
-    nmn_status st = nmn_index_create(desc, &ivf->vectors);
-    if (st != NMN_OK) return bail(st);
+    nmn_status st = NMN_OK;
+    if (!coded) {
+        st = nmn_index_create(desc, &ivf->vectors);
+        if (st != NMN_OK) return bail(st);
+    }
     nmn_index_desc cd = *desc;
     cd.capacity_rows = n_clusters;
     cd.row_base = 0;
-    cd.device = ivf->vectors->device;
+    cd.device = coded ? desc->device : ivf->vectors->device;
     st = nmn_index_create(&cd, &ivf->centroids);
     if (st != NMN_OK) return bail(st);
     if (centroids) {
@@ -331,16 +360,17 @@ static nmn_status ivf_new(const nmn_index_desc* desc, const float* centroids, ui
     ivf->flags = desc->flags;
     ivf->cand_cap = desc->cand_cap;
     ivf->dim = desc->dim;
-    ivf->device = ivf->vectors->device;
-    ivf->cap = ivf->vectors->cap;
-    const uint32_t ld = ivf->vectors->ld;
+    ivf->device = ivf->centroids->device;
+    ivf->cap = coded ? desc->capacity_rows : ivf->vectors->cap;
+    ivf->row_base = desc->row_base;
+    const uint32_t ld = coded ? ivf->centroids->ld : ivf->vectors->ld;
     const size_t c_pad = ivf->centroids->cap_pad;
     hipError_t e = hipSetDevice(ivf->device);
     auto alloc = [&](void** p, size_t bytes) {
         if (e == hipSuccess) e = hipMalloc(p, std::max<size_t>(bytes, 64));
     };
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&ivf->stream, hipStreamNonBlocking);
-    alloc(reinterpret_cast<void**>(&ivf->assign), std::max<uint64_t>(ivf->cap, 1) * 4);
+    alloc(reinterpret_cast<void**>(&ivf->assign), coded ? 64 : std::max<uint64_t>(ivf->cap, 1) * 4);
     // rows assigned per sweep: bound the score matrix to 64 MiB whatever the number of clusters
     ivf->assign_chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(kAssignChunk, (16ull << 20) / c_pad));
     ivf->cscores_cap = c_pad * ivf->assign_chunk;
@@ -350,7 +380,7 @@ static nmn_status ivf_new(const nmn_index_desc* desc, const float* centroids, ui
     alloc(reinterpret_cast<void**>(&ivf->probe_scores), (size_t)n_clusters * 4);
     alloc(reinterpret_cast<void**>(&ivf->probe_count), 8);  // [0] clusters probed, [1] results of the list scan
     alloc(reinterpret_cast<void**>(&ivf->probe_rank), (size_t)n_clusters * 4);
-    alloc(reinterpret_cast<void**>(&ivf->mask), ((ivf->cap + 63) / 64 + 1) * 8);
+    alloc(reinterpret_cast<void**>(&ivf->mask), coded ? 64 : ((ivf->cap + 63) / 64 + 1) * 8);
     alloc(reinterpret_cast<void**>(&ivf->qraw), (size_t)desc->dim * 4);
     alloc(reinterpret_cast<void**>(&ivf->qpad), (size_t)ld * 4);
     alloc(reinterpret_cast<void**>(&ivf->qinfo), sizeof(QInfo) * kAssignChunk);
@@ -369,7 +399,7 @@ extern "C" nmn_status nmn_ivf_create(const nmn_index_desc* desc, const float* ce
     return ivf_new(desc, centroids, n_clusters, out);
 }
 
-extern "C" uint64_t nmn_ivf_len(const nmn_ivf* ivf) { return ivf ? ivf->vectors->rows : 0; }
+extern "C" uint64_t nmn_ivf_len(const nmn_ivf* ivf) { return ivf ? (ivf->vectors ? ivf->vectors->rows : ivf->n_coded) : 0; }
 extern "C" uint32_t nmn_ivf_clusters(const nmn_ivf* ivf) { return ivf ? ivf->n_clusters : 0; }
 extern "C" nmn_index* nmn_ivf_vectors(nmn_ivf* ivf) { return ivf ? ivf->vectors : nullptr; }
 
@@ -494,10 +524,13 @@ static nmn_status ivf_relayout(nmn_ivf* ivf) {
 
 extern "C" uint64_t nmn_ivf_list_major_rows(const nmn_ivf* ivf) { return ivf ? ivf->c_rows : 0; }
 
+static nmn_status codec_add(nmn_ivf* ivf, const float* rows_host, uint64_t n, uint32_t* clusters_out);
+
 extern "C" nmn_status nmn_ivf_add(nmn_ivf* ivf, const float* rows_host, uint64_t n, uint32_t* clusters_out) {
     if (!ivf || (n && !rows_host)) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
     if (n == 0) return NMN_OK;
     std::unique_lock<std::shared_mutex> g(ivf->rw);
+    if (ivf->kind != NMN_IVF_FLAT) return codec_add(ivf, rows_host, n, clusters_out);
     const uint64_t row0 = ivf->vectors->rows;
     nmn_status st = nmn_index_upload(ivf->vectors, rows_host, row0, n);  // ids = insertion order (ivf.rs:287-289)
     if (st != NMN_OK) return st;
@@ -531,8 +564,10 @@ float host_dist_sq(const float* a, const float* b, uint64_t dim) {
 
 }  // namespace
 
-extern "C" nmn_status nmn_ivf_build(const nmn_index_desc* desc, const float* rows_host, uint64_t n, uint32_t num_clusters,
-                                    const nmn_kmeans_options* opt, nmn_ivf** out) {
+// IVFIndex::train + add for IVFStorage::Flat; layout = false leaves out the list-major copy (a PQ / Binary build and the
+// codebook's per-subspace k-means only need the centroids and the assignments of this index, then destroy it)
+static nmn_status ivf_train_flat(const nmn_index_desc* desc, const float* rows_host, uint64_t n, uint32_t num_clusters,
+                                 const nmn_kmeans_options* opt, bool layout, nmn_ivf** out) {
     if (!desc || !rows_host || !opt || !out) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
     *out = nullptr;
     if (n == 0 || num_clusters == 0) return set_error(NMN_ERR_INVALID_ARGUMENT, "nothing to train on");
@@ -677,10 +712,15 @@ extern "C" nmn_status nmn_ivf_build(const nmn_index_desc* desc, const float* row
     st = assign_rows(ivf, 0, n);
     if (st != NMN_OK) return bail(st);
     ivf->centroids_host = cents;
-    st = ivf_relayout(ivf);
+    st = layout ? ivf_relayout(ivf) : NMN_OK;
     if (st != NMN_OK) return bail(st);
     *out = ivf;
     return NMN_OK;
+}
+
+extern "C" nmn_status nmn_ivf_build(const nmn_index_desc* desc, const float* rows_host, uint64_t n, uint32_t num_clusters,
+                                    const nmn_kmeans_options* opt, nmn_ivf** out) {
+    return ivf_train_flat(desc, rows_host, n, num_clusters, opt, true, out);
 }
 
 extern "C" nmn_status nmn_ivf_centroids(nmn_ivf* ivf, float* out, uint64_t cap_floats) {
@@ -798,6 +838,9 @@ static void probe_slot_release(nmn_ivf* ivf, nmn_ivf::ProbeSlot* sl) {
     ivf->slot_cv.notify_one();
 }
 
+static nmn_status codec_search(nmn_ivf* ivf, const float* queries, uint32_t nq, uint32_t k, uint32_t nprobe, uint64_t* out_ids,
+                               float* out_distances, uint32_t* out_counts);
+
 extern "C" nmn_status nmn_ivf_search(nmn_ivf* ivf, const float* queries, uint32_t nq, uint32_t k, uint32_t nprobe,
                                      uint64_t* out_ids, float* out_distances, uint32_t* out_counts,
                                      nmn_search_stats* stats) {
@@ -806,6 +849,10 @@ extern "C" nmn_status nmn_ivf_search(nmn_ivf* ivf, const float* queries, uint32_
     if (k == 0) return set_error(NMN_ERR_INVALID_TOP_K, "k == 0");
     if (nq == 0) return NMN_OK;
     std::shared_lock<std::shared_mutex> g(ivf->rw);  // concurrent with other searches, not with add / build
+    if (ivf->kind != NMN_IVF_FLAT) {
+        if (stats) memset(stats, 0, sizeof *stats);
+        return codec_search(ivf, queries, nq, k, nprobe, out_ids, out_distances, out_counts);
+    }
     IVF_TRY(hipSetDevice(ivf->device));
     const uint64_t n_rows = ivf->vectors->rows;
     const uint32_t np = std::min<uint32_t>(nprobe, ivf->n_clusters);  // ivf.rs:339
@@ -1145,6 +1192,520 @@ extern "C" nmn_status nmn_ivf_search(nmn_ivf* ivf, const float* queries, uint32_
     return NMN_OK;
 }
 
+// ---- IVF-PQ / IVF-Binary storage (ivf.rs:61-157, 222-406; pq.rs:114-430; binary_quantization.rs:27-155) --------------------
+// Centroids and list assignment are IVF-Flat's (the same exact k-means, the same nearest-centroid sweep); what a list holds
+// is codes: M bytes per vector (PQ, residual v - centroid[list] encoded against the codebook) or ceil(dim / 64) u64 words
+// (Binary, v itself against its own threshold).  The device keeps the codes LIST-MAJOR (rows of list 0, then list 1, ..., ids
+// ascending inside a list, `perm_host` maps back) plus the centroids and the codebook — no f32 vector after the build.
+// The host keeps the codes in id order too (inspection, re-layout after `add`: a stable counting sort and one upload).
+// A search: the centroid ranking exactly as Flat's (exact -d^2 sweep + ivf_rank_kernel, up to 64 queries per launch), the probe
+// orders to the host (one wait), then per group of queries one scan launch over every probed list of every query
+// (nmn_ivf_codec.hip) writing the negated distance of each candidate in candidate order, one large-k sort per query (score
+// desc, candidate index asc = the reference's stable sort by distance, ivf.rs:402-404), and one copy back.
+namespace {
+
+size_t index_hbm_bytes(const nmn_index* x) {
+    if (!x) return 0;
+    size_t b = (size_t)x->cap_pad * x->ld * 4 + (size_t)x->cap_pad * 8;  // f32 rows, magnitudes and their inverses
+    if (x->half) b += (size_t)x->cap_pad * x->ld * 2;
+    if (x->q8) b += (size_t)x->cap_pad * x->ld + (size_t)x->cap_pad * 16;
+    return b;
+}
+
+// grow-only device scratch of the coded search
+hipError_t grow(nmn_ivf::Grow& g, size_t bytes) {
+    bytes = std::max<size_t>(bytes, 64);
+    if (g.cap >= bytes) return hipSuccess;
+    if (g.p) (void)hipFree(g.p);
+    g.p = nullptr;
+    g.cap = 0;
+    hipError_t e = hipMalloc(&g.p, bytes);
+    if (e == hipSuccess) g.cap = bytes;
+    return e;
+}
+template <class T>
+T* gp(nmn_ivf::Grow& g) {
+    return static_cast<T*>(g.p);
+}
+
+nmn_status check_storage(const nmn_ivf_storage* s, uint32_t dim) {
+    if (s->kind == NMN_IVF_PQ) {
+        if (s->pq_num_subspaces == 0 || dim % s->pq_num_subspaces != 0)
+            return set_error(NMN_ERR_CONFIGURATION, "IVF-PQ: vector dimension must be divisible by num_subspaces");
+        if ((size_t)dim * 4 > 64 * 1024)
+            return set_error(NMN_ERR_CONFIGURATION, "IVF-PQ: dimensions above 16384 are not supported on the device");
+        return NMN_OK;
+    }
+    if (s->kind == NMN_IVF_BINARY) {
+        if (s->binary_threshold < NMN_BINARY_SIGN || s->binary_threshold > NMN_BINARY_MEDIAN)
+            return set_error(NMN_ERR_CONFIGURATION, "IVF-Binary: unknown threshold method");
+        return NMN_OK;
+    }
+    return set_error(NMN_ERR_CONFIGURATION, "unknown IVF storage kind");
+}
+
+// the coded index shell: centroids uploaded, storage parameters set, code buffers allocated for desc->capacity_rows
+nmn_status codec_new(const nmn_index_desc* desc, const float* centroids, uint32_t C, const nmn_ivf_storage* s, const float* codebook,
+                     uint32_t K, nmn_ivf** out) {
+    nmn_ivf* ivf = nullptr;
+    nmn_status st = ivf_new(desc, centroids, C, &ivf, true);
+    if (st != NMN_OK) return st;
+    ivf->kind = s->kind;
+    ivf->centroids_host.assign(centroids, centroids + (size_t)C * desc->dim);
+    if (s->kind == NMN_IVF_PQ) {
+        ivf->pq_m = s->pq_num_subspaces;
+        ivf->pq_sub = desc->dim / ivf->pq_m;
+        ivf->pq_k = K;
+        ivf->code_bytes = ivf->pq_m;
+        const size_t cbn = (size_t)ivf->pq_m * K * ivf->pq_sub;
+        if (cbn) ivf->codebook_host.assign(codebook, codebook + cbn);
+    } else {
+        ivf->bq_method = s->binary_threshold;
+        ivf->code_bytes = 8 * ((desc->dim + 63) / 64);
+    }
+    hipError_t e = hipSetDevice(ivf->device);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&ivf->codebook), std::max<size_t>(ivf->codebook_host.size() * 4, 64));
+    if (e == hipSuccess && !ivf->codebook_host.empty())
+        e = hipMemcpy(ivf->codebook, ivf->codebook_host.data(), ivf->codebook_host.size() * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = hipMalloc(reinterpret_cast<void**>(&ivf->lcodes), std::max<size_t>((size_t)std::max<uint64_t>(ivf->cap, 1) * ivf->code_bytes, 64));
+    if (e != hipSuccess) {
+        nmn_ivf_destroy(ivf);
+        return set_error_hip(e, "IVF code buffers");
+    }
+    ivf->list_sizes.assign(C, 0);
+    *out = ivf;
+    return NMN_OK;
+}
+
+// list-major codes from the id-ordered ones: stable counting sort of the assignments, one upload.  Caller holds rw exclusively.
+nmn_status codec_layout(nmn_ivf* ivf) {
+    const uint64_t n = ivf->n_coded;
+    const uint32_t C = ivf->n_clusters, cb = ivf->code_bytes;
+    ivf->list_off_host.assign((size_t)C + 1, 0u);
+    for (uint64_t r = 0; r < n; r++) ivf->list_off_host[ivf->assign_host[r] + 1]++;
+    for (uint32_t c = 0; c < C; c++) ivf->list_off_host[c + 1] += ivf->list_off_host[c];
+    ivf->perm_host.resize(n);
+    std::vector<uint8_t> lm((size_t)n * cb);
+    {
+        std::vector<uint32_t> cur(ivf->list_off_host.begin(), ivf->list_off_host.end() - 1);
+        for (uint64_t r = 0; r < n; r++) {
+            const uint32_t pos = cur[ivf->assign_host[r]]++;
+            ivf->perm_host[pos] = (uint32_t)r;
+            memcpy(lm.data() + (size_t)pos * cb, ivf->codes_host.data() + (size_t)r * cb, cb);
+        }
+    }
+    IVF_TRY(hipSetDevice(ivf->device));
+    if (n) IVF_TRY(hipMemcpy(ivf->lcodes, lm.data(), lm.size(), hipMemcpyHostToDevice));
+    ivf->c_rows = n;
+    ivf->list_sizes.assign(C, 0);
+    for (uint32_t c = 0; c < C; c++) ivf->list_sizes[c] = ivf->list_off_host[c + 1] - ivf->list_off_host[c];
+    ivf->list_sizes_rows = n;
+    return NMN_OK;
+}
+
+// codes of n rows already on the device (stride ld) whose lists are assign_dev: PQ residual + encode, or Binary quantize -> host
+nmn_status codec_encode(nmn_ivf* ivf, const float* rows_dev, uint32_t ld, const uint32_t* assign_dev, uint64_t n, uint8_t* out_host) {
+    if (n == 0) return NMN_OK;
+    hipStream_t s = ivf->stream;
+    void* codes_dev = nullptr;
+    float* res = nullptr;
+    hipError_t e = hipMalloc(&codes_dev, std::max<size_t>((size_t)n * ivf->code_bytes, 64));
+    if (ivf->kind == NMN_IVF_PQ) {
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&res), std::max<size_t>((size_t)n * ivf->dim * 4, 64));
+        if (e == hipSuccess)
+            e = launch_pq_residual(rows_dev, ld, ivf->centroids->corpus, ivf->centroids->ld, assign_dev, n, ivf->dim, ivf->pq_sub, res, s);
+        if (e == hipSuccess)
+            e = launch_pq_encode(res, n, ivf->pq_m, ivf->pq_sub, ivf->codebook, ivf->pq_k, static_cast<uint8_t*>(codes_dev), s);
+    } else if (e == hipSuccess) {
+        e = launch_bq_quantize(rows_dev, ld, n, ivf->dim, ivf->bq_method, static_cast<uint64_t*>(codes_dev), s);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out_host, codes_dev, (size_t)n * ivf->code_bytes, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (codes_dev) (void)hipFree(codes_dev);
+    if (res) (void)hipFree(res);
+    return e == hipSuccess ? NMN_OK : set_error_hip(e, "IVF encode");
+}
+
+}  // namespace
+
+extern "C" void nmn_ivf_storage_default(nmn_ivf_storage* s) {  // IVFStorage::Flat, PQConfig::default (pq.rs:60-68), Sign
+    if (!s) return;
+    memset(s, 0, sizeof *s);
+    s->kind = NMN_IVF_FLAT;
+    s->pq_num_subspaces = 8;
+    s->pq_num_centroids = 256;
+    s->pq_kmeans.max_iterations = 100;  // KMeansConfig::default
+    s->pq_kmeans.convergence_threshold = 1e-4f;
+    s->pq_kmeans.seed = 42;
+    s->pq_kmeans.init_method = 1;
+    s->binary_threshold = NMN_BINARY_SIGN;
+}
+
+extern "C" nmn_status nmn_ivf_build_ex(const nmn_index_desc* desc, const float* rows_host, uint64_t n, uint32_t num_clusters,
+                                       const nmn_kmeans_options* kmeans, const nmn_ivf_storage* storage, nmn_ivf** out) {
+    if (!desc || !rows_host || !kmeans || !out) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    *out = nullptr;
+    if (!storage || storage->kind == NMN_IVF_FLAT) return ivf_train_flat(desc, rows_host, n, num_clusters, kmeans, true, out);
+    nmn_status st = check_storage(storage, desc->dim);  // (the reference asserts in PQCodebook::train; no index is built here)
+    if (st != NMN_OK) return st;
+    if (n == 0 || num_clusters == 0) return set_error(NMN_ERR_INVALID_ARGUMENT, "nothing to train on");
+    if (desc->capacity_rows < n) return set_error(NMN_ERR_CAPACITY, "capacity_rows < n");
+    // IVFIndex::train's k-means and `find_nearest_centroid` of every vector: the Flat trainer over a transient copy of the rows
+    nmn_index_desc td = *desc;
+    td.capacity_rows = n;
+    td.row_base = 0;
+    nmn_ivf* t = nullptr;
+    st = ivf_train_flat(&td, rows_host, n, num_clusters, kmeans, false, &t);
+    if (st != NMN_OK) return st;
+    struct Drop {
+        nmn_ivf* p;
+        ~Drop() {
+            if (p) nmn_ivf_destroy(p);
+        }
+    } drop_t{t};
+    const uint32_t C = t->n_clusters, dim = desc->dim;
+    std::vector<float> codebook;
+    uint32_t Kp = 0;
+    if (storage->kind == NMN_IVF_PQ) {
+        // PQCodebook::train (pq.rs:114-169) over the residuals: K' = min(num_centroids, n); subspace m = one KMeans::fit with
+        // pq_config.kmeans_config over the m-th sub-vectors — the exact GPU k-means again, on an n x subdim index
+        const uint32_t M = storage->pq_num_subspaces, sub = dim / M;
+        Kp = (uint32_t)std::min<uint64_t>(storage->pq_num_centroids, n);
+        codebook.assign((size_t)M * Kp * sub, 0.0f);  // (zero padding should a fit return fewer codewords, pq.rs:150-157)
+        if (Kp) {
+            float* res = nullptr;
+            hipError_t e = hipSetDevice(t->device);
+            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&res), (size_t)n * dim * 4);
+            if (e == hipSuccess)
+                e = launch_pq_residual(t->vectors->corpus, t->vectors->ld, t->centroids->corpus, t->centroids->ld, t->assign, n, dim, sub, res,
+                                       t->stream);
+            std::vector<float> subv((size_t)n * sub);
+            for (uint32_t m = 0; m < M && e == hipSuccess && st == NMN_OK; m++) {
+                e = hipMemcpyAsync(subv.data(), res + (size_t)m * n * sub, subv.size() * 4, hipMemcpyDeviceToHost, t->stream);
+                if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
+                if (e != hipSuccess) break;
+                nmn_index_desc sd{};
+                sd.dim = sub;
+                sd.capacity_rows = n;
+                sd.device = t->device;
+                nmn_ivf* km = nullptr;
+                st = ivf_train_flat(&sd, subv.data(), n, Kp, &storage->pq_kmeans, false, &km);
+                if (st != NMN_OK) break;
+                const size_t got = std::min(km->centroids_host.size(), (size_t)Kp * sub);
+                std::copy(km->centroids_host.begin(), km->centroids_host.begin() + got, codebook.begin() + (size_t)m * Kp * sub);
+                nmn_ivf_destroy(km);
+            }
+            if (res) (void)hipFree(res);
+            if (e != hipSuccess) return set_error_hip(e, "IVF-PQ codebook training");
+            if (st != NMN_OK) return st;
+        }
+    }
+    nmn_ivf* ivf = nullptr;
+    st = codec_new(desc, t->centroids_host.data(), C, storage, codebook.data(), Kp, &ivf);
+    if (st != NMN_OK) return st;
+    // `for vector in &vectors { index.add(vector) }`: the lists are the trainer's assignments, the codes come from its rows
+    ivf->codes_host.resize((size_t)n * ivf->code_bytes);
+    ivf->assign_host.assign(t->assign_host.begin(), t->assign_host.begin() + n);
+    ivf->n_coded = n;
+    st = codec_encode(ivf, t->vectors->corpus, t->vectors->ld, t->assign, n, ivf->codes_host.data());
+    if (st == NMN_OK) st = codec_layout(ivf);
+    if (st != NMN_OK) {
+        nmn_ivf_destroy(ivf);
+        return st;
+    }
+    *out = ivf;  // (the f32 rows go with `t` on return)
+    return NMN_OK;
+}
+
+extern "C" nmn_status nmn_ivf_create_ex(const nmn_index_desc* desc, const float* centroids, uint32_t n_clusters,
+                                        const nmn_ivf_storage* storage, const float* pq_codebook, uint32_t K, nmn_ivf** out) {
+    if (!desc || !centroids || !out) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    *out = nullptr;
+    if (!storage || storage->kind == NMN_IVF_FLAT) return ivf_new(desc, centroids, n_clusters, out);
+    nmn_status st = check_storage(storage, desc->dim);
+    if (st != NMN_OK) return st;
+    if (storage->kind == NMN_IVF_PQ && K && !pq_codebook) return set_error(NMN_ERR_INVALID_ARGUMENT, "null codebook");
+    return codec_new(desc, centroids, n_clusters, storage, pq_codebook, storage->kind == NMN_IVF_PQ ? K : 0, out);
+}
+
+// IVFIndex::add (ivf.rs:276-316) for a PQ / Binary index: the rows pass through a transient flat index (padded like queries,
+// so the exact centroid sweep scores them in place), get their lists and codes, and leave the device again
+static nmn_status codec_add(nmn_ivf* ivf, const float* rows_host, uint64_t n, uint32_t* clusters_out) {
+    if (ivf->n_coded + n > ivf->cap) return set_error(NMN_ERR_CAPACITY, "capacity_rows exceeded");
+    IVF_TRY(hipSetDevice(ivf->device));
+    const uint64_t row0 = ivf->n_coded;
+    const uint64_t kStage = std::min<uint64_t>(n, 65536);
+    nmn_index_desc sd{};
+    sd.dim = ivf->dim;
+    sd.flags = ivf->flags;
+    sd.capacity_rows = kStage;
+    sd.device = ivf->device;
+    nmn_index* stg = nullptr;
+    nmn_status st = nmn_index_create(&sd, &stg);
+    if (st != NMN_OK) return st;
+    uint32_t* assign_dev = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&assign_dev), kStage * 4);
+    if (e != hipSuccess) {
+        nmn_index_destroy(stg);
+        return set_error_hip(e, "IVF add");
+    }
+    if (stg->ld != ivf->centroids->ld) st = set_error(NMN_ERR_STORAGE, "IVF add: staging layout differs from the centroids'");
+    ivf->assign_host.resize(row0 + n);
+    ivf->codes_host.resize((size_t)(row0 + n) * ivf->code_bytes);
+    const uint32_t ld = stg->ld;
+    for (uint64_t off = 0; off < n && st == NMN_OK; off += kStage) {
+        const uint64_t cnt = std::min(kStage, n - off);
+        st = nmn_index_upload(stg, rows_host + off * ivf->dim, 0, cnt);
+        if (st != NMN_OK) break;
+        e = hipStreamSynchronize(stg->host_stream);
+        // find_nearest_centroid (ivf.rs:490-497): the same sweep + first minimum as Flat's add
+        for (uint64_t a = 0; a < cnt && e == hipSuccess && st == NMN_OK; a += ivf->assign_chunk) {
+            const uint32_t c = (uint32_t)std::min<uint64_t>(ivf->assign_chunk, cnt - a);
+            st = centroid_scores(ivf, stg->corpus + a * ld, c);
+            if (st != NMN_OK) break;
+            hipLaunchKernelGGL(ivf_assign_kernel, dim3((c * 64 + 255) / 256), dim3(256), 0, ivf->stream, ivf->cscores, ivf->n_clusters, c, c,
+                               assign_dev + a);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess && st == NMN_OK)
+            e = hipMemcpyAsync(ivf->assign_host.data() + row0 + off, assign_dev, cnt * 4, hipMemcpyDeviceToHost, ivf->stream);
+        if (e == hipSuccess && st == NMN_OK)
+            st = codec_encode(ivf, stg->corpus, ld, assign_dev, cnt, ivf->codes_host.data() + (size_t)(row0 + off) * ivf->code_bytes);
+        if (e != hipSuccess && st == NMN_OK) st = set_error_hip(e, "IVF add");
+    }
+    (void)hipFree(assign_dev);
+    nmn_index_destroy(stg);
+    if (st != NMN_OK) {
+        ivf->assign_host.resize(row0);
+        ivf->codes_host.resize((size_t)row0 * ivf->code_bytes);
+        return st;
+    }
+    if (clusters_out) memcpy(clusters_out, ivf->assign_host.data() + row0, n * 4);
+    ivf->n_coded = row0 + n;
+    return codec_layout(ivf);
+}
+
+static nmn_status codec_search(nmn_ivf* ivf, const float* queries, uint32_t nq, uint32_t k, uint32_t nprobe, uint64_t* out_ids,
+                               float* out_distances, uint32_t* out_counts) {
+    for (uint32_t q = 0; q < nq; q++) {  // unused slots as Flat's: id UINT64_MAX, distance +inf
+        std::fill(out_ids + (size_t)q * k, out_ids + (size_t)(q + 1) * k, UINT64_MAX);
+        std::fill(out_distances + (size_t)q * k, out_distances + (size_t)(q + 1) * k, __builtin_inff());
+        out_counts[q] = 0;
+    }
+    const uint32_t C = ivf->n_clusters, dim = ivf->dim;
+    const uint32_t np = std::min<uint32_t>(nprobe, C);  // ivf.rs:339
+    if (ivf->n_coded == 0 || np == 0) return NMN_OK;
+    std::lock_guard<std::mutex> lk(ivf->codec_mu);
+    IVF_TRY(hipSetDevice(ivf->device));
+    hipStream_t s = ivf->stream;
+    const uint32_t ld = ivf->centroids->ld;
+    const size_t c_pad = ivf->centroids->cap_pad;
+    const uint32_t chunk = C <= kRankMax ? std::min<uint32_t>(nq, 64) : 1u;
+    IVF_TRY(grow(ivf->cs_qraw, (size_t)dim * chunk * 4));
+    IVF_TRY(grow(ivf->cs_qpad, (size_t)ld * chunk * 4));
+    IVF_TRY(grow(ivf->cs_qinfo, sizeof(QInfo) * chunk));
+    IVF_TRY(grow(ivf->cs_qstate, sizeof(QState) * chunk));
+    IVF_TRY(grow(ivf->cs_cscores, c_pad * chunk * 4));
+    IVF_TRY(grow(ivf->cs_probe_rows, (size_t)C * chunk * 8));
+    IVF_TRY(grow(ivf->cs_probe_scores, (size_t)C * 4));
+    IVF_TRY(grow(ivf->cs_probe_count, (size_t)chunk * 8));
+    if (C > kRankMax) IVF_TRY(grow(ivf->cs_ckeys, largek_sort_len(C) * 8));
+    std::vector<uint64_t> probe_host((size_t)C * chunk);
+    std::vector<uint32_t> pcount(chunk);
+    const size_t seg_bytes = codec_seg_bytes();
+    struct Seg {
+        uint32_t list, start, count, cand;
+    };
+    static_assert(sizeof(Seg) == 16, "CodecSeg layout");
+    if (seg_bytes != sizeof(Seg)) return set_error(NMN_ERR_STORAGE, "IVF codec: segment layout mismatch");
+    constexpr uint64_t kScoreBudget = 64ull << 20;  // candidates' scores per scan launch (256 MiB)
+    const uint32_t Kt = std::min<uint32_t>(ivf->pq_k, 256);
+    for (uint32_t q0 = 0; q0 < nq; q0 += chunk) {
+        const uint32_t nb = std::min<uint32_t>(chunk, nq - q0);
+        // 1. the centroid ranking of the chunk, exactly as Flat ranks (squared distance ascending, ties by index)
+        IVF_TRY(hipMemcpyAsync(ivf->cs_qraw.p, queries + (size_t)q0 * dim, (size_t)nb * dim * 4, hipMemcpyHostToDevice, s));
+        const bool raw_q = ld == dim && C < (1u << 16);
+        if (!raw_q)
+            IVF_TRY(launch_qprep(gp<float>(ivf->cs_qraw), nb, dim, ld, kMetricNegL2Sq, ivf->centroids->max_norm_bits, gp<float>(ivf->cs_qpad),
+                                 gp<QInfo>(ivf->cs_qinfo), gp<QState>(ivf->cs_qstate), 0, s));
+        else
+            IVF_TRY(hipMemsetAsync(ivf->cs_qinfo.p, 0, sizeof(QInfo) * nb, s));
+        ExactScanParams ep{};
+        ep.corpus = ivf->centroids->corpus;
+        ep.norms = ivf->centroids->norms;
+        ep.qpad = raw_q ? gp<float>(ivf->cs_qraw) : gp<float>(ivf->cs_qpad);
+        ep.qinfo = gp<QInfo>(ivf->cs_qinfo);
+        ep.scores = gp<uint32_t>(ivf->cs_cscores);
+        ep.n_rows = C;
+        ep.nql = nb;
+        ep.ld = ld;
+        ep.dim = dim;
+        ep.nq = nb;
+        ep.metric = kMetricNegL2Sq;
+        IVF_TRY(launch_exact_scan(ep, s));
+        uint32_t* rank_scratch = gp<uint32_t>(ivf->cs_probe_scores);  // (probe_rank of the rank kernel: written, not read here)
+        if (C <= kRankMax) {
+            uint32_t np2 = 2;
+            while (np2 < C) np2 <<= 1;
+            IVF_TRY(grow(ivf->cs_probe_scores, (size_t)C * nb * 4));
+            rank_scratch = gp<uint32_t>(ivf->cs_probe_scores);
+            hipLaunchKernelGGL(ivf_rank_kernel, dim3(nb), dim3(1024), 0, s, gp<uint32_t>(ivf->cs_cscores), nb, C, np2, np,
+                               gp<uint64_t>(ivf->cs_probe_rows), gp<uint32_t>(ivf->cs_probe_count), rank_scratch);
+        } else {
+            IVF_TRY(launch_largek(gp<uint32_t>(ivf->cs_cscores), C, gp<uint64_t>(ivf->cs_ckeys), np, 0, gp<uint64_t>(ivf->cs_probe_rows),
+                                  gp<float>(ivf->cs_probe_scores), gp<uint32_t>(ivf->cs_probe_count), s));
+        }
+        IVF_TRY(hipGetLastError());
+        if (C <= kRankMax) {
+            IVF_TRY(hipMemcpyAsync(probe_host.data(), ivf->cs_probe_rows.p, (size_t)nb * C * 8, hipMemcpyDeviceToHost, s));
+        } else {
+            IVF_TRY(hipMemcpyAsync(probe_host.data(), ivf->cs_probe_rows.p, (size_t)np * 8, hipMemcpyDeviceToHost, s));
+        }
+        IVF_TRY(hipMemcpyAsync(pcount.data(), ivf->cs_probe_count.p, (size_t)nb * 4, hipMemcpyDeviceToHost, s));
+        IVF_TRY(hipStreamSynchronize(s));
+        // 2. candidates = the probed lists in probe order, each in list order (= id order)
+        const size_t pstride = C <= kRankMax ? C : 0;
+        std::vector<Seg> segs((size_t)nb * np);
+        std::vector<uint64_t> total(nb, 0);
+        uint32_t max_count = 0;
+        for (uint32_t b = 0; b < nb; b++) {
+            const uint32_t cnt = std::min(pcount[b], np);
+            uint64_t cand = 0;
+            for (uint32_t i = 0; i < np; i++) {
+                Seg& sg = segs[(size_t)b * np + i];
+                sg = Seg{0, 0, 0, (uint32_t)cand};
+                const uint64_t c = probe_host[(size_t)b * pstride + i];
+                if (i >= cnt || c >= C) continue;
+                sg.list = (uint32_t)c;
+                sg.start = ivf->list_off_host[c];
+                sg.count = ivf->list_off_host[c + 1] - ivf->list_off_host[c];
+                cand += sg.count;
+                max_count = std::max(max_count, sg.count);
+            }
+            total[b] = cand;
+        }
+        // 3. scans + one large-k sort per query, in groups whose scores fit the budget
+        for (uint32_t g0 = 0; g0 < nb;) {
+            uint32_t g1 = g0 + 1;
+            uint64_t sum = total[g0];
+            while (g1 < nb && sum + total[g1] <= kScoreBudget) sum += total[g1++];
+            const uint32_t ng = g1 - g0;
+            std::vector<uint64_t> base(ng), rbase(ng);
+            uint64_t max_total = 0, rsum = 0;
+            for (uint32_t b = 0; b < ng; b++) {
+                base[b] = b ? base[b - 1] + total[g0 + b - 1] : 0;
+                rbase[b] = rsum;
+                rsum += std::min<uint64_t>(k, total[g0 + b]);
+                max_total = std::max(max_total, total[g0 + b]);
+            }
+            IVF_TRY(grow(ivf->cs_segs, (size_t)ng * np * sizeof(Seg)));
+            IVF_TRY(grow(ivf->cs_base, (size_t)ng * 8));
+            IVF_TRY(grow(ivf->cs_scores, (size_t)sum * 4));
+            IVF_TRY(grow(ivf->cs_keys, largek_sort_len(std::max<uint64_t>(max_total, 1)) * 8));
+            IVF_TRY(grow(ivf->cs_rows, (size_t)rsum * 8));
+            IVF_TRY(grow(ivf->cs_rscores, (size_t)rsum * 4));
+            IVF_TRY(grow(ivf->cs_rcnt, (size_t)ng * 4));
+            IVF_TRY(hipMemcpyAsync(ivf->cs_segs.p, segs.data() + (size_t)g0 * np, (size_t)ng * np * sizeof(Seg), hipMemcpyHostToDevice, s));
+            IVF_TRY(hipMemcpyAsync(ivf->cs_base.p, base.data(), (size_t)ng * 8, hipMemcpyHostToDevice, s));
+            const float* qg = gp<float>(ivf->cs_qraw) + (size_t)g0 * dim;
+            if (ivf->kind == NMN_IVF_PQ) {
+                IVF_TRY(grow(ivf->cs_tables, (size_t)ng * np * ivf->pq_m * Kt * 4));
+                IVF_TRY(launch_pq_search(qg, dim, ivf->centroids->corpus, ld, ivf->cs_segs.p, np, ng, max_count, ivf->codebook, ivf->pq_k,
+                                         ivf->pq_m, ivf->lcodes, gp<float>(ivf->cs_tables), gp<uint64_t>(ivf->cs_base),
+                                         gp<uint32_t>(ivf->cs_scores), s));
+            } else {
+                const uint32_t W = (dim + 63) / 64;
+                IVF_TRY(grow(ivf->cs_qwords, (size_t)ng * W * 8));
+                IVF_TRY(launch_bq_quantize(qg, dim, ng, dim, ivf->bq_method, gp<uint64_t>(ivf->cs_qwords), s));
+                IVF_TRY(launch_bq_search(gp<uint64_t>(ivf->cs_qwords), dim, ivf->cs_segs.p, np, ng, max_count,
+                                         reinterpret_cast<const uint64_t*>(ivf->lcodes), gp<uint64_t>(ivf->cs_base),
+                                         gp<uint32_t>(ivf->cs_scores), s));
+            }
+            IVF_TRY(hipMemsetAsync(ivf->cs_rcnt.p, 0, (size_t)ng * 4, s));
+            for (uint32_t b = 0; b < ng; b++) {
+                const uint64_t tot = total[g0 + b];
+                if (tot == 0) continue;
+                const uint32_t kq = (uint32_t)std::min<uint64_t>(k, tot);
+                IVF_TRY(launch_largek(gp<uint32_t>(ivf->cs_scores) + base[b], tot, gp<uint64_t>(ivf->cs_keys), kq, 0,
+                                      gp<uint64_t>(ivf->cs_rows) + rbase[b], gp<float>(ivf->cs_rscores) + rbase[b],
+                                      gp<uint32_t>(ivf->cs_rcnt) + b, s));
+            }
+            std::vector<uint64_t> rrows(rsum);
+            std::vector<float> rsc(rsum);
+            std::vector<uint32_t> rcnt(ng);
+            if (rsum) {
+                IVF_TRY(hipMemcpyAsync(rrows.data(), ivf->cs_rows.p, rsum * 8, hipMemcpyDeviceToHost, s));
+                IVF_TRY(hipMemcpyAsync(rsc.data(), ivf->cs_rscores.p, rsum * 4, hipMemcpyDeviceToHost, s));
+            }
+            IVF_TRY(hipMemcpyAsync(rcnt.data(), ivf->cs_rcnt.p, (size_t)ng * 4, hipMemcpyDeviceToHost, s));
+            IVF_TRY(hipStreamSynchronize(s));
+            // 4. candidate index -> (probed list, position) -> id; distance = -score
+            for (uint32_t b = 0; b < ng; b++) {
+                const uint32_t q = q0 + g0 + b;
+                const Seg* sq = segs.data() + (size_t)(g0 + b) * np;
+                const uint32_t cnt = std::min<uint32_t>(rcnt[b], (uint32_t)std::min<uint64_t>(k, total[g0 + b]));
+                for (uint32_t j = 0; j < cnt; j++) {
+                    const uint64_t cand = rrows[rbase[b] + j];
+                    uint32_t lo = 0, hi = np;  // last segment whose first candidate <= cand (empty ones share offsets: take the last)
+                    while (hi - lo > 1) {
+                        const uint32_t mid = (lo + hi) >> 1;
+                        if (sq[mid].cand <= cand) lo = mid;
+                        else hi = mid;
+                    }
+                    while (sq[lo].count == 0 || cand - sq[lo].cand >= sq[lo].count) lo--;  // (never below 0: cand < total)
+                    out_ids[(size_t)q * k + j] = ivf->row_base + ivf->perm_host[sq[lo].start + (cand - sq[lo].cand)];
+                    out_distances[(size_t)q * k + j] = 0.0f - rsc[rbase[b] + j];
+                }
+                out_counts[q] = cnt;
+            }
+            g0 = g1;
+        }
+    }
+    return NMN_OK;
+}
+
+extern "C" int32_t nmn_ivf_storage_kind(const nmn_ivf* ivf) { return ivf ? ivf->kind : NMN_IVF_FLAT; }
+extern "C" uint32_t nmn_ivf_pq_codewords(const nmn_ivf* ivf) { return (ivf && ivf->kind == NMN_IVF_PQ) ? ivf->pq_k : 0; }
+
+extern "C" nmn_status nmn_ivf_pq_codebook(nmn_ivf* ivf, float* out, uint64_t cap_floats) {
+    if (!ivf || !out) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (ivf->kind != NMN_IVF_PQ) return set_error(NMN_ERR_CONFIGURATION, "not an IVF-PQ index");
+    std::shared_lock<std::shared_mutex> g(ivf->rw);
+    if (cap_floats < ivf->codebook_host.size()) return set_error(NMN_ERR_BUFFER_TOO_SMALL, "codebook buffer too small");
+    std::copy(ivf->codebook_host.begin(), ivf->codebook_host.end(), out);
+    return NMN_OK;
+}
+
+extern "C" nmn_status nmn_ivf_codes(nmn_ivf* ivf, void* out, uint64_t cap_bytes) {
+    if (!ivf || !out) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (ivf->kind == NMN_IVF_FLAT) return set_error(NMN_ERR_CONFIGURATION, "an IVF-Flat index holds no codes");
+    std::shared_lock<std::shared_mutex> g(ivf->rw);
+    const size_t need = (size_t)ivf->n_coded * ivf->code_bytes;
+    if (cap_bytes < need) return set_error(NMN_ERR_BUFFER_TOO_SMALL, "code buffer too small");
+    if (need) memcpy(out, ivf->codes_host.data(), need);
+    return NMN_OK;
+}
+
+extern "C" uint64_t nmn_ivf_hbm_bytes(nmn_ivf* ivf) {
+    if (!ivf) return 0;
+    std::unique_lock<std::shared_mutex> g(ivf->rw);
+    uint64_t b = index_hbm_bytes(ivf->vectors) + index_hbm_bytes(ivf->cvec) + index_hbm_bytes(ivf->centroids);
+    if (ivf->kind == NMN_IVF_FLAT) {
+        b += ivf->cap * 4 + ((ivf->cap + 63) / 64 + 1) * 8 + (ivf->list_off ? ((uint64_t)ivf->n_clusters + 1) * 4 : 0);
+        for (auto& sl : ivf->slots) b += ((ivf->cap + 63) / 64 + 1) * 16 * sl->nb;  // probe bitmaps
+    } else {
+        b += std::max<uint64_t>(ivf->cap, 1) * ivf->code_bytes + ivf->codebook_host.size() * 4;
+        for (const nmn_ivf::Grow* gr : {&ivf->cs_qraw, &ivf->cs_qpad, &ivf->cs_qinfo, &ivf->cs_qstate, &ivf->cs_cscores, &ivf->cs_ckeys,
+                                        &ivf->cs_probe_rows, &ivf->cs_probe_scores, &ivf->cs_probe_count, &ivf->cs_segs, &ivf->cs_base,
+                                        &ivf->cs_tables, &ivf->cs_qwords, &ivf->cs_scores, &ivf->cs_keys, &ivf->cs_rows, &ivf->cs_rscores,
+                                        &ivf->cs_rcnt})
+            b += gr->cap;
+    }
+    b += ivf->cscores_cap * 4 + largek_sort_len(ivf->n_clusters) * 8;  // the assignment sweep's scores, the ranking's sort buffer
+    return b;
+}
+
 // ---- persistence of the device layout ------------------------------------------------------------------
 // File = Header{kind = ivf, dim, rows = vectors, aux = clusters} | centroids clusters x dim f32 | assign[] rows x u32 | a flat
 // shard section (nmn_persist.hip) holding the vectors in id order.  A load re-creates the index WITHOUT re-running k-means or
@@ -1154,6 +1715,8 @@ extern "C" nmn_status nmn_ivf_search(nmn_ivf* ivf, const float* queries, uint32_
 
 namespace nmn {
 nmn_status persist_write_ivf(nmn_ivf* ivf, FILE* fp, const char* path) {
+    if (ivf->kind != NMN_IVF_FLAT)
+        return set_error(NMN_ERR_CONFIGURATION, "IVF-PQ / IVF-Binary indexes cannot be saved (only IVF-Flat persists its device layout)");
     std::unique_lock<std::shared_mutex> g(ivf->rw);
     const uint64_t rows = ivf->vectors->rows;
     std::vector<float> cents((size_t)ivf->n_clusters * ivf->dim);
@@ -1243,6 +1806,8 @@ nmn_status persist_read_ivf(FILE* fp, const char* path, const PersistHeader& h, 
 
 extern "C" nmn_status nmn_ivf_save(nmn_ivf* ivf, const char* path) {
     if (!ivf || !path) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (ivf->kind != NMN_IVF_FLAT)  // (before the file is created: a refused save leaves nothing behind)
+        return set_error(NMN_ERR_CONFIGURATION, "IVF-PQ / IVF-Binary indexes cannot be saved (only IVF-Flat persists its device layout)");
     FILE* fp = fopen(path, "wb");
     if (!fp) return persist_io_error("cannot create", path);
     nmn_status st = persist_write_ivf(ivf, fp, path);

@@ -86,6 +86,8 @@ ENGINE_SIGNATURES = {
     "nmn_results_aux": (C.c_char_p, [vp, C.c_uint64]),
     "nmn_ivf_options_default": (None, [vp]),
     "nmn_engine_build_ivf_index": (C.c_int32, [vp, vp, C.POINTER(vp)]),
+    "nmn_engine_build_ivf_index_ex": (C.c_int32, [vp, vp, vp, C.POINTER(vp)]),
+    "nmn_engine_estimate_ivf_memory": (C.c_int32, [vp, vp, vp, C.POINTER(C.c_uint64)]),
     "nmn_engine_ivf_free": (None, [vp]),
     "nmn_engine_ivf_len": (C.c_uint64, [vp]),
     "nmn_engine_ivf_clusters": (C.c_uint32, [vp]),
@@ -298,19 +300,104 @@ class _IvfOptions(C.Structure):
 
 
 @dataclass
+class KMeansConfig:
+    """tensor_store::delta_vector::KMeansConfig (delta_vector.rs:691-711)."""
+    max_iterations: int = 100
+    convergence_threshold: float = 1e-4
+    seed: int = 42
+    init_method: str = "kmeans++"   # or "random"
+
+
+@dataclass
+class PQConfig:
+    """tensor_store::pq::PQConfig (pq.rs:40-85): M subspaces, K codewords each, the codebook's own k-means."""
+    num_subspaces: int = 8
+    num_centroids: int = 256
+    kmeans_config: KMeansConfig = None
+
+    def __post_init__(self):
+        if self.kmeans_config is None:
+            self.kmeans_config = KMeansConfig()
+
+    @staticmethod
+    def default():
+        return PQConfig()
+
+    @staticmethod
+    def high_compression():
+        return PQConfig(num_subspaces=4)
+
+    @staticmethod
+    def high_recall():
+        return PQConfig(num_subspaces=32)
+
+
+class BinaryThreshold:
+    """tensor_store::binary_quantization::BinaryThreshold (binary_quantization.rs:27-60)."""
+    SIGN, MEAN, MEDIAN = "sign", "mean", "median"
+    _CODES = {"sign": _capi.BINARY_SIGN, "mean": _capi.BINARY_MEAN, "median": _capi.BINARY_MEDIAN}
+
+    @classmethod
+    def code(cls, t):
+        if t not in cls._CODES:
+            raise ValueError(f"unknown binary threshold {t!r} (sign / mean / median)")
+        return cls._CODES[t]
+
+
+def _storage_struct(storage):
+    """("flat",) / ("pq", PQConfig) / ("binary", threshold) -> nmn_ivf_storage"""
+    s = _capi.IvfStorage()
+    _capi.load().nmn_ivf_storage_default(C.byref(s))
+    kind = storage[0]
+    if kind == "pq":
+        pq = storage[1]
+        km = pq.kmeans_config
+        s.kind = _capi.IVF_PQ
+        s.pq_num_subspaces = int(pq.num_subspaces)
+        s.pq_num_centroids = int(pq.num_centroids)
+        s.pq_kmeans = _capi.KMeansOptions(max_iterations=int(km.max_iterations),
+                                          convergence_threshold=float(km.convergence_threshold), seed=int(km.seed),
+                                          init_method=0 if km.init_method == "random" else 1)
+    elif kind == "binary":
+        s.kind = _capi.IVF_BINARY
+        s.binary_threshold = BinaryThreshold.code(storage[1])
+    elif kind != "flat":
+        raise ValueError(f"unknown IVF storage {kind!r}")
+    return s
+
+
+@dataclass
 class IVFBuildOptions:
-    """vector_engine::IVFBuildOptions with IVFConfig::flat + KMeansConfig (lib.rs:941-1000, ivf.rs:61-147,
-    delta_vector.rs:691-711).  nprobe None = default_nprobe(num_clusters)."""
+    """vector_engine::IVFBuildOptions with IVFConfig + KMeansConfig (lib.rs:941-1000, ivf.rs:61-147,
+    delta_vector.rs:691-711).  nprobe None = default_nprobe(num_clusters).  storage: ("flat",), ("pq", PQConfig) or
+    ("binary", threshold)."""
     num_clusters: int = 100
     nprobe: int = None
     max_iterations: int = 100
     convergence_threshold: float = 1e-4
     seed: int = 42
     init_method: str = "kmeans++"   # or "random"
+    storage: tuple = ("flat",)
 
     @staticmethod
     def flat(num_clusters):
         return IVFBuildOptions(num_clusters=num_clusters)
+
+    @staticmethod
+    def pq(num_clusters, pq_config=None):
+        """IVFBuildOptions::pq (lib.rs:966-976)"""
+        return IVFBuildOptions(num_clusters=num_clusters, storage=("pq", pq_config or PQConfig()))
+
+    @staticmethod
+    def binary(num_clusters, threshold="sign"):
+        """IVFBuildOptions::binary (lib.rs:978-988; the reference fixes BinaryThreshold::Sign, the others via IVFConfig)"""
+        BinaryThreshold.code(threshold)
+        return IVFBuildOptions(num_clusters=num_clusters, storage=("binary", threshold))
+
+    def _c(self):
+        return _IvfOptions(num_clusters=self.num_clusters, nprobe=self.nprobe or 0, max_iterations=self.max_iterations,
+                           convergence_threshold=self.convergence_threshold, seed=self.seed,
+                           init_method=0 if self.init_method == "random" else 1)
 
 
 class IVFIndex:
@@ -601,13 +688,23 @@ class VectorEngine:
     def build_ivf_index(self, options=None):
         """-> (IVFIndex, key_mapping) like the reference; k-means as the reference runs it, lists on the GPU."""
         o = options or IVFBuildOptions()
-        co = _IvfOptions(num_clusters=o.num_clusters, nprobe=o.nprobe or 0, max_iterations=o.max_iterations,
-                         convergence_threshold=o.convergence_threshold, seed=o.seed,
-                         init_method=0 if o.init_method == "random" else 1)
+        co = o._c()
         h = vp()
-        _check(_lib().nmn_engine_build_ivf_index(self._h, C.byref(co), C.byref(h)))
+        if o.storage[0] == "flat":
+            _check(_lib().nmn_engine_build_ivf_index(self._h, C.byref(co), C.byref(h)))
+        else:
+            so = _storage_struct(o.storage)
+            _check(_lib().nmn_engine_build_ivf_index_ex(self._h, C.byref(co), C.byref(so), C.byref(h)))
         index = IVFIndex(h)
         return index, index.keys
+
+    def estimate_ivf_memory(self, options):
+        """estimate_ivf_memory (lib.rs:2821-2851): bytes of centroids + stored vectors / codes + ids; host arithmetic."""
+        co = options._c()
+        so = _storage_struct(options.storage)
+        out = C.c_uint64()
+        _check(_lib().nmn_engine_estimate_ivf_memory(self._h, C.byref(co), C.byref(so), C.byref(out)))
+        return int(out.value)
 
     # -- index persistence (lib.rs:3733-4000) -----------------------------------------------------
     DEFAULT_COLLECTION = "default"
