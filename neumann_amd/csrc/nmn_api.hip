@@ -288,7 +288,7 @@ constexpr uint64_t kCrowdPool = 8ull << 20;
 
 // Frees what ws_alloc allocates (and only that), leaving the workspace as ws_get made it.
 static void ws_release_core(Workspace* w) {
-    void** ptrs[] = {(void**)&w->scores, (void**)&w->tmax, (void**)&w->wmax, (void**)&w->tsample, (void**)&w->skip_key,
+    void** ptrs[] = {(void**)&w->scores, (void**)&w->tmax, (void**)&w->wmax, (void**)&w->ring_ctr, (void**)&w->tsample, (void**)&w->skip_key,
                      (void**)&w->k_extra, (void**)&w->qpad, (void**)&w->qi8, (void**)&w->qinfo, (void**)&w->qinfo_f32, (void**)&w->qstate,
                      (void**)&w->cand_rows, (void**)&w->cand_scores, (void**)&w->split_sg, (void**)&w->split_ctr, (void**)&w->final_ticket, (void**)&w->done_ctr, (void**)&w->run_slots, (void**)&w->run_bound, (void**)&w->h_counts2, (void**)&w->crowd_ctr,
                      (void**)&w->crowd_rows, (void**)&w->crowd_scores, (void**)&w->fb_hist, (void**)&w->fb_list, (void**)&w->fb_count,
@@ -325,6 +325,8 @@ static nmn_status ws_alloc_core(nmn_index* idx, Workspace* w) {
     w->tmax_stride = ((uint64_t)w->n_tiles_cap + 3) & ~3ull;  // rows of tmax stay 16-B aligned (uint4 sweeps)
     HIP_TRY(hipMalloc(reinterpret_cast<void**>(&w->tmax), std::max<size_t>(nq * w->tmax_stride, 4) * 4));
     HIP_TRY(hipMalloc(reinterpret_cast<void**>(&w->wmax), nq * kMaxScanWaves * 4));
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&w->ring_ctr), 2 * 4));
+    HIP_TRY(hipMemset(w->ring_ctr, 0, 2 * 4));
     w->n_sample_cap = (w->n_tiles_cap + kSampleStep - 1) / kSampleStep + 4;
     HIP_TRY(hipMalloc(reinterpret_cast<void**>(&w->tsample), nq * w->n_sample_cap * 4));
     HIP_TRY(hipMalloc(reinterpret_cast<void**>(&w->skip_key), nq * 4));
@@ -1221,7 +1223,9 @@ static nmn_status search_enqueue(nmn_index* idx, Workspace* w, const float* quer
                 long v = e ? atol(e) : (long)kMaxScanWaves;
                 return (uint32_t)std::min<long>(std::max<long>(v, 64), (long)kMaxScanWaves);
             }();
-            if (use_ring) sp.tiles_per_wave = std::max<uint32_t>(1, (n_tiles + ring_wgs - 1) / ring_wgs);  // per workgroup
+            if (use_ring) sp.tiles_per_wave = std::max<uint32_t>(1, (n_tiles + ring_wgs - 1) / ring_wgs);  // per wmax group
+            // ... and the tiles in chunks taken from a ticket counter, long ones first (ring_set_grid; NMN_NO_RING_EVEN=1: one workgroup per group)
+            ring_set_grid(sp, use_ring ? w->ring_ctr : nullptr);
             sp.metric = (int)metric;
             sp.strided = (!use_mfma && mask_dev) ? 1u : 0u;  // masked VALU sweeps: a wave takes every W-th tile (runs of selected rows spread over all waves)
             static const bool no_walk = getenv("NMN_NO_WALK") != nullptr;  // (A/B switch of the survivor walk)
@@ -1285,6 +1289,9 @@ static nmn_status search_enqueue(nmn_index* idx, Workspace* w, const float* quer
             static const bool no_chain = getenv("NMN_NO_SWEEP_CHAIN") != nullptr;
             const bool chain = !no_chain && (uint64_t)n_rows * idx->ld * w->last_elem_bytes >= (2ull << 30);  // (sweeps of >= ~0.35 ms: below, the two
             // event packets of the chain cost more than the overlap of two short sweeps — 1M x 768: 5.8 k q/s without, 5.6 k with)
+            // wmax entries two chunks of a ring sweep share are joined by atomicMax: zeroed here, ahead of the chain's wait and of the
+            // sweep's timing event (it runs under the previous sweep)
+            if (sp.ring_wgs) HIP_TRY(hipMemsetAsync(w->wmax, 0, (size_t)((n_tiles + sp.tiles_per_wave - 1) / sp.tiles_per_wave) * sizeof(uint32_t), stream));
             if (chain && idx->sweep_seq && idx->sweep_stream != stream)
                 HIP_TRY(hipStreamWaitEvent(stream, idx->sweep_ev[(idx->sweep_seq - 1) & 3u], 0));
             if (w->timed && qa == 0 && !nested) {
@@ -2332,7 +2339,8 @@ extern "C" nmn_status nmn_index_read_probe(nmn_index* idx, uint32_t reps, double
     IdleGuard idle(idx, lk);
     hipStream_t s = idx->host_stream;
     float* sink = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&sink), 4));
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&sink), 2 * 4));  // (the ring probe: its ticket counter)
+    HIP_TRY(hipMemset(sink, 0, 2 * 4));
     hipEvent_t a = nullptr, b = nullptr;
     hipError_t e = hipEventCreate(&a);
     if (e == hipSuccess) e = hipEventCreate(&b);
@@ -2344,7 +2352,7 @@ extern "C" nmn_status nmn_index_read_probe(nmn_index* idx, uint32_t reps, double
     const bool ring = n_tiles >= 4096u && scan_ring_supported(idx->ld, idx->dim, NMN_METRIC_DOT_PRODUCT) && !getenv("NMN_NO_RING");
     const uint32_t ring_tpw = (uint32_t)std::max<uint64_t>(1, (n_tiles + kMaxScanWaves - 1) / kMaxScanWaves);
     uint64_t probe_rows = ring ? n_tiles * kTileRows : idx->rows;
-    auto probe = [&]() { return ring ? launch_ring_probe(idx->corpus, idx->rows, idx->ld, ring_tpw, s) : launch_read_probe(idx->corpus, idx->rows, idx->ld, sink, s); };
+    auto probe = [&]() { return ring ? launch_ring_probe(idx->corpus, idx->rows, idx->ld, ring_tpw, reinterpret_cast<uint32_t*>(sink), s) : launch_read_probe(idx->corpus, idx->rows, idx->ld, sink, s); };
     if (e == hipSuccess) e = probe();  // warm-up
     for (uint32_t i = 0; i < std::max(reps, 1u) && e == hipSuccess; i++) {
         e = hipEventRecord(a, s);

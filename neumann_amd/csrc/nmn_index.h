@@ -24,6 +24,7 @@ struct Workspace {
     uint32_t* scores = nullptr;
     uint32_t* tmax = nullptr;
     uint32_t* wmax = nullptr;
+    uint32_t* ring_ctr = nullptr;  // [2] the ring sweep's ticket counter (zero between sweeps)
     uint32_t* tsample = nullptr;   // [nq][n_sample_cap] tile maxima of the sampling pass (batched sweep)
     uint32_t* skip_key = nullptr;  // [nq] score-write threshold of the batched sweep
     uint32_t* k_extra = nullptr;   // [1] rows forced into the candidates (f64 artifact similarity)

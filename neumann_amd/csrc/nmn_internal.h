@@ -186,6 +186,12 @@ struct ScanParams {
     uint32_t* run_bound;     // [nq rounded up to 128] keys (kKeyNaN = no bound yet: every tile writes)
     uint32_t run_S;          // 0 = off; else the rank of the bound among the running maxima (= k)
     uint32_t i8_one_plane;   // 8-bit matrix-core sweep: 1 = the queries' h plane only (qprep approx_pass bit 16 measured the rounding accordingly)
+    uint32_t ring_wgs;       // ring sweep (nmn_scan_ring.hip): 0 = one workgroup per wmax group of tiles_per_wave tiles; else the tiles in this
+                             // many chunks, taken by ring_grid workgroups from the ticket counter ring_ctr (wmax entries shared by two chunks
+                             // joined by atomicMax: the launching stream zeroes wmax before the sweep)
+    uint32_t ring_tail;      // ... of which the last ring_tail chunks are a quarter of one of the others each (ring_tail < ring_wgs)
+    uint32_t ring_grid;
+    uint32_t* ring_ctr;      // [2] zero between sweeps (the last workgroup of a sweep resets them)
     uint32_t run_dbg;        // measurement only (NMN_RUN_BOUND_DEBUG): 1 = decide the stores by skip_key, 2 = no slot atomics, 4 = no refresh, 8 = no bound DMA
     int metric;
 };
@@ -222,7 +228,10 @@ bool ingest_q8_supported(uint32_t ld, uint32_t dim);
 hipError_t launch_ingest_q8(const float* corpus, uint32_t ld, uint64_t row0, uint64_t n, float* norms, float* inv_norms, uint32_t* max_norm_bits,
                             int8_t* q8, float* scale, float* vv, float* cosf, uint32_t* err_bits, hipStream_t s);
 hipError_t launch_read_probe(const float* corpus, uint64_t n_rows, uint32_t ld, float* sink, hipStream_t s);
-hipError_t launch_ring_probe(const float* corpus, uint64_t n_rows, uint32_t ld, uint32_t tiles_per_wg, hipStream_t s);  // nmn_scan_ring.hip
+hipError_t launch_ring_probe(const float* corpus, uint64_t n_rows, uint32_t ld, uint32_t tiles_per_wg, uint32_t* ctr, hipStream_t s);  // nmn_scan_ring.hip
+// the ring sweep's split into chunks taken from a ticket counter (ScanParams::ring_*); ctr == nullptr or NMN_NO_RING_EVEN=1: one workgroup
+// per wmax group
+void ring_set_grid(ScanParams& p, uint32_t* ctr);
 // batched-query sweep on the matrix cores (nmn_scan_mfma.hip); tiles_per_wave = tiles per WORKGROUP there
 bool scan_mfma_supported(uint32_t ld, uint32_t dim, int metric);
 hipError_t launch_scan_mfma(const ScanParams& p, hipStream_t s);

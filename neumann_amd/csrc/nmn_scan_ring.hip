@@ -37,6 +37,16 @@ constexpr int kRingStageBytes = 64 * 128 * 4;  // [64 rows][128 f32] = 32 KiB
 constexpr int kRingStages = 4;                 // 128 KiB, three stages in flight
 constexpr int kRingPieces = 8;                 // 1-KiB LDS-DMA instructions per wave and stage (2 rows x 512 B each)
 constexpr int kRingRowPitch = 128;             // floats between the rows of a stage
+constexpr uint32_t kRingTailWeight = 4;        // tiles of a long workgroup of an evenly split sweep per tile of a short one
+
+#ifdef NMN_RING_WG_CLOCK
+// Measurement-only build (tools/micro/ring_clock.hip): every workgroup records wall_clock64() at its start, when its first stage has
+// landed, when it issues no further real stage, and at its end, plus the CU it ran on — [workgroup][5] u64, ordinary vector stores.
+__device__ unsigned long long* nmn_ring_clk;
+#define NMN_RING_CLK(i, v) do { if (threadIdx.x == 0) nmn_ring_clk[(uint64_t)blockIdx.x * 5u + (i)] = (v); } while (0)
+#else
+#define NMN_RING_CLK(i, v) do { } while (0)
+#endif
 
 template <int N>
 __device__ __forceinline__ void ring_wait_vm() {
@@ -49,7 +59,7 @@ __device__ __forceinline__ void ring_wait_vm() {
 // very kernel reaches on this device (nmn_index_read_probe: bench.py's `ring_only_read_ceiling`; 7.0-7.2 TB/s at 10M x 768).
 template <int METRIC, bool PROBE = false>
 __global__ void __launch_bounds__(256, 1) scan_ring_kernel(ScanParams p) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];  // ring | [8 tiles][64] row magnitudes | [2][4] tile-maximum parts | query [ld]
+    extern __shared__ __attribute__((aligned(16))) float lds[];  // ring | [8 tiles][64] row magnitudes | [2][4] tile-maximum parts | query [ld] | ticket
     float* const nrm = lds + kRingStages * (kRingStageBytes / 4);
     uint32_t* const tpart = reinterpret_cast<uint32_t*>(nrm + 8 * 64);  // (8 slots: with one stage per row the ring runs 4 tiles ahead of the epilogue)
     float* const qlds = nrm + 8 * 64 + 8;
@@ -61,10 +71,36 @@ __global__ void __launch_bounds__(256, 1) scan_ring_kernel(ScanParams p) {
     const uint32_t r4 = lane >> 4, j = lane & 15u;
     const uint32_t ld = p.ld;
     const uint32_t row_bytes = ld * 4u;
-    const uint32_t bx = blockIdx.x;
-    const uint32_t t0 = bx * p.tiles_per_wave;  // tiles per WORKGROUP on this path
-    if (t0 >= p.n_tiles) return;
-    const uint32_t t1 = min(t0 + p.tiles_per_wave, p.n_tiles);
+    NMN_RING_CLK(0, wall_clock64());
+    NMN_RING_CLK(4, __smid());
+    // Tile ranges ("chunks"): ring_wgs == 0 — one per workgroup, chunk bx = wmax group bx (tiles_per_wave tiles).  Else ring_wgs chunks:
+    // the first ring_wgs - ring_tail take kRingTailWeight shares of the tiles each, the last ring_tail one share each, and ring_grid
+    // workgroups (one per CU) take them in order from a ticket counter until none is left.  Workgroups are spread over the XCDs
+    // round-robin at launch, and an XCD cannot take over another one's workgroups: with a fixed range per workgroup, CUs of the XCDs
+    // that stream faster ran out of work 0.4-0.6 ms before the sweep's end (profiles/r07b_*).  With tickets every CU keeps taking
+    // chunks, the short ones last, and the CUs finish within a short chunk of each other.  A group of tiles_per_wave tiles may then
+    // straddle two or more chunks: see flush_group below.
+    const uint32_t tpw = p.tiles_per_wave;
+    auto first_tile = [&](uint32_t b) -> uint32_t {
+        const uint64_t gm = p.ring_wgs - p.ring_tail;
+        const uint64_t u = b <= gm ? (uint64_t)kRingTailWeight * b : (uint64_t)kRingTailWeight * gm + (b - gm);
+        return (uint32_t)(u * p.n_tiles / ((uint64_t)kRingTailWeight * gm + p.ring_tail));
+    };
+    uint32_t* const ticket = reinterpret_cast<uint32_t*>(qlds + ld);
+    for (uint32_t round = 0;; round++) {
+    uint32_t bx = blockIdx.x;
+    if (p.ring_wgs) {
+        if (threadIdx.x == 0) *ticket = atomicAdd(p.ring_ctr, 1u);
+        __syncthreads();
+        bx = __builtin_amdgcn_readfirstlane(*ticket);
+        __syncthreads();
+        if (bx >= p.ring_wgs) break;
+    } else if (round) {
+        break;
+    }
+    const uint32_t t0 = p.ring_wgs ? first_tile(bx) : bx * tpw;
+    const uint32_t t1 = p.ring_wgs ? first_tile(bx + 1u) : min(t0 + tpw, p.n_tiles);
+    if (t0 >= p.n_tiles || t1 <= t0) continue;
     const uint32_t n_stage = (t1 - t0) * KC;
 
     // ---- the query into LDS (read back per stage: elements 128 kc + 8 j .. + 7 for this lane), by LDS-DMA as well: 1 KiB per
@@ -123,7 +159,14 @@ __global__ void __launch_bounds__(256, 1) scan_ring_kernel(ScanParams p) {
         off[sub] = (wave * 16u + rr) * kRingRowPitch + (((j * 2u) ^ rr) * 4u);
     }
 
-    uint32_t wmax = kKeyMasked;   // (wave 0: over the finished tiles of the workgroup)
+    uint32_t wmax = kKeyMasked;   // (wave 0: over the finished tiles of the workgroup in the current wmax group)
+    // the maximum of wmax group g (wave 0, lane 0): a plain store where this workgroup covers the whole group, else atomicMax into an
+    // entry the launching stream zeroed before the sweep (kKeyMasked == 0: neutral); every other reader of wmax runs after the sweep
+    auto flush_group = [&](uint32_t g, uint32_t m) __attribute__((always_inline)) {
+        if (lane != 0) return;
+        if (g * tpw >= t0 && min(g * tpw + tpw, p.n_tiles) <= t1) p.wmax[g] = m;
+        else atomicMax(p.wmax + g, m);
+    };
     uint32_t sidx = 0;
     // the stage the loop issues next (stage index sidx + kRingStages - 1), advanced incrementally: a division per stage costs more
     // scalar instructions than the stage's arithmetic
@@ -139,15 +182,21 @@ __global__ void __launch_bounds__(256, 1) scan_ring_kernel(ScanParams p) {
             // hand-over a stage needs.  The workgroup meets once per TILE — for the query (first tile) and the tile maxima's parts.
             if (kc == 0) __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
+            if (sidx == 0) NMN_RING_CLK(1, wall_clock64());
             if (!PROBE && kc == 0 && wave == 0 && tile > t0) {
                 // the previous tile's maximum: its four parts were written before this barrier
                 const uint32_t* tp = tpart + ((tile - 1u - t0) & 1u) * 4u;
                 const uint32_t m = max(max(tp[0], tp[1]), max(tp[2], tp[3]));
                 if (lane == 0) p.tmax[tile - 1u] = m;
                 wmax = max(wmax, m);
+                if (tile % tpw == 0) {  // tile - 1 closed its group
+                    flush_group((tile - 1u) / tpw, wmax);
+                    wmax = kKeyMasked;
+                }
             }
             const uint32_t ns = sidx + (kRingStages - 1);
             const bool issue = ns < n_stage;
+            if (ns == n_stage) NMN_RING_CLK(2, wall_clock64());
             const char* const nsrc = issue ? stage_src(nt, nkc) : mat;
             const uint32_t lmask = issue ? 0xFFFFFFFFu : 0u;
             float* const nbuf = lds + (ns % kRingStages) * (kRingStageBytes / 4);
@@ -235,17 +284,22 @@ __global__ void __launch_bounds__(256, 1) scan_ring_kernel(ScanParams p) {
         const uint32_t* tp = tpart + ((t1 - 1u - t0) & 1u) * 4u;
         const uint32_t m = max(max(tp[0], tp[1]), max(tp[2], tp[3]));
         wmax = max(wmax, m);
-        if (lane == 0) {
-            p.tmax[t1 - 1u] = m;
-            p.wmax[bx] = wmax;
-        }
+        if (lane == 0) p.tmax[t1 - 1u] = m;
+        flush_group((t1 - 1u) / tpw, wmax);
     }
+    }  // chunks
+    // the last workgroup out resets the ticket counter for the next sweep on this workspace (every other one has drawn its last ticket)
+    if (p.ring_wgs && threadIdx.x == 0 && atomicAdd(p.ring_ctr + 1, 1u) == gridDim.x - 1u) {
+        p.ring_ctr[0] = 0u;
+        p.ring_ctr[1] = 0u;
+    }
+    NMN_RING_CLK(3, wall_clock64());
 }
 
 template <int METRIC>
 hipError_t launch_ring_metric(const ScanParams& p, hipStream_t s) {
-    const uint32_t blocks = (p.n_tiles + p.tiles_per_wave - 1) / p.tiles_per_wave;
-    const size_t lds = (size_t)kRingStages * kRingStageBytes + 8 * 64 * 4 + 8 * 4 + (size_t)p.ld * 4;
+    const uint32_t blocks = p.ring_wgs ? p.ring_grid : (p.n_tiles + p.tiles_per_wave - 1) / p.tiles_per_wave;
+    const size_t lds = (size_t)kRingStages * kRingStageBytes + 8 * 64 * 4 + 8 * 4 + (size_t)p.ld * 4 + 16;
     auto kern = scan_ring_kernel<METRIC>;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
@@ -261,17 +315,44 @@ bool scan_ring_supported(uint32_t ld, uint32_t dim, int metric) {
     return dim <= ld && ld % 128u == 0 && ld >= 128u && ld <= 4096u;  // (the query behind the ring: 16 KiB at 4096 elements)
 }
 
+// The split of a sweep into chunks, in units of the CU count n: 14 n chunks of four shares of the tiles each, then 8 n of one share
+// (10M x 768: 38 and 9-10 tiles; NMN_RING_MAIN / NMN_RING_TAIL chunks per CU), taken by n workgroups.  With one workgroup per wmax
+// group (NMN_NO_RING_EVEN=1, the round-6 form) 10M rows made 4007 workgroups of 39 tiles, 270 us each, 15-16 per CU: the sweep ran its
+// last 0.56-0.64 ms with fewer than all CUs busy, 5.6-6.7 % of the CU time idle (profiles/r07b_*).  ctr: two words, zero before the
+// first sweep (the kernel leaves them zero).
+void ring_set_grid(ScanParams& p, uint32_t* ctr) {
+    struct Grid {
+        uint32_t chunks, tail, wgs;
+    };
+    static const Grid g = []() -> Grid {
+        if (getenv("NMN_NO_RING_EVEN")) return {0, 0, 0};
+        int dev = 0, n = 256;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+        auto knob = [](const char* name, long def) {
+            const char* e = getenv(name);
+            return std::min<long>(std::max<long>(e ? atol(e) : def, 0), 32);
+        };
+        const long m = std::max<long>(knob("NMN_RING_MAIN", 14), 1), t = knob("NMN_RING_TAIL", 8);
+        return {(uint32_t)((m + t) * n), (uint32_t)(t * n), (uint32_t)n};
+    }();
+    p.ring_wgs = ctr ? g.chunks : 0u;
+    p.ring_tail = g.tail;
+    p.ring_grid = g.wgs;
+    p.ring_ctr = ctr;
+}
+
 // The ring with nothing behind it: the read ceiling of the headline sweep's own data movement (same workgroups, stages, pieces).
-hipError_t launch_ring_probe(const float* corpus, uint64_t n_rows, uint32_t ld, uint32_t tiles_per_wg, hipStream_t s) {
+hipError_t launch_ring_probe(const float* corpus, uint64_t n_rows, uint32_t ld, uint32_t tiles_per_wg, uint32_t* ctr, hipStream_t s) {
     ScanParams p{};
     p.corpus = corpus;
     p.n_rows = n_rows;
     p.ld = ld;
     p.n_tiles = (uint32_t)(n_rows / kTileRows);  // whole tiles only (no row guard in the probe)
     p.tiles_per_wave = std::max<uint32_t>(1, tiles_per_wg);
+    ring_set_grid(p, ctr);
     if (p.n_tiles == 0) return hipSuccess;
-    const uint32_t blocks = (p.n_tiles + p.tiles_per_wave - 1) / p.tiles_per_wave;
-    const size_t lds = (size_t)kRingStages * kRingStageBytes + 8 * 64 * 4 + 8 * 4 + (size_t)p.ld * 4;
+    const uint32_t blocks = p.ring_wgs ? p.ring_grid : (p.n_tiles + p.tiles_per_wave - 1) / p.tiles_per_wave;
+    const size_t lds = (size_t)kRingStages * kRingStageBytes + 8 * 64 * 4 + 8 * 4 + (size_t)p.ld * 4 + 16;
     auto kern = scan_ring_kernel<NMN_METRIC_DOT_PRODUCT, true>;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;

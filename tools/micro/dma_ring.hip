@@ -209,11 +209,15 @@ __global__ void __launch_bounds__(WAVES * 64, 1) ring_kernel(const char* __restr
 }
 
 template <int STAGE, int RING, int AUX, int SEGB, int WAVES, int WORK = 0>
-static void run(const char* name, const char* src, uint64_t total_bytes, uint32_t pitch, uint32_t wgs, float* sink) {
-    // whole tiles of 64 rows per workgroup
+static void run(const char* name, const char* src, uint64_t total_bytes, uint32_t pitch, uint32_t wgs, float* sink, uint64_t tpw = 0) {
+    // whole tiles of 64 rows per workgroup (tpw > 0: that many, wgs * tpw tiles at most all there are)
     const uint64_t tile_bytes = 64ull * pitch;
     const uint64_t tiles = total_bytes / tile_bytes;
-    const uint64_t tiles_per_wg = tiles / wgs;
+    const uint64_t tiles_per_wg = tpw ? tpw : tiles / wgs;
+    if (tiles_per_wg * wgs > tiles) {
+        printf("%-44s: skipped (%u x %llu tiles > %llu)\n", name, wgs, (unsigned long long)tiles_per_wg, (unsigned long long)tiles);
+        return;
+    }
     const uint64_t wg_bytes = tiles_per_wg * tile_bytes;
     if (wg_bytes % STAGE) {
         printf("%-44s: skipped (workgroup range not a multiple of the stage)\n", name);
@@ -269,6 +273,20 @@ int main(int argc, char** argv) {
     else hipLaunchKernelGGL(fill_random, dim3(4096), dim3(256), 0, 0, reinterpret_cast<uint32_t*>(buf), (size_t)(bytes / 4));
     hipDeviceSynchronize();
     printf("mirror %.2f GB, row pitch %u B\n", bytes / 1e9, pitch);
+    if (argc > 2 && argv[2][0] == 'g') {  // "grid": the two layouts at 4096 workgroups, and on the round-6 product grid (full groups of 39 tiles)
+        const uint64_t tiles = bytes / (64ull * pitch);
+        const uint64_t tpw = (tiles + 4095) / 4096;
+        const uint32_t full = (uint32_t)(tiles / tpw);
+        for (int r = 0; r < 2; r++) {
+            run<32768, 4, 2, 512, 4>("SEG  64x512B  ring 4x32K nt, even", buf, bytes, pitch, 4096, sink);
+            run<32768, 4, 2, 512, 4>("SEG  64x512B  ring 4x32K nt, groups", buf, bytes, pitch, full, sink, tpw);
+            run<24576, 6, 2, 0, 4>("FULL 8 rows   ring 6x24K nt, even", buf, bytes, pitch, 4096, sink);
+            run<24576, 6, 2, 0, 4>("FULL 8 rows   ring 6x24K nt, groups", buf, bytes, pitch, full, sink, tpw);
+            run<32768, 4, 2, 512, 4>("SEG  64x512B  ring 4x32K nt, even", buf, bytes, pitch, 2048, sink);
+            run<24576, 6, 2, 0, 4>("FULL 8 rows   ring 6x24K nt, even", buf, bytes, pitch, 2048, sink);
+        }
+        return 0;
+    }
     if (pitch == 768 && argc > 2) {  // consumption models on the 8-bit sweep's stages
         for (uint32_t wgs : {256u, 1024u}) {
             run<16384, 8, 2, 256, 4, 0>("SEG  8x16K nt   ring alone", buf, bytes, pitch, wgs, sink);
@@ -310,7 +328,7 @@ int main(int argc, char** argv) {
         }
         return 0;
     }
-    for (uint32_t wgs : {256u, 512u, 1024u, 2048u}) {
+    for (uint32_t wgs : {256u, 512u, 1024u, 2048u, 4096u}) {
         run<32768, 4, 2, 512, 4>("SEG  64x512B  ring 4x32K nt (round 1)", buf, bytes, pitch, wgs, sink);
         run<32768, 4, 0, 512, 4>("SEG  64x512B  ring 4x32K default", buf, bytes, pitch, wgs, sink);
         run<24576, 6, 2, 0, 4>("FULL 16 rows  ring 6x24K nt", buf, bytes, pitch, wgs, sink);
