@@ -519,6 +519,18 @@ nmn_status nmn_ivf_cluster_sizes(nmn_ivf* ivf, uint64_t* out_sizes /* [n_cluster
  * 0.21 ms per call at nq = 1, 0.033 ms per query at nq = 32). */
 nmn_status nmn_ivf_search(nmn_ivf* ivf, const float* queries, uint32_t nq, uint32_t k, uint32_t nprobe,
                           uint64_t* out_ids, float* out_distances, uint32_t* out_counts, nmn_search_stats* stats);
+/* nmn_ivf_search with every buffer in DEVICE memory, for every storage (Flat, PQ, Binary): queries_dev nq x dim (tightly
+ * packed), out_ids_dev / out_distances_dev nq x k, out_counts_dev nq.  Returns what nmn_ivf_search returns for the same index
+ * state, bit for bit.  Enqueues on `stream` (NULL: the default stream) and returns without waiting: the centroid ranking, the
+ * candidate plan, the scan of the probed lists, the top-k selection and the id map all run on the device, nothing is read
+ * back, and a call of a shape (nq, k, nprobe, index size) the stream has served before allocates nothing and waits for
+ * nothing (growing a stream's workspace waits for that stream).  Calls on one stream may be pipelined (they share that
+ * stream's workspace); none of the host call's scratch is used, so host and device searches of one index run side by side.
+ * A call answers for the index as it was when it returned: nmn_ivf_add and nmn_ivf_destroy wait for the device searches in
+ * flight before they change or free what those read.  The first call builds a device copy of the list offsets and the
+ * candidate-order id map (4 bytes per vector; rebuilt after an add), counted by nmn_ivf_hbm_bytes from then on. */
+nmn_status nmn_ivf_search_device(nmn_ivf* ivf, const float* queries_dev, uint32_t nq, uint32_t k, uint32_t nprobe,
+                                 uint64_t* out_ids_dev, float* out_distances_dev, uint32_t* out_counts_dev, void* stream);
 /* Vectors (ids [0, n)) the LIST-MAJOR copy covers: the reference keeps a Vec of entries per list (ivf.rs:160-175), and so
  * does the device — a second copy of the vectors ordered by list, over which a probe reads contiguous row ranges and no
  * per-row array; laid out after nmn_ivf_build / nmn_ivf_load and again whenever the vectors added since make up an eighth of

@@ -165,6 +165,7 @@ SIGNATURES = {
     "nmn_ivf_clusters": (C.c_uint32, [vp]),
     "nmn_ivf_cluster_sizes": (C.c_int32, [vp, vp]),
     "nmn_ivf_search": (C.c_int32, [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.POINTER(SearchStats)]),
+    "nmn_ivf_search_device": (C.c_int32, [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp]),
     "nmn_ivf_vectors": (vp, [vp]),
     "nmn_ivf_storage_default": (None, [C.POINTER(IvfStorage)]),
     "nmn_ivf_build_ex": (C.c_int32, [C.POINTER(IndexDesc), vp, C.c_uint64, C.c_uint32, C.POINTER(KMeansOptions),

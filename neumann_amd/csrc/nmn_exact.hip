@@ -694,6 +694,48 @@ hipError_t launch_exact_scan(const ExactScanParams& p, hipStream_t s) {
     return hipGetLastError();
 }
 
+// ---- IVF-Flat candidate scan of nmn_ivf_search_device ---------------------------------------------------------------------
+// One probed list (blockIdx.x) of one query (blockIdx.z), kIvfScanRows of its rows per workgroup and step (blockIdx.y, grid-
+// stride): an 8-lane group per row as everywhere in this file, the row read through the candidate-order id map, the score the
+// kMetricNegL2 one of exact_score written at the row's candidate position.  Every probed row is scored exactly, so the
+// selection after it needs no margin, no rescore and no tie fix.
+namespace {
+constexpr uint32_t kIvfScanRows = 64;
+struct IvfSeg {  // = CodecSeg of nmn_ivf_codec.hip (launch_ivf_flat_scan checks the size)
+    uint32_t list, start, count, cand;
+};
+}  // namespace
+
+__global__ void __launch_bounds__(256) ivf_flat_scan_kernel(const float* __restrict__ queries, uint32_t dim, const float* __restrict__ corpus,
+                                                            uint32_t ld, const uint32_t* __restrict__ perm, const IvfSeg* __restrict__ segs,
+                                                            uint32_t np, const uint64_t* __restrict__ score_base,
+                                                            uint32_t* __restrict__ scores) {
+    const uint32_t q = blockIdx.z;
+    const IvfSeg sg = segs[(size_t)q * np + blockIdx.x];
+    const float* qv = queries + (size_t)q * dim;
+    uint32_t* out = scores + score_base[q] + sg.cand;
+    const uint32_t l = threadIdx.x & 7u, grp = threadIdx.x >> 3;
+    for (uint32_t r0 = blockIdx.y * kIvfScanRows; r0 < sg.count; r0 += gridDim.y * kIvfScanRows) {
+        const uint32_t r1 = min(sg.count, r0 + kIvfScanRows);
+        for (uint32_t r = r0 + grp; r < r1; r += 32) {  // (uniform per 8-lane group)
+            const float* v = corpus + (uint64_t)perm[sg.start + r] * ld;
+            const float ss = euclid_sumsq_seq<16>(qv, v, dim, l);
+            if (l == 0) out[r] = f2u(-sqrt_rn(ss));
+        }
+    }
+}
+
+hipError_t launch_ivf_flat_scan(const float* queries, uint32_t dim, const float* corpus, uint32_t ld, const uint32_t* perm,
+                                const void* segs, uint32_t np, uint32_t nq, uint32_t max_count, const uint64_t* score_base,
+                                uint32_t* scores, hipStream_t s) {
+    if (nq == 0 || np == 0 || max_count == 0) return hipSuccess;
+    if (codec_seg_bytes() != sizeof(IvfSeg)) return hipErrorInvalidValue;
+    const dim3 grid(np, std::min<uint32_t>((max_count + kIvfScanRows - 1) / kIvfScanRows, 65535u), nq);
+    hipLaunchKernelGGL(ivf_flat_scan_kernel, grid, dim3(256), 0, s, queries, dim, corpus, ld, perm, static_cast<const IvfSeg*>(segs), np,
+                       score_base, scores);
+    return hipGetLastError();
+}
+
 // ---- the whole SIMILAR TOP-K of a small shard in ONE launch ----------------------------------------------------------------
 // The sizes the reference itself publishes (1k-10k rows of 128 floats, vector_engine/benches/vector_engine_bench.rs:40-61;
 // lib.rs:4255-4276) are launch-bound on a GPU: the five launches of the pipeline, one H2D and one D2H cost 57 us at

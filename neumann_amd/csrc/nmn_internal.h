@@ -457,6 +457,13 @@ hipError_t launch_bq_quantize(const float* rows, uint32_t ld, uint64_t n, uint32
 hipError_t launch_bq_search(const uint64_t* qwords, uint32_t dim, const void* segs, uint32_t np, uint32_t nq, uint32_t max_count,
                             const uint64_t* codes, const uint64_t* score_base, uint32_t* scores, hipStream_t s);
 
+// the IVF-Flat candidate scan of the stream-ordered search (nmn_exact.hip): for every (query, probed list) segment of `segs`
+// (codec_seg_bytes() each, the codec scans' layout) and every row r of it, scores[score_base[q] + cand + r] =
+// -sqrt(sequential sum (q - v)^2) of the f32 row perm[start + r] of `corpus` — exactly the kMetricNegL2 score
+hipError_t launch_ivf_flat_scan(const float* queries, uint32_t dim, const float* corpus, uint32_t ld, const uint32_t* perm,
+                                const void* segs, uint32_t np, uint32_t nq, uint32_t max_count, const uint64_t* score_base,
+                                uint32_t* scores, hipStream_t s);
+
 // synthetic data
 hipError_t launch_synth_fill(float* corpus, uint32_t ld, uint32_t dim, uint64_t seed, uint64_t global_row0,
                              uint64_t local_row0, uint64_t n, hipStream_t s);

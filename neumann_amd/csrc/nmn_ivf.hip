@@ -285,6 +285,27 @@ struct nmn_ivf {
     };
     Grow cs_qraw, cs_qpad, cs_qinfo, cs_qstate, cs_cscores, cs_ckeys, cs_probe_rows, cs_probe_scores, cs_probe_count, cs_segs,
         cs_base, cs_tables, cs_qwords, cs_scores, cs_keys, cs_rows, cs_rscores, cs_rcnt;
+    // ---- nmn_ivf_search_device (docs/ivf.md §3.10c): none of the scratch above, nothing of the probe slots ----------------
+    // The candidate-order id map of every storage: dev_perm[dev_off[c] + j] = id - id base of the j-th vector of list c (ids
+    // ascending inside a list; for Flat over ALL the vectors, list-major copy and younger ones alike), built by the first
+    // device search and again after an `add` (dev_gen != gen).  dev_top[i] = rows of the i largest lists (the host-known bound
+    // of a query's candidates at nprobe i).
+    std::mutex dev_mu;                   // the members below
+    uint64_t gen = 0, dev_gen = ~0ull;   // gen: bumped by every add
+    uint32_t* dev_perm = nullptr;
+    uint32_t* dev_off = nullptr;
+    uint64_t dev_rows = 0;
+    std::vector<uint64_t> dev_top;
+    struct DevScratch {                  // per caller stream: pipelined calls on one stream share it, in stream order
+        hipStream_t stream = nullptr;
+        std::mutex mu;                   // held while a call enqueues
+        Grow qpad, qinfo, qstate, cscores, ckeys, probe_rows, probe_scores, probe_rank, probe_count, segs, base, totals, scores, keys,
+            tables, qwords;
+    };
+    std::vector<std::unique_ptr<DevScratch>> dev_scratch;
+    // an event per device search, recorded behind its last kernel: add / destroy wait for the pending ones before they touch
+    // what those searches read (completed events are recycled)
+    std::vector<hipEvent_t> ev_pending, ev_free;
 };
 
 #define IVF_TRY(expr)                                         \
@@ -293,9 +314,28 @@ struct nmn_ivf {
         if (_e != hipSuccess) return set_error_hip(_e, #expr); \
     } while (0)
 
+// wait for the device searches still in flight (caller holds rw exclusively, or owns the index alone)
+static void ivf_wait_device_searches(nmn_ivf* ivf) {
+    std::lock_guard<std::mutex> lk(ivf->dev_mu);
+    for (hipEvent_t e : ivf->ev_pending) {
+        (void)hipEventSynchronize(e);
+        ivf->ev_free.push_back(e);
+    }
+    ivf->ev_pending.clear();
+}
+
 extern "C" nmn_status nmn_ivf_destroy(nmn_ivf* ivf) {
     if (!ivf) return NMN_OK;
     (void)hipSetDevice(ivf->device);
+    ivf_wait_device_searches(ivf);
+    for (hipEvent_t e : ivf->ev_free) (void)hipEventDestroy(e);
+    for (auto& sc : ivf->dev_scratch)
+        for (nmn_ivf::Grow* g : {&sc->qpad, &sc->qinfo, &sc->qstate, &sc->cscores, &sc->ckeys, &sc->probe_rows, &sc->probe_scores,
+                                 &sc->probe_rank, &sc->probe_count, &sc->segs, &sc->base, &sc->totals, &sc->scores, &sc->keys, &sc->tables,
+                                 &sc->qwords})
+            if (g->p) (void)hipFree(g->p);
+    if (ivf->dev_perm) (void)hipFree(ivf->dev_perm);
+    if (ivf->dev_off) (void)hipFree(ivf->dev_off);
     if (ivf->stream) (void)hipStreamSynchronize(ivf->stream);
     for (void* p : {(void*)ivf->assign, (void*)ivf->cscores, (void*)ivf->ckeys, (void*)ivf->probe_rows,
                     (void*)ivf->probe_scores, (void*)ivf->probe_count, (void*)ivf->probe_rank, (void*)ivf->mask,
@@ -530,6 +570,10 @@ extern "C" nmn_status nmn_ivf_add(nmn_ivf* ivf, const float* rows_host, uint64_t
     if (!ivf || (n && !rows_host)) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
     if (n == 0) return NMN_OK;
     std::unique_lock<std::shared_mutex> g(ivf->rw);
+    // a device search answers for the index as it was when it was enqueued: let those in flight finish before anything they
+    // read changes (the codes' re-layout rewrites lcodes in place), and have the next one rebuild its id map
+    ivf_wait_device_searches(ivf);
+    ivf->gen++;
     if (ivf->kind != NMN_IVF_FLAT) return codec_add(ivf, rows_host, n, clusters_out);
     const uint64_t row0 = ivf->vectors->rows;
     nmn_status st = nmn_index_upload(ivf->vectors, rows_host, row0, n);  // ids = insertion order (ivf.rs:287-289)
@@ -1665,6 +1709,425 @@ static nmn_status codec_search(nmn_ivf* ivf, const float* queries, uint32_t nq, 
     return NMN_OK;
 }
 
+// ---- nmn_ivf_search_device: the whole search in stream order (docs/ivf.md §3.10c) ----------------------------------------------
+// One pipeline for every storage, nothing read back: centroid ranking (as above) -> ivf_plan_kernel (the probed lists of each
+// query as segments of its candidates, from the device list offsets) -> a scan writing the negated distance of every candidate
+// in candidate order (Flat: launch_ivf_flat_scan, exact f32; PQ / Binary: the codec scans) -> ivf_select_kernel (k <= 4096: the
+// k best by (score desc, candidate asc) = the reference's stable sort, one workgroup per query) or the large-k sort -> ivf_idmap_kernel
+// (candidate -> list-major row -> id, distance = -score).  Per query the scores take a slot of `bound` = the rows of the np
+// largest lists, which the host knows, so every grid and buffer is sized without looking at the probe orders.
+namespace {
+
+constexpr uint32_t kSelMax = 4096;  // ivf_select_kernel's LDS list
+
+// query blockIdx.x: segs[q * np + i] = {list, first row, rows, first candidate} of its i-th probed list (empty past the probe
+// count), totals[q] = its candidates, base[q] = q * stride (where its scores start)
+__global__ __launch_bounds__(64) void ivf_plan_kernel(const uint64_t* __restrict__ probe_rows, uint32_t pstride,
+                                                      const uint32_t* __restrict__ probe_count, uint32_t np, uint32_t n_clusters,
+                                                      const uint32_t* __restrict__ off, uint64_t stride, uint4* __restrict__ segs,
+                                                      uint64_t* __restrict__ totals, uint64_t* __restrict__ base) {
+    const uint32_t q = blockIdx.x, lane = threadIdx.x;
+    const uint32_t cnt = min(probe_count[q], np);
+    uint32_t run = 0;
+    for (uint32_t i0 = 0; i0 < np; i0 += 64) {
+        const uint32_t i = i0 + lane;
+        uint32_t list = 0, start = 0, count = 0;
+        if (i < cnt) {
+            const uint64_t c = probe_rows[(size_t)q * pstride + i];
+            if (c < n_clusters) {
+                list = (uint32_t)c;
+                start = off[c];
+                count = off[c + 1] - start;
+            }
+        }
+        uint32_t x = count;  // inclusive prefix over the wave = candidates up to and including probe i
+        for (uint32_t o = 1; o < 64; o <<= 1) {
+            const uint32_t y = __shfl_up(x, o);
+            if (lane >= o) x += y;
+        }
+        if (i < np) segs[(size_t)q * np + i] = make_uint4(list, start, count, run + x - count);
+        run += __shfl(x, 63);
+    }
+    if (lane == 0) {
+        totals[q] = run;
+        base[q] = (uint64_t)q * stride;
+    }
+}
+
+// the k best candidates of query blockIdx.x (k <= kSelMax): composite keys (score key << 32 | ~candidate) — descending composite
+// = score descending, candidate ascending.  A radix select (8 bits a pass, histograms in LDS) finds the key T of the k-th; every
+// key above T and the first (in candidate order) of those equal to it go to LDS, a bitonic sort orders them.  Writes the
+// candidate index and the score; ivf_idmap_kernel turns them into ids and distances.
+__global__ __launch_bounds__(1024) void ivf_select_kernel(const uint32_t* __restrict__ scores, uint64_t stride,
+                                                          const uint64_t* __restrict__ totals, uint32_t k, uint64_t* __restrict__ out_cand,
+                                                          float* __restrict__ out_score) {
+    __shared__ uint64_t sel[kSelMax];
+    __shared__ uint32_t hist[256];
+    __shared__ uint32_t wsum[16];
+    __shared__ uint32_t sh[4];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, q = blockIdx.x;
+    const uint64_t total = totals[q];
+    const uint32_t need = (uint32_t)min<uint64_t>(k, total);
+    if (need == 0) return;
+    const uint32_t* sc = scores + (uint64_t)q * stride;
+    auto composite = [](uint32_t key, uint64_t i) { return ((uint64_t)key << 32) | (uint32_t)~(uint32_t)i; };
+    uint32_t n_sort = need;
+    if (total <= kSelMax) {  // everything fits: sort it all
+        n_sort = (uint32_t)total;
+        for (uint32_t i = tid; i < n_sort; i += 1024) sel[i] = composite(bits_to_key(sc[i]), i);
+    } else {
+        uint32_t prefix = 0, pmask = 0, r = need - 1;  // r: descending rank of the k-th among the keys matching prefix
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            for (uint32_t b = tid; b < 256; b += 1024) hist[b] = 0;
+            __syncthreads();
+            for (uint64_t i = tid; i < total; i += 1024) {
+                const uint32_t key = bits_to_key(sc[i]);
+                if ((key & pmask) == prefix) atomicAdd(&hist[(key >> shift) & 0xFFu], 1u);
+            }
+            __syncthreads();
+            if (tid == 0) {
+                uint32_t b = 255, above = 0;
+                while (above + hist[b] <= r) above += hist[b--];
+                sh[0] = b;
+                sh[1] = r - above;
+            }
+            __syncthreads();
+            prefix |= sh[0] << shift;
+            pmask |= 0xFFu << shift;
+            r = sh[1];
+            __syncthreads();
+        }
+        const uint32_t T = prefix, take_eq = r + 1, n_gt = need - take_eq;
+        if (tid == 0) {
+            sh[2] = 0;  // keys above T placed
+            sh[3] = 0;  // keys equal to T seen, in candidate order
+        }
+        __syncthreads();
+        for (uint64_t i0 = 0; i0 < total; i0 += 1024) {
+            const uint64_t i = i0 + tid;
+            const uint32_t key = i < total ? bits_to_key(sc[i]) : 0u;
+            if (key > T) sel[atomicAdd(&sh[2], 1u)] = composite(key, i);  // (exactly n_gt of them in all)
+            const bool eq = i < total && key == T;
+            const uint64_t bal = __ballot(eq);
+            if (lane == 0) wsum[wave] = (uint32_t)__popcll(bal);
+            __syncthreads();
+            uint32_t before = sh[3];
+            for (uint32_t w = 0; w < wave; w++) before += wsum[w];
+            if (eq) {
+                const uint32_t rank = before + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+                if (rank < take_eq) sel[n_gt + rank] = composite(key, i);
+            }
+            __syncthreads();
+            if (tid == 0) {
+                uint32_t t = 0;
+                for (uint32_t w = 0; w < 16; w++) t += wsum[w];
+                sh[3] += t;
+            }
+            __syncthreads();
+        }
+    }
+    uint32_t np2 = 1;
+    while (np2 < n_sort) np2 <<= 1;
+    for (uint32_t i = n_sort + tid; i < np2; i += 1024) sel[i] = 0;  // (sorts last)
+    __syncthreads();
+    for (uint32_t size = 2; size <= np2; size <<= 1) {
+        for (uint32_t stride2 = size >> 1; stride2 > 0; stride2 >>= 1) {
+            for (uint32_t p = tid; p < (np2 >> 1); p += 1024) {
+                const uint32_t lo = ((p & ~(stride2 - 1)) << 1) | (p & (stride2 - 1));
+                const uint32_t hi = lo + stride2;
+                const bool desc = (lo & size) == 0;
+                const uint64_t a = sel[lo], b = sel[hi];
+                if ((a < b) == desc) {
+                    sel[lo] = b;
+                    sel[hi] = a;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    out_cand += (size_t)q * k;
+    out_score += (size_t)q * k;
+    for (uint32_t i = tid; i < need; i += 1024) {
+        out_cand[i] = (uint32_t)~(uint32_t)sel[i];
+        out_score[i] = key_to_score((uint32_t)(sel[i] >> 32));
+    }
+}
+
+// candidates [totals[q], stride) of query blockIdx.y take no part in the large-k sort
+__global__ __launch_bounds__(256) void ivf_pad_kernel(uint32_t* __restrict__ scores, uint64_t stride, const uint64_t* __restrict__ totals) {
+    const uint32_t q = blockIdx.y;
+    for (uint64_t i = totals[q] + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < stride; i += (uint64_t)gridDim.x * blockDim.x)
+        scores[(uint64_t)q * stride + i] = kScoreSentinelBits;
+}
+
+// slots [0, k) of query blockIdx.y: candidate j (as selected) -> its segment (the last one starting at or before j that holds
+// rows) -> list-major row -> id; distance = -score (Flat: as the host call negates its list scans' scores; PQ / Binary: 0 - score,
+// as codec_search does); the rest id UINT64_MAX, distance +inf.  totals == nullptr: nothing found (empty index, nprobe 0).
+__global__ __launch_bounds__(256) void ivf_idmap_kernel(const uint4* __restrict__ segs, uint32_t np, const uint64_t* __restrict__ totals,
+                                                        const uint32_t* __restrict__ perm, uint64_t id_base, int flat, uint32_t k,
+                                                        uint64_t* __restrict__ ids, float* __restrict__ dist, uint32_t* __restrict__ counts) {
+    const uint32_t q = blockIdx.y;
+    const uint32_t cnt = totals ? (uint32_t)min<uint64_t>(k, totals[q]) : 0u;
+    ids += (size_t)q * k;
+    dist += (size_t)q * k;
+    const uint4* sq = segs ? segs + (size_t)q * np : nullptr;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < k; i += gridDim.x * blockDim.x) {
+        if (i < cnt) {
+            const uint32_t cand = (uint32_t)ids[i];
+            const float s = dist[i];
+            uint32_t lo = 0, hi = np;
+            while (hi - lo > 1) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (sq[mid].w <= cand) lo = mid;
+                else hi = mid;
+            }
+            while (sq[lo].z == 0 || cand - sq[lo].w >= sq[lo].z) lo--;  // (never below 0: cand < total)
+            ids[i] = id_base + perm[sq[lo].y + (cand - sq[lo].w)];
+            dist[i] = flat ? -s : 0.0f - s;
+        } else {
+            ids[i] = UINT64_MAX;
+            dist[i] = __builtin_inff();
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) counts[q] = cnt;
+}
+
+// grow-only scratch of one stream's device searches: a buffer that must grow waits for the stream first (the calls before
+// this one may still read it) — the only wait of the pipeline, never in steady state
+struct DevGrow {
+    hipStream_t s;
+    bool synced = false;
+    hipError_t e = hipSuccess;
+    void operator()(nmn_ivf::Grow& g, size_t bytes) {
+        bytes = std::max<size_t>(bytes, 64);
+        if (e != hipSuccess || g.cap >= bytes) return;
+        if (!synced) {
+            e = hipStreamSynchronize(s);
+            synced = true;
+            if (e != hipSuccess) return;
+        }
+        if (g.p) (void)hipFree(g.p);
+        g.p = nullptr;
+        g.cap = 0;
+        e = hipMalloc(&g.p, bytes);
+        if (e == hipSuccess) g.cap = bytes;
+    }
+};
+
+// the candidate-order id map and list offsets of the current index state on the device (caller holds rw shared and dev_mu)
+nmn_status dev_map_build(nmn_ivf* ivf, hipStream_t s) {
+    const bool flat = ivf->kind == NMN_IVF_FLAT;
+    const uint64_t n = flat ? ivf->vectors->rows : ivf->n_coded;
+    const uint32_t C = ivf->n_clusters;
+    std::vector<uint32_t> off((size_t)C + 1, 0u), perm_flat;
+    const uint32_t* perm = ivf->perm_host.data();
+    if (flat) {  // every vector by list, ids ascending inside a list: list-major rows, then the younger ones of the same list
+        if (ivf->assign_host.size() < n) return set_error(NMN_ERR_STORAGE, "IVF lists are not current");
+        for (uint64_t r = 0; r < n; r++) off[ivf->assign_host[r] + 1]++;
+        for (uint32_t c = 0; c < C; c++) off[c + 1] += off[c];
+        perm_flat.resize(n);
+        std::vector<uint32_t> cur(off.begin(), off.end() - 1);
+        for (uint64_t r = 0; r < n; r++) perm_flat[cur[ivf->assign_host[r]]++] = (uint32_t)r;
+        perm = perm_flat.data();
+    } else {  // the list-major codes' own layout (codec_layout)
+        if (ivf->list_off_host.size() != (size_t)C + 1 || ivf->perm_host.size() < n) return set_error(NMN_ERR_STORAGE, "IVF lists are not current");
+        off.assign(ivf->list_off_host.begin(), ivf->list_off_host.end());
+    }
+    // (the searches that read the previous map have finished: `add` waited for them before it changed the index)
+    if (ivf->dev_perm) (void)hipFree(ivf->dev_perm);
+    if (ivf->dev_off) (void)hipFree(ivf->dev_off);
+    ivf->dev_perm = nullptr;
+    ivf->dev_off = nullptr;
+    ivf->dev_gen = ~0ull;
+    IVF_TRY(hipMalloc(reinterpret_cast<void**>(&ivf->dev_perm), std::max<uint64_t>(n, 1) * 4));
+    IVF_TRY(hipMalloc(reinterpret_cast<void**>(&ivf->dev_off), ((size_t)C + 1) * 4));
+    if (n) IVF_TRY(hipMemcpyAsync(ivf->dev_perm, perm, n * 4, hipMemcpyHostToDevice, s));
+    IVF_TRY(hipMemcpyAsync(ivf->dev_off, off.data(), ((size_t)C + 1) * 4, hipMemcpyHostToDevice, s));
+    IVF_TRY(hipStreamSynchronize(s));  // (the host arrays go out of scope)
+    std::vector<uint64_t> sizes(C);
+    for (uint32_t c = 0; c < C; c++) sizes[c] = off[c + 1] - off[c];
+    std::sort(sizes.begin(), sizes.end(), std::greater<uint64_t>());
+    ivf->dev_top.assign((size_t)C + 1, 0);
+    for (uint32_t c = 0; c < C; c++) ivf->dev_top[c + 1] = ivf->dev_top[c] + sizes[c];
+    ivf->dev_rows = n;
+    ivf->dev_gen = ivf->gen;
+    return NMN_OK;
+}
+
+}  // namespace
+
+extern "C" nmn_status nmn_ivf_search_device(nmn_ivf* ivf, const float* queries_dev, uint32_t nq, uint32_t k, uint32_t nprobe,
+                                            uint64_t* out_ids_dev, float* out_distances_dev, uint32_t* out_counts_dev, void* stream) {
+    if (!ivf || !queries_dev || !out_ids_dev || !out_distances_dev || !out_counts_dev)
+        return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (k == 0) return set_error(NMN_ERR_INVALID_TOP_K, "k == 0");
+    if (nq == 0) return NMN_OK;
+    std::shared_lock<std::shared_mutex> g(ivf->rw);  // concurrent with other searches, not with add / build
+    IVF_TRY(hipSetDevice(ivf->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool flat = ivf->kind == NMN_IVF_FLAT;
+    const uint64_t n = flat ? ivf->vectors->rows : ivf->n_coded;
+    const uint32_t C = ivf->n_clusters, dim = ivf->dim;
+    const uint32_t np = std::min<uint32_t>(nprobe, C);  // ivf.rs:339
+    const bool empty = n == 0 || np == 0;
+    nmn_ivf::DevScratch* sc = nullptr;
+    const uint32_t* perm = nullptr;
+    const uint32_t* off = nullptr;
+    uint64_t bound = 0, max_list = 0;
+    {
+        std::lock_guard<std::mutex> lk(ivf->dev_mu);
+        if (!empty && ivf->dev_gen != ivf->gen) {
+            nmn_status st = dev_map_build(ivf, s);
+            if (st != NMN_OK) return st;
+        }
+        for (auto& x : ivf->dev_scratch)
+            if (x->stream == s) sc = x.get();
+        if (!sc) {
+            ivf->dev_scratch.push_back(std::make_unique<nmn_ivf::DevScratch>());
+            sc = ivf->dev_scratch.back().get();
+            sc->stream = s;
+        }
+        perm = ivf->dev_perm;
+        off = ivf->dev_off;
+        if (!empty) {
+            bound = std::max<uint64_t>(ivf->dev_top[np], 1);
+            max_list = ivf->dev_top[1];
+        }
+    }
+    std::lock_guard<std::mutex> slk(sc->mu);
+    const uint64_t id_base = flat ? ivf->vectors->row_base : ivf->row_base;
+    auto record = [&]() -> nmn_status {  // the event add / destroy wait for
+        std::lock_guard<std::mutex> lk(ivf->dev_mu);
+        for (size_t i = 0; i < ivf->ev_pending.size();) {  // recycle the completed ones (a query, not a wait)
+            if (hipEventQuery(ivf->ev_pending[i]) == hipSuccess) {
+                ivf->ev_free.push_back(ivf->ev_pending[i]);
+                ivf->ev_pending[i] = ivf->ev_pending.back();
+                ivf->ev_pending.pop_back();
+            } else {
+                i++;
+            }
+        }
+        hipEvent_t e = nullptr;
+        if (!ivf->ev_free.empty()) {
+            e = ivf->ev_free.back();
+            ivf->ev_free.pop_back();
+        } else {
+            IVF_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        }
+        const hipError_t he = hipEventRecord(e, s);
+        if (he != hipSuccess) {
+            ivf->ev_free.push_back(e);
+            return set_error_hip(he, "nmn_ivf_search_device");
+        }
+        ivf->ev_pending.push_back(e);
+        return NMN_OK;
+    };
+    if (empty) {  // unused slots and zero counts, on the stream
+        hipLaunchKernelGGL(ivf_idmap_kernel, dim3((uint32_t)std::min<uint64_t>(((uint64_t)k + 255) / 256, 4096), nq), dim3(256), 0, s, nullptr, 0u,
+                           nullptr, nullptr, 0ull, 0, k, out_ids_dev, out_distances_dev, out_counts_dev);
+        IVF_TRY(hipGetLastError());
+        return record();
+    }
+    if (codec_seg_bytes() != sizeof(uint4)) return set_error(NMN_ERR_STORAGE, "IVF: segment layout mismatch");
+    const uint32_t ld = ivf->centroids->ld;
+    const size_t c_pad = ivf->centroids->cap_pad;
+    const bool big_c = C > kRankMax;  // (the large-k sort ranks the centroids, one query at a time)
+    constexpr uint64_t kScoreBudget = 64ull << 20;  // candidates' scores per chunk (256 MiB)
+    uint32_t chunk = big_c ? 1u : std::min<uint32_t>(nq, 64);
+    chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(chunk, kScoreBudget / bound));
+    const uint32_t Kt = std::min<uint32_t>(ivf->pq_k, 256), W = (dim + 63) / 64;
+    DevGrow grow_s{s};
+    grow_s(sc->qpad, (size_t)ld * chunk * 4);
+    grow_s(sc->qinfo, sizeof(QInfo) * chunk);
+    grow_s(sc->qstate, sizeof(QState) * chunk);
+    grow_s(sc->cscores, c_pad * chunk * 4);
+    grow_s(sc->probe_rows, (size_t)C * chunk * 8);
+    grow_s(sc->probe_rank, (size_t)C * chunk * 4);
+    grow_s(sc->probe_count, (size_t)chunk * 8);
+    if (big_c) {
+        grow_s(sc->ckeys, largek_sort_len(C) * 8);
+        grow_s(sc->probe_scores, (size_t)C * 4);
+    }
+    grow_s(sc->segs, (size_t)chunk * np * sizeof(uint4));
+    grow_s(sc->base, (size_t)chunk * 8);
+    grow_s(sc->totals, (size_t)chunk * 8);
+    grow_s(sc->scores, (size_t)chunk * bound * 4);
+    if (k > kSelMax) grow_s(sc->keys, largek_sort_len(bound) * 8);
+    if (ivf->kind == NMN_IVF_PQ) grow_s(sc->tables, (size_t)chunk * np * ivf->pq_m * Kt * 4);
+    if (ivf->kind == NMN_IVF_BINARY) grow_s(sc->qwords, (size_t)chunk * W * 8);
+    if (grow_s.e != hipSuccess) return set_error_hip(grow_s.e, "nmn_ivf_search_device (scratch)");
+    const bool raw_q = ld == dim && C < (1u << 16);  // (as the host call: the raw queries ARE the padded ones)
+    if (raw_q && grow_s.synced) IVF_TRY(hipMemsetAsync(sc->qinfo.p, 0, sc->qinfo.cap, s));  // (fresh buffer: exact_scan reads qmag)
+    auto* segs = gp<uint4>(sc->segs);
+    for (uint32_t q0 = 0; q0 < nq; q0 += chunk) {
+        const uint32_t nb = std::min<uint32_t>(chunk, nq - q0);
+        const float* qg = queries_dev + (size_t)q0 * dim;
+        uint64_t* o_ids = out_ids_dev + (size_t)q0 * k;
+        float* o_dist = out_distances_dev + (size_t)q0 * k;
+        uint32_t* o_cnt = out_counts_dev + q0;
+        // 1. centroid ranking, exactly the host call's
+        if (!raw_q)
+            IVF_TRY(launch_qprep(qg, nb, dim, ld, kMetricNegL2Sq, ivf->centroids->max_norm_bits, gp<float>(sc->qpad), gp<QInfo>(sc->qinfo),
+                                 gp<QState>(sc->qstate), 0, s));
+        ExactScanParams ep{};
+        ep.corpus = ivf->centroids->corpus;
+        ep.norms = ivf->centroids->norms;
+        ep.qpad = raw_q ? qg : gp<float>(sc->qpad);
+        ep.qinfo = gp<QInfo>(sc->qinfo);
+        ep.scores = gp<uint32_t>(sc->cscores);
+        ep.n_rows = C;
+        ep.nql = nb;
+        ep.ld = ld;
+        ep.dim = dim;
+        ep.nq = nb;
+        ep.metric = kMetricNegL2Sq;
+        IVF_TRY(launch_exact_scan(ep, s));
+        if (!big_c) {
+            uint32_t np2 = 2;
+            while (np2 < C) np2 <<= 1;
+            hipLaunchKernelGGL(ivf_rank_kernel, dim3(nb), dim3(1024), 0, s, gp<uint32_t>(sc->cscores), nb, C, np2, np,
+                               gp<uint64_t>(sc->probe_rows), gp<uint32_t>(sc->probe_count), gp<uint32_t>(sc->probe_rank));
+        } else {
+            IVF_TRY(launch_largek(gp<uint32_t>(sc->cscores), C, gp<uint64_t>(sc->ckeys), np, 0, gp<uint64_t>(sc->probe_rows),
+                                  gp<float>(sc->probe_scores), gp<uint32_t>(sc->probe_count), s));
+        }
+        // 2. candidate plan
+        hipLaunchKernelGGL(ivf_plan_kernel, dim3(nb), dim3(64), 0, s, gp<uint64_t>(sc->probe_rows), C, gp<uint32_t>(sc->probe_count), np, C,
+                           off, bound, segs, gp<uint64_t>(sc->totals), gp<uint64_t>(sc->base));
+        IVF_TRY(hipGetLastError());
+        // 3. scores of every candidate, in candidate order
+        if (flat) {
+            IVF_TRY(launch_ivf_flat_scan(qg, dim, ivf->vectors->corpus, ivf->vectors->ld, perm, segs, np, nb, (uint32_t)max_list,
+                                         gp<uint64_t>(sc->base), gp<uint32_t>(sc->scores), s));
+        } else if (ivf->kind == NMN_IVF_PQ) {
+            IVF_TRY(launch_pq_search(qg, dim, ivf->centroids->corpus, ld, segs, np, nb, (uint32_t)max_list, ivf->codebook, ivf->pq_k,
+                                     ivf->pq_m, ivf->lcodes, gp<float>(sc->tables), gp<uint64_t>(sc->base), gp<uint32_t>(sc->scores), s));
+        } else {
+            IVF_TRY(launch_bq_quantize(qg, dim, nb, dim, ivf->bq_method, gp<uint64_t>(sc->qwords), s));
+            IVF_TRY(launch_bq_search(gp<uint64_t>(sc->qwords), dim, segs, np, nb, (uint32_t)max_list,
+                                     reinterpret_cast<const uint64_t*>(ivf->lcodes), gp<uint64_t>(sc->base), gp<uint32_t>(sc->scores), s));
+        }
+        // 4. selection: (score desc, candidate asc)
+        if (k <= kSelMax) {
+            hipLaunchKernelGGL(ivf_select_kernel, dim3(nb), dim3(1024), 0, s, gp<uint32_t>(sc->scores), bound, gp<uint64_t>(sc->totals), k,
+                               o_ids, o_dist);
+            IVF_TRY(hipGetLastError());
+        } else {
+            const uint32_t pad_blocks = (uint32_t)std::min<uint64_t>((bound + 255) / 256, 1024);
+            hipLaunchKernelGGL(ivf_pad_kernel, dim3(pad_blocks, nb), dim3(256), 0, s, gp<uint32_t>(sc->scores), bound, gp<uint64_t>(sc->totals));
+            IVF_TRY(hipGetLastError());
+            for (uint32_t b = 0; b < nb; b++)
+                IVF_TRY(launch_largek(gp<uint32_t>(sc->scores) + (size_t)b * bound, bound, gp<uint64_t>(sc->keys), k, 0, o_ids + (size_t)b * k,
+                                      o_dist + (size_t)b * k, o_cnt + b, s));
+        }
+        // 5. ids, distances, counts
+        hipLaunchKernelGGL(ivf_idmap_kernel, dim3((uint32_t)std::min<uint64_t>(((uint64_t)k + 255) / 256, 4096), nb), dim3(256), 0, s, segs, np,
+                           gp<uint64_t>(sc->totals), perm, id_base, flat ? 1 : 0, k, o_ids, o_dist, o_cnt);
+        IVF_TRY(hipGetLastError());
+    }
+    return record();
+}
+
 extern "C" int32_t nmn_ivf_storage_kind(const nmn_ivf* ivf) { return ivf ? ivf->kind : NMN_IVF_FLAT; }
 extern "C" uint32_t nmn_ivf_pq_codewords(const nmn_ivf* ivf) { return (ivf && ivf->kind == NMN_IVF_PQ) ? ivf->pq_k : 0; }
 
@@ -1703,6 +2166,15 @@ extern "C" uint64_t nmn_ivf_hbm_bytes(nmn_ivf* ivf) {
             b += gr->cap;
     }
     b += ivf->cscores_cap * 4 + largek_sort_len(ivf->n_clusters) * 8;  // the assignment sweep's scores, the ranking's sort buffer
+    {   // what device searches added: the candidate-order id map and the per-stream scratch (nothing before the first one)
+        std::lock_guard<std::mutex> lk(ivf->dev_mu);
+        if (ivf->dev_perm) b += std::max<uint64_t>(ivf->dev_rows, 1) * 4 + ((uint64_t)ivf->n_clusters + 1) * 4;
+        for (auto& sc : ivf->dev_scratch)
+            for (const nmn_ivf::Grow* gr : {&sc->qpad, &sc->qinfo, &sc->qstate, &sc->cscores, &sc->ckeys, &sc->probe_rows, &sc->probe_scores,
+                                            &sc->probe_rank, &sc->probe_count, &sc->segs, &sc->base, &sc->totals, &sc->scores, &sc->keys,
+                                            &sc->tables, &sc->qwords})
+                b += gr->cap;
+    }
     return b;
 }
 

@@ -10,6 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
+from .flat_index import _stream_ptr
 
 
 class GpuIvfFlat:
@@ -125,6 +126,39 @@ class GpuIvfFlat:
                                              C.c_void_p(counts.ctypes.data), None))
         return ids, dist, counts
 
+    def search_device(self, queries_t, k, nprobe=None, out=None, stream=None):
+        """`search` with torch device tensors, in stream order (nmn_ivf_search_device): enqueued on `stream` (None: torch's
+        current stream), returns without waiting.  queries_t: [nq, dim] f32 on the index's device.  Returns (ids int64 [nq,k]
+        holding the u64 bit pattern, -1 = unused slot; distances f32 [nq,k]; counts int32 [nq]), allocated on the queries'
+        device unless `out` supplies them — the same answer `search` gives for the index as it is when the call returns."""
+        import torch
+
+        if not (isinstance(queries_t, torch.Tensor) and queries_t.is_cuda):
+            raise _capi.NeumannGpuError(_capi.ERR_INVALID_ARGUMENT, "queries must be a device tensor")
+        if queries_t.dtype != torch.float32 or not queries_t.is_contiguous():
+            raise _capi.NeumannGpuError(_capi.ERR_INVALID_ARGUMENT, "queries must be contiguous float32")
+        if queries_t.dim() == 1:
+            queries_t = queries_t[None, :]
+        nq, k = queries_t.shape[0], int(k)
+        if queries_t.shape[1] != self.dim:
+            raise _capi.NeumannGpuError(_capi.ERR_DIMENSION_MISMATCH, f"expected {self.dim}")
+        if out is None:
+            kk = max(k, 1)
+            ids = torch.empty((nq, kk), dtype=torch.int64, device=queries_t.device)
+            dist = torch.empty((nq, kk), dtype=torch.float32, device=queries_t.device)
+            counts = torch.empty((nq,), dtype=torch.int32, device=queries_t.device)
+        else:
+            ids, dist, counts = out
+        _capi.check(self._lib.nmn_ivf_search_device(
+            self._h, C.c_void_p(queries_t.data_ptr()), nq, k, self.nprobe if nprobe is None else int(nprobe),
+            C.c_void_p(ids.data_ptr()), C.c_void_p(dist.data_ptr()), C.c_void_p(counts.data_ptr()), _stream_ptr(stream)))
+        return ids, dist, counts
+
+    @property
+    def hbm_bytes(self):
+        """device memory the index holds right now (vectors or codes, centroids, codebook, search scratch)"""
+        return int(self._lib.nmn_ivf_hbm_bytes(self._h))
+
 
 def _kmeans_options(max_iterations=100, convergence_threshold=1e-4, seed=42, init_method="kmeans++"):
     return _capi.KMeansOptions(max_iterations=int(max_iterations), convergence_threshold=float(convergence_threshold),
@@ -179,12 +213,6 @@ class _GpuIvfCoded(GpuIvfFlat):
     @property
     def storage_kind(self):
         return int(self._lib.nmn_ivf_storage_kind(self._h))
-
-    @property
-    def hbm_bytes(self):
-        """device memory the index holds right now (codes, centroids, codebook, search scratch)"""
-        return int(self._lib.nmn_ivf_hbm_bytes(self._h))
-
 
 class GpuIvfPQ(_GpuIvfCoded):
     """IVFIndex with IVFStorage::PQ (ivf.rs:222-406, pq.rs:114-430): M bytes of codes per vector, residuals against the
