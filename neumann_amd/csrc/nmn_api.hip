@@ -495,7 +495,7 @@ extern "C" nmn_status nmn_index_create(const nmn_index_desc* d, nmn_index** out)
         return cleanup(fail_hip(e, "hipMalloc(norms)"));
     if ((e = hipMalloc(reinterpret_cast<void**>(&idx->inv_norms), idx->cap_pad * sizeof(float))) != hipSuccess)
         return cleanup(fail_hip(e, "hipMalloc(inv_norms)"));
-    if ((e = hipMalloc(reinterpret_cast<void**>(&idx->max_norm_bits), 4)) != hipSuccess)
+    if ((e = hipMalloc(reinterpret_cast<void**>(&idx->max_norm_bits), 8)) != hipSuccess)
         return cleanup(fail_hip(e, "hipMalloc(max_norm)"));
     if ((e = hipStreamCreateWithFlags(&idx->host_stream, hipStreamNonBlocking)) != hipSuccess)
         return cleanup(fail_hip(e, "hipStreamCreate"));
@@ -503,6 +503,7 @@ extern "C" nmn_status nmn_index_create(const nmn_index_desc* d, nmn_index** out)
         (e = hipMemsetAsync(idx->norms, 0, idx->cap_pad * sizeof(float), idx->host_stream)) != hipSuccess ||
         (e = hipMemsetAsync(idx->inv_norms, 0, idx->cap_pad * sizeof(float), idx->host_stream)) != hipSuccess ||
         (e = hipMemsetAsync(idx->max_norm_bits, 0, 4, idx->host_stream)) != hipSuccess ||
+        (e = hipMemsetAsync(idx->max_norm_bits + 1, 0xFF, 4, idx->host_stream)) != hipSuccess ||
         (e = hipStreamSynchronize(idx->host_stream)) != hipSuccess)
         return cleanup(fail_hip(e, "memset"));
     *out = idx;
@@ -737,6 +738,9 @@ static nmn_status rows_written(nmn_index* idx, uint64_t row0, uint64_t n, hipStr
     static const bool no_ingest = env_set("NMN_NO_INGEST");  // measurement knob: the separate passes of rounds 1-3
     const bool bulk = n >= 4096 && row0 == 0;
     const bool q8_first = ingest_wants_q8(idx);
+    // the smallest nonzero |x| of the new rows joins the shard's (max_norm_bits[1]: qprep_kernel's underflow guard).  Only ever
+    // lowered — an overwritten row keeps its old elements' say, which can only send queries to the exact path
+    HIP_TRY(launch_minabs(idx->corpus, idx->ld, idx->dim, row0, n, idx->max_norm_bits + 1, stream));
     if (bulk && q8_first && !idx->q8) {
         nmn_status st = q8_alloc(idx, stream);
         if (st != NMN_OK) return st;

@@ -195,6 +195,33 @@ __device__ __forceinline__ float exact_score(const float* __restrict__ q, const 
     return div_rn(dot, mul_rn(qmag, vmag));
 }
 
+// ---- the smallest nonzero |x| of uploaded rows (the underflow guard, docs/exactness.md §4a) --------------------------------
+// |x| as bits: zeros are skipped; inf and NaN order above every finite value, so they never lower the minimum.
+__global__ void __launch_bounds__(256) minabs_kernel(const float* __restrict__ corpus, uint32_t ld, uint32_t dim, uint64_t row0,
+                                                     uint64_t n, uint32_t* __restrict__ min_abs_bits) {
+    uint32_t m = 0xFFFFFFFFu;
+    for (uint64_t i = blockIdx.x; i < n; i += gridDim.x) {
+        const float* v = corpus + (row0 + i) * (uint64_t)ld;
+        for (uint32_t c = threadIdx.x; c < dim; c += 256u) {
+            const uint32_t b = f2u(v[c]) & 0x7FFFFFFFu;
+            if (b != 0u) m = b < m ? b : m;
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint32_t o = (uint32_t)__shfl_xor((int)m, off);
+        m = o < m ? o : m;
+    }
+    if ((threadIdx.x & 63u) == 0u && m != 0xFFFFFFFFu) atomicMin(min_abs_bits, m);
+}
+
+hipError_t launch_minabs(const float* corpus, uint32_t ld, uint32_t dim, uint64_t row0, uint64_t n, uint32_t* min_abs_bits,
+                         hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    const uint64_t blocks = n < 4096u ? n : 4096u;
+    hipLaunchKernelGGL(minabs_kernel, dim3((unsigned)blocks), dim3(256), 0, s, corpus, ld, dim, row0, n, min_abs_bits);
+    return hipGetLastError();
+}
+
 // ---- |v| for uploaded rows -------------------------------------------------------------------
 __global__ void __launch_bounds__(256) norms_kernel(const float* __restrict__ corpus, uint32_t ld, uint32_t dim,
                                                     uint64_t row0, uint64_t n, float* __restrict__ norms,
@@ -283,6 +310,16 @@ __global__ void __launch_bounds__(64) qprep_kernel(const float* __restrict__ que
         for (uint32_t i = threadIdx.x; i < (ld >> 2); i += 64) dst4[i] = reinterpret_cast<const qv4*>(src)[i];
     }
     const float ss = dot8_group<32>(src, src, dim, threadIdx.x & 7u);
+    // the smallest nonzero |q_i| (bits; all ones for the zero query): the underflow guard below
+    uint32_t qmin = 0xFFFFFFFFu;
+    for (uint32_t i = threadIdx.x; i < dim; i += 64) {
+        const uint32_t b = f2u(src[i]) & 0x7FFFFFFFu;
+        if (b != 0u) qmin = b < qmin ? b : qmin;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint32_t o = (uint32_t)__shfl_xor((int)qmin, off);
+        qmin = o < qmin ? o : qmin;
+    }
     // MFMA sweep: the stationary copy of this query is bf16 — its rounding error |q - bf16(q)| goes into the margin
     float qerr2 = 0.0f;
     float qscale = 0.0f, qq8 = 0.0f;
@@ -436,6 +473,13 @@ __global__ void __launch_bounds__(64) qprep_kernel(const float* __restrict__ que
                 else qi.pad = two_d;  // score = 1/(1+d): threshold T -> T / (1 + 2D T), applied by margin_key
             }
         }
+        // Underflow guard (docs/exactness.md §4a).  Every margin above rests on f32 arithmetic without underflow: products and
+        // squares with a relative error, error sums of e*e that do not vanish, magnitudes that are not far below the true ones.
+        // That holds when every nonzero |q_i| and |v_i| is at least 2^-50; below it (the shard's smallest nonzero |x|, recorded
+        // by minabs_kernel, or this query's) no margin is claimed at all: margin_rel = inf puts every row inside the margin
+        // (threshold -inf, or NaN = every key), and the exact path answers.  Exact zeros never trip it (they are skipped).
+        const bool underflow = u2f(qmin) < kUnderflowGuard || u2f(max_norm_bits[1]) < kUnderflowGuard;  // (all ones: NaN, false)
+        if (underflow) qi.margin_rel = __builtin_inff();
         qinfo[q] = qi;
         if (qinfo_plain) {
             // the same query for a sweep over the f32 corpus itself (the retry of a mirror pass whose margin overflowed): what
@@ -457,6 +501,7 @@ __global__ void __launch_bounds__(64) qprep_kernel(const float* __restrict__ que
                 qp.margin_abs = 0.0f;
                 qp.margin_rel = 4.0f * (dd + 8.0f) * u;
             }
+            if (underflow) qp.margin_rel = __builtin_inff();
             qinfo_plain[q] = qp;
         }
         QState st;

@@ -185,7 +185,8 @@ struct nmn_index {
     float* norms = nullptr;
     float* inv_norms = nullptr;         // 1 / |v| (0 for a zero row): what the batched cosine sweep multiplies by (one rcp per ROW at
                                         // ingest instead of one per (row, query) in every sweep's epilogue)
-    uint32_t* max_norm_bits = nullptr;
+    uint32_t* max_norm_bits = nullptr;  // [0] the largest stored |v| (bits), [1] the smallest nonzero |x| of any element ever
+                                        // written (bits, all ones while there is none): the underflow guard of qprep_kernel
     // Sweeps of a large shard never run side by side: each is HBM-bound on its own, so two at once each take twice as long and
     // every query waits for both.  A search on another stream waits (on the device) for the previous search's SWEEP — not for its
     // selection / rescore tail, which runs under the next sweep (nmn_api.hip: sweep chain).

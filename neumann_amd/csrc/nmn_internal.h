@@ -366,6 +366,11 @@ hipError_t launch_merge(const uint64_t* rows, const float* scores, const uint32_
 // exact (reference-order) kernels
 hipError_t launch_norms(const float* corpus, uint32_t ld, uint32_t dim, uint64_t row0, uint64_t n, float* norms,
                         float* inv_norms, uint32_t* max_norm_bits, hipStream_t s);
+// atomicMin of the bits of the smallest nonzero |x| among rows [row0, row0 + n) into *min_abs_bits (docs/exactness.md §4a)
+hipError_t launch_minabs(const float* corpus, uint32_t ld, uint32_t dim, uint64_t row0, uint64_t n, uint32_t* min_abs_bits,
+                         hipStream_t s);
+// elements below this magnitude void every approximate margin (docs/exactness.md §4a): 2^-50
+constexpr float kUnderflowGuard = 8.8817841970012523e-16f;
 hipError_t launch_qprep(const float* queries, uint32_t nq, uint32_t dim, uint32_t ld, int metric,
                         const uint32_t* max_norm_bits, float* qpad, QInfo* qinfo, QState* qstate, int approx_pass,
                         hipStream_t s, const uint32_t* half_err_bits = nullptr, uint32_t* qi8 = nullptr,

@@ -1314,6 +1314,9 @@ __global__ void __launch_bounds__(kSelThreads) fallback_select_kernel(FallbackPa
             p.list_count[q] = min(got, list_cap);
             if (!p.all) p.qstate[q].overflow = 3u;  // final_kernel: the list is ready
         }
+        // ... and only then may the next flagged query's run zero the counters: without this meeting a workgroup that ran ahead
+        // zeroed g_fill before workgroup 0 had read it, and a query of a multi-query pass came back with count 0
+        if (!fb_grid_barrier(p.sync, &s_target, patience, &s_abort)) return;
     }
 }
 

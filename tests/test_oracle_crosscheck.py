@@ -54,8 +54,20 @@ class ieee:
             return sign * math.inf
         return sign * float(v)
 
+    @staticmethod
+    def nonfinite(op, *xs):
+        """An operand is +-inf or NaN: IEEE-754 fixes the result without any rounding (inf + finite = inf, inf * 0 = NaN,
+        x / inf = 0, sqrt(inf) = inf ...), so binary32 arithmetic itself states it; None when every operand is finite."""
+        if all(math.isfinite(x) for x in xs):
+            return None
+        with np.errstate(all="ignore"):
+            return float(op(*(F(x) for x in xs)))
+
     @classmethod
     def add(cls, a, b):
+        r = cls.nonfinite(lambda x, y: x + y, a, b)
+        if r is not None:
+            return r
         if a == 0 and b == 0:  # signed zeros: (-0)+(-0) = -0, otherwise +0
             return -0.0 if (math.copysign(1, a) < 0 and math.copysign(1, b) < 0) else 0.0
         return cls.round(Fraction(a) + Fraction(b))
@@ -66,18 +78,29 @@ class ieee:
 
     @classmethod
     def mul(cls, a, b):
+        r = cls.nonfinite(lambda x, y: x * y, a, b)
+        if r is not None:
+            return r
         if a == 0 or b == 0:
             return math.copysign(0.0, math.copysign(1, a) * math.copysign(1, b))
         return cls.round(Fraction(a) * Fraction(b))
 
     @classmethod
     def div(cls, a, b):
+        r = cls.nonfinite(lambda x, y: x / y, a, b)
+        if r is not None:
+            return r
+        if b == 0:  # (|q| * |v| of two tiny magnitudes can underflow to 0): x / 0 = +-inf, 0 / 0 = NaN
+            return math.nan if a == 0 else math.copysign(math.inf, math.copysign(1, a) * math.copysign(1, b))
         if a == 0:
             return math.copysign(0.0, math.copysign(1, a) * math.copysign(1, b))
         return cls.round(Fraction(a) / Fraction(b))
 
     @classmethod
     def sqrt(cls, a):
+        r = cls.nonfinite(np.sqrt, a)
+        if r is not None:
+            return r
         if a == 0:
             return a
         x = Fraction(a)
@@ -193,3 +216,80 @@ def test_native_build_matches_plain_build():
         a = oc.scores_all(A, q, m, native=False)
         b = oc.scores_all(A, q, m, native=True, nthreads=4)
         assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+
+
+def _edge_rows(rng, d):
+    """(name, q, v) at the ends of the f32 range: elements whose squares and products underflow (1e-21 ... 1e-44, the
+    last subnormal themselves), the straddle row whose stored magnitude is 18.5x too small (767 x 2.5e-23 and one 4e-23),
+    rows near +-1e6 (the reference fuzz target's bound) and near 2e19, where the squares overflow and |v| is inf."""
+    out = []
+    for scale in (1e-21, 1e-23, 1e-30, 1e-44):
+        out.append((f"scale {scale:g}", (rng.standard_normal(d) * scale).astype(F), (rng.standard_normal(d) * scale).astype(F)))
+    strad = np.full(d, 2.5e-23, F)
+    strad[-1] = F(4e-23)
+    mixed = np.where(rng.random(d) < 0.5, F(2.5e-23), F(4e-23)).astype(F) * rng.choice(np.array([-1, 1], F), d)
+    out.append(("straddle x straddle", strad, strad.copy()))
+    out.append(("straddle x mixed", strad, mixed))
+    out.append(("normal x straddle", rng.standard_normal(d).astype(F), strad))
+    out.append(("+-1e6", (rng.uniform(-1e6, 1e6, d)).astype(F), (rng.uniform(-1e6, 1e6, d)).astype(F)))
+    big = (2e19 * (1.0 + 0.1 * rng.random(d))).astype(F) * rng.choice(np.array([-1, 1], F), d)
+    out.append(("2e19 x normal", rng.standard_normal(d).astype(F), big))
+    out.append(("2e19 x 2e19", big, big[::-1].copy()))
+    return out
+
+
+@pytest.mark.parametrize("d", [8, 40, 768])
+@pytest.mark.parametrize("metric", [0, 1, 2])
+def test_oracle_bit_exact_at_the_f32_range_edges(d, metric):
+    """The GPU underflow tests (tests/test_gpu_underflow.py) trust the oracle where squares and products underflow or
+    overflow: walk the same rows through the rational simulator.  A NaN must come out as a NaN (its payload is the
+    platform's; ranking puts every NaN last)."""
+    rng = np.random.default_rng(7000 + 10 * d + metric)
+    for name, q, v in _edge_rows(rng, d):
+        exp = ref_score(q, v, metric)
+        with np.errstate(all="ignore"):
+            got_c = oc.score(q, v, metric)
+            got_np = on.scores(v[None, :], q, metric)[0]
+        for got in (got_c, got_np):
+            if math.isnan(exp):
+                assert math.isnan(float(got)), (d, metric, name, float(got))
+            else:
+                assert bits(got) == bits(exp), (d, metric, name, float(got), exp)
+
+
+def test_straddle_row_magnitude_is_the_underflowed_one():
+    """The case docs/exactness.md §4, "The underflow guard", is about: the reference's |v| of 767 x 2.5e-23 + one 4e-23 is 3.74e-23 (the squares
+    6.25e-46 are subnormal), against a true 6.94e-22 — the oracle must keep the underflowed value, and the cosine of that
+    row with the all-ones query (whose products stay normal) comes out 18.5 times too large."""
+    v = np.full(768, 2.5e-23, F)
+    v[-1] = F(4e-23)
+    mag = float(oc.magnitude(v))
+    assert bits(mag) == bits(ieee.sqrt(ref_dot8([float(x) for x in v], [float(x) for x in v])))
+    assert 3.7e-23 < mag < 3.8e-23
+    ones = np.ones(768, F)
+    cos = float(oc.score(ones, v, 0))
+    assert bits(cos) == bits(ref_score(ones, v, 0)) and 18.0 < cos < 19.0
+
+
+def test_native_build_matches_plain_build_at_the_f32_range_edges():
+    """-O3 -march=native with threads keeps every bit where squares and products underflow or overflow too (no flush to
+    zero, no reassociation): a corpus of the edge rows above, whole searches and every score."""
+    rng = np.random.default_rng(77)
+    d = 96
+    rows = []
+    for _ in range(20):
+        for _, q, v in _edge_rows(rng, d):
+            rows += [q, v]
+    A = np.stack(rows + [rng.standard_normal(d).astype(F) for _ in range(200)]).astype(F)
+    rng.shuffle(A)
+    queries = [A[3], A[17], (rng.standard_normal(d) * 1e-21).astype(F), (rng.standard_normal(d) * 1e-44).astype(F),
+               rng.standard_normal(d).astype(F)]
+    with np.errstate(all="ignore"):
+        for q in queries:
+            for m in (0, 1, 2):
+                a = oc.scores_all(A, q, m, native=False)
+                b = oc.scores_all(A, q, m, native=True, nthreads=4)
+                assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), m
+                ra, sa = oc.search(A, q, 50, m)
+                rb, sb = oc.search(A, q, 50, m, nthreads=4, partial=True, native=True)
+                assert np.array_equal(ra, rb) and np.array_equal(sa.view(np.uint32), sb.view(np.uint32)), m
