@@ -252,6 +252,27 @@ nmn_status nmn_engine_ivf_cluster_sizes(nmn_engine_ivf* ivf, uint64_t* out);
 nmn_status nmn_engine_search_with_ivf(nmn_engine* e, nmn_engine_ivf* ivf, const float* q, uint64_t dim, uint64_t top_k,
                                       uint64_t nprobe, nmn_results** out);
 
+/* ---- HNSW (lib.rs:2378-2550; tensor_store/src/hnsw.rs) ------------------------------------------- */
+typedef struct nmn_engine_hnsw nmn_engine_hnsw; /* (HNSWIndex, Vec<String> key_mapping) */
+/* build_hnsw_index (lib.rs:2378-2470) with HNSWStorageStrategy::Dense (cfg->storage; Auto / Quantized: NMN_ERR_CONFIGURATION):
+ * list_keys() order, the first vector fixes the dimension, max_dimension check (DimensionMismatch{expected: max, got}), a later
+ * vector of another length DimensionMismatch{expected, got}; an empty engine gives an empty index.  cfg NULL =
+ * HNSWConfig::default (build_hnsw_index_default, 2478-2480).  The graph is nmn_hnsw_insert's (the reference's, bit for bit); the
+ * handle is a snapshot: later stores do not change it. */
+nmn_status nmn_engine_build_hnsw_index(nmn_engine* e, const nmn_hnsw_config* cfg, nmn_engine_hnsw** out);
+void nmn_engine_hnsw_free(nmn_engine_hnsw* h);
+uint64_t nmn_engine_hnsw_len(const nmn_engine_hnsw* h);
+const char* nmn_engine_hnsw_key(const nmn_engine_hnsw* h, uint64_t id);
+/* the GPU index itself (owned by h; NULL for an index built from an empty engine) */
+nmn_hnsw* nmn_engine_hnsw_index(nmn_engine_hnsw* h);
+/* search_with_hnsw (lib.rs:2516-2550): EmptyVector, InvalidTopK, index.search(query, top_k), node id -> key, ids past the
+ * mapping dropped; scores are HNSWDistanceMetric::to_similarity of the index's metric */
+nmn_status nmn_engine_search_with_hnsw(nmn_engine* e, nmn_engine_hnsw* h, const float* q, uint64_t dim, uint64_t top_k,
+                                       nmn_results** out);
+/* estimate_hnsw_memory (lib.rs:2489-2509): count x d x 4 + count x 16 x 2 x 8 + count x 32; 0 for an empty engine.  Host
+ * arithmetic, no device needed. */
+nmn_status nmn_engine_estimate_hnsw_memory(nmn_engine* e, uint64_t* out_bytes);
+
 /* ---- unified entity mode (lib.rs:3060-3237): vectors in the `_embedding` field of entity keys ---- */
 nmn_status nmn_engine_set_entity_embedding(nmn_engine* e, const char* entity_key, const float* v, uint64_t dim);
 nmn_status nmn_engine_get_entity_embedding(nmn_engine* e, const char* entity_key, float* out, uint64_t cap,

@@ -111,7 +111,8 @@ typedef struct nmn_search_stats {
 #define NMN_SWEEP_MFMA_BF16 6u  /* nmn::scan_mfma_kernel over the bf16 mirror */
 #define NMN_SWEEP_MFMA_I8 7u    /* nmn::scan_mfma_kernel over the 8-bit mirror */
 #define NMN_SWEEP_EXACT 8u      /* exact reference-order scores of every row, no approximate sweep (tiny_search_kernel, large-k path) */
-/* Name of a NMN_SWEEP_* value ("ring_f32", "valu_f32", "valu_bf16", "valu_i8", "mfma_f32", "mfma_bf16", "mfma_i8", "exact", "none"). */
+#define NMN_SWEEP_GRAPH 9u      /* not a sweep: nmn::hnsw_search_kernel walked an HNSW graph; rows_scanned = distance evaluations made */
+/* Name of a NMN_SWEEP_* value ("ring_f32", "valu_f32", "valu_bf16", "valu_i8", "mfma_f32", "mfma_bf16", "mfma_i8", "exact", "graph", "none"). */
 const char* nmn_sweep_kind_str(uint32_t sweep_kind);
 
 /* ---- device / lifecycle ------------------------------------------------------------------- */
@@ -579,6 +580,79 @@ nmn_status nmn_ivf_pq_codebook(nmn_ivf* ivf, float* out, uint64_t cap_floats);
 nmn_status nmn_ivf_codes(nmn_ivf* ivf, void* out, uint64_t cap_bytes);
 /* Device memory the index holds right now (vectors or codes, centroids, codebook, lists, search scratch). */
 uint64_t nmn_ivf_hbm_bytes(nmn_ivf* ivf);
+
+/* ---- HNSW graph index (tensor_store/src/hnsw.rs:1554-2335), searched on the GPU ------------------------------- */
+
+/* `tensor_store::HNSWIndex` with dense storage.  The graph is built on the host in the reference's order (the build is
+ * sequential by definition of its result; the reference's is too) and is resident in HBM: layer 0 as n x m0 u32 slots and a
+ * count per node, the upper layers as a compact n_upper x max_layer x m table with a row index per node.  Node id == row of
+ * the flat index the handle owns (nmn_hnsw_vectors).  Answers are the reference's bit for bit, ties included: both priority
+ * queues of search_layer are kept as the array algorithm of std::collections::BinaryHeap (docs/hnsw.md). */
+typedef struct nmn_hnsw nmn_hnsw;
+
+/* HNSWStorageStrategy (hnsw.rs): only Dense is served; the others are refused with NMN_ERR_CONFIGURATION. */
+#define NMN_HNSW_STORAGE_DENSE 0
+#define NMN_HNSW_STORAGE_AUTO 1
+#define NMN_HNSW_STORAGE_QUANTIZED 2
+
+/* HNSWConfig (hnsw.rs:1434-1463). */
+typedef struct nmn_hnsw_config {
+    uint32_t m;                /* connections per node per layer (16) */
+    uint32_t m0;               /* connections at layer 0 (2 m) */
+    uint32_t ef_construction;  /* 200 */
+    uint32_t ef_search;        /* 50 */
+    double ml;                 /* level multiplier, 1 / ln(m) */
+    uint64_t max_nodes;        /* 0 = unlimited; default 10 000 000 */
+    float sparsity_threshold;  /* carried, not acted on (dense storage only) */
+    int32_t distance_metric;   /* HNSWDistanceMetric (hnsw.rs:135-159) = NMN_METRIC_COSINE / _EUCLIDEAN / _DOT_PRODUCT */
+    int32_t storage;           /* NMN_HNSW_STORAGE_* */
+    uint32_t reserved;         /* 0 */
+} nmn_hnsw_config;
+/* HNSWConfig::default (hnsw.rs:1465-1480), ::high_recall (1508-1519), ::high_speed (1523-1534). */
+void nmn_hnsw_config_default(nmn_hnsw_config* cfg);
+void nmn_hnsw_config_high_recall(nmn_hnsw_config* cfg);
+void nmn_hnsw_config_high_speed(nmn_hnsw_config* cfg);
+
+/* HNSWIndex::with_config (hnsw.rs:1578-1587) for vectors of `dim` elements (<= 8192) on `device` (-1 = current).
+ * capacity_hint: rows the flat index is allocated for at first (0 = 1); it is re-created at twice the size when an insert
+ * outgrows it, so the pointer nmn_hnsw_vectors returns is valid until the next nmn_hnsw_insert. */
+nmn_status nmn_hnsw_create(const nmn_hnsw_config* cfg, uint32_t dim, uint64_t capacity_hint, int32_t device, nmn_hnsw** out);
+nmn_status nmn_hnsw_destroy(nmn_hnsw* h);
+/* HNSWIndex::insert for each of the n rows (HOST, n x dim) in order (try_insert_embedding, hnsw.rs:1936-2051): level from the
+ * xorshift generator seeded 42 (1631-1651), greedy descent above it, search_layer with ef_construction per layer, the first
+ * m (m0 on layer 0) of its result as neighbours, back links pruned to the closest m / m0 by a stable sort of the id-ascending
+ * list (2015-2036).  ids_out (nullable, [n]) receives the node ids.  If the batch would pass max_nodes nothing is inserted:
+ * NMN_ERR_CAPACITY, nmn_last_error() = "HNSW index at capacity: {current} nodes (limit: {limit})" (hnsw.rs:102-107).
+ * Waits for the device searches in flight, then uploads the new adjacency. */
+nmn_status nmn_hnsw_insert(nmn_hnsw* h, const float* rows_host, uint64_t n, uint64_t* ids_out);
+uint64_t nmn_hnsw_len(const nmn_hnsw* h);          /* HNSWIndex::len, hnsw.rs:1620-1622 */
+uint32_t nmn_hnsw_dim(const nmn_hnsw* h);
+uint64_t nmn_hnsw_entry_point(const nmn_hnsw* h);  /* UINT64_MAX while empty (hnsw.rs:1581) */
+uint32_t nmn_hnsw_max_layer(const nmn_hnsw* h);
+/* level of every node (out[len], cap >= len) and one neighbour list, id-ascending (hnsw.rs:1306-1314); a layer above the
+ * node's level has count 0.  out may be null to ask for the count. */
+nmn_status nmn_hnsw_levels(nmn_hnsw* h, uint32_t* out, uint64_t cap);
+nmn_status nmn_hnsw_neighbors(nmn_hnsw* h, uint64_t node, uint32_t layer, uint64_t* out, uint32_t cap, uint32_t* count);
+/* HNSWIndex::search_with_ef (hnsw.rs:2069-2111), ef == 0: config.ef_search.  queries HOST nq x dim; out_ids nq x k (unused =
+ * UINT64_MAX), out_scores nq x k = to_similarity(distance) (hnsw.rs:152-158; unused = -inf), out_counts nq.  Empty index:
+ * counts 0.  k == 0: NMN_ERR_INVALID_TOP_K.  stats: sweep_kind NMN_SWEEP_GRAPH, rows_scanned = distance evaluations,
+ * fallback_queries = queries answered by the spill launch.  Synchronous; host callers take turns.  With the environment
+ * variable NMN_HNSW_HOST_SEARCH=1 the walk runs on the host instead (the code insertion uses): same bits, for A/B runs. */
+nmn_status nmn_hnsw_search(nmn_hnsw* h, const float* queries, uint32_t nq, uint32_t k, uint32_t ef, uint64_t* out_ids,
+                           float* out_scores, uint32_t* out_counts, nmn_search_stats* stats);
+/* The same with every buffer in DEVICE memory: enqueued on `stream` (NULL: the default stream), not waited for.  Two kernel
+ * launches per chunk of queries (the walk with both heaps in LDS, then the spill launch for the queries whose candidate
+ * heap outgrew LDS), nothing is read back; a shape the stream has served before allocates nothing.  nmn_hnsw_insert and
+ * nmn_hnsw_destroy wait for the searches in flight. */
+nmn_status nmn_hnsw_search_device(nmn_hnsw* h, const float* queries_dev, uint32_t nq, uint32_t k, uint32_t ef,
+                                  uint64_t* out_ids_dev, float* out_scores_dev, uint32_t* out_counts_dev, void* stream);
+/* Entries of the results / candidate heaps a wave keeps in LDS (0 = default: 1024 results, 1024 .. 4096 candidates by ef).
+ * Smaller heaps leave more LDS per workgroup; a query that outgrows them is answered by the spill launch, same bits. */
+nmn_status nmn_hnsw_set_heap_capacity(nmn_hnsw* h, uint32_t results, uint32_t candidates);
+/* The flat index holding the rows (exhaustive search over the same rows). */
+nmn_index* nmn_hnsw_vectors(nmn_hnsw* h);
+/* Device memory the index holds: rows, magnitudes, mirrors, adjacency. */
+uint64_t nmn_hnsw_hbm_bytes(nmn_hnsw* h);
 
 /* ---- persistence of the device layout ----------------------------------- */
 

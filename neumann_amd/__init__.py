@@ -9,5 +9,6 @@ from .flat_index import (DistanceMetric, GpuFlatIndex, merge_topk_device, merge_
                          merge_topk_host, packed_layout, synth_rows)
 
 from .sharded import GpuShardedIndex  # noqa: F401,E402
+from .hnsw import GpuHnsw, HNSWConfig  # noqa: F401,E402
 
 __version__ = "0.3.0"

@@ -69,7 +69,7 @@ class SearchStats(C.Structure):
         return load().nmn_sweep_kind_str(self.sweep_kind).decode()
 
 
-SWEEP_NONE, SWEEP_RING_F32, SWEEP_VALU_F32, SWEEP_VALU_BF16, SWEEP_VALU_I8, SWEEP_MFMA_F32, SWEEP_MFMA_BF16, SWEEP_MFMA_I8, SWEEP_EXACT = range(9)
+SWEEP_NONE, SWEEP_RING_F32, SWEEP_VALU_F32, SWEEP_VALU_BF16, SWEEP_VALU_I8, SWEEP_MFMA_F32, SWEEP_MFMA_BF16, SWEEP_MFMA_I8, SWEEP_EXACT, SWEEP_GRAPH = range(10)
 
 
 class KMeansOptions(C.Structure):
@@ -86,6 +86,16 @@ class IvfStorage(C.Structure):
 
 IVF_FLAT, IVF_PQ, IVF_BINARY = range(3)
 BINARY_SIGN, BINARY_MEAN, BINARY_MEDIAN = range(3)
+
+
+class HnswConfig(C.Structure):
+    """nmn_hnsw_config (HNSWConfig, tensor_store/src/hnsw.rs:1434-1463)."""
+    _fields_ = [("m", C.c_uint32), ("m0", C.c_uint32), ("ef_construction", C.c_uint32), ("ef_search", C.c_uint32),
+                ("ml", C.c_double), ("max_nodes", C.c_uint64), ("sparsity_threshold", C.c_float),
+                ("distance_metric", C.c_int32), ("storage", C.c_int32), ("reserved", C.c_uint32)]
+
+
+HNSW_STORAGE_DENSE, HNSW_STORAGE_AUTO, HNSW_STORAGE_QUANTIZED = range(3)
 
 
 class PredOp(C.Structure):
@@ -177,6 +187,23 @@ SIGNATURES = {
     "nmn_ivf_pq_codebook": (C.c_int32, [vp, vp, C.c_uint64]),
     "nmn_ivf_codes": (C.c_int32, [vp, vp, C.c_uint64]),
     "nmn_ivf_hbm_bytes": (C.c_uint64, [vp]),
+    "nmn_hnsw_config_default": (None, [C.POINTER(HnswConfig)]),
+    "nmn_hnsw_config_high_recall": (None, [C.POINTER(HnswConfig)]),
+    "nmn_hnsw_config_high_speed": (None, [C.POINTER(HnswConfig)]),
+    "nmn_hnsw_create": (C.c_int32, [C.POINTER(HnswConfig), C.c_uint32, C.c_uint64, C.c_int32, C.POINTER(vp)]),
+    "nmn_hnsw_destroy": (C.c_int32, [vp]),
+    "nmn_hnsw_insert": (C.c_int32, [vp, vp, C.c_uint64, vp]),
+    "nmn_hnsw_len": (C.c_uint64, [vp]),
+    "nmn_hnsw_dim": (C.c_uint32, [vp]),
+    "nmn_hnsw_entry_point": (C.c_uint64, [vp]),
+    "nmn_hnsw_max_layer": (C.c_uint32, [vp]),
+    "nmn_hnsw_levels": (C.c_int32, [vp, vp, C.c_uint64]),
+    "nmn_hnsw_neighbors": (C.c_int32, [vp, C.c_uint64, C.c_uint32, vp, C.c_uint32, u32p]),
+    "nmn_hnsw_search": (C.c_int32, [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.POINTER(SearchStats)]),
+    "nmn_hnsw_search_device": (C.c_int32, [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp]),
+    "nmn_hnsw_set_heap_capacity": (C.c_int32, [vp, C.c_uint32, C.c_uint32]),
+    "nmn_hnsw_vectors": (vp, [vp]),
+    "nmn_hnsw_hbm_bytes": (C.c_uint64, [vp]),
     "nmn_index_save": (C.c_int32, [vp, C.c_char_p]),
     "nmn_index_load": (C.c_int32, [C.c_char_p, C.POINTER(IndexDesc), C.c_uint64, C.c_uint64, C.POINTER(vp)]),
     "nmn_ivf_save": (C.c_int32, [vp, C.c_char_p]),

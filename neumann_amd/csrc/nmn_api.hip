@@ -432,8 +432,8 @@ extern "C" const char* nmn_status_str(nmn_status s) {
 }
 
 extern "C" const char* nmn_sweep_kind_str(uint32_t kind) {
-    static const char* const names[] = {"none", "ring_f32", "valu_f32", "valu_bf16", "valu_i8", "mfma_f32", "mfma_bf16", "mfma_i8", "exact"};
-    return kind <= NMN_SWEEP_EXACT ? names[kind] : "unknown";
+    static const char* const names[] = {"none", "ring_f32", "valu_f32", "valu_bf16", "valu_i8", "mfma_f32", "mfma_bf16", "mfma_i8", "exact", "graph"};
+    return kind <= NMN_SWEEP_GRAPH ? names[kind] : "unknown";
 }
 
 extern "C" const char* nmn_last_error(void) { return g_last_error.c_str(); }

@@ -135,6 +135,16 @@ struct nmn_engine_ivf {
     }
 };
 
+// (HNSWIndex, Vec<String>) as build_hnsw_index returns it (lib.rs:2378-2470): the GPU index + node id -> key mapping
+struct nmn_engine_hnsw {
+    nmn_hnsw* index = nullptr;          // null = built from an empty store
+    std::vector<std::string> keys;
+    uint64_t dim = 0;
+    ~nmn_engine_hnsw() {
+        if (index) nmn_hnsw_destroy(index);
+    }
+};
+
 namespace {
 
 using Meta = std::map<std::string, Value>;
@@ -273,7 +283,7 @@ struct Collection {
 struct CollectionConfig {  // VectorCollectionConfig (lib.rs:455-475)
     uint64_t dimension = 0;  // 0 = None
     int32_t metric = NMN_METRIC_COSINE;
-    bool auto_index = false;               // HNSW auto-indexing: carried through index files, not acted on (CPU structure)
+    bool auto_index = false;               // HNSW auto-indexing: carried through index files, not acted on (the hnsw_cache hook is out of scope; build_hnsw_index is served)
     uint64_t auto_index_threshold = 1000;
 };
 
@@ -1739,6 +1749,114 @@ nmn_status nmn_engine_search_with_ivf(nmn_engine* e, nmn_engine_ivf* ivf, const 
         }
     }
     *out = res;
+    return NMN_OK;
+}
+
+// ---- HNSW (lib.rs:2378-2550) -------------------------------------------------------------------------
+nmn_status nmn_engine_build_hnsw_index(nmn_engine* e, const nmn_hnsw_config* cfg, nmn_engine_hnsw** out) {
+    if (!e || !out) return fail(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    *out = nullptr;
+    nmn_hnsw_config c;
+    if (cfg) c = *cfg;
+    else nmn_hnsw_config_default(&c);
+    if (c.storage != NMN_HNSW_STORAGE_DENSE)
+        return fail(NMN_ERR_CONFIGURATION, "Configuration error: only HNSWStorageStrategy::Dense is served on the GPU (Auto / Quantized are out of scope)");
+    auto res = std::unique_ptr<nmn_engine_hnsw>(new (std::nothrow) nmn_engine_hnsw());
+    if (!res) return fail(NMN_ERR_OUT_OF_MEMORY, "hnsw alloc");
+    WriteLock g(e);
+    std::vector<float> rows;
+    uint64_t dim = 0;
+    bool first = true;
+    for (const auto& ent : e->dflt.slots) {  // `let keys = self.list_keys()`, every vector in that order
+        if (!ent.live) continue;
+        if (first) {
+            first = false;
+            dim = ent.vec.size();  // lib.rs:2434-2446
+            if (e->cfg.max_dimension && dim > e->cfg.max_dimension) return err_dim(e->cfg.max_dimension, dim);
+        } else if (ent.vec.size() != dim) {
+            return err_dim(dim, ent.vec.size());  // lib.rs:2458-2463
+        }
+        res->keys.push_back(ent.key);
+        rows.insert(rows.end(), ent.vec.begin(), ent.vec.end());
+    }
+    const uint64_t n = res->keys.size();
+    if (n == 0) {  // `return Ok((HNSWIndex::with_config(..), Vec::new()))`
+        *out = res.release();
+        return NMN_OK;
+    }
+    res->dim = dim;
+    if (dim > 0xFFFFFFFFull) return fail(NMN_ERR_INVALID_ARGUMENT, "dimension does not fit the device index (> 2^32 - 1)");
+    nmn_status st = nmn_hnsw_create(&c, (uint32_t)dim, n, e->cfg.device, &res->index);
+    if (st == NMN_ERR_CONFIGURATION) return fail(st, std::string("Configuration error: ") + nmn_last_error());
+    if (st != NMN_OK) return err_gpu(st);
+    st = nmn_hnsw_insert(res->index, rows.data(), n, nullptr);
+    if (st == NMN_ERR_CAPACITY) return fail(st, std::string("Insert failed: ") + nmn_last_error());  // the reference panics here (hnsw.rs:1916-1918)
+    if (st != NMN_OK) return err_gpu(st);
+    *out = res.release();
+    return NMN_OK;
+}
+
+void nmn_engine_hnsw_free(nmn_engine_hnsw* h) { delete h; }
+uint64_t nmn_engine_hnsw_len(const nmn_engine_hnsw* h) { return (h && h->index) ? nmn_hnsw_len(h->index) : 0; }
+const char* nmn_engine_hnsw_key(const nmn_engine_hnsw* h, uint64_t id) {
+    return (h && id < h->keys.size()) ? h->keys[id].c_str() : nullptr;
+}
+nmn_hnsw* nmn_engine_hnsw_index(nmn_engine_hnsw* h) { return h ? h->index : nullptr; }
+
+nmn_status nmn_engine_search_with_hnsw(nmn_engine* e, nmn_engine_hnsw* h, const float* q, uint64_t dim, uint64_t top_k,
+                                       nmn_results** out) {
+    if (!e || !h || !out) return fail(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    *out = nullptr;
+    const Deadline dl(e->cfg.search_timeout_ms);
+    if (!q || dim == 0) return err_empty();  // lib.rs:2525-2527
+    if (top_k == 0) return err_topk();       // lib.rs:2528-2530
+    nmn_results* res = new_results();
+    if (!res) return fail(NMN_ERR_OUT_OF_MEMORY, "results alloc");
+    if (h->index) {  // empty index: `return Vec::new()` (hnsw.rs:2070-2073)
+        if (dim != h->dim) {
+            delete res;
+            return err_dim(h->dim, dim);  // the reference's SIMD loops would read past the shorter slice; refused here
+        }
+        const uint64_t len = nmn_hnsw_len(h->index);
+        // search_layer runs with max(ef_search, top_k); any ef >= len keeps every node the walk reaches and never ends it early, so
+        // a top_k beyond len is served as len
+        const uint32_t k = (uint32_t)std::min<uint64_t>(top_k, std::max<uint64_t>(len, 1));
+        std::vector<uint64_t> ids(k);
+        std::vector<float> sc(k);
+        uint32_t count = 0;
+        nmn_status st = nmn_hnsw_search(h->index, q, 1, k, 0, ids.data(), sc.data(), &count, nullptr);
+        if (st != NMN_OK) {
+            delete res;
+            return err_gpu(st);
+        }
+        if (dl.expired()) {  // lib.rs:2534-2539
+            delete res;
+            return err_timeout("search_with_hnsw", dl.ms);
+        }
+        for (uint32_t i = 0; i < count; i++) {
+            if (ids[i] >= h->keys.size()) continue;  // `key_mapping.get(node_id)` -> filter_map
+            res->keys.push_back(h->keys[ids[i]]);
+            res->scores.push_back(sc[i]);
+        }
+    }
+    *out = res;
+    return NMN_OK;
+}
+
+// estimate_hnsw_memory (lib.rs:2489-2509): vectors + count x M(16) x 2 x 8 of graph + 32 bytes a key; host arithmetic only
+nmn_status nmn_engine_estimate_hnsw_memory(nmn_engine* e, uint64_t* out_bytes) {
+    if (!e || !out_bytes) return fail(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    *out_bytes = 0;
+    ReadLock g(e);
+    const uint64_t count = e->dflt.live;
+    if (count == 0) return NMN_OK;
+    uint64_t dim = 0;
+    for (const auto& ent : e->dflt.slots)
+        if (ent.live) {
+            dim = ent.vec.size();
+            break;
+        }
+    *out_bytes = count * dim * 4 + count * 16 * 2 * 8 + count * 32;
     return NMN_OK;
 }
 

@@ -1,0 +1,1125 @@
+// nmn_hnsw.hip — `tensor_store::HNSWIndex` (tensor_store/src/hnsw.rs:1554-2335) with Dense storage: the graph is built on the
+// host in the reference's order and searched on the GPU, one query per wave, the whole walk in one launch.
+// THIS TRANSLATION UNIT IS BUILT WITH -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt (build.py), host and device:
+// every distance below restates the reference's unfused f32 arithmetic and must give its bits.
+//
+// Reference order restated here (docs/hnsw.md has the long form):
+//   simd::dot_product / sum_of_squares / euclidean_distance (hnsw.rs:168-261): eight accumulator chains over whole chunks of
+//       eight elements (acc starts +0.0, product and sum rounded separately), the chains summed left to right from -0.0
+//       (`arr.iter().sum()`), the scalar tail added after that, one sqrt.
+//   distance_dense (hnsw.rs:1035-1045, 1084-1086, 1136-1138, 1157-1163): 1 - dot / (|v| |q|) (1.0 when a magnitude is 0),
+//       euclidean_distance, -dot.  The pruning side (hnsw.rs:2437-2452 and siblings) is the same arithmetic on two rows.
+//   Neighbor / MaxNeighbor (hnsw.rs:1380-1430) order by distance alone, so every tie is decided by the array layout of
+//       std::collections::BinaryHeap: push = append + sift up from the new slot until a parent is not smaller; pop = last element
+//       into the root, the hole sifted down to the bottom following the greater child (the right one when equal: the test is
+//       `left <= right`), then sifted up; into_iter = the backing vector's order.  Both heaps are kept as that array algorithm.
+//   search_layer (hnsw.rs:2276-2335), search_layer_greedy (2170-2200), search_with_ef (2069-2111), try_insert_embedding
+//       (1936-2051), random_level (1631-1651).
+#include <algorithm>
+#include <atomic>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <memory>
+#include <mutex>
+#include <shared_mutex>
+#include <string>
+#include <vector>
+
+#include "nmn_index.h"
+#include "nmn_internal.h"
+
+#pragma clang fp contract(off)
+
+namespace nmn {
+namespace {
+
+constexpr uint32_t kNone = 0xFFFFFFFFu;
+constexpr uint32_t kLdsResultsMax = 1024;  // entries of the results heap a wave keeps in LDS (+1 for the push before the pop)
+constexpr uint32_t kLdsCandMax = 4096;     // entries of the candidate heap a wave keeps in LDS
+constexpr uint32_t kMaxDim = 8192;         // the query sits in LDS for the whole walk (32 KiB at most)
+
+struct Ent {
+    float d;
+    uint32_t id;
+};
+
+// ---- the two heaps, shared by host and device ------------------------------------------------------------------------------
+// MAX == true: MaxNeighbor (a <= b iff a.d <= b.d); MAX == false: Neighbor, reversed (a <= b iff b.d <= a.d).  NaN distances are out of scope.
+template <bool MAX>
+__host__ __device__ inline bool heap_le(const Ent& a, const Ent& b) {
+    return MAX ? a.d <= b.d : b.d <= a.d;
+}
+// BinaryHeap::sift_up(start = 0, pos): the hole moves up while the element is GREATER than the parent
+template <bool MAX>
+__host__ __device__ inline void heap_sift_up(Ent* v, uint32_t pos) {
+    const Ent e = v[pos];
+    while (pos > 0) {
+        const uint32_t parent = (pos - 1) / 2;
+        if (heap_le<MAX>(e, v[parent])) break;
+        v[pos] = v[parent];
+        pos = parent;
+    }
+    v[pos] = e;
+}
+template <bool MAX>
+__host__ __device__ inline void heap_push(Ent* v, uint32_t& n, Ent e) {
+    v[n] = e;
+    heap_sift_up<MAX>(v, n);
+    n++;
+}
+// BinaryHeap::pop: Vec::pop, swap with the root, sift_down_to_bottom(0)
+template <bool MAX>
+__host__ __device__ inline Ent heap_pop(Ent* v, uint32_t& n) {
+    Ent item = v[--n];
+    if (n > 0) {
+        const Ent root = v[0];
+        const uint32_t end = n;
+        uint32_t pos = 0, child = 1;
+        while (child + 1 < end) {  // child <= end.saturating_sub(2)
+            if (heap_le<MAX>(v[child], v[child + 1])) child++;
+            v[pos] = v[child];
+            pos = child;
+            child = 2 * pos + 1;
+        }
+        if (child == end - 1) {
+            v[pos] = v[child];
+            pos = child;
+        }
+        v[pos] = item;
+        heap_sift_up<MAX>(v, pos);
+        item = root;
+    }
+    return item;
+}
+
+// ---- host arithmetic ---------------------------------------------------------------------------------------------------------
+inline float h_dot8(const float* a, const float* b, uint32_t dim) {
+    float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    const uint32_t chunks = dim / 8;
+    for (uint32_t c = 0; c < chunks; c++)
+        for (int l = 0; l < 8; l++) {
+            const float p = a[8 * c + l] * b[8 * c + l];
+            acc[l] = acc[l] + p;
+        }
+    float r = -0.0f;
+    for (int l = 0; l < 8; l++) r = r + acc[l];
+    for (uint32_t i = chunks * 8; i < dim; i++) {
+        const float p = a[i] * b[i];
+        r = r + p;
+    }
+    return r;
+}
+inline float h_eucl8(const float* a, const float* b, uint32_t dim) {
+    float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    const uint32_t chunks = dim / 8;
+    for (uint32_t c = 0; c < chunks; c++)
+        for (int l = 0; l < 8; l++) {
+            const float d = a[8 * c + l] - b[8 * c + l];
+            const float p = d * d;
+            acc[l] = acc[l] + p;
+        }
+    float r = -0.0f;
+    for (int l = 0; l < 8; l++) r = r + acc[l];
+    for (uint32_t i = chunks * 8; i < dim; i++) {
+        const float d = a[i] - b[i];
+        const float p = d * d;
+        r = r + p;
+    }
+    return sqrtf(r);
+}
+inline float h_distance(int metric, const float* v, float vmag, const float* q, float qmag, uint32_t dim) {
+    if (metric == NMN_METRIC_EUCLIDEAN) return h_eucl8(v, q, dim);
+    const float dot = h_dot8(v, q, dim);
+    if (metric == NMN_METRIC_DOT_PRODUCT) return -dot;
+    if (vmag == 0.0f || qmag == 0.0f) return 1.0f;
+    const float den = vmag * qmag;
+    const float sim = dot / den;
+    return 1.0f - sim;
+}
+__host__ __device__ inline float to_similarity(int metric, float d) {  // hnsw.rs:152-158
+    if (metric == NMN_METRIC_EUCLIDEAN) return 1.0f / (1.0f + d);
+    if (metric == NMN_METRIC_DOT_PRODUCT) return -d;
+    return 1.0f - d;
+}
+
+// ---- device graph --------------------------------------------------------------------------------------------------------------
+struct GraphDev {
+    const float* corpus;    // the flat index's rows, stride ld
+    const float* norms;     // simd::magnitude of every row (ingest kernels)
+    const uint32_t* l0;     // [n][m0] layer-0 neighbour slots, id-ascending
+    const uint32_t* l0cnt;  // [n]
+    const uint32_t* up_idx; // [n] row of the upper table, kNone for a level-0 node
+    const uint32_t* up;     // [n_upper][up_layers][m]
+    const uint32_t* upcnt;  // [n_upper][up_layers]
+    uint32_t ld, dim, m, m0, up_layers, n, entry, max_layer;
+    int metric;
+};
+
+struct SearchArgs {
+    GraphDev g;
+    const float* queries;  // [nq][dim]
+    uint32_t nq, k, ef;    // ef = max(ef, k) already
+    uint32_t rcap, ccap;   // entries of the results / candidate heaps of this launch
+    uint32_t qlds;         // query elements in LDS (dim rounded up to 8)
+    uint32_t* visited;     // [nq][vwords]
+    uint32_t vwords;
+    uint32_t* flags;       // [nq] 0 = answered by the first launch, 1 = candidate heap overflowed, 2 = answered by the spill launch
+    uint32_t* evals;       // [nq] distance evaluations
+    Ent* spill;            // spill launch: [regions][rcap + ccap]
+    uint64_t* out_ids;
+    float* out_scores;
+    uint32_t* out_counts;
+};
+
+__device__ __forceinline__ float d_sqrt(float a) { return __builtin_sqrtf(a); }
+
+// Distance between row `row` and the query, computed by a PAIR of lanes: lane h (0 / 1) of the pair owns the accumulator chains
+// 4h .. 4h+3 and reads elements 8c + 4h .. 8c + 4h + 3 of every chunk c with one 16-byte load; the chains are the reference's eight
+// (the order inside a chain is untouched), summed left to right by both lanes.  Chunks past the end read as zeros: a product +0.0
+// added to a chain that is never -0.0 (it starts at +0.0) changes nothing.  Both lanes return the distance.
+__device__ __forceinline__ float pair_distance(const float* __restrict__ row, float rowmag, const float* q, float qmag, uint32_t dim,
+                                               int metric, uint32_t h) {
+    const uint32_t chunks = dim >> 3;
+    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
+    const float4* r4 = reinterpret_cast<const float4*>(row + 4u * h);
+    const float4* q4 = reinterpret_cast<const float4*>(q + 4u * h);
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    constexpr int PF = 4;
+    const bool eu = metric == NMN_METRIC_EUCLIDEAN;
+    for (uint32_t c0 = 0; c0 < chunks; c0 += PF) {
+        float4 x[PF], y[PF];
+#pragma unroll
+        for (int i = 0; i < PF; i++) {
+            const bool in = c0 + (uint32_t)i < chunks;
+            x[i] = in ? r4[2u * (c0 + i)] : z;
+            y[i] = in ? q4[2u * (c0 + i)] : z;
+        }
+#pragma unroll
+        for (int i = 0; i < PF; i++) {
+            if (eu) {
+                const float d0 = x[i].x - y[i].x, d1 = x[i].y - y[i].y, d2 = x[i].z - y[i].z, d3 = x[i].w - y[i].w;
+                a0 = a0 + d0 * d0;
+                a1 = a1 + d1 * d1;
+                a2 = a2 + d2 * d2;
+                a3 = a3 + d3 * d3;
+            } else {
+                a0 = a0 + x[i].x * y[i].x;
+                a1 = a1 + x[i].y * y[i].y;
+                a2 = a2 + x[i].z * y[i].z;
+                a3 = a3 + x[i].w * y[i].w;
+            }
+        }
+    }
+    const float b0 = __shfl_xor(a0, 1), b1 = __shfl_xor(a1, 1), b2 = __shfl_xor(a2, 1), b3 = __shfl_xor(a3, 1);
+    float r = -0.0f;
+    r = r + (h ? b0 : a0);
+    r = r + (h ? b1 : a1);
+    r = r + (h ? b2 : a2);
+    r = r + (h ? b3 : a3);
+    r = r + (h ? a0 : b0);
+    r = r + (h ? a1 : b1);
+    r = r + (h ? a2 : b2);
+    r = r + (h ? a3 : b3);
+    for (uint32_t i = chunks * 8u; i < dim; i++) {
+        if (eu) {
+            const float d = row[i] - q[i];
+            r = r + d * d;
+        } else {
+            r = r + row[i] * q[i];
+        }
+    }
+    if (eu) return d_sqrt(r);
+    if (metric == NMN_METRIC_DOT_PRODUCT) return -r;
+    if (rowmag == 0.0f || qmag == 0.0f) return 1.0f;
+    return 1.0f - r / (rowmag * qmag);
+}
+
+// One query per wave (one wave per workgroup).  SPILL == false: both heaps in LDS; a query whose candidate heap fills up is flagged
+// and left.  SPILL == true: workgroup b answers the flagged queries b, b + grid, ... from scratch with both heaps in its region of
+// global memory (candidates: n entries, the proven bound — nothing is pushed twice).
+// Only lane 0 touches the heaps; the other lanes learn what to do next through `ctrl` in LDS.
+template <bool SPILL>
+__global__ __launch_bounds__(64) void hnsw_search_kernel(SearchArgs a) {
+    extern __shared__ float4 smem4[];
+    const GraphDev& g = a.g;
+    const uint32_t lane = threadIdx.x, p = lane >> 1, h = lane & 1u;
+    float* qs = reinterpret_cast<float*>(smem4);
+    uint32_t* stage_id = reinterpret_cast<uint32_t*>(qs + a.qlds);
+    float* stage_d = reinterpret_cast<float*>(stage_id + 32);
+    uint32_t* ctrl = reinterpret_cast<uint32_t*>(stage_d + 32);  // [0] done, [1] current node, [2] overflow, [3] results
+    Ent* R;
+    Ent* Cn;
+    if (SPILL) {
+        R = a.spill + (size_t)blockIdx.x * ((size_t)a.rcap + a.ccap);
+        Cn = R + a.rcap;
+    } else {
+        R = reinterpret_cast<Ent*>(ctrl + 4);
+        Cn = R + a.rcap;
+    }
+    const float ninf = __int_as_float(0xFF800000u);
+    for (uint32_t q = blockIdx.x; q < a.nq; q += gridDim.x) {
+        if (SPILL && a.flags[q] != 1u) continue;
+        const float* qg = a.queries + (size_t)q * g.dim;
+        const float* qv = qs;
+        __syncthreads();
+        for (uint32_t i = lane; i < a.qlds; i += 64) qs[i] = i < g.dim ? qg[i] : 0.0f;
+        uint32_t* vis = a.visited + (size_t)q * a.vwords;
+        if (SPILL) {
+            for (uint32_t w = lane; w < a.vwords; w += 64) vis[w] = 0u;
+            __threadfence();
+        }
+        __syncthreads();
+        uint64_t* o_ids = a.out_ids + (size_t)q * a.k;
+        float* o_sc = a.out_scores + (size_t)q * a.k;
+        if (g.n == 0 || g.entry == kNone) {  // hnsw.rs:2070-2073
+            for (uint32_t i = lane; i < a.k; i += 64) {
+                o_ids[i] = ~0ull;
+                o_sc[i] = ninf;
+            }
+            if (lane == 0) {
+                a.out_counts[q] = 0;
+                a.evals[q] = 0;
+                if (SPILL) a.flags[q] = 2u;
+            }
+            continue;
+        }
+        float qmag = 0.0f;
+        if (g.metric == NMN_METRIC_COSINE) qmag = d_sqrt(-pair_distance(qv, 0.f, qv, 0.f, g.dim, NMN_METRIC_DOT_PRODUCT, h));
+        uint32_t evals = 1;
+        // greedy descent, hnsw.rs:2086-2092 / 2170-2200
+        uint32_t cur = g.entry;
+        float cur_d = pair_distance(g.corpus + (size_t)cur * g.ld, g.norms[cur], qv, qmag, g.dim, g.metric, h);
+        for (uint32_t layer = g.max_layer; layer >= 1; layer--) {
+            for (;;) {
+                const uint32_t ui = g.up_idx[cur];
+                const size_t slot = (size_t)ui * g.up_layers + (layer - 1);
+                const uint32_t cnt = ui == kNone ? 0u : g.upcnt[slot];
+                const uint32_t* base = g.up + slot * g.m;
+                uint32_t best = cur;
+                float best_d = cur_d;
+                for (uint32_t j0 = 0; j0 < cnt; j0 += 32) {
+                    const uint32_t j = j0 + p;
+                    uint32_t nid = kNone;
+                    float d = 0.0f;
+                    if (j < cnt) {
+                        nid = base[j];
+                        d = pair_distance(g.corpus + (size_t)nid * g.ld, g.norms[nid], qv, qmag, g.dim, g.metric, h);
+                    }
+                    __syncthreads();
+                    if (h == 0) {
+                        stage_id[p] = nid;
+                        stage_d[p] = d;
+                    }
+                    __syncthreads();
+                    const uint32_t lim = min(32u, cnt - j0);
+                    for (uint32_t t = 0; t < lim; t++) {  // every lane, the same reads: the list in id order
+                        const float dt = stage_d[t];
+                        if (dt < best_d) {
+                            best = stage_id[t];
+                            best_d = dt;
+                        }
+                    }
+                }
+                evals += cnt;
+                if (best == cur) break;  // (`changed` is false exactly when no neighbour was strictly closer)
+                cur = best;
+                cur_d = best_d;
+            }
+        }
+        // layer 0: search_layer, hnsw.rs:2276-2335
+        uint32_t rn = 0, cn = 0;  // (lane 0's are the real ones)
+        if (lane == 0) {
+            atomicOr(&vis[cur >> 5], 1u << (cur & 31u));
+            heap_push<false>(Cn, cn, Ent{cur_d, cur});
+            heap_push<true>(R, rn, Ent{cur_d, cur});
+            ctrl[2] = 0;
+        }
+        bool overflow = false;
+        for (;;) {
+            __syncthreads();
+            if (lane == 0) {
+                uint32_t done = 0, c = 0;
+                if (cn == 0) {
+                    done = 1;
+                } else {
+                    const Ent e = heap_pop<false>(Cn, cn);
+                    c = e.id;
+                    if (rn >= a.ef && e.d > R[0].d) done = 1;
+                }
+                ctrl[0] = done;
+                ctrl[1] = c;
+            }
+            __syncthreads();
+            if (ctrl[0]) break;
+            const uint32_t c = ctrl[1];
+            const uint32_t cnt = g.l0cnt[c];
+            const uint32_t* base = g.l0 + (size_t)c * g.m0;
+            for (uint32_t j0 = 0; j0 < cnt; j0 += 32) {
+                const uint32_t j = j0 + p;
+                uint32_t nid = kNone;
+                float d = 0.0f;
+                if (j < cnt) {
+                    nid = base[j];
+                    uint32_t seen = 0;
+                    if (h == 0) seen = (atomicOr(&vis[nid >> 5], 1u << (nid & 31u)) >> (nid & 31u)) & 1u;
+                    seen = __shfl(seen, (int)(lane & ~1u));
+                    if (seen)
+                        nid = kNone;
+                    else
+                        d = pair_distance(g.corpus + (size_t)nid * g.ld, g.norms[nid], qv, qmag, g.dim, g.metric, h);
+                }
+                if (h == 0) {
+                    stage_id[p] = nid;
+                    stage_d[p] = d;
+                }
+                __syncthreads();
+                if (lane == 0) {
+                    const uint32_t lim = min(32u, cnt - j0);
+                    for (uint32_t t = 0; t < lim; t++) {
+                        const uint32_t id = stage_id[t];
+                        if (id == kNone) continue;
+                        evals++;
+                        const float dt = stage_d[t];
+                        const bool should_add = rn < a.ef || dt < R[0].d;
+                        if (should_add) {
+                            if (cn == a.ccap) {
+                                ctrl[2] = 1;
+                                break;
+                            }
+                            heap_push<false>(Cn, cn, Ent{dt, id});
+                            heap_push<true>(R, rn, Ent{dt, id});
+                            while (rn > a.ef) (void)heap_pop<true>(R, rn);
+                        }
+                    }
+                }
+                __syncthreads();
+                if (ctrl[2]) {
+                    overflow = true;
+                    break;
+                }
+            }
+            if (overflow) break;
+        }
+        if (overflow) {  // the spill launch answers this query; nothing of it has been written
+            if (lane == 0) a.flags[q] = 1u;
+            continue;
+        }
+        if (lane == 0) ctrl[3] = rn;
+        if (SPILL) __threadfence();
+        __syncthreads();
+        const uint32_t n_res = ctrl[3];
+        const uint32_t count = min(a.k, n_res);
+        // stable sort by distance of the vector order (hnsw.rs:2328-2333), as ranks: element e goes to
+        // #{j : d_j < d_e} + #{j < e : d_j == d_e}
+        for (uint32_t e = lane; e < n_res; e += 64) {
+            const Ent me = R[e];
+            uint32_t rank = 0;
+            for (uint32_t j = 0; j < n_res; j++) {
+                const float dj = R[j].d;
+                rank += (dj < me.d || (dj == me.d && j < e)) ? 1u : 0u;
+            }
+            if (rank < a.k) {
+                o_ids[rank] = (uint64_t)me.id;
+                o_sc[rank] = to_similarity(g.metric, me.d);
+            }
+        }
+        for (uint32_t i = count + lane; i < a.k; i += 64) {
+            o_ids[i] = ~0ull;
+            o_sc[i] = ninf;
+        }
+        if (lane == 0) {
+            a.out_counts[q] = count;
+            a.evals[q] = evals;
+            if (SPILL) a.flags[q] = 2u;
+        }
+    }
+}
+
+struct DevBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+};
+
+}  // namespace
+}  // namespace nmn
+
+using namespace nmn;
+
+struct nmn_hnsw {
+    nmn_hnsw_config cfg{};
+    uint32_t dim = 0;
+    int device = 0;
+    nmn_index* vectors = nullptr;
+    uint64_t vec_cap = 0;
+    // host side: the rows, their magnitudes, the graph
+    std::vector<float> rows;
+    std::vector<float> mags;
+    std::vector<uint8_t> level;
+    std::vector<std::vector<std::vector<uint32_t>>> nbr;  // [node][layer], id-ascending
+    uint64_t entry = ~0ull;
+    uint32_t max_layer = 0;
+    uint64_t rng = 42;  // hnsw.rs:1584
+    // device side
+    DevBuf d_l0, d_l0cnt, d_upidx, d_up, d_upcnt;
+    uint32_t up_layers = 1, n_upper = 0;
+    uint32_t lds_rcap = 0, lds_ccap = 0;  // nmn_hnsw_set_heap_capacity (0 = default)
+    struct Scratch {
+        hipStream_t stream = nullptr;
+        std::mutex mu;
+        DevBuf vis, flags, evals, spill;
+    };
+    std::vector<std::unique_ptr<Scratch>> scratch;
+    std::vector<hipEvent_t> ev_pending, ev_free;
+    std::mutex dev_mu;          // scratch list and events
+    std::shared_mutex rw;       // searches shared, insert exclusive
+    // the host-buffer search
+    std::mutex host_mu;
+    hipStream_t host_stream = nullptr;
+    DevBuf hq, hids, hsc, hcnt;
+};
+
+namespace {
+
+#define HN_TRY(expr)                                                  \
+    do {                                                              \
+        hipError_t _e = (expr);                                       \
+        if (_e != hipSuccess) return set_error_hip(_e, #expr);        \
+    } while (0)
+
+hipError_t grow(DevBuf& b, size_t bytes, hipStream_t s, bool* synced) {
+    if (bytes <= b.cap) return hipSuccess;
+    if (s != (hipStream_t)-1 && !*synced) {  // what is in flight on the stream may read the old buffer
+        hipError_t e = hipStreamSynchronize(s);
+        if (e != hipSuccess) return e;
+        *synced = true;
+    }
+    if (b.p) (void)hipFree(b.p);
+    b.p = nullptr;
+    b.cap = 0;
+    const size_t want = std::max<size_t>(bytes + bytes / 4, 256);
+    hipError_t e = hipMalloc(&b.p, want);
+    if (e != hipSuccess) return e;
+    b.cap = want;
+    return hipSuccess;
+}
+void drop(DevBuf& b) {
+    if (b.p) (void)hipFree(b.p);
+    b.p = nullptr;
+    b.cap = 0;
+}
+
+// random_level, hnsw.rs:1631-1651 (usize = 64 bits)
+uint32_t next_level(nmn_hnsw* h) {
+    uint64_t s = h->rng;
+    s ^= s << 13;
+    s ^= s >> 7;
+    s ^= s << 17;
+    h->rng = s;
+    const double f = (double)s / (double)UINT64_MAX;
+    const double lv = std::floor(-std::log(f) * h->cfg.ml);
+    if (!(lv > 0.0)) return 0;
+    return lv >= 32.0 ? 32u : (uint32_t)lv;
+}
+
+struct HostVisited {
+    std::vector<uint32_t> stamp;
+    uint32_t epoch = 0;
+    void begin(size_t n) {
+        if (stamp.size() < n) stamp.resize(n, 0);
+        if (++epoch == 0) {
+            std::fill(stamp.begin(), stamp.end(), 0);
+            epoch = 1;
+        }
+    }
+    bool insert(uint32_t id) {
+        if (stamp[id] == epoch) return false;
+        stamp[id] = epoch;
+        return true;
+    }
+};
+
+inline float node_distance(const nmn_hnsw* h, uint32_t node, const float* q, float qmag) {
+    return h_distance(h->cfg.distance_metric, h->rows.data() + (size_t)node * h->dim, h->mags[node], q, qmag, h->dim);
+}
+
+uint32_t host_greedy(const nmn_hnsw* h, const float* q, float qmag, uint32_t entry, uint32_t layer, uint64_t* evals) {
+    uint32_t cur = entry;
+    float cur_d = node_distance(h, cur, q, qmag);
+    (*evals)++;
+    for (;;) {
+        const std::vector<uint32_t>& ids = h->nbr[cur][layer];  // (the list of the node the round started from)
+        bool changed = false;
+        uint32_t best = cur;
+        for (uint32_t id : ids) {
+            const float d = node_distance(h, id, q, qmag);
+            (*evals)++;
+            if (d < cur_d) {
+                best = id;
+                cur_d = d;
+                changed = true;
+            }
+        }
+        cur = best;
+        if (!changed) break;
+    }
+    return cur;
+}
+
+// search_layer: the results in the order the reference returns them (stable sort by distance of the heap's vector)
+void host_search_layer(const nmn_hnsw* h, const float* q, float qmag, uint32_t entry, uint64_t ef, uint32_t layer, HostVisited& vis,
+                       std::vector<Ent>& out, uint64_t* evals) {
+    static thread_local std::vector<Ent> cand, res;  // grown on demand, kept: a walk touches a few thousand entries of a graph of millions
+    vis.begin(h->level.size());
+    if (cand.size() < 1024) cand.resize(1024);
+    if (res.size() < 1024) res.resize(1024);
+    uint32_t cn = 0, rn = 0;
+    const float ed = node_distance(h, entry, q, qmag);
+    (*evals)++;
+    vis.insert(entry);
+    heap_push<false>(cand.data(), cn, Ent{ed, entry});
+    heap_push<true>(res.data(), rn, Ent{ed, entry});
+    while (cn > 0) {
+        const Ent cur = heap_pop<false>(cand.data(), cn);
+        if (rn >= ef && cur.d > res[0].d) break;
+        for (uint32_t id : h->nbr[cur.id][layer]) {
+            if (!vis.insert(id)) continue;
+            const float d = node_distance(h, id, q, qmag);
+            (*evals)++;
+            const bool should_add = rn < ef || d < res[0].d;
+            if (should_add) {
+                if (cn == cand.size()) cand.resize(2 * cand.size());
+                if (rn == res.size()) res.resize(2 * res.size());
+                heap_push<false>(cand.data(), cn, Ent{d, id});
+                heap_push<true>(res.data(), rn, Ent{d, id});
+                while (rn > ef) (void)heap_pop<true>(res.data(), rn);
+            }
+        }
+    }
+    out.assign(res.begin(), res.begin() + rn);
+    std::stable_sort(out.begin(), out.end(), [](const Ent& a, const Ent& b) { return a.d < b.d; });
+}
+
+float host_qmag(const nmn_hnsw* h, const float* q) {
+    return h->cfg.distance_metric == NMN_METRIC_COSINE ? sqrtf(h_dot8(q, q, h->dim)) : 0.0f;
+}
+
+// try_insert_embedding, hnsw.rs:1936-2051 (the row and its magnitude are already in h->rows / h->mags)
+void host_insert_node(nmn_hnsw* h, uint32_t node_id, HostVisited& vis) {
+    const uint32_t node_level = next_level(h);
+    h->level.push_back((uint8_t)node_level);
+    h->nbr.emplace_back(node_level + 1);
+    if (h->entry == ~0ull) {
+        h->entry = node_id;
+        h->max_layer = node_level;
+        return;
+    }
+    const uint32_t current_max = h->max_layer;
+    const float* q = h->rows.data() + (size_t)node_id * h->dim;
+    const float qmag = h->cfg.distance_metric == NMN_METRIC_COSINE ? sqrtf(h_dot8(q, q, h->dim)) : 0.0f;
+    uint64_t evals = 0;
+    uint32_t cur = (uint32_t)h->entry;
+    for (uint32_t layer = current_max; layer >= node_level + 1; layer--) cur = host_greedy(h, q, qmag, cur, layer, &evals);
+    std::vector<Ent> found;
+    std::vector<std::pair<float, uint32_t>> wd;
+    for (int layer = (int)std::min(node_level, current_max); layer >= 0; layer--) {
+        host_search_layer(h, q, qmag, cur, h->cfg.ef_construction, (uint32_t)layer, vis, found, &evals);
+        const uint32_t m = layer == 0 ? h->cfg.m0 : h->cfg.m;
+        std::vector<uint32_t> selected;
+        for (size_t i = 0; i < found.size() && i < m; i++) selected.push_back(found[i].id);
+        {
+            std::vector<uint32_t>& mine = h->nbr[node_id][layer];
+            mine.insert(mine.end(), selected.begin(), selected.end());
+            std::sort(mine.begin(), mine.end());
+        }
+        for (uint32_t nb : selected) {
+            std::vector<uint32_t>& lst = h->nbr[nb][layer];
+            lst.insert(std::upper_bound(lst.begin(), lst.end(), node_id), node_id);  // push + sort: stays id-ascending
+            if (lst.size() > m) {
+                const float* a = h->rows.data() + (size_t)nb * h->dim;
+                wd.clear();
+                for (uint32_t id : lst) wd.emplace_back(node_distance(h, id, a, h->mags[nb]), id);
+                std::stable_sort(wd.begin(), wd.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
+                lst.clear();
+                for (size_t i = 0; i < m; i++) lst.push_back(wd[i].second);
+                std::sort(lst.begin(), lst.end());
+            }
+        }
+        if (!found.empty()) cur = found[0].id;
+    }
+    if (node_level > current_max) {
+        h->entry = node_id;
+        h->max_layer = node_level;
+    }
+}
+
+void host_search_one(const nmn_hnsw* h, const float* q, uint32_t k, uint64_t ef, HostVisited& vis, uint64_t* ids, float* scores,
+                     uint32_t* count, uint64_t* evals) {
+    uint32_t c = 0;
+    if (h->entry != ~0ull) {
+        const float qmag = host_qmag(h, q);
+        uint32_t cur = (uint32_t)h->entry;
+        for (uint32_t layer = h->max_layer; layer >= 1; layer--) cur = host_greedy(h, q, qmag, cur, layer, evals);
+        std::vector<Ent> found;
+        host_search_layer(h, q, qmag, cur, std::max<uint64_t>(ef, k), 0, vis, found, evals);
+        for (; c < found.size() && c < k; c++) {
+            ids[c] = found[c].id;
+            scores[c] = to_similarity(h->cfg.distance_metric, found[c].d);
+        }
+    }
+    *count = c;
+    for (uint32_t i = c; i < k; i++) {
+        ids[i] = ~0ull;
+        scores[i] = -INFINITY;
+    }
+}
+
+nmn_status wait_in_flight(nmn_hnsw* h) {  // caller holds rw exclusively
+    std::lock_guard<std::mutex> lk(h->dev_mu);
+    for (hipEvent_t e : h->ev_pending) {
+        HN_TRY(hipEventSynchronize(e));
+        h->ev_free.push_back(e);
+    }
+    h->ev_pending.clear();
+    return NMN_OK;
+}
+
+// the adjacency as it sits in HBM: layer 0 [n][m0] + counts, upper layers [n_upper][up_layers][m] + counts + a row per node
+nmn_status upload_graph(nmn_hnsw* h) {
+    const size_t n = h->level.size();
+    const uint32_t m = h->cfg.m, m0 = h->cfg.m0;
+    std::vector<uint32_t> l0(n * (size_t)m0, kNone), l0cnt(n), upidx(n, kNone);
+    uint32_t n_upper = 0;
+    for (size_t i = 0; i < n; i++)
+        if (h->level[i] > 0) upidx[i] = n_upper++;
+    const uint32_t L = std::max<uint32_t>(h->max_layer, 1);
+    std::vector<uint32_t> up((size_t)n_upper * L * m, kNone), upcnt((size_t)n_upper * L, 0);
+    for (size_t i = 0; i < n; i++) {
+        const auto& a = h->nbr[i][0];
+        l0cnt[i] = (uint32_t)a.size();
+        std::copy(a.begin(), a.end(), l0.begin() + i * m0);
+        for (uint32_t l = 1; l <= h->level[i]; l++) {
+            const auto& b = h->nbr[i][l];
+            const size_t slot = (size_t)upidx[i] * L + (l - 1);
+            upcnt[slot] = (uint32_t)b.size();
+            std::copy(b.begin(), b.end(), up.begin() + slot * m);
+        }
+    }
+    bool synced = true;  // (the caller waited for every search in flight)
+    const hipStream_t none = (hipStream_t)-1;
+    HN_TRY(grow(h->d_l0, l0.size() * 4, none, &synced));
+    HN_TRY(grow(h->d_l0cnt, n * 4, none, &synced));
+    HN_TRY(grow(h->d_upidx, n * 4, none, &synced));
+    HN_TRY(grow(h->d_up, up.size() * 4, none, &synced));
+    HN_TRY(grow(h->d_upcnt, upcnt.size() * 4, none, &synced));
+    if (n) {
+        HN_TRY(hipMemcpy(h->d_l0.p, l0.data(), l0.size() * 4, hipMemcpyHostToDevice));
+        HN_TRY(hipMemcpy(h->d_l0cnt.p, l0cnt.data(), n * 4, hipMemcpyHostToDevice));
+        HN_TRY(hipMemcpy(h->d_upidx.p, upidx.data(), n * 4, hipMemcpyHostToDevice));
+    }
+    if (!up.empty()) {
+        HN_TRY(hipMemcpy(h->d_up.p, up.data(), up.size() * 4, hipMemcpyHostToDevice));
+        HN_TRY(hipMemcpy(h->d_upcnt.p, upcnt.data(), upcnt.size() * 4, hipMemcpyHostToDevice));
+    }
+    h->up_layers = L;
+    h->n_upper = n_upper;
+    return NMN_OK;
+}
+
+nmn_status ensure_vectors(nmn_hnsw* h, uint64_t need) {
+    if (h->vectors && need <= h->vec_cap) return NMN_OK;
+    uint64_t cap = std::max<uint64_t>(h->vec_cap, 1024);
+    while (cap < need) cap *= 2;
+    if (h->cfg.max_nodes > 0) cap = std::min<uint64_t>(cap, std::max<uint64_t>(h->cfg.max_nodes, need));
+    nmn_index_desc d{};
+    d.dim = h->dim;
+    d.capacity_rows = cap;
+    d.device = h->device;
+    nmn_index* nv = nullptr;
+    nmn_status st = nmn_index_create(&d, &nv);
+    if (st != NMN_OK) return st;
+    const uint64_t have = h->level.size();
+    if (have) {
+        st = nmn_index_upload(nv, h->rows.data(), 0, have);
+        if (st != NMN_OK) {
+            nmn_index_destroy(nv);
+            return st;
+        }
+    }
+    if (h->vectors) nmn_index_destroy(h->vectors);
+    h->vectors = nv;
+    h->vec_cap = cap;
+    return NMN_OK;
+}
+
+nmn_status record_search(nmn_hnsw* h, hipStream_t s) {
+    std::lock_guard<std::mutex> lk(h->dev_mu);
+    for (size_t i = 0; i < h->ev_pending.size();) {
+        if (hipEventQuery(h->ev_pending[i]) == hipSuccess) {
+            h->ev_free.push_back(h->ev_pending[i]);
+            h->ev_pending[i] = h->ev_pending.back();
+            h->ev_pending.pop_back();
+        } else {
+            i++;
+        }
+    }
+    (void)hipGetLastError();
+    hipEvent_t e = nullptr;
+    if (!h->ev_free.empty()) {
+        e = h->ev_free.back();
+        h->ev_free.pop_back();
+    } else {
+        HN_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    const hipError_t he = hipEventRecord(e, s);
+    if (he != hipSuccess) {
+        h->ev_free.push_back(e);
+        return set_error_hip(he, "nmn_hnsw_search_device");
+    }
+    h->ev_pending.push_back(e);
+    return NMN_OK;
+}
+
+// Enqueue the search of nq queries (device buffers) on s.  Caller holds rw (shared).  *sc_out: the stream's scratch, whose flags /
+// evals the host-buffer search reads back.
+nmn_status enqueue_search(nmn_hnsw* h, const float* q_dev, uint32_t nq, uint32_t k, uint32_t ef, uint64_t* o_ids, float* o_sc,
+                          uint32_t* o_cnt, hipStream_t s, nmn_hnsw::Scratch** sc_out) {
+    nmn_hnsw::Scratch* sc = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(h->dev_mu);
+        for (auto& x : h->scratch)
+            if (x->stream == s) sc = x.get();
+        if (!sc) {
+            h->scratch.push_back(std::make_unique<nmn_hnsw::Scratch>());
+            sc = h->scratch.back().get();
+            sc->stream = s;
+        }
+    }
+    if (sc_out) *sc_out = sc;
+    std::lock_guard<std::mutex> slk(sc->mu);
+    const uint32_t n = (uint32_t)h->level.size();
+    const uint32_t ef_eff = std::max<uint32_t>(ef ? ef : h->cfg.ef_search, k);  // hnsw.rs:2102
+    const uint32_t vwords = std::max<uint32_t>((n + 31) / 32, 1);
+    const uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(nq, (256ull << 20) / ((uint64_t)vwords * 4)));
+    // heaps of the first launch (LDS) and of the spill launch (global memory)
+    const uint32_t res_need = std::min<uint32_t>(ef_eff, std::max<uint32_t>(n, 1)) + 1;
+    const uint32_t rmax = h->lds_rcap ? h->lds_rcap : kLdsResultsMax;
+    const bool lds_ok = res_need <= rmax + 1;
+    uint32_t ccap = h->lds_ccap ? h->lds_ccap : std::min<uint32_t>(kLdsCandMax, std::max<uint32_t>(1024, 16 * std::min<uint32_t>(ef_eff, 4096)));
+    if (h->dim > 4096) ccap = std::min<uint32_t>(ccap, 2048);   // (64 KiB of LDS: a long query leaves less for the heap)
+    ccap = std::min<uint32_t>(ccap, std::max<uint32_t>(n, 1));  // (never more than the proven bound)
+    const uint32_t qlds = (h->dim + 7u) & ~7u;
+    const uint32_t s_rcap = res_need, s_ccap = std::max<uint32_t>(n, 1);
+    const uint64_t region = (uint64_t)s_rcap + s_ccap;
+    const uint32_t regions = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint32_t>(chunk, 64), (256ull << 20) / (region * sizeof(Ent))));
+    bool synced = false;
+    HN_TRY(grow(sc->vis, (size_t)chunk * vwords * 4, s, &synced));
+    HN_TRY(grow(sc->flags, (size_t)nq * 4, s, &synced));
+    HN_TRY(grow(sc->evals, (size_t)nq * 4, s, &synced));
+    HN_TRY(grow(sc->spill, (size_t)regions * region * sizeof(Ent), s, &synced));
+    SearchArgs a{};
+    a.g.corpus = h->vectors ? h->vectors->corpus : nullptr;
+    a.g.norms = h->vectors ? h->vectors->norms : nullptr;
+    a.g.l0 = (const uint32_t*)h->d_l0.p;
+    a.g.l0cnt = (const uint32_t*)h->d_l0cnt.p;
+    a.g.up_idx = (const uint32_t*)h->d_upidx.p;
+    a.g.up = (const uint32_t*)h->d_up.p;
+    a.g.upcnt = (const uint32_t*)h->d_upcnt.p;
+    a.g.ld = h->vectors ? h->vectors->ld : 0;
+    a.g.dim = h->dim;
+    a.g.m = h->cfg.m;
+    a.g.m0 = h->cfg.m0;
+    a.g.up_layers = h->up_layers;
+    a.g.n = n;
+    a.g.entry = n ? (uint32_t)h->entry : kNone;
+    a.g.max_layer = h->max_layer;
+    a.g.metric = h->cfg.distance_metric;
+    a.k = k;
+    a.ef = ef_eff;
+    a.qlds = qlds;
+    a.vwords = vwords;
+    a.visited = (uint32_t*)sc->vis.p;
+    a.spill = (Ent*)sc->spill.p;
+    for (uint32_t q0 = 0; q0 < nq; q0 += chunk) {
+        const uint32_t nb = std::min<uint32_t>(chunk, nq - q0);
+        a.queries = q_dev + (size_t)q0 * h->dim;
+        a.nq = nb;
+        a.flags = (uint32_t*)sc->flags.p + q0;
+        a.evals = (uint32_t*)sc->evals.p + q0;
+        a.out_ids = o_ids + (size_t)q0 * k;
+        a.out_scores = o_sc + (size_t)q0 * k;
+        a.out_counts = o_cnt + q0;
+        HN_TRY(hipMemsetAsync(sc->vis.p, 0, (size_t)nb * vwords * 4, s));
+        const size_t fixed = (size_t)qlds * 4 + 32 * 4 + 32 * 4 + 4 * 4;
+        if (lds_ok || n == 0) {
+            HN_TRY(hipMemsetAsync(a.flags, 0, (size_t)nb * 4, s));
+            a.rcap = res_need;
+            a.ccap = ccap;
+            const size_t lds = fixed + ((size_t)a.rcap + a.ccap) * sizeof(Ent);
+            hipLaunchKernelGGL(hnsw_search_kernel<false>, dim3(nb), dim3(64), lds, s, a);
+            HN_TRY(hipGetLastError());
+        } else {  // a results heap no wave can keep in LDS: every query goes to the spill launch
+            HN_TRY(hipMemsetD32Async((hipDeviceptr_t)a.flags, 1, nb, s));
+        }
+        a.rcap = s_rcap;
+        a.ccap = s_ccap;
+        hipLaunchKernelGGL(hnsw_search_kernel<true>, dim3(std::min(regions, nb)), dim3(64), fixed, s, a);
+        HN_TRY(hipGetLastError());
+    }
+    return NMN_OK;
+}
+
+nmn_status check_cfg(const nmn_hnsw_config* c) {
+    if (c->storage != NMN_HNSW_STORAGE_DENSE)
+        return set_error(NMN_ERR_CONFIGURATION, "HNSW: only HNSWStorageStrategy::Dense is served (Auto / Quantized are out of scope)");
+    if (c->distance_metric < NMN_METRIC_COSINE || c->distance_metric > NMN_METRIC_DOT_PRODUCT)
+        return set_error(NMN_ERR_CONFIGURATION, "HNSW: distance_metric must be Cosine, Euclidean or DotProduct");
+    if (c->m == 0 || c->m0 == 0 || c->m > 4096 || c->m0 > 4096) return set_error(NMN_ERR_CONFIGURATION, "HNSW: m / m0 out of range");
+    return NMN_OK;
+}
+
+void fill_cfg(nmn_hnsw_config* c, uint32_t m, uint32_t efc, uint32_t efs) {
+    memset(c, 0, sizeof *c);
+    c->m = m;
+    c->m0 = 2 * m;
+    c->ef_construction = efc;
+    c->ef_search = efs;
+    c->ml = 1.0 / std::log((double)m);
+    c->sparsity_threshold = 0.5f;
+    c->max_nodes = 10000000ull;
+    c->distance_metric = NMN_METRIC_COSINE;
+    c->storage = NMN_HNSW_STORAGE_DENSE;
+}
+
+bool host_search_forced() {
+    const char* e = getenv("NMN_HNSW_HOST_SEARCH");
+    return e && e[0] == '1';
+}
+
+}  // namespace
+
+extern "C" void nmn_hnsw_config_default(nmn_hnsw_config* c) {
+    if (c) fill_cfg(c, 16, 200, 50);
+}
+extern "C" void nmn_hnsw_config_high_recall(nmn_hnsw_config* c) {
+    if (c) fill_cfg(c, 32, 400, 200);
+}
+extern "C" void nmn_hnsw_config_high_speed(nmn_hnsw_config* c) {
+    if (c) fill_cfg(c, 8, 100, 20);
+}
+
+extern "C" nmn_status nmn_hnsw_create(const nmn_hnsw_config* cfg, uint32_t dim, uint64_t capacity_hint, int32_t device, nmn_hnsw** out) {
+    if (!cfg || !out) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    *out = nullptr;
+    if (dim == 0) return set_error(NMN_ERR_EMPTY_VECTOR, "dim == 0");
+    if (dim > kMaxDim) return set_error(NMN_ERR_CONFIGURATION, "HNSW: dimension above 8192 (the query is kept in LDS)");
+    nmn_status st = check_cfg(cfg);
+    if (st != NMN_OK) return st;
+    auto h = std::make_unique<nmn_hnsw>();
+    h->cfg = *cfg;
+    h->dim = dim;
+    h->device = device;
+    h->vec_cap = 0;
+    {
+        // the flat index fixes the device (and fails with NMN_ERR_NO_DEVICE where there is none)
+        const uint64_t cap0 = std::max<uint64_t>(capacity_hint, 1);
+        h->vec_cap = 0;
+        nmn_index_desc d{};
+        d.dim = dim;
+        d.capacity_rows = cfg->max_nodes > 0 ? std::min<uint64_t>(cap0, cfg->max_nodes) : cap0;
+        d.device = device;
+        st = nmn_index_create(&d, &h->vectors);
+        if (st != NMN_OK) return st;
+        h->vec_cap = d.capacity_rows;
+        h->device = h->vectors->device;
+    }
+    HN_TRY(hipSetDevice(h->device));
+    HN_TRY(hipStreamCreateWithFlags(&h->host_stream, hipStreamNonBlocking));
+    *out = h.release();
+    return NMN_OK;
+}
+
+extern "C" nmn_status nmn_hnsw_destroy(nmn_hnsw* h) {
+    if (!h) return NMN_OK;
+    (void)hipSetDevice(h->device);
+    {
+        std::unique_lock<std::shared_mutex> g(h->rw);
+        (void)wait_in_flight(h);
+        if (h->host_stream) (void)hipStreamSynchronize(h->host_stream);
+    }
+    for (hipEvent_t e : h->ev_free) (void)hipEventDestroy(e);
+    for (auto& s : h->scratch) {
+        drop(s->vis);
+        drop(s->flags);
+        drop(s->evals);
+        drop(s->spill);
+    }
+    for (DevBuf* b : {&h->d_l0, &h->d_l0cnt, &h->d_upidx, &h->d_up, &h->d_upcnt, &h->hq, &h->hids, &h->hsc, &h->hcnt}) drop(*b);
+    if (h->host_stream) (void)hipStreamDestroy(h->host_stream);
+    if (h->vectors) nmn_index_destroy(h->vectors);
+    delete h;
+    return NMN_OK;
+}
+
+extern "C" nmn_status nmn_hnsw_insert(nmn_hnsw* h, const float* rows_host, uint64_t n, uint64_t* ids_out) {
+    if (!h || (!rows_host && n)) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (n == 0) return NMN_OK;
+    std::unique_lock<std::shared_mutex> g(h->rw);
+    const uint64_t have = h->level.size();
+    if (h->cfg.max_nodes > 0 && have + n > h->cfg.max_nodes) {  // hnsw.rs:1947-1955, text of 102-107; the batch is all or nothing
+        char buf[160];
+        snprintf(buf, sizeof buf, "HNSW index at capacity: %llu nodes (limit: %llu)", (unsigned long long)have,
+                 (unsigned long long)h->cfg.max_nodes);
+        return set_error(NMN_ERR_CAPACITY, buf);
+    }
+    if (have + n >= (uint64_t)kNone) return set_error(NMN_ERR_CAPACITY, "HNSW: node ids are 32 bits on the device");
+    HN_TRY(hipSetDevice(h->device));
+    nmn_status st = wait_in_flight(h);
+    if (st != NMN_OK) return st;
+    {
+        std::lock_guard<std::mutex> hl(h->host_mu);
+        HN_TRY(hipStreamSynchronize(h->host_stream));
+    }
+    h->rows.insert(h->rows.end(), rows_host, rows_host + n * h->dim);
+    st = ensure_vectors(h, have + n);
+    if (st == NMN_OK) st = nmn_index_upload(h->vectors, rows_host, have, n);
+    if (st != NMN_OK) {
+        h->rows.resize(have * h->dim);
+        return st;
+    }
+    static thread_local HostVisited vis;
+    for (uint64_t i = 0; i < n; i++) {
+        const float* v = h->rows.data() + (have + i) * h->dim;
+        h->mags.push_back(sqrtf(h_dot8(v, v, h->dim)));  // simd::magnitude, hnsw.rs:198-229
+        host_insert_node(h, (uint32_t)(have + i), vis);
+        if (ids_out) ids_out[i] = have + i;
+    }
+    return upload_graph(h);
+}
+
+extern "C" uint64_t nmn_hnsw_len(const nmn_hnsw* h) { return h ? h->level.size() : 0; }
+extern "C" uint32_t nmn_hnsw_dim(const nmn_hnsw* h) { return h ? h->dim : 0; }
+extern "C" uint64_t nmn_hnsw_entry_point(const nmn_hnsw* h) { return h ? h->entry : ~0ull; }
+extern "C" uint32_t nmn_hnsw_max_layer(const nmn_hnsw* h) { return h ? h->max_layer : 0; }
+extern "C" nmn_index* nmn_hnsw_vectors(nmn_hnsw* h) { return h ? h->vectors : nullptr; }
+
+extern "C" nmn_status nmn_hnsw_levels(nmn_hnsw* h, uint32_t* out, uint64_t cap) {
+    if (!h || !out) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    std::shared_lock<std::shared_mutex> g(h->rw);
+    if (cap < h->level.size()) return set_error(NMN_ERR_BUFFER_TOO_SMALL, "nmn_hnsw_levels");
+    for (size_t i = 0; i < h->level.size(); i++) out[i] = h->level[i];
+    return NMN_OK;
+}
+
+extern "C" nmn_status nmn_hnsw_neighbors(nmn_hnsw* h, uint64_t node, uint32_t layer, uint64_t* out, uint32_t cap, uint32_t* count) {
+    if (!h || !count) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    std::shared_lock<std::shared_mutex> g(h->rw);
+    if (node >= h->level.size()) return set_error(NMN_ERR_NOT_FOUND, "HNSW: no such node");
+    if (layer > h->level[node]) {
+        *count = 0;
+        return NMN_OK;
+    }
+    const auto& l = h->nbr[node][layer];
+    *count = (uint32_t)l.size();
+    if (!out) return NMN_OK;
+    if (cap < l.size()) return set_error(NMN_ERR_BUFFER_TOO_SMALL, "nmn_hnsw_neighbors");
+    for (size_t i = 0; i < l.size(); i++) out[i] = l[i];
+    return NMN_OK;
+}
+
+extern "C" nmn_status nmn_hnsw_set_heap_capacity(nmn_hnsw* h, uint32_t results, uint32_t candidates) {
+    if (!h) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (results > kLdsResultsMax || candidates > kLdsCandMax) return set_error(NMN_ERR_INVALID_ARGUMENT, "HNSW: beyond the LDS heaps");
+    std::unique_lock<std::shared_mutex> g(h->rw);
+    h->lds_rcap = results;
+    h->lds_ccap = candidates;
+    return NMN_OK;
+}
+
+extern "C" uint64_t nmn_hnsw_hbm_bytes(nmn_hnsw* h) {
+    if (!h) return 0;
+    std::shared_lock<std::shared_mutex> g(h->rw);
+    uint64_t t = h->d_l0.cap + h->d_l0cnt.cap + h->d_upidx.cap + h->d_up.cap + h->d_upcnt.cap;
+    uint64_t a = 0, b = 0, c = 0;
+    if (h->vectors && nmn_index_hbm_bytes(h->vectors, &a, &b, &c) == NMN_OK) t += a + b + c;
+    return t;
+}
+
+extern "C" nmn_status nmn_hnsw_search_device(nmn_hnsw* h, const float* queries_dev, uint32_t nq, uint32_t k, uint32_t ef,
+                                             uint64_t* out_ids_dev, float* out_scores_dev, uint32_t* out_counts_dev, void* stream) {
+    if (!h) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (k == 0) return set_error(NMN_ERR_INVALID_TOP_K, "k == 0");
+    if (nq == 0) return NMN_OK;
+    if (!queries_dev || !out_ids_dev || !out_scores_dev || !out_counts_dev) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    std::shared_lock<std::shared_mutex> g(h->rw);
+    HN_TRY(hipSetDevice(h->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    nmn_status st = enqueue_search(h, queries_dev, nq, k, ef, out_ids_dev, out_scores_dev, out_counts_dev, s, nullptr);
+    if (st != NMN_OK) return st;
+    return record_search(h, s);
+}
+
+extern "C" nmn_status nmn_hnsw_search(nmn_hnsw* h, const float* queries, uint32_t nq, uint32_t k, uint32_t ef, uint64_t* out_ids,
+                                      float* out_scores, uint32_t* out_counts, nmn_search_stats* stats) {
+    if (!h) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (k == 0) return set_error(NMN_ERR_INVALID_TOP_K, "k == 0");
+    if (stats) {
+        memset(stats, 0, sizeof *stats);
+        stats->scan_ms = stats->total_ms = -1.0f;
+    }
+    if (nq == 0) return NMN_OK;
+    if (!queries || !out_ids || !out_scores || !out_counts) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    std::shared_lock<std::shared_mutex> g(h->rw);
+    const uint64_t ef_eff = ef ? ef : h->cfg.ef_search;
+    uint64_t evals = 0;
+    uint32_t spilled = 0;
+    if (host_search_forced()) {
+        static thread_local HostVisited vis;
+        for (uint32_t q = 0; q < nq; q++)
+            host_search_one(h, queries + (size_t)q * h->dim, k, ef_eff, vis, out_ids + (size_t)q * k, out_scores + (size_t)q * k,
+                            out_counts + q, &evals);
+    } else {
+        std::lock_guard<std::mutex> hl(h->host_mu);  // host callers take turns on the handle's own stream and staging
+        HN_TRY(hipSetDevice(h->device));
+        hipStream_t s = h->host_stream;
+        bool synced = true;  // (every earlier host call ended with a wait)
+        const hipStream_t none = (hipStream_t)-1;
+        HN_TRY(grow(h->hq, (size_t)nq * h->dim * 4, none, &synced));
+        HN_TRY(grow(h->hids, (size_t)nq * k * 8, none, &synced));
+        HN_TRY(grow(h->hsc, (size_t)nq * k * 4, none, &synced));
+        HN_TRY(grow(h->hcnt, (size_t)nq * 4, none, &synced));
+        HN_TRY(hipMemcpyAsync(h->hq.p, queries, (size_t)nq * h->dim * 4, hipMemcpyHostToDevice, s));
+        nmn_hnsw::Scratch* sc = nullptr;
+        nmn_status st = enqueue_search(h, (const float*)h->hq.p, nq, k, ef, (uint64_t*)h->hids.p, (float*)h->hsc.p, (uint32_t*)h->hcnt.p, s, &sc);
+        if (st != NMN_OK) return st;
+        std::vector<uint32_t> fl(nq), ev(nq);
+        HN_TRY(hipMemcpyAsync(out_ids, h->hids.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost, s));
+        HN_TRY(hipMemcpyAsync(out_scores, h->hsc.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, s));
+        HN_TRY(hipMemcpyAsync(out_counts, h->hcnt.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+        HN_TRY(hipMemcpyAsync(fl.data(), sc->flags.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+        HN_TRY(hipMemcpyAsync(ev.data(), sc->evals.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+        HN_TRY(hipStreamSynchronize(s));
+        static thread_local HostVisited vis;
+        for (uint32_t q = 0; q < nq; q++) {
+            if (fl[q] == 1u) {  // the spill launch could not answer it (cannot happen while its heap holds n entries): the host walk does
+                uint64_t e2 = 0;
+                host_search_one(h, queries + (size_t)q * h->dim, k, ef_eff, vis, out_ids + (size_t)q * k, out_scores + (size_t)q * k,
+                                out_counts + q, &e2);
+                ev[q] = (uint32_t)e2;
+                spilled++;
+            } else if (fl[q] == 2u) {
+                spilled++;
+            }
+            evals += ev[q];
+        }
+    }
+    if (stats) {
+        stats->rows_scanned = evals;
+        stats->bytes_scanned = evals * h->dim * 4;
+        stats->fallback_queries = spilled;
+        stats->sweep_kind = h->level.empty() ? NMN_SWEEP_NONE : NMN_SWEEP_GRAPH;
+        stats->sweep_launches = host_search_forced() ? 0 : 2;
+    }
+    return NMN_OK;
+}

@@ -96,6 +96,13 @@ ENGINE_SIGNATURES = {
     "nmn_engine_ivf_centroids": (C.c_int32, [vp, vp, C.c_uint64]),
     "nmn_engine_ivf_cluster_sizes": (C.c_int32, [vp, vp]),
     "nmn_engine_search_with_ivf": (C.c_int32, [vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(vp)]),
+    "nmn_engine_build_hnsw_index": (C.c_int32, [vp, vp, C.POINTER(vp)]),
+    "nmn_engine_hnsw_free": (None, [vp]),
+    "nmn_engine_hnsw_len": (C.c_uint64, [vp]),
+    "nmn_engine_hnsw_key": (C.c_char_p, [vp, C.c_uint64]),
+    "nmn_engine_hnsw_index": (vp, [vp]),
+    "nmn_engine_search_with_hnsw": (C.c_int32, [vp, vp, vp, C.c_uint64, C.c_uint64, C.POINTER(vp)]),
+    "nmn_engine_estimate_hnsw_memory": (C.c_int32, [vp, C.POINTER(C.c_uint64)]),
     "nmn_engine_set_entity_embedding": (C.c_int32, [vp, C.c_char_p, vp, C.c_uint64]),
     "nmn_engine_get_entity_embedding": (C.c_int32, [vp, C.c_char_p, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "nmn_engine_entity_has_embedding": (C.c_int32, [vp, C.c_char_p]),
@@ -446,6 +453,42 @@ class IVFIndex:
             pass
 
 
+class HNSWIndex:
+    """The (HNSWIndex, key_mapping) pair build_hnsw_index returns; rows and graph live on the GPU (a snapshot of the engine)."""
+
+    def __init__(self, handle, config):
+        self._h = handle
+        self.config = config
+        n = int(_lib().nmn_engine_hnsw_len(handle))
+        self.keys = [_lib().nmn_engine_hnsw_key(handle, i).decode() for i in range(n)]
+
+    def __len__(self):
+        return int(_lib().nmn_engine_hnsw_len(self._h))
+
+    def gpu(self):
+        """the index as a neumann_amd.GpuHnsw (levels, neighbors, search, search_device); owned by this object.  None when empty."""
+        from .hnsw import GpuHnsw
+        h = _lib().nmn_engine_hnsw_index(self._h)
+        if not h:
+            return None
+        g = GpuHnsw.__new__(GpuHnsw)
+        g._lib, g._h, g.config, g._borrowed = _capi.load(), C.c_void_p(h), self.config, self
+        g.dim = int(g._lib.nmn_hnsw_dim(g._h))
+        g.close = lambda: None
+        return g
+
+    def close(self):
+        if self._h:
+            _lib().nmn_engine_hnsw_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class FilterCondition:
     """vector_engine::FilterCondition (lib.rs:296-340), built from the same constructors."""
 
@@ -704,6 +747,38 @@ class VectorEngine:
         so = _storage_struct(options.storage)
         out = C.c_uint64()
         _check(_lib().nmn_engine_estimate_ivf_memory(self._h, C.byref(co), C.byref(so), C.byref(out)))
+        return int(out.value)
+
+    # ---- HNSW (lib.rs:2378-2550) ----
+    def build_hnsw_index(self, config=None):
+        """-> (HNSWIndex, key_mapping) like the reference: dense storage, the reference's graph, searched on the GPU."""
+        from .hnsw import HNSWConfig
+        cfg = config or HNSWConfig()
+        cc = cfg._c()
+        h = vp()
+        _check(_lib().nmn_engine_build_hnsw_index(self._h, C.byref(cc), C.byref(h)))
+        index = HNSWIndex(h, cfg)
+        return index, index.keys
+
+    def build_hnsw_index_default(self):
+        return self.build_hnsw_index(None)
+
+    def search_with_hnsw(self, index, key_mapping, query, top_k):
+        """search_with_hnsw (lib.rs:2516-2550)"""
+        a, p, n = _vec(query)
+        h = vp()
+        _check(_lib().nmn_engine_search_with_hnsw(self._h, index._h, p, n, int(top_k), C.byref(h)))
+        res = self._take_results(h)
+        if key_mapping is not index.keys and list(key_mapping) != index.keys:
+            # `key_mapping.get(node_id)` (lib.rs:2543-2548) with a caller-supplied mapping
+            ids = {k: i for i, k in enumerate(index.keys)}
+            res = [SearchResult(key_mapping[ids[r.key]], r.score) for r in res if ids[r.key] < len(key_mapping)]
+        return res
+
+    def estimate_hnsw_memory(self):
+        """estimate_hnsw_memory (lib.rs:2489-2509); host arithmetic."""
+        out = C.c_uint64()
+        _check(_lib().nmn_engine_estimate_hnsw_memory(self._h, C.byref(out)))
         return int(out.value)
 
     # -- index persistence (lib.rs:3733-4000) -----------------------------------------------------

@@ -1,0 +1,182 @@
+"""HNSW graph index searched on the GPU — host wrapper of `nmn_hnsw_*` (include/neumann_gpu.h).
+
+Mirrors `tensor_store::HNSWIndex` with dense storage (tensor_store/src/hnsw.rs:1554-2335): `insert` builds the graph on the
+host in the reference's order (level generator, search_layer with ef_construction, stable pruning), `search` /
+`search_device` run `search_with_ef` as one HIP kernel launch per chunk of queries, one query per wave.  Answers are the
+reference's bit for bit, ties included (docs/hnsw.md)."""
+import ctypes as C
+import math
+
+import numpy as np
+
+from . import _capi
+from .flat_index import DistanceMetric, GpuFlatIndex, _stream_ptr
+
+
+class HNSWConfig:
+    """HNSWConfig (hnsw.rs:1434-1551)."""
+
+    def __init__(self, m=16, m0=None, ef_construction=200, ef_search=50, ml=None, sparsity_threshold=0.5, max_nodes=10_000_000,
+                 distance_metric=DistanceMetric.Cosine, storage="dense"):
+        self.m = int(m)
+        self.m0 = 2 * self.m if m0 is None else int(m0)
+        self.ef_construction = int(ef_construction)
+        self.ef_search = int(ef_search)
+        self.ml = 1.0 / math.log(self.m) if ml is None else float(ml)
+        self.sparsity_threshold = float(sparsity_threshold)
+        self.max_nodes = int(max_nodes)
+        self.distance_metric = DistanceMetric(int(distance_metric))
+        self.storage = storage  # HNSWStorageStrategy: only "dense" is served ("auto" / "quantized" are refused)
+
+    @classmethod
+    def default(cls):
+        return cls()
+
+    @classmethod
+    def high_recall(cls):  # hnsw.rs:1508-1519
+        return cls(m=32, m0=64, ef_construction=400, ef_search=200)
+
+    @classmethod
+    def high_speed(cls):  # hnsw.rs:1523-1534
+        return cls(m=8, m0=16, ef_construction=100, ef_search=20)
+
+    def with_distance_metric(self, metric):  # hnsw.rs:1547-1550
+        self.distance_metric = DistanceMetric(int(metric))
+        return self
+
+    def _c(self):
+        try:
+            storage = {"dense": _capi.HNSW_STORAGE_DENSE, "auto": _capi.HNSW_STORAGE_AUTO,
+                       "quantized": _capi.HNSW_STORAGE_QUANTIZED}[self.storage]
+        except KeyError:
+            raise _capi.NeumannGpuError(_capi.ERR_CONFIGURATION, f"unknown HNSW storage strategy {self.storage!r}")
+        return _capi.HnswConfig(m=self.m, m0=self.m0, ef_construction=self.ef_construction, ef_search=self.ef_search, ml=self.ml,
+                                max_nodes=self.max_nodes, sparsity_threshold=self.sparsity_threshold,
+                                distance_metric=int(self.distance_metric), storage=storage, reserved=0)
+
+    @classmethod
+    def _from_c(cls, c):
+        return cls(m=c.m, m0=c.m0, ef_construction=c.ef_construction, ef_search=c.ef_search, ml=c.ml,
+                   sparsity_threshold=c.sparsity_threshold, max_nodes=c.max_nodes, distance_metric=c.distance_metric)
+
+
+class GpuHnsw:
+    def __init__(self, dim, config=None, capacity_hint=0, device=-1):
+        self._lib = _capi.load()
+        self._h = None
+        self.config = config or HNSWConfig()
+        self.dim = int(dim)
+        cfg = self.config._c()
+        h = C.c_void_p()
+        _capi.check(self._lib.nmn_hnsw_create(C.byref(cfg), self.dim, int(capacity_hint), int(device), C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.nmn_hnsw_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        return int(self._lib.nmn_hnsw_len(self._h))
+
+    @property
+    def entry_point(self):
+        """node id of the entry point, None while the index is empty"""
+        e = int(self._lib.nmn_hnsw_entry_point(self._h))
+        return None if e == 0xFFFFFFFFFFFFFFFF else e
+
+    @property
+    def max_layer(self):
+        return int(self._lib.nmn_hnsw_max_layer(self._h))
+
+    @property
+    def hbm_bytes(self):
+        return int(self._lib.nmn_hnsw_hbm_bytes(self._h))
+
+    def insert(self, rows):
+        """HNSWIndex::insert for each row in order; returns the node ids."""
+        r = np.ascontiguousarray(rows, dtype=np.float32)
+        if r.ndim == 1:
+            r = r[None, :]
+        if r.shape[1] != self.dim:
+            raise _capi.NeumannGpuError(_capi.ERR_DIMENSION_MISMATCH, f"expected {self.dim}, got {r.shape[1]}")
+        ids = np.empty(r.shape[0], dtype=np.uint64)
+        _capi.check(self._lib.nmn_hnsw_insert(self._h, C.c_void_p(r.ctypes.data), r.shape[0], C.c_void_p(ids.ctypes.data)))
+        return ids
+
+    def levels(self):
+        out = np.empty(len(self), dtype=np.uint32)
+        _capi.check(self._lib.nmn_hnsw_levels(self._h, C.c_void_p(out.ctypes.data), out.size))
+        return out
+
+    def neighbors(self, node, layer):
+        """neighbour ids of `node` on `layer`, ascending (empty above the node's level)"""
+        cap = max(self.config.m, self.config.m0)
+        out = np.empty(cap, dtype=np.uint64)
+        cnt = C.c_uint32()
+        _capi.check(self._lib.nmn_hnsw_neighbors(self._h, int(node), int(layer), C.c_void_p(out.ctypes.data), cap, C.byref(cnt)))
+        return out[:cnt.value].copy()
+
+    def vectors(self):
+        """the flat index holding the rows (node id == row), valid until the next insert"""
+        return GpuFlatIndex._view(self._lib.nmn_hnsw_vectors(self._h), self)
+
+    def set_heap_capacity(self, results=0, candidates=0):
+        """entries of the two heaps a wave keeps in LDS (0 = default); what outgrows them goes to the spill launch"""
+        _capi.check(self._lib.nmn_hnsw_set_heap_capacity(self._h, int(results), int(candidates)))
+
+    def search(self, queries, k, ef=None, with_stats=False):
+        """-> (ids u64 [nq,k], scores f32 [nq,k], counts u32 [nq]); HNSWIndex::search_with_ef per query (ef None: ef_search)."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.shape[1] != self.dim:
+            raise _capi.NeumannGpuError(_capi.ERR_DIMENSION_MISMATCH, f"expected {self.dim}, got {q.shape[1]}")
+        nq, k = q.shape[0], int(k)
+        ids = np.empty((nq, max(k, 1)), dtype=np.uint64)
+        sc = np.empty((nq, max(k, 1)), dtype=np.float32)
+        counts = np.empty(nq, dtype=np.uint32)
+        st = _capi.SearchStats()
+        _capi.check(self._lib.nmn_hnsw_search(self._h, C.c_void_p(q.ctypes.data), nq, k, 0 if ef is None else int(ef),
+                                              C.c_void_p(ids.ctypes.data), C.c_void_p(sc.ctypes.data),
+                                              C.c_void_p(counts.ctypes.data), C.byref(st)))
+        return (ids, sc, counts, st) if with_stats else (ids, sc, counts)
+
+    def search_device(self, queries_t, k, ef=None, out=None, stream=None):
+        """`search` with torch device tensors, in stream order (nmn_hnsw_search_device): enqueued on `stream` (None: torch's
+        current stream), returns without waiting.  Returns (ids int64 [nq,k] holding the u64 bit pattern, -1 = unused slot;
+        scores f32 [nq,k]; counts int32 [nq]), allocated on the queries' device unless `out` supplies them."""
+        import torch
+
+        if not (isinstance(queries_t, torch.Tensor) and queries_t.is_cuda):
+            raise _capi.NeumannGpuError(_capi.ERR_INVALID_ARGUMENT, "queries must be a device tensor")
+        if queries_t.dtype != torch.float32 or not queries_t.is_contiguous():
+            raise _capi.NeumannGpuError(_capi.ERR_INVALID_ARGUMENT, "queries must be contiguous float32")
+        if queries_t.dim() == 1:
+            queries_t = queries_t[None, :]
+        nq, k = queries_t.shape[0], int(k)
+        if queries_t.shape[1] != self.dim:
+            raise _capi.NeumannGpuError(_capi.ERR_DIMENSION_MISMATCH, f"expected {self.dim}")
+        if out is None:
+            kk = max(k, 1)
+            ids = torch.empty((nq, kk), dtype=torch.int64, device=queries_t.device)
+            sc = torch.empty((nq, kk), dtype=torch.float32, device=queries_t.device)
+            counts = torch.empty((nq,), dtype=torch.int32, device=queries_t.device)
+        else:
+            ids, sc, counts = out
+        _capi.check(self._lib.nmn_hnsw_search_device(
+            self._h, C.c_void_p(queries_t.data_ptr()), nq, k, 0 if ef is None else int(ef), C.c_void_p(ids.data_ptr()),
+            C.c_void_p(sc.data_ptr()), C.c_void_p(counts.data_ptr()), _stream_ptr(stream)))
+        return ids, sc, counts

@@ -1,0 +1,144 @@
+#!/usr/bin/env python
+"""The GPU graph walk (nmn_hnsw_search / nmn_hnsw_search_device) against the exhaustive search over the same rows
+(nmn_index_search through nmn_hnsw_vectors) and against the host walk (NMN_HNSW_HOST_SEARCH=1), on one MI355X and one
+synthetic corpus (docs/hnsw.md §6).
+
+  timeout -k 10 1100 python tools/hnsw_bench.py --rows 1000000 --dim 128 && \\
+  timeout -k 10 1100 python tools/hnsw_bench.py --rows 200000 --dim 768
+  python tools/hnsw_bench.py --launch-calls N ...   # N device calls and nothing else (for `rocprofv3 --kernel-trace --stats -- ...`)
+
+(each corpus a process of its own under its own time limit, chained: a failure ends the chain).  The graph is built on the host
+by nmn_hnsw_insert — one thread, the reference's sequential algorithm — and `build_s` says how long that took.  For ef_search 50
+and 200 at k = 10 it reports, as one JSON line:
+  gpu_ms_nq1                  a lone nmn_hnsw_search call, host buffers (wall time, median of --calls)
+  gpu_ms_per_query_nq64/1024  the same call with 64 / 1024 queries, per query
+  dev_ms_per_query_nq64/1024  nmn_hnsw_search_device, HIP events around the call on its stream (median of --calls), per query
+  b2b_ms_per_query_nq64       --b2b device calls back to back on one stream, one synchronise at the end
+  flat_ms_nq1 / flat_ms_per_query_nq64/1024   nmn_index_search over the same rows, measured ALTERNATING with the walk
+  host_ms_per_query           the host walk, wall time per query over 64 queries
+  *_spread                    (max - min) / median over --repeats repetitions of the whole measurement
+  recall_at_10                of the walk against the exhaustive search (1024 queries)
+  evals_per_query             distance evaluations per query (nmn_search_stats.rows_scanned)
+and checks that device, host-buffer and host-walk answers are the same bits."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=1_000_000)
+    ap.add_argument("--dim", type=int, default=128)
+    ap.add_argument("--preset", default="default", choices=["default", "high_recall", "high_speed"])
+    ap.add_argument("--metric", type=int, default=0)
+    ap.add_argument("--calls", type=int, default=50)
+    ap.add_argument("--b2b", type=int, default=100)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--k", type=int, default=10)
+    ap.add_argument("--launch-calls", type=int, default=None)
+    args = ap.parse_args()
+    import torch
+    from neumann_amd import DistanceMetric, GpuHnsw, HNSWConfig, synth_rows
+
+    n, d, k = args.rows, args.dim, args.k
+    cfg = getattr(HNSWConfig, args.preset)().with_distance_metric(args.metric)
+    metric = DistanceMetric(args.metric)
+    Q = synth_rows(0x2F8, 0, 1024, d)
+    out = {"rows": n, "dim": d, "preset": args.preset, "metric": args.metric, "k": k}
+    with GpuHnsw(d, cfg, capacity_hint=n) as g:
+        t0 = time.perf_counter()
+        step = 50_000
+        for r0 in range(0, n, step):
+            g.insert(synth_rows(0x2F6, r0, min(step, n - r0), d))
+            print(f"built {min(r0 + step, n)} nodes in {time.perf_counter() - t0:.1f} s", file=sys.stderr, flush=True)
+        out["build_s"] = round(time.perf_counter() - t0, 1)
+        out["max_layer"], out["hbm_bytes"] = g.max_layer, g.hbm_bytes
+        flat = g.vectors()
+        s = torch.cuda.Stream()
+        qd = torch.from_numpy(Q).cuda()
+        if args.launch_calls is not None:
+            with torch.cuda.stream(s):
+                for _ in range(args.launch_calls):
+                    g.search_device(qd[:64], k, 50, stream=s)
+            s.synchronize()
+            out["device_calls"] = args.launch_calls
+            print(json.dumps(out), flush=True)
+            return
+        for ef in (50, 200):
+            r = {}
+            # warm every shape, and the three paths against each other
+            dev = {}
+            for nq in (1, 64, 1024):
+                o = (torch.empty((nq, k), dtype=torch.int64, device="cuda"), torch.empty((nq, k), dtype=torch.float32, device="cuda"),
+                     torch.empty((nq,), dtype=torch.int32, device="cuda"))
+                dev[nq] = o
+                g.search_device(qd[:nq], k, ef, out=o, stream=s)
+                g.search(Q[:nq], k, ef)
+                flat.search(Q[:nq], k, metric)
+            s.synchronize()
+            ids, sc, cnt, st = g.search(Q, k, ef, with_stats=True)
+            r["evals_per_query"] = round(st.rows_scanned / 1024, 1)
+            r["spilled_queries"] = int(st.fallback_queries)
+            same = np.array_equal(dev[1024][0].cpu().numpy().view(np.uint64), ids) and \
+                np.array_equal(dev[1024][1].cpu().numpy().view(np.uint32), sc.view(np.uint32))
+            os.environ["NMN_HNSW_HOST_SEARCH"] = "1"
+            try:
+                t0 = time.perf_counter()
+                hids, hsc, _ = g.search(Q[:64], k, ef)
+                r["host_ms_per_query"] = round((time.perf_counter() - t0) * 1e3 / 64, 4)
+            finally:
+                del os.environ["NMN_HNSW_HOST_SEARCH"]
+            same = same and np.array_equal(hids, ids[:64]) and np.array_equal(hsc.view(np.uint32), sc[:64].view(np.uint32))
+            r["device_host_buffer_and_host_walk_agree"] = bool(same)
+            ex_rows, _, _ = flat.search(Q, k, metric)
+            r["recall_at_10"] = round(float(np.mean([len(set(a.tolist()) & set(b.tolist())) / k for a, b in zip(ids, ex_rows)])), 4)
+            reps = {}
+            for _ in range(args.repeats):
+                m = {}
+                for nq, calls in ((1, args.calls), (64, args.calls), (1024, max(args.calls // 5, 5))):
+                    qs = Q[:nq]
+                    # the walk and the exhaustive search alternate call by call: both see the same machine state
+                    tw, tf = [], []
+                    for _ in range(calls):
+                        t0 = time.perf_counter()
+                        g.search(qs, k, ef)
+                        t1 = time.perf_counter()
+                        flat.search(qs, k, metric)
+                        t2 = time.perf_counter()
+                        tw.append(t1 - t0)
+                        tf.append(t2 - t1)
+                    name = "nq1" if nq == 1 else f"per_query_nq{nq}"
+                    m[f"gpu_ms_{name}"] = float(np.median(tw)) * 1e3 / nq
+                    m[f"flat_ms_{name}"] = float(np.median(tf)) * 1e3 / nq
+                    if nq > 1:
+                        ev = []
+                        for _ in range(calls):
+                            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                            e0.record(s)
+                            g.search_device(qd[:nq], k, ef, out=dev[nq], stream=s)
+                            e1.record(s)
+                            ev.append((e0, e1))
+                        s.synchronize()
+                        m[f"dev_ms_{name}"] = float(np.median([a.elapsed_time(b) for a, b in ev])) / nq
+                t0 = time.perf_counter()
+                for _ in range(args.b2b):
+                    g.search_device(qd[:64], k, ef, out=dev[64], stream=s)
+                s.synchronize()
+                m["b2b_ms_per_query_nq64"] = (time.perf_counter() - t0) * 1e3 / args.b2b / 64
+                for key, v in m.items():
+                    reps.setdefault(key, []).append(v)
+            for key, v in reps.items():
+                r[key] = round(float(np.median(v)), 5)
+                r[key + "_spread"] = round(float((max(v) - min(v)) / np.median(v)), 3)
+            out[f"ef{ef}"] = r
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()
