@@ -269,6 +269,23 @@ nmn_hnsw* nmn_engine_hnsw_index(nmn_engine_hnsw* h);
  * mapping dropped; scores are HNSWDistanceMetric::to_similarity of the index's metric */
 nmn_status nmn_engine_search_with_hnsw(nmn_engine* e, nmn_engine_hnsw* h, const float* q, uint64_t dim, uint64_t top_k,
                                        nmn_results** out);
+/* search_with_hnsw_and_metric (lib.rs:2560-2619): EmptyVector, InvalidTopK (no zero-magnitude rule), c = max(top_k * 2, 10)
+ * candidates from index.search(query, c), each re-scored as metric.to_similarity(metric.compute(query, CURRENT vector of its key))
+ * — a key that no longer exists is dropped —, stable sort by score descending, truncate(top_k).  Deadline checks after the walk
+ * and after the re-rank (SearchTimeout, operation "search_with_hnsw_and_metric").  A query of another dimension than the index
+ * is refused as by nmn_engine_search_with_hnsw; an unknown metric kind is NMN_ERR_CONFIGURATION.
+ * Two paths, one answer: while no store, delete or clear has touched the default collection since build_hnsw_index the handle's
+ * rows are the current vectors and the call is nmn_hnsw_search_metric (walk, re-rank, ordering in one stream-ordered chain);
+ * otherwise the walk runs with k = c, the current vectors of the surviving keys are gathered into a staging matrix (a vector
+ * of another length zero-padded, as is the query: from_dense drops zeros) and scored there by the same kernel
+ * (nmn_xmetric_score_host_rows: no index is built for it, and a vector longer than an index may be is scored all the same). */
+nmn_status nmn_engine_search_with_hnsw_and_metric(nmn_engine* e, nmn_engine_hnsw* h, const float* q, uint64_t dim, uint64_t top_k,
+                                                  const nmn_xmetric* metric, nmn_results** out);
+/* The same with a caller-supplied key_mapping (`key_mapping.get(*node_id)?`, lib.rs:2594: node ids at or past n_keys are dropped
+ * before the ordering); keys NULL = the handle's own mapping.  A supplied mapping always takes the gathering path. */
+nmn_status nmn_engine_search_with_hnsw_and_metric_mapped(nmn_engine* e, nmn_engine_hnsw* h, const float* q, uint64_t dim,
+                                                         uint64_t top_k, const nmn_xmetric* metric, const char* const* keys,
+                                                         uint64_t n_keys, nmn_results** out);
 /* estimate_hnsw_memory (lib.rs:2489-2509): count x d x 4 + count x 16 x 2 x 8 + count x 32; 0 for an empty engine.  Host
  * arithmetic, no device needed. */
 nmn_status nmn_engine_estimate_hnsw_memory(nmn_engine* e, uint64_t* out_bytes);

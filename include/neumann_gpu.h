@@ -654,6 +654,65 @@ nmn_index* nmn_hnsw_vectors(nmn_hnsw* h);
 /* Device memory the index holds: rows, magnitudes, mirrors, adjacency. */
 uint64_t nmn_hnsw_hbm_bytes(nmn_hnsw* h);
 
+/* ---- extended distance metrics: the re-rank of search_with_hnsw_and_metric ------------------------------------ */
+
+/* `tensor_store::DistanceMetric` (tensor_store/src/distance.rs:13-52), the ExtendedDistanceMetric of vector_engine.  Both
+ * vectors go through SparseVector::from_dense (a value is stored iff != 0.0); every sum is a sequential f64 sum over the
+ * merged stored positions, rounded once to f32 (sparse_vector.rs:414-443, 548-599, 795-1059).  docs/hnsw.md §8. */
+#define NMN_XMETRIC_COSINE 0            /* cosine_similarity, sparse_vector.rs:583-599 */
+#define NMN_XMETRIC_ANGULAR 1           /* angular_distance, 795-798 */
+#define NMN_XMETRIC_GEODESIC 2          /* geodesic_distance, 805-808 */
+#define NMN_XMETRIC_JACCARD 3           /* jaccard_index, 816-845 */
+#define NMN_XMETRIC_OVERLAP 4           /* overlap_coefficient, 852-878 */
+#define NMN_XMETRIC_WEIGHTED_JACCARD 5  /* weighted_jaccard, 886-935 */
+#define NMN_XMETRIC_EUCLIDEAN 6         /* euclidean_distance, 942-1006 */
+#define NMN_XMETRIC_MANHATTAN 7         /* manhattan_distance, 1013-1059 */
+#define NMN_XMETRIC_COMPOSITE 8         /* Composite(GeometricConfig), distance.rs:172-193 */
+/* DistanceMetric; the three weights are GeometricConfig (distance.rs:115-125) and matter for NMN_XMETRIC_COMPOSITE only. */
+typedef struct nmn_xmetric {
+    int32_t kind; /* NMN_XMETRIC_* */
+    float cosine_weight;
+    float structural_weight;
+    float magnitude_weight;
+} nmn_xmetric;
+/* Composite(GeometricConfig::default()) = (0.5, 0.3, 0.2), ::angular_heavy() = (0.8, 0.1, 0.1), ::structural_heavy() =
+ * (0.2, 0.7, 0.1), ::conflict_detection() = (0.4, 0.5, 0.1) (distance.rs:127-166). */
+void nmn_xmetric_geometric_default(nmn_xmetric* m);
+void nmn_xmetric_geometric_angular_heavy(nmn_xmetric* m);
+void nmn_xmetric_geometric_structural_heavy(nmn_xmetric* m);
+void nmn_xmetric_geometric_conflict_detection(nmn_xmetric* m);
+/* DistanceMetric::to_similarity (distance.rs:92-106): host arithmetic, no device needed.  NaN for an unknown kind. */
+float nmn_xmetric_to_similarity(const nmn_xmetric* m, float raw);
+/* DistanceMetric::higher_is_better (distance.rs:60-69): 1 / 0. */
+int32_t nmn_xmetric_higher_is_better(const nmn_xmetric* m);
+/* DistanceMetric::compute (distance.rs:76-88) and to_similarity(compute()) of every (query, row) pair, on the GPU:
+ * out[q * n_rows + i] for local row local_rows[i].  HOST buffers; either output may be NULL.  The reference's bits, except
+ * Angular / Geodesic: `acos` is the platform's libm there; here it is acos in f64 of the f32 cosine, rounded once.
+ * Unknown kind: NMN_ERR_CONFIGURATION. */
+nmn_status nmn_index_score_rows_xmetric(nmn_index* idx, const float* queries, uint32_t nq, const nmn_xmetric* metric,
+                                        const uint64_t* local_rows, uint32_t n_rows, float* out_raw, float* out_similarity);
+/* The same for ONE query against rows that live in HOST memory (n_rows x dim, tightly packed, any dim > 0): the re-rank of
+ * search_with_hnsw_and_metric when the candidates' current vectors are not the rows of an index (lib.rs:2595-2598).  One device
+ * block per call, the same kernel; out[i] for row i.  device -1: the current device. */
+nmn_status nmn_xmetric_score_host_rows(int32_t device, const float* rows_host, uint32_t n_rows, uint32_t dim, const float* query,
+                                       const nmn_xmetric* metric, float* out_raw, float* out_similarity);
+/* VectorEngine::search_with_hnsw_and_metric (vector_engine/src/lib.rs:2560-2619) with node id == row of nmn_hnsw_vectors(h):
+ * c = max(top_k.saturating_mul(2), 10) (2578), served as min(c, len); index.search(query, c) (2579; layer 0 runs with
+ * max(ef_search, c), hnsw.rs:2055-2111), the walk's scores dropped; every candidate scored as
+ * metric.to_similarity(metric.compute(query, row)) (2588-2601); stable sort by score descending, truncated to top_k
+ * (2611-2617).  queries HOST nq x dim; out_ids nq x top_k (unused = UINT64_MAX), out_scores nq x top_k (unused = -inf),
+ * out_counts nq.  Empty index: counts 0.  top_k == 0: NMN_ERR_INVALID_TOP_K; unknown kind: NMN_ERR_CONFIGURATION.  stats: sweep_kind NMN_SWEEP_GRAPH, rows_scanned = the walk's
+ * distance evaluations, candidates_rescored = the most candidates re-ranked for one query.  NMN_HNSW_HOST_SEARCH=1 moves the
+ * walk to the host as for nmn_hnsw_search; the re-rank still runs on the device. */
+nmn_status nmn_hnsw_search_metric(nmn_hnsw* h, const float* queries, uint32_t nq, uint32_t top_k, const nmn_xmetric* metric,
+                                  uint64_t* out_ids, float* out_scores, uint32_t* out_counts, nmn_search_stats* stats);
+/* The same with every buffer in DEVICE memory, enqueued on `stream` behind the walk and not waited for: the walk's launches,
+ * the re-rank and the ordering (one launch; above 16 384 candidates the large-k sort, query by query); nothing is read back.  The nq x c candidate block lives in the stream's scratch: a shape the
+ * stream has served before allocates nothing. */
+nmn_status nmn_hnsw_search_metric_device(nmn_hnsw* h, const float* queries_dev, uint32_t nq, uint32_t top_k,
+                                         const nmn_xmetric* metric, uint64_t* out_ids_dev, float* out_scores_dev,
+                                         uint32_t* out_counts_dev, void* stream);
+
 /* ---- persistence of the device layout ----------------------------------- */
 
 /* The reference persists a collection as PersistentVectorIndex — (key, vector, metadata) entries in JSON or bitcode —

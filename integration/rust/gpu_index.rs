@@ -39,6 +39,30 @@ impl From<DistanceMetric> for ffi::nmn_metric {
     }
 }
 
+/// `tensor_store::DistanceMetric` (the crate's `ExtendedDistanceMetric`, tensor_store/src/distance.rs:13-52) as the library takes it.
+impl From<&crate::ExtendedDistanceMetric> for ffi::nmn_xmetric {
+    fn from(m: &crate::ExtendedDistanceMetric) -> Self {
+        use crate::ExtendedDistanceMetric as M;
+        let unit = |kind| ffi::nmn_xmetric { kind, cosine_weight: 0.0, structural_weight: 0.0, magnitude_weight: 0.0 };
+        match m {
+            M::Cosine => unit(ffi::NMN_XMETRIC_COSINE),
+            M::Angular => unit(ffi::NMN_XMETRIC_ANGULAR),
+            M::Geodesic => unit(ffi::NMN_XMETRIC_GEODESIC),
+            M::Jaccard => unit(ffi::NMN_XMETRIC_JACCARD),
+            M::Overlap => unit(ffi::NMN_XMETRIC_OVERLAP),
+            M::WeightedJaccard => unit(ffi::NMN_XMETRIC_WEIGHTED_JACCARD),
+            M::Euclidean => unit(ffi::NMN_XMETRIC_EUCLIDEAN),
+            M::Manhattan => unit(ffi::NMN_XMETRIC_MANHATTAN),
+            M::Composite(c) => ffi::nmn_xmetric {
+                kind: ffi::NMN_XMETRIC_COMPOSITE,
+                cosine_weight: c.cosine_weight,
+                structural_weight: c.structural_weight,
+                magnitude_weight: c.magnitude_weight,
+            },
+        }
+    }
+}
+
 fn c_path(p: &Path) -> Result<CString> {
     CString::new(p.to_string_lossy().as_bytes()).map_err(|e| VectorError::IoError(e.to_string()))
 }
@@ -122,6 +146,24 @@ impl GpuFlatIndex {
         Ok((0..nq)
             .map(|i| (0..counts[i] as usize).map(|j| (rows[i * k + j] as usize, scores[i * k + j])).collect())
             .collect())
+    }
+
+    /// The re-rank of `search_with_hnsw_and_metric` (lib.rs:2588-2601) for candidates that are rows of this shard:
+    /// `metric.to_similarity(metric.compute(from_dense(q), from_dense(row)))` per row, on the GPU (nmn_index_score_rows_xmetric).
+    /// The caller sorts (stable, descending) and truncates, as lib.rs:2611-2617 does.
+    pub fn score_rows_extended(&self, q: &[f32], rows: &[u64], metric: &crate::ExtendedDistanceMetric) -> Result<Vec<f32>> {
+        if q.len() != self.dim {
+            return Err(VectorError::DimensionMismatch { expected: self.dim, got: q.len() });
+        }
+        let m: ffi::nmn_xmetric = metric.into();
+        let mut sim = vec![0f32; rows.len()];
+        let st = unsafe {
+            ffi::nmn_index_score_rows_xmetric(
+                self.raw, q.as_ptr(), 1, &m, rows.as_ptr(), rows.len() as u32, std::ptr::null_mut(), sim.as_mut_ptr(),
+            )
+        };
+        check(st, self.dim, q.len())?;
+        Ok(sim)
     }
 
     /// Overwrite (or append at `len()`) one row: `store_embedding` keeps the mirror current instead of dropping it.

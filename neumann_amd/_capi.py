@@ -98,6 +98,16 @@ class HnswConfig(C.Structure):
 HNSW_STORAGE_DENSE, HNSW_STORAGE_AUTO, HNSW_STORAGE_QUANTIZED = range(3)
 
 
+class XMetric(C.Structure):
+    """nmn_xmetric (tensor_store::DistanceMetric, tensor_store/src/distance.rs:13-52; the weights are GeometricConfig, 115-125)."""
+    _fields_ = [("kind", C.c_int32), ("cosine_weight", C.c_float), ("structural_weight", C.c_float),
+                ("magnitude_weight", C.c_float)]
+
+
+(XMETRIC_COSINE, XMETRIC_ANGULAR, XMETRIC_GEODESIC, XMETRIC_JACCARD, XMETRIC_OVERLAP, XMETRIC_WEIGHTED_JACCARD,
+ XMETRIC_EUCLIDEAN, XMETRIC_MANHATTAN, XMETRIC_COMPOSITE) = range(9)
+
+
 class PredOp(C.Structure):
     """nmn_pred_op: one step of a WHERE-predicate program (include/neumann_gpu.h, NMN_PRED_*)."""
     _fields_ = [("op", C.c_uint32), ("cmp", C.c_uint32), ("vkind", C.c_uint32), ("column", C.c_uint32),
@@ -204,6 +214,17 @@ SIGNATURES = {
     "nmn_hnsw_set_heap_capacity": (C.c_int32, [vp, C.c_uint32, C.c_uint32]),
     "nmn_hnsw_vectors": (vp, [vp]),
     "nmn_hnsw_hbm_bytes": (C.c_uint64, [vp]),
+    "nmn_xmetric_geometric_default": (None, [C.POINTER(XMetric)]),
+    "nmn_xmetric_geometric_angular_heavy": (None, [C.POINTER(XMetric)]),
+    "nmn_xmetric_geometric_structural_heavy": (None, [C.POINTER(XMetric)]),
+    "nmn_xmetric_geometric_conflict_detection": (None, [C.POINTER(XMetric)]),
+    "nmn_xmetric_to_similarity": (C.c_float, [C.POINTER(XMetric), C.c_float]),
+    "nmn_xmetric_higher_is_better": (C.c_int32, [C.POINTER(XMetric)]),
+    "nmn_index_score_rows_xmetric": (C.c_int32, [vp, vp, C.c_uint32, C.POINTER(XMetric), vp, C.c_uint32, vp, vp]),
+    "nmn_xmetric_score_host_rows": (C.c_int32, [C.c_int32, vp, C.c_uint32, C.c_uint32, vp, C.POINTER(XMetric), vp, vp]),
+    "nmn_hnsw_search_metric": (C.c_int32, [vp, vp, C.c_uint32, C.c_uint32, C.POINTER(XMetric), vp, vp, vp,
+                                           C.POINTER(SearchStats)]),
+    "nmn_hnsw_search_metric_device": (C.c_int32, [vp, vp, C.c_uint32, C.c_uint32, C.POINTER(XMetric), vp, vp, vp, vp]),
     "nmn_index_save": (C.c_int32, [vp, C.c_char_p]),
     "nmn_index_load": (C.c_int32, [C.c_char_p, C.POINTER(IndexDesc), C.c_uint64, C.c_uint64, C.POINTER(vp)]),
     "nmn_ivf_save": (C.c_int32, [vp, C.c_char_p]),

@@ -140,6 +140,7 @@ struct nmn_engine_hnsw {
     nmn_hnsw* index = nullptr;          // null = built from an empty store
     std::vector<std::string> keys;
     uint64_t dim = 0;
+    uint64_t writes_at_build = 0;       // Collection::writes of the default collection when the rows were read
     ~nmn_engine_hnsw() {
         if (index) nmn_hnsw_destroy(index);
     }
@@ -275,6 +276,7 @@ struct Collection {
     std::unordered_map<std::string, uint32_t> by_key;
     std::vector<uint32_t> free_slots;
     uint64_t live = 0;
+    uint64_t writes = 0;  // stores, deletes and clears so far: an HNSW handle built at the same count still holds the current vectors
     std::unordered_map<uint64_t, std::unique_ptr<Mirror>> mirrors;  // by dimension
     bool has_dirty = false;                                          // some mirror here has stores pending
     void invalidate() { mirrors.clear(); }  // full drop (delete_collection / clear)
@@ -539,6 +541,7 @@ nmn_status store_into(nmn_engine* e, Collection* c, const char* key, const float
     Entry ent;
     ent.key = key;
     ent.vec.assign(v, v + dim);
+    c->writes++;
     for (uint32_t i = 0; i < n_meta; i++)
         if (meta[i].name) ent.meta[meta[i].name] = Value::from(meta[i].value);
     ent.live = true;
@@ -578,6 +581,7 @@ nmn_status store_into(nmn_engine* e, Collection* c, const char* key, const float
 nmn_status delete_from(Collection* c, const std::string& key, const std::string& shown) {
     auto it = c->by_key.find(key);
     if (it == c->by_key.end()) return err_not_found(shown);
+    c->writes++;
     Entry& ent = c->slots[it->second];
     mirror_tombstone(c, ent.vec.size(), ent.mrow);
     ent = Entry();
@@ -1234,7 +1238,9 @@ nmn_status nmn_engine_clear(nmn_engine* e, uint64_t* removed) {  // lib.rs:2340-
     const uint64_t max_keys = scan_limit(e);
     if (e->dflt.live <= max_keys) {
         if (removed) *removed = e->dflt.live;
+        const uint64_t writes = e->dflt.writes;
         e->dflt = Collection();
+        e->dflt.writes = writes + 1;
         return NMN_OK;
     }
     // more keys than one bounded scan covers: the first max_keys go ("call again until 0 is returned")
@@ -1779,6 +1785,7 @@ nmn_status nmn_engine_build_hnsw_index(nmn_engine* e, const nmn_hnsw_config* cfg
         res->keys.push_back(ent.key);
         rows.insert(rows.end(), ent.vec.begin(), ent.vec.end());
     }
+    res->writes_at_build = e->dflt.writes;
     const uint64_t n = res->keys.size();
     if (n == 0) {  // `return Ok((HNSWIndex::with_config(..), Vec::new()))`
         *out = res.release();
@@ -1841,6 +1848,105 @@ nmn_status nmn_engine_search_with_hnsw(nmn_engine* e, nmn_engine_hnsw* h, const 
     }
     *out = res;
     return NMN_OK;
+}
+
+// search_with_hnsw_and_metric (lib.rs:2560-2619).  keys NULL: the handle's own key_mapping.
+nmn_status nmn_engine_search_with_hnsw_and_metric_mapped(nmn_engine* e, nmn_engine_hnsw* h, const float* q, uint64_t dim,
+                                                         uint64_t top_k, const nmn_xmetric* metric, const char* const* keys,
+                                                         uint64_t n_keys, nmn_results** out) {
+    if (!e || !h || !out || !metric) return fail(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    *out = nullptr;
+    const Deadline dl(e->cfg.search_timeout_ms);
+    if (!q || dim == 0) return err_empty();  // lib.rs:2570-2572
+    if (top_k == 0) return err_topk();       // lib.rs:2573-2575
+    if (metric->kind < NMN_XMETRIC_COSINE || metric->kind > NMN_XMETRIC_COMPOSITE)
+        return fail(NMN_ERR_CONFIGURATION, "Configuration error: unknown extended distance metric");
+    std::unique_ptr<nmn_results> res(new_results());
+    if (!res) return fail(NMN_ERR_OUT_OF_MEMORY, "results alloc");
+    if (!h->index) {  // empty index: `index.search` returns nothing (hnsw.rs:2070-2073)
+        *out = res.release();
+        return NMN_OK;
+    }
+    if (dim != h->dim) return err_dim(h->dim, dim);  // as search_with_hnsw: the reference's SIMD loops would read past the shorter slice
+    const char* const op = "search_with_hnsw_and_metric";
+    const uint64_t len = nmn_hnsw_len(h->index);
+    const uint64_t k64 = std::min<uint64_t>(top_k, std::max<uint64_t>(len, 1));  // at most len candidates come back
+    const uint32_t k = (uint32_t)k64;
+    auto key_of = [&](uint64_t id) -> const char* {  // `key_mapping.get(*node_id)?`
+        if (keys) return id < n_keys ? keys[id] : nullptr;
+        return id < h->keys.size() ? h->keys[id].c_str() : nullptr;
+    };
+    ReadLock g(e);
+    if (!keys && h->writes_at_build == e->dflt.writes) {
+        // fast path: nothing was stored, deleted or cleared since build_hnsw_index, so the handle's rows ARE the current vectors of
+        // its keys: walk, re-rank and ordering as one stream-ordered chain
+        std::vector<uint64_t> ids(k);
+        std::vector<float> sc(k);
+        uint32_t count = 0;
+        nmn_status st = nmn_hnsw_search_metric(h->index, q, 1, k, metric, ids.data(), sc.data(), &count, nullptr);
+        if (st != NMN_OK) return err_gpu(st);
+        if (dl.expired()) return err_timeout(op, dl.ms);  // lib.rs:2581-2586, 2603-2608
+        for (uint32_t i = 0; i < count; i++) {
+            const char* key = key_of(ids[i]);
+            if (!key) continue;
+            res->keys.push_back(key);
+            res->scores.push_back(sc[i]);
+        }
+        *out = res.release();
+        return NMN_OK;
+    }
+    // changed path: the walk, then the CURRENT vector of every candidate's key (`self.get_embedding(key).ok()?`, lib.rs:2595) gathered
+    // into a staging matrix and scored there by the same kernel
+    const uint64_t c64 = std::min<uint64_t>(std::max<uint64_t>(top_k > UINT64_MAX / 2 ? UINT64_MAX : 2 * top_k, 10), std::max<uint64_t>(len, 1));
+    const uint32_t c = (uint32_t)c64;
+    std::vector<uint64_t> ids(c);
+    std::vector<float> sc(c);
+    uint32_t count = 0;
+    nmn_status st = nmn_hnsw_search(h->index, q, 1, c, 0, ids.data(), sc.data(), &count, nullptr);
+    if (st != NMN_OK) return err_gpu(st);
+    if (dl.expired()) return err_timeout(op, dl.ms);  // lib.rs:2581-2586
+    std::vector<const char*> cand_keys;
+    std::vector<const Entry*> cand;
+    uint64_t width = dim;
+    for (uint32_t i = 0; i < count; i++) {
+        const char* key = key_of(ids[i]);
+        if (!key) continue;
+        auto it = e->dflt.by_key.find(key);
+        if (it == e->dflt.by_key.end()) continue;  // the key is gone
+        const Entry& ent = e->dflt.slots[it->second];
+        cand_keys.push_back(key);
+        cand.push_back(&ent);
+        width = std::max<uint64_t>(width, ent.vec.size());
+    }
+    const uint32_t m = (uint32_t)cand.size();
+    if (m > 0) {
+        // a vector of another length: both sides zero-padded to the longer one (from_dense drops the zeros: the reference's merge)
+        if (width > 0xFFFFFFFFull) return fail(NMN_ERR_INVALID_ARGUMENT, "dimension does not fit the device index (> 2^32 - 1)");
+        std::vector<float> stage((size_t)m * width, 0.0f), qpad(width, 0.0f);
+        std::copy(q, q + dim, qpad.begin());
+        for (uint32_t i = 0; i < m; i++) std::copy(cand[i]->vec.begin(), cand[i]->vec.end(), stage.begin() + (size_t)i * width);
+        std::vector<float> sim(m);
+        st = nmn_xmetric_score_host_rows(e->cfg.device, stage.data(), m, (uint32_t)width, qpad.data(), metric, nullptr, sim.data());
+        if (st != NMN_OK) return err_gpu(st);
+        if (dl.expired()) return err_timeout(op, dl.ms);  // lib.rs:2603-2608
+        // `results.sort_by(|a, b| b.score.partial_cmp(&a.score).unwrap_or(Equal))`, stable; truncate(top_k)
+        std::vector<uint32_t> order(m);
+        for (uint32_t i = 0; i < m; i++) order[i] = i;
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return sim[a] > sim[b]; });
+        for (uint32_t i = 0; i < m && i < top_k; i++) {
+            res->keys.push_back(cand_keys[order[i]]);
+            res->scores.push_back(sim[order[i]]);
+        }
+    } else if (dl.expired()) {
+        return err_timeout(op, dl.ms);
+    }
+    *out = res.release();
+    return NMN_OK;
+}
+
+nmn_status nmn_engine_search_with_hnsw_and_metric(nmn_engine* e, nmn_engine_hnsw* h, const float* q, uint64_t dim, uint64_t top_k,
+                                                  const nmn_xmetric* metric, nmn_results** out) {
+    return nmn_engine_search_with_hnsw_and_metric_mapped(e, h, q, dim, top_k, metric, nullptr, 0, out);
 }
 
 // estimate_hnsw_memory (lib.rs:2489-2509): vectors + count x M(16) x 2 x 8 of graph + 32 bytes a key; host arithmetic only

@@ -15,6 +15,8 @@
 //       `left <= right`), then sifted up; into_iter = the backing vector's order.  Both heaps are kept as that array algorithm.
 //   search_layer (hnsw.rs:2276-2335), search_layer_greedy (2170-2200), search_with_ef (2069-2111), try_insert_embedding
 //       (1936-2051), random_level (1631-1651).
+//   nmn_hnsw_search_metric* (the end of this file): the walk with k = c, then the re-rank of its candidates under an extended
+//       metric and their stable ordering (nmn_xmetric.hip) — VectorEngine::search_with_hnsw_and_metric, vector_engine/src/lib.rs:2560-2619.
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -469,6 +471,8 @@ struct nmn_hnsw {
         hipStream_t stream = nullptr;
         std::mutex mu;
         DevBuf vis, flags, evals, spill;
+        bool xsort_use = false;  // this call's ordering goes through the large-k sort (xmetric_order_scratch_bytes != 0)
+        DevBuf xids, xsc, xcnt, xsim, xsort;  // nmn_hnsw_search_metric*: the walk's nq x c candidate block, its re-rank scores, the sort's scratch
     };
     std::vector<std::unique_ptr<Scratch>> scratch;
     std::vector<hipEvent_t> ev_pending, ev_free;
@@ -781,23 +785,20 @@ nmn_status record_search(nmn_hnsw* h, hipStream_t s) {
     return NMN_OK;
 }
 
-// Enqueue the search of nq queries (device buffers) on s.  Caller holds rw (shared).  *sc_out: the stream's scratch, whose flags /
-// evals the host-buffer search reads back.
-nmn_status enqueue_search(nmn_hnsw* h, const float* q_dev, uint32_t nq, uint32_t k, uint32_t ef, uint64_t* o_ids, float* o_sc,
-                          uint32_t* o_cnt, hipStream_t s, nmn_hnsw::Scratch** sc_out) {
-    nmn_hnsw::Scratch* sc = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(h->dev_mu);
-        for (auto& x : h->scratch)
-            if (x->stream == s) sc = x.get();
-        if (!sc) {
-            h->scratch.push_back(std::make_unique<nmn_hnsw::Scratch>());
-            sc = h->scratch.back().get();
-            sc->stream = s;
-        }
-    }
-    if (sc_out) *sc_out = sc;
-    std::lock_guard<std::mutex> slk(sc->mu);
+// The scratch of stream s (created on first use).
+nmn_hnsw::Scratch* scratch_of(nmn_hnsw* h, hipStream_t s) {
+    std::lock_guard<std::mutex> lk(h->dev_mu);
+    for (auto& x : h->scratch)
+        if (x->stream == s) return x.get();
+    h->scratch.push_back(std::make_unique<nmn_hnsw::Scratch>());
+    h->scratch.back()->stream = s;
+    return h->scratch.back().get();
+}
+
+// Enqueue the search of nq queries (device buffers) on s.  Caller holds rw (shared) AND sc->mu, sc being scratch_of(h, s): growing
+// the scratch, the fills and the launches of one call are one unit, two callers on one stream never interleave.
+nmn_status enqueue_search_locked(nmn_hnsw* h, nmn_hnsw::Scratch* sc, const float* q_dev, uint32_t nq, uint32_t k, uint32_t ef,
+                                 uint64_t* o_ids, float* o_sc, uint32_t* o_cnt, hipStream_t s) {
     const uint32_t n = (uint32_t)h->level.size();
     const uint32_t ef_eff = std::max<uint32_t>(ef ? ef : h->cfg.ef_search, k);  // hnsw.rs:2102
     const uint32_t vwords = std::max<uint32_t>((n + 31) / 32, 1);
@@ -867,6 +868,54 @@ nmn_status enqueue_search(nmn_hnsw* h, const float* q_dev, uint32_t nq, uint32_t
         hipLaunchKernelGGL(hnsw_search_kernel<true>, dim3(std::min(regions, nb)), dim3(64), fixed, s, a);
         HN_TRY(hipGetLastError());
     }
+    return NMN_OK;
+}
+
+// The same for a caller that holds rw (shared) only.  *sc_out: the stream's scratch, whose flags / evals the host-buffer search
+// reads back.
+nmn_status enqueue_search(nmn_hnsw* h, const float* q_dev, uint32_t nq, uint32_t k, uint32_t ef, uint64_t* o_ids, float* o_sc,
+                          uint32_t* o_cnt, hipStream_t s, nmn_hnsw::Scratch** sc_out) {
+    nmn_hnsw::Scratch* sc = scratch_of(h, s);
+    if (sc_out) *sc_out = sc;
+    std::lock_guard<std::mutex> slk(sc->mu);
+    return enqueue_search_locked(h, sc, q_dev, nq, k, ef, o_ids, o_sc, o_cnt, s);
+}
+
+// search_with_hnsw_and_metric's candidate count (lib.rs:2578), served as min(c, len): search_layer runs with max(ef_search, c) and any
+// ef >= len keeps every node the walk reaches (the rule nmn_engine_search_with_hnsw applies to k)
+uint64_t metric_candidates(const nmn_hnsw* h, uint32_t top_k) {
+    const uint64_t c = std::max<uint64_t>(2ull * top_k, 10);
+    return std::min<uint64_t>(c, std::max<uint64_t>(h->level.size(), 1));
+}
+
+// The candidate block of the stream's scratch grown for nq x c.  Caller holds rw (shared) and sc->mu, and keeps sc->mu until the
+// last launch that reads the block is enqueued: the block belongs to ONE call at a time (another caller on the same stream would
+// overwrite the candidates, or free the block under a launch being prepared).
+nmn_status metric_scratch(nmn_hnsw::Scratch* sc, hipStream_t s, uint32_t nq, uint32_t c, uint32_t top_k) {
+    bool synced = false;
+    HN_TRY(grow(sc->xids, (size_t)nq * c * 8, s, &synced));
+    HN_TRY(grow(sc->xsc, (size_t)nq * c * 4, s, &synced));
+    HN_TRY(grow(sc->xsim, (size_t)nq * c * 4, s, &synced));
+    HN_TRY(grow(sc->xcnt, (size_t)nq * 4, s, &synced));
+    const size_t sort_bytes = xmetric_order_scratch_bytes(c, top_k);
+    sc->xsort_use = sort_bytes != 0;
+    HN_TRY(grow(sc->xsort, sort_bytes, s, &synced));
+    return NMN_OK;
+}
+
+// The re-rank and the ordering of the candidate block in sc, behind whatever filled it on s.  Caller holds sc->mu.
+nmn_status enqueue_rerank(nmn_hnsw* h, nmn_hnsw::Scratch* sc, const float* q_dev, uint32_t nq, uint32_t c, uint32_t top_k,
+                          const nmn_xmetric& m, uint64_t* o_ids, float* o_sc, uint32_t* o_cnt, hipStream_t s) {
+    HN_TRY(launch_xmetric_rerank(h->vectors ? h->vectors->corpus : nullptr, h->vectors ? h->vectors->ld : 0, h->dim, h->level.size(),
+                                 q_dev, nq, c, (const uint64_t*)sc->xids.p, (const uint32_t*)sc->xcnt.p, m, top_k, (float*)sc->xsim.p,
+                                 o_ids, o_sc, o_cnt, sc->xsort_use ? sc->xsort.p : nullptr, s));
+    return NMN_OK;
+}
+
+nmn_status check_metric_call(nmn_hnsw* h, uint32_t top_k, const nmn_xmetric* m) {
+    if (!h || !m) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (!xmetric_valid(m)) return set_error(NMN_ERR_CONFIGURATION, "unknown extended distance metric");
+    if (top_k == 0) return set_error(NMN_ERR_INVALID_TOP_K, "top_k == 0");
     return NMN_OK;
 }
 
@@ -954,6 +1003,11 @@ extern "C" nmn_status nmn_hnsw_destroy(nmn_hnsw* h) {
         drop(s->flags);
         drop(s->evals);
         drop(s->spill);
+        drop(s->xids);
+        drop(s->xsc);
+        drop(s->xcnt);
+        drop(s->xsim);
+        drop(s->xsort);
     }
     for (DevBuf* b : {&h->d_l0, &h->d_l0cnt, &h->d_upidx, &h->d_up, &h->d_upcnt, &h->hq, &h->hids, &h->hsc, &h->hcnt}) drop(*b);
     if (h->host_stream) (void)hipStreamDestroy(h->host_stream);
@@ -1120,6 +1174,131 @@ extern "C" nmn_status nmn_hnsw_search(nmn_hnsw* h, const float* queries, uint32_
         stats->fallback_queries = spilled;
         stats->sweep_kind = h->level.empty() ? NMN_SWEEP_NONE : NMN_SWEEP_GRAPH;
         stats->sweep_launches = host_search_forced() ? 0 : 2;
+    }
+    return NMN_OK;
+}
+
+extern "C" nmn_status nmn_hnsw_search_metric_device(nmn_hnsw* h, const float* queries_dev, uint32_t nq, uint32_t top_k,
+                                                    const nmn_xmetric* metric, uint64_t* out_ids_dev, float* out_scores_dev,
+                                                    uint32_t* out_counts_dev, void* stream) {
+    nmn_status st = check_metric_call(h, top_k, metric);
+    if (st != NMN_OK) return st;
+    if (nq == 0) return NMN_OK;
+    if (!queries_dev || !out_ids_dev || !out_scores_dev || !out_counts_dev) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    std::shared_lock<std::shared_mutex> g(h->rw);
+    const uint64_t c64 = metric_candidates(h, top_k);
+    const uint32_t c = (uint32_t)c64;
+    HN_TRY(hipSetDevice(h->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    nmn_hnsw::Scratch* sc = scratch_of(h, s);
+    {
+        std::lock_guard<std::mutex> slk(sc->mu);  // grow, walk, re-rank and ordering as one unit on this stream
+        st = metric_scratch(sc, s, nq, c, top_k);
+        if (st != NMN_OK) return st;
+        st = enqueue_search_locked(h, sc, queries_dev, nq, c, 0, (uint64_t*)sc->xids.p, (float*)sc->xsc.p, (uint32_t*)sc->xcnt.p, s);
+        if (st != NMN_OK) return st;
+        st = enqueue_rerank(h, sc, queries_dev, nq, c, top_k, *metric, out_ids_dev, out_scores_dev, out_counts_dev, s);
+        if (st != NMN_OK) return st;
+    }
+    return record_search(h, s);
+}
+
+extern "C" nmn_status nmn_hnsw_search_metric(nmn_hnsw* h, const float* queries, uint32_t nq, uint32_t top_k, const nmn_xmetric* metric,
+                                             uint64_t* out_ids, float* out_scores, uint32_t* out_counts, nmn_search_stats* stats) {
+    nmn_status st = check_metric_call(h, top_k, metric);
+    if (st != NMN_OK) return st;
+    if (stats) {
+        memset(stats, 0, sizeof *stats);
+        stats->scan_ms = stats->total_ms = -1.0f;
+    }
+    if (nq == 0) return NMN_OK;
+    if (!queries || !out_ids || !out_scores || !out_counts) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    std::shared_lock<std::shared_mutex> g(h->rw);
+    const uint64_t c64 = metric_candidates(h, top_k);
+    const uint32_t c = (uint32_t)c64;
+    const bool on_host = host_search_forced();
+    uint64_t evals = 0;
+    uint32_t spilled = 0, rescored = 0;
+    std::lock_guard<std::mutex> hl(h->host_mu);  // host callers take turns on the handle's own stream and staging
+    HN_TRY(hipSetDevice(h->device));
+    hipStream_t s = h->host_stream;
+    bool synced = true;  // (every earlier host call ended with a wait)
+    const hipStream_t none = (hipStream_t)-1;
+    HN_TRY(grow(h->hq, (size_t)nq * h->dim * 4, none, &synced));
+    HN_TRY(grow(h->hids, (size_t)nq * top_k * 8, none, &synced));
+    HN_TRY(grow(h->hsc, (size_t)nq * top_k * 4, none, &synced));
+    HN_TRY(grow(h->hcnt, (size_t)nq * 4, none, &synced));
+    // host_mu makes this caller the only one on host_stream; sc->mu is held all the same, for the whole call: the candidate block
+    // is read back and, should a query stay flagged, filled again
+    nmn_hnsw::Scratch* sc = scratch_of(h, s);
+    std::lock_guard<std::mutex> slk(sc->mu);
+    st = metric_scratch(sc, s, nq, c, top_k);
+    if (st != NMN_OK) return st;
+    HN_TRY(hipMemcpyAsync(h->hq.p, queries, (size_t)nq * h->dim * 4, hipMemcpyHostToDevice, s));
+    std::vector<uint64_t> cid;
+    std::vector<float> csc;
+    std::vector<uint32_t> ccnt(nq), fl(nq, 0), ev(nq, 0);
+    auto host_walk = [&](uint32_t q) {  // the walk of query q on the host, its candidates into the staging vectors
+        static thread_local HostVisited vis;
+        if (cid.empty()) {
+            cid.resize((size_t)nq * c);
+            csc.resize((size_t)nq * c);
+        }
+        uint64_t e2 = 0;
+        host_search_one(h, queries + (size_t)q * h->dim, c, h->cfg.ef_search, vis, cid.data() + (size_t)q * c, csc.data() + (size_t)q * c,
+                        &ccnt[q], &e2);
+        ev[q] = (uint32_t)e2;
+    };
+    if (on_host) {
+        for (uint32_t q = 0; q < nq; q++) host_walk(q);
+        HN_TRY(hipMemcpyAsync(sc->xids.p, cid.data(), (size_t)nq * c * 8, hipMemcpyHostToDevice, s));
+        HN_TRY(hipMemcpyAsync(sc->xcnt.p, ccnt.data(), (size_t)nq * 4, hipMemcpyHostToDevice, s));
+    } else {
+        st = enqueue_search_locked(h, sc, (const float*)h->hq.p, nq, c, 0, (uint64_t*)sc->xids.p, (float*)sc->xsc.p, (uint32_t*)sc->xcnt.p, s);
+        if (st != NMN_OK) return st;
+    }
+    st = enqueue_rerank(h, sc, (const float*)h->hq.p, nq, c, top_k, *metric, (uint64_t*)h->hids.p, (float*)h->hsc.p, (uint32_t*)h->hcnt.p, s);
+    if (st != NMN_OK) return st;
+    HN_TRY(hipMemcpyAsync(out_ids, h->hids.p, (size_t)nq * top_k * 8, hipMemcpyDeviceToHost, s));
+    HN_TRY(hipMemcpyAsync(out_scores, h->hsc.p, (size_t)nq * top_k * 4, hipMemcpyDeviceToHost, s));
+    HN_TRY(hipMemcpyAsync(out_counts, h->hcnt.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+    if (!on_host) {
+        HN_TRY(hipMemcpyAsync(ccnt.data(), sc->xcnt.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+        HN_TRY(hipMemcpyAsync(fl.data(), sc->flags.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+        HN_TRY(hipMemcpyAsync(ev.data(), sc->evals.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+    }
+    HN_TRY(hipStreamSynchronize(s));
+    bool redo = false;
+    for (uint32_t q = 0; q < nq; q++) {
+        if (fl[q] == 1u) redo = true;  // the spill launch could not answer it (cannot happen while its heap holds n entries)
+        if (fl[q] != 0u) spilled++;
+    }
+    if (redo) {  // ... then the host walks every query and the device re-ranks again
+        cid.resize((size_t)nq * c);
+        csc.resize((size_t)nq * c);
+        HN_TRY(hipMemcpy(cid.data(), sc->xids.p, (size_t)nq * c * 8, hipMemcpyDeviceToHost));
+        for (uint32_t q = 0; q < nq; q++)
+            if (fl[q] == 1u) host_walk(q);
+        HN_TRY(hipMemcpyAsync(sc->xids.p, cid.data(), (size_t)nq * c * 8, hipMemcpyHostToDevice, s));
+        HN_TRY(hipMemcpyAsync(sc->xcnt.p, ccnt.data(), (size_t)nq * 4, hipMemcpyHostToDevice, s));
+        st = enqueue_rerank(h, sc, (const float*)h->hq.p, nq, c, top_k, *metric, (uint64_t*)h->hids.p, (float*)h->hsc.p, (uint32_t*)h->hcnt.p, s);
+        if (st != NMN_OK) return st;
+        HN_TRY(hipMemcpyAsync(out_ids, h->hids.p, (size_t)nq * top_k * 8, hipMemcpyDeviceToHost, s));
+        HN_TRY(hipMemcpyAsync(out_scores, h->hsc.p, (size_t)nq * top_k * 4, hipMemcpyDeviceToHost, s));
+        HN_TRY(hipMemcpyAsync(out_counts, h->hcnt.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+        HN_TRY(hipStreamSynchronize(s));
+    }
+    for (uint32_t q = 0; q < nq; q++) {
+        evals += ev[q];
+        rescored = std::max(rescored, std::min(ccnt[q], c));
+    }
+    if (stats) {
+        stats->rows_scanned = evals;
+        stats->bytes_scanned = evals * h->dim * 4;
+        stats->candidates_rescored = rescored;
+        stats->fallback_queries = spilled;
+        stats->sweep_kind = h->level.empty() ? NMN_SWEEP_NONE : NMN_SWEEP_GRAPH;
+        stats->sweep_launches = on_host ? 0 : 2;
     }
     return NMN_OK;
 }

@@ -469,6 +469,18 @@ hipError_t launch_ivf_flat_scan(const float* queries, uint32_t dim, const float*
                                 const void* segs, uint32_t np, uint32_t nq, uint32_t max_count, const uint64_t* score_base,
                                 uint32_t* scores, hipStream_t s);
 
+// extended metrics (nmn_xmetric.hip): sim[q][e] = to_similarity(compute(query q, row cand_ids[q][e])) for e < cand_counts[q]
+// (ids and counts as hnsw_search_kernel leaves them, nq x c), then the stable descending order of each query's scores, the
+// first top_k of it to out_* (unused slots UINT64_MAX / -inf).  Two launches, nothing read back.  Above 16 384 candidates the
+// ordering goes query by query through the large-k sort instead: xmetric_order_scratch_bytes(c, top_k) decides it, once per call
+// (0: the rank count, order_scratch NULL; otherwise order_scratch holds that many bytes and its presence selects the sort).
+bool xmetric_valid(const nmn_xmetric* m);
+size_t xmetric_order_scratch_bytes(uint32_t c, uint32_t top_k);
+hipError_t launch_xmetric_rerank(const float* rows, uint32_t ld, uint32_t dim, uint64_t n_rows, const float* queries, uint32_t nq,
+                                 uint32_t c, const uint64_t* cand_ids, const uint32_t* cand_counts, const nmn_xmetric& m,
+                                 uint32_t top_k, float* sim, uint64_t* out_ids, float* out_scores, uint32_t* out_counts,
+                                 void* order_scratch, hipStream_t s);
+
 // synthetic data
 hipError_t launch_synth_fill(float* corpus, uint32_t ld, uint32_t dim, uint64_t seed, uint64_t global_row0,
                              uint64_t local_row0, uint64_t n, hipStream_t s);

@@ -1,0 +1,558 @@
+// nmn_xmetric.hip — `tensor_store::DistanceMetric` (tensor_store/src/distance.rs:13-194), the ExtendedDistanceMetric of
+// VectorEngine::search_with_hnsw_and_metric (vector_engine/src/lib.rs:2560-2619): the re-rank of an HNSW walk's candidates
+// under any of its nine metrics, and the stable descending order of the scores.
+// THIS TRANSLATION UNIT IS BUILT WITH -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt (build.py), host and device.
+//
+// Reference arithmetic restated here (docs/hnsw.md §8 has the table):
+//   SparseVector::from_dense (sparse_vector.rs:221-229) stores a value iff `val != 0.0`: +-0.0 are skipped, NaN is stored.
+//   dot_f64 (419-443), magnitude_f64 (553-559), cosine_similarity (583-599), angular / geodesic_distance (795-808),
+//   jaccard_index (816-845), overlap_coefficient (852-878), weighted_jaccard (886-935), euclidean_distance (942-1006),
+//   manhattan_distance (1013-1059): sequential f64 sums over the merged stored positions, one rounding to f32 at the end.
+//   A dense left-to-right loop gives the same bits: a position neither side stores adds +0.0 to a sum that starts at 0.0 and
+//   can never be -0.0 (products of two f32 are exact in f64 and never underflow), a position one side stores adds exactly what
+//   the merge loop's one-sided arm adds (the missing value read as 0.0).
+//   GeometricConfig::compute (distance.rs:172-193), DistanceMetric::to_similarity (92-106).
+// Work split, as nmn_exact.hip's sparse_cos64: the eight lanes of a group form the terms of eight consecutive positions, and
+// every lane then adds them to the f64 chains in index order.  Eight pairs to a wave.  The intersection / stored counts are
+// integers and are reduced in any order.
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <mutex>
+#include <vector>
+
+#include "nmn_index.h"
+#include "nmn_internal.h"
+
+#pragma clang fp contract(off)
+
+namespace nmn {
+namespace {
+
+constexpr uint32_t kPairsPerRound = 32;   // 256 threads, eight lanes a pair
+constexpr uint32_t kPairsPerBlock = 256;  // a block serves up to eight rounds of one query: the query's constants once per block
+constexpr float kPi = 3.14159274101257324f;  // std::f32::consts::PI
+constexpr float kF32Max = 3.40282346638528859812e+38f;
+
+// which f64 chains a metric needs from the one pass over the row
+enum Chains : int { kChCos = 0, kChSet = 1, kChWJ = 2, kChEucl = 3, kChManh = 4, kChComposite = 5 };
+
+__host__ __device__ inline int chains_of(int kind) {
+    switch (kind) {
+        case NMN_XMETRIC_COSINE:
+        case NMN_XMETRIC_ANGULAR:
+        case NMN_XMETRIC_GEODESIC: return kChCos;
+        case NMN_XMETRIC_JACCARD:
+        case NMN_XMETRIC_OVERLAP: return kChSet;
+        case NMN_XMETRIC_WEIGHTED_JACCARD: return kChWJ;
+        case NMN_XMETRIC_EUCLIDEAN: return kChEucl;
+        case NMN_XMETRIC_MANHATTAN: return kChManh;
+        default: return kChComposite;
+    }
+}
+
+// f32::midpoint(a, 1.0) on x86-64: ((a as f64 + 1.0) / 2.0) as f32, one rounding
+__host__ __device__ inline float midpoint1(float a) { return (float)(((double)a + 1.0) / 2.0); }
+
+// DistanceMetric::to_similarity, distance.rs:92-106
+__host__ __device__ inline float xm_to_similarity(int kind, float raw) {
+    switch (kind) {
+        case NMN_XMETRIC_COSINE: return midpoint1(raw);
+        case NMN_XMETRIC_ANGULAR:
+        case NMN_XMETRIC_GEODESIC: {
+            const float t = raw / kPi;
+            return 1.0f - t;
+        }
+        case NMN_XMETRIC_EUCLIDEAN:
+        case NMN_XMETRIC_MANHATTAN: {
+            const float t = 1.0f + raw;
+            return 1.0f / t;
+        }
+        default: return raw;
+    }
+}
+
+// lane T of the caller's 8-lane group to all eight (nmn_exact.hip: group8_bcast), for the two halves of an f64
+template <int T>
+__device__ __forceinline__ int group8_bcast_i(int v) {
+    int r = __builtin_amdgcn_update_dpp(0, v, 0x150 + T, 0xF, 0x3, false);
+    r = __builtin_amdgcn_update_dpp(r, v, 0x158 + T, 0xF, 0xC, false);
+    return r;
+}
+template <int T>
+__device__ __forceinline__ double group8_bcast_d(double v) {
+    return __hiloint2double(group8_bcast_i<T>(__double2hiint(v)), group8_bcast_i<T>(__double2loint(v)));
+}
+// chain = chain + term of position 8c + 0, .., 8c + 7, in that order
+__device__ __forceinline__ double chain8(double chain, double term) {
+    chain = chain + group8_bcast_d<0>(term);
+    chain = chain + group8_bcast_d<1>(term);
+    chain = chain + group8_bcast_d<2>(term);
+    chain = chain + group8_bcast_d<3>(term);
+    chain = chain + group8_bcast_d<4>(term);
+    chain = chain + group8_bcast_d<5>(term);
+    chain = chain + group8_bcast_d<6>(term);
+    chain = chain + group8_bcast_d<7>(term);
+    return chain;
+}
+__device__ __forceinline__ uint32_t group8_sum(uint32_t v) {
+    v += (uint32_t)__shfl_xor((int)v, 1);
+    v += (uint32_t)__shfl_xor((int)v, 2);
+    v += (uint32_t)__shfl_xor((int)v, 4);
+    return v;
+}
+
+struct PairSums {
+    double dot, sb, sd, man, wmin, wmax;
+    uint32_t inter, nb;
+};
+
+// One pass over (query a, row b) by the eight lanes of a group, lane l owning the positions 8c + l.  Every lane returns the sums.
+template <int CH>
+__device__ __forceinline__ PairSums pair_pass(const float* __restrict__ a, const float* __restrict__ b, uint32_t dim, uint32_t l) {
+    PairSums r{0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0u, 0u};
+    constexpr int PF = 4;
+    constexpr bool kDot = CH == kChCos || CH == kChComposite;
+    constexpr bool kSd = CH == kChEucl || CH == kChComposite;
+    const uint32_t chunks = (dim + 7u) >> 3;
+    for (uint32_t c0 = 0; c0 < chunks; c0 += PF) {
+        float x[PF], y[PF];
+#pragma unroll
+        for (int i = 0; i < PF; i++) {
+            const uint32_t e = 8u * (c0 + (uint32_t)i) + l;
+            x[i] = e < dim ? a[e] : 0.0f;
+            y[i] = e < dim ? b[e] : 0.0f;
+        }
+#pragma unroll
+        for (int i = 0; i < PF; i++) {
+            const bool sx = x[i] != 0.0f, sy = y[i] != 0.0f;  // stored in the sparse form (true for NaN)
+            const double xd = sx ? (double)x[i] : 0.0, yd = sy ? (double)y[i] : 0.0;
+            r.inter += (sx && sy) ? 1u : 0u;
+            r.nb += sy ? 1u : 0u;
+            if (kDot) {
+                r.dot = chain8(r.dot, (sx && sy) ? xd * yd : 0.0);
+                r.sb = chain8(r.sb, yd * yd);
+            }
+            if (kSd || CH == kChManh) {
+                const double d = xd - yd;
+                if (kSd) r.sd = chain8(r.sd, d * d);
+                if (CH == kChManh) r.man = chain8(r.man, __builtin_fabs(d));
+            }
+            if (CH == kChWJ) {
+                const double ax = __builtin_fabs(xd), ay = __builtin_fabs(yd);
+                r.wmin = chain8(r.wmin, ax < ay ? ax : ay);
+                r.wmax = chain8(r.wmax, ax > ay ? ax : ay);
+            }
+        }
+    }
+    r.inter = group8_sum(r.inter);
+    r.nb = group8_sum(r.nb);
+    return r;
+}
+
+// cosine_similarity, sparse_vector.rs:583-599 (mag_a = sqrt of the query's sum, once per query)
+__host__ __device__ inline float cos_from(double dot, double mag_a, double sb) {
+    const double mag_b = __builtin_sqrt(sb);
+    if (mag_a == 0.0 || mag_b == 0.0) return 0.0f;
+    const double r = dot / (mag_a * mag_b);
+    if (r != r || __builtin_isinf(r)) return 0.0f;
+    const double c = r < -1.0 ? -1.0 : (r > 1.0 ? 1.0 : r);
+    return (float)c;
+}
+__host__ __device__ inline float jaccard_from(uint32_t na, uint32_t nb, uint32_t inter) {  // 816-845
+    if (na == 0u && nb == 0u) return 1.0f;
+    if (na == 0u || nb == 0u) return 0.0f;
+    return (float)inter / (float)(na + nb - inter);
+}
+__host__ __device__ inline float clamp_f32max(double v) {  // 943-948, 1054-1058
+    return v > (double)kF32Max ? kF32Max : (float)v;
+}
+
+// DistanceMetric::compute (distance.rs:76-88) from the sums of one pass: mag_a / na are the query's magnitude_f64 and stored count
+__host__ __device__ inline float finish_pair(int kind, const PairSums& s, double mag_a, uint32_t na, float cw, float sw, float mw) {
+    switch (kind) {
+        case NMN_XMETRIC_COSINE: return cos_from(s.dot, mag_a, s.sb);
+        case NMN_XMETRIC_ANGULAR:
+        case NMN_XMETRIC_GEODESIC: {  // angular_distance, 795-798: acos in f64 of the f32 cosine, rounded once
+            const float c = cos_from(s.dot, mag_a, s.sb);
+            const float cl = c < -1.0f ? -1.0f : (c > 1.0f ? 1.0f : c);
+            return (float)acos((double)cl);
+        }
+        case NMN_XMETRIC_JACCARD: return jaccard_from(na, s.nb, s.inter);
+        case NMN_XMETRIC_OVERLAP: {  // overlap_coefficient, 852-878
+            if (na == 0u || s.nb == 0u) return 0.0f;
+            return (float)s.inter / (float)(na < s.nb ? na : s.nb);
+        }
+        case NMN_XMETRIC_WEIGHTED_JACCARD: return s.wmax == 0.0 ? 1.0f : (float)(s.wmin / s.wmax);  // 930-934
+        case NMN_XMETRIC_EUCLIDEAN: return clamp_f32max(__builtin_sqrt(s.sd));
+        case NMN_XMETRIC_MANHATTAN: return clamp_f32max(s.man);
+        default: {  // GeometricConfig::compute, distance.rs:172-193
+            const float t0 = cw + sw;
+            const float tw = t0 + mw;
+            if (tw == 0.0f) return 0.0f;
+            const float cosine_sim = midpoint1(cos_from(s.dot, mag_a, s.sb));
+            const float jaccard_sim = jaccard_from(na, s.nb, s.inter);
+            const float dist = clamp_f32max(__builtin_sqrt(s.sd));
+            const float den = 1.0f + dist;
+            const float euclidean_sim = 1.0f / den;
+            const float m = mw * euclidean_sim;
+            const float inner = __builtin_fmaf(sw, jaccard_sim, m);
+            const float outer = __builtin_fmaf(cw, cosine_sim, inner);
+            return outer / tw;
+        }
+    }
+}
+
+struct RerankArgs {
+    const float* rows;      // row r at rows + r * ld
+    const float* queries;   // [nq][dim]
+    const uint64_t* ids;    // candidate ids: query q's at ids + q * id_stride (id_stride 0: one list for every query)
+    const uint32_t* counts; // [nq] candidates of each query (nullable: c for every query)
+    float* raw;             // [nq][c] compute()               (nullable)
+    float* sim;             // [nq][c] to_similarity(compute()) (nullable)
+    uint64_t n_rows;        // rows behind `rows`: an id at or past it is scored as NaN and never read
+    uint32_t ld, dim, nq, c, id_stride;
+    int kind;
+    float cw, sw, mw;
+};
+
+template <int CH>
+__global__ __launch_bounds__(256) void xmetric_rerank_kernel(RerankArgs p) {
+    __shared__ double s_mag;
+    __shared__ uint32_t s_na;
+    const uint32_t q = blockIdx.y;
+    const uint32_t l = threadIdx.x & 7u, g = threadIdx.x >> 3;
+    const float* a = p.queries + (size_t)q * p.dim;
+    if (threadIdx.x < 8u) {  // the query's own constants: sum of squares in index order and stored positions, once
+        double sa = 0.0;
+        uint32_t na = 0;
+        const uint32_t chunks = (p.dim + 7u) >> 3;
+        for (uint32_t c = 0; c < chunks; c++) {
+            const uint32_t e = 8u * c + l;
+            const float x = e < p.dim ? a[e] : 0.0f;
+            const bool sx = x != 0.0f;
+            const double xd = sx ? (double)x : 0.0;
+            na += sx ? 1u : 0u;
+            sa = chain8(sa, xd * xd);
+        }
+        na = group8_sum(na);
+        if (l == 0u) {
+            s_mag = __builtin_sqrt(sa);  // magnitude_f64, sparse_vector.rs:553-559
+            s_na = na;
+        }
+    }
+    __syncthreads();
+    const double mag_a = s_mag;
+    const uint32_t na = s_na;
+    const uint32_t count = p.counts ? min(p.counts[q], p.c) : p.c;
+    const uint32_t first = blockIdx.x * kPairsPerBlock;
+    const uint32_t last = min(first + kPairsPerBlock, count);
+    for (uint32_t e0 = first; e0 < last; e0 += kPairsPerRound) {
+        const uint32_t e = e0 + g;
+        const bool used = e < last;
+        const uint64_t id = used ? p.ids[(size_t)q * p.id_stride + e] : ~0ull;
+        const bool readable = id < p.n_rows;
+        const float* b = readable ? p.rows + (size_t)id * p.ld : a;  // (an unused group runs on the query: the wave stays whole)
+        const PairSums s = pair_pass<CH>(a, b, p.dim, l);
+        if (!used || l != 0u) continue;
+        const float raw = readable ? finish_pair(p.kind, s, mag_a, na, p.cw, p.sw, p.mw) : __int_as_float(0x7FC00000);
+        const size_t o = (size_t)q * p.c + e;
+        if (p.raw) p.raw[o] = raw;
+        if (p.sim) p.sim[o] = xm_to_similarity(p.kind, raw);
+    }
+}
+
+// The stable descending order of each query's `count` scores (lib.rs:2611-2617): entry e goes to
+// #{j : s_j > s_e} + #{j < e : s_j == s_e} — the rule hnsw_search_kernel's final ordering uses.  NaN scores (not a parity case)
+// rank behind every number, among themselves by position, so the ranks are always a permutation.
+struct OrderArgs {
+    const float* sim;        // [nq][c]
+    const uint64_t* ids;     // [nq][c]
+    const uint32_t* counts;  // [nq]
+    uint64_t* out_ids;       // [nq][top_k]
+    float* out_scores;       // [nq][top_k]
+    uint32_t* out_counts;    // [nq]
+    uint32_t c, top_k;
+};
+__device__ __forceinline__ bool ranks_before(float sj, uint32_t j, float se, uint32_t e) {
+    const bool nj = sj != sj, ne = se != se;
+    if (nj || ne) return (!nj && ne) || (nj && ne && j < e);
+    return sj > se || (sj == se && j < e);
+}
+__global__ __launch_bounds__(256) void xmetric_order_kernel(OrderArgs p) {
+    const uint32_t q = blockIdx.y;
+    const uint32_t count = min(p.counts[q], p.c);
+    const float* s = p.sim + (size_t)q * p.c;
+    const uint64_t* ids = p.ids + (size_t)q * p.c;
+    uint64_t* o_ids = p.out_ids + (size_t)q * p.top_k;
+    float* o_sc = p.out_scores + (size_t)q * p.top_k;
+    const uint32_t stride = gridDim.x * 256u;
+    for (uint32_t e = blockIdx.x * 256u + threadIdx.x; e < count; e += stride) {
+        const float se = s[e];
+        uint32_t rank = 0;
+        for (uint32_t j = 0; j < count; j++) rank += ranks_before(s[j], j, se, e) ? 1u : 0u;
+        if (rank < p.top_k) {
+            o_ids[rank] = ids[e];
+            o_sc[rank] = se;
+        }
+    }
+    const uint32_t n_out = min(count, p.top_k);
+    for (uint32_t i = n_out + blockIdx.x * 256u + threadIdx.x; i < p.top_k; i += stride) {
+        o_ids[i] = ~0ull;
+        o_sc[i] = __int_as_float(0xFF800000u);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) p.out_counts[q] = n_out;
+}
+
+// ---- more candidates than the rank count should order: the large-k sort (nmn_sortk.hip) --------------------------------------
+// Its composite keys order by (score descending with -0.0 == +0.0, NaN last, position ascending): the same permutation as
+// ranks_before, for one query per call.
+constexpr uint32_t kRankMax = 16384;  // c x c comparisons a query up to here
+uint32_t sort_from() {  // NMN_XMETRIC_SORT_FROM=<c>: the sort orders every call with more than c candidates (A/B runs, same bits);
+                        // read once per call, by xmetric_order_scratch_bytes — the launcher follows what that returned
+    const char* e = getenv("NMN_XMETRIC_SORT_FROM");
+    return e && *e ? (uint32_t)strtoul(e, nullptr, 10) : kRankMax;
+}
+__global__ __launch_bounds__(256) void xmetric_sort_prep_kernel(const float* __restrict__ sim, const uint32_t* __restrict__ count_q,
+                                                                uint32_t c, uint32_t* __restrict__ bits) {
+    const uint32_t count = min(*count_q, c);
+    for (uint32_t e = blockIdx.x * 256u + threadIdx.x; e < c; e += gridDim.x * 256u) {
+        const float v = sim[e];
+        bits[e] = e < count ? (v != v ? 0x7FC00000u : f2u(v)) : kScoreSentinelBits;
+    }
+}
+__global__ __launch_bounds__(256) void xmetric_sort_gather_kernel(const uint64_t* __restrict__ pos, const float* __restrict__ sim,
+                                                                  const uint64_t* __restrict__ ids, uint32_t c, uint32_t top_k,
+                                                                  uint64_t* __restrict__ o_ids, float* __restrict__ o_sc) {
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < top_k; i += gridDim.x * 256u) {
+        const uint64_t p = pos[i];
+        const bool used = p < (uint64_t)c;
+        o_ids[i] = used ? ids[p] : ~0ull;
+        o_sc[i] = used ? sim[p] : __int_as_float(0xFF800000u);
+    }
+}
+struct SortScratch {
+    uint64_t* keys;
+    uint64_t* pos;
+    uint32_t* bits;
+    float* scores;
+    size_t bytes;
+};
+SortScratch sort_scratch(void* base, uint32_t c, uint32_t top_k) {
+    SortScratch r{};
+    const size_t n_keys = (size_t)largek_sort_len(c);
+    r.bytes = (n_keys + top_k) * 8 + ((size_t)c + top_k) * 4;
+    if (!base) return r;  // (the size alone)
+    r.keys = static_cast<uint64_t*>(base);
+    r.pos = r.keys + n_keys;
+    r.bits = reinterpret_cast<uint32_t*>(r.pos + top_k);
+    r.scores = reinterpret_cast<float*>(r.bits + c);
+    return r;
+}
+
+hipError_t launch_rerank(const RerankArgs& a, hipStream_t s) {
+    if (a.nq == 0 || a.c == 0) return hipSuccess;
+    const dim3 grid((a.c + kPairsPerBlock - 1) / kPairsPerBlock, a.nq);
+    switch (chains_of(a.kind)) {
+        case kChCos: hipLaunchKernelGGL(xmetric_rerank_kernel<kChCos>, grid, dim3(256), 0, s, a); break;
+        case kChSet: hipLaunchKernelGGL(xmetric_rerank_kernel<kChSet>, grid, dim3(256), 0, s, a); break;
+        case kChWJ: hipLaunchKernelGGL(xmetric_rerank_kernel<kChWJ>, grid, dim3(256), 0, s, a); break;
+        case kChEucl: hipLaunchKernelGGL(xmetric_rerank_kernel<kChEucl>, grid, dim3(256), 0, s, a); break;
+        case kChManh: hipLaunchKernelGGL(xmetric_rerank_kernel<kChManh>, grid, dim3(256), 0, s, a); break;
+        default: hipLaunchKernelGGL(xmetric_rerank_kernel<kChComposite>, grid, dim3(256), 0, s, a); break;
+    }
+    return hipGetLastError();
+}
+
+}  // namespace
+
+size_t xmetric_order_scratch_bytes(uint32_t c, uint32_t top_k) { return c > sort_from() ? sort_scratch(nullptr, c, top_k).bytes : 0; }
+
+bool xmetric_valid(const nmn_xmetric* m) { return m && m->kind >= NMN_XMETRIC_COSINE && m->kind <= NMN_XMETRIC_COMPOSITE; }
+
+hipError_t launch_xmetric_rerank(const float* rows, uint32_t ld, uint32_t dim, uint64_t n_rows, const float* queries, uint32_t nq,
+                                 uint32_t c, const uint64_t* cand_ids, const uint32_t* cand_counts, const nmn_xmetric& m,
+                                 uint32_t top_k, float* sim, uint64_t* out_ids, float* out_scores, uint32_t* out_counts,
+                                 void* order_scratch, hipStream_t s) {
+    if (nq == 0) return hipSuccess;
+    RerankArgs a{};
+    a.rows = rows;
+    a.queries = queries;
+    a.ids = cand_ids;
+    a.counts = cand_counts;
+    a.raw = nullptr;
+    a.sim = sim;
+    a.n_rows = n_rows;
+    a.ld = ld;
+    a.dim = dim;
+    a.nq = nq;
+    a.c = c;
+    a.id_stride = c;
+    a.kind = m.kind;
+    a.cw = m.cosine_weight;
+    a.sw = m.structural_weight;
+    a.mw = m.magnitude_weight;
+    hipError_t e = launch_rerank(a, s);
+    if (e != hipSuccess) return e;
+    if (order_scratch) {  // query by query through the large-k sort (the caller's xmetric_order_scratch_bytes said so)
+        const SortScratch w = sort_scratch(order_scratch, c, top_k);
+        const uint32_t gc = std::min<uint32_t>((c + 255u) / 256u, 4096u), gk = std::min<uint32_t>((top_k + 255u) / 256u, 4096u);
+        for (uint32_t q = 0; q < nq; q++) {
+            const float* sim_q = sim + (size_t)q * c;
+            hipLaunchKernelGGL(xmetric_sort_prep_kernel, dim3(gc), dim3(256), 0, s, sim_q, cand_counts + q, c, w.bits);
+            e = launch_largek(w.bits, c, w.keys, top_k, 0, w.pos, w.scores, out_counts + q, s);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL(xmetric_sort_gather_kernel, dim3(gk), dim3(256), 0, s, w.pos, sim_q, cand_ids + (size_t)q * c, c, top_k,
+                               out_ids + (size_t)q * top_k, out_scores + (size_t)q * top_k);
+        }
+        return hipGetLastError();
+    }
+    OrderArgs o{sim, cand_ids, cand_counts, out_ids, out_scores, out_counts, c, top_k};
+    const uint32_t gx = std::max<uint32_t>(1, std::min<uint32_t>((std::max(c, top_k) + 255u) / 256u, 1024u));
+    hipLaunchKernelGGL(xmetric_order_kernel, dim3(gx, nq), dim3(256), 0, s, o);
+    return hipGetLastError();
+}
+
+}  // namespace nmn
+
+using namespace nmn;
+
+// ---- the C ABI -------------------------------------------------------------------------------------------------------------
+static void set_geometric(nmn_xmetric* m, float cw, float sw, float mw) {
+    if (!m) return;
+    m->kind = NMN_XMETRIC_COMPOSITE;
+    m->cosine_weight = cw;
+    m->structural_weight = sw;
+    m->magnitude_weight = mw;
+}
+extern "C" void nmn_xmetric_geometric_default(nmn_xmetric* m) { set_geometric(m, 0.5f, 0.3f, 0.2f); }             // distance.rs:127-135
+extern "C" void nmn_xmetric_geometric_angular_heavy(nmn_xmetric* m) { set_geometric(m, 0.8f, 0.1f, 0.1f); }       // 140-146
+extern "C" void nmn_xmetric_geometric_structural_heavy(nmn_xmetric* m) { set_geometric(m, 0.2f, 0.7f, 0.1f); }    // 150-156
+extern "C" void nmn_xmetric_geometric_conflict_detection(nmn_xmetric* m) { set_geometric(m, 0.4f, 0.5f, 0.1f); }  // 160-166
+
+extern "C" float nmn_xmetric_to_similarity(const nmn_xmetric* m, float raw) {
+    if (!xmetric_valid(m)) return std::nanf("");
+    return xm_to_similarity(m->kind, raw);
+}
+
+extern "C" int32_t nmn_xmetric_higher_is_better(const nmn_xmetric* m) {  // distance.rs:60-69
+    if (!xmetric_valid(m)) return 0;
+    switch (m->kind) {
+        case NMN_XMETRIC_COSINE:
+        case NMN_XMETRIC_JACCARD:
+        case NMN_XMETRIC_OVERLAP:
+        case NMN_XMETRIC_WEIGHTED_JACCARD:
+        case NMN_XMETRIC_COMPOSITE: return 1;
+        default: return 0;
+    }
+}
+
+extern "C" nmn_status nmn_index_score_rows_xmetric(nmn_index* idx, const float* queries, uint32_t nq, const nmn_xmetric* metric,
+                                                   const uint64_t* local_rows, uint32_t n_rows, float* out_raw,
+                                                   float* out_similarity) {
+    if (!idx || !queries || !local_rows || !metric) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (!xmetric_valid(metric)) return set_error(NMN_ERR_CONFIGURATION, "unknown extended distance metric");
+    if (nq == 0 || n_rows == 0 || (!out_raw && !out_similarity)) return NMN_OK;
+    if (nq > NMN_MAX_QUERIES) return set_error(NMN_ERR_INVALID_ARGUMENT, "nq out of range");
+    hipError_t e = hipSetDevice(idx->device);
+    if (e != hipSuccess) return set_error_hip(e, "hipSetDevice");
+    // idx->mu for the whole call, without nmn_index_score_rows' wait for idle slots: this only READS the rows, into buffers of its
+    // own, on host_stream behind every upload; searches in flight on the other slots read too.  Writers take idx->mu, so none runs
+    // under it.
+    std::unique_lock<std::mutex> lk(idx->mu);
+    for (uint32_t i = 0; i < n_rows; i++)
+        if (local_rows[i] >= idx->rows) return set_error(NMN_ERR_NOT_FOUND, "row out of range");
+    hipStream_t s = idx->host_stream;
+    const size_t n_out = (size_t)nq * n_rows;
+    float *dq = nullptr, *draw = nullptr, *dsim = nullptr;
+    uint64_t* drows = nullptr;
+    auto done = [&](nmn_status st) {
+        for (void* p : {(void*)dq, (void*)draw, (void*)dsim, (void*)drows})
+            if (p) (void)hipFree(p);
+        return st;
+    };
+#define XM_TRY(x) if ((e = (x)) != hipSuccess) return done(set_error_hip(e, #x))
+    XM_TRY(hipMalloc(reinterpret_cast<void**>(&dq), (size_t)nq * idx->dim * 4));
+    XM_TRY(hipMalloc(reinterpret_cast<void**>(&draw), n_out * 4));
+    XM_TRY(hipMalloc(reinterpret_cast<void**>(&dsim), n_out * 4));
+    XM_TRY(hipMalloc(reinterpret_cast<void**>(&drows), (size_t)n_rows * 8));
+    XM_TRY(hipMemcpyAsync(dq, queries, (size_t)nq * idx->dim * 4, hipMemcpyHostToDevice, s));
+    XM_TRY(hipMemcpyAsync(drows, local_rows, (size_t)n_rows * 8, hipMemcpyHostToDevice, s));
+    RerankArgs a{};
+    a.rows = idx->corpus;
+    a.queries = dq;
+    a.ids = drows;
+    a.counts = nullptr;
+    a.raw = draw;
+    a.sim = dsim;
+    a.n_rows = idx->rows;
+    a.ld = idx->ld;
+    a.dim = idx->dim;
+    a.nq = nq;
+    a.c = n_rows;
+    a.id_stride = 0;
+    a.kind = metric->kind;
+    a.cw = metric->cosine_weight;
+    a.sw = metric->structural_weight;
+    a.mw = metric->magnitude_weight;
+    XM_TRY(launch_rerank(a, s));
+    if (out_raw) XM_TRY(hipMemcpyAsync(out_raw, draw, n_out * 4, hipMemcpyDeviceToHost, s));
+    if (out_similarity) XM_TRY(hipMemcpyAsync(out_similarity, dsim, n_out * 4, hipMemcpyDeviceToHost, s));
+    XM_TRY(hipStreamSynchronize(s));
+#undef XM_TRY
+    return done(NMN_OK);
+}
+
+extern "C" nmn_status nmn_xmetric_score_host_rows(int32_t device, const float* rows_host, uint32_t n_rows, uint32_t dim,
+                                                  const float* query, const nmn_xmetric* metric, float* out_raw,
+                                                  float* out_similarity) {
+    if (!rows_host || !query || !metric) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (!xmetric_valid(metric)) return set_error(NMN_ERR_CONFIGURATION, "unknown extended distance metric");
+    if (dim == 0) return set_error(NMN_ERR_EMPTY_VECTOR, "dim == 0");
+    if (n_rows == 0 || (!out_raw && !out_similarity)) return NMN_OK;
+    hipError_t e;
+    if (device >= 0 && (e = hipSetDevice(device)) != hipSuccess) return set_error_hip(e, "hipSetDevice");
+    // one block for the call: rows | query | ids 0 .. n-1 | raw | similarity
+    const size_t row_bytes = (size_t)n_rows * dim * 4, q_bytes = ((size_t)dim * 4 + 7) & ~(size_t)7;
+    const size_t ids_off = ((row_bytes + 7) & ~(size_t)7) + q_bytes, raw_off = ids_off + (size_t)n_rows * 8;
+    std::vector<uint64_t> ids(n_rows);
+    for (uint32_t i = 0; i < n_rows; i++) ids[i] = i;
+    uint8_t* blk = nullptr;
+    if ((e = hipMalloc(reinterpret_cast<void**>(&blk), raw_off + (size_t)n_rows * 8)) != hipSuccess) return set_error_hip(e, "hipMalloc");
+    auto done = [&](nmn_status st) {
+        (void)hipFree(blk);
+        return st;
+    };
+    hipStream_t s = hipStreamPerThread;
+    float* d_rows = reinterpret_cast<float*>(blk);
+    float* d_q = reinterpret_cast<float*>(blk + ids_off - q_bytes);
+    float* d_raw = reinterpret_cast<float*>(blk + raw_off);
+#define XM_TRY(x) if ((e = (x)) != hipSuccess) return done(set_error_hip(e, #x))
+    XM_TRY(hipMemcpyAsync(d_rows, rows_host, row_bytes, hipMemcpyHostToDevice, s));
+    XM_TRY(hipMemcpyAsync(d_q, query, (size_t)dim * 4, hipMemcpyHostToDevice, s));
+    XM_TRY(hipMemcpyAsync(blk + ids_off, ids.data(), (size_t)n_rows * 8, hipMemcpyHostToDevice, s));
+    RerankArgs a{};
+    a.rows = d_rows;
+    a.queries = d_q;
+    a.ids = reinterpret_cast<const uint64_t*>(blk + ids_off);
+    a.counts = nullptr;
+    a.raw = d_raw;
+    a.sim = d_raw + n_rows;
+    a.n_rows = n_rows;
+    a.ld = dim;
+    a.dim = dim;
+    a.nq = 1;
+    a.c = n_rows;
+    a.id_stride = 0;
+    a.kind = metric->kind;
+    a.cw = metric->cosine_weight;
+    a.sw = metric->structural_weight;
+    a.mw = metric->magnitude_weight;
+    XM_TRY(launch_rerank(a, s));
+    if (out_raw) XM_TRY(hipMemcpyAsync(out_raw, a.raw, (size_t)n_rows * 4, hipMemcpyDeviceToHost, s));
+    if (out_similarity) XM_TRY(hipMemcpyAsync(out_similarity, a.sim, (size_t)n_rows * 4, hipMemcpyDeviceToHost, s));
+    XM_TRY(hipStreamSynchronize(s));
+#undef XM_TRY
+    return done(NMN_OK);
+}

@@ -102,6 +102,10 @@ ENGINE_SIGNATURES = {
     "nmn_engine_hnsw_key": (C.c_char_p, [vp, C.c_uint64]),
     "nmn_engine_hnsw_index": (vp, [vp]),
     "nmn_engine_search_with_hnsw": (C.c_int32, [vp, vp, vp, C.c_uint64, C.c_uint64, C.POINTER(vp)]),
+    "nmn_engine_search_with_hnsw_and_metric": (C.c_int32, [vp, vp, vp, C.c_uint64, C.c_uint64, C.POINTER(_capi.XMetric),
+                                                           C.POINTER(vp)]),
+    "nmn_engine_search_with_hnsw_and_metric_mapped": (C.c_int32, [vp, vp, vp, C.c_uint64, C.c_uint64, C.POINTER(_capi.XMetric),
+                                                                  C.POINTER(C.c_char_p), C.c_uint64, C.POINTER(vp)]),
     "nmn_engine_estimate_hnsw_memory": (C.c_int32, [vp, C.POINTER(C.c_uint64)]),
     "nmn_engine_set_entity_embedding": (C.c_int32, [vp, C.c_char_p, vp, C.c_uint64]),
     "nmn_engine_get_entity_embedding": (C.c_int32, [vp, C.c_char_p, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
@@ -774,6 +778,21 @@ class VectorEngine:
             ids = {k: i for i, k in enumerate(index.keys)}
             res = [SearchResult(key_mapping[ids[r.key]], r.score) for r in res if ids[r.key] < len(key_mapping)]
         return res
+
+    def search_with_hnsw_and_metric(self, index, key_mapping, query, top_k, metric):
+        """search_with_hnsw_and_metric (lib.rs:2560-2619): HNSW candidates re-ranked on the GPU under an ExtendedDistanceMetric.
+        A key_mapping other than the index's own goes to the library as it is (`key_mapping.get(*node_id)?`)."""
+        a, p, n = _vec(query)
+        h = vp()
+        m = metric._c()
+        if key_mapping is index.keys or list(key_mapping) == index.keys:
+            _check(_lib().nmn_engine_search_with_hnsw_and_metric(self._h, index._h, p, n, int(top_k), C.byref(m), C.byref(h)))
+        else:
+            keys = [k.encode() for k in key_mapping]
+            arr = (C.c_char_p * max(len(keys), 1))(*keys)
+            _check(_lib().nmn_engine_search_with_hnsw_and_metric_mapped(self._h, index._h, p, n, int(top_k), C.byref(m), arr,
+                                                                        len(keys), C.byref(h)))
+        return self._take_results(h)
 
     def estimate_hnsw_memory(self):
         """estimate_hnsw_memory (lib.rs:2489-2509); host arithmetic."""

@@ -275,6 +275,22 @@ class GpuFlatIndex:
                                                    _ptr(out)))
         return out
 
+    def score_rows_xmetric(self, queries, local_rows, metric):
+        """ExtendedDistanceMetric on explicit rows (nmn_index_score_rows_xmetric): (compute(), to_similarity(compute())), each
+        f32 [nq, len(local_rows)]."""
+        q = _f32(queries)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.shape[1] != self.dim:
+            raise _capi.NeumannGpuError(_capi.ERR_DIMENSION_MISMATCH, f"expected {self.dim}, got {q.shape[1]}")
+        r = np.ascontiguousarray(local_rows, dtype=np.uint64)
+        raw = np.empty((q.shape[0], r.size), dtype=np.float32)
+        sim = np.empty((q.shape[0], r.size), dtype=np.float32)
+        m = metric._c()
+        _capi.check(self._lib.nmn_index_score_rows_xmetric(self._h, _ptr(q), q.shape[0], C.byref(m), _ptr(r), r.size, _ptr(raw),
+                                                           _ptr(sim)))
+        return raw, sim
+
     def read_probe(self, reps=3):
         """GB/s of a pure read sweep over this shard (the scan's access pattern without arithmetic)."""
         out = C.c_double()

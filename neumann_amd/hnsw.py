@@ -180,3 +180,50 @@ class GpuHnsw:
             self._h, C.c_void_p(queries_t.data_ptr()), nq, k, 0 if ef is None else int(ef), C.c_void_p(ids.data_ptr()),
             C.c_void_p(sc.data_ptr()), C.c_void_p(counts.data_ptr()), _stream_ptr(stream)))
         return ids, sc, counts
+
+    def search_metric(self, queries, top_k, metric, with_stats=False):
+        """search_with_hnsw_and_metric's steps per query (nmn_hnsw_search_metric): c = max(2 top_k, 10) candidates from the walk,
+        re-ranked under `metric` (an ExtendedDistanceMetric), the first top_k of the stable descending order.
+        -> (ids u64 [nq,top_k], scores f32 [nq,top_k], counts u32 [nq])"""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.shape[1] != self.dim:
+            raise _capi.NeumannGpuError(_capi.ERR_DIMENSION_MISMATCH, f"expected {self.dim}, got {q.shape[1]}")
+        nq, k = q.shape[0], int(top_k)
+        ids = np.empty((nq, max(k, 1)), dtype=np.uint64)
+        sc = np.empty((nq, max(k, 1)), dtype=np.float32)
+        counts = np.empty(nq, dtype=np.uint32)
+        st = _capi.SearchStats()
+        m = metric._c()
+        _capi.check(self._lib.nmn_hnsw_search_metric(self._h, C.c_void_p(q.ctypes.data), nq, k, C.byref(m),
+                                                     C.c_void_p(ids.ctypes.data), C.c_void_p(sc.ctypes.data),
+                                                     C.c_void_p(counts.ctypes.data), C.byref(st)))
+        return (ids, sc, counts, st) if with_stats else (ids, sc, counts)
+
+    def search_metric_device(self, queries_t, top_k, metric, out=None, stream=None):
+        """`search_metric` with torch device tensors, in stream order (nmn_hnsw_search_metric_device); same conventions as
+        `search_device`."""
+        import torch
+
+        if not (isinstance(queries_t, torch.Tensor) and queries_t.is_cuda):
+            raise _capi.NeumannGpuError(_capi.ERR_INVALID_ARGUMENT, "queries must be a device tensor")
+        if queries_t.dtype != torch.float32 or not queries_t.is_contiguous():
+            raise _capi.NeumannGpuError(_capi.ERR_INVALID_ARGUMENT, "queries must be contiguous float32")
+        if queries_t.dim() == 1:
+            queries_t = queries_t[None, :]
+        nq, k = queries_t.shape[0], int(top_k)
+        if queries_t.shape[1] != self.dim:
+            raise _capi.NeumannGpuError(_capi.ERR_DIMENSION_MISMATCH, f"expected {self.dim}")
+        if out is None:
+            kk = max(k, 1)
+            ids = torch.empty((nq, kk), dtype=torch.int64, device=queries_t.device)
+            sc = torch.empty((nq, kk), dtype=torch.float32, device=queries_t.device)
+            counts = torch.empty((nq,), dtype=torch.int32, device=queries_t.device)
+        else:
+            ids, sc, counts = out
+        m = metric._c()
+        _capi.check(self._lib.nmn_hnsw_search_metric_device(
+            self._h, C.c_void_p(queries_t.data_ptr()), nq, k, C.byref(m), C.c_void_p(ids.data_ptr()), C.c_void_p(sc.data_ptr()),
+            C.c_void_p(counts.data_ptr()), _stream_ptr(stream)))
+        return ids, sc, counts

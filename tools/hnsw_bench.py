@@ -19,7 +19,14 @@ and 200 at k = 10 it reports, as one JSON line:
   *_spread                    (max - min) / median over --repeats repetitions of the whole measurement
   recall_at_10                of the walk against the exhaustive search (1024 queries)
   evals_per_query             distance evaluations per query (nmn_search_stats.rows_scanned)
-and checks that device, host-buffer and host-walk answers are the same bits."""
+and checks that device, host-buffer and host-walk answers are the same bits.
+
+  python tools/hnsw_bench.py --rows 50000 --dim 128 --metric composite     # or cosine, angular, weighted_jaccard, ...
+With a NAME instead of a number, --metric is an ExtendedDistanceMetric and the tool times the re-rank instead (docs/hnsw.md §8):
+nmn_hnsw_search_metric_device at top_k = --k beside nmn_hnsw_search_device at k = c = max(2 top_k, 10) — the walk alone, the same
+candidates — at the preset's ef_search (50 by default), 1 / 64 / 1024 queries per call, HIP events around each call on one stream, the two alternating call by
+call: medians of --calls (a fifth of it at 1024 queries), spread over --repeats repetitions.  The index metric stays cosine.
+--launch-calls N then makes N search_metric_device calls and nothing else."""
 import argparse
 import json
 import os
@@ -31,12 +38,55 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
+def time_rerank(g, xmetric, Q, qd, k, s, args):
+    """device time of search_metric_device (top_k = k) and of search_device at k = c and the index's ef_search: the walk alone"""
+    import torch
+    c = min(max(2 * k, 10), max(len(g), 1))
+    ef = g.config.ef_search  # what search_metric_device walks with: the two columns are the same walk under every preset
+    r = {"top_k": k, "c": c, "ef": ef}
+    bufs = {}
+    for nq in (1, 64, 1024):
+        bufs[nq] = tuple((torch.empty((nq, kk), dtype=torch.int64, device="cuda"), torch.empty((nq, kk), dtype=torch.float32, device="cuda"),
+                          torch.empty((nq,), dtype=torch.int32, device="cuda")) for kk in (k, c))
+        g.search_metric_device(qd[:nq], k, xmetric, out=bufs[nq][0], stream=s)  # warm every shape
+        g.search_device(qd[:nq], c, ef, out=bufs[nq][1], stream=s)
+    s.synchronize()
+    got = g.search_metric(Q[:64], k, xmetric, with_stats=True)
+    r["device_and_host_buffers_agree"] = bool(
+        np.array_equal(bufs[64][0][0].cpu().numpy().view(np.uint64), got[0]) and
+        np.array_equal(bufs[64][0][1].cpu().numpy().view(np.uint32), got[1].view(np.uint32)))
+    r["candidates_rescored"] = int(got[3].candidates_rescored)
+    reps = {}
+    for _ in range(args.repeats):
+        for nq, calls in ((1, args.calls), (64, args.calls), (1024, max(args.calls // 5, 5))):
+            ev_m, ev_w = [], []
+            for _ in range(calls):  # the two alternate call by call: both see the same machine state
+                e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+                e[0].record(s)
+                g.search_metric_device(qd[:nq], k, xmetric, out=bufs[nq][0], stream=s)
+                e[1].record(s)
+                e[2].record(s)
+                g.search_device(qd[:nq], c, ef, out=bufs[nq][1], stream=s)
+                e[3].record(s)
+                ev_m.append((e[0], e[1]))
+                ev_w.append((e[2], e[3]))
+            s.synchronize()
+            reps.setdefault(f"metric_dev_ms_per_call_nq{nq}", []).append(float(np.median([a.elapsed_time(b) for a, b in ev_m])))
+            reps.setdefault(f"walk_dev_ms_per_call_nq{nq}", []).append(float(np.median([a.elapsed_time(b) for a, b in ev_w])))
+    for key, v in reps.items():
+        r[key] = round(float(np.median(v)), 5)
+        r[key + "_spread"] = round(float((max(v) - min(v)) / np.median(v)), 3)
+    for nq in (1, 64, 1024):
+        r[f"rerank_extra_ms_per_call_nq{nq}"] = round(r[f"metric_dev_ms_per_call_nq{nq}"] - r[f"walk_dev_ms_per_call_nq{nq}"], 5)
+    return r
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1_000_000)
     ap.add_argument("--dim", type=int, default=128)
     ap.add_argument("--preset", default="default", choices=["default", "high_recall", "high_speed"])
-    ap.add_argument("--metric", type=int, default=0)
+    ap.add_argument("--metric", default="0", help="a number: the index's HNSWDistanceMetric; a name: time the re-rank under that ExtendedDistanceMetric")
     ap.add_argument("--calls", type=int, default=50)
     ap.add_argument("--b2b", type=int, default=100)
     ap.add_argument("--repeats", type=int, default=3)
@@ -44,9 +94,15 @@ def main():
     ap.add_argument("--launch-calls", type=int, default=None)
     args = ap.parse_args()
     import torch
-    from neumann_amd import DistanceMetric, GpuHnsw, HNSWConfig, synth_rows
+    from neumann_amd import DistanceMetric, ExtendedDistanceMetric, GpuHnsw, HNSWConfig, synth_rows
 
     n, d, k = args.rows, args.dim, args.k
+    xmetric = None
+    if args.metric.lstrip("-").isdigit():
+        args.metric = int(args.metric)
+    else:
+        xmetric = ExtendedDistanceMetric.from_name(args.metric)
+        args.metric = 0
     cfg = getattr(HNSWConfig, args.preset)().with_distance_metric(args.metric)
     metric = DistanceMetric(args.metric)
     Q = synth_rows(0x2F8, 0, 1024, d)
@@ -62,12 +118,21 @@ def main():
         flat = g.vectors()
         s = torch.cuda.Stream()
         qd = torch.from_numpy(Q).cuda()
+        if xmetric is not None:
+            out["xmetric"] = xmetric.name
         if args.launch_calls is not None:
             with torch.cuda.stream(s):
                 for _ in range(args.launch_calls):
-                    g.search_device(qd[:64], k, 50, stream=s)
+                    if xmetric is not None:
+                        g.search_metric_device(qd[:64], k, xmetric, stream=s)
+                    else:
+                        g.search_device(qd[:64], k, 50, stream=s)
             s.synchronize()
             out["device_calls"] = args.launch_calls
+            print(json.dumps(out), flush=True)
+            return
+        if xmetric is not None:
+            out.update(time_rerank(g, xmetric, Q, qd, k, s, args))
             print(json.dumps(out), flush=True)
             return
         for ef in (50, 200):
