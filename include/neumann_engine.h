@@ -260,6 +260,24 @@ typedef struct nmn_engine_hnsw nmn_engine_hnsw; /* (HNSWIndex, Vec<String> key_m
  * HNSWConfig::default (build_hnsw_index_default, 2478-2480).  The graph is nmn_hnsw_insert's (the reference's, bit for bit); the
  * handle is a snapshot: later stores do not change it. */
 nmn_status nmn_engine_build_hnsw_index(nmn_engine* e, const nmn_hnsw_config* cfg, nmn_engine_hnsw** out);
+/* HNSWBuildOptions (lib.rs:848-932): the storage strategy (NMN_HNSW_STORAGE_*) and the HNSWConfig.  hnsw_config.storage is not
+ * read.  Presets: ::default (860-867: Dense, HNSWConfig::default), ::memory_optimized (880-885: Quantized, ::high_speed),
+ * ::high_recall (891-896: Dense, ::high_recall), ::sparse_optimized (902-907: Auto, ::default). */
+typedef struct nmn_hnsw_build_options {
+    int32_t storage;
+    uint32_t reserved; /* 0 */
+    nmn_hnsw_config hnsw_config;
+} nmn_hnsw_build_options;
+void nmn_hnsw_build_options_default(nmn_hnsw_build_options* opt);
+void nmn_hnsw_build_options_memory_optimized(nmn_hnsw_build_options* opt);
+void nmn_hnsw_build_options_high_recall(nmn_hnsw_build_options* opt);
+void nmn_hnsw_build_options_sparse_optimized(nmn_hnsw_build_options* opt);
+/* build_hnsw_index_with_options (lib.rs:2423-2470): the key order, dimension rules and empty-engine rule of
+ * nmn_engine_build_hnsw_index; every vector goes in by insert_with_strategy — Dense: insert, Quantized: insert_quantized (the
+ * handle is nmn_hnsw_create_with_storage's).  Auto is refused with NMN_ERR_CONFIGURATION.  opt NULL = ::default.
+ * nmn_engine_search_with_hnsw serves either handle.  nmn_engine_search_with_hnsw_and_metric(_mapped) on a quantized handle always
+ * takes the gathering path: the reference re-ranks with the engine's current f32 vectors, which the handle does not keep. */
+nmn_status nmn_engine_build_hnsw_index_with_options(nmn_engine* e, const nmn_hnsw_build_options* opt, nmn_engine_hnsw** out);
 void nmn_engine_hnsw_free(nmn_engine_hnsw* h);
 uint64_t nmn_engine_hnsw_len(const nmn_engine_hnsw* h);
 const char* nmn_engine_hnsw_key(const nmn_engine_hnsw* h, uint64_t id);

@@ -583,14 +583,17 @@ uint64_t nmn_ivf_hbm_bytes(nmn_ivf* ivf);
 
 /* ---- HNSW graph index (tensor_store/src/hnsw.rs:1554-2335), searched on the GPU ------------------------------- */
 
-/* `tensor_store::HNSWIndex` with dense storage.  The graph is built on the host in the reference's order (the build is
+/* `tensor_store::HNSWIndex` with dense or 8-bit quantized storage.  The graph is built on the host in the reference's order (the build is
  * sequential by definition of its result; the reference's is too) and is resident in HBM: layer 0 as n x m0 u32 slots and a
  * count per node, the upper layers as a compact n_upper x max_layer x m table with a row index per node.  Node id == row of
  * the flat index the handle owns (nmn_hnsw_vectors).  Answers are the reference's bit for bit, ties included: both priority
  * queues of search_layer are kept as the array algorithm of std::collections::BinaryHeap (docs/hnsw.md). */
 typedef struct nmn_hnsw nmn_hnsw;
 
-/* HNSWStorageStrategy (hnsw.rs): only Dense is served; the others are refused with NMN_ERR_CONFIGURATION. */
+/* HNSWStorageStrategy (vector_engine/src/lib.rs:833-846).  Dense and Quantized are served, Auto (sparse storage) is refused
+ * with NMN_ERR_CONFIGURATION.  The strategy's home is the build options, as in the reference: it is the `storage` argument of
+ * nmn_hnsw_create_with_storage (and nmn_hnsw_build_options.storage of neumann_engine.h).  nmn_hnsw_config.storage is the older
+ * field: nmn_hnsw_create reads it and serves NMN_HNSW_STORAGE_DENSE only. */
 #define NMN_HNSW_STORAGE_DENSE 0
 #define NMN_HNSW_STORAGE_AUTO 1
 #define NMN_HNSW_STORAGE_QUANTIZED 2
@@ -649,10 +652,41 @@ nmn_status nmn_hnsw_search_device(nmn_hnsw* h, const float* queries_dev, uint32_
 /* Entries of the results / candidate heaps a wave keeps in LDS (0 = default: 1024 results, 1024 .. 4096 candidates by ef).
  * Smaller heaps leave more LDS per workgroup; a query that outgrows them is answered by the spill launch, same bits. */
 nmn_status nmn_hnsw_set_heap_capacity(nmn_hnsw* h, uint32_t results, uint32_t candidates);
-/* The flat index holding the rows (exhaustive search over the same rows). */
+/* The flat index holding the rows (exhaustive search over the same rows).  NULL on a quantized handle: it keeps no f32 rows on
+ * the device. */
 nmn_index* nmn_hnsw_vectors(nmn_hnsw* h);
-/* Device memory the index holds: rows, magnitudes, mirrors, adjacency. */
+/* Device memory the index holds: rows, magnitudes, mirrors, adjacency (dense); codes, records, adjacency (quantized). */
 uint64_t nmn_hnsw_hbm_bytes(nmn_hnsw* h);
+
+/* nmn_hnsw_create with the storage strategy of HNSWBuildOptions: `storage` is NMN_HNSW_STORAGE_*, cfg->storage is not read.
+ * DENSE is exactly nmn_hnsw_create.  QUANTIZED: nmn_hnsw_insert is insert_quantized (hnsw.rs:1711-1714) — every row becomes a
+ * ScalarQuantizedVector (from_dense, 324-356: scale (max - min) / 255, or 1.0 below f32::EPSILON; codes rounded half away from
+ * zero), resident in HBM as n x ld8 codes (ld8 = dim rounded up to 16) and one 16-byte record {scale, min_val, magnitude,
+ * squared_magnitude} per row.  Searches and insertion score a row against a query by dot_dense / euclidean_distance_dense /
+ * the cosine of EmbeddingStorage (414-527, 1035-1045) on the codes; pruning dequantizes both rows (2489-2500, 2585-2589,
+ * 2662-2666).  Same graph, ids and score bits as the reference.  nmn_hnsw_vectors is NULL and nmn_hnsw_search_metric* are
+ * refused with NMN_ERR_CONFIGURATION (they re-rank with the f32 rows of nmn_hnsw_vectors); every other entry works unchanged.
+ * AUTO: NMN_ERR_CONFIGURATION.  A handle has one strategy. */
+nmn_status nmn_hnsw_create_with_storage(const nmn_hnsw_config* cfg, int32_t storage, uint32_t dim, uint64_t capacity_hint,
+                                        int32_t device, nmn_hnsw** out);
+int32_t nmn_hnsw_storage(const nmn_hnsw* h); /* NMN_HNSW_STORAGE_DENSE or _QUANTIZED */
+/* The ScalarQuantizedVector of a node: codes_out[dim], scale, min_val (each nullable).  Dense handle: NMN_ERR_CONFIGURATION. */
+nmn_status nmn_hnsw_quantized_row(nmn_hnsw* h, uint64_t node, uint8_t* codes_out, float* scale, float* min_val);
+/* HNSWIndex::get_vector: out[dim] = the row as inserted (dense) or dequantize() = code.mul_add(scale, min_val) (quantized). */
+nmn_status nmn_hnsw_get_vector(nmn_hnsw* h, uint64_t node, float* out);
+/* HNSWMemoryStats (hnsw.rs:2733-2768); embedding_bytes = 4 dim per dense node, 16 + dim per quantized node. */
+typedef struct nmn_hnsw_memstats {
+    uint64_t total_nodes;
+    uint64_t dense_count;
+    uint64_t sparse_count;
+    uint64_t delta_count;
+    uint64_t tt_count;
+    uint64_t quantized_count;
+    uint64_t pq_count;
+    uint64_t binary_count;
+    uint64_t embedding_bytes;
+} nmn_hnsw_memstats;
+nmn_status nmn_hnsw_memory_stats(nmn_hnsw* h, nmn_hnsw_memstats* out);
 
 /* ---- extended distance metrics: the re-rank of search_with_hnsw_and_metric ------------------------------------ */
 

@@ -9,7 +9,7 @@ from .flat_index import (DistanceMetric, GpuFlatIndex, merge_topk_device, merge_
                          merge_topk_host, packed_layout, synth_rows)
 
 from .sharded import GpuShardedIndex  # noqa: F401,E402
-from .hnsw import GpuHnsw, HNSWConfig  # noqa: F401,E402
+from .hnsw import GpuHnsw, HNSWBuildOptions, HNSWConfig  # noqa: F401,E402
 from .xmetric import ExtendedDistanceMetric, GeometricConfig  # noqa: F401,E402
 
 __version__ = "0.3.0"

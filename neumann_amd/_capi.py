@@ -98,6 +98,17 @@ class HnswConfig(C.Structure):
 HNSW_STORAGE_DENSE, HNSW_STORAGE_AUTO, HNSW_STORAGE_QUANTIZED = range(3)
 
 
+class HnswBuildOptions(C.Structure):
+    """nmn_hnsw_build_options (HNSWBuildOptions, vector_engine/src/lib.rs:848-858; include/neumann_engine.h)."""
+    _fields_ = [("storage", C.c_int32), ("reserved", C.c_uint32), ("hnsw_config", HnswConfig)]
+
+
+class HnswMemStats(C.Structure):
+    """nmn_hnsw_memstats (HNSWMemoryStats, tensor_store/src/hnsw.rs:2733-2768)."""
+    _fields_ = [(n, C.c_uint64) for n in ("total_nodes", "dense_count", "sparse_count", "delta_count", "tt_count",
+                                          "quantized_count", "pq_count", "binary_count", "embedding_bytes")]
+
+
 class XMetric(C.Structure):
     """nmn_xmetric (tensor_store::DistanceMetric, tensor_store/src/distance.rs:13-52; the weights are GeometricConfig, 115-125)."""
     _fields_ = [("kind", C.c_int32), ("cosine_weight", C.c_float), ("structural_weight", C.c_float),
@@ -214,6 +225,12 @@ SIGNATURES = {
     "nmn_hnsw_set_heap_capacity": (C.c_int32, [vp, C.c_uint32, C.c_uint32]),
     "nmn_hnsw_vectors": (vp, [vp]),
     "nmn_hnsw_hbm_bytes": (C.c_uint64, [vp]),
+    "nmn_hnsw_create_with_storage": (C.c_int32, [C.POINTER(HnswConfig), C.c_int32, C.c_uint32, C.c_uint64, C.c_int32,
+                                                 C.POINTER(vp)]),
+    "nmn_hnsw_storage": (C.c_int32, [vp]),
+    "nmn_hnsw_quantized_row": (C.c_int32, [vp, C.c_uint64, vp, f32p, f32p]),
+    "nmn_hnsw_get_vector": (C.c_int32, [vp, C.c_uint64, vp]),
+    "nmn_hnsw_memory_stats": (C.c_int32, [vp, C.POINTER(HnswMemStats)]),
     "nmn_xmetric_geometric_default": (None, [C.POINTER(XMetric)]),
     "nmn_xmetric_geometric_angular_heavy": (None, [C.POINTER(XMetric)]),
     "nmn_xmetric_geometric_structural_heavy": (None, [C.POINTER(XMetric)]),

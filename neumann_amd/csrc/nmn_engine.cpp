@@ -1759,14 +1759,8 @@ nmn_status nmn_engine_search_with_ivf(nmn_engine* e, nmn_engine_ivf* ivf, const 
 }
 
 // ---- HNSW (lib.rs:2378-2550) -------------------------------------------------------------------------
-nmn_status nmn_engine_build_hnsw_index(nmn_engine* e, const nmn_hnsw_config* cfg, nmn_engine_hnsw** out) {
-    if (!e || !out) return fail(NMN_ERR_INVALID_ARGUMENT, "null argument");
-    *out = nullptr;
-    nmn_hnsw_config c;
-    if (cfg) c = *cfg;
-    else nmn_hnsw_config_default(&c);
-    if (c.storage != NMN_HNSW_STORAGE_DENSE)
-        return fail(NMN_ERR_CONFIGURATION, "Configuration error: only HNSWStorageStrategy::Dense is served on the GPU (Auto / Quantized are out of scope)");
+// build_hnsw_index_with_options (lib.rs:2423-2470) for a storage the index serves (Dense, Quantized)
+static nmn_status build_hnsw_with_storage(nmn_engine* e, const nmn_hnsw_config& c, int32_t storage, nmn_engine_hnsw** out) {
     auto res = std::unique_ptr<nmn_engine_hnsw>(new (std::nothrow) nmn_engine_hnsw());
     if (!res) return fail(NMN_ERR_OUT_OF_MEMORY, "hnsw alloc");
     WriteLock g(e);
@@ -1793,7 +1787,7 @@ nmn_status nmn_engine_build_hnsw_index(nmn_engine* e, const nmn_hnsw_config* cfg
     }
     res->dim = dim;
     if (dim > 0xFFFFFFFFull) return fail(NMN_ERR_INVALID_ARGUMENT, "dimension does not fit the device index (> 2^32 - 1)");
-    nmn_status st = nmn_hnsw_create(&c, (uint32_t)dim, n, e->cfg.device, &res->index);
+    nmn_status st = nmn_hnsw_create_with_storage(&c, storage, (uint32_t)dim, n, e->cfg.device, &res->index);
     if (st == NMN_ERR_CONFIGURATION) return fail(st, std::string("Configuration error: ") + nmn_last_error());
     if (st != NMN_OK) return err_gpu(st);
     st = nmn_hnsw_insert(res->index, rows.data(), n, nullptr);
@@ -1801,6 +1795,44 @@ nmn_status nmn_engine_build_hnsw_index(nmn_engine* e, const nmn_hnsw_config* cfg
     if (st != NMN_OK) return err_gpu(st);
     *out = res.release();
     return NMN_OK;
+}
+
+nmn_status nmn_engine_build_hnsw_index(nmn_engine* e, const nmn_hnsw_config* cfg, nmn_engine_hnsw** out) {
+    if (!e || !out) return fail(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    *out = nullptr;
+    nmn_hnsw_config c;
+    if (cfg) c = *cfg;
+    else nmn_hnsw_config_default(&c);
+    if (c.storage != NMN_HNSW_STORAGE_DENSE)
+        return fail(NMN_ERR_CONFIGURATION, "Configuration error: build_hnsw_index is HNSWStorageStrategy::Dense; the strategy is chosen by nmn_engine_build_hnsw_index_with_options");
+    return build_hnsw_with_storage(e, c, NMN_HNSW_STORAGE_DENSE, out);
+}
+
+static void fill_build_options(nmn_hnsw_build_options* o, int32_t storage, void (*preset)(nmn_hnsw_config*)) {
+    if (!o) return;
+    o->storage = storage;
+    o->reserved = 0;
+    preset(&o->hnsw_config);
+}
+void nmn_hnsw_build_options_default(nmn_hnsw_build_options* o) { fill_build_options(o, NMN_HNSW_STORAGE_DENSE, nmn_hnsw_config_default); }
+void nmn_hnsw_build_options_memory_optimized(nmn_hnsw_build_options* o) {
+    fill_build_options(o, NMN_HNSW_STORAGE_QUANTIZED, nmn_hnsw_config_high_speed);
+}
+void nmn_hnsw_build_options_high_recall(nmn_hnsw_build_options* o) { fill_build_options(o, NMN_HNSW_STORAGE_DENSE, nmn_hnsw_config_high_recall); }
+void nmn_hnsw_build_options_sparse_optimized(nmn_hnsw_build_options* o) { fill_build_options(o, NMN_HNSW_STORAGE_AUTO, nmn_hnsw_config_default); }
+
+nmn_status nmn_engine_build_hnsw_index_with_options(nmn_engine* e, const nmn_hnsw_build_options* opt, nmn_engine_hnsw** out) {
+    if (!e || !out) return fail(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    *out = nullptr;
+    nmn_hnsw_build_options o;
+    if (opt) o = *opt;
+    else nmn_hnsw_build_options_default(&o);
+    if (o.storage == NMN_HNSW_STORAGE_AUTO)
+        return fail(NMN_ERR_CONFIGURATION, "Configuration error: HNSWStorageStrategy::Auto (sparse storage) is not served on the GPU; Dense and Quantized are");
+    if (o.storage != NMN_HNSW_STORAGE_DENSE && o.storage != NMN_HNSW_STORAGE_QUANTIZED)
+        return fail(NMN_ERR_CONFIGURATION, "Configuration error: unknown HNSW storage strategy");
+    o.hnsw_config.storage = NMN_HNSW_STORAGE_DENSE;  // (the older field plays no part)
+    return build_hnsw_with_storage(e, o.hnsw_config, o.storage, out);
 }
 
 void nmn_engine_hnsw_free(nmn_engine_hnsw* h) { delete h; }
@@ -1877,7 +1909,7 @@ nmn_status nmn_engine_search_with_hnsw_and_metric_mapped(nmn_engine* e, nmn_engi
         return id < h->keys.size() ? h->keys[id].c_str() : nullptr;
     };
     ReadLock g(e);
-    if (!keys && h->writes_at_build == e->dflt.writes) {
+    if (!keys && h->writes_at_build == e->dflt.writes && nmn_hnsw_storage(h->index) == NMN_HNSW_STORAGE_DENSE) {
         // fast path: nothing was stored, deleted or cleared since build_hnsw_index, so the handle's rows ARE the current vectors of
         // its keys: walk, re-rank and ordering as one stream-ordered chain
         std::vector<uint64_t> ids(k);
@@ -1895,7 +1927,7 @@ nmn_status nmn_engine_search_with_hnsw_and_metric_mapped(nmn_engine* e, nmn_engi
         *out = res.release();
         return NMN_OK;
     }
-    // changed path: the walk, then the CURRENT vector of every candidate's key (`self.get_embedding(key).ok()?`, lib.rs:2595) gathered
+    // changed path (and every call on a quantized handle, which keeps no f32 rows): the walk, then the CURRENT vector of every candidate's key (`self.get_embedding(key).ok()?`, lib.rs:2595) gathered
     // into a staging matrix and scored there by the same kernel
     const uint64_t c64 = std::min<uint64_t>(std::max<uint64_t>(top_k > UINT64_MAX / 2 ? UINT64_MAX : 2 * top_k, 10), std::max<uint64_t>(len, 1));
     const uint32_t c = (uint32_t)c64;

@@ -15,6 +15,11 @@
 //       `left <= right`), then sifted up; into_iter = the backing vector's order.  Both heaps are kept as that array algorithm.
 //   search_layer (hnsw.rs:2276-2335), search_layer_greedy (2170-2200), search_with_ef (2069-2111), try_insert_embedding
 //       (1936-2051), random_level (1631-1651).
+//   HNSWStorageStrategy::Quantized (nmn_hnsw_create_with_storage): every row is a ScalarQuantizedVector (hnsw.rs:308-541).  The
+//       query side (search_layer* at search AND insert time) is dot_dense / squared_magnitude / euclidean_distance_dense on the
+//       codes, closed by one fused multiply-add each (`mul_add` = fmaf, the only fused operations of this file); the pruning
+//       side (the (Quantized, Quantized) arms, 2489-2500, 2585-2589, 2662-2666) is the dense arithmetic on the dequantized rows,
+//       which the host keeps where a dense handle keeps its rows.  The two sides differ in bits; both are restated.
 //   nmn_hnsw_search_metric* (the end of this file): the walk with k = c, then the re-rank of its candidates under an extended
 //       metric and their stable ordering (nmn_xmetric.hip) — VectorEngine::search_with_hnsw_and_metric, vector_engine/src/lib.rs:2560-2619.
 #include <algorithm>
@@ -146,16 +151,119 @@ __host__ __device__ inline float to_similarity(int metric, float d) {  // hnsw.r
     return 1.0f - d;
 }
 
+// ---- ScalarQuantizedVector on the host (hnsw.rs:324-368, 414-527) ----------------------------------------------------------------
+// from_dense: min / max by f32::min / f32::max folds, scale 1.0 when the range is below f32::EPSILON, round = half away from zero
+inline void h_quantize(const float* v, uint32_t dim, uint8_t* code, float* scale_out, float* min_out) {
+    float mn = INFINITY, mx = -INFINITY;
+    for (uint32_t i = 0; i < dim; i++) {
+        mn = fminf(mn, v[i]);
+        mx = fmaxf(mx, v[i]);
+    }
+    const float range = mx - mn;
+    const float scale = fabsf(range) < 1.1920928955078125e-07f ? 1.0f : range / 255.0f;
+    for (uint32_t i = 0; i < dim; i++) {
+        const float t = v[i] - mn;
+        float r = roundf(t / scale);
+        r = r < 0.0f ? 0.0f : (r > 255.0f ? 255.0f : r);
+        code[i] = (uint8_t)r;
+    }
+    *scale_out = scale;
+    *min_out = mn;
+}
+inline void h_dequantize(const uint8_t* code, uint32_t dim, float scale, float mn, float* out) {
+    for (uint32_t i = 0; i < dim; i++) out[i] = __builtin_fmaf((float)code[i], scale, mn);
+}
+// the eight chains of `y` alone (sum_y of dot_dense: it depends on the query only)
+inline float h_sum8(const float* y, uint32_t dim) {
+    float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    const uint32_t chunks = dim / 8;
+    for (uint32_t c = 0; c < chunks; c++)
+        for (int l = 0; l < 8; l++) acc[l] = acc[l] + y[8 * c + l];
+    float r = -0.0f;
+    for (int l = 0; l < 8; l++) r = r + acc[l];
+    for (uint32_t i = chunks * 8; i < dim; i++) r = r + y[i];
+    return r;
+}
+// dot_dense: q_dot_y in eight chains (product and sum rounded separately), then scale.mul_add(q_dot_y, min * sum_y)
+inline float h_q8_dot(const uint8_t* code, float scale, float mn, const float* y, float sum_y, uint32_t dim) {
+    float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    const uint32_t chunks = dim / 8;
+    for (uint32_t c = 0; c < chunks; c++)
+        for (int l = 0; l < 8; l++) {
+            const float p = (float)code[8 * c + l] * y[8 * c + l];
+            acc[l] = acc[l] + p;
+        }
+    float r = -0.0f;
+    for (int l = 0; l < 8; l++) r = r + acc[l];
+    for (uint32_t i = chunks * 8; i < dim; i++) {
+        const float p = (float)code[i] * y[i];
+        r = r + p;
+    }
+    const float ms = mn * sum_y;
+    return __builtin_fmaf(scale, r, ms);
+}
+// squared_magnitude: chains of q*q and q, then scale_sq.mul_add(sum_q_sq, ((2 scale) min).mul_add(sum_q, (min min) n))
+inline float h_q8_sqmag(const uint8_t* code, float scale, float mn, uint32_t dim) {
+    float a2[8] = {0, 0, 0, 0, 0, 0, 0, 0}, a1[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    const uint32_t chunks = dim / 8;
+    for (uint32_t c = 0; c < chunks; c++)
+        for (int l = 0; l < 8; l++) {
+            const float q = (float)code[8 * c + l];
+            const float p = q * q;
+            a2[l] = a2[l] + p;
+            a1[l] = a1[l] + q;
+        }
+    float s2 = -0.0f, s1 = -0.0f;
+    for (int l = 0; l < 8; l++) s2 = s2 + a2[l];
+    for (int l = 0; l < 8; l++) s1 = s1 + a1[l];
+    for (uint32_t i = chunks * 8; i < dim; i++) {
+        const float q = (float)code[i];
+        const float p = q * q;
+        s2 = s2 + p;
+        s1 = s1 + q;
+    }
+    const float n = (float)dim;
+    const float scale_sq = scale * scale;
+    const float min_sq = mn * mn;
+    const float two_s = 2.0f * scale;
+    const float tsm = two_s * mn;
+    const float msn = min_sq * n;
+    const float inner = __builtin_fmaf(tsm, s1, msn);
+    return __builtin_fmaf(scale_sq, s2, inner);
+}
+// what the query contributes to every distance, computed once: simd::magnitude (Cosine), sum_y (quantized rows), sum_of_squares
+// (quantized rows under Euclidean)
+struct HQ {
+    float mag = 0.0f, sum = 0.0f, sq = 0.0f;
+};
+// EmbeddingStorage::distance_dense on a Quantized row (hnsw.rs:1035-1045 with magnitude_immutable 401-407; 522-527; 1136-1138)
+inline float h_q8_distance(int metric, const uint8_t* code, float scale, float mn, float mag, float x_sq, const float* q, const HQ& hq,
+                           uint32_t dim) {
+    const float dot = h_q8_dot(code, scale, mn, q, hq.sum, dim);
+    if (metric == NMN_METRIC_DOT_PRODUCT) return -dot;
+    if (metric == NMN_METRIC_EUCLIDEAN) {
+        const float s = x_sq + hq.sq;
+        const float t = __builtin_fmaf(2.0f, -dot, s);
+        return sqrtf(t > 0.0f ? t : 0.0f);  // `.max(0.0)`: NaN and negatives to 0.0
+    }
+    if (mag == 0.0f || hq.mag == 0.0f) return 1.0f;
+    const float den = mag * hq.mag;
+    const float sim = dot / den;
+    return 1.0f - sim;
+}
+
 // ---- device graph --------------------------------------------------------------------------------------------------------------
 struct GraphDev {
     const float* corpus;    // the flat index's rows, stride ld
     const float* norms;     // simd::magnitude of every row (ingest kernels)
+    const uint8_t* codes;   // quantized handle: the codes, stride ld8 (dim rounded up to 16, the padding zero)
+    const float4* rec;      // quantized handle: {scale, min_val, simd::magnitude(dequantize()), squared_magnitude()} per row
     const uint32_t* l0;     // [n][m0] layer-0 neighbour slots, id-ascending
     const uint32_t* l0cnt;  // [n]
     const uint32_t* up_idx; // [n] row of the upper table, kNone for a level-0 node
     const uint32_t* up;     // [n_upper][up_layers][m]
     const uint32_t* upcnt;  // [n_upper][up_layers]
-    uint32_t ld, dim, m, m0, up_layers, n, entry, max_layer;
+    uint32_t ld, ld8, dim, m, m0, up_layers, n, entry, max_layer;
     int metric;
 };
 
@@ -238,11 +346,108 @@ __device__ __forceinline__ float pair_distance(const float* __restrict__ row, fl
     return 1.0f - r / (rowmag * qmag);
 }
 
+// sum_y of dot_dense (hnsw.rs:424, 443, 450, 458): the eight chains of the query alone, by the same pair of lanes.
+__device__ __forceinline__ float pair_sum(const float* q, uint32_t dim, uint32_t h) {
+    const uint32_t chunks = dim >> 3;
+    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
+    const float4* q4 = reinterpret_cast<const float4*>(q + 4u * h);
+    for (uint32_t c = 0; c < chunks; c++) {
+        const float4 y = q4[2u * c];
+        a0 = a0 + y.x;
+        a1 = a1 + y.y;
+        a2 = a2 + y.z;
+        a3 = a3 + y.w;
+    }
+    const float b0 = __shfl_xor(a0, 1), b1 = __shfl_xor(a1, 1), b2 = __shfl_xor(a2, 1), b3 = __shfl_xor(a3, 1);
+    float r = -0.0f;
+    r = r + (h ? b0 : a0);
+    r = r + (h ? b1 : a1);
+    r = r + (h ? b2 : a2);
+    r = r + (h ? b3 : a3);
+    r = r + (h ? a0 : b0);
+    r = r + (h ? a1 : b1);
+    r = r + (h ? a2 : b2);
+    r = r + (h ? a3 : b3);
+    for (uint32_t i = chunks * 8u; i < dim; i++) r = r + q[i];
+    return r;
+}
+
+// what a wave computes once per query: simd::magnitude (Cosine), and for quantized rows sum_y and sum_of_squares (Euclidean)
+struct QuerySide {
+    float mag, sum, sq;
+};
+
+__device__ __forceinline__ float ub0(uint32_t w) { return (float)(w & 0xFFu); }          // v_cvt_f32_ubyte0 .. 3
+__device__ __forceinline__ float ub1(uint32_t w) { return (float)((w >> 8) & 0xFFu); }
+__device__ __forceinline__ float ub2(uint32_t w) { return (float)((w >> 16) & 0xFFu); }
+__device__ __forceinline__ float ub3(uint32_t w) { return (float)(w >> 24); }
+
+// distance_dense on a ScalarQuantizedVector row, by the same PAIR of lanes as pair_distance: one 16-byte load holds the chunks 2j
+// and 2j + 1; both lanes of the pair issue it (one address, one request) and lane h takes the dwords h and 2 + h of it — the codes
+// 8c + 4h .. 8c + 4h + 3 of either chunk, its four chains.  A chain still sees the chunks in ascending order.  A chunk past the
+// last whole one (the second half of the last load when the count is odd, where the row's tail codes or its zero padding sit, and
+// the loads past the end) meets a query masked to +0.0: a code is never negative, so the product is +0.0 and changes no chain.
+// The scalar tail follows the lane sum; then dot_dense's one fused multiply-add and the metric's closing arithmetic on the record.
+__device__ __forceinline__ float q8_distance(const uint8_t* __restrict__ row, const float4 rec, const float* q, const QuerySide qs,
+                                             uint32_t dim, int metric, uint32_t h) {
+    const uint32_t chunks = dim >> 3;
+    const uint32_t loads = (chunks + 1u) >> 1;
+    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
+    const uint4* r16 = reinterpret_cast<const uint4*>(row);
+    const float4* q4 = reinterpret_cast<const float4*>(q + 4u * h);
+    const uint4 zu = make_uint4(0u, 0u, 0u, 0u);
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    constexpr int PF = 4;
+    for (uint32_t j0 = 0; j0 < loads; j0 += PF) {
+        uint4 x[PF];
+        float4 y0[PF], y1[PF];
+#pragma unroll
+        for (int i = 0; i < PF; i++) {
+            const uint32_t j = j0 + (uint32_t)i;
+            x[i] = j < loads ? r16[j] : zu;
+            y0[i] = 2u * j < chunks ? q4[4u * j] : z;
+            y1[i] = 2u * j + 1u < chunks ? q4[4u * j + 2u] : z;
+        }
+#pragma unroll
+        for (int i = 0; i < PF; i++) {
+            const uint32_t w0 = h ? x[i].y : x[i].x, w1 = h ? x[i].w : x[i].z;
+            a0 = a0 + ub0(w0) * y0[i].x;
+            a1 = a1 + ub1(w0) * y0[i].y;
+            a2 = a2 + ub2(w0) * y0[i].z;
+            a3 = a3 + ub3(w0) * y0[i].w;
+            a0 = a0 + ub0(w1) * y1[i].x;
+            a1 = a1 + ub1(w1) * y1[i].y;
+            a2 = a2 + ub2(w1) * y1[i].z;
+            a3 = a3 + ub3(w1) * y1[i].w;
+        }
+    }
+    const float b0 = __shfl_xor(a0, 1), b1 = __shfl_xor(a1, 1), b2 = __shfl_xor(a2, 1), b3 = __shfl_xor(a3, 1);
+    float r = -0.0f;
+    r = r + (h ? b0 : a0);
+    r = r + (h ? b1 : a1);
+    r = r + (h ? b2 : a2);
+    r = r + (h ? b3 : a3);
+    r = r + (h ? a0 : b0);
+    r = r + (h ? a1 : b1);
+    r = r + (h ? a2 : b2);
+    r = r + (h ? a3 : b3);
+    for (uint32_t i = chunks * 8u; i < dim; i++) r = r + (float)row[i] * q[i];
+    const float dot = __builtin_fmaf(rec.x, r, rec.y * qs.sum);  // scale.mul_add(q_dot_y, min * sum_y)
+    if (metric == NMN_METRIC_DOT_PRODUCT) return -dot;
+    if (metric == NMN_METRIC_EUCLIDEAN) {
+        const float t = __builtin_fmaf(2.0f, -dot, rec.w + qs.sq);
+        return d_sqrt(t > 0.0f ? t : 0.0f);
+    }
+    if (rec.z == 0.0f || qs.mag == 0.0f) return 1.0f;
+    return 1.0f - dot / (rec.z * qs.mag);
+}
+
 // One query per wave (one wave per workgroup).  SPILL == false: both heaps in LDS; a query whose candidate heap fills up is flagged
 // and left.  SPILL == true: workgroup b answers the flagged queries b, b + grid, ... from scratch with both heaps in its region of
 // global memory (candidates: n entries, the proven bound — nothing is pushed twice).
 // Only lane 0 touches the heaps; the other lanes learn what to do next through `ctrl` in LDS.
-template <bool SPILL>
+// Q8 == true: the rows are ScalarQuantizedVectors (codes + a record per row), scored by q8_distance.
+template <bool SPILL, bool Q8>
 __global__ __launch_bounds__(64) void hnsw_search_kernel(SearchArgs a) {
     extern __shared__ float4 smem4[];
     const GraphDev& g = a.g;
@@ -289,10 +494,24 @@ __global__ __launch_bounds__(64) void hnsw_search_kernel(SearchArgs a) {
         }
         float qmag = 0.0f;
         if (g.metric == NMN_METRIC_COSINE) qmag = d_sqrt(-pair_distance(qv, 0.f, qv, 0.f, g.dim, NMN_METRIC_DOT_PRODUCT, h));
-        uint32_t evals = 1;
+        QuerySide qside{qmag, 0.0f, 0.0f};
+        if (Q8) {
+            qside.sum = pair_sum(qv, g.dim, h);
+            if (g.metric == NMN_METRIC_EUCLIDEAN) qside.sq = -pair_distance(qv, 0.f, qv, 0.f, g.dim, NMN_METRIC_DOT_PRODUCT, h);
+        }
+        auto row_distance = [&](uint32_t node) -> float {
+            if constexpr (Q8)
+                return q8_distance(g.codes + (size_t)node * g.ld8, g.rec[node], qv, qside, g.dim, g.metric, h);
+            else
+                return pair_distance(g.corpus + (size_t)node * g.ld, g.norms[node], qv, qmag, g.dim, g.metric, h);
+        };
+        // distance evaluations.  The reference scores the entry of every search_layer* call again (one per greedy layer, one for
+        // search_layer); this kernel carries the distance along.  A quantized handle counts the evaluations the reference makes,
+        // as the host walk does; a dense handle keeps the count it has always reported.
+        uint32_t evals = Q8 ? g.max_layer + 1u : 1u;
         // greedy descent, hnsw.rs:2086-2092 / 2170-2200
         uint32_t cur = g.entry;
-        float cur_d = pair_distance(g.corpus + (size_t)cur * g.ld, g.norms[cur], qv, qmag, g.dim, g.metric, h);
+        float cur_d = row_distance(cur);
         for (uint32_t layer = g.max_layer; layer >= 1; layer--) {
             for (;;) {
                 const uint32_t ui = g.up_idx[cur];
@@ -307,7 +526,7 @@ __global__ __launch_bounds__(64) void hnsw_search_kernel(SearchArgs a) {
                     float d = 0.0f;
                     if (j < cnt) {
                         nid = base[j];
-                        d = pair_distance(g.corpus + (size_t)nid * g.ld, g.norms[nid], qv, qmag, g.dim, g.metric, h);
+                        d = row_distance(nid);
                     }
                     __syncthreads();
                     if (h == 0) {
@@ -370,7 +589,7 @@ __global__ __launch_bounds__(64) void hnsw_search_kernel(SearchArgs a) {
                     if (seen)
                         nid = kNone;
                     else
-                        d = pair_distance(g.corpus + (size_t)nid * g.ld, g.norms[nid], qv, qmag, g.dim, g.metric, h);
+                        d = row_distance(nid);
                 }
                 if (h == 0) {
                     stage_id[p] = nid;
@@ -453,11 +672,18 @@ struct nmn_hnsw {
     nmn_hnsw_config cfg{};
     uint32_t dim = 0;
     int device = 0;
-    nmn_index* vectors = nullptr;
-    uint64_t vec_cap = 0;
-    // host side: the rows, their magnitudes, the graph
+    int storage = NMN_HNSW_STORAGE_DENSE;  // one strategy per handle
+    nmn_index* vectors = nullptr;          // dense handle only
+    uint64_t vec_cap = 0;                  // rows the flat index (dense) or the code / record arrays (quantized) are allocated for
+    // host side: the rows (quantized handle: the DEQUANTIZED rows, what the pruning side computes on), their magnitudes, the graph
     std::vector<float> rows;
     std::vector<float> mags;
+    // quantized handle: ScalarQuantizedVector per row — codes [n][dim], scale, min_val, squared_magnitude()
+    std::vector<uint8_t> codes;
+    std::vector<float> qscale, qmin, qxsq;
+    void* d_codes = nullptr;  // [vec_cap][ld8] u8
+    void* d_rec = nullptr;    // [vec_cap] float4 {scale, min_val, magnitude, squared_magnitude}
+    uint32_t ld8 = 0;
     std::vector<uint8_t> level;
     std::vector<std::vector<std::vector<uint32_t>>> nbr;  // [node][layer], id-ascending
     uint64_t entry = ~0ull;
@@ -544,11 +770,32 @@ struct HostVisited {
     }
 };
 
-inline float node_distance(const nmn_hnsw* h, uint32_t node, const float* q, float qmag) {
-    return h_distance(h->cfg.distance_metric, h->rows.data() + (size_t)node * h->dim, h->mags[node], q, qmag, h->dim);
+// the query side: distance_dense(stored row `node`, q)
+inline float node_distance(const nmn_hnsw* h, uint32_t node, const float* q, const HQ& hq) {
+    if (h->storage == NMN_HNSW_STORAGE_QUANTIZED)
+        return h_q8_distance(h->cfg.distance_metric, h->codes.data() + (size_t)node * h->dim, h->qscale[node], h->qmin[node],
+                             h->mags[node], h->qxsq[node], q, hq, h->dim);
+    return h_distance(h->cfg.distance_metric, h->rows.data() + (size_t)node * h->dim, h->mags[node], q, hq.mag, h->dim);
+}
+// the pruning side: try_*_distance on two stored rows — dense arithmetic on the rows the host keeps (a quantized handle keeps the
+// dequantized rows and their simd::magnitude there: the (Quantized, Quantized) arms)
+inline float pair_of_nodes_distance(const nmn_hnsw* h, uint32_t a, uint32_t b) {
+    return h_distance(h->cfg.distance_metric, h->rows.data() + (size_t)b * h->dim, h->mags[b], h->rows.data() + (size_t)a * h->dim,
+                      h->mags[a], h->dim);
+}
+HQ host_query(const nmn_hnsw* h, const float* q) {
+    HQ hq;
+    const int metric = h->cfg.distance_metric;
+    const bool q8 = h->storage == NMN_HNSW_STORAGE_QUANTIZED;
+    if (metric == NMN_METRIC_COSINE || (q8 && metric == NMN_METRIC_EUCLIDEAN)) {
+        hq.sq = h_dot8(q, q, h->dim);
+        if (metric == NMN_METRIC_COSINE) hq.mag = sqrtf(hq.sq);
+    }
+    if (q8) hq.sum = h_sum8(q, h->dim);
+    return hq;
 }
 
-uint32_t host_greedy(const nmn_hnsw* h, const float* q, float qmag, uint32_t entry, uint32_t layer, uint64_t* evals) {
+uint32_t host_greedy(const nmn_hnsw* h, const float* q, const HQ& qmag, uint32_t entry, uint32_t layer, uint64_t* evals) {
     uint32_t cur = entry;
     float cur_d = node_distance(h, cur, q, qmag);
     (*evals)++;
@@ -572,7 +819,7 @@ uint32_t host_greedy(const nmn_hnsw* h, const float* q, float qmag, uint32_t ent
 }
 
 // search_layer: the results in the order the reference returns them (stable sort by distance of the heap's vector)
-void host_search_layer(const nmn_hnsw* h, const float* q, float qmag, uint32_t entry, uint64_t ef, uint32_t layer, HostVisited& vis,
+void host_search_layer(const nmn_hnsw* h, const float* q, const HQ& qmag, uint32_t entry, uint64_t ef, uint32_t layer, HostVisited& vis,
                        std::vector<Ent>& out, uint64_t* evals) {
     static thread_local std::vector<Ent> cand, res;  // grown on demand, kept: a walk touches a few thousand entries of a graph of millions
     vis.begin(h->level.size());
@@ -605,10 +852,6 @@ void host_search_layer(const nmn_hnsw* h, const float* q, float qmag, uint32_t e
     std::stable_sort(out.begin(), out.end(), [](const Ent& a, const Ent& b) { return a.d < b.d; });
 }
 
-float host_qmag(const nmn_hnsw* h, const float* q) {
-    return h->cfg.distance_metric == NMN_METRIC_COSINE ? sqrtf(h_dot8(q, q, h->dim)) : 0.0f;
-}
-
 // try_insert_embedding, hnsw.rs:1936-2051 (the row and its magnitude are already in h->rows / h->mags)
 void host_insert_node(nmn_hnsw* h, uint32_t node_id, HostVisited& vis) {
     const uint32_t node_level = next_level(h);
@@ -621,7 +864,7 @@ void host_insert_node(nmn_hnsw* h, uint32_t node_id, HostVisited& vis) {
     }
     const uint32_t current_max = h->max_layer;
     const float* q = h->rows.data() + (size_t)node_id * h->dim;
-    const float qmag = h->cfg.distance_metric == NMN_METRIC_COSINE ? sqrtf(h_dot8(q, q, h->dim)) : 0.0f;
+    const HQ qmag = host_query(h, q);  // (a quantized node's own query is its to_dense(), hnsw.rs:1985: the row kept here)
     uint64_t evals = 0;
     uint32_t cur = (uint32_t)h->entry;
     for (uint32_t layer = current_max; layer >= node_level + 1; layer--) cur = host_greedy(h, q, qmag, cur, layer, &evals);
@@ -641,9 +884,8 @@ void host_insert_node(nmn_hnsw* h, uint32_t node_id, HostVisited& vis) {
             std::vector<uint32_t>& lst = h->nbr[nb][layer];
             lst.insert(std::upper_bound(lst.begin(), lst.end(), node_id), node_id);  // push + sort: stays id-ascending
             if (lst.size() > m) {
-                const float* a = h->rows.data() + (size_t)nb * h->dim;
                 wd.clear();
-                for (uint32_t id : lst) wd.emplace_back(node_distance(h, id, a, h->mags[nb]), id);
+                for (uint32_t id : lst) wd.emplace_back(pair_of_nodes_distance(h, nb, id), id);
                 std::stable_sort(wd.begin(), wd.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
                 lst.clear();
                 for (size_t i = 0; i < m; i++) lst.push_back(wd[i].second);
@@ -662,7 +904,7 @@ void host_search_one(const nmn_hnsw* h, const float* q, uint32_t k, uint64_t ef,
                      uint32_t* count, uint64_t* evals) {
     uint32_t c = 0;
     if (h->entry != ~0ull) {
-        const float qmag = host_qmag(h, q);
+        const HQ qmag = host_query(h, q);
         uint32_t cur = (uint32_t)h->entry;
         for (uint32_t layer = h->max_layer; layer >= 1; layer--) cur = host_greedy(h, q, qmag, cur, layer, evals);
         std::vector<Ent> found;
@@ -731,11 +973,48 @@ nmn_status upload_graph(nmn_hnsw* h) {
     return NMN_OK;
 }
 
+// quantized handle: rows [first, first + count) of the host's codes and records into the device arrays (caller waited for the searches)
+nmn_status upload_codes(nmn_hnsw* h, uint64_t first, uint64_t count) {
+    if (count == 0) return NMN_OK;
+    const uint32_t dim = h->dim, ld8 = h->ld8;
+    std::vector<uint8_t> stage((size_t)count * ld8, 0);
+    std::vector<float> rec((size_t)count * 4);
+    for (uint64_t i = 0; i < count; i++) {
+        const uint64_t r = first + i;
+        memcpy(stage.data() + (size_t)i * ld8, h->codes.data() + (size_t)r * dim, dim);
+        rec[4 * i + 0] = h->qscale[r];
+        rec[4 * i + 1] = h->qmin[r];
+        rec[4 * i + 2] = h->mags[r];
+        rec[4 * i + 3] = h->qxsq[r];
+    }
+    HN_TRY(hipMemcpy((uint8_t*)h->d_codes + (size_t)first * ld8, stage.data(), stage.size(), hipMemcpyHostToDevice));
+    HN_TRY(hipMemcpy((float*)h->d_rec + (size_t)first * 4, rec.data(), rec.size() * 4, hipMemcpyHostToDevice));
+    return NMN_OK;
+}
+
+// quantized handle: device arrays for `cap` rows; the `have` rows already inserted are sent again from the host's copy
+nmn_status alloc_codes(nmn_hnsw* h, uint64_t cap, uint64_t have) {
+    void *nc = nullptr, *nr = nullptr;
+    HN_TRY(hipMalloc(&nc, std::max<size_t>((size_t)cap * h->ld8, 256)));
+    hipError_t e = hipMalloc(&nr, std::max<size_t>((size_t)cap * 16, 256));
+    if (e != hipSuccess) {
+        (void)hipFree(nc);
+        return set_error_hip(e, "hipMalloc");
+    }
+    if (h->d_codes) (void)hipFree(h->d_codes);
+    if (h->d_rec) (void)hipFree(h->d_rec);
+    h->d_codes = nc;
+    h->d_rec = nr;
+    h->vec_cap = cap;
+    return upload_codes(h, 0, have);
+}
+
 nmn_status ensure_vectors(nmn_hnsw* h, uint64_t need) {
-    if (h->vectors && need <= h->vec_cap) return NMN_OK;
+    if ((h->vectors || h->d_codes) && need <= h->vec_cap) return NMN_OK;
     uint64_t cap = std::max<uint64_t>(h->vec_cap, 1024);
     while (cap < need) cap *= 2;
     if (h->cfg.max_nodes > 0) cap = std::min<uint64_t>(cap, std::max<uint64_t>(h->cfg.max_nodes, need));
+    if (h->storage == NMN_HNSW_STORAGE_QUANTIZED) return alloc_codes(h, cap, h->level.size());
     nmn_index_desc d{};
     d.dim = h->dim;
     d.capacity_rows = cap;
@@ -828,6 +1107,10 @@ nmn_status enqueue_search_locked(nmn_hnsw* h, nmn_hnsw::Scratch* sc, const float
     a.g.up = (const uint32_t*)h->d_up.p;
     a.g.upcnt = (const uint32_t*)h->d_upcnt.p;
     a.g.ld = h->vectors ? h->vectors->ld : 0;
+    a.g.codes = (const uint8_t*)h->d_codes;
+    a.g.rec = (const float4*)h->d_rec;
+    a.g.ld8 = h->ld8;
+    const bool q8 = h->storage == NMN_HNSW_STORAGE_QUANTIZED;
     a.g.dim = h->dim;
     a.g.m = h->cfg.m;
     a.g.m0 = h->cfg.m0;
@@ -858,14 +1141,20 @@ nmn_status enqueue_search_locked(nmn_hnsw* h, nmn_hnsw::Scratch* sc, const float
             a.rcap = res_need;
             a.ccap = ccap;
             const size_t lds = fixed + ((size_t)a.rcap + a.ccap) * sizeof(Ent);
-            hipLaunchKernelGGL(hnsw_search_kernel<false>, dim3(nb), dim3(64), lds, s, a);
+            if (q8)
+                hipLaunchKernelGGL((hnsw_search_kernel<false, true>), dim3(nb), dim3(64), lds, s, a);
+            else
+                hipLaunchKernelGGL((hnsw_search_kernel<false, false>), dim3(nb), dim3(64), lds, s, a);
             HN_TRY(hipGetLastError());
         } else {  // a results heap no wave can keep in LDS: every query goes to the spill launch
             HN_TRY(hipMemsetD32Async((hipDeviceptr_t)a.flags, 1, nb, s));
         }
         a.rcap = s_rcap;
         a.ccap = s_ccap;
-        hipLaunchKernelGGL(hnsw_search_kernel<true>, dim3(std::min(regions, nb)), dim3(64), fixed, s, a);
+        if (q8)
+            hipLaunchKernelGGL((hnsw_search_kernel<true, true>), dim3(std::min(regions, nb)), dim3(64), fixed, s, a);
+        else
+            hipLaunchKernelGGL((hnsw_search_kernel<true, false>), dim3(std::min(regions, nb)), dim3(64), fixed, s, a);
         HN_TRY(hipGetLastError());
     }
     return NMN_OK;
@@ -916,6 +1205,10 @@ nmn_status check_metric_call(nmn_hnsw* h, uint32_t top_k, const nmn_xmetric* m) 
     if (!h || !m) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
     if (!xmetric_valid(m)) return set_error(NMN_ERR_CONFIGURATION, "unknown extended distance metric");
     if (top_k == 0) return set_error(NMN_ERR_INVALID_TOP_K, "top_k == 0");
+    if (h->storage != NMN_HNSW_STORAGE_DENSE)
+        return set_error(NMN_ERR_CONFIGURATION,
+                         "HNSW: nmn_hnsw_search_metric re-ranks with the rows of nmn_hnsw_vectors(h), and a quantized handle keeps no f32 "
+                         "rows on the device (re-rank the candidates of nmn_hnsw_search against your own vectors)");
     return NMN_OK;
 }
 
@@ -958,19 +1251,40 @@ extern "C" void nmn_hnsw_config_high_speed(nmn_hnsw_config* c) {
     if (c) fill_cfg(c, 8, 100, 20);
 }
 
-extern "C" nmn_status nmn_hnsw_create(const nmn_hnsw_config* cfg, uint32_t dim, uint64_t capacity_hint, int32_t device, nmn_hnsw** out) {
-    if (!cfg || !out) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
-    *out = nullptr;
+namespace {
+nmn_status create_handle(const nmn_hnsw_config* cfg, int storage, uint32_t dim, uint64_t capacity_hint, int32_t device, nmn_hnsw** out) {
     if (dim == 0) return set_error(NMN_ERR_EMPTY_VECTOR, "dim == 0");
     if (dim > kMaxDim) return set_error(NMN_ERR_CONFIGURATION, "HNSW: dimension above 8192 (the query is kept in LDS)");
     nmn_status st = check_cfg(cfg);
     if (st != NMN_OK) return st;
     auto h = std::make_unique<nmn_hnsw>();
     h->cfg = *cfg;
+    h->cfg.storage = storage;
+    h->storage = storage;
     h->dim = dim;
     h->device = device;
     h->vec_cap = 0;
-    {
+    const uint64_t cap_rows = cfg->max_nodes > 0 ? std::min<uint64_t>(std::max<uint64_t>(capacity_hint, 1), cfg->max_nodes)
+                                                 : std::max<uint64_t>(capacity_hint, 1);
+    if (storage == NMN_HNSW_STORAGE_QUANTIZED) {
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+            (void)hipGetLastError();
+            return set_error(NMN_ERR_NO_DEVICE, "no HIP device");
+        }
+        int dev = device;
+        if (dev < 0) HN_TRY(hipGetDevice(&dev));
+        if (dev >= ndev) return set_error(NMN_ERR_NO_DEVICE, "device ordinal out of range");
+        HN_TRY(hipSetDevice(dev));
+        h->device = dev;
+        h->ld8 = (dim + 15u) & ~15u;
+        st = alloc_codes(h.get(), cap_rows, 0);
+        if (st != NMN_OK) {
+            if (h->d_codes) (void)hipFree(h->d_codes);
+            if (h->d_rec) (void)hipFree(h->d_rec);
+            return st;
+        }
+    } else {
         // the flat index fixes the device (and fails with NMN_ERR_NO_DEVICE where there is none)
         const uint64_t cap0 = std::max<uint64_t>(capacity_hint, 1);
         h->vec_cap = 0;
@@ -983,10 +1297,37 @@ extern "C" nmn_status nmn_hnsw_create(const nmn_hnsw_config* cfg, uint32_t dim, 
         h->vec_cap = d.capacity_rows;
         h->device = h->vectors->device;
     }
-    HN_TRY(hipSetDevice(h->device));
-    HN_TRY(hipStreamCreateWithFlags(&h->host_stream, hipStreamNonBlocking));
+    hipError_t he = hipSetDevice(h->device);
+    if (he == hipSuccess) he = hipStreamCreateWithFlags(&h->host_stream, hipStreamNonBlocking);
+    if (he != hipSuccess) {
+        if (h->vectors) nmn_index_destroy(h->vectors);
+        if (h->d_codes) (void)hipFree(h->d_codes);
+        if (h->d_rec) (void)hipFree(h->d_rec);
+        return set_error_hip(he, "nmn_hnsw_create");
+    }
     *out = h.release();
     return NMN_OK;
+}
+}  // namespace
+
+extern "C" nmn_status nmn_hnsw_create(const nmn_hnsw_config* cfg, uint32_t dim, uint64_t capacity_hint, int32_t device, nmn_hnsw** out) {
+    if (!cfg || !out) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    *out = nullptr;
+    return create_handle(cfg, NMN_HNSW_STORAGE_DENSE, dim, capacity_hint, device, out);
+}
+
+// HNSWBuildOptions' storage (vector_engine/src/lib.rs:853-858) applied to the index: cfg->storage is not read
+extern "C" nmn_status nmn_hnsw_create_with_storage(const nmn_hnsw_config* cfg, int32_t storage, uint32_t dim, uint64_t capacity_hint,
+                                                   int32_t device, nmn_hnsw** out) {
+    if (!cfg || !out) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    *out = nullptr;
+    if (storage == NMN_HNSW_STORAGE_AUTO)
+        return set_error(NMN_ERR_CONFIGURATION, "HNSW: HNSWStorageStrategy::Auto (sparse storage) is not served; Dense and Quantized are");
+    if (storage != NMN_HNSW_STORAGE_DENSE && storage != NMN_HNSW_STORAGE_QUANTIZED)
+        return set_error(NMN_ERR_CONFIGURATION, "HNSW: unknown storage strategy");
+    nmn_hnsw_config c = *cfg;
+    c.storage = NMN_HNSW_STORAGE_DENSE;  // (the old field plays no part here)
+    return create_handle(&c, storage, dim, capacity_hint, device, out);
 }
 
 extern "C" nmn_status nmn_hnsw_destroy(nmn_hnsw* h) {
@@ -1012,6 +1353,8 @@ extern "C" nmn_status nmn_hnsw_destroy(nmn_hnsw* h) {
     for (DevBuf* b : {&h->d_l0, &h->d_l0cnt, &h->d_upidx, &h->d_up, &h->d_upcnt, &h->hq, &h->hids, &h->hsc, &h->hcnt}) drop(*b);
     if (h->host_stream) (void)hipStreamDestroy(h->host_stream);
     if (h->vectors) nmn_index_destroy(h->vectors);
+    if (h->d_codes) (void)hipFree(h->d_codes);
+    if (h->d_rec) (void)hipFree(h->d_rec);
     delete h;
     return NMN_OK;
 }
@@ -1035,17 +1378,47 @@ extern "C" nmn_status nmn_hnsw_insert(nmn_hnsw* h, const float* rows_host, uint6
         std::lock_guard<std::mutex> hl(h->host_mu);
         HN_TRY(hipStreamSynchronize(h->host_stream));
     }
-    h->rows.insert(h->rows.end(), rows_host, rows_host + n * h->dim);
-    st = ensure_vectors(h, have + n);
-    if (st == NMN_OK) st = nmn_index_upload(h->vectors, rows_host, have, n);
+    const bool q8 = h->storage == NMN_HNSW_STORAGE_QUANTIZED;
+    const uint32_t dim = h->dim;
+    if (q8) {  // insert_quantized, hnsw.rs:1711-1714: from_dense; what the host keeps as the row is dequantize()
+        h->rows.resize((have + n) * dim);
+        h->codes.resize((have + n) * dim);
+        h->qscale.resize(have + n);
+        h->qmin.resize(have + n);
+        h->qxsq.resize(have + n);
+        h->mags.resize(have + n);
+        for (uint64_t r = have; r < have + n; r++) {
+            uint8_t* code = h->codes.data() + r * dim;
+            h_quantize(rows_host + (r - have) * dim, dim, code, &h->qscale[r], &h->qmin[r]);
+            float* v = h->rows.data() + r * dim;
+            h_dequantize(code, dim, h->qscale[r], h->qmin[r], v);
+            h->mags[r] = sqrtf(h_dot8(v, v, dim));  // magnitude_immutable, hnsw.rs:401-407
+            h->qxsq[r] = h_q8_sqmag(code, h->qscale[r], h->qmin[r], dim);
+        }
+        st = ensure_vectors(h, have + n);
+        if (st == NMN_OK && have + n <= h->vec_cap) st = upload_codes(h, have, n);
+    } else {
+        h->rows.insert(h->rows.end(), rows_host, rows_host + n * dim);
+        st = ensure_vectors(h, have + n);
+        if (st == NMN_OK) st = nmn_index_upload(h->vectors, rows_host, have, n);
+    }
     if (st != NMN_OK) {
-        h->rows.resize(have * h->dim);
+        h->rows.resize(have * dim);
+        if (q8) {
+            h->codes.resize(have * dim);
+            h->qscale.resize(have);
+            h->qmin.resize(have);
+            h->qxsq.resize(have);
+            h->mags.resize(have);
+        }
         return st;
     }
     static thread_local HostVisited vis;
     for (uint64_t i = 0; i < n; i++) {
-        const float* v = h->rows.data() + (have + i) * h->dim;
-        h->mags.push_back(sqrtf(h_dot8(v, v, h->dim)));  // simd::magnitude, hnsw.rs:198-229
+        if (!q8) {
+            const float* v = h->rows.data() + (have + i) * dim;
+            h->mags.push_back(sqrtf(h_dot8(v, v, dim)));  // simd::magnitude, hnsw.rs:198-229
+        }
         host_insert_node(h, (uint32_t)(have + i), vis);
         if (ids_out) ids_out[i] = have + i;
     }
@@ -1057,6 +1430,44 @@ extern "C" uint32_t nmn_hnsw_dim(const nmn_hnsw* h) { return h ? h->dim : 0; }
 extern "C" uint64_t nmn_hnsw_entry_point(const nmn_hnsw* h) { return h ? h->entry : ~0ull; }
 extern "C" uint32_t nmn_hnsw_max_layer(const nmn_hnsw* h) { return h ? h->max_layer : 0; }
 extern "C" nmn_index* nmn_hnsw_vectors(nmn_hnsw* h) { return h ? h->vectors : nullptr; }
+extern "C" int32_t nmn_hnsw_storage(const nmn_hnsw* h) { return h ? h->storage : -1; }
+
+extern "C" nmn_status nmn_hnsw_quantized_row(nmn_hnsw* h, uint64_t node, uint8_t* codes_out, float* scale, float* min_val) {
+    if (!h) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    std::shared_lock<std::shared_mutex> g(h->rw);
+    if (h->storage != NMN_HNSW_STORAGE_QUANTIZED) return set_error(NMN_ERR_CONFIGURATION, "HNSW: the handle's storage is not Quantized");
+    if (node >= h->level.size()) return set_error(NMN_ERR_NOT_FOUND, "HNSW: no such node");
+    if (codes_out) memcpy(codes_out, h->codes.data() + node * h->dim, h->dim);
+    if (scale) *scale = h->qscale[node];
+    if (min_val) *min_val = h->qmin[node];
+    return NMN_OK;
+}
+
+// HNSWIndex::get_vector: the row as stored (Dense), dequantize() (Quantized)
+extern "C" nmn_status nmn_hnsw_get_vector(nmn_hnsw* h, uint64_t node, float* out) {
+    if (!h || !out) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    std::shared_lock<std::shared_mutex> g(h->rw);
+    if (node >= h->level.size()) return set_error(NMN_ERR_NOT_FOUND, "HNSW: no such node");
+    memcpy(out, h->rows.data() + node * h->dim, (size_t)h->dim * 4);
+    return NMN_OK;
+}
+
+// HNSWIndex::memory_stats, hnsw.rs:2733-2768: embedding.memory_bytes() is 4 dim (Dense, 1227) or 16 + dim (Quantized, 381-383)
+extern "C" nmn_status nmn_hnsw_memory_stats(nmn_hnsw* h, nmn_hnsw_memstats* out) {
+    if (!h || !out) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    std::shared_lock<std::shared_mutex> g(h->rw);
+    memset(out, 0, sizeof *out);
+    const uint64_t n = h->level.size();
+    out->total_nodes = n;
+    if (h->storage == NMN_HNSW_STORAGE_QUANTIZED) {
+        out->quantized_count = n;
+        out->embedding_bytes = n * (16ull + h->dim);
+    } else {
+        out->dense_count = n;
+        out->embedding_bytes = n * 4ull * h->dim;
+    }
+    return NMN_OK;
+}
 
 extern "C" nmn_status nmn_hnsw_levels(nmn_hnsw* h, uint32_t* out, uint64_t cap) {
     if (!h || !out) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
@@ -1097,6 +1508,7 @@ extern "C" uint64_t nmn_hnsw_hbm_bytes(nmn_hnsw* h) {
     uint64_t t = h->d_l0.cap + h->d_l0cnt.cap + h->d_upidx.cap + h->d_up.cap + h->d_upcnt.cap;
     uint64_t a = 0, b = 0, c = 0;
     if (h->vectors && nmn_index_hbm_bytes(h->vectors, &a, &b, &c) == NMN_OK) t += a + b + c;
+    if (h->d_codes) t += std::max<uint64_t>(h->vec_cap * h->ld8, 256) + std::max<uint64_t>(h->vec_cap * 16, 256);
     return t;
 }
 
@@ -1170,7 +1582,7 @@ extern "C" nmn_status nmn_hnsw_search(nmn_hnsw* h, const float* queries, uint32_
     }
     if (stats) {
         stats->rows_scanned = evals;
-        stats->bytes_scanned = evals * h->dim * 4;
+        stats->bytes_scanned = h->storage == NMN_HNSW_STORAGE_QUANTIZED ? evals * (h->dim + 16ull) : evals * h->dim * 4;
         stats->fallback_queries = spilled;
         stats->sweep_kind = h->level.empty() ? NMN_SWEEP_NONE : NMN_SWEEP_GRAPH;
         stats->sweep_launches = host_search_forced() ? 0 : 2;

@@ -97,6 +97,11 @@ ENGINE_SIGNATURES = {
     "nmn_engine_ivf_cluster_sizes": (C.c_int32, [vp, vp]),
     "nmn_engine_search_with_ivf": (C.c_int32, [vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(vp)]),
     "nmn_engine_build_hnsw_index": (C.c_int32, [vp, vp, C.POINTER(vp)]),
+    "nmn_engine_build_hnsw_index_with_options": (C.c_int32, [vp, vp, C.POINTER(vp)]),
+    "nmn_hnsw_build_options_default": (None, [vp]),
+    "nmn_hnsw_build_options_memory_optimized": (None, [vp]),
+    "nmn_hnsw_build_options_high_recall": (None, [vp]),
+    "nmn_hnsw_build_options_sparse_optimized": (None, [vp]),
     "nmn_engine_hnsw_free": (None, [vp]),
     "nmn_engine_hnsw_len": (C.c_uint64, [vp]),
     "nmn_engine_hnsw_key": (C.c_char_p, [vp, C.c_uint64]),
@@ -762,6 +767,19 @@ class VectorEngine:
         h = vp()
         _check(_lib().nmn_engine_build_hnsw_index(self._h, C.byref(cc), C.byref(h)))
         index = HNSWIndex(h, cfg)
+        return index, index.keys
+
+    def build_hnsw_index_with_options(self, options=None):
+        """build_hnsw_index_with_options (lib.rs:2423-2470) -> (HNSWIndex, key_mapping); options: neumann_amd.HNSWBuildOptions
+        ("dense" or "quantized" storage; "auto" is refused)."""
+        from .hnsw import HNSWBuildOptions, _storage_code
+        opt = options or HNSWBuildOptions()
+        cc = opt.hnsw_config._c()
+        cc.storage = _capi.HNSW_STORAGE_DENSE
+        co = _capi.HnswBuildOptions(storage=_storage_code(opt.storage), reserved=0, hnsw_config=cc)
+        h = vp()
+        _check(_lib().nmn_engine_build_hnsw_index_with_options(self._h, C.byref(co), C.byref(h)))
+        index = HNSWIndex(h, opt.hnsw_config)
         return index, index.keys
 
     def build_hnsw_index_default(self):

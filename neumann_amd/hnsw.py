@@ -1,6 +1,6 @@
 """HNSW graph index searched on the GPU — host wrapper of `nmn_hnsw_*` (include/neumann_gpu.h).
 
-Mirrors `tensor_store::HNSWIndex` with dense storage (tensor_store/src/hnsw.rs:1554-2335): `insert` builds the graph on the
+Mirrors `tensor_store::HNSWIndex` with dense or 8-bit quantized storage (tensor_store/src/hnsw.rs:1554-2335): `insert` builds the graph on the
 host in the reference's order (level generator, search_layer with ef_construction, stable pruning), `search` /
 `search_device` run `search_with_ef` as one HIP kernel launch per chunk of queries, one query per wave.  Answers are the
 reference's bit for bit, ties included (docs/hnsw.md)."""
@@ -26,7 +26,9 @@ class HNSWConfig:
         self.sparsity_threshold = float(sparsity_threshold)
         self.max_nodes = int(max_nodes)
         self.distance_metric = DistanceMetric(int(distance_metric))
-        self.storage = storage  # HNSWStorageStrategy: only "dense" is served ("auto" / "quantized" are refused)
+        # the older home of HNSWStorageStrategy: GpuHnsw(config) serves "dense" here and refuses the others.  The strategy's home
+        # is HNSWBuildOptions.storage / GpuHnsw(..., storage=...), as in the reference.
+        self.storage = storage
 
     @classmethod
     def default(cls):
@@ -60,15 +62,70 @@ class HNSWConfig:
                    sparsity_threshold=c.sparsity_threshold, max_nodes=c.max_nodes, distance_metric=c.distance_metric)
 
 
+_STORAGE = {"dense": _capi.HNSW_STORAGE_DENSE, "auto": _capi.HNSW_STORAGE_AUTO, "quantized": _capi.HNSW_STORAGE_QUANTIZED}
+
+
+def _storage_code(storage):
+    try:
+        return _STORAGE[storage]
+    except KeyError:
+        raise _capi.NeumannGpuError(_capi.ERR_CONFIGURATION, f"unknown HNSW storage strategy {storage!r}")
+
+
+class HNSWBuildOptions:
+    """HNSWBuildOptions (vector_engine/src/lib.rs:848-932): a storage strategy ("dense", "auto", "quantized") and an HNSWConfig."""
+
+    def __init__(self, storage="dense", hnsw_config=None):
+        self.storage = storage
+        self.hnsw_config = hnsw_config or HNSWConfig()
+
+    @classmethod
+    def default(cls):  # lib.rs:860-867
+        return cls("dense", HNSWConfig.default())
+
+    new = default
+
+    @classmethod
+    def memory_optimized(cls):  # lib.rs:880-885
+        return cls("quantized", HNSWConfig.high_speed())
+
+    @classmethod
+    def high_recall(cls):  # lib.rs:891-896
+        return cls("dense", HNSWConfig.high_recall())
+
+    @classmethod
+    def sparse_optimized(cls):  # lib.rs:902-907
+        return cls("auto", HNSWConfig.default())
+
+    def with_storage(self, storage):  # lib.rs:911-914
+        self.storage = storage
+        return self
+
+    def with_hnsw_config(self, config):  # lib.rs:918-921
+        self.hnsw_config = config
+        return self
+
+    def with_sparsity_threshold(self, threshold):  # lib.rs:928-931
+        self.hnsw_config.sparsity_threshold = float(threshold)
+        return self
+
+
 class GpuHnsw:
-    def __init__(self, dim, config=None, capacity_hint=0, device=-1):
+    def __init__(self, dim, config=None, capacity_hint=0, device=-1, storage=None):
+        """storage None: nmn_hnsw_create (config.storage, dense only).  storage "dense" / "quantized": the strategy of
+        HNSWBuildOptions through nmn_hnsw_create_with_storage (config.storage is not read; "auto" is refused)."""
         self._lib = _capi.load()
         self._h = None
         self.config = config or HNSWConfig()
         self.dim = int(dim)
         cfg = self.config._c()
         h = C.c_void_p()
-        _capi.check(self._lib.nmn_hnsw_create(C.byref(cfg), self.dim, int(capacity_hint), int(device), C.byref(h)))
+        if storage is None:
+            _capi.check(self._lib.nmn_hnsw_create(C.byref(cfg), self.dim, int(capacity_hint), int(device), C.byref(h)))
+        else:
+            cfg.storage = _capi.HNSW_STORAGE_DENSE
+            _capi.check(self._lib.nmn_hnsw_create_with_storage(C.byref(cfg), _storage_code(storage), self.dim, int(capacity_hint),
+                                                               int(device), C.byref(h)))
         self._h = h
 
     def close(self):
@@ -130,8 +187,34 @@ class GpuHnsw:
         return out[:cnt.value].copy()
 
     def vectors(self):
-        """the flat index holding the rows (node id == row), valid until the next insert"""
-        return GpuFlatIndex._view(self._lib.nmn_hnsw_vectors(self._h), self)
+        """the flat index holding the rows (node id == row), valid until the next insert; None on a quantized handle"""
+        v = self._lib.nmn_hnsw_vectors(self._h)
+        return GpuFlatIndex._view(v, self) if v else None
+
+    @property
+    def storage(self):
+        """"dense" or "quantized": the handle's one storage strategy"""
+        code = int(self._lib.nmn_hnsw_storage(self._h))
+        return {v: k for k, v in _STORAGE.items()}[code]
+
+    def quantized_row(self, node):
+        """the node's ScalarQuantizedVector -> (codes u8 [dim], scale f32, min_val f32)"""
+        codes = np.empty(self.dim, dtype=np.uint8)
+        scale, mn = C.c_float(), C.c_float()
+        _capi.check(self._lib.nmn_hnsw_quantized_row(self._h, int(node), C.c_void_p(codes.ctypes.data), C.byref(scale), C.byref(mn)))
+        return codes, np.float32(scale.value), np.float32(mn.value)
+
+    def get_vector(self, node):
+        """HNSWIndex::get_vector: the row as inserted (dense) or dequantize() (quantized)"""
+        out = np.empty(self.dim, dtype=np.float32)
+        _capi.check(self._lib.nmn_hnsw_get_vector(self._h, int(node), C.c_void_p(out.ctypes.data)))
+        return out
+
+    def memory_stats(self):
+        """HNSWIndex::memory_stats (hnsw.rs:2733-2768) as a dict"""
+        st = _capi.HnswMemStats()
+        _capi.check(self._lib.nmn_hnsw_memory_stats(self._h, C.byref(st)))
+        return {n: int(getattr(st, n)) for n, _ in st._fields_}
 
     def set_heap_capacity(self, results=0, candidates=0):
         """entries of the two heaps a wave keeps in LDS (0 = default); what outgrows them goes to the spill launch"""

@@ -26,7 +26,14 @@ With a NAME instead of a number, --metric is an ExtendedDistanceMetric and the t
 nmn_hnsw_search_metric_device at top_k = --k beside nmn_hnsw_search_device at k = c = max(2 top_k, 10) — the walk alone, the same
 candidates — at the preset's ef_search (50 by default), 1 / 64 / 1024 queries per call, HIP events around each call on one stream, the two alternating call by
 call: medians of --calls (a fifth of it at 1024 queries), spread over --repeats repetitions.  The index metric stays cosine.
---launch-calls N then makes N search_metric_device calls and nothing else."""
+--launch-calls N then makes N search_metric_device calls and nothing else.
+
+  python tools/hnsw_bench.py --rows 200000 --dim 768 --storage quantized
+builds the corpus twice — a quantized handle (HNSWStorageStrategy::Quantized, docs/hnsw.md §9) and a dense one — and times the
+quantized walk beside the dense walk OF THE SAME RUN, the two alternating call by call: nmn_hnsw_search_device under HIP events at
+1 / 64 / 1024 queries per call and a lone host-buffer nmn_hnsw_search call, ef 50 and 200, medians of --calls, spread over
+--repeats.  It prints both handles' hbm_bytes, build times, evaluations per query and recall@10 of each against the exhaustive
+search over the f32 rows, and checks that the quantized handle's device, host-buffer and host-walk answers are the same bits."""
 import argparse
 import json
 import os
@@ -81,6 +88,75 @@ def time_rerank(g, xmetric, Q, qd, k, s, args):
     return r
 
 
+def time_storage(gq, gd, Q, qd, k, s, args, metric):
+    """the quantized walk beside the dense walk of the same corpus, alternating call by call"""
+    import torch
+    out = {}
+    flat = gd.vectors()
+    ex_rows, _, _ = flat.search(Q, k, metric)
+    for ef in (50, 200):
+        r = {}
+        bufs = {}
+        for nq in (1, 64, 1024):
+            bufs[nq] = tuple((torch.empty((nq, k), dtype=torch.int64, device="cuda"), torch.empty((nq, k), dtype=torch.float32, device="cuda"),
+                              torch.empty((nq,), dtype=torch.int32, device="cuda")) for _ in range(2))
+            gq.search_device(qd[:nq], k, ef, out=bufs[nq][0], stream=s)  # warm every shape
+            gd.search_device(qd[:nq], k, ef, out=bufs[nq][1], stream=s)
+            gq.search(Q[:nq], k, ef)
+            gd.search(Q[:nq], k, ef)
+        s.synchronize()
+        for name, g, b in (("q8", gq, 0), ("dense", gd, 1)):
+            ids, sc, cnt, st = g.search(Q, k, ef, with_stats=True)
+            r[f"{name}_evals_per_query"] = round(st.rows_scanned / len(Q), 1)
+            r[f"{name}_spilled_queries"] = int(st.fallback_queries)
+            r[f"{name}_recall_at_{k}"] = round(float(np.mean([len(set(a.tolist()) & set(e.tolist())) / k for a, e in zip(ids, ex_rows)])), 4)
+            same = np.array_equal(bufs[1024][b][0].cpu().numpy().view(np.uint64), ids) and \
+                np.array_equal(bufs[1024][b][1].cpu().numpy().view(np.uint32), sc.view(np.uint32))
+            if name == "q8":
+                os.environ["NMN_HNSW_HOST_SEARCH"] = "1"
+                try:
+                    hids, hsc, _ = g.search(Q[:64], k, ef)
+                finally:
+                    del os.environ["NMN_HNSW_HOST_SEARCH"]
+                same = same and np.array_equal(hids, ids[:64]) and np.array_equal(hsc.view(np.uint32), sc[:64].view(np.uint32))
+            r[f"{name}_paths_agree"] = bool(same)
+        reps = {}
+        for _ in range(args.repeats):
+            for nq, calls in ((1, args.calls), (64, args.calls), (1024, max(args.calls // 5, 5))):
+                ev = {"q8": [], "dense": []}
+                for _ in range(calls):
+                    e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+                    e[0].record(s)
+                    gq.search_device(qd[:nq], k, ef, out=bufs[nq][0], stream=s)
+                    e[1].record(s)
+                    e[2].record(s)
+                    gd.search_device(qd[:nq], k, ef, out=bufs[nq][1], stream=s)
+                    e[3].record(s)
+                    ev["q8"].append((e[0], e[1]))
+                    ev["dense"].append((e[2], e[3]))
+                s.synchronize()
+                for name in ev:
+                    reps.setdefault(f"{name}_dev_ms_per_query_nq{nq}", []).append(float(np.median([a.elapsed_time(b) for a, b in ev[name]])) / nq)
+            tq, td = [], []
+            for _ in range(args.calls):
+                t0 = time.perf_counter()
+                gq.search(Q[:1], k, ef)
+                t1 = time.perf_counter()
+                gd.search(Q[:1], k, ef)
+                t2 = time.perf_counter()
+                tq.append(t1 - t0)
+                td.append(t2 - t1)
+            reps.setdefault("q8_gpu_ms_nq1", []).append(float(np.median(tq)) * 1e3)
+            reps.setdefault("dense_gpu_ms_nq1", []).append(float(np.median(td)) * 1e3)
+        for key, v in reps.items():
+            r[key] = round(float(np.median(v)), 5)
+            r[key + "_spread"] = round(float((max(v) - min(v)) / np.median(v)), 3)
+        for nq in (1, 64, 1024):
+            r[f"q8_over_dense_nq{nq}"] = round(r[f"q8_dev_ms_per_query_nq{nq}"] / r[f"dense_dev_ms_per_query_nq{nq}"], 3)
+        out[f"ef{ef}"] = r
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1_000_000)
@@ -92,6 +168,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--launch-calls", type=int, default=None)
+    ap.add_argument("--storage", default="dense", choices=["dense", "quantized"],
+                    help="quantized: time the quantized walk beside the dense walk of the same corpus (docs/hnsw.md §9)")
     args = ap.parse_args()
     import torch
     from neumann_amd import DistanceMetric, ExtendedDistanceMetric, GpuHnsw, HNSWConfig, synth_rows
@@ -107,6 +185,21 @@ def main():
     metric = DistanceMetric(args.metric)
     Q = synth_rows(0x2F8, 0, 1024, d)
     out = {"rows": n, "dim": d, "preset": args.preset, "metric": args.metric, "k": k}
+    if args.storage == "quantized":
+        out["storage"] = "quantized"
+        with GpuHnsw(d, cfg, capacity_hint=n, storage="quantized") as gq, GpuHnsw(d, cfg, capacity_hint=n, storage="dense") as gd:
+            step = 50_000
+            for name, g in (("q8", gq), ("dense", gd)):
+                t0 = time.perf_counter()
+                for r0 in range(0, n, step):
+                    g.insert(synth_rows(0x2F6, r0, min(step, n - r0), d))
+                    print(f"{name}: built {min(r0 + step, n)} nodes in {time.perf_counter() - t0:.1f} s", file=sys.stderr, flush=True)
+                out[f"{name}_build_s"] = round(time.perf_counter() - t0, 1)
+                out[f"{name}_hbm_bytes"], out[f"{name}_max_layer"] = g.hbm_bytes, g.max_layer
+            s = torch.cuda.Stream()
+            out.update(time_storage(gq, gd, Q, torch.from_numpy(Q).cuda(), k, s, args, metric))
+        print(json.dumps(out), flush=True)
+        return
     with GpuHnsw(d, cfg, capacity_hint=n) as g:
         t0 = time.perf_counter()
         step = 50_000
