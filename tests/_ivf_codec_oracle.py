@@ -78,6 +78,24 @@ class PQCodebook:
             codes[m] = best_idx & 0xFF  # `k as u8`
         return codes
 
+    def encode_rows(self, R):
+        """encode for every row of R [n][original_dim] -> u8 [n][M]: vectorised over rows and codewords, each distance a
+        sequential f32 sum over the subspace's dimensions as in sq_dist_rows"""
+        R = np.asarray(R, dtype=F)
+        codes = np.zeros((R.shape[0], self.num_subspaces), dtype=np.uint8)
+        if self.subspace_dim == 0 or R.shape[1] != self.original_dim or self.num_centroids == 0:
+            return codes
+        sub = self.subspace_dim
+        for m in range(self.num_subspaces):
+            acc = np.full((R.shape[0], self.num_centroids), -0.0, dtype=F)
+            for d in range(sub):
+                t = self.centroids[m, :, d][None, :] - R[:, m * sub + d][:, None]  # (codeword - v), as sq_dist_rows(cb, v)
+                acc = acc + t * t
+            best = np.argmin(acc, axis=1)  # NaN-free: the first minimum = the first k with `dist < best_dist` ...
+            won = acc[np.arange(R.shape[0]), best] < F32_MAX  # ... unless no distance is below f32::MAX: index 0 stays
+            codes[:, m] = (np.where(won, best, 0) & 0xFF).astype(np.uint8)
+        return codes
+
     def decode(self, codes):
         if self.subspace_dim == 0:
             return np.zeros(0, dtype=F)
@@ -153,6 +171,39 @@ def from_dense(v, method):
     return words
 
 
+def thresholds_rows(V, method):
+    """threshold for every row of V [n][dim] (dim >= 1): vectorised over rows, the Mean's sum sequential over the columns"""
+    V = np.asarray(V, dtype=F)
+    n, dim = V.shape
+    if method == "sign":
+        return np.zeros(n, dtype=F)
+    if method == "mean":
+        s = np.full(n, -0.0, dtype=F)
+        for j in range(dim):
+            s = s + V[:, j]
+        return (s / F(dim)).astype(F)
+    if method == "median":
+        srt = np.sort(V, axis=1)  # (NaN-free rows; -0.0 and +0.0 compare equal, and `v > t` is the same for either)
+        mid = dim // 2
+        if dim % 2 == 0:
+            return ((srt[:, mid - 1].astype(np.float64) + srt[:, mid].astype(np.float64)) / 2.0).astype(F)
+        return srt[:, mid].copy()
+    raise ValueError(method)
+
+
+def from_dense_rows(V, method):
+    """from_dense for every row of V [n][dim] -> u64 [n][ceil(dim / 64)]"""
+    V = np.asarray(V, dtype=F)
+    n, dim = V.shape
+    W = (dim + 63) // 64
+    if dim == 0:
+        return np.zeros((n, 0), dtype=np.uint64)
+    bits = V > thresholds_rows(V, method)[:, None]
+    packed = np.zeros((n, W * 8), dtype=np.uint8)
+    packed[:, :(dim + 7) // 8] = np.packbits(bits, axis=1, bitorder="little")
+    return np.ascontiguousarray(packed).view("<u8").astype(np.uint64)
+
+
 def hamming(a, b):
     return int(sum(bin(int(x) ^ int(y)).count("1") for x, y in zip(a, b)))
 
@@ -161,6 +212,25 @@ def normalized_distance(a, b, dim):
     if dim == 0:
         return F(0.0)
     return F(F(hamming(a, b)) / F(dim))
+
+
+def normalized_distances(qwords, words, dim):
+    """normalized_distance(qwords, row, dim) for every row of words [n][W]"""
+    words = np.asarray(words, dtype=np.uint64)
+    if dim == 0:
+        return np.zeros(words.shape[0], dtype=F)
+    x = np.ascontiguousarray(words ^ np.asarray(qwords, dtype=np.uint64)[None, :])
+    h = np.unpackbits(x.view(np.uint8), axis=1).sum(axis=1, dtype=np.int64)
+    return (h.astype(F) / F(dim)).astype(F)  # hamming <= dim < 2^24: `as f32` is exact
+
+
+def assign_rows(V, centroids):
+    """nearest_centroid(v, centroids) for every row of V (NaN-free rows: np.argmin is the first minimum)"""
+    V = np.asarray(V, dtype=F)
+    D = np.stack([sq_dist_rows(V, c) for c in np.asarray(centroids, dtype=F)], axis=1)  # (v - c)^2 = (c - v)^2 bit for bit
+    if np.isnan(D).any():
+        return np.array([nearest_centroid(v, centroids) for v in V], dtype=np.int64)
+    return np.argmin(D, axis=1)
 
 
 # ---- IVFIndex with PQ / Binary storage (ivf.rs) ------------------------------------------------------------------
@@ -210,6 +280,21 @@ class IVFCoded:
         self.lists[c].append(vid)
         return vid
 
+    def add_rows(self, V):
+        """add(v) for every row of V through the batch helpers: codes, assign and lists end as repeated add leaves them.
+        Returns the clusters chosen."""
+        V = np.asarray(V, dtype=F)
+        a = assign_rows(V, self.centroids)
+        if self.storage == "pq":
+            new = self.codebook.encode_rows((V - self.centroids[a]).astype(F))
+        else:
+            new = from_dense_rows(V, self.threshold)
+        for c, row in zip(a.tolist(), new):
+            self.lists[c].append(len(self.codes))
+            self.codes.append(row.copy())
+            self.assign.append(c)
+        return a
+
     def cluster_sizes(self):
         return [len(lst) for lst in self.lists]
 
@@ -230,7 +315,7 @@ class IVFCoded:
                 table = self.codebook.compute_adc_table((q - self.centroids[c]).astype(F))
                 d = adc_distances(table, np.stack([self.codes[i] for i in ids]))
             else:
-                d = np.array([normalized_distance(qbits, self.codes[i], len(q)) for i in ids], dtype=F)
+                d = normalized_distances(qbits, np.stack([self.codes[i] for i in ids]), len(q))
             cand_ids.extend(ids)
             cand_d.extend(d.tolist())
         order2 = sorted(range(len(cand_d)), key=lambda i: cand_d[i])  # stable: probe order, then list order
