@@ -197,6 +197,59 @@ __global__ __launch_bounds__(256) void ivf_gather_kernel(const float* __restrict
     }
 }
 
+// A grow-only buffer of search scratch: device memory, or (pinned) host memory the device copies from and to.
+struct Grow {
+    void* p = nullptr;
+    size_t cap = 0;
+    bool pinned = false;
+    // At least `bytes` (64 at the least); a buffer too small is replaced, its content lost.  `wait`: work enqueued on `s` may still
+    // use the old buffer, so `s` is synchronised first — and `wait` cleared, so a run of reservations waits once, and only when
+    // something grows.  false: the caller has waited already.
+    hipError_t reserve(size_t bytes, hipStream_t s, bool& wait) {
+        bytes = std::max<size_t>(bytes, 64);
+        if (cap >= bytes) return hipSuccess;
+        if (wait) {
+            hipError_t e = hipStreamSynchronize(s);
+            if (e != hipSuccess) return e;
+            wait = false;
+        }
+        release();
+        hipError_t e = pinned ? hipHostMalloc(&p, bytes, hipHostMallocDefault) : hipMalloc(&p, bytes);
+        if (e == hipSuccess) cap = bytes;
+        return e;
+    }
+    void release() {
+        if (p) (void)(pinned ? hipHostFree(p) : hipFree(p));
+        p = nullptr;
+        cap = 0;
+    }
+};
+template <class T>
+T* gp(const Grow& g) {
+    return static_cast<T*>(g.p);
+}
+
+// Scratch of the centroid ranking (rank_centroids) of a chunk of queries.  Three holders: a probe slot (nmn_ivf_search of a
+// Flat index), the coded search's scratch, and the per-stream scratch of nmn_ivf_search_device.
+struct RankScratch {
+    Grow qraw;          // the chunk's queries as the host passed them (dim floats each)
+    Grow qpad;          // padded to the centroids' row stride (launch_qprep; not written where the raw queries serve)
+    Grow qinfo;         // all zero while the queries are raw: zeroed whenever it is (re)allocated, written by launch_qprep only
+    Grow qstate;
+    Grow cscores;       // exact -d^2 of every query against every centroid (tile-major)
+    Grow ckeys;         // sort buffer and scores of the large-k sort (more than kRankMax centroids only)
+    Grow probe_rows;    // [query][n_clusters] clusters in probe order
+    Grow probe_scores;
+    Grow probe_rank;    // [query][n_clusters] probe rank or kNoRank
+    Grow probe_count;
+    template <class F>
+    void for_each(F&& fn) {
+        for (Grow* g : {&qraw, &qpad, &qinfo, &qstate, &cscores, &ckeys, &probe_rows, &probe_scores, &probe_rank, &probe_count}) fn(*g);
+    }
+    // sized for chunks of `nb` queries; stage: the queries come from the host and pass through qraw
+    hipError_t reserve(const nmn_ivf* ivf, uint32_t nb, bool stage, hipStream_t s, bool& wait);
+};
+
 }  // namespace
 
 struct nmn_ivf {
@@ -222,17 +275,7 @@ struct nmn_ivf {
     hipStream_t stream = nullptr;
     uint32_t* cscores = nullptr;         // exact -d^2 of a chunk of queries vs every centroid (tile-major)
     size_t cscores_cap = 0;
-    uint64_t* ckeys = nullptr;           // sort buffer of the centroid ranking
-    uint64_t* probe_rows = nullptr;      // [n_clusters] clusters in probe order
-    float* probe_scores = nullptr;
-    uint32_t* probe_count = nullptr;
-    uint32_t* probe_rank = nullptr;      // [n_clusters] probe rank or kNoRank
-    uint64_t* mask = nullptr;            // [ceil(cap/64)]
-    float* qraw = nullptr;               // one query, dim floats
-    float* qpad = nullptr;               // padded to ld
-    QInfo* qinfo = nullptr;              // [kAssignChunk] (qmag is unused by the L2 metrics)
-    QState* qstate = nullptr;
-    uint32_t* assign_tmp = nullptr;      // [kAssignChunk]
+    QInfo* qinfo = nullptr;              // [kAssignChunk] zeros (the assignment sweep's rows are padded queries as they are)
     uint32_t assign_chunk = kAssignChunk;
     // Searches hold `rw` shared (add / build / the accessors exclusive) and take a PROBE SLOT each: stream and scratch of
     // one centroid ranking + selection bitmap, created on demand.  The list scans themselves go through the flat index's
@@ -240,26 +283,21 @@ struct nmn_ivf {
     std::shared_mutex rw;
     struct ProbeSlot {
         hipStream_t stream = nullptr;
-        uint32_t* cscores = nullptr;     // [centroids padded]
-        uint64_t* ckeys = nullptr;       // large-k sort buffer (more than kRankMax centroids only)
-        uint64_t* probe_rows = nullptr;  // [n_clusters]
-        float* probe_scores = nullptr;
-        uint32_t* probe_count = nullptr;
-        uint32_t* probe_rank = nullptr;
-        uint64_t* mask = nullptr;
-        uint64_t* mask_c = nullptr;      // selection over the list-major copy
-        float* qraw = nullptr;
-        float* qpad = nullptr;
-        QInfo* qinfo = nullptr;
-        QState* qstate = nullptr;
-        uint8_t* pin = nullptr;          // pinned: [queries nb x dim x 4 | probe rows nb x n_clusters x 8]
-        uint32_t nb = 1;                 // queries of one chunk the buffers above are sized for (probe_slot_grow)
+        RankScratch rank;
+        Grow mask;                       // selection over the id-ordered vectors, a bitmap per query of the chunk
+        Grow mask_c;                     // selection over the list-major copy
+        Grow pin{nullptr, 0, true};      // [queries nb x dim x 4 | probe rows nb x n_clusters x 8]
+        uint32_t nb = 0;                 // queries of one chunk the buffers above are sized for (probe_slot_grow)
         // a lone query's list scans enqueued right behind its bitmaps (one round trip per call): their results, device and pinned,
         // two parts (list-major copy, younger vectors) of res_k entries each: [rows u64 | scores f32 | count u32]
-        uint8_t* res_dev = nullptr;
-        uint8_t* res_pin = nullptr;
+        Grow res_dev, res_pin{nullptr, 0, true};
         uint64_t res_k = 0;
         bool busy = false;
+        template <class F>
+        void for_each(F&& fn) {
+            rank.for_each(fn);
+            for (Grow* g : {&mask, &mask_c, &pin, &res_dev, &res_pin}) fn(*g);
+        }
     };
     std::vector<std::unique_ptr<ProbeSlot>> slots;
     std::mutex slot_mu;
@@ -279,13 +317,16 @@ struct nmn_ivf {
     uint8_t* lcodes = nullptr;                // device, LIST-MAJOR codes [cap][code_bytes] (order of perm_host)
     // one coded search at a time owns the scratch below (searches of a PQ / Binary index are serialised; `add` holds rw exclusively)
     std::mutex codec_mu;
-    struct Grow {
-        void* p = nullptr;
-        size_t cap = 0;
-    };
-    Grow cs_qraw, cs_qpad, cs_qinfo, cs_qstate, cs_cscores, cs_ckeys, cs_probe_rows, cs_probe_scores, cs_probe_count, cs_segs,
-        cs_base, cs_tables, cs_qwords, cs_scores, cs_keys, cs_rows, cs_rscores, cs_rcnt;
-    // ---- nmn_ivf_search_device (docs/ivf.md §3.10c): none of the scratch above, nothing of the probe slots ----------------
+    struct CodecScratch {
+        RankScratch rank;
+        Grow segs, base, tables, qwords, scores, keys, rows, rscores, rcnt;
+        template <class F>
+        void for_each(F&& fn) {
+            rank.for_each(fn);
+            for (Grow* g : {&segs, &base, &tables, &qwords, &scores, &keys, &rows, &rscores, &rcnt}) fn(*g);
+        }
+    } cs;
+    // ---- nmn_ivf_search_device (docs/ivf.md §3.10c): a scratch of its own per caller stream, nothing of the probe slots or `cs` ----
     // The candidate-order id map of every storage: dev_perm[dev_off[c] + j] = id - id base of the j-th vector of list c (ids
     // ascending inside a list; for Flat over ALL the vectors, list-major copy and younger ones alike), built by the first
     // device search and again after an `add` (dev_gen != gen).  dev_top[i] = rows of the i largest lists (the host-known bound
@@ -299,8 +340,13 @@ struct nmn_ivf {
     struct DevScratch {                  // per caller stream: pipelined calls on one stream share it, in stream order
         hipStream_t stream = nullptr;
         std::mutex mu;                   // held while a call enqueues
-        Grow qpad, qinfo, qstate, cscores, ckeys, probe_rows, probe_scores, probe_rank, probe_count, segs, base, totals, scores, keys,
-            tables, qwords;
+        RankScratch rank;
+        Grow segs, base, totals, scores, keys, tables, qwords;
+        template <class F>
+        void for_each(F&& fn) {
+            rank.for_each(fn);
+            for (Grow* g : {&segs, &base, &totals, &scores, &keys, &tables, &qwords}) fn(*g);
+        }
     };
     std::vector<std::unique_ptr<DevScratch>> dev_scratch;
     // an event per device search, recorded behind its last kernel: add / destroy wait for the pending ones before they touch
@@ -329,40 +375,21 @@ extern "C" nmn_status nmn_ivf_destroy(nmn_ivf* ivf) {
     (void)hipSetDevice(ivf->device);
     ivf_wait_device_searches(ivf);
     for (hipEvent_t e : ivf->ev_free) (void)hipEventDestroy(e);
-    for (auto& sc : ivf->dev_scratch)
-        for (nmn_ivf::Grow* g : {&sc->qpad, &sc->qinfo, &sc->qstate, &sc->cscores, &sc->ckeys, &sc->probe_rows, &sc->probe_scores,
-                                 &sc->probe_rank, &sc->probe_count, &sc->segs, &sc->base, &sc->totals, &sc->scores, &sc->keys, &sc->tables,
-                                 &sc->qwords})
-            if (g->p) (void)hipFree(g->p);
-    if (ivf->dev_perm) (void)hipFree(ivf->dev_perm);
-    if (ivf->dev_off) (void)hipFree(ivf->dev_off);
+    auto drop = [](Grow& g) { g.release(); };  // (nmn_ivf_hbm_bytes walks the same enumerators)
+    for (auto& sc : ivf->dev_scratch) sc->for_each(drop);
     if (ivf->stream) (void)hipStreamSynchronize(ivf->stream);
-    for (void* p : {(void*)ivf->assign, (void*)ivf->cscores, (void*)ivf->ckeys, (void*)ivf->probe_rows,
-                    (void*)ivf->probe_scores, (void*)ivf->probe_count, (void*)ivf->probe_rank, (void*)ivf->mask,
-                    (void*)ivf->qraw, (void*)ivf->qpad, (void*)ivf->qinfo, (void*)ivf->qstate, (void*)ivf->assign_tmp,
-                    (void*)ivf->list_off})
-        if (p) (void)hipFree(p);
     for (auto& sl : ivf->slots) {
         if (sl->stream) {
             (void)hipStreamSynchronize(sl->stream);
             (void)hipStreamDestroy(sl->stream);
         }
-        for (void* p : {(void*)sl->cscores, (void*)sl->ckeys, (void*)sl->probe_rows, (void*)sl->probe_scores,
-                        (void*)sl->probe_count, (void*)sl->probe_rank, (void*)sl->mask, (void*)sl->mask_c, (void*)sl->qraw, (void*)sl->qpad,
-                        (void*)sl->qinfo, (void*)sl->qstate})
-            if (p) (void)hipFree(p);
-        if (sl->pin) (void)hipHostFree(sl->pin);
-        if (sl->res_dev) (void)hipFree(sl->res_dev);
-        if (sl->res_pin) (void)hipHostFree(sl->res_pin);
+        sl->for_each(drop);
     }
     if (ivf->stream) (void)hipStreamDestroy(ivf->stream);
-    for (nmn_ivf::Grow* g : {&ivf->cs_qraw, &ivf->cs_qpad, &ivf->cs_qinfo, &ivf->cs_qstate, &ivf->cs_cscores, &ivf->cs_ckeys,
-                             &ivf->cs_probe_rows, &ivf->cs_probe_scores, &ivf->cs_probe_count, &ivf->cs_segs, &ivf->cs_base,
-                             &ivf->cs_tables, &ivf->cs_qwords, &ivf->cs_scores, &ivf->cs_keys, &ivf->cs_rows, &ivf->cs_rscores,
-                             &ivf->cs_rcnt})
-        if (g->p) (void)hipFree(g->p);
-    if (ivf->codebook) (void)hipFree(ivf->codebook);
-    if (ivf->lcodes) (void)hipFree(ivf->lcodes);
+    ivf->cs.for_each(drop);
+    for (void* p : {(void*)ivf->assign, (void*)ivf->cscores, (void*)ivf->qinfo, (void*)ivf->list_off, (void*)ivf->codebook,
+                    (void*)ivf->lcodes, (void*)ivf->dev_perm, (void*)ivf->dev_off})
+        if (p) (void)hipFree(p);
     if (ivf->cvec) nmn_index_destroy(ivf->cvec);
     if (ivf->vectors) nmn_index_destroy(ivf->vectors);
     if (ivf->centroids) nmn_index_destroy(ivf->centroids);
@@ -403,7 +430,6 @@ static nmn_status ivf_new(const nmn_index_desc* desc, const float* centroids, ui
     ivf->device = ivf->centroids->device;
     ivf->cap = coded ? desc->capacity_rows : ivf->vectors->cap;
     ivf->row_base = desc->row_base;
-    const uint32_t ld = coded ? ivf->centroids->ld : ivf->vectors->ld;
     const size_t c_pad = ivf->centroids->cap_pad;
     hipError_t e = hipSetDevice(ivf->device);
     auto alloc = [&](void** p, size_t bytes) {
@@ -415,17 +441,7 @@ static nmn_status ivf_new(const nmn_index_desc* desc, const float* centroids, ui
     ivf->assign_chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(kAssignChunk, (16ull << 20) / c_pad));
     ivf->cscores_cap = c_pad * ivf->assign_chunk;
     alloc(reinterpret_cast<void**>(&ivf->cscores), ivf->cscores_cap * 4);
-    alloc(reinterpret_cast<void**>(&ivf->ckeys), largek_sort_len(n_clusters) * 8);
-    alloc(reinterpret_cast<void**>(&ivf->probe_rows), (size_t)n_clusters * 8);
-    alloc(reinterpret_cast<void**>(&ivf->probe_scores), (size_t)n_clusters * 4);
-    alloc(reinterpret_cast<void**>(&ivf->probe_count), 8);  // [0] clusters probed, [1] results of the list scan
-    alloc(reinterpret_cast<void**>(&ivf->probe_rank), (size_t)n_clusters * 4);
-    alloc(reinterpret_cast<void**>(&ivf->mask), coded ? 64 : ((ivf->cap + 63) / 64 + 1) * 8);
-    alloc(reinterpret_cast<void**>(&ivf->qraw), (size_t)desc->dim * 4);
-    alloc(reinterpret_cast<void**>(&ivf->qpad), (size_t)ld * 4);
     alloc(reinterpret_cast<void**>(&ivf->qinfo), sizeof(QInfo) * kAssignChunk);
-    alloc(reinterpret_cast<void**>(&ivf->qstate), sizeof(QState) * kAssignChunk);
-    alloc(reinterpret_cast<void**>(&ivf->assign_tmp), 4 * kAssignChunk);
     if (e == hipSuccess) e = hipMemsetAsync(ivf->qinfo, 0, sizeof(QInfo) * kAssignChunk, ivf->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ivf->stream);
     if (e != hipSuccess) return bail(set_error_hip(e, "nmn_ivf_create"));
@@ -451,23 +467,89 @@ extern "C" nmn_status nmn_ivf_cluster_sizes(nmn_ivf* ivf, uint64_t* out_sizes) {
     return NMN_OK;
 }
 
-// exact -d^2 of `nq` queries (already padded to ld in device memory) against every centroid -> cscores
-static nmn_status centroid_scores(nmn_ivf* ivf, const float* qpad_dev, uint32_t nq) {
+// The exact sweep every stage here is built on: scores (tile-major, score_at) = -d^2 of `nq` padded queries (device memory, stride
+// x->ld; qinfo: zeros, or launch_qprep's) against rows [0, n_rows) of `x`.
+static hipError_t sweep_neg_l2sq(const nmn_index* x, uint64_t n_rows, uint32_t dim, const float* qpad, const QInfo* qinfo, uint32_t nq,
+                                 uint32_t* scores, hipStream_t s) {
     ExactScanParams ep{};
-    ep.corpus = ivf->centroids->corpus;
-    ep.norms = ivf->centroids->norms;
-    ep.qpad = qpad_dev;
-    ep.qinfo = ivf->qinfo;
-    ep.qstate = nullptr;
-    ep.mask = nullptr;
-    ep.scores = ivf->cscores;
-    ep.n_rows = ivf->n_clusters;
+    ep.corpus = x->corpus;
+    ep.norms = x->norms;
+    ep.qpad = qpad;
+    ep.qinfo = qinfo;
+    ep.scores = scores;
+    ep.n_rows = n_rows;
     ep.nql = nq;
-    ep.ld = ivf->centroids->ld;
-    ep.dim = ivf->dim;
+    ep.ld = x->ld;
+    ep.dim = dim;
     ep.nq = nq;
     ep.metric = kMetricNegL2Sq;
-    IVF_TRY(launch_exact_scan(ep, ivf->stream));
+    return launch_exact_scan(ep, s);
+}
+
+// exact -d^2 of `nq` queries (already padded to ld in device memory) against every centroid -> cscores
+static nmn_status centroid_scores(nmn_ivf* ivf, const float* qpad_dev, uint32_t nq) {
+    IVF_TRY(sweep_neg_l2sq(ivf->centroids, ivf->n_clusters, ivf->dim, qpad_dev, ivf->qinfo, nq, ivf->cscores, ivf->stream));
+    return NMN_OK;
+}
+
+// The raw queries ARE the padded ones where the rows are not padded (stride == dim) and the eight-lanes-per-row scan serves
+// (fewer than 2^16 centroids): the centroid ranking is a squared-distance scan, it reads the first `dim` elements of each query and
+// nothing qprep derives (no magnitude, no margins), so no qprep launch in front of it (5.6 us + a 4-us gap of a lone probe's ~150,
+// profiles/r05q_*).  Constant for the life of an index.
+static bool raw_queries(const nmn_ivf* ivf) {
+    return ivf->centroids->ld == ivf->dim && (!ivf->vectors || ivf->vectors->ld == ivf->dim) && ivf->n_clusters < (1u << 16);
+}
+
+hipError_t RankScratch::reserve(const nmn_ivf* ivf, uint32_t nb, bool stage, hipStream_t s, bool& wait) {
+    const size_t C = ivf->n_clusters, c_pad = ivf->centroids->cap_pad, ld = ivf->centroids->ld, qinfo_cap = qinfo.cap;
+    hipError_t e = hipSuccess;
+    auto need = [&](Grow& g, size_t bytes) {
+        if (e == hipSuccess) e = g.reserve(bytes, s, wait);
+    };
+    if (stage) need(qraw, (size_t)ivf->dim * nb * 4);
+    need(qpad, ld * nb * 4);
+    need(qinfo, sizeof(QInfo) * nb);
+    need(qstate, sizeof(QState) * nb);
+    need(cscores, c_pad * nb * 4);
+    need(probe_rows, C * nb * 8);
+    need(probe_rank, C * nb * 4);
+    need(probe_count, (size_t)nb * 8);
+    if (C > kRankMax) {  // the large-k sort, one query at a time
+        need(ckeys, largek_sort_len(C) * 8);
+        need(probe_scores, C * 4);
+    }
+    if (e == hipSuccess && qinfo.cap != qinfo_cap) e = hipMemsetAsync(qinfo.p, 0, qinfo.cap, s);
+    return e;
+}
+
+// Stage one of every search: the centroids of `nb` queries (device memory, dim floats each) ranked by squared distance, ascending,
+// ties by centroid index; the first `np` kept.  Everything on `s`, nothing waited for.  Up to kRankMax centroids: query q's probe
+// order at probe_rows + q * n_clusters, its ranks at probe_rank + q * n_clusters, its count at probe_count + q.  Above: nb == 1,
+// the large-k sort writes probe_rows, probe_scores and probe_count; probe_rank only where the caller reads it (fill_rank).
+static nmn_status rank_centroids(nmn_ivf* ivf, const float* queries_dev, uint32_t nb, uint32_t np, RankScratch& sc, bool fill_rank,
+                                 hipStream_t s) {
+    const uint32_t C = ivf->n_clusters;
+    const bool raw_q = raw_queries(ivf);
+    if (!raw_q)
+        IVF_TRY(launch_qprep(queries_dev, nb, ivf->dim, ivf->centroids->ld, kMetricNegL2Sq, ivf->centroids->max_norm_bits, gp<float>(sc.qpad),
+                             gp<QInfo>(sc.qinfo), gp<QState>(sc.qstate), 0, s));
+    IVF_TRY(sweep_neg_l2sq(ivf->centroids, C, ivf->dim, raw_q ? queries_dev : gp<float>(sc.qpad), gp<QInfo>(sc.qinfo), nb,
+                           gp<uint32_t>(sc.cscores), s));
+    if (C <= kRankMax) {
+        uint32_t np2 = 2;
+        while (np2 < C) np2 <<= 1;
+        hipLaunchKernelGGL(ivf_rank_kernel, dim3(nb), dim3(1024), 0, s, gp<uint32_t>(sc.cscores), nb, C, np2, np, gp<uint64_t>(sc.probe_rows),
+                           gp<uint32_t>(sc.probe_count), gp<uint32_t>(sc.probe_rank));
+    } else {
+        IVF_TRY(launch_largek(gp<uint32_t>(sc.cscores), C, gp<uint64_t>(sc.ckeys), np, 0, gp<uint64_t>(sc.probe_rows), gp<float>(sc.probe_scores),
+                              gp<uint32_t>(sc.probe_count), s));
+        if (fill_rank) {
+            IVF_TRY(hipMemsetAsync(sc.probe_rank.p, 0xFF, (size_t)C * 4, s));
+            hipLaunchKernelGGL(ivf_probe_rank_kernel, dim3((np + 255) / 256), dim3(256), 0, s, gp<uint64_t>(sc.probe_rows),
+                               gp<uint32_t>(sc.probe_count), gp<uint32_t>(sc.probe_rank));
+        }
+    }
+    IVF_TRY(hipGetLastError());
     return NMN_OK;
 }
 
@@ -658,19 +740,7 @@ static nmn_status ivf_train_flat(const nmn_index_desc* desc, const float* rows_h
         memcpy(cents.data(), rows_host + pick * dim, dim * sizeof(float));
         for (uint32_t j = 1; j < k && he == hipSuccess; j++) {
             // dist[i] = min(dist[i], |v_i - last centroid|^2): the last centroid is row `pick`, already a padded query
-            ExactScanParams ep{};
-            ep.corpus = ivf->vectors->corpus;
-            ep.norms = ivf->vectors->norms;
-            ep.qpad = ivf->vectors->corpus + pick * (uint64_t)ld;
-            ep.qinfo = ivf->qinfo;
-            ep.scores = sweep;
-            ep.n_rows = n;
-            ep.nql = 1;
-            ep.ld = ld;
-            ep.dim = (uint32_t)dim;
-            ep.nq = 1;
-            ep.metric = kMetricNegL2Sq;
-            he = launch_exact_scan(ep, s);
+            he = sweep_neg_l2sq(ivf->vectors, n, (uint32_t)dim, ivf->vectors->corpus + pick * (uint64_t)ld, ivf->qinfo, 1, sweep, s);
             if (he == hipSuccess) he = launch_kmeans_min_update(dist_dev, sweep, n, s);
             if (he == hipSuccess) he = hipMemcpyAsync(dist.data(), dist_dev, n * 4, hipMemcpyDeviceToHost, s);
             if (he == hipSuccess) he = hipStreamSynchronize(s);
@@ -782,6 +852,24 @@ extern "C" nmn_status nmn_ivf_centroids(nmn_ivf* ivf, float* out, uint64_t cap_f
     return NMN_OK;
 }
 
+// Size a slot's per-query buffers for chunks of `nb` queries (many queries of one nmn_ivf_search call share the centroid
+// sweep, the ranking launch, the bitmap launches and ONE round trip to the host).  Only grows.
+static nmn_status probe_slot_grow(nmn_ivf* ivf, nmn_ivf::ProbeSlot* sl, uint32_t nb) {
+    if (nb <= sl->nb) return NMN_OK;
+    const size_t C = ivf->n_clusters, words = (ivf->cap + 63) / 64 + 1;
+    bool wait = sl->nb != 0;  // (nothing is enqueued on a slot just created, nor since a growth that failed: that one had waited)
+    hipError_t e = sl->rank.reserve(ivf, nb, true, sl->stream, wait);
+    if (e == hipSuccess) e = sl->mask.reserve(words * nb * 8, sl->stream, wait);
+    if (e == hipSuccess) e = sl->mask_c.reserve(words * nb * 8, sl->stream, wait);
+    if (e == hipSuccess) e = sl->pin.reserve((((size_t)ivf->dim * 4 * nb + 15) & ~(size_t)15) + C * 8 * nb + 16, sl->stream, wait);
+    if (e != hipSuccess) {
+        sl->nb = 0;  // (buffers in an unknown state: the next call grows them again from scratch)
+        return set_error_hip(e, "IVF probe slot (chunk buffers)");
+    }
+    sl->nb = nb;
+    return NMN_OK;
+}
+
 // a free probe slot (created on demand; waits when kMaxSlots are all busy)
 static nmn_status probe_slot_acquire(nmn_ivf* ivf, nmn_ivf::ProbeSlot** out, uint32_t* busy_now = nullptr) {
     std::unique_lock<std::mutex> lk(ivf->slot_mu);
@@ -800,77 +888,16 @@ static nmn_status probe_slot_acquire(nmn_ivf* ivf, nmn_ivf::ProbeSlot** out, uin
         ivf->slot_cv.wait(lk);
     }
     auto sl = std::make_unique<nmn_ivf::ProbeSlot>();
-    const size_t c_pad = ivf->centroids->cap_pad;
-    const uint32_t ld = ivf->vectors->ld;
     hipError_t e = hipStreamCreateWithFlags(&sl->stream, hipStreamNonBlocking);
-    auto alloc = [&](void** p, size_t bytes) {
-        if (e == hipSuccess) e = hipMalloc(p, std::max<size_t>(bytes, 64));
-    };
-    alloc(reinterpret_cast<void**>(&sl->cscores), c_pad * 4);
-    if (ivf->n_clusters > kRankMax) alloc(reinterpret_cast<void**>(&sl->ckeys), largek_sort_len(ivf->n_clusters) * 8);
-    alloc(reinterpret_cast<void**>(&sl->probe_rows), (size_t)ivf->n_clusters * 8);
-    alloc(reinterpret_cast<void**>(&sl->probe_scores), (size_t)ivf->n_clusters * 4);
-    alloc(reinterpret_cast<void**>(&sl->probe_count), 8);
-    alloc(reinterpret_cast<void**>(&sl->probe_rank), (size_t)ivf->n_clusters * 4);
-    alloc(reinterpret_cast<void**>(&sl->mask), ((ivf->cap + 63) / 64 + 1) * 8);
-    alloc(reinterpret_cast<void**>(&sl->mask_c), ((ivf->cap + 63) / 64 + 1) * 8);
-    alloc(reinterpret_cast<void**>(&sl->qraw), (size_t)ivf->dim * 4);
-    alloc(reinterpret_cast<void**>(&sl->qpad), (size_t)ld * 4);
-    alloc(reinterpret_cast<void**>(&sl->qinfo), sizeof(QInfo));
-    alloc(reinterpret_cast<void**>(&sl->qstate), sizeof(QState));
-    if (e == hipSuccess) e = hipMemsetAsync(sl->qinfo, 0, sizeof(QInfo), sl->stream);
-    if (e == hipSuccess)
-        e = hipHostMalloc(reinterpret_cast<void**>(&sl->pin), (size_t)ivf->dim * 4 + (size_t)ivf->n_clusters * 8 + 16,
-                          hipHostMallocDefault);
-    if (e != hipSuccess) {
+    nmn_status st = e == hipSuccess ? probe_slot_grow(ivf, sl.get(), 1) : set_error_hip(e, "IVF probe slot");
+    if (st != NMN_OK) {
         if (sl->stream) (void)hipStreamDestroy(sl->stream);
-        for (void* p : {(void*)sl->cscores, (void*)sl->ckeys, (void*)sl->probe_rows, (void*)sl->probe_scores,
-                        (void*)sl->probe_count, (void*)sl->probe_rank, (void*)sl->mask, (void*)sl->mask_c, (void*)sl->qraw, (void*)sl->qpad,
-                        (void*)sl->qinfo, (void*)sl->qstate})
-            if (p) (void)hipFree(p);
-        if (sl->pin) (void)hipHostFree(sl->pin);
-        return set_error_hip(e, "IVF probe slot");
+        sl->for_each([](Grow& g) { g.release(); });
+        return st;
     }
     sl->busy = true;
     *out = sl.get();
     ivf->slots.push_back(std::move(sl));
-    return NMN_OK;
-}
-// Size a slot's per-query buffers for chunks of `nb` queries (many queries of one nmn_ivf_search call share the centroid
-// sweep, the ranking launch, the bitmap launches and ONE round trip to the host).  Only grows.
-static nmn_status probe_slot_grow(nmn_ivf* ivf, nmn_ivf::ProbeSlot* sl, uint32_t nb) {
-    if (nb <= sl->nb) return NMN_OK;
-    IVF_TRY(hipStreamSynchronize(sl->stream));
-    const size_t c_pad = ivf->centroids->cap_pad, C = ivf->n_clusters, words = (ivf->cap + 63) / 64 + 1;
-    const uint32_t ld = ivf->vectors->ld;
-    hipError_t e = hipSuccess;
-    auto regrow = [&](void** p, size_t bytes) {
-        if (e != hipSuccess) return;
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-        e = hipMalloc(p, std::max<size_t>(bytes, 64));
-    };
-    regrow(reinterpret_cast<void**>(&sl->cscores), c_pad * nb * 4);
-    regrow(reinterpret_cast<void**>(&sl->probe_rows), C * nb * 8);
-    regrow(reinterpret_cast<void**>(&sl->probe_count), (size_t)nb * 8);
-    regrow(reinterpret_cast<void**>(&sl->probe_rank), C * nb * 4);
-    regrow(reinterpret_cast<void**>(&sl->mask), words * nb * 8);
-    regrow(reinterpret_cast<void**>(&sl->mask_c), words * nb * 8);
-    regrow(reinterpret_cast<void**>(&sl->qraw), (size_t)ivf->dim * nb * 4);
-    regrow(reinterpret_cast<void**>(&sl->qpad), (size_t)ld * nb * 4);
-    regrow(reinterpret_cast<void**>(&sl->qinfo), sizeof(QInfo) * nb);
-    regrow(reinterpret_cast<void**>(&sl->qstate), sizeof(QState) * nb);
-    if (e == hipSuccess) e = hipMemsetAsync(sl->qinfo, 0, sizeof(QInfo) * nb, sl->stream);
-    if (e == hipSuccess) {
-        if (sl->pin) (void)hipHostFree(sl->pin);
-        sl->pin = nullptr;
-        e = hipHostMalloc(reinterpret_cast<void**>(&sl->pin), ((size_t)ivf->dim * 4 * nb + 15 & ~(size_t)15) + C * 8 * nb + 16, hipHostMallocDefault);
-    }
-    if (e != hipSuccess) {
-        sl->nb = 0;  // (buffers in an unknown state: the next call grows them again from scratch)
-        return set_error_hip(e, "IVF probe slot (chunk buffers)");
-    }
-    sl->nb = nb;
     return NMN_OK;
 }
 
@@ -923,8 +950,13 @@ extern "C" nmn_status nmn_ivf_search(nmn_ivf* ivf, const float* queries, uint32_
     const uint32_t chunk = (ivf->n_clusters <= kRankMax) ? std::min<uint32_t>(nq, kProbeChunk) : 1u;  // (> 4096 lists: the large-k sort, one query at a time)
     st = probe_slot_grow(ivf, sl, chunk);
     if (st != NMN_OK) return st;
-    float* pin_q = reinterpret_cast<float*>(sl->pin);
-    uint64_t* probe_host_all = reinterpret_cast<uint64_t*>(sl->pin + (((size_t)ivf->dim * 4 * sl->nb + 15) & ~(size_t)15));
+    float* pin_q = gp<float>(sl->pin);
+    uint64_t* probe_host_all = reinterpret_cast<uint64_t*>(gp<uint8_t>(sl->pin) + (((size_t)ivf->dim * 4 * sl->nb + 15) & ~(size_t)15));
+    float* const qraw = gp<float>(sl->rank.qraw);
+    const uint64_t* const probe_rows = gp<uint64_t>(sl->rank.probe_rows);
+    const uint32_t* const probe_rank = gp<uint32_t>(sl->rank.probe_rank);
+    uint64_t* const mask = gp<uint64_t>(sl->mask);
+    uint64_t* const mask_c = gp<uint64_t>(sl->mask_c);
     const uint64_t c_rows = ivf->cvec ? std::min(ivf->c_rows, n_rows) : 0;  // ids the list-major copy covers
     // The list scans of a chunk as ONE batch per part (list-major copy / younger vectors): the flat index's batched sweep reads a
     // bitmap per query, so sixteen probes cost one pass over the vectors instead of sixteen launch-bound searches — whenever that
@@ -988,52 +1020,19 @@ extern "C" nmn_status nmn_ivf_search(nmn_ivf* ivf, const float* queries, uint32_
             //    list assignments into selection bitmaps — all on this slot's stream, one wait
             const uint32_t nb = std::min<uint32_t>(chunk, nq - q);
             memcpy(pin_q, qh, (size_t)ivf->dim * 4 * nb);
-            IVF_TRY(hipMemcpyAsync(sl->qraw, pin_q, (size_t)ivf->dim * 4 * nb, hipMemcpyHostToDevice, s));
-            // The centroid ranking is a squared-distance scan: it reads the first `dim` elements of each query and nothing qprep
-            // derives (no magnitude, no margins).  Where the rows are not padded (stride == dim) and the eight-lanes-per-row scan
-            // serves (fewer than 2^16 centroids) the raw queries ARE the padded ones: no qprep launch in front of it (5.6 us +
-            // a 4-us gap of a lone probe's ~150, profiles/r05q_*).
-            const bool raw_q = ivf->centroids->ld == ivf->dim && ivf->vectors->ld == ivf->dim && ivf->n_clusters < (1u << 16);
-            if (!raw_q)
-                IVF_TRY(launch_qprep(sl->qraw, nb, ivf->dim, ivf->vectors->ld, kMetricNegL2Sq, ivf->centroids->max_norm_bits, sl->qpad,
-                                     sl->qinfo, sl->qstate, 0, s));
-            {
-                ExactScanParams ep{};
-                ep.corpus = ivf->centroids->corpus;
-                ep.norms = ivf->centroids->norms;
-                ep.qpad = raw_q ? sl->qraw : sl->qpad;
-                ep.qinfo = sl->qinfo;
-                ep.scores = sl->cscores;
-                ep.n_rows = ivf->n_clusters;
-                ep.nql = nb;
-                ep.ld = ivf->centroids->ld;
-                ep.dim = ivf->dim;
-                ep.nq = nb;
-                ep.metric = kMetricNegL2Sq;
-                IVF_TRY(launch_exact_scan(ep, s));
-            }
-            if (ivf->n_clusters <= kRankMax) {
-                uint32_t np2 = 2;
-                while (np2 < ivf->n_clusters) np2 <<= 1;
-                hipLaunchKernelGGL(ivf_rank_kernel, dim3(nb), dim3(1024), 0, s, sl->cscores, nb, ivf->n_clusters, np2, np, sl->probe_rows,
-                                   sl->probe_count, sl->probe_rank);
-            } else {
-                IVF_TRY(launch_largek(sl->cscores, ivf->n_clusters, sl->ckeys, np, 0, sl->probe_rows, sl->probe_scores,
-                                      sl->probe_count, s));
-                IVF_TRY(hipMemsetAsync(sl->probe_rank, 0xFF, (size_t)ivf->n_clusters * 4, s));
-                hipLaunchKernelGGL(ivf_probe_rank_kernel, dim3((np + 255) / 256), dim3(256), 0, s, sl->probe_rows, sl->probe_count,
-                                   sl->probe_rank);
-            }
+            IVF_TRY(hipMemcpyAsync(qraw, pin_q, (size_t)ivf->dim * 4 * nb, hipMemcpyHostToDevice, s));
+            st = rank_centroids(ivf, qraw, nb, np, sl->rank, true, s);  // (the bitmaps below read the ranks: above kRankMax too)
+            if (st != NMN_OK) return st;
             if (c_rows) {
                 const uint64_t cw = (c_rows + 63) / 64;
                 hipLaunchKernelGGL(ivf_range_mask_kernel, dim3((uint32_t)std::min<uint64_t>((cw + 3) / 4, 4096), nb), dim3(256), 0, s,
-                                   ivf->list_off, ivf->n_clusters, sl->probe_rank, c_rows, sl->mask_c, (uint64_t)mask_words);
+                                   ivf->list_off, ivf->n_clusters, probe_rank, c_rows, mask_c, (uint64_t)mask_words);
             }
             if (c_rows < n_rows) {
                 const uint64_t n_words = (n_rows + 63) / 64;
                 const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_words + 3) / 4, 4096);
-                hipLaunchKernelGGL(ivf_mask_kernel, dim3(blocks, nb), dim3(256), 0, s, ivf->assign, sl->probe_rank, ivf->n_clusters, n_rows,
-                                   c_rows, sl->mask, (uint64_t)mask_words);
+                hipLaunchKernelGGL(ivf_mask_kernel, dim3(blocks, nb), dim3(256), 0, s, ivf->assign, probe_rank, ivf->n_clusters, n_rows,
+                                   c_rows, mask, (uint64_t)mask_words);
             }
             IVF_TRY(hipGetLastError());
             // A lone query, nobody else searching: its list scans are enqueued HERE, on this stream, behind the bitmaps they read —
@@ -1045,15 +1044,14 @@ extern "C" nmn_status nmn_ivf_search(nmn_ivf* ivf, const float* queries, uint32_
             const size_t part_bytes = ((size_t)kk1 * 12 + 4 + 15) & ~(size_t)15;
             if (direct) {
                 if (sl->res_k < kk1) {
-                    IVF_TRY(hipStreamSynchronize(s));
-                    if (sl->res_dev) (void)hipFree(sl->res_dev);
-                    if (sl->res_pin) (void)hipHostFree(sl->res_pin);
-                    sl->res_dev = sl->res_pin = nullptr;
                     sl->res_k = 0;
-                    IVF_TRY(hipMalloc(reinterpret_cast<void**>(&sl->res_dev), 2 * part_bytes));
-                    IVF_TRY(hipHostMalloc(reinterpret_cast<void**>(&sl->res_pin), 2 * part_bytes, hipHostMallocDefault));
+                    bool wait = true;
+                    IVF_TRY(sl->res_dev.reserve(2 * part_bytes, s, wait));
+                    IVF_TRY(sl->res_pin.reserve(2 * part_bytes, s, wait));
                     sl->res_k = kk1;
                 }
+                uint8_t* const res_dev = gp<uint8_t>(sl->res_dev);
+                const uint8_t* const res_pin = gp<uint8_t>(sl->res_pin);
                 const size_t pb = (((size_t)sl->res_k * 12 + 4 + 15) & ~(size_t)15);
                 auto part = [&](uint8_t* base, int i, uint64_t** r, float** sc, uint32_t** c) {
                     uint8_t* b = base + (size_t)i * pb;
@@ -1069,24 +1067,24 @@ extern "C" nmn_status nmn_ivf_search(nmn_ivf* ivf, const float* queries, uint32_
                     uint32_t* c;
                     nmn_status e = NMN_OK;
                     if (c_rows && want_c) {
-                        part(sl->res_dev, 0, &r, &sc, &c);
-                        e = index_search_device(ivf->cvec, sl->qraw, 1, (uint32_t)kk1, kMetricNegL2, sl->mask_c, r, sc, c, s, short_chain);
+                        part(res_dev, 0, &r, &sc, &c);
+                        e = index_search_device(ivf->cvec, qraw, 1, (uint32_t)kk1, kMetricNegL2, mask_c, r, sc, c, s, short_chain);
                         if (e != NMN_OK) return e;
                     }
                     if (c_rows < n_rows && want_t) {
-                        part(sl->res_dev, 1, &r, &sc, &c);
-                        e = index_search_device(ivf->vectors, sl->qraw, 1, (uint32_t)kk1, kMetricNegL2, sl->mask, r, sc, c, s, short_chain);
+                        part(res_dev, 1, &r, &sc, &c);
+                        e = index_search_device(ivf->vectors, qraw, 1, (uint32_t)kk1, kMetricNegL2, mask, r, sc, c, s, short_chain);
                         if (e != NMN_OK) return e;
                     }
-                    if (hipMemcpyAsync(sl->res_pin, sl->res_dev, 2 * pb, hipMemcpyDeviceToHost, s) != hipSuccess)
+                    if (hipMemcpyAsync(sl->res_pin.p, res_dev, 2 * pb, hipMemcpyDeviceToHost, s) != hipSuccess)
                         return set_error(NMN_ERR_STORAGE, "ivf: result copy");
                     return NMN_OK;
                 };
                 st = enqueue_scans(true, true, true);
                 if (st != NMN_OK) return st;
-                IVF_TRY(hipMemcpyAsync(probe_host_all, sl->probe_rows, (size_t)nb * ivf->n_clusters * 8, hipMemcpyDeviceToHost, s));
+                IVF_TRY(hipMemcpyAsync(probe_host_all, probe_rows, (size_t)nb * ivf->n_clusters * 8, hipMemcpyDeviceToHost, s));
                 IVF_TRY(hipStreamSynchronize(s));
-                auto flagged = [&](int i) { return *reinterpret_cast<const uint32_t*>(sl->res_pin + (size_t)i * pb + (size_t)sl->res_k * 12) == 0xFFFFFFFFu; };
+                auto flagged = [&](int i) { return *reinterpret_cast<const uint32_t*>(res_pin + (size_t)i * pb + (size_t)sl->res_k * 12) == 0xFFFFFFFFu; };
                 const bool again_c = c_rows && flagged(0), again_t = c_rows < n_rows && flagged(1);
                 if (again_c || again_t) {
                     if (again_c) index_short_chain_flagged(ivf->cvec);
@@ -1096,13 +1094,13 @@ extern "C" nmn_status nmn_ivf_search(nmn_ivf* ivf, const float* queries, uint32_
                     IVF_TRY(hipStreamSynchronize(s));
                 }
             } else {
-                IVF_TRY(hipMemcpyAsync(probe_host_all, sl->probe_rows, (size_t)nb * ivf->n_clusters * 8, hipMemcpyDeviceToHost, s));
+                IVF_TRY(hipMemcpyAsync(probe_host_all, probe_rows, (size_t)nb * ivf->n_clusters * 8, hipMemcpyDeviceToHost, s));
                 IVF_TRY(hipStreamSynchronize(s));
             }
             if (direct) {
                 const size_t pb = (((size_t)sl->res_k * 12 + 4 + 15) & ~(size_t)15);
                 auto take = [&](int i, std::vector<uint64_t>& ids, std::vector<float>& dist, std::vector<uint32_t>& cnt) {
-                    const uint8_t* b = sl->res_pin + (size_t)i * pb;
+                    const uint8_t* b = gp<uint8_t>(sl->res_pin) + (size_t)i * pb;
                     const uint64_t* r = reinterpret_cast<const uint64_t*>(b);
                     const float* sc = reinterpret_cast<const float*>(b + (size_t)sl->res_k * 8);
                     ids.assign(r, r + kk1);
@@ -1129,18 +1127,18 @@ extern "C" nmn_status nmn_ivf_search(nmn_ivf* ivf, const float* queries, uint32_
             for (uint32_t i = 0; i < nb; i++) probed_of(probe_host_all + (size_t)i * ivf->n_clusters, &hint_c[i], &hint_t[i]);
             if (!direct) batched_c = batched_t = false;
             if (c_rows && !direct) {
-                st = scan_many(ivf->cvec, sl->mask_c, hint_c, qh, nb, bc_ids, bc_dist, bc_cnt, &batched_c, (stats && q + nb == nq) ? stats : nullptr);
+                st = scan_many(ivf->cvec, mask_c, hint_c, qh, nb, bc_ids, bc_dist, bc_cnt, &batched_c, (stats && q + nb == nq) ? stats : nullptr);
                 if (st != NMN_OK) return st;
             }
             if (c_rows < n_rows && !direct) {
-                st = scan_many(ivf->vectors, sl->mask, hint_t, qh, nb, bt_ids, bt_dist, bt_cnt, &batched_t,
+                st = scan_many(ivf->vectors, mask, hint_t, qh, nb, bt_ids, bt_dist, bt_cnt, &batched_t,
                                (stats && q + nb == nq && !c_rows) ? stats : nullptr);
                 if (st != NMN_OK) return st;
             }
         }
         const uint64_t* probe_host = probe_host_all + (size_t)qc * ivf->n_clusters;
-        const uint64_t* mask_q = sl->mask + (size_t)qc * mask_words;
-        const uint64_t* mask_cq = sl->mask_c + (size_t)qc * mask_words;
+        const uint64_t* mask_q = mask + (size_t)qc * mask_words;
+        const uint64_t* mask_cq = mask_c + (size_t)qc * mask_words;
         // rows in the probed lists: the selectivity hint of the list scan (how the flat index's coalescer decides what may
         // run side by side) and the most the scan can return
         uint64_t probed_c = 0, probed_t = 0;
@@ -1254,22 +1252,6 @@ size_t index_hbm_bytes(const nmn_index* x) {
     if (x->half) b += (size_t)x->cap_pad * x->ld * 2;
     if (x->q8) b += (size_t)x->cap_pad * x->ld + (size_t)x->cap_pad * 16;
     return b;
-}
-
-// grow-only device scratch of the coded search
-hipError_t grow(nmn_ivf::Grow& g, size_t bytes) {
-    bytes = std::max<size_t>(bytes, 64);
-    if (g.cap >= bytes) return hipSuccess;
-    if (g.p) (void)hipFree(g.p);
-    g.p = nullptr;
-    g.cap = 0;
-    hipError_t e = hipMalloc(&g.p, bytes);
-    if (e == hipSuccess) g.cap = bytes;
-    return e;
-}
-template <class T>
-T* gp(nmn_ivf::Grow& g) {
-    return static_cast<T*>(g.p);
 }
 
 nmn_status check_storage(const nmn_ivf_storage* s, uint32_t dim) {
@@ -1544,17 +1526,11 @@ static nmn_status codec_search(nmn_ivf* ivf, const float* queries, uint32_t nq, 
     IVF_TRY(hipSetDevice(ivf->device));
     hipStream_t s = ivf->stream;
     const uint32_t ld = ivf->centroids->ld;
-    const size_t c_pad = ivf->centroids->cap_pad;
     const uint32_t chunk = C <= kRankMax ? std::min<uint32_t>(nq, 64) : 1u;
-    IVF_TRY(grow(ivf->cs_qraw, (size_t)dim * chunk * 4));
-    IVF_TRY(grow(ivf->cs_qpad, (size_t)ld * chunk * 4));
-    IVF_TRY(grow(ivf->cs_qinfo, sizeof(QInfo) * chunk));
-    IVF_TRY(grow(ivf->cs_qstate, sizeof(QState) * chunk));
-    IVF_TRY(grow(ivf->cs_cscores, c_pad * chunk * 4));
-    IVF_TRY(grow(ivf->cs_probe_rows, (size_t)C * chunk * 8));
-    IVF_TRY(grow(ivf->cs_probe_scores, (size_t)C * 4));
-    IVF_TRY(grow(ivf->cs_probe_count, (size_t)chunk * 8));
-    if (C > kRankMax) IVF_TRY(grow(ivf->cs_ckeys, largek_sort_len(C) * 8));
+    nmn_ivf::CodecScratch& cs = ivf->cs;
+    bool wait = false;  // (every coded search ends with a wait of its own: nothing enqueued still reads the scratch)
+    auto need = [&](Grow& g, size_t bytes) { return g.reserve(bytes, s, wait); };
+    IVF_TRY(cs.rank.reserve(ivf, chunk, true, s, wait));
     std::vector<uint64_t> probe_host((size_t)C * chunk);
     std::vector<uint32_t> pcount(chunk);
     const size_t seg_bytes = codec_seg_bytes();
@@ -1568,45 +1544,15 @@ static nmn_status codec_search(nmn_ivf* ivf, const float* queries, uint32_t nq, 
     for (uint32_t q0 = 0; q0 < nq; q0 += chunk) {
         const uint32_t nb = std::min<uint32_t>(chunk, nq - q0);
         // 1. the centroid ranking of the chunk, exactly as Flat ranks (squared distance ascending, ties by index)
-        IVF_TRY(hipMemcpyAsync(ivf->cs_qraw.p, queries + (size_t)q0 * dim, (size_t)nb * dim * 4, hipMemcpyHostToDevice, s));
-        const bool raw_q = ld == dim && C < (1u << 16);
-        if (!raw_q)
-            IVF_TRY(launch_qprep(gp<float>(ivf->cs_qraw), nb, dim, ld, kMetricNegL2Sq, ivf->centroids->max_norm_bits, gp<float>(ivf->cs_qpad),
-                                 gp<QInfo>(ivf->cs_qinfo), gp<QState>(ivf->cs_qstate), 0, s));
-        else
-            IVF_TRY(hipMemsetAsync(ivf->cs_qinfo.p, 0, sizeof(QInfo) * nb, s));
-        ExactScanParams ep{};
-        ep.corpus = ivf->centroids->corpus;
-        ep.norms = ivf->centroids->norms;
-        ep.qpad = raw_q ? gp<float>(ivf->cs_qraw) : gp<float>(ivf->cs_qpad);
-        ep.qinfo = gp<QInfo>(ivf->cs_qinfo);
-        ep.scores = gp<uint32_t>(ivf->cs_cscores);
-        ep.n_rows = C;
-        ep.nql = nb;
-        ep.ld = ld;
-        ep.dim = dim;
-        ep.nq = nb;
-        ep.metric = kMetricNegL2Sq;
-        IVF_TRY(launch_exact_scan(ep, s));
-        uint32_t* rank_scratch = gp<uint32_t>(ivf->cs_probe_scores);  // (probe_rank of the rank kernel: written, not read here)
+        IVF_TRY(hipMemcpyAsync(cs.rank.qraw.p, queries + (size_t)q0 * dim, (size_t)nb * dim * 4, hipMemcpyHostToDevice, s));
+        nmn_status st = rank_centroids(ivf, gp<float>(cs.rank.qraw), nb, np, cs.rank, false, s);
+        if (st != NMN_OK) return st;
         if (C <= kRankMax) {
-            uint32_t np2 = 2;
-            while (np2 < C) np2 <<= 1;
-            IVF_TRY(grow(ivf->cs_probe_scores, (size_t)C * nb * 4));
-            rank_scratch = gp<uint32_t>(ivf->cs_probe_scores);
-            hipLaunchKernelGGL(ivf_rank_kernel, dim3(nb), dim3(1024), 0, s, gp<uint32_t>(ivf->cs_cscores), nb, C, np2, np,
-                               gp<uint64_t>(ivf->cs_probe_rows), gp<uint32_t>(ivf->cs_probe_count), rank_scratch);
+            IVF_TRY(hipMemcpyAsync(probe_host.data(), cs.rank.probe_rows.p, (size_t)nb * C * 8, hipMemcpyDeviceToHost, s));
         } else {
-            IVF_TRY(launch_largek(gp<uint32_t>(ivf->cs_cscores), C, gp<uint64_t>(ivf->cs_ckeys), np, 0, gp<uint64_t>(ivf->cs_probe_rows),
-                                  gp<float>(ivf->cs_probe_scores), gp<uint32_t>(ivf->cs_probe_count), s));
+            IVF_TRY(hipMemcpyAsync(probe_host.data(), cs.rank.probe_rows.p, (size_t)np * 8, hipMemcpyDeviceToHost, s));
         }
-        IVF_TRY(hipGetLastError());
-        if (C <= kRankMax) {
-            IVF_TRY(hipMemcpyAsync(probe_host.data(), ivf->cs_probe_rows.p, (size_t)nb * C * 8, hipMemcpyDeviceToHost, s));
-        } else {
-            IVF_TRY(hipMemcpyAsync(probe_host.data(), ivf->cs_probe_rows.p, (size_t)np * 8, hipMemcpyDeviceToHost, s));
-        }
-        IVF_TRY(hipMemcpyAsync(pcount.data(), ivf->cs_probe_count.p, (size_t)nb * 4, hipMemcpyDeviceToHost, s));
+        IVF_TRY(hipMemcpyAsync(pcount.data(), cs.rank.probe_count.p, (size_t)nb * 4, hipMemcpyDeviceToHost, s));
         IVF_TRY(hipStreamSynchronize(s));
         // 2. candidates = the probed lists in probe order, each in list order (= id order)
         const size_t pstride = C <= kRankMax ? C : 0;
@@ -1643,46 +1589,46 @@ static nmn_status codec_search(nmn_ivf* ivf, const float* queries, uint32_t nq, 
                 rsum += std::min<uint64_t>(k, total[g0 + b]);
                 max_total = std::max(max_total, total[g0 + b]);
             }
-            IVF_TRY(grow(ivf->cs_segs, (size_t)ng * np * sizeof(Seg)));
-            IVF_TRY(grow(ivf->cs_base, (size_t)ng * 8));
-            IVF_TRY(grow(ivf->cs_scores, (size_t)sum * 4));
-            IVF_TRY(grow(ivf->cs_keys, largek_sort_len(std::max<uint64_t>(max_total, 1)) * 8));
-            IVF_TRY(grow(ivf->cs_rows, (size_t)rsum * 8));
-            IVF_TRY(grow(ivf->cs_rscores, (size_t)rsum * 4));
-            IVF_TRY(grow(ivf->cs_rcnt, (size_t)ng * 4));
-            IVF_TRY(hipMemcpyAsync(ivf->cs_segs.p, segs.data() + (size_t)g0 * np, (size_t)ng * np * sizeof(Seg), hipMemcpyHostToDevice, s));
-            IVF_TRY(hipMemcpyAsync(ivf->cs_base.p, base.data(), (size_t)ng * 8, hipMemcpyHostToDevice, s));
-            const float* qg = gp<float>(ivf->cs_qraw) + (size_t)g0 * dim;
+            IVF_TRY(need(cs.segs, (size_t)ng * np * sizeof(Seg)));
+            IVF_TRY(need(cs.base, (size_t)ng * 8));
+            IVF_TRY(need(cs.scores, (size_t)sum * 4));
+            IVF_TRY(need(cs.keys, largek_sort_len(std::max<uint64_t>(max_total, 1)) * 8));
+            IVF_TRY(need(cs.rows, (size_t)rsum * 8));
+            IVF_TRY(need(cs.rscores, (size_t)rsum * 4));
+            IVF_TRY(need(cs.rcnt, (size_t)ng * 4));
+            IVF_TRY(hipMemcpyAsync(cs.segs.p, segs.data() + (size_t)g0 * np, (size_t)ng * np * sizeof(Seg), hipMemcpyHostToDevice, s));
+            IVF_TRY(hipMemcpyAsync(cs.base.p, base.data(), (size_t)ng * 8, hipMemcpyHostToDevice, s));
+            const float* qg = gp<float>(cs.rank.qraw) + (size_t)g0 * dim;
             if (ivf->kind == NMN_IVF_PQ) {
-                IVF_TRY(grow(ivf->cs_tables, (size_t)ng * np * ivf->pq_m * Kt * 4));
-                IVF_TRY(launch_pq_search(qg, dim, ivf->centroids->corpus, ld, ivf->cs_segs.p, np, ng, max_count, ivf->codebook, ivf->pq_k,
-                                         ivf->pq_m, ivf->lcodes, gp<float>(ivf->cs_tables), gp<uint64_t>(ivf->cs_base),
-                                         gp<uint32_t>(ivf->cs_scores), s));
+                IVF_TRY(need(cs.tables, (size_t)ng * np * ivf->pq_m * Kt * 4));
+                IVF_TRY(launch_pq_search(qg, dim, ivf->centroids->corpus, ld, cs.segs.p, np, ng, max_count, ivf->codebook, ivf->pq_k,
+                                         ivf->pq_m, ivf->lcodes, gp<float>(cs.tables), gp<uint64_t>(cs.base),
+                                         gp<uint32_t>(cs.scores), s));
             } else {
                 const uint32_t W = (dim + 63) / 64;
-                IVF_TRY(grow(ivf->cs_qwords, (size_t)ng * W * 8));
-                IVF_TRY(launch_bq_quantize(qg, dim, ng, dim, ivf->bq_method, gp<uint64_t>(ivf->cs_qwords), s));
-                IVF_TRY(launch_bq_search(gp<uint64_t>(ivf->cs_qwords), dim, ivf->cs_segs.p, np, ng, max_count,
-                                         reinterpret_cast<const uint64_t*>(ivf->lcodes), gp<uint64_t>(ivf->cs_base),
-                                         gp<uint32_t>(ivf->cs_scores), s));
+                IVF_TRY(need(cs.qwords, (size_t)ng * W * 8));
+                IVF_TRY(launch_bq_quantize(qg, dim, ng, dim, ivf->bq_method, gp<uint64_t>(cs.qwords), s));
+                IVF_TRY(launch_bq_search(gp<uint64_t>(cs.qwords), dim, cs.segs.p, np, ng, max_count,
+                                         reinterpret_cast<const uint64_t*>(ivf->lcodes), gp<uint64_t>(cs.base),
+                                         gp<uint32_t>(cs.scores), s));
             }
-            IVF_TRY(hipMemsetAsync(ivf->cs_rcnt.p, 0, (size_t)ng * 4, s));
+            IVF_TRY(hipMemsetAsync(cs.rcnt.p, 0, (size_t)ng * 4, s));
             for (uint32_t b = 0; b < ng; b++) {
                 const uint64_t tot = total[g0 + b];
                 if (tot == 0) continue;
                 const uint32_t kq = (uint32_t)std::min<uint64_t>(k, tot);
-                IVF_TRY(launch_largek(gp<uint32_t>(ivf->cs_scores) + base[b], tot, gp<uint64_t>(ivf->cs_keys), kq, 0,
-                                      gp<uint64_t>(ivf->cs_rows) + rbase[b], gp<float>(ivf->cs_rscores) + rbase[b],
-                                      gp<uint32_t>(ivf->cs_rcnt) + b, s));
+                IVF_TRY(launch_largek(gp<uint32_t>(cs.scores) + base[b], tot, gp<uint64_t>(cs.keys), kq, 0,
+                                      gp<uint64_t>(cs.rows) + rbase[b], gp<float>(cs.rscores) + rbase[b],
+                                      gp<uint32_t>(cs.rcnt) + b, s));
             }
             std::vector<uint64_t> rrows(rsum);
             std::vector<float> rsc(rsum);
             std::vector<uint32_t> rcnt(ng);
             if (rsum) {
-                IVF_TRY(hipMemcpyAsync(rrows.data(), ivf->cs_rows.p, rsum * 8, hipMemcpyDeviceToHost, s));
-                IVF_TRY(hipMemcpyAsync(rsc.data(), ivf->cs_rscores.p, rsum * 4, hipMemcpyDeviceToHost, s));
+                IVF_TRY(hipMemcpyAsync(rrows.data(), cs.rows.p, rsum * 8, hipMemcpyDeviceToHost, s));
+                IVF_TRY(hipMemcpyAsync(rsc.data(), cs.rscores.p, rsum * 4, hipMemcpyDeviceToHost, s));
             }
-            IVF_TRY(hipMemcpyAsync(rcnt.data(), ivf->cs_rcnt.p, (size_t)ng * 4, hipMemcpyDeviceToHost, s));
+            IVF_TRY(hipMemcpyAsync(rcnt.data(), cs.rcnt.p, (size_t)ng * 4, hipMemcpyDeviceToHost, s));
             IVF_TRY(hipStreamSynchronize(s));
             // 4. candidate index -> (probed list, position) -> id; distance = -score
             for (uint32_t b = 0; b < ng; b++) {
@@ -1892,28 +1838,6 @@ __global__ __launch_bounds__(256) void ivf_idmap_kernel(const uint4* __restrict_
     if (blockIdx.x == 0 && threadIdx.x == 0) counts[q] = cnt;
 }
 
-// grow-only scratch of one stream's device searches: a buffer that must grow waits for the stream first (the calls before
-// this one may still read it) — the only wait of the pipeline, never in steady state
-struct DevGrow {
-    hipStream_t s;
-    bool synced = false;
-    hipError_t e = hipSuccess;
-    void operator()(nmn_ivf::Grow& g, size_t bytes) {
-        bytes = std::max<size_t>(bytes, 64);
-        if (e != hipSuccess || g.cap >= bytes) return;
-        if (!synced) {
-            e = hipStreamSynchronize(s);
-            synced = true;
-            if (e != hipSuccess) return;
-        }
-        if (g.p) (void)hipFree(g.p);
-        g.p = nullptr;
-        g.cap = 0;
-        e = hipMalloc(&g.p, bytes);
-        if (e == hipSuccess) g.cap = bytes;
-    }
-};
-
 // the candidate-order id map and list offsets of the current index state on the device (caller holds rw shared and dev_mu)
 nmn_status dev_map_build(nmn_ivf* ivf, hipStream_t s) {
     const bool flat = ivf->kind == NMN_IVF_FLAT;
@@ -2030,34 +1954,26 @@ extern "C" nmn_status nmn_ivf_search_device(nmn_ivf* ivf, const float* queries_d
     }
     if (codec_seg_bytes() != sizeof(uint4)) return set_error(NMN_ERR_STORAGE, "IVF: segment layout mismatch");
     const uint32_t ld = ivf->centroids->ld;
-    const size_t c_pad = ivf->centroids->cap_pad;
     const bool big_c = C > kRankMax;  // (the large-k sort ranks the centroids, one query at a time)
     constexpr uint64_t kScoreBudget = 64ull << 20;  // candidates' scores per chunk (256 MiB)
     uint32_t chunk = big_c ? 1u : std::min<uint32_t>(nq, 64);
     chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(chunk, kScoreBudget / bound));
     const uint32_t Kt = std::min<uint32_t>(ivf->pq_k, 256), W = (dim + 63) / 64;
-    DevGrow grow_s{s};
-    grow_s(sc->qpad, (size_t)ld * chunk * 4);
-    grow_s(sc->qinfo, sizeof(QInfo) * chunk);
-    grow_s(sc->qstate, sizeof(QState) * chunk);
-    grow_s(sc->cscores, c_pad * chunk * 4);
-    grow_s(sc->probe_rows, (size_t)C * chunk * 8);
-    grow_s(sc->probe_rank, (size_t)C * chunk * 4);
-    grow_s(sc->probe_count, (size_t)chunk * 8);
-    if (big_c) {
-        grow_s(sc->ckeys, largek_sort_len(C) * 8);
-        grow_s(sc->probe_scores, (size_t)C * 4);
-    }
-    grow_s(sc->segs, (size_t)chunk * np * sizeof(uint4));
-    grow_s(sc->base, (size_t)chunk * 8);
-    grow_s(sc->totals, (size_t)chunk * 8);
-    grow_s(sc->scores, (size_t)chunk * bound * 4);
-    if (k > kSelMax) grow_s(sc->keys, largek_sort_len(bound) * 8);
-    if (ivf->kind == NMN_IVF_PQ) grow_s(sc->tables, (size_t)chunk * np * ivf->pq_m * Kt * 4);
-    if (ivf->kind == NMN_IVF_BINARY) grow_s(sc->qwords, (size_t)chunk * W * 8);
-    if (grow_s.e != hipSuccess) return set_error_hip(grow_s.e, "nmn_ivf_search_device (scratch)");
-    const bool raw_q = ld == dim && C < (1u << 16);  // (as the host call: the raw queries ARE the padded ones)
-    if (raw_q && grow_s.synced) IVF_TRY(hipMemsetAsync(sc->qinfo.p, 0, sc->qinfo.cap, s));  // (fresh buffer: exact_scan reads qmag)
+    // grow-only scratch of this stream's device searches: a buffer that must grow waits for the stream first (the calls before this
+    // one may still read it) — the only wait of the pipeline, at most one per call, never in steady state
+    bool wait = true;
+    hipError_t ge = sc->rank.reserve(ivf, chunk, false, s, wait);
+    auto need = [&](Grow& g, size_t bytes) {
+        if (ge == hipSuccess) ge = g.reserve(bytes, s, wait);
+    };
+    need(sc->segs, (size_t)chunk * np * sizeof(uint4));
+    need(sc->base, (size_t)chunk * 8);
+    need(sc->totals, (size_t)chunk * 8);
+    need(sc->scores, (size_t)chunk * bound * 4);
+    if (k > kSelMax) need(sc->keys, largek_sort_len(bound) * 8);
+    if (ivf->kind == NMN_IVF_PQ) need(sc->tables, (size_t)chunk * np * ivf->pq_m * Kt * 4);
+    if (ivf->kind == NMN_IVF_BINARY) need(sc->qwords, (size_t)chunk * W * 8);
+    if (ge != hipSuccess) return set_error_hip(ge, "nmn_ivf_search_device (scratch)");
     auto* segs = gp<uint4>(sc->segs);
     for (uint32_t q0 = 0; q0 < nq; q0 += chunk) {
         const uint32_t nb = std::min<uint32_t>(chunk, nq - q0);
@@ -2065,34 +1981,11 @@ extern "C" nmn_status nmn_ivf_search_device(nmn_ivf* ivf, const float* queries_d
         uint64_t* o_ids = out_ids_dev + (size_t)q0 * k;
         float* o_dist = out_distances_dev + (size_t)q0 * k;
         uint32_t* o_cnt = out_counts_dev + q0;
-        // 1. centroid ranking, exactly the host call's
-        if (!raw_q)
-            IVF_TRY(launch_qprep(qg, nb, dim, ld, kMetricNegL2Sq, ivf->centroids->max_norm_bits, gp<float>(sc->qpad), gp<QInfo>(sc->qinfo),
-                                 gp<QState>(sc->qstate), 0, s));
-        ExactScanParams ep{};
-        ep.corpus = ivf->centroids->corpus;
-        ep.norms = ivf->centroids->norms;
-        ep.qpad = raw_q ? qg : gp<float>(sc->qpad);
-        ep.qinfo = gp<QInfo>(sc->qinfo);
-        ep.scores = gp<uint32_t>(sc->cscores);
-        ep.n_rows = C;
-        ep.nql = nb;
-        ep.ld = ld;
-        ep.dim = dim;
-        ep.nq = nb;
-        ep.metric = kMetricNegL2Sq;
-        IVF_TRY(launch_exact_scan(ep, s));
-        if (!big_c) {
-            uint32_t np2 = 2;
-            while (np2 < C) np2 <<= 1;
-            hipLaunchKernelGGL(ivf_rank_kernel, dim3(nb), dim3(1024), 0, s, gp<uint32_t>(sc->cscores), nb, C, np2, np,
-                               gp<uint64_t>(sc->probe_rows), gp<uint32_t>(sc->probe_count), gp<uint32_t>(sc->probe_rank));
-        } else {
-            IVF_TRY(launch_largek(gp<uint32_t>(sc->cscores), C, gp<uint64_t>(sc->ckeys), np, 0, gp<uint64_t>(sc->probe_rows),
-                                  gp<float>(sc->probe_scores), gp<uint32_t>(sc->probe_count), s));
-        }
+        // 1. centroid ranking, the host call's
+        nmn_status st = rank_centroids(ivf, qg, nb, np, sc->rank, false, s);
+        if (st != NMN_OK) return st;
         // 2. candidate plan
-        hipLaunchKernelGGL(ivf_plan_kernel, dim3(nb), dim3(64), 0, s, gp<uint64_t>(sc->probe_rows), C, gp<uint32_t>(sc->probe_count), np, C,
+        hipLaunchKernelGGL(ivf_plan_kernel, dim3(nb), dim3(64), 0, s, gp<uint64_t>(sc->rank.probe_rows), C, gp<uint32_t>(sc->rank.probe_count), np, C,
                            off, bound, segs, gp<uint64_t>(sc->totals), gp<uint64_t>(sc->base));
         IVF_TRY(hipGetLastError());
         // 3. scores of every candidate, in candidate order
@@ -2154,26 +2047,21 @@ extern "C" uint64_t nmn_ivf_hbm_bytes(nmn_ivf* ivf) {
     if (!ivf) return 0;
     std::unique_lock<std::shared_mutex> g(ivf->rw);
     uint64_t b = index_hbm_bytes(ivf->vectors) + index_hbm_bytes(ivf->cvec) + index_hbm_bytes(ivf->centroids);
-    if (ivf->kind == NMN_IVF_FLAT) {
-        b += ivf->cap * 4 + ((ivf->cap + 63) / 64 + 1) * 8 + (ivf->list_off ? ((uint64_t)ivf->n_clusters + 1) * 4 : 0);
-        for (auto& sl : ivf->slots) b += ((ivf->cap + 63) / 64 + 1) * 16 * sl->nb;  // probe bitmaps
-    } else {
-        b += std::max<uint64_t>(ivf->cap, 1) * ivf->code_bytes + ivf->codebook_host.size() * 4;
-        for (const nmn_ivf::Grow* gr : {&ivf->cs_qraw, &ivf->cs_qpad, &ivf->cs_qinfo, &ivf->cs_qstate, &ivf->cs_cscores, &ivf->cs_ckeys,
-                                        &ivf->cs_probe_rows, &ivf->cs_probe_scores, &ivf->cs_probe_count, &ivf->cs_segs, &ivf->cs_base,
-                                        &ivf->cs_tables, &ivf->cs_qwords, &ivf->cs_scores, &ivf->cs_keys, &ivf->cs_rows, &ivf->cs_rscores,
-                                        &ivf->cs_rcnt})
-            b += gr->cap;
-    }
-    b += ivf->cscores_cap * 4 + largek_sort_len(ivf->n_clusters) * 8;  // the assignment sweep's scores, the ranking's sort buffer
+    if (ivf->kind == NMN_IVF_FLAT)  // the list of every row; the list-major copy's offsets
+        b += std::max<uint64_t>(ivf->cap, 1) * 4 + (ivf->list_off ? ((uint64_t)ivf->n_clusters + 1) * 4 : 0);
+    else  // the codes, the codebook (and the 64 bytes `assign` is without rows of its own)
+        b += std::max<uint64_t>(ivf->cap, 1) * ivf->code_bytes + ivf->codebook_host.size() * 4 + 64;
+    b += ivf->cscores_cap * 4 + sizeof(QInfo) * kAssignChunk;  // the assignment sweep's scores and its zero query records
+    // the search scratch: what nmn_ivf_destroy frees, through the same enumerators
+    auto count = [&](const Grow& g) {
+        if (!g.pinned) b += g.cap;
+    };
+    for (auto& sl : ivf->slots) sl->for_each(count);
+    ivf->cs.for_each(count);
     {   // what device searches added: the candidate-order id map and the per-stream scratch (nothing before the first one)
         std::lock_guard<std::mutex> lk(ivf->dev_mu);
         if (ivf->dev_perm) b += std::max<uint64_t>(ivf->dev_rows, 1) * 4 + ((uint64_t)ivf->n_clusters + 1) * 4;
-        for (auto& sc : ivf->dev_scratch)
-            for (const nmn_ivf::Grow* gr : {&sc->qpad, &sc->qinfo, &sc->qstate, &sc->cscores, &sc->ckeys, &sc->probe_rows, &sc->probe_scores,
-                                            &sc->probe_rank, &sc->probe_count, &sc->segs, &sc->base, &sc->totals, &sc->scores, &sc->keys,
-                                            &sc->tables, &sc->qwords})
-                b += gr->cap;
+        for (auto& sc : ivf->dev_scratch) sc->for_each(count);
     }
     return b;
 }

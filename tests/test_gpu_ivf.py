@@ -409,3 +409,67 @@ def test_list_major_copy_after_build_and_after_load(tmp_path):
         flat.upload(V)
         rows, scores, counts = flat.search(Q, 30, 1)
         assert np.array_equal(rows, ex[0])
+
+
+# ---- the ranking of more than 4096 centroids (the large-k sort instead of the one-workgroup ranking) ------------------------
+@pytest.fixture(scope="module")
+def many_centroids():
+    """4,100 centroids x 8 set directly (no training), 6,000 rows, 3 queries, and both oracles filled once (read only)."""
+    from tests import _ivf_codec_oracle as co
+    from tests.test_gpu_ivf_device import data
+    cents, V, Q = data(4100, 8, seed=18), data(6000, 8, seed=17), data(3, 8, seed=19)
+    flat = io.IVFFlat(len(cents), nprobe=16)
+    flat.centroids = cents
+    flat.lists = [[] for _ in cents]
+    binary = co.IVFCoded(len(cents), "binary", threshold="sign", nprobe=16)
+    binary.set_trained(cents)
+    assign = binary.add_rows(V).tolist()
+    for v, c in zip(V, assign):               # (IVFFlat.add with the nearest centroid already known: the same first minimum)
+        flat.lists[c].append(len(flat.vectors))
+        flat.vectors.append(v)
+        flat.assign.append(c)
+    return cents, V, Q, {"flat": flat, "binary": binary}
+
+
+@pytest.mark.parametrize("kind", ["flat", "binary"])
+def test_more_than_4096_centroids_match_oracle(many_centroids, kind):
+    """Above 4,096 centroids the probe order comes from the large-k sort, one query at a time.  Host and device search are
+    held to the numpy oracle here (squared distance ascending, ties by centroid index), not to each other: ids, counts and
+    distance bits, for one probe, a few, and every list; k below and above the one-workgroup selection."""
+    import torch
+    from neumann_amd.ivf import GpuIvfBinary, GpuIvfFlat
+    from tests.test_gpu_ivf_device import dev, host
+    cents, V, Q, oracles = many_centroids
+    orc = oracles[kind]
+    gpu = GpuIvfFlat(cents, capacity_rows=6000, nprobe=16) if kind == "flat" else GpuIvfBinary(cents, capacity_rows=6000, nprobe=16)
+    with gpu:
+        assert gpu.add(V).tolist() == list(orc.assign)
+        for nprobe in (1, 16, 4100):
+            for k in (10, 5000):
+                want = [orc.search(q, k, nprobe) for q in Q]
+                got_dev = gpu.search_device(dev(Q), k, nprobe)
+                torch.cuda.synchronize()
+                for name, (ids, dist, counts) in (("search", gpu.search(Q, k, nprobe)), ("search_device", host(got_dev))):
+                    for i, (eids, ed) in enumerate(want):
+                        where = (name, nprobe, k, i)
+                        assert counts[i] == len(eids), where
+                        assert ids[i, :len(eids)].tolist() == eids, where
+                        assert np.array_equal(dist[i, :len(eids)].view(np.uint32), np.asarray(ed, F).view(np.uint32)), where
+                        assert np.all(ids[i, len(eids):] == np.uint64(0xFFFFFFFFFFFFFFFF)), where
+                        assert np.all(np.isposinf(dist[i, len(eids):])), where
+
+
+def test_hbm_bytes_is_what_destroy_frees():
+    """Two fresh IVF-Flat indexes (16 dimensions, never searched) whose capacities differ by 64 x 1,024 rows: hbm_bytes differs by
+    the members that grow with the capacity and exist — the list assignment (4 bytes a row) and the flat index of the vectors —
+    and by nothing else.  (The value changed with the removal of the per-index selection bitmap nobody read: until then the
+    difference held another 8 x 1,024 bytes, one bit a row.)"""
+    from neumann_amd import GpuFlatIndex
+    from neumann_amd.ivf import GpuIvfFlat
+    from tests.test_gpu_ivf_device import data
+    cents = data(8, 16, seed=40)
+    more = 64 * 1024
+    with GpuIvfFlat(cents, capacity_rows=4096) as a, GpuIvfFlat(cents, capacity_rows=4096 + more) as b:
+        va, vb = (sum(GpuFlatIndex._view(g._lib.nmn_ivf_vectors(g._h), g).hbm_bytes()) for g in (a, b))
+        assert vb > va
+        assert b.hbm_bytes - a.hbm_bytes == more * 4 + (vb - va)

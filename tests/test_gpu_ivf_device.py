@@ -400,3 +400,44 @@ def test_hbm_bytes_grow_only_once_device_searched(kind):
         a.search_device(dev(data(2, 32, seed=36)), 10)
         torch.cuda.synchronize()
         assert a.hbm_bytes >= b.hbm_bytes + 6000 * 4
+
+
+@pytest.mark.parametrize("storage,d", [("flat", 1), ("flat", 17), ("binary", 1), ("binary", 17), ("pq", 4), ("pq", 20)])
+def test_padded_stride_matches_oracle(storage, d):
+    """A row stride different from the dimension: the queries go through the padding kernel before the centroid sweep, on the
+    host call and on the device call of every storage.  Both against the oracles.  (d: the smallest dimension the storage takes
+    here — PQ: two subspaces of two — and one whose padded row spans several 8-element groups.)"""
+    import torch
+    from neumann_amd import GpuFlatIndex
+    from neumann_amd.ivf import GpuIvfBinary, GpuIvfFlat, GpuIvfPQ
+    with GpuFlatIndex(d, 8) as probe:          # the stride every index of this dimension gets (centroids and vectors alike)
+        assert probe.row_stride != d
+    V = data(400, d, seed=37)
+    km = co.KMeansConfig(**FAST)
+    if storage == "flat":
+        orc = io.IVFFlat(8, nprobe=3, kmeans=io.KMeansConfig(**FAST))
+        orc.train(V)
+        gpu = GpuIvfFlat(orc.centroids, capacity_rows=500, nprobe=3)
+    elif storage == "pq":
+        M = 2 if d == 4 else 4
+        orc = co.IVFCoded(8, "pq", pq_config=co.PQConfig(M, 16, km), nprobe=3, kmeans=km)
+        orc.train(V)
+        gpu = GpuIvfPQ(orc.centroids, orc.codebook.centroids, capacity_rows=500, num_subspaces=M, nprobe=3)
+    else:
+        orc = co.IVFCoded(8, "binary", threshold="mean", nprobe=3, kmeans=km)
+        orc.train(V)
+        gpu = GpuIvfBinary(orc.centroids, capacity_rows=500, threshold="mean", nprobe=3)
+    with gpu:
+        if storage == "flat":
+            assert GpuFlatIndex._view(gpu._lib.nmn_ivf_vectors(gpu._h), gpu).row_stride != d
+        gpu.add(V)
+        for v in V:
+            orc.add(v)
+        Q = data(5, d, seed=38)
+        got_dev = gpu.search_device(dev(Q), 30)
+        torch.cuda.synchronize()
+        for name, (ids, dist, counts) in (("search", gpu.search(Q, 30)), ("search_device", host(got_dev))):
+            for i, q in enumerate(Q):
+                eids, ed = orc.search(q, 30)
+                assert counts[i] == len(eids) and ids[i, :len(eids)].tolist() == eids, (name, i)
+                assert np.array_equal(dist[i, :len(eids)].view(np.uint32), np.asarray(ed, F).view(np.uint32)), (name, i)
