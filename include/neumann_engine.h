@@ -339,6 +339,15 @@ nmn_strlist* nmn_engine_load_all_indices(nmn_engine* e, const char* dir, nmn_sta
  * without k-means (the reference rebuilds: lib.rs:2641-2694).  IVF-Flat only (PQ / Binary: NMN_ERR_CONFIGURATION). */
 nmn_status nmn_engine_ivf_save(nmn_engine_ivf* ivf, const char* path);
 nmn_status nmn_engine_ivf_load(nmn_engine* e, const char* path, nmn_engine_ivf** out);
+/* The (HNSWIndex, key_mapping) pair of build_hnsw_index / build_hnsw_index_with_options, persisted: header {kind = engine,
+ * flags = 2, rows = keys, aux = text bytes} | {"dim", "built", "keys"} | when built, the HNSW file of nmn_hnsw_save (docs/hnsw.md
+ * §10); an index built from an empty engine has "built": false and no section.  The load honours max_index_file_bytes /
+ * max_index_entries (NMN_ERR_CONFIGURATION, the reference's texts), checks that key count, node count and dim agree, and uses the
+ * engine's device; a damaged file is NMN_ERR_SERIALIZATION.  A loaded handle has no build-time relation to the engine's
+ * collection: nmn_engine_search_with_hnsw_and_metric on it always gathers the CURRENT vectors of the candidates' keys (the
+ * reference's semantics), never the fast path of a handle built in this process. */
+nmn_status nmn_engine_hnsw_save(nmn_engine_hnsw* h, const char* path);
+nmn_status nmn_engine_hnsw_load(nmn_engine* e, const char* path, nmn_engine_hnsw** out);
 
 /* count_matching / estimate_filter_selectivity (lib.rs:3698-3722) */
 uint64_t nmn_engine_count_matching(nmn_engine* e, const nmn_filter* f);

@@ -587,7 +587,8 @@ uint64_t nmn_ivf_hbm_bytes(nmn_ivf* ivf);
  * sequential by definition of its result; the reference's is too) and is resident in HBM: layer 0 as n x m0 u32 slots and a
  * count per node, the upper layers as a compact n_upper x max_layer x m table with a row index per node.  Node id == row of
  * the flat index the handle owns (nmn_hnsw_vectors).  Answers are the reference's bit for bit, ties included: both priority
- * queues of search_layer are kept as the array algorithm of std::collections::BinaryHeap (docs/hnsw.md). */
+ * queues of search_layer are kept as the array algorithm of std::collections::BinaryHeap (docs/hnsw.md).  nmn_hnsw_save /
+ * nmn_hnsw_load (index persistence, below) keep a built graph across restarts. */
 typedef struct nmn_hnsw nmn_hnsw;
 
 /* HNSWStorageStrategy (vector_engine/src/lib.rs:833-846).  Dense and Quantized are served, Auto (sparse storage) is refused
@@ -687,6 +688,8 @@ typedef struct nmn_hnsw_memstats {
     uint64_t embedding_bytes;
 } nmn_hnsw_memstats;
 nmn_status nmn_hnsw_memory_stats(nmn_hnsw* h, nmn_hnsw_memstats* out);
+/* The handle's HNSWConfig; `storage` = the handle's strategy (nmn_hnsw_storage), `reserved` 0.  What nmn_hnsw_load read from a file. */
+nmn_status nmn_hnsw_get_config(const nmn_hnsw* h, nmn_hnsw_config* out);
 
 /* ---- extended distance metrics: the re-rank of search_with_hnsw_and_metric ------------------------------------ */
 
@@ -769,6 +772,27 @@ nmn_status nmn_index_load(const char* path, const nmn_index_desc* overrides, uin
 nmn_status nmn_ivf_save(nmn_ivf* ivf, const char* path);
 nmn_status nmn_ivf_load(const char* path, const nmn_index_desc* overrides, uint64_t max_file_bytes, uint64_t max_entries,
                         nmn_ivf** out);
+/* The same for an HNSW index, the most expensive one to build (nmn_hnsw_insert is one host thread by definition of its result).
+ * The reference does not serialise HNSWIndex (tensor_store/src/hnsw.rs derives serde for the metric, ScalarQuantizedVector and
+ * HNSWConfig only), so the format is this library's own; docs/hnsw.md §10 is its specification.  File: 64-byte header (kind 4,
+ * flags bit 0 = quantized, rows = nodes, aux = bytes of the graph section, reserved = its FNV-1a 64) | graph section (the 48
+ * bytes of nmn_hnsw_config, the level generator's state, entry point, max_layer, levels, every neighbour list) | rows (dense: a
+ * flat section as nmn_index_save writes it; quantized: n x dim codes, n x {scale, min_val, magnitude, squared_magnitude}).
+ * A loaded handle is indistinguishable from the one saved: same graph, same ids and score bits from every search entry, and
+ * nmn_hnsw_insert continues exactly where the saved handle would have (levels, lists and generator state come back).  The heap
+ * capacities of nmn_hnsw_set_heap_capacity are a run-time knob and are not stored.
+ *   save   takes the handle's lock shared: searches may run, inserts wait.  Host state only, no device traffic, no kernel.
+ *   load   no kernel of its own either: sequential reads, host checks, bulk copies.  EVERY check runs on the host before any
+ *          allocation sized by an unchecked number and before anything reaches the search kernel: sizes against the bytes in the
+ *          file, the checksum, the config, levels / entry point / max_layer, and of every list its count (<= m0 / m), ids (< n,
+ *          strictly ascending) and that every id listed on layer L >= 1 has level >= L; the rows' magnitudes recomputed on the
+ *          host (and, dense, on the device) must equal the stored bits.  A missing file is NMN_ERR_IO, the two limits are
+ *          nmn_index_load's (NMN_ERR_CONFIGURATION, the same texts), anything else wrong with a file NMN_ERR_SERIALIZATION with
+ *          a text that names the first failed check.  Files of the other kinds are refused, and nmn_index_load / nmn_ivf_load
+ *          refuse an HNSW file.  capacity_hint sizes the row arrays as in nmn_hnsw_create (at least the file's nodes). */
+nmn_status nmn_hnsw_save(nmn_hnsw* h, const char* path);
+nmn_status nmn_hnsw_load(const char* path, int32_t device, uint64_t capacity_hint, uint64_t max_file_bytes, uint64_t max_entries,
+                         nmn_hnsw** out);
 
 /* ---- synthetic data (bench / tests) ------------------------------------------------------- */
 

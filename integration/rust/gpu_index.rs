@@ -252,3 +252,76 @@ impl Drop for GpuShardedIndex {
         unsafe { ffi::nmn_sharded_destroy(self.raw) };
     }
 }
+
+/// `tensor_store::HNSWIndex` built on the host in the reference's order and searched on the GPU (nmn_hnsw_*), with the one thing
+/// the reference's index lacks: it can be saved and loaded (docs/hnsw.md §10), so the sequential build is paid once.
+pub struct GpuHnswIndex {
+    raw: *mut ffi::nmn_hnsw,
+    dim: usize,
+}
+unsafe impl Send for GpuHnswIndex {}
+unsafe impl Sync for GpuHnswIndex {}
+
+impl GpuHnswIndex {
+    pub fn with_config(dim: usize, cfg: &ffi::nmn_hnsw_config, storage: i32, capacity_hint: usize, device: i32) -> Result<Self> {
+        let mut raw = std::ptr::null_mut();
+        let st = unsafe { ffi::nmn_hnsw_create_with_storage(cfg, storage, dim as u32, capacity_hint as u64, device, &mut raw) };
+        check(st, dim, dim)?;
+        Ok(Self { raw, dim })
+    }
+
+    pub fn len(&self) -> usize {
+        unsafe { ffi::nmn_hnsw_len(self.raw) as usize }
+    }
+
+    /// HNSWIndex::insert for every row in order; the node ids are len() .. len() + n.
+    pub fn insert(&self, rows: &[f32]) -> Result<()> {
+        let n = (rows.len() / self.dim.max(1)) as u64;
+        check(unsafe { ffi::nmn_hnsw_insert(self.raw, rows.as_ptr(), n, std::ptr::null_mut()) }, self.dim, self.dim)
+    }
+
+    /// HNSWIndex::search: (node id, to_similarity(distance)), best first.
+    pub fn search(&self, q: &[f32], k: usize) -> Result<Vec<(usize, f32)>> {
+        if q.len() != self.dim {
+            return Err(VectorError::DimensionMismatch { expected: self.dim, got: q.len() });
+        }
+        let mut ids = vec![u64::MAX; k];
+        let mut scores = vec![f32::NEG_INFINITY; k];
+        let mut n = 0u32;
+        let st = unsafe {
+            ffi::nmn_hnsw_search(self.raw, q.as_ptr(), 1, k as u32, 0, ids.as_mut_ptr(), scores.as_mut_ptr(), &mut n, std::ptr::null_mut())
+        };
+        check(st, self.dim, q.len())?;
+        Ok(ids.into_iter().zip(scores).take(n as usize).map(|(r, s)| (r as usize, s)).collect())
+    }
+
+    /// The handle's HNSWConfig; after `load`, the file's.
+    pub fn config(&self) -> Result<ffi::nmn_hnsw_config> {
+        let mut c = std::mem::MaybeUninit::<ffi::nmn_hnsw_config>::zeroed();
+        check(unsafe { ffi::nmn_hnsw_get_config(self.raw, c.as_mut_ptr()) }, self.dim, self.dim)?;
+        Ok(unsafe { c.assume_init() })
+    }
+
+    /// Graph, level generator state and rows (nmn_hnsw_save).  Searches may run meanwhile, inserts wait.
+    pub fn save(&self, path: &Path) -> Result<()> {
+        let p = c_path(path)?;
+        check(unsafe { ffi::nmn_hnsw_save(self.raw, p.as_ptr()) }, self.dim, self.dim)
+    }
+
+    /// No build: the index comes back as saved (same answers, and `insert` continues where the saved index would have).  Every
+    /// index of the file is checked on the host first; a damaged file is a SerializationError.  `max_file_bytes` /
+    /// `max_entries` as for `GpuFlatIndex::load`.
+    pub fn load(path: &Path, device: i32, capacity_hint: usize, max_file_bytes: u64, max_entries: u64) -> Result<Self> {
+        let p = c_path(path)?;
+        let mut raw = std::ptr::null_mut();
+        check(unsafe { ffi::nmn_hnsw_load(p.as_ptr(), device, capacity_hint as u64, max_file_bytes, max_entries, &mut raw) }, 0, 0)?;
+        let dim = unsafe { ffi::nmn_hnsw_dim(raw) } as usize;
+        Ok(Self { raw, dim })
+    }
+}
+
+impl Drop for GpuHnswIndex {
+    fn drop(&mut self) {
+        unsafe { ffi::nmn_hnsw_destroy(self.raw) };
+    }
+}

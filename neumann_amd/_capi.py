@@ -231,6 +231,7 @@ SIGNATURES = {
     "nmn_hnsw_quantized_row": (C.c_int32, [vp, C.c_uint64, vp, f32p, f32p]),
     "nmn_hnsw_get_vector": (C.c_int32, [vp, C.c_uint64, vp]),
     "nmn_hnsw_memory_stats": (C.c_int32, [vp, C.POINTER(HnswMemStats)]),
+    "nmn_hnsw_get_config": (C.c_int32, [vp, C.POINTER(HnswConfig)]),
     "nmn_xmetric_geometric_default": (None, [C.POINTER(XMetric)]),
     "nmn_xmetric_geometric_angular_heavy": (None, [C.POINTER(XMetric)]),
     "nmn_xmetric_geometric_structural_heavy": (None, [C.POINTER(XMetric)]),
@@ -246,6 +247,8 @@ SIGNATURES = {
     "nmn_index_load": (C.c_int32, [C.c_char_p, C.POINTER(IndexDesc), C.c_uint64, C.c_uint64, C.POINTER(vp)]),
     "nmn_ivf_save": (C.c_int32, [vp, C.c_char_p]),
     "nmn_ivf_load": (C.c_int32, [C.c_char_p, C.POINTER(IndexDesc), C.c_uint64, C.c_uint64, C.POINTER(vp)]),
+    "nmn_hnsw_save": (C.c_int32, [vp, C.c_char_p]),
+    "nmn_hnsw_load": (C.c_int32, [C.c_char_p, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(vp)]),
     "nmn_sharded_create": (C.c_int32, [C.POINTER(ShardedDesc), C.POINTER(vp)]),
     "nmn_sharded_destroy": (C.c_int32, [vp]),
     "nmn_sharded_upload": (C.c_int32, [vp, vp, C.c_uint64, C.c_uint64]),

@@ -3392,4 +3392,79 @@ nmn_status nmn_engine_ivf_load(nmn_engine* e, const char* path, nmn_engine_ivf**
     return NMN_OK;
 }
 
+// (HNSWIndex, key_mapping) of build_hnsw_index(_with_options), persisted: Header{kind = engine, flags = 2, aux = text bytes} |
+// {"dim", "built", "keys"} | when built, the HNSW file (docs/hnsw.md §10) — a restart restores the graph without the sequential build
+nmn_status nmn_engine_hnsw_save(nmn_engine_hnsw* hn, const char* path) {
+    if (!hn || !path) return fail(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    std::string o = "{\"dim\": " + std::to_string(hn->dim) + ", \"built\": " + (hn->index ? "true" : "false") + ", \"keys\": [";
+    for (size_t i = 0; i < hn->keys.size(); i++) {
+        if (i) o += ", ";
+        json_str(o, hn->keys[i]);
+    }
+    o += "]}";
+    FILE* fp = fopen(path, "wb");
+    if (!fp) return err_io(std::string("cannot create '") + path + "': " + strerror(errno));
+    nmn::PersistHeader h{};
+    memcpy(h.magic, "NMNIDX\0\1", 8);
+    h.version = 1;
+    h.kind = nmn::kPersistEngine;
+    h.rows = hn->keys.size();
+    h.aux = o.size();
+    h.flags = 2;  // an HNSW index follows
+    nmn_status st = NMN_OK;
+    if (fwrite(&h, sizeof h, 1, fp) != 1 || fwrite(o.data(), 1, o.size(), fp) != o.size()) st = err_io(std::string("cannot write '") + path + "'");
+    if (st == NMN_OK && hn->index && nmn::persist_write_hnsw(hn->index, fp, path) != NMN_OK) st = err_gpu(NMN_ERR_STORAGE);
+    if (fclose(fp) != 0 && st == NMN_OK) st = err_io(std::string("cannot close '") + path + "'");
+    return st;
+}
+
+nmn_status nmn_engine_hnsw_load(nmn_engine* e, const char* path, nmn_engine_hnsw** out) {
+    if (!e || !path || !out) return fail(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    *out = nullptr;
+    nmn_status st = check_file_limit(e, path);
+    if (st != NMN_OK) return st;
+    FILE* fp = fopen(path, "rb");
+    if (!fp) return err_io(std::string("cannot open '") + path + "': " + strerror(errno));
+    struct Closer {
+        FILE* f;
+        ~Closer() { fclose(f); }
+    } closer{fp};
+    nmn::PersistHeader h{};
+    if (nmn::persist_read_header(fp, path, &h) != NMN_OK || h.kind != nmn::kPersistEngine || h.flags != 2)
+        return err_serialization("not a neumann_gpu HNSW index file");
+    st = check_entry_limit(e, h.rows);
+    if (st != NMN_OK) return st;
+    if (h.aux > (1ull << 40) || h.aux > nmn::persist_bytes_left(fp)) return err_serialization("file truncated (text block)");
+    std::string text((size_t)h.aux, '\0');
+    if (h.aux && fread(&text[0], 1, (size_t)h.aux, fp) != h.aux) return err_serialization("file truncated (text block)");
+    JVal root;
+    JParser jp(text.data(), text.size());
+    if (!jp.value(&root, 0) || root.t != JVal::Obj) return err_serialization(jp.err.empty() ? "invalid text block" : jp.err);
+    const JVal* jd = root.get("dim");
+    const JVal* jb = root.get("built");
+    const JVal* jk = root.get("keys");
+    if (!jd || !jd->is_int || jd->i < 0 || !jb || jb->t != JVal::Bool || !jk || jk->t != JVal::Arr || !jk->nums.empty())
+        return err_serialization("invalid text block");
+    auto res = std::make_unique<nmn_engine_hnsw>();
+    res->dim = (uint64_t)jd->i;
+    res->writes_at_build = UINT64_MAX;  // never the collection's counter: the handle's rows are not known to be its current vectors
+    for (auto& k : jk->arr) {
+        if (k.t != JVal::Str) return err_serialization("invalid key");
+        res->keys.push_back(k.s);
+    }
+    if (res->keys.size() != h.rows) return err_serialization("key count differs from the header");
+    if (jb->b) {
+        nmn::PersistHeader hi{};
+        if (nmn::persist_read_header(fp, path, &hi) != NMN_OK) return err_serialization(nmn_last_error());
+        st = nmn::persist_read_hnsw(fp, path, hi, e->cfg.device, 0, &res->index);
+        if (st == NMN_ERR_SERIALIZATION) return err_serialization(nmn_last_error());
+        if (st != NMN_OK) return err_gpu(st);
+        if (nmn_hnsw_len(res->index) != res->keys.size() || hi.dim != res->dim) return err_serialization("HNSW section does not match the keys");
+    } else if (!res->keys.empty() || nmn::persist_bytes_left(fp) != 0) {
+        return err_serialization("an index that was never built carries keys or a section");
+    }
+    *out = res.release();
+    return NMN_OK;
+}
+
 }  // extern "C"

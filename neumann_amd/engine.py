@@ -167,6 +167,8 @@ ENGINE_SIGNATURES = {
     "nmn_engine_load_all_indices": (vp, [vp, C.c_char_p, C.POINTER(C.c_int32)]),
     "nmn_engine_ivf_save": (C.c_int32, [vp, C.c_char_p]),
     "nmn_engine_ivf_load": (C.c_int32, [vp, C.c_char_p, C.POINTER(vp)]),
+    "nmn_engine_hnsw_save": (C.c_int32, [vp, C.c_char_p]),
+    "nmn_engine_hnsw_load": (C.c_int32, [vp, C.c_char_p, C.POINTER(vp)]),
 }
 
 _bound = False
@@ -866,6 +868,23 @@ class VectorEngine:
         h = vp()
         _check(_lib().nmn_engine_ivf_load(self._h, str(path).encode(), C.byref(h)))
         index = IVFIndex(h)
+        return index, index.keys
+
+    def save_hnsw_index(self, index, path):
+        """The (HNSWIndex, key_mapping) pair with its graph, rows and level generator state: restored without the build."""
+        _check(_lib().nmn_engine_hnsw_save(index._h, str(path).encode()))
+
+    def load_hnsw_index(self, path):
+        """-> (HNSWIndex, key_mapping); max_index_file_bytes / max_index_entries apply.  search_with_hnsw_and_metric on a loaded
+        index always re-ranks the CURRENT vectors of the candidates' keys (the reference's semantics)."""
+        from .hnsw import HNSWConfig
+        h = vp()
+        _check(_lib().nmn_engine_hnsw_load(self._h, str(path).encode(), C.byref(h)))
+        index = HNSWIndex(h, HNSWConfig())
+        g = index.gpu()
+        if g is not None:  # the file's config
+            g._adopt_config()
+            index.config = g.config
         return index, index.keys
 
     def build_ivf_index_default(self):

@@ -128,6 +128,33 @@ class GpuHnsw:
                                                                int(device), C.byref(h)))
         self._h = h
 
+    def save(self, path):
+        """Graph, level generator state and rows -> `path` (nmn_hnsw_save; the format is docs/hnsw.md §10).  Searches may run
+        meanwhile, inserts wait."""
+        _capi.check(self._lib.nmn_hnsw_save(self._h, str(path).encode()))
+
+    @classmethod
+    def load(cls, path, device=-1, capacity_hint=0, max_file_bytes=0, max_entries=0):
+        """nmn_hnsw_load: no build — graph, rows and generator state come back exactly as saved, so searches answer the same bits
+        and `insert` continues where the saved index would have.  `config`, `dim` and `storage` are the file's.  Every index of
+        the file is checked on the host before anything reaches the GPU; a damaged file is ERR_SERIALIZATION."""
+        lib = _capi.load()
+        h = C.c_void_p()
+        _capi.check(lib.nmn_hnsw_load(str(path).encode(), int(device), int(capacity_hint), int(max_file_bytes), int(max_entries),
+                                      C.byref(h)))
+        g = cls.__new__(cls)
+        g._lib, g._h = lib, h
+        g._adopt_config()
+        return g
+
+    def _adopt_config(self):
+        """config and dim as the handle holds them (nmn_hnsw_get_config)"""
+        c = _capi.HnswConfig()
+        _capi.check(self._lib.nmn_hnsw_get_config(self._h, C.byref(c)))
+        self.config = HNSWConfig._from_c(c)
+        self.config.storage = {v: k for k, v in _STORAGE.items()}[int(c.storage)]
+        self.dim = int(self._lib.nmn_hnsw_dim(self._h))
+
     def close(self):
         if getattr(self, "_h", None):
             self._lib.nmn_hnsw_destroy(self._h)

@@ -33,7 +33,14 @@ builds the corpus twice — a quantized handle (HNSWStorageStrategy::Quantized, 
 quantized walk beside the dense walk OF THE SAME RUN, the two alternating call by call: nmn_hnsw_search_device under HIP events at
 1 / 64 / 1024 queries per call and a lone host-buffer nmn_hnsw_search call, ef 50 and 200, medians of --calls, spread over
 --repeats.  It prints both handles' hbm_bytes, build times, evaluations per query and recall@10 of each against the exhaustive
-search over the f32 rows, and checks that the quantized handle's device, host-buffer and host-walk answers are the same bits."""
+search over the f32 rows, and checks that the quantized handle's device, host-buffer and host-walk answers are the same bits.
+
+  python tools/hnsw_bench.py --rows 1000000 --dim 128 --index-file /data/hnsw_1m_128.idx
+With --index-file the run stops paying for builds (docs/hnsw.md §10): when PATH exists the handle is GpuHnsw.load(PATH) and the
+output has load_s and index_file_bytes; otherwise the corpus is built as before, saved to PATH and loaded back once, and the
+output has build_s, save_s, load_s and index_file_bytes.  The file must hold the index the other arguments describe (rows, dim,
+preset, metric, storage) or the run ends.  With --storage quantized, PATH is the quantized handle's file and PATH + ".dense" the
+dense one's."""
 import argparse
 import json
 import os
@@ -157,6 +164,43 @@ def time_storage(gq, gd, Q, qd, k, s, args, metric):
     return out
 
 
+def build_or_load(path, n, d, cfg, storage, out, label=""):
+    """the handle of the run: GpuHnsw.load(path) when the file exists; otherwise built by nmn_hnsw_insert and, with a path, saved
+    and loaded back once.  Seconds and file bytes go to `out`."""
+    from neumann_amd import GpuHnsw, synth_rows
+    pre = f"{label}_" if label else ""
+    if path and os.path.exists(path):
+        t0 = time.perf_counter()
+        g = GpuHnsw.load(path, capacity_hint=n)
+        out[pre + "load_s"] = round(time.perf_counter() - t0, 3)
+        out[pre + "index_file_bytes"] = os.path.getsize(path)
+        have = (len(g), g.dim, g.storage, g.config.m, g.config.m0, g.config.ef_construction, g.config.ef_search, int(g.config.distance_metric))
+        want = (n, d, storage, cfg.m, cfg.m0, cfg.ef_construction, cfg.ef_search, int(cfg.distance_metric))
+        if have != want:
+            g.close()
+            raise SystemExit(f"{path} holds another index: (rows, dim, storage, m, m0, ef_construction, ef_search, metric) = {have}, asked for {want}")
+        print(f"{pre}loaded {n} nodes from {path} in {out[pre + 'load_s']} s", file=sys.stderr, flush=True)
+        return g
+    g = GpuHnsw(d, cfg, capacity_hint=n, storage=storage)
+    t0 = time.perf_counter()
+    step = 50_000
+    for r0 in range(0, n, step):
+        g.insert(synth_rows(0x2F6, r0, min(step, n - r0), d))
+        print(f"{pre}built {min(r0 + step, n)} nodes in {time.perf_counter() - t0:.1f} s", file=sys.stderr, flush=True)
+    out[pre + "build_s"] = round(time.perf_counter() - t0, 1)
+    if path:
+        t0 = time.perf_counter()
+        g.save(path)
+        out[pre + "save_s"] = round(time.perf_counter() - t0, 3)
+        out[pre + "index_file_bytes"] = os.path.getsize(path)
+        t0 = time.perf_counter()
+        with GpuHnsw.load(path) as g2:
+            out[pre + "load_s"] = round(time.perf_counter() - t0, 3)
+            if (len(g2), g2.entry_point, g2.max_layer) != (len(g), g.entry_point, g.max_layer):
+                raise SystemExit(f"{path} did not load as it was saved")
+    return g
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1_000_000)
@@ -170,9 +214,11 @@ def main():
     ap.add_argument("--launch-calls", type=int, default=None)
     ap.add_argument("--storage", default="dense", choices=["dense", "quantized"],
                     help="quantized: time the quantized walk beside the dense walk of the same corpus (docs/hnsw.md §9)")
+    ap.add_argument("--index-file", default=None,
+                    help="load the index from this file when it exists; otherwise build, save it there and report build / save / load seconds")
     args = ap.parse_args()
     import torch
-    from neumann_amd import DistanceMetric, ExtendedDistanceMetric, GpuHnsw, HNSWConfig, synth_rows
+    from neumann_amd import DistanceMetric, ExtendedDistanceMetric, HNSWConfig, synth_rows
 
     n, d, k = args.rows, args.dim, args.k
     xmetric = None
@@ -187,26 +233,15 @@ def main():
     out = {"rows": n, "dim": d, "preset": args.preset, "metric": args.metric, "k": k}
     if args.storage == "quantized":
         out["storage"] = "quantized"
-        with GpuHnsw(d, cfg, capacity_hint=n, storage="quantized") as gq, GpuHnsw(d, cfg, capacity_hint=n, storage="dense") as gd:
-            step = 50_000
+        dense_file = args.index_file + ".dense" if args.index_file else None
+        with build_or_load(args.index_file, n, d, cfg, "quantized", out, "q8") as gq, build_or_load(dense_file, n, d, cfg, "dense", out, "dense") as gd:
             for name, g in (("q8", gq), ("dense", gd)):
-                t0 = time.perf_counter()
-                for r0 in range(0, n, step):
-                    g.insert(synth_rows(0x2F6, r0, min(step, n - r0), d))
-                    print(f"{name}: built {min(r0 + step, n)} nodes in {time.perf_counter() - t0:.1f} s", file=sys.stderr, flush=True)
-                out[f"{name}_build_s"] = round(time.perf_counter() - t0, 1)
                 out[f"{name}_hbm_bytes"], out[f"{name}_max_layer"] = g.hbm_bytes, g.max_layer
             s = torch.cuda.Stream()
             out.update(time_storage(gq, gd, Q, torch.from_numpy(Q).cuda(), k, s, args, metric))
         print(json.dumps(out), flush=True)
         return
-    with GpuHnsw(d, cfg, capacity_hint=n) as g:
-        t0 = time.perf_counter()
-        step = 50_000
-        for r0 in range(0, n, step):
-            g.insert(synth_rows(0x2F6, r0, min(step, n - r0), d))
-            print(f"built {min(r0 + step, n)} nodes in {time.perf_counter() - t0:.1f} s", file=sys.stderr, flush=True)
-        out["build_s"] = round(time.perf_counter() - t0, 1)
+    with build_or_load(args.index_file, n, d, cfg, "dense", out) as g:
         out["max_layer"], out["hbm_bytes"] = g.max_layer, g.hbm_bytes
         flat = g.vectors()
         s = torch.cuda.Stream()
