@@ -283,6 +283,42 @@ uint64_t nmn_engine_hnsw_len(const nmn_engine_hnsw* h);
 const char* nmn_engine_hnsw_key(const nmn_engine_hnsw* h, uint64_t id);
 /* the GPU index itself (owned by h; NULL for an index built from an empty engine) */
 nmn_hnsw* nmn_engine_hnsw_index(nmn_engine_hnsw* h);
+/* ---- hnsw_cache (lib.rs:1305-1334): the index search_similar and search_in_collection answer from ------------------------------
+ * A map from collection name to (shared index, key mapping).  The default collection's name is the literal "_default" (lib.rs:1332,
+ * 1979); a user collection of that name shares the entry, as in the reference.  While `collection` has an entry whose mapping is
+ * NOT empty, nmn_engine_search_similar ("_default"; lib.rs:1976-2001) and nmn_engine_search_in_collection (lib.rs:1622-1646) answer,
+ * after their validations and zero-magnitude rules, from index.search(query, top_k): node ids mapped to keys (ids past the mapping
+ * dropped), the prefix `emb:` / `coll:{c}:emb:` stripped from a key that has it, stable sort by score descending, truncated to
+ * top_k.  Scores are the INDEX's to_similarity under the INDEX's metric, whatever the collection's metric is.  An entry with an
+ * empty mapping falls through to the exhaustive search; an empty index under a non-empty mapping answers nothing.  No deadline
+ * check on this path (the reference has none).  A query of another dimension than the index is DimensionMismatch {expected: the
+ * index's, got}, the stated divergence of nmn_engine_search_with_hnsw.  search_similar_paginated and nmn_engine_search_probe
+ * inherit the hook through search_similar; search_similar_with_metric, the filtered searches and search_entities have none.
+ * Concurrent callers walk as one launch (nmn_hnsw_search's coalescer, docs/hnsw.md §11).
+ *
+ * The entry is dropped where the reference drops it and nowhere else: after a SUCCESSFUL store_embedding (lib.rs:1866; so
+ * batch_store invalidates once per stored vector), delete_embedding (1923), store_in_collection[_with_metadata] (1497) and
+ * delete_from_collection (1532) — hence after load_index* of a named collection, which stores through 1497.  A call that fails
+ * leaves it.  store_embedding_with_metadata (3272-3309), batch_delete (2924-2940), clear, delete_collection, load_index* of the
+ * default collection and the metadata calls do NOT invalidate: after them the cached index keeps answering, deleted keys among
+ * the results.  That is the reference's behaviour and this library's.
+ *
+ * cache_hnsw_index (lib.rs:1311-1315) with the handle's own key mapping / with the caller's (which may be empty, shorter than the
+ * index, or made of storage keys `coll:{c}:emb:{k}`).  The cache takes a reference of its own to the index, as Arc<HNSWIndex>:
+ * nmn_engine_hnsw_free drops only the caller's, an index in use by a search outlives its invalidation, nmn_engine_destroy drops the
+ * cache.  Dense, quantized and loaded (nmn_engine_hnsw_load) handles alike; caching under a name again replaces the entry. */
+nmn_status nmn_engine_cache_hnsw_index(nmn_engine* e, const char* collection, nmn_engine_hnsw* h);
+nmn_status nmn_engine_cache_hnsw_index_mapped(nmn_engine* e, const char* collection, nmn_engine_hnsw* h, const char* const* keys,
+                                              uint64_t n_keys);
+/* invalidate_hnsw_cache (lib.rs:1321-1323); nothing happens for an unknown name. */
+nmn_status nmn_engine_invalidate_hnsw_cache(nmn_engine* e, const char* collection);
+/* build_and_cache_index (lib.rs:1330-1334): build_hnsw_index + cache_hnsw_index("_default", ..); an empty store leaves an entry
+ * whose mapping is empty.  cfg NULL = HNSWConfig::default. */
+nmn_status nmn_engine_build_and_cache_index(nmn_engine* e, const nmn_hnsw_config* cfg);
+/* What the reference's tests read from the map (lib.rs:9730, 9864-9867): `contains_key`, and the entry's mapping (NULL when
+ * there is no entry; free with nmn_strlist_free). */
+int32_t nmn_engine_hnsw_cache_contains(nmn_engine* e, const char* collection);
+nmn_strlist* nmn_engine_hnsw_cache_keys(nmn_engine* e, const char* collection, uint64_t* n);
 /* search_with_hnsw (lib.rs:2516-2550): EmptyVector, InvalidTopK, index.search(query, top_k), node id -> key, ids past the
  * mapping dropped; scores are HNSWDistanceMetric::to_similarity of the index's metric */
 nmn_status nmn_engine_search_with_hnsw(nmn_engine* e, nmn_engine_hnsw* h, const float* q, uint64_t dim, uint64_t top_k,

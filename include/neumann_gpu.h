@@ -640,10 +640,25 @@ nmn_status nmn_hnsw_neighbors(nmn_hnsw* h, uint64_t node, uint32_t layer, uint64
 /* HNSWIndex::search_with_ef (hnsw.rs:2069-2111), ef == 0: config.ef_search.  queries HOST nq x dim; out_ids nq x k (unused =
  * UINT64_MAX), out_scores nq x k = to_similarity(distance) (hnsw.rs:152-158; unused = -inf), out_counts nq.  Empty index:
  * counts 0.  k == 0: NMN_ERR_INVALID_TOP_K.  stats: sweep_kind NMN_SWEEP_GRAPH, rows_scanned = distance evaluations,
- * fallback_queries = queries answered by the spill launch.  Synchronous; host callers take turns.  With the environment
- * variable NMN_HNSW_HOST_SEARCH=1 the walk runs on the host instead (the code insertion uses): same bits, for A/B runs. */
+ * fallback_queries = queries answered by the spill launch.  Synchronous.  Concurrent host callers are coalesced: a call that
+ * arrives while a walk of the handle is running waits, and leaves with every other waiting call as ONE launch that carries a
+ * k and an ef per query (docs/hnsw.md §11); each caller receives exactly what it would have received alone, stats included.
+ * NMN_HNSW_NO_COALESCE=1 makes callers take turns instead, for A/B runs.  With the environment variable
+ * NMN_HNSW_HOST_SEARCH=1 the walk runs on the host instead (the code insertion uses; no coalescing): same bits, for A/B runs. */
 nmn_status nmn_hnsw_search(nmn_hnsw* h, const float* queries, uint32_t nq, uint32_t k, uint32_t ef, uint64_t* out_ids,
                            float* out_scores, uint32_t* out_counts, nmn_search_stats* stats);
+/* HNSWIndex::search_with_ef (hnsw.rs:2069-2111) with a k and an ef per query, all in one launch: the walk runs with
+ * ef_i = max(ef[i], k[i]) (hnsw.rs:2102) and keeps the first k[i].  ef NULL, or an entry 0: config.ef_search.  out_ids /
+ * out_scores are nq x kstride (slots past the count = UINT64_MAX / -inf), out_counts nq.  Every k[i] must be in 1 .. kstride:
+ * 0 is NMN_ERR_INVALID_TOP_K, above kstride NMN_ERR_INVALID_ARGUMENT, before anything is enqueued or written.  The answer for
+ * query i is bit for bit what nmn_hnsw_search(h, q_i, 1, k[i], ef[i], ..) returns alone; stats are the sums of those calls'.
+ * Dense and quantized handles; coalesced with concurrent callers like nmn_hnsw_search. */
+nmn_status nmn_hnsw_search_multi(nmn_hnsw* h, const float* queries, uint32_t nq, const uint32_t* k, const uint32_t* ef,
+                                 uint32_t kstride, uint64_t* out_ids, float* out_scores, uint32_t* out_counts,
+                                 nmn_search_stats* stats);
+/* What the coalescer of nmn_hnsw_search / nmn_hnsw_search_multi has done so far: batches that carried two or more calls, and
+ * the calls in them (the meaning nmn_index_coalesce_stats and nmn_sharded_coalesce_stats give these counters). */
+nmn_status nmn_hnsw_coalesce_stats(nmn_hnsw* h, uint64_t* batches, uint64_t* calls);
 /* The same with every buffer in DEVICE memory: enqueued on `stream` (NULL: the default stream), not waited for.  Two kernel
  * launches per chunk of queries (the walk with both heaps in LDS, then the spill launch for the queries whose candidate
  * heap outgrew LDS), nothing is read back; a shape the stream has served before allocates nothing.  nmn_hnsw_insert and

@@ -295,6 +295,42 @@ impl GpuHnswIndex {
         Ok(ids.into_iter().zip(scores).take(n as usize).map(|(r, s)| (r as usize, s)).collect())
     }
 
+    /// `search` for several queries in ONE launch, each with its own k and ef (nmn_hnsw_search_multi; ef 0 = ef_search).  Answer i is
+    /// bit for bit what `search_with_ef(q_i, k_i, ef_i)` returns alone.  Concurrent callers of `search` / `search_multi` are
+    /// coalesced into such launches by the library (docs/hnsw.md §11).
+    pub fn search_multi(&self, queries: &[&[f32]], k: &[u32], ef: &[u32]) -> Result<Vec<Vec<(usize, f32)>>> {
+        let nq = queries.len();
+        if k.len() != nq || ef.len() != nq {
+            return Err(VectorError::ConfigurationError("one k and one ef per query".to_string()));
+        }
+        let mut flat = Vec::with_capacity(nq * self.dim);
+        for q in queries {
+            if q.len() != self.dim {
+                return Err(VectorError::DimensionMismatch { expected: self.dim, got: q.len() });
+            }
+            flat.extend_from_slice(q);
+        }
+        let kstride = k.iter().copied().max().unwrap_or(1).max(1) as usize;
+        let mut ids = vec![u64::MAX; nq * kstride];
+        let mut scores = vec![f32::NEG_INFINITY; nq * kstride];
+        let mut counts = vec![0u32; nq];
+        let st = unsafe {
+            ffi::nmn_hnsw_search_multi(self.raw, flat.as_ptr(), nq as u32, k.as_ptr(), ef.as_ptr(), kstride as u32, ids.as_mut_ptr(),
+                                       scores.as_mut_ptr(), counts.as_mut_ptr(), std::ptr::null_mut())
+        };
+        check(st, self.dim, self.dim)?;
+        Ok((0..nq)
+            .map(|i| (0..counts[i] as usize).map(|j| (ids[i * kstride + j] as usize, scores[i * kstride + j])).collect())
+            .collect())
+    }
+
+    /// (batches that carried two or more concurrent calls, the calls in them) — nmn_hnsw_coalesce_stats.
+    pub fn coalesce_stats(&self) -> (u64, u64) {
+        let (mut b, mut c) = (0u64, 0u64);
+        unsafe { ffi::nmn_hnsw_coalesce_stats(self.raw, &mut b, &mut c) };
+        (b, c)
+    }
+
     /// The handle's HNSWConfig; after `load`, the file's.
     pub fn config(&self) -> Result<ffi::nmn_hnsw_config> {
         let mut c = std::mem::MaybeUninit::<ffi::nmn_hnsw_config>::zeroed();

@@ -141,14 +141,21 @@ struct nmn_engine_hnsw {
     std::vector<std::string> keys;
     uint64_t dim = 0;
     uint64_t writes_at_build = 0;       // Collection::writes of the default collection when the rows were read
+    // `Arc<HNSWIndex>`: the handle's reference to `index`; the engine's hnsw_cache takes references of its own, so the index lives
+    // until the handle is freed AND no cache entry or cached search holds it any more
+    std::shared_ptr<nmn_hnsw> owner;
+    void own() {
+        if (index && !owner) owner.reset(index, [](nmn_hnsw* p) { nmn_hnsw_destroy(p); });
+    }
     ~nmn_engine_hnsw() {
-        if (index) nmn_hnsw_destroy(index);
+        if (index && !owner) nmn_hnsw_destroy(index);
     }
 };
 
 namespace {
 
 using Meta = std::map<std::string, Value>;
+constexpr const char* kHnswDefaultEntry = "_default";  // the default collection's name in hnsw_cache (lib.rs:1332, 1866, 1923, 1979)
 
 // evaluate_filter (lib.rs:3592-3630)
 bool evaluate_filter(const Meta& meta, const nmn_filter& f) {
@@ -285,7 +292,7 @@ struct Collection {
 struct CollectionConfig {  // VectorCollectionConfig (lib.rs:455-475)
     uint64_t dimension = 0;  // 0 = None
     int32_t metric = NMN_METRIC_COSINE;
-    bool auto_index = false;               // HNSW auto-indexing: carried through index files, not acted on (the hnsw_cache hook is out of scope; build_hnsw_index is served)
+    bool auto_index = false;               // HNSW auto-indexing: carried through index files, not acted on (the reference only stores the field; the hnsw_cache hook itself is served)
     uint64_t auto_index_threshold = 1000;
 };
 
@@ -373,6 +380,19 @@ struct nmn_engine {
     uint64_t column_builds = 0;    // metadata column sets built from the store
     std::atomic<uint64_t> device_filters{0};   // predicates evaluated by the GPU kernel (bumped under the shared lock too)
     std::unordered_map<uint64_t, std::unique_ptr<Mirror>> scratch;  // compute_similarity, by dim
+    // `hnsw_cache: RwLock<HashMap<String, (Arc<HNSWIndex>, Vec<String>)>>` (lib.rs:1305-1334).  An entry is immutable and shared: a
+    // search copies the pointer under cache_mu and walks without it, so an index in use outlives its invalidation.
+    struct HnswCacheEntry {
+        std::shared_ptr<nmn_hnsw> index;  // null: an empty index (built from an empty store)
+        uint64_t dim = 0;
+        std::vector<std::string> keys;    // the mapping: node id -> key, plain or storage key
+    };
+    std::mutex cache_mu;
+    std::map<std::string, std::shared_ptr<const HnswCacheEntry>> hnsw_cache;
+    void invalidate_hnsw(const std::string& collection) {  // lib.rs:1321-1323
+        std::lock_guard<std::mutex> g(cache_mu);
+        hnsw_cache.erase(collection);
+    }
 
     Collection* storage(const char* coll, bool create) {
         if (!coll) return &dflt;
@@ -1131,7 +1151,9 @@ nmn_status nmn_engine_store_embedding_with_metadata(nmn_engine* e, const char* k
 }
 
 nmn_status nmn_engine_store_embedding(nmn_engine* e, const char* key, const float* v, uint64_t dim) {
-    return nmn_engine_store_embedding_with_metadata(e, key, v, dim, nullptr, 0);
+    const nmn_status st = nmn_engine_store_embedding_with_metadata(e, key, v, dim, nullptr, 0);
+    if (st == NMN_OK) e->invalidate_hnsw(kHnswDefaultEntry);  // lib.rs:1866 (store_embedding_with_metadata itself, 3272-3309, does not)
+    return st;
 }
 
 nmn_status nmn_engine_batch_store(nmn_engine* e, const char* const* keys, const float* rows, uint64_t n,
@@ -1142,7 +1164,8 @@ nmn_status nmn_engine_batch_store(nmn_engine* e, const char* const* keys, const 
     WriteLock g(e);
     for (uint64_t i = 0; i < n; i++) {
         if (!keys[i]) return fail(NMN_ERR_INVALID_ARGUMENT, "null key");
-        store_into(e, &e->dflt, keys[i], rows + i * dim, dim, nullptr, 0);
+        if (store_into(e, &e->dflt, keys[i], rows + i * dim, dim, nullptr, 0) == NMN_OK)
+            e->invalidate_hnsw(kHnswDefaultEntry);  // batch_store_embeddings stores through store_embedding: lib.rs:1866 per vector
     }
     return NMN_OK;
 }
@@ -1167,7 +1190,9 @@ nmn_status nmn_engine_get_embedding(nmn_engine* e, const char* key, float* out, 
 nmn_status nmn_engine_delete_embedding(nmn_engine* e, const char* key) {
     if (!e || !key) return fail(NMN_ERR_INVALID_ARGUMENT, "null argument");
     WriteLock g(e);
-    return delete_from(&e->dflt, key, key);
+    const nmn_status st = delete_from(&e->dflt, key, key);
+    if (st == NMN_OK) e->invalidate_hnsw(kHnswDefaultEntry);  // lib.rs:1923
+    return st;
 }
 
 int32_t nmn_engine_exists(nmn_engine* e, const char* key) {
@@ -1255,6 +1280,42 @@ nmn_status nmn_engine_clear(nmn_engine* e, uint64_t* removed) {  // lib.rs:2340-
 }
 
 // ---- searches ------------------------------------------------------------------------------------
+// The cached path of search_similar (lib.rs:1976-2001) and search_in_collection (1622-1646): if `collection` has an entry whose
+// mapping is not empty, answer from index.search(query, top_k) — ids mapped to keys (ids past the mapping dropped), `prefix`
+// stripped where a key has it, stable sort by score descending, truncate — and set *served.  No deadline check: the reference has
+// none here.  Concurrent callers meet in the coalescer of nmn_hnsw_search and walk as one launch (docs/hnsw.md §11).
+static nmn_status cached_hnsw_search(nmn_engine* e, const std::string& collection, const std::string& prefix, const float* q,
+                                     uint64_t dim, uint64_t top_k, nmn_results* res, bool* served) {
+    std::shared_ptr<const nmn_engine::HnswCacheEntry> ent;
+    {
+        std::lock_guard<std::mutex> g(e->cache_mu);
+        auto it = e->hnsw_cache.find(collection);
+        if (it != e->hnsw_cache.end()) ent = it->second;
+    }
+    if (!ent || ent->keys.empty()) return NMN_OK;  // `if !mapping.is_empty()`: an empty mapping falls through
+    *served = true;
+    if (!ent->index) return NMN_OK;  // an empty index under a mapping: `index.search` returns nothing (hnsw.rs:2070-2073)
+    if (dim != ent->dim) return err_dim(ent->dim, dim);  // as search_with_hnsw: the reference's SIMD loops would read past the shorter slice
+    const uint64_t len = nmn_hnsw_len(ent->index.get());
+    const uint32_t k = (uint32_t)std::min<uint64_t>(top_k, std::max<uint64_t>(len, 1));  // the rule of nmn_engine_search_with_hnsw
+    std::vector<uint64_t> ids(k);
+    std::vector<float> sc(k);
+    uint32_t count = 0;
+    const nmn_status st = nmn_hnsw_search(ent->index.get(), q, 1, k, 0, ids.data(), sc.data(), &count, nullptr);
+    if (st != NMN_OK) return err_gpu(st);
+    std::vector<uint32_t> order;
+    for (uint32_t i = 0; i < count; i++)
+        if (ids[i] < ent->keys.size()) order.push_back(i);  // `mapping.get(idx)` -> filter_map
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return sc[a] > sc[b]; });  // b.score.partial_cmp(&a.score)
+    if (order.size() > top_k) order.resize(top_k);
+    for (uint32_t i : order) {
+        const std::string& key = ent->keys[ids[i]];
+        res->keys.push_back(key.compare(0, prefix.size(), prefix) == 0 ? key.substr(prefix.size()) : key);  // strip_prefix().unwrap_or(key)
+        res->scores.push_back(sc[i]);
+    }
+    return NMN_OK;
+}
+
 nmn_status nmn_engine_search_similar_with_metric(nmn_engine* e, const float* q, uint64_t dim, uint64_t top_k,
                                                  int32_t metric, nmn_results** out) {
     if (!e || !out) return fail(NMN_ERR_INVALID_ARGUMENT, "null argument");
@@ -1285,7 +1346,10 @@ nmn_status nmn_engine_search_similar(nmn_engine* e, const float* q, uint64_t dim
     nmn_results* res = new_results();
     if (!res) return fail(NMN_ERR_OUT_OF_MEMORY, "results alloc");
     if (!zero_magnitude(q, dim)) {  // lib.rs:1970-1974
-        st = locked_search(e, [&] { return &e->dflt; }, q, dim, top_k, NMN_METRIC_COSINE, "search_similar", dl, res);
+        bool served = false;
+        st = cached_hnsw_search(e, kHnswDefaultEntry, "emb:", q, dim, top_k, res, &served);  // lib.rs:1976-2001
+        if (st == NMN_OK && !served)
+            st = locked_search(e, [&] { return &e->dflt; }, q, dim, top_k, NMN_METRIC_COSINE, "search_similar", dl, res);
         if (st != NMN_OK) {
             delete res;
             return st;
@@ -1793,6 +1857,7 @@ static nmn_status build_hnsw_with_storage(nmn_engine* e, const nmn_hnsw_config& 
     st = nmn_hnsw_insert(res->index, rows.data(), n, nullptr);
     if (st == NMN_ERR_CAPACITY) return fail(st, std::string("Insert failed: ") + nmn_last_error());  // the reference panics here (hnsw.rs:1916-1918)
     if (st != NMN_OK) return err_gpu(st);
+    res->own();
     *out = res.release();
     return NMN_OK;
 }
@@ -1841,6 +1906,69 @@ const char* nmn_engine_hnsw_key(const nmn_engine_hnsw* h, uint64_t id) {
     return (h && id < h->keys.size()) ? h->keys[id].c_str() : nullptr;
 }
 nmn_hnsw* nmn_engine_hnsw_index(nmn_engine_hnsw* h) { return h ? h->index : nullptr; }
+
+// ---- hnsw_cache (lib.rs:1305-1334) ----
+nmn_status nmn_engine_cache_hnsw_index_mapped(nmn_engine* e, const char* collection, nmn_engine_hnsw* h, const char* const* keys,
+                                              uint64_t n_keys) {
+    if (!e || !collection || !h || (!keys && n_keys)) return fail(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    auto ent = std::make_shared<nmn_engine::HnswCacheEntry>();
+    h->own();
+    ent->index = h->owner;
+    ent->dim = h->dim;
+    for (uint64_t i = 0; i < n_keys; i++) {
+        if (!keys[i]) return fail(NMN_ERR_INVALID_ARGUMENT, "null key");
+        ent->keys.emplace_back(keys[i]);
+    }
+    std::lock_guard<std::mutex> g(e->cache_mu);
+    e->hnsw_cache[collection] = std::move(ent);  // `.insert(collection, (index, keys))`: replaces an entry of that name
+    return NMN_OK;
+}
+
+nmn_status nmn_engine_cache_hnsw_index(nmn_engine* e, const char* collection, nmn_engine_hnsw* h) {
+    if (!e || !collection || !h) return fail(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    std::vector<const char*> keys;
+    keys.reserve(h->keys.size());
+    for (const auto& k : h->keys) keys.push_back(k.c_str());
+    return nmn_engine_cache_hnsw_index_mapped(e, collection, h, keys.data(), keys.size());
+}
+
+nmn_status nmn_engine_invalidate_hnsw_cache(nmn_engine* e, const char* collection) {
+    if (!e || !collection) return fail(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    e->invalidate_hnsw(collection);
+    return NMN_OK;
+}
+
+nmn_status nmn_engine_build_and_cache_index(nmn_engine* e, const nmn_hnsw_config* cfg) {  // lib.rs:1330-1334
+    nmn_engine_hnsw* h = nullptr;
+    nmn_status st = nmn_engine_build_hnsw_index(e, cfg, &h);
+    if (st != NMN_OK) return st;
+    st = nmn_engine_cache_hnsw_index(e, kHnswDefaultEntry, h);
+    nmn_engine_hnsw_free(h);  // the cache keeps its own reference
+    return st;
+}
+
+int32_t nmn_engine_hnsw_cache_contains(nmn_engine* e, const char* collection) {
+    if (!e || !collection) return 0;
+    std::lock_guard<std::mutex> g(e->cache_mu);
+    return e->hnsw_cache.count(collection) ? 1 : 0;
+}
+
+nmn_strlist* nmn_engine_hnsw_cache_keys(nmn_engine* e, const char* collection, uint64_t* n) {
+    if (n) *n = 0;
+    if (!e || !collection) return nullptr;
+    std::shared_ptr<const nmn_engine::HnswCacheEntry> ent;
+    {
+        std::lock_guard<std::mutex> g(e->cache_mu);
+        auto it = e->hnsw_cache.find(collection);
+        if (it == e->hnsw_cache.end()) return nullptr;
+        ent = it->second;
+    }
+    auto* l = new (std::nothrow) nmn_strlist();
+    if (!l) return nullptr;
+    l->items = ent->keys;
+    if (n) *n = l->items.size();
+    return l;
+}
 
 nmn_status nmn_engine_search_with_hnsw(nmn_engine* e, nmn_engine_hnsw* h, const float* q, uint64_t dim, uint64_t top_k,
                                        nmn_results** out) {
@@ -2290,7 +2418,9 @@ nmn_status nmn_engine_store_in_collection(nmn_engine* e, const char* coll, const
     if (cit != e->configs.end() && cit->second.dimension && dim != cit->second.dimension)
         return err_dim(cit->second.dimension, dim);  // lib.rs:1459-1469
     if (e->cfg.max_dimension && dim > e->cfg.max_dimension) return err_dim(e->cfg.max_dimension, dim);
-    return store_into(e, e->storage(coll, true), key, v, dim, meta, n_meta);
+    const nmn_status st = store_into(e, e->storage(coll, true), key, v, dim, meta, n_meta);
+    if (st == NMN_OK) e->invalidate_hnsw(coll);  // lib.rs:1497
+    return st;
 }
 
 nmn_status nmn_engine_get_from_collection(nmn_engine* e, const char* coll, const char* key, float* out,
@@ -2306,7 +2436,9 @@ nmn_status nmn_engine_delete_from_collection(nmn_engine* e, const char* coll, co
     Collection* c = e->storage(coll, false);
     const std::string shown = std::string(coll) + ":" + key;
     if (!c) return err_not_found(shown);
-    return delete_from(c, key, shown);
+    const nmn_status st = delete_from(c, key, shown);
+    if (st == NMN_OK) e->invalidate_hnsw(coll);  // lib.rs:1532
+    return st;
 }
 
 nmn_status nmn_engine_search_in_collection(nmn_engine* e, const char* coll, const float* q, uint64_t dim,
@@ -2328,7 +2460,10 @@ nmn_status nmn_engine_search_in_collection(nmn_engine* e, const char* coll, cons
     nmn_results* res = new_results();
     if (!res) return fail(NMN_ERR_OUT_OF_MEMORY, "results alloc");
     if (!(zero_magnitude(q, dim) && metric == NMN_METRIC_COSINE)) {  // lib.rs:1617-1620
-        st = locked_search(e, [&] { return e->storage(coll, false); }, q, dim, top_k, metric, "search_in_collection", dl, res);
+        bool served = false;
+        st = cached_hnsw_search(e, coll, "coll:" + std::string(coll) + ":emb:", q, dim, top_k, res, &served);  // lib.rs:1622-1646
+        if (st == NMN_OK && !served)
+            st = locked_search(e, [&] { return e->storage(coll, false); }, q, dim, top_k, metric, "search_in_collection", dl, res);
         if (st != NMN_OK) {
             delete res;
             return st;
@@ -2995,6 +3130,9 @@ nmn_status restore_from_index(nmn_engine* e, Decoded& d) {
         }
         nmn_status st = store_into(e, c, ent.key.c_str(), ent.vec.data(), ent.vec.size(), mf.data(), (uint32_t)mf.size());
         if (st != NMN_OK) return st;
+        // lib.rs:3921-3929: a named collection is restored through store_in_collection_with_metadata, which invalidates (1497);
+        // the default one through store_embedding_with_metadata, which does not
+        if (!is_default) e->invalidate_hnsw(d.collection);
     }
     return NMN_OK;
 }
@@ -3463,6 +3601,7 @@ nmn_status nmn_engine_hnsw_load(nmn_engine* e, const char* path, nmn_engine_hnsw
     } else if (!res->keys.empty() || nmn::persist_bytes_left(fp) != 0) {
         return err_serialization("an index that was never built carries keys or a section");
     }
+    res->own();
     *out = res.release();
     return NMN_OK;
 }

@@ -25,9 +25,11 @@
 #include <algorithm>
 #include <atomic>
 #include <cmath>
+#include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <memory>
 #include <mutex>
 #include <shared_mutex>
@@ -36,6 +38,7 @@
 
 #include "nmn_index.h"
 #include "nmn_internal.h"
+#include "nmn_hnsw_queue.h"
 
 #pragma clang fp contract(off)
 
@@ -281,7 +284,25 @@ struct SearchArgs {
     uint64_t* out_ids;
     float* out_scores;
     uint32_t* out_counts;
+    // hnsw_search_kernel<.., PERQ = true>: one k and one ef (= max(ef, k) already) per query of the launch, each array nullable
+    // (null: k / ef above); kstride = row stride of out_ids / out_scores, the largest k of the launch.  ccap_fixed / the formula of
+    // cand_cap() give every query the candidate limit it has in a launch of its own (rcap / ccap stay the launch's: the regions).
+    const uint32_t* qk;
+    const uint32_t* qef;
+    uint32_t kstride, ccap_fixed;
 };
+
+// Entries of the candidate heap the first launch gives a query walking with `ef` (fixed: nmn_hnsw_set_heap_capacity, 0 = default).
+// No answer depends on it: a query that fills the heap is answered from scratch by the spill launch.
+__host__ __device__ inline uint32_t cand_cap(uint32_t ef, uint32_t fixed, uint32_t dim, uint32_t n) {
+    uint32_t c = 16u * (ef < 4096u ? ef : 4096u);
+    c = c < 1024u ? 1024u : c;
+    c = c > kLdsCandMax ? kLdsCandMax : c;
+    if (fixed) c = fixed;
+    if (dim > 4096u && c > 2048u) c = 2048u;  // (64 KiB of LDS: a long query leaves less for the heap)
+    const uint32_t n1 = n ? n : 1u;
+    return c < n1 ? c : n1;                   // (never more than the proven bound)
+}
 
 __device__ __forceinline__ float d_sqrt(float a) { return __builtin_sqrtf(a); }
 
@@ -447,7 +468,9 @@ __device__ __forceinline__ float q8_distance(const uint8_t* __restrict__ row, co
 // global memory (candidates: n entries, the proven bound — nothing is pushed twice).
 // Only lane 0 touches the heaps; the other lanes learn what to do next through `ctrl` in LDS.
 // Q8 == true: the rows are ScalarQuantizedVectors (codes + a record per row), scored by q8_distance.
-template <bool SPILL, bool Q8>
+// PERQ == true: k and ef are the query's own (a.qk / a.qef, read once per query: a wave serves one query, so they are
+// wave-uniform), rows of the outputs are a.kstride apart.  PERQ == false is the kernel as it has always been.
+template <bool SPILL, bool Q8, bool PERQ>
 __global__ __launch_bounds__(64) void hnsw_search_kernel(SearchArgs a) {
     extern __shared__ float4 smem4[];
     const GraphDev& g = a.g;
@@ -478,10 +501,14 @@ __global__ __launch_bounds__(64) void hnsw_search_kernel(SearchArgs a) {
             __threadfence();
         }
         __syncthreads();
-        uint64_t* o_ids = a.out_ids + (size_t)q * a.k;
-        float* o_sc = a.out_scores + (size_t)q * a.k;
+        const uint32_t k_q = PERQ && a.qk ? a.qk[q] : a.k;
+        const uint32_t ef_q = PERQ && a.qef ? a.qef[q] : a.ef;
+        const uint32_t kstride = PERQ ? a.kstride : a.k;
+        const uint32_t ccap_q = PERQ && !SPILL ? min(a.ccap, cand_cap(ef_q, a.ccap_fixed, g.dim, g.n)) : a.ccap;
+        uint64_t* o_ids = a.out_ids + (size_t)q * kstride;
+        float* o_sc = a.out_scores + (size_t)q * kstride;
         if (g.n == 0 || g.entry == kNone) {  // hnsw.rs:2070-2073
-            for (uint32_t i = lane; i < a.k; i += 64) {
+            for (uint32_t i = lane; i < kstride; i += 64) {
                 o_ids[i] = ~0ull;
                 o_sc[i] = ninf;
             }
@@ -567,7 +594,7 @@ __global__ __launch_bounds__(64) void hnsw_search_kernel(SearchArgs a) {
                 } else {
                     const Ent e = heap_pop<false>(Cn, cn);
                     c = e.id;
-                    if (rn >= a.ef && e.d > R[0].d) done = 1;
+                    if (rn >= ef_q && e.d > R[0].d) done = 1;
                 }
                 ctrl[0] = done;
                 ctrl[1] = c;
@@ -603,15 +630,15 @@ __global__ __launch_bounds__(64) void hnsw_search_kernel(SearchArgs a) {
                         if (id == kNone) continue;
                         evals++;
                         const float dt = stage_d[t];
-                        const bool should_add = rn < a.ef || dt < R[0].d;
+                        const bool should_add = rn < ef_q || dt < R[0].d;
                         if (should_add) {
-                            if (cn == a.ccap) {
+                            if (cn == ccap_q) {
                                 ctrl[2] = 1;
                                 break;
                             }
                             heap_push<false>(Cn, cn, Ent{dt, id});
                             heap_push<true>(R, rn, Ent{dt, id});
-                            while (rn > a.ef) (void)heap_pop<true>(R, rn);
+                            while (rn > ef_q) (void)heap_pop<true>(R, rn);
                         }
                     }
                 }
@@ -631,7 +658,7 @@ __global__ __launch_bounds__(64) void hnsw_search_kernel(SearchArgs a) {
         if (SPILL) __threadfence();
         __syncthreads();
         const uint32_t n_res = ctrl[3];
-        const uint32_t count = min(a.k, n_res);
+        const uint32_t count = min(k_q, n_res);
         // stable sort by distance of the vector order (hnsw.rs:2328-2333), as ranks: element e goes to
         // #{j : d_j < d_e} + #{j < e : d_j == d_e}
         for (uint32_t e = lane; e < n_res; e += 64) {
@@ -641,12 +668,12 @@ __global__ __launch_bounds__(64) void hnsw_search_kernel(SearchArgs a) {
                 const float dj = R[j].d;
                 rank += (dj < me.d || (dj == me.d && j < e)) ? 1u : 0u;
             }
-            if (rank < a.k) {
+            if (rank < k_q) {
                 o_ids[rank] = (uint64_t)me.id;
                 o_sc[rank] = to_similarity(g.metric, me.d);
             }
         }
-        for (uint32_t i = count + lane; i < a.k; i += 64) {
+        for (uint32_t i = count + lane; i < kstride; i += 64) {
             o_ids[i] = ~0ull;
             o_sc[i] = ninf;
         }
@@ -664,6 +691,7 @@ struct DevBuf {
 };
 
 }  // namespace
+
 }  // namespace nmn
 
 using namespace nmn;
@@ -707,7 +735,15 @@ struct nmn_hnsw {
     // the host-buffer search
     std::mutex host_mu;
     hipStream_t host_stream = nullptr;
-    DevBuf hq, hids, hsc, hcnt;
+    DevBuf hq, hids, hsc, hcnt, hkef;
+    // ... and what a batch of mixed k / ef passes through on the host (under host_mu): the queries gathered in launch order, k and ef
+    // per query, the launch's rows before they are handed to their callers
+    std::vector<float> st_q;
+    std::vector<uint32_t> st_kef, st_cnt;
+    std::vector<uint64_t> st_ids;
+    std::vector<float> st_sc;
+    // the request coalescer in front of it (docs/hnsw.md §11): one batch runs at a time, whoever arrives meanwhile waits here
+    nmn::WalkQueue co;
 };
 
 namespace {
@@ -1074,30 +1110,7 @@ nmn_hnsw::Scratch* scratch_of(nmn_hnsw* h, hipStream_t s) {
     return h->scratch.back().get();
 }
 
-// Enqueue the search of nq queries (device buffers) on s.  Caller holds rw (shared) AND sc->mu, sc being scratch_of(h, s): growing
-// the scratch, the fills and the launches of one call are one unit, two callers on one stream never interleave.
-nmn_status enqueue_search_locked(nmn_hnsw* h, nmn_hnsw::Scratch* sc, const float* q_dev, uint32_t nq, uint32_t k, uint32_t ef,
-                                 uint64_t* o_ids, float* o_sc, uint32_t* o_cnt, hipStream_t s) {
-    const uint32_t n = (uint32_t)h->level.size();
-    const uint32_t ef_eff = std::max<uint32_t>(ef ? ef : h->cfg.ef_search, k);  // hnsw.rs:2102
-    const uint32_t vwords = std::max<uint32_t>((n + 31) / 32, 1);
-    const uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(nq, (256ull << 20) / ((uint64_t)vwords * 4)));
-    // heaps of the first launch (LDS) and of the spill launch (global memory)
-    const uint32_t res_need = std::min<uint32_t>(ef_eff, std::max<uint32_t>(n, 1)) + 1;
-    const uint32_t rmax = h->lds_rcap ? h->lds_rcap : kLdsResultsMax;
-    const bool lds_ok = res_need <= rmax + 1;
-    uint32_t ccap = h->lds_ccap ? h->lds_ccap : std::min<uint32_t>(kLdsCandMax, std::max<uint32_t>(1024, 16 * std::min<uint32_t>(ef_eff, 4096)));
-    if (h->dim > 4096) ccap = std::min<uint32_t>(ccap, 2048);   // (64 KiB of LDS: a long query leaves less for the heap)
-    ccap = std::min<uint32_t>(ccap, std::max<uint32_t>(n, 1));  // (never more than the proven bound)
-    const uint32_t qlds = (h->dim + 7u) & ~7u;
-    const uint32_t s_rcap = res_need, s_ccap = std::max<uint32_t>(n, 1);
-    const uint64_t region = (uint64_t)s_rcap + s_ccap;
-    const uint32_t regions = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint32_t>(chunk, 64), (256ull << 20) / (region * sizeof(Ent))));
-    bool synced = false;
-    HN_TRY(grow(sc->vis, (size_t)chunk * vwords * 4, s, &synced));
-    HN_TRY(grow(sc->flags, (size_t)nq * 4, s, &synced));
-    HN_TRY(grow(sc->evals, (size_t)nq * 4, s, &synced));
-    HN_TRY(grow(sc->spill, (size_t)regions * region * sizeof(Ent), s, &synced));
+SearchArgs graph_args(const nmn_hnsw* h, uint32_t n) {
     SearchArgs a{};
     a.g.corpus = h->vectors ? h->vectors->corpus : nullptr;
     a.g.norms = h->vectors ? h->vectors->norms : nullptr;
@@ -1110,7 +1123,6 @@ nmn_status enqueue_search_locked(nmn_hnsw* h, nmn_hnsw::Scratch* sc, const float
     a.g.codes = (const uint8_t*)h->d_codes;
     a.g.rec = (const float4*)h->d_rec;
     a.g.ld8 = h->ld8;
-    const bool q8 = h->storage == NMN_HNSW_STORAGE_QUANTIZED;
     a.g.dim = h->dim;
     a.g.m = h->cfg.m;
     a.g.m0 = h->cfg.m0;
@@ -1119,45 +1131,113 @@ nmn_status enqueue_search_locked(nmn_hnsw* h, nmn_hnsw::Scratch* sc, const float
     a.g.entry = n ? (uint32_t)h->entry : kNone;
     a.g.max_layer = h->max_layer;
     a.g.metric = h->cfg.distance_metric;
-    a.k = k;
-    a.ef = ef_eff;
+    return a;
+}
+
+template <bool SPILL>
+void launch_walk(bool q8, bool perq, uint32_t grid, size_t lds, hipStream_t s, const SearchArgs& a) {
+    if (q8 && perq)
+        hipLaunchKernelGGL((hnsw_search_kernel<SPILL, true, true>), dim3(grid), dim3(64), lds, s, a);
+    else if (q8)
+        hipLaunchKernelGGL((hnsw_search_kernel<SPILL, true, false>), dim3(grid), dim3(64), lds, s, a);
+    else if (perq)
+        hipLaunchKernelGGL((hnsw_search_kernel<SPILL, false, true>), dim3(grid), dim3(64), lds, s, a);
+    else
+        hipLaunchKernelGGL((hnsw_search_kernel<SPILL, false, false>), dim3(grid), dim3(64), lds, s, a);
+}
+
+// What one call of enqueue_walk_locked walks with.  Uniform (qk == qef == nullptr): k and ef (= max(ef, k) already) for every query.
+// Per query: DEVICE arrays qk / qef, rows of the outputs kstride apart.  Either way the caller has ORDERED the queries: the first
+// n_lds are those whose results heap fits LDS (min(ef_q, n) + 1 <= the LDS limit + 1), the others go straight to the spill launch,
+// so no launch mixes queries that would take different first launches.  rcap_lds / ef_lds: the largest results heap and the
+// largest ef among the first n_lds; rcap_all: the largest results heap of all.
+struct WalkShape {
+    uint32_t k = 0, ef = 0;
+    const uint32_t* qk = nullptr;
+    const uint32_t* qef = nullptr;
+    uint32_t kstride = 0, n_lds = 0, rcap_lds = 0, ef_lds = 0, rcap_all = 0;
+};
+
+uint32_t results_need(uint32_t ef_eff, uint32_t n) { return std::min<uint32_t>(ef_eff, std::max<uint32_t>(n, 1)) + 1; }
+bool results_fit_lds(const nmn_hnsw* h, uint32_t ef_eff, uint32_t n) {
+    const uint32_t rmax = h->lds_rcap ? h->lds_rcap : kLdsResultsMax;
+    return n == 0 || results_need(ef_eff, n) <= rmax + 1;
+}
+
+// Enqueue the walk of nq queries (device buffers) on s.  Caller holds rw (shared) AND sc->mu, sc being scratch_of(h, s): growing
+// the scratch, the fills and the launches of one call are one unit, two callers on one stream never interleave.
+nmn_status enqueue_walk_locked(nmn_hnsw* h, nmn_hnsw::Scratch* sc, const float* q_dev, uint32_t nq, const WalkShape& w,
+                               uint64_t* o_ids, float* o_sc, uint32_t* o_cnt, hipStream_t s) {
+    const uint32_t n = (uint32_t)h->level.size();
+    const bool perq = w.qk || w.qef;
+    const uint32_t kstride = perq ? w.kstride : w.k;
+    const uint32_t vwords = std::max<uint32_t>((n + 31) / 32, 1);
+    const uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(nq, (256ull << 20) / ((uint64_t)vwords * 4)));
+    // heaps of the first launch (LDS) and of the spill launch (global memory)
+    const uint32_t ccap = cand_cap(w.ef_lds, h->lds_ccap, h->dim, n);
+    const uint32_t qlds = (h->dim + 7u) & ~7u;
+    const uint32_t s_rcap = w.rcap_all, s_ccap = std::max<uint32_t>(n, 1);
+    const uint64_t region = (uint64_t)s_rcap + s_ccap;
+    const uint32_t regions = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint32_t>(chunk, 64), (256ull << 20) / (region * sizeof(Ent))));
+    bool synced = false;
+    HN_TRY(grow(sc->vis, (size_t)chunk * vwords * 4, s, &synced));
+    HN_TRY(grow(sc->flags, (size_t)nq * 4, s, &synced));
+    HN_TRY(grow(sc->evals, (size_t)nq * 4, s, &synced));
+    HN_TRY(grow(sc->spill, (size_t)regions * region * sizeof(Ent), s, &synced));
+    SearchArgs a = graph_args(h, n);
+    const bool q8 = h->storage == NMN_HNSW_STORAGE_QUANTIZED;
+    a.k = w.k;
+    a.ef = w.ef;
+    a.kstride = kstride;
+    a.ccap_fixed = h->lds_ccap;
     a.qlds = qlds;
     a.vwords = vwords;
     a.visited = (uint32_t*)sc->vis.p;
     a.spill = (Ent*)sc->spill.p;
     for (uint32_t q0 = 0; q0 < nq; q0 += chunk) {
         const uint32_t nb = std::min<uint32_t>(chunk, nq - q0);
+        const uint32_t nl = w.n_lds > q0 ? std::min<uint32_t>(w.n_lds - q0, nb) : 0;  // the chunk's queries that start in LDS: its first nl
         a.queries = q_dev + (size_t)q0 * h->dim;
-        a.nq = nb;
+        a.qk = w.qk ? w.qk + q0 : nullptr;
+        a.qef = w.qef ? w.qef + q0 : nullptr;
         a.flags = (uint32_t*)sc->flags.p + q0;
         a.evals = (uint32_t*)sc->evals.p + q0;
-        a.out_ids = o_ids + (size_t)q0 * k;
-        a.out_scores = o_sc + (size_t)q0 * k;
+        a.out_ids = o_ids + (size_t)q0 * kstride;
+        a.out_scores = o_sc + (size_t)q0 * kstride;
         a.out_counts = o_cnt + q0;
         HN_TRY(hipMemsetAsync(sc->vis.p, 0, (size_t)nb * vwords * 4, s));
         const size_t fixed = (size_t)qlds * 4 + 32 * 4 + 32 * 4 + 4 * 4;
-        if (lds_ok || n == 0) {
-            HN_TRY(hipMemsetAsync(a.flags, 0, (size_t)nb * 4, s));
-            a.rcap = res_need;
+        if (nl) {
+            HN_TRY(hipMemsetAsync(a.flags, 0, (size_t)nl * 4, s));
+            a.nq = nl;
+            a.rcap = w.rcap_lds;
             a.ccap = ccap;
             const size_t lds = fixed + ((size_t)a.rcap + a.ccap) * sizeof(Ent);
-            if (q8)
-                hipLaunchKernelGGL((hnsw_search_kernel<false, true>), dim3(nb), dim3(64), lds, s, a);
-            else
-                hipLaunchKernelGGL((hnsw_search_kernel<false, false>), dim3(nb), dim3(64), lds, s, a);
+            launch_walk<false>(q8, perq, nl, lds, s, a);
             HN_TRY(hipGetLastError());
-        } else {  // a results heap no wave can keep in LDS: every query goes to the spill launch
-            HN_TRY(hipMemsetD32Async((hipDeviceptr_t)a.flags, 1, nb, s));
         }
+        if (nl < nb)  // results heaps no wave can keep in LDS: these queries go straight to the spill launch
+            HN_TRY(hipMemsetD32Async((hipDeviceptr_t)(a.flags + nl), 1, nb - nl, s));
+        a.nq = nb;
         a.rcap = s_rcap;
         a.ccap = s_ccap;
-        if (q8)
-            hipLaunchKernelGGL((hnsw_search_kernel<true, true>), dim3(std::min(regions, nb)), dim3(64), fixed, s, a);
-        else
-            hipLaunchKernelGGL((hnsw_search_kernel<true, false>), dim3(std::min(regions, nb)), dim3(64), fixed, s, a);
+        launch_walk<true>(q8, perq, std::min(regions, nb), fixed, s, a);
         HN_TRY(hipGetLastError());
     }
     return NMN_OK;
+}
+
+// The same k and ef for every query: the walk as nmn_hnsw_search_device and nmn_hnsw_search_metric* enqueue it.
+nmn_status enqueue_search_locked(nmn_hnsw* h, nmn_hnsw::Scratch* sc, const float* q_dev, uint32_t nq, uint32_t k, uint32_t ef,
+                                 uint64_t* o_ids, float* o_sc, uint32_t* o_cnt, hipStream_t s) {
+    const uint32_t n = (uint32_t)h->level.size();
+    WalkShape w;
+    w.k = k;
+    w.ef = std::max<uint32_t>(ef ? ef : h->cfg.ef_search, k);  // hnsw.rs:2102
+    w.n_lds = results_fit_lds(h, w.ef, n) ? nq : 0;
+    w.rcap_lds = w.rcap_all = results_need(w.ef, n);
+    w.ef_lds = w.ef;
+    return enqueue_walk_locked(h, sc, q_dev, nq, w, o_ids, o_sc, o_cnt, s);
 }
 
 // The same for a caller that holds rw (shared) only.  *sc_out: the stream's scratch, whose flags / evals the host-buffer search
@@ -1350,7 +1430,7 @@ extern "C" nmn_status nmn_hnsw_destroy(nmn_hnsw* h) {
         drop(s->xsim);
         drop(s->xsort);
     }
-    for (DevBuf* b : {&h->d_l0, &h->d_l0cnt, &h->d_upidx, &h->d_up, &h->d_upcnt, &h->hq, &h->hids, &h->hsc, &h->hcnt}) drop(*b);
+    for (DevBuf* b : {&h->d_l0, &h->d_l0cnt, &h->d_upidx, &h->d_up, &h->d_upcnt, &h->hq, &h->hids, &h->hsc, &h->hcnt, &h->hkef}) drop(*b);
     if (h->host_stream) (void)hipStreamDestroy(h->host_stream);
     if (h->vectors) nmn_index_destroy(h->vectors);
     if (h->d_codes) (void)hipFree(h->d_codes);
@@ -1526,6 +1606,191 @@ extern "C" nmn_status nmn_hnsw_search_device(nmn_hnsw* h, const float* queries_d
     return record_search(h, s);
 }
 
+// ---- the host-buffer walk: batches, and the coalescer in front of them (docs/hnsw.md §11) ----------------------------------------
+namespace {
+
+bool hnsw_coalesce_enabled() {
+    static const bool on = [] {
+        const char* e = getenv("NMN_HNSW_NO_COALESCE");
+        return !(e && e[0] && e[0] != '0');
+    }();
+    return on;
+}
+
+void pad_row(uint64_t* ids, float* sc, uint32_t from, uint32_t to) {
+    for (uint32_t i = from; i < to; i++) {
+        ids[i] = ~0ull;
+        sc[i] = -INFINITY;
+    }
+}
+
+// The calls of `batch`, in order, as ONE walk on the handle's own stream; every call gets its own rows, counts and figures.  A batch
+// whose queries all walk with the same k and ef and whose callers' rows are k apart (a lone nmn_hnsw_search is one) is the uniform
+// launch, straight between the callers' buffers and the device.  Any other batch is the per-query launch: the queries are gathered in
+// launch order (those that start in LDS first), and the launch's rows, kstride = the largest k apart, are handed out on the host.
+// Takes rw (shared) and host_mu for the batch.  A failure is the whole batch's.
+nmn_status run_batch(nmn_hnsw* h, const std::vector<HostWalk*>& batch) {
+    std::shared_lock<std::shared_mutex> g(h->rw);
+    std::lock_guard<std::mutex> hl(h->host_mu);  // nmn_hnsw_search_metric and the insert's upload use the same stream and staging
+    HN_TRY(hipSetDevice(h->device));
+    const uint32_t n = (uint32_t)h->level.size(), dim = h->dim;
+    uint32_t N = 0;
+    for (const HostWalk* r : batch) N += r->nq;
+    struct Slot {
+        HostWalk* r;
+        uint32_t i, k, ef;
+    };
+    std::vector<Slot> slot;  // launch order
+    slot.reserve(N);
+    const uint32_t k0 = batch[0]->k_of(0), ef0 = batch[0]->ef_of(0, h->cfg.ef_search);
+    bool uniform = true;
+    uint32_t kmax = 0;
+    for (HostWalk* r : batch) {
+        r->evals = 0;
+        r->spilled = 0;
+        if (r->kstride != k0) uniform = false;
+        for (uint32_t i = 0; i < r->nq; i++) {
+            const Slot sl{r, i, r->k_of(i), r->ef_of(i, h->cfg.ef_search)};
+            if (sl.k != k0 || sl.ef != ef0) uniform = false;
+            kmax = std::max(kmax, sl.k);
+            slot.push_back(sl);
+        }
+    }
+    hipStream_t s = h->host_stream;
+    bool synced = true;  // (every earlier host call ended with a wait)
+    const hipStream_t none = (hipStream_t)-1;
+    const uint32_t kstride = uniform ? k0 : kmax;
+    HN_TRY(grow(h->hq, (size_t)N * dim * 4, none, &synced));
+    HN_TRY(grow(h->hids, (size_t)N * kstride * 8, none, &synced));
+    HN_TRY(grow(h->hsc, (size_t)N * kstride * 4, none, &synced));
+    HN_TRY(grow(h->hcnt, (size_t)N * 4, none, &synced));
+    nmn_hnsw::Scratch* sc = scratch_of(h, s);
+    std::vector<uint32_t> fl(N), ev(N);
+    if (uniform) {
+        uint32_t off = 0;
+        for (const HostWalk* r : batch) {
+            HN_TRY(hipMemcpyAsync((float*)h->hq.p + (size_t)off * dim, r->q, (size_t)r->nq * dim * 4, hipMemcpyHostToDevice, s));
+            off += r->nq;
+        }
+        {
+            std::lock_guard<std::mutex> slk(sc->mu);
+            nmn_status st = enqueue_search_locked(h, sc, (const float*)h->hq.p, N, k0, ef0, (uint64_t*)h->hids.p, (float*)h->hsc.p,
+                                                  (uint32_t*)h->hcnt.p, s);
+            if (st != NMN_OK) return st;
+        }
+        off = 0;
+        for (const HostWalk* r : batch) {
+            HN_TRY(hipMemcpyAsync(r->out_ids, (uint64_t*)h->hids.p + (size_t)off * k0, (size_t)r->nq * k0 * 8, hipMemcpyDeviceToHost, s));
+            HN_TRY(hipMemcpyAsync(r->out_scores, (float*)h->hsc.p + (size_t)off * k0, (size_t)r->nq * k0 * 4, hipMemcpyDeviceToHost, s));
+            HN_TRY(hipMemcpyAsync(r->out_counts, (uint32_t*)h->hcnt.p + off, (size_t)r->nq * 4, hipMemcpyDeviceToHost, s));
+            off += r->nq;
+        }
+    } else {
+        // the grid must not mix queries that would take different first launches: those whose results heap fits LDS come first
+        std::stable_partition(slot.begin(), slot.end(), [&](const Slot& x) { return results_fit_lds(h, x.ef, n); });
+        WalkShape w;
+        w.kstride = kstride;
+        h->st_q.resize((size_t)N * dim);
+        h->st_kef.resize((size_t)2 * N);
+        for (uint32_t j = 0; j < N; j++) {
+            const Slot& x = slot[j];
+            memcpy(h->st_q.data() + (size_t)j * dim, x.r->q + (size_t)x.i * dim, (size_t)dim * 4);
+            h->st_kef[j] = x.k;
+            h->st_kef[N + j] = x.ef;
+            const uint32_t need = results_need(x.ef, n);
+            w.rcap_all = std::max(w.rcap_all, need);
+            if (results_fit_lds(h, x.ef, n)) {
+                w.n_lds = j + 1;
+                w.rcap_lds = std::max(w.rcap_lds, need);
+                w.ef_lds = std::max(w.ef_lds, x.ef);
+            }
+        }
+        HN_TRY(grow(h->hkef, (size_t)2 * N * 4, none, &synced));
+        w.qk = (const uint32_t*)h->hkef.p;
+        w.qef = w.qk + N;
+        HN_TRY(hipMemcpyAsync(h->hq.p, h->st_q.data(), (size_t)N * dim * 4, hipMemcpyHostToDevice, s));
+        HN_TRY(hipMemcpyAsync(h->hkef.p, h->st_kef.data(), (size_t)2 * N * 4, hipMemcpyHostToDevice, s));
+        {
+            std::lock_guard<std::mutex> slk(sc->mu);
+            nmn_status st = enqueue_walk_locked(h, sc, (const float*)h->hq.p, N, w, (uint64_t*)h->hids.p, (float*)h->hsc.p,
+                                                (uint32_t*)h->hcnt.p, s);
+            if (st != NMN_OK) return st;
+        }
+        h->st_ids.resize((size_t)N * kstride);
+        h->st_sc.resize((size_t)N * kstride);
+        h->st_cnt.resize(N);
+        HN_TRY(hipMemcpyAsync(h->st_ids.data(), h->hids.p, (size_t)N * kstride * 8, hipMemcpyDeviceToHost, s));
+        HN_TRY(hipMemcpyAsync(h->st_sc.data(), h->hsc.p, (size_t)N * kstride * 4, hipMemcpyDeviceToHost, s));
+        HN_TRY(hipMemcpyAsync(h->st_cnt.data(), h->hcnt.p, (size_t)N * 4, hipMemcpyDeviceToHost, s));
+    }
+    HN_TRY(hipMemcpyAsync(fl.data(), sc->flags.p, (size_t)N * 4, hipMemcpyDeviceToHost, s));
+    HN_TRY(hipMemcpyAsync(ev.data(), sc->evals.p, (size_t)N * 4, hipMemcpyDeviceToHost, s));
+    HN_TRY(hipStreamSynchronize(s));
+    static thread_local HostVisited vis;
+    for (uint32_t j = 0; j < N; j++) {
+        const Slot& x = slot[j];
+        HostWalk* r = x.r;
+        uint64_t* ids = r->out_ids + (size_t)x.i * r->kstride;
+        float* scs = r->out_scores + (size_t)x.i * r->kstride;
+        if (fl[j] == 1u) {  // the spill launch could not answer it (cannot happen while its heap holds n entries): the host walk does
+            uint64_t e2 = 0;
+            host_search_one(h, r->q + (size_t)x.i * dim, x.k, x.ef, vis, ids, scs, r->out_counts + x.i, &e2);
+            pad_row(ids, scs, x.k, r->kstride);
+            ev[j] = (uint32_t)e2;
+            r->spilled++;
+        } else {
+            if (fl[j] == 2u) r->spilled++;
+            if (!uniform) {  // slots [count, kstride) of the launch's row hold the sentinels already; the caller's row may be longer
+                const uint32_t c = std::min(kstride, r->kstride);
+                memcpy(ids, h->st_ids.data() + (size_t)j * kstride, (size_t)c * 8);
+                memcpy(scs, h->st_sc.data() + (size_t)j * kstride, (size_t)c * 4);
+                pad_row(ids, scs, c, r->kstride);
+                r->out_counts[x.i] = h->st_cnt[j];
+            }
+        }
+        r->evals += ev[j];
+    }
+    return NMN_OK;
+}
+
+// queue / lead / ride (coalesce_walk, nmn_hnsw_queue.h) around run_batch
+nmn_status submit_walk(nmn_hnsw* h, HostWalk& me) {
+    if (!hnsw_coalesce_enabled()) return run_batch(h, std::vector<HostWalk*>{&me});  // callers take turns on host_mu, as they always have
+    const nmn_status st = coalesce_walk(
+        h->co, me, [&](const std::vector<HostWalk*>& batch) { return run_batch(h, batch); }, [] { return std::string(nmn_last_error()); });
+    if (st != NMN_OK && me.done) return set_error(st, me.err.c_str());  // rode in a batch that failed: the leader's text, on this thread
+    return st;
+}
+
+// nmn_hnsw_search and nmn_hnsw_search_multi behind their argument checks
+nmn_status host_walk_call(nmn_hnsw* h, HostWalk& me, nmn_search_stats* stats) {
+    const bool on_host = host_search_forced();
+    if (on_host) {  // no turn to take: every caller walks on its own thread
+        std::shared_lock<std::shared_mutex> g(h->rw);
+        static thread_local HostVisited vis;
+        for (uint32_t q = 0; q < me.nq; q++) {
+            uint64_t* ids = me.out_ids + (size_t)q * me.kstride;
+            float* scs = me.out_scores + (size_t)q * me.kstride;
+            host_search_one(h, me.q + (size_t)q * h->dim, me.k_of(q), me.ef_of(q, h->cfg.ef_search), vis, ids, scs, me.out_counts + q, &me.evals);
+            pad_row(ids, scs, me.k_of(q), me.kstride);
+        }
+    } else {
+        nmn_status st = submit_walk(h, me);
+        if (st != NMN_OK) return st;
+    }
+    if (stats) {
+        stats->rows_scanned = me.evals;
+        stats->bytes_scanned = h->storage == NMN_HNSW_STORAGE_QUANTIZED ? me.evals * (h->dim + 16ull) : me.evals * h->dim * 4;
+        stats->fallback_queries = me.spilled;
+        std::shared_lock<std::shared_mutex> g(h->rw);
+        stats->sweep_kind = h->level.empty() ? NMN_SWEEP_NONE : NMN_SWEEP_GRAPH;
+        stats->sweep_launches = on_host ? 0 : 2;
+    }
+    return NMN_OK;
+}
+
+}  // namespace
+
 extern "C" nmn_status nmn_hnsw_search(nmn_hnsw* h, const float* queries, uint32_t nq, uint32_t k, uint32_t ef, uint64_t* out_ids,
                                       float* out_scores, uint32_t* out_counts, nmn_search_stats* stats) {
     if (!h) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
@@ -1536,57 +1801,49 @@ extern "C" nmn_status nmn_hnsw_search(nmn_hnsw* h, const float* queries, uint32_
     }
     if (nq == 0) return NMN_OK;
     if (!queries || !out_ids || !out_scores || !out_counts) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
-    std::shared_lock<std::shared_mutex> g(h->rw);
-    const uint64_t ef_eff = ef ? ef : h->cfg.ef_search;
-    uint64_t evals = 0;
-    uint32_t spilled = 0;
-    if (host_search_forced()) {
-        static thread_local HostVisited vis;
-        for (uint32_t q = 0; q < nq; q++)
-            host_search_one(h, queries + (size_t)q * h->dim, k, ef_eff, vis, out_ids + (size_t)q * k, out_scores + (size_t)q * k,
-                            out_counts + q, &evals);
-    } else {
-        std::lock_guard<std::mutex> hl(h->host_mu);  // host callers take turns on the handle's own stream and staging
-        HN_TRY(hipSetDevice(h->device));
-        hipStream_t s = h->host_stream;
-        bool synced = true;  // (every earlier host call ended with a wait)
-        const hipStream_t none = (hipStream_t)-1;
-        HN_TRY(grow(h->hq, (size_t)nq * h->dim * 4, none, &synced));
-        HN_TRY(grow(h->hids, (size_t)nq * k * 8, none, &synced));
-        HN_TRY(grow(h->hsc, (size_t)nq * k * 4, none, &synced));
-        HN_TRY(grow(h->hcnt, (size_t)nq * 4, none, &synced));
-        HN_TRY(hipMemcpyAsync(h->hq.p, queries, (size_t)nq * h->dim * 4, hipMemcpyHostToDevice, s));
-        nmn_hnsw::Scratch* sc = nullptr;
-        nmn_status st = enqueue_search(h, (const float*)h->hq.p, nq, k, ef, (uint64_t*)h->hids.p, (float*)h->hsc.p, (uint32_t*)h->hcnt.p, s, &sc);
-        if (st != NMN_OK) return st;
-        std::vector<uint32_t> fl(nq), ev(nq);
-        HN_TRY(hipMemcpyAsync(out_ids, h->hids.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost, s));
-        HN_TRY(hipMemcpyAsync(out_scores, h->hsc.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, s));
-        HN_TRY(hipMemcpyAsync(out_counts, h->hcnt.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
-        HN_TRY(hipMemcpyAsync(fl.data(), sc->flags.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
-        HN_TRY(hipMemcpyAsync(ev.data(), sc->evals.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
-        HN_TRY(hipStreamSynchronize(s));
-        static thread_local HostVisited vis;
-        for (uint32_t q = 0; q < nq; q++) {
-            if (fl[q] == 1u) {  // the spill launch could not answer it (cannot happen while its heap holds n entries): the host walk does
-                uint64_t e2 = 0;
-                host_search_one(h, queries + (size_t)q * h->dim, k, ef_eff, vis, out_ids + (size_t)q * k, out_scores + (size_t)q * k,
-                                out_counts + q, &e2);
-                ev[q] = (uint32_t)e2;
-                spilled++;
-            } else if (fl[q] == 2u) {
-                spilled++;
-            }
-            evals += ev[q];
-        }
-    }
+    HostWalk me;
+    me.q = queries;
+    me.nq = nq;
+    me.k1 = me.kstride = k;
+    me.ef1 = ef;
+    me.out_ids = out_ids;
+    me.out_scores = out_scores;
+    me.out_counts = out_counts;
+    return host_walk_call(h, me, stats);
+}
+
+extern "C" nmn_status nmn_hnsw_search_multi(nmn_hnsw* h, const float* queries, uint32_t nq, const uint32_t* k, const uint32_t* ef,
+                                            uint32_t kstride, uint64_t* out_ids, float* out_scores, uint32_t* out_counts,
+                                            nmn_search_stats* stats) {
+    if (!h) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (kstride == 0) return set_error(NMN_ERR_INVALID_TOP_K, "kstride == 0");
     if (stats) {
-        stats->rows_scanned = evals;
-        stats->bytes_scanned = h->storage == NMN_HNSW_STORAGE_QUANTIZED ? evals * (h->dim + 16ull) : evals * h->dim * 4;
-        stats->fallback_queries = spilled;
-        stats->sweep_kind = h->level.empty() ? NMN_SWEEP_NONE : NMN_SWEEP_GRAPH;
-        stats->sweep_launches = host_search_forced() ? 0 : 2;
+        memset(stats, 0, sizeof *stats);
+        stats->scan_ms = stats->total_ms = -1.0f;
     }
+    if (nq == 0) return NMN_OK;
+    if (!queries || !k || !out_ids || !out_scores || !out_counts) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    for (uint32_t i = 0; i < nq; i++) {  // before the call joins a batch: a bad call fails alone, and nothing is written
+        if (k[i] == 0) return set_error(NMN_ERR_INVALID_TOP_K, "k == 0");
+        if (k[i] > kstride) return set_error(NMN_ERR_INVALID_ARGUMENT, "HNSW: k[i] above kstride, the row stride of the outputs");
+    }
+    HostWalk me;
+    me.q = queries;
+    me.nq = nq;
+    me.k = k;
+    me.ef = ef;
+    me.kstride = kstride;
+    me.out_ids = out_ids;
+    me.out_scores = out_scores;
+    me.out_counts = out_counts;
+    return host_walk_call(h, me, stats);
+}
+
+extern "C" nmn_status nmn_hnsw_coalesce_stats(nmn_hnsw* h, uint64_t* batches, uint64_t* calls) {
+    if (!h) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    std::lock_guard<std::mutex> lk(h->co.mu);
+    if (batches) *batches = h->co.batches;
+    if (calls) *calls = h->co.calls;
     return NMN_OK;
 }
 

@@ -107,6 +107,12 @@ ENGINE_SIGNATURES = {
     "nmn_engine_hnsw_key": (C.c_char_p, [vp, C.c_uint64]),
     "nmn_engine_hnsw_index": (vp, [vp]),
     "nmn_engine_search_with_hnsw": (C.c_int32, [vp, vp, vp, C.c_uint64, C.c_uint64, C.POINTER(vp)]),
+    "nmn_engine_cache_hnsw_index": (C.c_int32, [vp, C.c_char_p, vp]),
+    "nmn_engine_cache_hnsw_index_mapped": (C.c_int32, [vp, C.c_char_p, vp, C.POINTER(C.c_char_p), C.c_uint64]),
+    "nmn_engine_invalidate_hnsw_cache": (C.c_int32, [vp, C.c_char_p]),
+    "nmn_engine_build_and_cache_index": (C.c_int32, [vp, vp]),
+    "nmn_engine_hnsw_cache_contains": (C.c_int32, [vp, C.c_char_p]),
+    "nmn_engine_hnsw_cache_keys": (vp, [vp, C.c_char_p, C.POINTER(C.c_uint64)]),
     "nmn_engine_search_with_hnsw_and_metric": (C.c_int32, [vp, vp, vp, C.c_uint64, C.c_uint64, C.POINTER(_capi.XMetric),
                                                            C.POINTER(vp)]),
     "nmn_engine_search_with_hnsw_and_metric_mapped": (C.c_int32, [vp, vp, vp, C.c_uint64, C.c_uint64, C.POINTER(_capi.XMetric),
@@ -786,6 +792,44 @@ class VectorEngine:
 
     def build_hnsw_index_default(self):
         return self.build_hnsw_index(None)
+
+    # ---- hnsw_cache (lib.rs:1305-1334): the index search_similar / search_in_collection answer from ----
+    def cache_hnsw_index(self, collection, index, keys=None):
+        """cache_hnsw_index (lib.rs:1311-1315): `index` (an HNSWIndex of build_hnsw_index* / load_hnsw_index) answers
+        search_similar ("_default") / search_in_collection(collection) until the entry is invalidated.  keys None: the index's own
+        mapping; else the caller's (plain or storage keys, possibly empty or shorter than the index).  The cache holds its own
+        reference: closing `index` afterwards leaves the entry answering."""
+        if keys is None:
+            _check(_lib().nmn_engine_cache_hnsw_index(self._h, collection.encode(), index._h))
+        else:
+            ks = [k.encode() for k in keys]
+            arr = (C.c_char_p * max(len(ks), 1))(*ks)
+            _check(_lib().nmn_engine_cache_hnsw_index_mapped(self._h, collection.encode(), index._h, arr, len(ks)))
+
+    def invalidate_hnsw_cache(self, collection):
+        """invalidate_hnsw_cache (lib.rs:1321-1323)"""
+        _check(_lib().nmn_engine_invalidate_hnsw_cache(self._h, collection.encode()))
+
+    def build_and_cache_index(self, config=None):
+        """build_and_cache_index (lib.rs:1330-1334): build_hnsw_index + cache_hnsw_index("_default", ..)"""
+        from .hnsw import HNSWConfig
+        cc = (config or HNSWConfig())._c()
+        _check(_lib().nmn_engine_build_and_cache_index(self._h, C.byref(cc)))
+
+    def hnsw_cache_contains(self, collection):
+        """`hnsw_cache.read().contains_key(collection)`"""
+        return bool(_lib().nmn_engine_hnsw_cache_contains(self._h, collection.encode()))
+
+    def hnsw_cache_keys(self, collection):
+        """the key mapping of the collection's cache entry, None when there is no entry"""
+        n = C.c_uint64()
+        l = _lib().nmn_engine_hnsw_cache_keys(self._h, collection.encode(), C.byref(n))
+        if not l:
+            return None
+        try:
+            return [_lib().nmn_strlist_get(l, i).decode() for i in range(n.value)]
+        finally:
+            _lib().nmn_strlist_free(l)
 
     def search_with_hnsw(self, index, key_mapping, query, top_k):
         """search_with_hnsw (lib.rs:2516-2550)"""

@@ -264,6 +264,37 @@ class GpuHnsw:
                                               C.c_void_p(counts.ctypes.data), C.byref(st)))
         return (ids, sc, counts, st) if with_stats else (ids, sc, counts)
 
+    def search_multi(self, queries, k, ef=None, kstride=None, with_stats=False):
+        """`search` with a k and an ef per query in ONE launch (nmn_hnsw_search_multi).  `k`: one integer per query; `ef`: None
+        (ef_search for all) or one per query, 0 = ef_search; `kstride`: row length of the outputs (None: max(k)).
+        -> (ids u64 [nq,kstride], scores f32 [nq,kstride], counts u32 [nq]); row i is what search(q_i, k[i], ef[i]) answers."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.shape[1] != self.dim:
+            raise _capi.NeumannGpuError(_capi.ERR_DIMENSION_MISMATCH, f"expected {self.dim}, got {q.shape[1]}")
+        nq = q.shape[0]
+        kk = np.ascontiguousarray(k, dtype=np.uint32).reshape(-1)
+        ee = None if ef is None else np.ascontiguousarray(ef, dtype=np.uint32).reshape(-1)
+        if kk.size != nq or (ee is not None and ee.size != nq):
+            raise _capi.NeumannGpuError(_capi.ERR_INVALID_ARGUMENT, "one k (and one ef) per query")
+        ks = int(kk.max()) if kstride is None and nq else int(kstride or 1)
+        ids = np.empty((nq, max(ks, 1)), dtype=np.uint64)
+        sc = np.empty((nq, max(ks, 1)), dtype=np.float32)
+        counts = np.empty(nq, dtype=np.uint32)
+        st = _capi.SearchStats()
+        _capi.check(self._lib.nmn_hnsw_search_multi(self._h, C.c_void_p(q.ctypes.data), nq, C.c_void_p(kk.ctypes.data),
+                                                    C.c_void_p(ee.ctypes.data) if ee is not None else None, ks,
+                                                    C.c_void_p(ids.ctypes.data), C.c_void_p(sc.ctypes.data),
+                                                    C.c_void_p(counts.ctypes.data), C.byref(st)))
+        return (ids, sc, counts, st) if with_stats else (ids, sc, counts)
+
+    def coalesce_stats(self):
+        """(batches that carried two or more concurrent calls, calls in them) — nmn_hnsw_coalesce_stats"""
+        b, c = C.c_uint64(), C.c_uint64()
+        _capi.check(self._lib.nmn_hnsw_coalesce_stats(self._h, C.byref(b), C.byref(c)))
+        return int(b.value), int(c.value)
+
     def search_device(self, queries_t, k, ef=None, out=None, stream=None):
         """`search` with torch device tensors, in stream order (nmn_hnsw_search_device): enqueued on `stream` (None: torch's
         current stream), returns without waiting.  Returns (ids int64 [nq,k] holding the u64 bit pattern, -1 = unused slot;

@@ -40,7 +40,16 @@ With --index-file the run stops paying for builds (docs/hnsw.md §10): when PATH
 output has load_s and index_file_bytes; otherwise the corpus is built as before, saved to PATH and loaded back once, and the
 output has build_s, save_s, load_s and index_file_bytes.  The file must hold the index the other arguments describe (rows, dim,
 preset, metric, storage) or the run ends.  With --storage quantized, PATH is the quantized handle's file and PATH + ".dense" the
-dense one's."""
+dense one's.
+
+  python tools/hnsw_bench.py --rows 1000000 --dim 128 --index-file PATH --callers 1,16,64,128 [--storage quantized]
+--callers times CONCURRENT host callers and nothing else (docs/hnsw.md §11): for every N of the list, N threads behind a barrier,
+each making --caller-calls calls of nmn_hnsw_search(nq = 1) with k taken in turn from 1, 10, 50, 100 (ef_search of the preset).
+Per N it reports queries_per_s (all calls / wall time), call_ms_median (one call as its caller saw it), and what
+nmn_hnsw_coalesce_stats counted meanwhile (merged batches, the calls in them, calls per merged batch); medians and spread over
+--repeats.  With --storage quantized the handle is the quantized one (PATH is its file).  A/B legs are separate processes:
+NMN_HNSW_NO_COALESCE=1 makes callers take turns, NEUMANN_GPU_LIB=<an older build> is the baseline (entries that build lacks are
+left unbound, and its coalesce figures read null)."""
 import argparse
 import json
 import os
@@ -164,6 +173,60 @@ def time_storage(gq, gd, Q, qd, k, s, args, metric):
     return out
 
 
+def time_callers(g, Q, counts, args):
+    """N threads, each calling g.search(one query, its k) --caller-calls times: throughput, a caller's median, the coalescer's counts"""
+    import threading
+    ks = (1, 10, 50, 100)
+    has_stats = hasattr(g._lib, "nmn_hnsw_coalesce_stats")  # (an older build has no coalescer)
+    out = {}
+    for N in counts:
+        per = args.caller_calls
+        reps = {}
+        for _ in range(args.repeats + 1):  # the first pass warms every shape and is dropped
+            lat = [[] for _ in range(N)]
+            errs = []
+            start = threading.Barrier(N + 1)
+
+            def work(t):
+                try:
+                    start.wait()
+                    for j in range(per):
+                        q = Q[(t * per + j) % len(Q)]
+                        t0 = time.perf_counter()
+                        g.search(q, ks[(t + j) % len(ks)])
+                        lat[t].append(time.perf_counter() - t0)
+                except Exception as e:  # noqa: BLE001
+                    errs.append(e)
+
+            th = [threading.Thread(target=work, args=(t,)) for t in range(N)]
+            for x in th:
+                x.start()
+            b0 = g.coalesce_stats() if has_stats else None
+            start.wait()
+            t0 = time.perf_counter()
+            for x in th:
+                x.join()
+            wall = time.perf_counter() - t0
+            if errs:
+                raise errs[0]
+            m = {"queries_per_s": N * per / wall, "call_ms_median": float(np.median(np.concatenate(lat))) * 1e3}
+            if has_stats:
+                b1 = g.coalesce_stats()
+                m["merged_batches"], m["merged_calls"] = b1[0] - b0[0], b1[1] - b0[1]
+                m["calls_per_merged_batch"] = (b1[1] - b0[1]) / max(b1[0] - b0[0], 1)
+            for key, v in m.items():
+                reps.setdefault(key, []).append(v)
+        r = {}
+        for key, v in reps.items():
+            v = v[1:]
+            r[key] = round(float(np.median(v)), 4)
+            r[key + "_spread"] = round(float((max(v) - min(v)) / max(np.median(v), 1e-12)), 3)
+        if not has_stats:
+            r["merged_batches"] = r["merged_calls"] = None
+        out[f"callers{N}"] = r
+    return out
+
+
 def build_or_load(path, n, d, cfg, storage, out, label=""):
     """the handle of the run: GpuHnsw.load(path) when the file exists; otherwise built by nmn_hnsw_insert and, with a path, saved
     and loaded back once.  Seconds and file bytes go to `out`."""
@@ -214,9 +277,17 @@ def main():
     ap.add_argument("--launch-calls", type=int, default=None)
     ap.add_argument("--storage", default="dense", choices=["dense", "quantized"],
                     help="quantized: time the quantized walk beside the dense walk of the same corpus (docs/hnsw.md §9)")
+    ap.add_argument("--callers", default=None, help="e.g. 1,16,64,128: time that many concurrent host callers (nq = 1, mixed k) and nothing else")
+    ap.add_argument("--caller-calls", type=int, default=200, help="calls every caller thread makes per repetition")
     ap.add_argument("--index-file", default=None,
                     help="load the index from this file when it exists; otherwise build, save it there and report build / save / load seconds")
     args = ap.parse_args()
+    if args.callers:  # an older build through NEUMANN_GPU_LIB: entries it lacks stay unbound instead of failing the load
+        import ctypes
+        from neumann_amd import _capi
+        probe = ctypes.CDLL(_capi.LIB_PATH)
+        for name in [x for x in _capi.SIGNATURES if not hasattr(probe, x)]:
+            del _capi.SIGNATURES[name]
     import torch
     from neumann_amd import DistanceMetric, ExtendedDistanceMetric, HNSWConfig, synth_rows
 
@@ -231,6 +302,14 @@ def main():
     metric = DistanceMetric(args.metric)
     Q = synth_rows(0x2F8, 0, 1024, d)
     out = {"rows": n, "dim": d, "preset": args.preset, "metric": args.metric, "k": k}
+    if args.callers:
+        out.update({"storage": args.storage, "lib": os.environ.get("NEUMANN_GPU_LIB", "default"),
+                    "no_coalesce": bool(os.environ.get("NMN_HNSW_NO_COALESCE")), "caller_calls": args.caller_calls})
+        del out["k"]
+        with build_or_load(args.index_file, n, d, cfg, args.storage, out) as g:
+            out.update(time_callers(g, Q, [int(x) for x in args.callers.split(",")], args))
+        print(json.dumps(out), flush=True)
+        return
     if args.storage == "quantized":
         out["storage"] = "quantized"
         dense_file = args.index_file + ".dense" if args.index_file else None

@@ -1,0 +1,98 @@
+// hnsw_queue_mt.cpp — the HNSW request coalescer's queue (neumann_amd/csrc/nmn_hnsw_queue.h) driven from many threads with a
+// stand-in for the batch, no GPU.  Built for the thread and address sanitizers:
+//
+//   c++ -std=c++17 -O1 -g -fsanitize=thread  -I include -I neumann_amd/csrc tools/micro/hnsw_queue_mt.cpp -o tools/micro/hnsw_queue_mt -lpthread && tools/micro/hnsw_queue_mt
+//   c++ -std=c++17 -O1 -g -fsanitize=address -I include -I neumann_amd/csrc tools/micro/hnsw_queue_mt.cpp -o tools/micro/hnsw_queue_mt -lpthread && tools/micro/hnsw_queue_mt
+//
+// The stand-in checks what the queue promises: one batch at a time; at most kBatchQueries queries in a batch unless it is one
+// call; every call is served exactly once, with its own answer (out_counts[i] = a
+// function of the call's own k and query), also when a batch fails — then every call of that batch gets the status and the text.
+#include <atomic>
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <thread>
+
+#include "nmn_hnsw_queue.h"
+
+using namespace nmn;
+
+static std::atomic<int> running{0};
+static std::atomic<uint64_t> batches_run{0}, calls_served{0}, failed_batches{0};
+static thread_local std::string tl_error;
+
+#define REQUIRE(c)                                                   \
+    do {                                                             \
+        if (!(c)) {                                                  \
+            fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #c); \
+            abort();                                                 \
+        }                                                            \
+    } while (0)
+
+static nmn_status fake_batch(const std::vector<HostWalk*>& batch) {
+    REQUIRE(running.fetch_add(1) == 0);  // one batch at a time
+    uint64_t total = 0;
+    for (const HostWalk* r : batch) total += r->nq;
+    REQUIRE(batch.size() == 1 || total <= kBatchQueries);
+    const uint64_t b = batches_run.fetch_add(1);
+    nmn_status st = NMN_OK;
+    if (b % 17 == 5) {  // a failing batch: nothing written, every call gets the status
+        tl_error = "batch " + std::to_string(b) + " failed";
+        failed_batches++;
+        st = NMN_ERR_INVALID_ARGUMENT;
+    } else {
+        for (HostWalk* r : batch) {
+            for (uint32_t i = 0; i < r->nq; i++) r->out_counts[i] = r->k_of(i) * 1000u + (uint32_t)r->q[i];
+            r->evals = r->nq;
+        }
+    }
+    std::this_thread::sleep_for(std::chrono::microseconds(50 + (b % 5) * 40));
+    calls_served += batch.size();
+    REQUIRE(running.fetch_sub(1) == 1);
+    return st;
+}
+
+int main() {
+    const int threads = 24, calls = 400;
+    WalkQueue q;
+    std::atomic<uint64_t> failures_seen{0};
+    std::vector<std::thread> th;
+    for (int t = 0; t < threads; t++) {
+        th.emplace_back([&, t] {
+            for (int c = 0; c < calls; c++) {
+                const uint32_t nq = (t == 0 && c % 50 == 0) ? 1500u : 1u + (uint32_t)((t + c) % 7 == 0 ? 300 : (t + c) % 3);  // some calls larger than a batch
+                std::vector<float> query(nq);
+                std::vector<uint32_t> k(nq), counts(nq, 0xFFFFFFFFu);
+                for (uint32_t i = 0; i < nq; i++) {
+                    query[i] = (float)((t * 31 + c + i) % 997);
+                    k[i] = 1 + (uint32_t)((t + c + i) % 200);
+                }
+                HostWalk me;
+                me.q = query.data();
+                me.nq = nq;
+                me.k = k.data();
+                me.kstride = 200;
+                me.out_counts = counts.data();
+                const nmn_status st = coalesce_walk(q, me, fake_batch, [] { return tl_error; });
+                if (st == NMN_OK) {
+                    REQUIRE(me.evals == nq || me.done);  // (a rider's evals are written by the leader before done is set)
+                    for (uint32_t i = 0; i < nq; i++) REQUIRE(counts[i] == k[i] * 1000u + (uint32_t)query[i]);
+                } else {
+                    REQUIRE(st == NMN_ERR_INVALID_ARGUMENT);
+                    if (me.done) REQUIRE(me.err.find("failed") != std::string::npos);  // a rider carries the leader's text
+                    for (uint32_t i = 0; i < nq; i++) REQUIRE(counts[i] == 0xFFFFFFFFu);
+                    failures_seen++;
+                }
+            }
+        });
+    }
+    for (auto& x : th) x.join();
+    REQUIRE(calls_served.load() == (uint64_t)threads * calls);
+    REQUIRE(!q.busy && q.waiting.empty());
+    REQUIRE(q.batches > 0 && q.calls >= 2 * q.batches);
+    REQUIRE(failed_batches.load() > 0 && failures_seen.load() >= failed_batches.load());
+    printf("hnsw_queue_mt ok: %llu calls in %llu batches (%llu merged batches carrying %llu calls), %llu failed batches, %llu failed calls\n",
+           (unsigned long long)calls_served.load(), (unsigned long long)batches_run.load(), (unsigned long long)q.batches,
+           (unsigned long long)q.calls, (unsigned long long)failed_batches.load(), (unsigned long long)failures_seen.load());
+    return 0;
+}
