@@ -656,7 +656,7 @@ nmn_status nmn_hnsw_search(nmn_hnsw* h, const float* queries, uint32_t nq, uint3
 nmn_status nmn_hnsw_search_multi(nmn_hnsw* h, const float* queries, uint32_t nq, const uint32_t* k, const uint32_t* ef,
                                  uint32_t kstride, uint64_t* out_ids, float* out_scores, uint32_t* out_counts,
                                  nmn_search_stats* stats);
-/* What the coalescer of nmn_hnsw_search / nmn_hnsw_search_multi has done so far: batches that carried two or more calls, and
+/* What the coalescer of nmn_hnsw_search / nmn_hnsw_search_multi / nmn_hnsw_search_metric / nmn_hnsw_search_metric_multi has done so far: batches that carried two or more calls, and
  * the calls in them (the meaning nmn_index_coalesce_stats and nmn_sharded_coalesce_stats give these counters). */
 nmn_status nmn_hnsw_coalesce_stats(nmn_hnsw* h, uint64_t* batches, uint64_t* calls);
 /* The same with every buffer in DEVICE memory: enqueued on `stream` (NULL: the default stream), not waited for.  Two kernel
@@ -758,6 +758,18 @@ nmn_status nmn_xmetric_score_host_rows(int32_t device, const float* rows_host, u
  * walk to the host as for nmn_hnsw_search; the re-rank still runs on the device. */
 nmn_status nmn_hnsw_search_metric(nmn_hnsw* h, const float* queries, uint32_t nq, uint32_t top_k, const nmn_xmetric* metric,
                                   uint64_t* out_ids, float* out_scores, uint32_t* out_counts, nmn_search_stats* stats);
+/* nmn_hnsw_search_metric for several queries in one call, each with its own top_k and its own metric (docs/hnsw.md §12).  HOST
+ * buffers; top_k[i] in 1 .. kstride, metrics[i] one per query, out_ids / out_scores nq x kstride, out_counts nq.  Answer i is bit for
+ * bit what nmn_hnsw_search_metric(h, q_i, 1, top_k[i], &metrics[i], ..) returns alone, padded to kstride with UINT64_MAX / -inf.
+ * Refused before anything is enqueued or written: a quantized handle NMN_ERR_CONFIGURATION, top_k[i] == 0 NMN_ERR_INVALID_TOP_K,
+ * top_k[i] > kstride NMN_ERR_INVALID_ARGUMENT, an unknown kind at any i NMN_ERR_CONFIGURATION.  stats: rows_scanned and
+ * fallback_queries are the sums over the queries, candidates_rescored the maximum, sweep_kind / sweep_launches the lone call's.
+ * Like nmn_hnsw_search_metric it joins the coalescer of nmn_hnsw_search: concurrent callers of any of the four leave as one walk,
+ * the re-rank and the ordering behind it carry kind, weights and top_k per query.  A call that asks for more than 4 096 candidates
+ * for a query (2 top_k, capped by the index's length) runs alone. */
+nmn_status nmn_hnsw_search_metric_multi(nmn_hnsw* h, const float* queries, uint32_t nq, const uint32_t* top_k,
+                                        const nmn_xmetric* metrics, uint32_t kstride, uint64_t* out_ids, float* out_scores,
+                                        uint32_t* out_counts, nmn_search_stats* stats);
 /* The same with every buffer in DEVICE memory, enqueued on `stream` behind the walk and not waited for: the walk's launches,
  * the re-rank and the ordering (one launch; above 16 384 candidates the large-k sort, query by query); nothing is read back.  The nq x c candidate block lives in the stream's scratch: a shape the
  * stream has served before allocates nothing. */

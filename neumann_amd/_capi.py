@@ -244,6 +244,7 @@ SIGNATURES = {
     "nmn_xmetric_score_host_rows": (C.c_int32, [C.c_int32, vp, C.c_uint32, C.c_uint32, vp, C.POINTER(XMetric), vp, vp]),
     "nmn_hnsw_search_metric": (C.c_int32, [vp, vp, C.c_uint32, C.c_uint32, C.POINTER(XMetric), vp, vp, vp,
                                            C.POINTER(SearchStats)]),
+    "nmn_hnsw_search_metric_multi": (C.c_int32, [vp, vp, C.c_uint32, vp, vp, C.c_uint32, vp, vp, vp, C.POINTER(SearchStats)]),
     "nmn_hnsw_search_metric_device": (C.c_int32, [vp, vp, C.c_uint32, C.c_uint32, C.POINTER(XMetric), vp, vp, vp, vp]),
     "nmn_index_save": (C.c_int32, [vp, C.c_char_p]),
     "nmn_index_load": (C.c_int32, [C.c_char_p, C.POINTER(IndexDesc), C.c_uint64, C.c_uint64, C.POINTER(vp)]),

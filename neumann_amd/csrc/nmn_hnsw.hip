@@ -736,12 +736,17 @@ struct nmn_hnsw {
     std::mutex host_mu;
     hipStream_t host_stream = nullptr;
     DevBuf hq, hids, hsc, hcnt, hkef;
+    DevBuf hxmeta, hxsim, hxoids, hxosc, hxocnt, hxsort;  // a batch's metric slots (docs/hnsw.md §12): what their launches read and answer into
     // ... and what a batch of mixed k / ef passes through on the host (under host_mu): the queries gathered in launch order, k and ef
     // per query, the launch's rows before they are handed to their callers
     std::vector<float> st_q;
     std::vector<uint32_t> st_kef, st_cnt;
     std::vector<uint64_t> st_ids;
     std::vector<float> st_sc;
+    std::vector<nmn::XmetricBatchItem> st_xitems;
+    std::vector<uint32_t> st_xmeta, st_xocnt;
+    std::vector<uint64_t> st_xoids;
+    std::vector<float> st_xosc;
     // the request coalescer in front of it (docs/hnsw.md §11): one batch runs at a time, whoever arrives meanwhile waits here
     nmn::WalkQueue co;
 };
@@ -1430,7 +1435,9 @@ extern "C" nmn_status nmn_hnsw_destroy(nmn_hnsw* h) {
         drop(s->xsim);
         drop(s->xsort);
     }
-    for (DevBuf* b : {&h->d_l0, &h->d_l0cnt, &h->d_upidx, &h->d_up, &h->d_upcnt, &h->hq, &h->hids, &h->hsc, &h->hcnt, &h->hkef}) drop(*b);
+    for (DevBuf* b : {&h->d_l0, &h->d_l0cnt, &h->d_upidx, &h->d_up, &h->d_upcnt, &h->hq, &h->hids, &h->hsc, &h->hcnt, &h->hkef,
+                       &h->hxmeta, &h->hxsim, &h->hxoids, &h->hxosc, &h->hxocnt, &h->hxsort})
+        drop(*b);
     if (h->host_stream) (void)hipStreamDestroy(h->host_stream);
     if (h->vectors) nmn_index_destroy(h->vectors);
     if (h->d_codes) (void)hipFree(h->d_codes);
@@ -1624,38 +1631,148 @@ void pad_row(uint64_t* ids, float* sc, uint32_t from, uint32_t to) {
     }
 }
 
+struct Slot {
+    HostWalk* r;
+    uint32_t i, k, ef;       // what the query walks with (a metric query: k = its candidate count c, ef = max(ef_search, c))
+    uint32_t top;            // a metric query's top_k
+    const nmn_xmetric* xm;   // ... and its metric (nullptr: a plain walk)
+};
+
+// A batch whose slots are all metric slots with one top_k and one metric (a lone nmn_hnsw_search_metric is one): the uniform chain
+// it has always been — the walk into the stream's candidate block, xmetric_rerank_kernel, the ordering — straight between the
+// callers' buffers and the device.  Caller holds rw (shared) and host_mu.  on_host: the walk on the host (NMN_HNSW_HOST_SEARCH=1).
+nmn_status run_metric_uniform(nmn_hnsw* h, const std::vector<HostWalk*>& batch, const std::vector<Slot>& slot, bool on_host) {
+    const uint32_t N = (uint32_t)slot.size(), dim = h->dim, top_k = slot[0].top, c = slot[0].k;
+    const nmn_xmetric& metric = *slot[0].xm;
+    hipStream_t s = h->host_stream;
+    bool synced = true;  // (every earlier host call ended with a wait)
+    const hipStream_t none = (hipStream_t)-1;
+    HN_TRY(grow(h->hq, (size_t)N * dim * 4, none, &synced));
+    HN_TRY(grow(h->hids, (size_t)N * top_k * 8, none, &synced));
+    HN_TRY(grow(h->hsc, (size_t)N * top_k * 4, none, &synced));
+    HN_TRY(grow(h->hcnt, (size_t)N * 4, none, &synced));
+    // host_mu makes this batch the only one on host_stream; sc->mu is held all the same, for the whole batch: the candidate block
+    // is read back and, should a query stay flagged, filled again
+    nmn_hnsw::Scratch* sc = scratch_of(h, s);
+    std::lock_guard<std::mutex> slk(sc->mu);
+    nmn_status st = metric_scratch(sc, s, N, c, top_k);
+    if (st != NMN_OK) return st;
+    uint32_t off = 0;
+    for (const HostWalk* r : batch) {
+        HN_TRY(hipMemcpyAsync((float*)h->hq.p + (size_t)off * dim, r->q, (size_t)r->nq * dim * 4, hipMemcpyHostToDevice, s));
+        off += r->nq;
+    }
+    std::vector<uint64_t> cid;
+    std::vector<float> csc;
+    std::vector<uint32_t> ccnt(N), fl(N, 0), ev(N, 0);
+    auto host_walk = [&](uint32_t q) {  // the walk of query q on the host, its candidates into the staging vectors
+        static thread_local HostVisited vis;
+        if (cid.empty()) {
+            cid.resize((size_t)N * c);
+            csc.resize((size_t)N * c);
+        }
+        uint64_t e2 = 0;
+        host_search_one(h, slot[q].r->q + (size_t)slot[q].i * dim, c, h->cfg.ef_search, vis, cid.data() + (size_t)q * c,
+                        csc.data() + (size_t)q * c, &ccnt[q], &e2);
+        ev[q] = (uint32_t)e2;
+    };
+    auto hand_out = [&]() -> nmn_status {  // the rows of every caller, top_k apart, to its own buffers
+        uint32_t o = 0;
+        for (const HostWalk* r : batch) {
+            HN_TRY(hipMemcpyAsync(r->out_ids, (uint64_t*)h->hids.p + (size_t)o * top_k, (size_t)r->nq * top_k * 8, hipMemcpyDeviceToHost, s));
+            HN_TRY(hipMemcpyAsync(r->out_scores, (float*)h->hsc.p + (size_t)o * top_k, (size_t)r->nq * top_k * 4, hipMemcpyDeviceToHost, s));
+            HN_TRY(hipMemcpyAsync(r->out_counts, (uint32_t*)h->hcnt.p + o, (size_t)r->nq * 4, hipMemcpyDeviceToHost, s));
+            o += r->nq;
+        }
+        return NMN_OK;
+    };
+    if (on_host) {
+        for (uint32_t q = 0; q < N; q++) host_walk(q);
+        HN_TRY(hipMemcpyAsync(sc->xids.p, cid.data(), (size_t)N * c * 8, hipMemcpyHostToDevice, s));
+        HN_TRY(hipMemcpyAsync(sc->xcnt.p, ccnt.data(), (size_t)N * 4, hipMemcpyHostToDevice, s));
+    } else {
+        st = enqueue_search_locked(h, sc, (const float*)h->hq.p, N, c, 0, (uint64_t*)sc->xids.p, (float*)sc->xsc.p, (uint32_t*)sc->xcnt.p, s);
+        if (st != NMN_OK) return st;
+    }
+    st = enqueue_rerank(h, sc, (const float*)h->hq.p, N, c, top_k, metric, (uint64_t*)h->hids.p, (float*)h->hsc.p, (uint32_t*)h->hcnt.p, s);
+    if (st != NMN_OK) return st;
+    if ((st = hand_out()) != NMN_OK) return st;
+    if (!on_host) {
+        HN_TRY(hipMemcpyAsync(ccnt.data(), sc->xcnt.p, (size_t)N * 4, hipMemcpyDeviceToHost, s));
+        HN_TRY(hipMemcpyAsync(fl.data(), sc->flags.p, (size_t)N * 4, hipMemcpyDeviceToHost, s));
+        HN_TRY(hipMemcpyAsync(ev.data(), sc->evals.p, (size_t)N * 4, hipMemcpyDeviceToHost, s));
+    }
+    HN_TRY(hipStreamSynchronize(s));
+    bool redo = false;
+    for (uint32_t q = 0; q < N; q++)
+        if (fl[q] == 1u) redo = true;  // the spill launch could not answer it (cannot happen while its heap holds n entries)
+    if (redo) {  // ... then the host walks every such query and the device re-ranks again
+        cid.resize((size_t)N * c);
+        csc.resize((size_t)N * c);
+        HN_TRY(hipMemcpy(cid.data(), sc->xids.p, (size_t)N * c * 8, hipMemcpyDeviceToHost));
+        for (uint32_t q = 0; q < N; q++)
+            if (fl[q] == 1u) host_walk(q);
+        HN_TRY(hipMemcpyAsync(sc->xids.p, cid.data(), (size_t)N * c * 8, hipMemcpyHostToDevice, s));
+        HN_TRY(hipMemcpyAsync(sc->xcnt.p, ccnt.data(), (size_t)N * 4, hipMemcpyHostToDevice, s));
+        st = enqueue_rerank(h, sc, (const float*)h->hq.p, N, c, top_k, metric, (uint64_t*)h->hids.p, (float*)h->hsc.p, (uint32_t*)h->hcnt.p, s);
+        if (st != NMN_OK) return st;
+        if ((st = hand_out()) != NMN_OK) return st;
+        HN_TRY(hipStreamSynchronize(s));
+    }
+    for (uint32_t q = 0; q < N; q++) {
+        HostWalk* r = slot[q].r;
+        r->evals += ev[q];
+        if (fl[q] != 0u) r->spilled++;
+        r->rescored = std::max(r->rescored, std::min(ccnt[q], c));
+    }
+    return NMN_OK;
+}
+
 // The calls of `batch`, in order, as ONE walk on the handle's own stream; every call gets its own rows, counts and figures.  A batch
 // whose queries all walk with the same k and ef and whose callers' rows are k apart (a lone nmn_hnsw_search is one) is the uniform
 // launch, straight between the callers' buffers and the device.  Any other batch is the per-query launch: the queries are gathered in
 // launch order (those that start in LDS first), and the launch's rows, kstride = the largest k apart, are handed out on the host.
-// Takes rw (shared) and host_mu for the batch.  A failure is the whole batch's.
-nmn_status run_batch(nmn_hnsw* h, const std::vector<HostWalk*>& batch) {
+// Metric calls (docs/hnsw.md §12) ride the same walk with k = their candidate count; behind it, on the same stream, the per-query
+// re-rank and ordering run over the metric slots, and one read-back serves everybody.  A batch of metric slots with one top_k and
+// one metric is run_metric_uniform.  Takes rw (shared) and host_mu for the batch.  A failure is the whole batch's.
+// on_host (a metric call under NMN_HNSW_HOST_SEARCH=1, alone): the walks on the host, the re-rank on the device.
+nmn_status run_batch(nmn_hnsw* h, const std::vector<HostWalk*>& batch, bool on_host = false) {
     std::shared_lock<std::shared_mutex> g(h->rw);
-    std::lock_guard<std::mutex> hl(h->host_mu);  // nmn_hnsw_search_metric and the insert's upload use the same stream and staging
+    std::lock_guard<std::mutex> hl(h->host_mu);  // the insert's upload uses the same stream and staging
     HN_TRY(hipSetDevice(h->device));
     const uint32_t n = (uint32_t)h->level.size(), dim = h->dim;
     uint32_t N = 0;
     for (const HostWalk* r : batch) N += r->nq;
-    struct Slot {
-        HostWalk* r;
-        uint32_t i, k, ef;
-    };
     std::vector<Slot> slot;  // launch order
     slot.reserve(N);
-    const uint32_t k0 = batch[0]->k_of(0), ef0 = batch[0]->ef_of(0, h->cfg.ef_search);
+    auto slot_of = [&](HostWalk* r, uint32_t i) {
+        if (!r->xm) return Slot{r, i, r->k_of(i), r->ef_of(i, h->cfg.ef_search), 0, nullptr};
+        const uint32_t c = (uint32_t)metric_candidates(h, r->k_of(i));  // here, under rw: an insert may have run since the call was checked
+        return Slot{r, i, c, std::max<uint32_t>(h->cfg.ef_search, c), r->k_of(i), &r->metric_of(i)};
+    };
+    const Slot s0 = slot_of(batch[0], 0);
+    const uint32_t k0 = s0.k, ef0 = s0.ef;
+    const uint32_t row0 = s0.xm ? s0.top : k0;  // the callers' row length a uniform batch needs
     bool uniform = true;
-    uint32_t kmax = 0;
+    uint32_t kmax = 0, M = 0, topmax = 0;
     for (HostWalk* r : batch) {
         r->evals = 0;
         r->spilled = 0;
-        if (r->kstride != k0) uniform = false;
+        r->rescored = 0;
+        if (r->kstride != row0) uniform = false;
         for (uint32_t i = 0; i < r->nq; i++) {
-            const Slot sl{r, i, r->k_of(i), r->ef_of(i, h->cfg.ef_search)};
-            if (sl.k != k0 || sl.ef != ef0) uniform = false;
+            const Slot sl = slot_of(r, i);
+            if (sl.k != k0 || sl.ef != ef0 || sl.top != s0.top || !sl.xm != !s0.xm || (sl.xm && memcmp(sl.xm, s0.xm, sizeof(nmn_xmetric)) != 0))
+                uniform = false;
             kmax = std::max(kmax, sl.k);
+            if (sl.xm) {
+                M++;
+                topmax = std::max(topmax, sl.top);
+            }
             slot.push_back(sl);
         }
     }
+    if (uniform && M) return run_metric_uniform(h, batch, slot, on_host);
     hipStream_t s = h->host_stream;
     bool synced = true;  // (every earlier host call ended with a wait)
     const hipStream_t none = (hipStream_t)-1;
@@ -1666,6 +1783,19 @@ nmn_status run_batch(nmn_hnsw* h, const std::vector<HostWalk*>& batch) {
     HN_TRY(grow(h->hcnt, (size_t)N * 4, none, &synced));
     nmn_hnsw::Scratch* sc = scratch_of(h, s);
     std::vector<uint32_t> fl(N), ev(N);
+    static thread_local HostVisited vis;
+    XmetricBatchPlan plan;
+    auto metric_chain = [&]() -> nmn_status {  // behind whatever filled the walk's rows on s; the answers on their way back
+        if (!M) return NMN_OK;
+        HN_TRY(launch_xmetric_rerank_batch(h->vectors ? h->vectors->corpus : nullptr, h->vectors ? h->vectors->ld : 0, dim, n,
+                                           (const float*)h->hq.p, kstride, (const uint64_t*)h->hids.p, (const uint32_t*)h->hcnt.p, plan,
+                                           (const uint32_t*)h->hxmeta.p, (float*)h->hxsim.p, topmax, (uint64_t*)h->hxoids.p,
+                                           (float*)h->hxosc.p, (uint32_t*)h->hxocnt.p, h->hxsort.p, s));
+        HN_TRY(hipMemcpyAsync(h->st_xoids.data(), h->hxoids.p, (size_t)M * topmax * 8, hipMemcpyDeviceToHost, s));
+        HN_TRY(hipMemcpyAsync(h->st_xosc.data(), h->hxosc.p, (size_t)M * topmax * 4, hipMemcpyDeviceToHost, s));
+        HN_TRY(hipMemcpyAsync(h->st_xocnt.data(), h->hxocnt.p, (size_t)M * 4, hipMemcpyDeviceToHost, s));
+        return NMN_OK;
+    };
     if (uniform) {
         uint32_t off = 0;
         for (const HostWalk* r : batch) {
@@ -1692,11 +1822,13 @@ nmn_status run_batch(nmn_hnsw* h, const std::vector<HostWalk*>& batch) {
         w.kstride = kstride;
         h->st_q.resize((size_t)N * dim);
         h->st_kef.resize((size_t)2 * N);
+        h->st_xitems.clear();
         for (uint32_t j = 0; j < N; j++) {
             const Slot& x = slot[j];
             memcpy(h->st_q.data() + (size_t)j * dim, x.r->q + (size_t)x.i * dim, (size_t)dim * 4);
             h->st_kef[j] = x.k;
             h->st_kef[N + j] = x.ef;
+            if (x.xm) h->st_xitems.push_back(XmetricBatchItem{j, x.k, x.top, *x.xm});
             const uint32_t need = results_need(x.ef, n);
             w.rcap_all = std::max(w.rcap_all, need);
             if (results_fit_lds(h, x.ef, n)) {
@@ -1710,29 +1842,83 @@ nmn_status run_batch(nmn_hnsw* h, const std::vector<HostWalk*>& batch) {
         w.qef = w.qk + N;
         HN_TRY(hipMemcpyAsync(h->hq.p, h->st_q.data(), (size_t)N * dim * 4, hipMemcpyHostToDevice, s));
         HN_TRY(hipMemcpyAsync(h->hkef.p, h->st_kef.data(), (size_t)2 * N * 4, hipMemcpyHostToDevice, s));
-        {
-            std::lock_guard<std::mutex> slk(sc->mu);
-            nmn_status st = enqueue_walk_locked(h, sc, (const float*)h->hq.p, N, w, (uint64_t*)h->hids.p, (float*)h->hsc.p,
-                                                (uint32_t*)h->hcnt.p, s);
-            if (st != NMN_OK) return st;
+        // the metric slots: what the re-rank and ordering launches read, and the rows they answer into (row m = the m-th metric slot)
+        if (M) {
+            xmetric_batch_plan(h->st_xitems.data(), M, N, h->st_xmeta, plan);
+            HN_TRY(grow(h->hxmeta, h->st_xmeta.size() * 4, none, &synced));
+            HN_TRY(grow(h->hxsim, (size_t)N * kstride * 4, none, &synced));
+            HN_TRY(grow(h->hxoids, (size_t)M * topmax * 8, none, &synced));
+            HN_TRY(grow(h->hxosc, (size_t)M * topmax * 4, none, &synced));
+            HN_TRY(grow(h->hxocnt, (size_t)M * 4, none, &synced));
+            HN_TRY(grow(h->hxsort, plan.sort_bytes, none, &synced));
+            HN_TRY(hipMemcpyAsync(h->hxmeta.p, h->st_xmeta.data(), h->st_xmeta.size() * 4, hipMemcpyHostToDevice, s));
+            h->st_xoids.resize((size_t)M * topmax);
+            h->st_xosc.resize((size_t)M * topmax);
+            h->st_xocnt.resize(M);
         }
         h->st_ids.resize((size_t)N * kstride);
         h->st_sc.resize((size_t)N * kstride);
         h->st_cnt.resize(N);
-        HN_TRY(hipMemcpyAsync(h->st_ids.data(), h->hids.p, (size_t)N * kstride * 8, hipMemcpyDeviceToHost, s));
-        HN_TRY(hipMemcpyAsync(h->st_sc.data(), h->hsc.p, (size_t)N * kstride * 4, hipMemcpyDeviceToHost, s));
-        HN_TRY(hipMemcpyAsync(h->st_cnt.data(), h->hcnt.p, (size_t)N * 4, hipMemcpyDeviceToHost, s));
+        if (!on_host) {
+            {
+                std::lock_guard<std::mutex> slk(sc->mu);
+                nmn_status st = enqueue_walk_locked(h, sc, (const float*)h->hq.p, N, w, (uint64_t*)h->hids.p, (float*)h->hsc.p,
+                                                    (uint32_t*)h->hcnt.p, s);
+                if (st != NMN_OK) return st;
+            }
+            nmn_status st = metric_chain();
+            if (st != NMN_OK) return st;
+            if (M < N) {  // (a metric slot's walk rows stay on the device)
+                HN_TRY(hipMemcpyAsync(h->st_ids.data(), h->hids.p, (size_t)N * kstride * 8, hipMemcpyDeviceToHost, s));
+                HN_TRY(hipMemcpyAsync(h->st_sc.data(), h->hsc.p, (size_t)N * kstride * 4, hipMemcpyDeviceToHost, s));
+            }
+            HN_TRY(hipMemcpyAsync(h->st_cnt.data(), h->hcnt.p, (size_t)N * 4, hipMemcpyDeviceToHost, s));
+        } else {
+            std::fill(fl.begin(), fl.end(), 1u);  // every walk is the host's
+            std::fill(ev.begin(), ev.end(), 0u);
+        }
     }
-    HN_TRY(hipMemcpyAsync(fl.data(), sc->flags.p, (size_t)N * 4, hipMemcpyDeviceToHost, s));
-    HN_TRY(hipMemcpyAsync(ev.data(), sc->evals.p, (size_t)N * 4, hipMemcpyDeviceToHost, s));
-    HN_TRY(hipStreamSynchronize(s));
-    static thread_local HostVisited vis;
-    for (uint32_t j = 0; j < N; j++) {
+    if (!on_host) {
+        HN_TRY(hipMemcpyAsync(fl.data(), sc->flags.p, (size_t)N * 4, hipMemcpyDeviceToHost, s));
+        HN_TRY(hipMemcpyAsync(ev.data(), sc->evals.p, (size_t)N * 4, hipMemcpyDeviceToHost, s));
+        HN_TRY(hipStreamSynchronize(s));
+    }
+    // a metric slot the spill launch could not answer (cannot happen while its heap holds n entries), or every one under on_host: the
+    // host walks it into the launch's row, the rows go up again, and the device re-ranks again
+    uint32_t redo = 0;
+    for (uint32_t j = 0; j < N && M; j++) {
+        const Slot& x = slot[j];
+        if (!x.xm || fl[j] != 1u) continue;
+        uint64_t* ids = h->st_ids.data() + (size_t)j * kstride;
+        float* scs = h->st_sc.data() + (size_t)j * kstride;
+        uint64_t e2 = 0;
+        host_search_one(h, x.r->q + (size_t)x.i * dim, x.k, x.ef, vis, ids, scs, &h->st_cnt[j], &e2);
+        pad_row(ids, scs, x.k, kstride);
+        ev[j] = (uint32_t)e2;
+        HN_TRY(hipMemcpyAsync((uint64_t*)h->hids.p + (size_t)j * kstride, ids, (size_t)kstride * 8, hipMemcpyHostToDevice, s));
+        redo++;
+    }
+    if (redo) {
+        HN_TRY(hipMemcpyAsync(h->hcnt.p, h->st_cnt.data(), (size_t)N * 4, hipMemcpyHostToDevice, s));
+        const nmn_status st = metric_chain();
+        if (st != NMN_OK) return st;
+        HN_TRY(hipStreamSynchronize(s));
+    }
+    for (uint32_t j = 0, m = 0; j < N; j++) {
         const Slot& x = slot[j];
         HostWalk* r = x.r;
         uint64_t* ids = r->out_ids + (size_t)x.i * r->kstride;
         float* scs = r->out_scores + (size_t)x.i * r->kstride;
-        if (fl[j] == 1u) {  // the spill launch could not answer it (cannot happen while its heap holds n entries): the host walk does
+        if (x.xm) {  // row m of the ordering's answers; the large-k sort wrote only the first top_k slots of its rows
+            const uint32_t c = std::min(x.top, r->kstride);
+            memcpy(ids, h->st_xoids.data() + (size_t)m * topmax, (size_t)c * 8);
+            memcpy(scs, h->st_xosc.data() + (size_t)m * topmax, (size_t)c * 4);
+            pad_row(ids, scs, c, r->kstride);
+            r->out_counts[x.i] = h->st_xocnt[m];
+            r->rescored = std::max(r->rescored, std::min(h->st_cnt[j], x.k));
+            if (!on_host && fl[j] != 0u) r->spilled++;
+            m++;
+        } else if (fl[j] == 1u) {  // the spill launch could not answer it (cannot happen while its heap holds n entries): the host walk does
             uint64_t e2 = 0;
             host_search_one(h, r->q + (size_t)x.i * dim, x.k, x.ef, vis, ids, scs, r->out_counts + x.i, &e2);
             pad_row(ids, scs, x.k, r->kstride);
@@ -1784,6 +1970,29 @@ nmn_status host_walk_call(nmn_hnsw* h, HostWalk& me, nmn_search_stats* stats) {
         stats->fallback_queries = me.spilled;
         std::shared_lock<std::shared_mutex> g(h->rw);
         stats->sweep_kind = h->level.empty() ? NMN_SWEEP_NONE : NMN_SWEEP_GRAPH;
+        stats->sweep_launches = on_host ? 0 : 2;
+    }
+    return NMN_OK;
+}
+
+// nmn_hnsw_search_metric and nmn_hnsw_search_metric_multi behind their argument checks
+nmn_status metric_walk_call(nmn_hnsw* h, HostWalk& me, nmn_search_stats* stats) {
+    const bool on_host = host_search_forced();
+    bool empty;
+    {
+        std::shared_lock<std::shared_mutex> g(h->rw);
+        empty = h->level.empty();
+        for (uint32_t i = 0; i < me.nq && !me.alone; i++) me.alone = metric_candidates(h, me.k_of(i)) > kShareCandMax;
+    }
+    // the host walk has no turn to take at the queue, but the re-rank runs on the handle's own stream: run_batch, alone
+    const nmn_status st = on_host ? run_batch(h, std::vector<HostWalk*>{&me}, true) : submit_walk(h, me);
+    if (st != NMN_OK) return st;
+    if (stats) {
+        stats->rows_scanned = me.evals;
+        stats->bytes_scanned = me.evals * h->dim * 4;
+        stats->candidates_rescored = me.rescored;
+        stats->fallback_queries = me.spilled;
+        stats->sweep_kind = empty ? NMN_SWEEP_NONE : NMN_SWEEP_GRAPH;
         stats->sweep_launches = on_host ? 0 : 2;
     }
     return NMN_OK;
@@ -1882,94 +2091,48 @@ extern "C" nmn_status nmn_hnsw_search_metric(nmn_hnsw* h, const float* queries, 
     }
     if (nq == 0) return NMN_OK;
     if (!queries || !out_ids || !out_scores || !out_counts) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
-    std::shared_lock<std::shared_mutex> g(h->rw);
-    const uint64_t c64 = metric_candidates(h, top_k);
-    const uint32_t c = (uint32_t)c64;
-    const bool on_host = host_search_forced();
-    uint64_t evals = 0;
-    uint32_t spilled = 0, rescored = 0;
-    std::lock_guard<std::mutex> hl(h->host_mu);  // host callers take turns on the handle's own stream and staging
-    HN_TRY(hipSetDevice(h->device));
-    hipStream_t s = h->host_stream;
-    bool synced = true;  // (every earlier host call ended with a wait)
-    const hipStream_t none = (hipStream_t)-1;
-    HN_TRY(grow(h->hq, (size_t)nq * h->dim * 4, none, &synced));
-    HN_TRY(grow(h->hids, (size_t)nq * top_k * 8, none, &synced));
-    HN_TRY(grow(h->hsc, (size_t)nq * top_k * 4, none, &synced));
-    HN_TRY(grow(h->hcnt, (size_t)nq * 4, none, &synced));
-    // host_mu makes this caller the only one on host_stream; sc->mu is held all the same, for the whole call: the candidate block
-    // is read back and, should a query stay flagged, filled again
-    nmn_hnsw::Scratch* sc = scratch_of(h, s);
-    std::lock_guard<std::mutex> slk(sc->mu);
-    st = metric_scratch(sc, s, nq, c, top_k);
-    if (st != NMN_OK) return st;
-    HN_TRY(hipMemcpyAsync(h->hq.p, queries, (size_t)nq * h->dim * 4, hipMemcpyHostToDevice, s));
-    std::vector<uint64_t> cid;
-    std::vector<float> csc;
-    std::vector<uint32_t> ccnt(nq), fl(nq, 0), ev(nq, 0);
-    auto host_walk = [&](uint32_t q) {  // the walk of query q on the host, its candidates into the staging vectors
-        static thread_local HostVisited vis;
-        if (cid.empty()) {
-            cid.resize((size_t)nq * c);
-            csc.resize((size_t)nq * c);
-        }
-        uint64_t e2 = 0;
-        host_search_one(h, queries + (size_t)q * h->dim, c, h->cfg.ef_search, vis, cid.data() + (size_t)q * c, csc.data() + (size_t)q * c,
-                        &ccnt[q], &e2);
-        ev[q] = (uint32_t)e2;
-    };
-    if (on_host) {
-        for (uint32_t q = 0; q < nq; q++) host_walk(q);
-        HN_TRY(hipMemcpyAsync(sc->xids.p, cid.data(), (size_t)nq * c * 8, hipMemcpyHostToDevice, s));
-        HN_TRY(hipMemcpyAsync(sc->xcnt.p, ccnt.data(), (size_t)nq * 4, hipMemcpyHostToDevice, s));
-    } else {
-        st = enqueue_search_locked(h, sc, (const float*)h->hq.p, nq, c, 0, (uint64_t*)sc->xids.p, (float*)sc->xsc.p, (uint32_t*)sc->xcnt.p, s);
-        if (st != NMN_OK) return st;
+    HostWalk me;  // through the coalescer like nmn_hnsw_search (docs/hnsw.md §12); a lone call is the uniform chain it always was
+    me.q = queries;
+    me.nq = nq;
+    me.k1 = me.kstride = top_k;
+    me.xm = metric;
+    me.out_ids = out_ids;
+    me.out_scores = out_scores;
+    me.out_counts = out_counts;
+    return metric_walk_call(h, me, stats);
+}
+
+extern "C" nmn_status nmn_hnsw_search_metric_multi(nmn_hnsw* h, const float* queries, uint32_t nq, const uint32_t* top_k,
+                                                   const nmn_xmetric* metrics, uint32_t kstride, uint64_t* out_ids, float* out_scores,
+                                                   uint32_t* out_counts, nmn_search_stats* stats) {
+    if (!h) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (h->storage != NMN_HNSW_STORAGE_DENSE) {
+        nmn_xmetric any{NMN_XMETRIC_COSINE, 0.0f, 0.0f, 0.0f};
+        return check_metric_call(h, 1, &any);  // the quantized handle's refusal, in nmn_hnsw_search_metric's words
     }
-    st = enqueue_rerank(h, sc, (const float*)h->hq.p, nq, c, top_k, *metric, (uint64_t*)h->hids.p, (float*)h->hsc.p, (uint32_t*)h->hcnt.p, s);
-    if (st != NMN_OK) return st;
-    HN_TRY(hipMemcpyAsync(out_ids, h->hids.p, (size_t)nq * top_k * 8, hipMemcpyDeviceToHost, s));
-    HN_TRY(hipMemcpyAsync(out_scores, h->hsc.p, (size_t)nq * top_k * 4, hipMemcpyDeviceToHost, s));
-    HN_TRY(hipMemcpyAsync(out_counts, h->hcnt.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
-    if (!on_host) {
-        HN_TRY(hipMemcpyAsync(ccnt.data(), sc->xcnt.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
-        HN_TRY(hipMemcpyAsync(fl.data(), sc->flags.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
-        HN_TRY(hipMemcpyAsync(ev.data(), sc->evals.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
-    }
-    HN_TRY(hipStreamSynchronize(s));
-    bool redo = false;
-    for (uint32_t q = 0; q < nq; q++) {
-        if (fl[q] == 1u) redo = true;  // the spill launch could not answer it (cannot happen while its heap holds n entries)
-        if (fl[q] != 0u) spilled++;
-    }
-    if (redo) {  // ... then the host walks every query and the device re-ranks again
-        cid.resize((size_t)nq * c);
-        csc.resize((size_t)nq * c);
-        HN_TRY(hipMemcpy(cid.data(), sc->xids.p, (size_t)nq * c * 8, hipMemcpyDeviceToHost));
-        for (uint32_t q = 0; q < nq; q++)
-            if (fl[q] == 1u) host_walk(q);
-        HN_TRY(hipMemcpyAsync(sc->xids.p, cid.data(), (size_t)nq * c * 8, hipMemcpyHostToDevice, s));
-        HN_TRY(hipMemcpyAsync(sc->xcnt.p, ccnt.data(), (size_t)nq * 4, hipMemcpyHostToDevice, s));
-        st = enqueue_rerank(h, sc, (const float*)h->hq.p, nq, c, top_k, *metric, (uint64_t*)h->hids.p, (float*)h->hsc.p, (uint32_t*)h->hcnt.p, s);
-        if (st != NMN_OK) return st;
-        HN_TRY(hipMemcpyAsync(out_ids, h->hids.p, (size_t)nq * top_k * 8, hipMemcpyDeviceToHost, s));
-        HN_TRY(hipMemcpyAsync(out_scores, h->hsc.p, (size_t)nq * top_k * 4, hipMemcpyDeviceToHost, s));
-        HN_TRY(hipMemcpyAsync(out_counts, h->hcnt.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
-        HN_TRY(hipStreamSynchronize(s));
-    }
-    for (uint32_t q = 0; q < nq; q++) {
-        evals += ev[q];
-        rescored = std::max(rescored, std::min(ccnt[q], c));
+    if (kstride == 0) return set_error(NMN_ERR_INVALID_TOP_K, "kstride == 0");
+    if (nq && (!queries || !top_k || !metrics || !out_ids || !out_scores || !out_counts)) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    for (uint32_t i = 0; i < nq; i++) {  // before the call joins a batch: a bad call fails alone, and nothing is written
+        if (top_k[i] == 0) return set_error(NMN_ERR_INVALID_TOP_K, "top_k == 0");
+        if (top_k[i] > kstride) return set_error(NMN_ERR_INVALID_ARGUMENT, "HNSW: top_k[i] above kstride, the row stride of the outputs");
+        if (!xmetric_valid(&metrics[i])) return set_error(NMN_ERR_CONFIGURATION, "unknown extended distance metric");
     }
     if (stats) {
-        stats->rows_scanned = evals;
-        stats->bytes_scanned = evals * h->dim * 4;
-        stats->candidates_rescored = rescored;
-        stats->fallback_queries = spilled;
-        stats->sweep_kind = h->level.empty() ? NMN_SWEEP_NONE : NMN_SWEEP_GRAPH;
-        stats->sweep_launches = on_host ? 0 : 2;
+        memset(stats, 0, sizeof *stats);
+        stats->scan_ms = stats->total_ms = -1.0f;
     }
-    return NMN_OK;
+    if (nq == 0) return NMN_OK;
+    HostWalk me;
+    me.q = queries;
+    me.nq = nq;
+    me.k = top_k;
+    me.xm = metrics;
+    me.xm_stride = 1;
+    me.kstride = kstride;
+    me.out_ids = out_ids;
+    me.out_scores = out_scores;
+    me.out_counts = out_counts;
+    return metric_walk_call(h, me, stats);
 }
 
 // ---- persistence (docs/hnsw.md §10) ----------------------------------------------------------------------------------------------

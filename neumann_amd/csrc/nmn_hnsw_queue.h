@@ -13,9 +13,12 @@
 
 namespace nmn {
 
+constexpr uint32_t kShareCandMax = 4096;  // a metric call that asks for more candidates than this runs alone: the launch's rows are
+                                          // N x max k, and one huge caller must not size them for a thousand others
 constexpr uint32_t kBatchQueries = 1024;  // queries a coalesced batch carries at most: four waves per CU, the largest call §6 measured
 
-// One call of nmn_hnsw_search (k1 / ef1) or nmn_hnsw_search_multi (k / ef per query) on its way through the coalescer.
+// One call of nmn_hnsw_search (k1 / ef1), nmn_hnsw_search_multi (k / ef per query), nmn_hnsw_search_metric (xm, one metric; k1 its
+// top_k) or nmn_hnsw_search_metric_multi (xm, xm_stride 1: a metric per query; k their top_k) on its way through the coalescer.
 struct HostWalk {
     const float* q = nullptr;
     uint32_t nq = 0, k1 = 0, ef1 = 0, kstride = 0;
@@ -24,6 +27,10 @@ struct HostWalk {
     uint64_t* out_ids = nullptr;
     float* out_scores = nullptr;
     uint32_t* out_counts = nullptr;
+    const nmn_xmetric* xm = nullptr;  // a metric call (docs/hnsw.md §12): k_of(i) is query i's top_k, metric_of(i) its metric
+    uint32_t xm_stride = 0;
+    bool alone = false;               // nobody rides with this call, and it rides with nobody (a metric call with c above kShareCandMax)
+    uint32_t rescored = 0;            // filled like evals: the largest candidate count re-ranked
     // filled by the leader of the batch this call rode in
     uint64_t evals = 0;
     uint32_t spilled = 0;
@@ -32,6 +39,7 @@ struct HostWalk {
     bool done = false, lead = false;
     std::condition_variable cv;
     uint32_t k_of(uint32_t i) const { return k ? k[i] : k1; }
+    const nmn_xmetric& metric_of(uint32_t i) const { return xm[(size_t)i * xm_stride]; }
     uint32_t ef_of(uint32_t i, uint32_t ef_search) const {  // hnsw.rs:2102
         const uint32_t e = ef ? ef[i] : ef1;
         return std::max<uint32_t>(e ? e : ef_search, k_of(i));
@@ -47,7 +55,8 @@ struct WalkQueue {
 
 // queue / lead / ride.  One batch runs at a time.  A call that finds one running waits in `waiting`; when the batch ends, its
 // leader makes the oldest waiter the next leader, and that one takes along every call waiting behind it, in arrival order, up to
-// kBatchQueries queries.  (A call that does not fit stays first in line for the batch after.)  run(batch) -> status is the
+// kBatchQueries queries.  (A call that does not fit stays first in line for the batch after; so does a call marked `alone`, which
+// then leads a batch of one.)  run(batch) -> status is the
 // batch's work, batch[0] being the leader's own call; a failure is every call's of the batch: riders get the status and
 // last_error()'s text (taken on the leader's thread) in HostWalk::st / err.  Returns this call's status.
 template <class Run, class LastError>
@@ -63,7 +72,8 @@ nmn_status coalesce_walk(WalkQueue& q, HostWalk& me, Run&& run, LastError&& last
             q.busy = true;
         }
         uint32_t total = me.nq;
-        while (!q.waiting.empty() && (uint64_t)total + q.waiting.front()->nq <= kBatchQueries) {
+        while (!me.alone && !q.waiting.empty() && !q.waiting.front()->alone &&
+               (uint64_t)total + q.waiting.front()->nq <= kBatchQueries) {
             batch.push_back(q.waiting.front());
             total += q.waiting.front()->nq;
             q.waiting.pop_front();

@@ -13,6 +13,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "../../include/neumann_gpu.h"
 
 namespace nmn {
@@ -480,6 +482,31 @@ hipError_t launch_xmetric_rerank(const float* rows, uint32_t ld, uint32_t dim, u
                                  uint32_t c, const uint64_t* cand_ids, const uint32_t* cand_counts, const nmn_xmetric& m,
                                  uint32_t top_k, float* sim, uint64_t* out_ids, float* out_scores, uint32_t* out_counts,
                                  void* order_scratch, hipStream_t s);
+
+// The same for a coalesced batch whose queries bring their own top_k and metric (docs/hnsw.md §12).  The batch's N queries sit where
+// a per-query walk left them: candidate rows kstride apart, the walk's counts.  items[m] (m < M) names the metric queries: q its
+// place in the batch, c its candidate count, top_k, metric.  xmetric_batch_plan groups them by chain family and writes the u32 words
+// the launches read (meta, to be copied to the device as they are); the launches then are at most one re-rank per family present,
+// one rank-count ordering, and the large-k sort for every query with c above the sort threshold, alone.  Output row m is
+// out_stride long; the sort writes only its first top_k slots (the caller pads the rest).  sim: N x kstride floats.
+struct XmetricBatchItem {
+    uint32_t q, c, top_k;
+    nmn_xmetric m;
+};
+struct XmetricBatchPlan {
+    const XmetricBatchItem* items = nullptr;
+    uint32_t N = 0, M = 0, sort_from = 0;
+    uint32_t fam_off[7] = {};  // fsel[fam_off[f] .. fam_off[f + 1]): the queries of chain family f
+    uint32_t fam_c[6] = {};    // the longest candidate list among them
+    uint32_t rank_len = 0;     // max(c, top_k) over the queries the rank count orders (0: none)
+    size_t sort_bytes = 0;     // scratch of the large-k sort (0: no query takes it)
+};
+void xmetric_batch_plan(const XmetricBatchItem* items, uint32_t M, uint32_t N, std::vector<uint32_t>& meta, XmetricBatchPlan& plan);
+hipError_t launch_xmetric_rerank_batch(const float* rows, uint32_t ld, uint32_t dim, uint64_t n_rows, const float* queries,
+                                       uint32_t kstride, const uint64_t* cand_ids, const uint32_t* cand_counts,
+                                       const XmetricBatchPlan& plan, const uint32_t* meta_dev, float* sim, uint32_t out_stride,
+                                       uint64_t* out_ids, float* out_scores, uint32_t* out_counts, void* sort_scratch_dev,
+                                       hipStream_t s);
 
 // synthetic data
 hipError_t launch_synth_fill(float* corpus, uint32_t ld, uint32_t dim, uint64_t seed, uint64_t global_row0,

@@ -20,6 +20,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "nmn_index.h"
@@ -217,11 +218,28 @@ struct RerankArgs {
     float cw, sw, mw;
 };
 
-template <int CH>
-__global__ __launch_bounds__(256) void xmetric_rerank_kernel(RerankArgs p) {
+// PERQ == true (docs/hnsw.md §12): workgroup row y serves query qsel[y] of a coalesced batch.  The candidates are read where the walk
+// left them (rows kstride apart, the walk's own count), kind and weights are the query's own, the scores go to sim rows kstride
+// apart.  CH stays the launch's: one launch per chain family present, over that family's queries, so a query runs the
+// instantiation it gets alone.  PERQ == false is the kernel as it has always been.
+struct RerankArgsQ : RerankArgs {
+    const uint32_t* qsel;  // [gridDim.y] queries of this launch
+    const int* qkind;      // [batch] by query
+    const float* qcw;
+    const float* qsw;
+    const float* qmw;
+    uint32_t kstride;
+};
+
+template <int CH, bool PERQ>
+__global__ __launch_bounds__(256) void xmetric_rerank_kernel(std::conditional_t<PERQ, RerankArgsQ, RerankArgs> p) {
     __shared__ double s_mag;
     __shared__ uint32_t s_na;
-    const uint32_t q = blockIdx.y;
+    uint32_t q = blockIdx.y;
+    if constexpr (PERQ) {
+        q = p.qsel[blockIdx.y];
+        if (blockIdx.x * kPairsPerBlock >= min(p.counts[q], p.kstride)) return;  // (the grid is as wide as the launch's longest list)
+    }
     const uint32_t l = threadIdx.x & 7u, g = threadIdx.x >> 3;
     const float* a = p.queries + (size_t)q * p.dim;
     if (threadIdx.x < 8u) {  // the query's own constants: sum of squares in index order and stored positions, once
@@ -245,21 +263,35 @@ __global__ __launch_bounds__(256) void xmetric_rerank_kernel(RerankArgs p) {
     __syncthreads();
     const double mag_a = s_mag;
     const uint32_t na = s_na;
-    const uint32_t count = p.counts ? min(p.counts[q], p.c) : p.c;
+    uint32_t count, id_stride, row_len;
+    int kind = p.kind;
+    float cw = p.cw, sw = p.sw, mw = p.mw;
+    if constexpr (PERQ) {
+        count = min(p.counts[q], p.kstride);
+        id_stride = row_len = p.kstride;
+        kind = p.qkind[q];
+        cw = p.qcw[q];
+        sw = p.qsw[q];
+        mw = p.qmw[q];
+    } else {
+        count = p.counts ? min(p.counts[q], p.c) : p.c;
+        id_stride = p.id_stride;
+        row_len = p.c;
+    }
     const uint32_t first = blockIdx.x * kPairsPerBlock;
     const uint32_t last = min(first + kPairsPerBlock, count);
     for (uint32_t e0 = first; e0 < last; e0 += kPairsPerRound) {
         const uint32_t e = e0 + g;
         const bool used = e < last;
-        const uint64_t id = used ? p.ids[(size_t)q * p.id_stride + e] : ~0ull;
+        const uint64_t id = used ? p.ids[(size_t)q * id_stride + e] : ~0ull;
         const bool readable = id < p.n_rows;
         const float* b = readable ? p.rows + (size_t)id * p.ld : a;  // (an unused group runs on the query: the wave stays whole)
         const PairSums s = pair_pass<CH>(a, b, p.dim, l);
         if (!used || l != 0u) continue;
-        const float raw = readable ? finish_pair(p.kind, s, mag_a, na, p.cw, p.sw, p.mw) : __int_as_float(0x7FC00000);
-        const size_t o = (size_t)q * p.c + e;
+        const float raw = readable ? finish_pair(kind, s, mag_a, na, cw, sw, mw) : __int_as_float(0x7FC00000);
+        const size_t o = (size_t)q * row_len + e;
         if (p.raw) p.raw[o] = raw;
-        if (p.sim) p.sim[o] = xm_to_similarity(p.kind, raw);
+        if (p.sim) p.sim[o] = xm_to_similarity(kind, raw);
     }
 }
 
@@ -280,29 +312,45 @@ __device__ __forceinline__ bool ranks_before(float sj, uint32_t j, float se, uin
     if (nj || ne) return (!nj && ne) || (nj && ne && j < e);
     return sj > se || (sj == se && j < e);
 }
-__global__ __launch_bounds__(256) void xmetric_order_kernel(OrderArgs p) {
-    const uint32_t q = blockIdx.y;
-    const uint32_t count = min(p.counts[q], p.c);
-    const float* s = p.sim + (size_t)q * p.c;
-    const uint64_t* ids = p.ids + (size_t)q * p.c;
-    uint64_t* o_ids = p.out_ids + (size_t)q * p.top_k;
-    float* o_sc = p.out_scores + (size_t)q * p.top_k;
+// PERQ == true (docs/hnsw.md §12): workgroup row y orders query qsel[y] of a coalesced batch into output row y: top_k is the
+// query's own (qtop[y]; 0 = this query's ordering is the large-k sort's, nothing to do here), input rows are kstride apart, output
+// rows out_stride apart, and slots [min(count, top_k), out_stride) get the sentinels.  PERQ == false is the kernel as it has always been.
+struct OrderArgsQ : OrderArgs {
+    const uint32_t* qsel;  // [gridDim.y]
+    const uint32_t* qtop;  // [gridDim.y]
+    uint32_t kstride, out_stride;
+};
+template <bool PERQ>
+__global__ __launch_bounds__(256) void xmetric_order_kernel(std::conditional_t<PERQ, OrderArgsQ, OrderArgs> p) {
+    uint32_t q = blockIdx.y, o = blockIdx.y, in_stride = p.c, out_len = p.top_k, top_k = p.top_k;
+    if constexpr (PERQ) {
+        q = p.qsel[blockIdx.y];
+        top_k = p.qtop[blockIdx.y];
+        if (top_k == 0u) return;
+        in_stride = p.kstride;
+        out_len = p.out_stride;
+    }
+    const uint32_t count = min(p.counts[q], in_stride);
+    const float* s = p.sim + (size_t)q * in_stride;
+    const uint64_t* ids = p.ids + (size_t)q * in_stride;
+    uint64_t* o_ids = p.out_ids + (size_t)o * out_len;
+    float* o_sc = p.out_scores + (size_t)o * out_len;
     const uint32_t stride = gridDim.x * 256u;
     for (uint32_t e = blockIdx.x * 256u + threadIdx.x; e < count; e += stride) {
         const float se = s[e];
         uint32_t rank = 0;
         for (uint32_t j = 0; j < count; j++) rank += ranks_before(s[j], j, se, e) ? 1u : 0u;
-        if (rank < p.top_k) {
+        if (rank < top_k) {
             o_ids[rank] = ids[e];
             o_sc[rank] = se;
         }
     }
-    const uint32_t n_out = min(count, p.top_k);
-    for (uint32_t i = n_out + blockIdx.x * 256u + threadIdx.x; i < p.top_k; i += stride) {
+    const uint32_t n_out = min(count, top_k);
+    for (uint32_t i = n_out + blockIdx.x * 256u + threadIdx.x; i < out_len; i += stride) {
         o_ids[i] = ~0ull;
         o_sc[i] = __int_as_float(0xFF800000u);
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0) p.out_counts[q] = n_out;
+    if (blockIdx.x == 0 && threadIdx.x == 0) p.out_counts[o] = n_out;
 }
 
 // ---- more candidates than the rank count should order: the large-k sort (nmn_sortk.hip) --------------------------------------
@@ -355,12 +403,12 @@ hipError_t launch_rerank(const RerankArgs& a, hipStream_t s) {
     if (a.nq == 0 || a.c == 0) return hipSuccess;
     const dim3 grid((a.c + kPairsPerBlock - 1) / kPairsPerBlock, a.nq);
     switch (chains_of(a.kind)) {
-        case kChCos: hipLaunchKernelGGL(xmetric_rerank_kernel<kChCos>, grid, dim3(256), 0, s, a); break;
-        case kChSet: hipLaunchKernelGGL(xmetric_rerank_kernel<kChSet>, grid, dim3(256), 0, s, a); break;
-        case kChWJ: hipLaunchKernelGGL(xmetric_rerank_kernel<kChWJ>, grid, dim3(256), 0, s, a); break;
-        case kChEucl: hipLaunchKernelGGL(xmetric_rerank_kernel<kChEucl>, grid, dim3(256), 0, s, a); break;
-        case kChManh: hipLaunchKernelGGL(xmetric_rerank_kernel<kChManh>, grid, dim3(256), 0, s, a); break;
-        default: hipLaunchKernelGGL(xmetric_rerank_kernel<kChComposite>, grid, dim3(256), 0, s, a); break;
+        case kChCos: hipLaunchKernelGGL((xmetric_rerank_kernel<kChCos, false>), grid, dim3(256), 0, s, a); break;
+        case kChSet: hipLaunchKernelGGL((xmetric_rerank_kernel<kChSet, false>), grid, dim3(256), 0, s, a); break;
+        case kChWJ: hipLaunchKernelGGL((xmetric_rerank_kernel<kChWJ, false>), grid, dim3(256), 0, s, a); break;
+        case kChEucl: hipLaunchKernelGGL((xmetric_rerank_kernel<kChEucl, false>), grid, dim3(256), 0, s, a); break;
+        case kChManh: hipLaunchKernelGGL((xmetric_rerank_kernel<kChManh, false>), grid, dim3(256), 0, s, a); break;
+        default: hipLaunchKernelGGL((xmetric_rerank_kernel<kChComposite, false>), grid, dim3(256), 0, s, a); break;
     }
     return hipGetLastError();
 }
@@ -410,8 +458,124 @@ hipError_t launch_xmetric_rerank(const float* rows, uint32_t ld, uint32_t dim, u
     }
     OrderArgs o{sim, cand_ids, cand_counts, out_ids, out_scores, out_counts, c, top_k};
     const uint32_t gx = std::max<uint32_t>(1, std::min<uint32_t>((std::max(c, top_k) + 255u) / 256u, 1024u));
-    hipLaunchKernelGGL(xmetric_order_kernel, dim3(gx, nq), dim3(256), 0, s, o);
+    hipLaunchKernelGGL(xmetric_order_kernel<false>, dim3(gx, nq), dim3(256), 0, s, o);
     return hipGetLastError();
+}
+
+// ---- a coalesced batch: a top_k and a metric per query (docs/hnsw.md §12) ------------------------------------------------------------
+// meta (u32 words, host staging and device copy alike): msel[M] | qtop[M] | fsel[M] | kind[N] | cw[N] | sw[N] | mw[N] — msel: the
+// metric queries in output-row order, qtop: their top_k (0: ordered by the sort), fsel: the same queries grouped by chain family.
+void xmetric_batch_plan(const XmetricBatchItem* items, uint32_t M, uint32_t N, std::vector<uint32_t>& meta, XmetricBatchPlan& plan) {
+    plan = XmetricBatchPlan{};
+    plan.items = items;
+    plan.N = N;
+    plan.M = M;
+    meta.assign((size_t)3 * M + (size_t)4 * N, 0u);
+    uint32_t* msel = meta.data();
+    uint32_t* qtop = msel + M;
+    uint32_t* fsel = qtop + M;
+    uint32_t* kind = fsel + M;
+    uint32_t* w[3] = {kind + N, kind + 2 * (size_t)N, kind + 3 * (size_t)N};
+    const uint32_t from = plan.sort_from = sort_from();  // read once per batch; the launcher follows the plan
+    uint32_t fam_n[kChComposite + 1] = {};
+    for (uint32_t m = 0; m < M; m++) fam_n[chains_of(items[m].m.kind)]++;
+    for (int f = 0; f <= kChComposite; f++) plan.fam_off[f + 1] = plan.fam_off[f] + fam_n[f];
+    uint32_t fill[kChComposite + 1];
+    std::copy(plan.fam_off, plan.fam_off + kChComposite + 1, fill);
+    for (uint32_t m = 0; m < M; m++) {
+        const XmetricBatchItem& it = items[m];
+        const int f = chains_of(it.m.kind);
+        const bool sorted = it.c > from;
+        msel[m] = it.q;
+        qtop[m] = sorted ? 0u : it.top_k;
+        fsel[fill[f]++] = it.q;
+        plan.fam_c[f] = std::max(plan.fam_c[f], it.c);
+        kind[it.q] = (uint32_t)it.m.kind;
+        memcpy(&w[0][it.q], &it.m.cosine_weight, 4);
+        memcpy(&w[1][it.q], &it.m.structural_weight, 4);
+        memcpy(&w[2][it.q], &it.m.magnitude_weight, 4);
+        if (sorted)
+            plan.sort_bytes = std::max(plan.sort_bytes, sort_scratch(nullptr, it.c, it.top_k).bytes);
+        else
+            plan.rank_len = std::max(plan.rank_len, std::max(it.c, it.top_k));
+    }
+}
+
+hipError_t launch_xmetric_rerank_batch(const float* rows, uint32_t ld, uint32_t dim, uint64_t n_rows, const float* queries,
+                                       uint32_t kstride, const uint64_t* cand_ids, const uint32_t* cand_counts,
+                                       const XmetricBatchPlan& plan, const uint32_t* meta_dev, float* sim, uint32_t out_stride,
+                                       uint64_t* out_ids, float* out_scores, uint32_t* out_counts, void* sort_scratch_dev,
+                                       hipStream_t s) {
+    const uint32_t M = plan.M, N = plan.N;
+    if (M == 0) return hipSuccess;
+    const uint32_t* msel = meta_dev;
+    const uint32_t* qtop = msel + M;
+    const uint32_t* fsel = qtop + M;
+    RerankArgsQ a{};
+    a.rows = rows;
+    a.queries = queries;
+    a.ids = cand_ids;
+    a.counts = cand_counts;
+    a.raw = nullptr;
+    a.sim = sim;
+    a.n_rows = n_rows;
+    a.ld = ld;
+    a.dim = dim;
+    a.qkind = reinterpret_cast<const int*>(fsel + M);
+    a.qcw = reinterpret_cast<const float*>(fsel + M + N);
+    a.qsw = a.qcw + N;
+    a.qmw = a.qsw + N;
+    a.kstride = kstride;
+    for (int f = 0; f <= kChComposite; f++) {  // at most one launch per chain family present, over that family's queries
+        const uint32_t nf = plan.fam_off[f + 1] - plan.fam_off[f];
+        if (nf == 0 || plan.fam_c[f] == 0) continue;
+        a.qsel = fsel + plan.fam_off[f];
+        a.nq = nf;
+        const dim3 grid((plan.fam_c[f] + kPairsPerBlock - 1) / kPairsPerBlock, nf);
+        switch (f) {
+            case kChCos: hipLaunchKernelGGL((xmetric_rerank_kernel<kChCos, true>), grid, dim3(256), 0, s, a); break;
+            case kChSet: hipLaunchKernelGGL((xmetric_rerank_kernel<kChSet, true>), grid, dim3(256), 0, s, a); break;
+            case kChWJ: hipLaunchKernelGGL((xmetric_rerank_kernel<kChWJ, true>), grid, dim3(256), 0, s, a); break;
+            case kChEucl: hipLaunchKernelGGL((xmetric_rerank_kernel<kChEucl, true>), grid, dim3(256), 0, s, a); break;
+            case kChManh: hipLaunchKernelGGL((xmetric_rerank_kernel<kChManh, true>), grid, dim3(256), 0, s, a); break;
+            default: hipLaunchKernelGGL((xmetric_rerank_kernel<kChComposite, true>), grid, dim3(256), 0, s, a); break;
+        }
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    if (plan.rank_len) {  // every query the rank count orders, in one launch (the sorted ones' workgroups leave at once)
+        OrderArgsQ o{};
+        o.sim = sim;
+        o.ids = cand_ids;
+        o.counts = cand_counts;
+        o.out_ids = out_ids;
+        o.out_scores = out_scores;
+        o.out_counts = out_counts;
+        o.qsel = msel;
+        o.qtop = qtop;
+        o.kstride = kstride;
+        o.out_stride = out_stride;
+        const uint32_t gx = std::max<uint32_t>(1, std::min<uint32_t>((std::max(plan.rank_len, out_stride) + 255u) / 256u, 1024u));
+        hipLaunchKernelGGL(xmetric_order_kernel<true>, dim3(gx, M), dim3(256), 0, s, o);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    if (plan.sort_bytes) {  // more candidates than the rank count should order: each such query alone, exactly as in a lone call
+        for (uint32_t m = 0; m < M; m++) {
+            const XmetricBatchItem& it = plan.items[m];
+            if (it.c <= plan.sort_from) continue;
+            const SortScratch w = sort_scratch(sort_scratch_dev, it.c, it.top_k);
+            const uint32_t gc = std::min<uint32_t>((it.c + 255u) / 256u, 4096u), gk = std::min<uint32_t>((it.top_k + 255u) / 256u, 4096u);
+            const float* sim_q = sim + (size_t)it.q * kstride;
+            hipLaunchKernelGGL(xmetric_sort_prep_kernel, dim3(gc), dim3(256), 0, s, sim_q, cand_counts + it.q, it.c, w.bits);
+            const hipError_t e = launch_largek(w.bits, it.c, w.keys, it.top_k, 0, w.pos, w.scores, out_counts + m, s);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL(xmetric_sort_gather_kernel, dim3(gk), dim3(256), 0, s, w.pos, sim_q, cand_ids + (size_t)it.q * kstride, it.c,
+                               it.top_k, out_ids + (size_t)m * out_stride, out_scores + (size_t)m * out_stride);
+        }
+        return hipGetLastError();
+    }
+    return hipSuccess;
 }
 
 }  // namespace nmn

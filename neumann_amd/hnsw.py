@@ -342,6 +342,32 @@ class GpuHnsw:
                                                      C.c_void_p(counts.ctypes.data), C.byref(st)))
         return (ids, sc, counts, st) if with_stats else (ids, sc, counts)
 
+    def search_metric_multi(self, queries, top_k, metrics, kstride=None, with_stats=False):
+        """`search_metric` with a top_k and a metric per query in ONE call (nmn_hnsw_search_metric_multi).  `top_k`: one integer
+        per query; `metrics`: one ExtendedDistanceMetric per query; `kstride`: row length of the outputs (None: max(top_k)).
+        -> (ids u64 [nq,kstride], scores f32 [nq,kstride], counts u32 [nq]); row i is what search_metric(q_i, top_k[i],
+        metrics[i]) answers."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.shape[1] != self.dim:
+            raise _capi.NeumannGpuError(_capi.ERR_DIMENSION_MISMATCH, f"expected {self.dim}, got {q.shape[1]}")
+        nq = q.shape[0]
+        kk = np.ascontiguousarray(top_k, dtype=np.uint32).reshape(-1)
+        metrics = list(metrics)
+        if kk.size != nq or len(metrics) != nq:
+            raise _capi.NeumannGpuError(_capi.ERR_INVALID_ARGUMENT, "one top_k and one metric per query")
+        mm = (_capi.XMetric * max(nq, 1))(*[m._c() for m in metrics])
+        ks = int(kk.max()) if kstride is None and nq else int(kstride or 1)
+        ids = np.empty((nq, max(ks, 1)), dtype=np.uint64)
+        sc = np.empty((nq, max(ks, 1)), dtype=np.float32)
+        counts = np.empty(nq, dtype=np.uint32)
+        st = _capi.SearchStats()
+        _capi.check(self._lib.nmn_hnsw_search_metric_multi(self._h, C.c_void_p(q.ctypes.data), nq, C.c_void_p(kk.ctypes.data),
+                                                           C.cast(mm, C.c_void_p), ks, C.c_void_p(ids.ctypes.data),
+                                                           C.c_void_p(sc.ctypes.data), C.c_void_p(counts.ctypes.data), C.byref(st)))
+        return (ids, sc, counts, st) if with_stats else (ids, sc, counts)
+
     def search_metric_device(self, queries_t, top_k, metric, out=None, stream=None):
         """`search_metric` with torch device tensors, in stream order (nmn_hnsw_search_metric_device); same conventions as
         `search_device`."""

@@ -49,7 +49,8 @@ Per N it reports queries_per_s (all calls / wall time), call_ms_median (one call
 nmn_hnsw_coalesce_stats counted meanwhile (merged batches, the calls in them, calls per merged batch); medians and spread over
 --repeats.  With --storage quantized the handle is the quantized one (PATH is its file).  A/B legs are separate processes:
 NMN_HNSW_NO_COALESCE=1 makes callers take turns, NEUMANN_GPU_LIB=<an older build> is the baseline (entries that build lacks are
-left unbound, and its coalesce figures read null)."""
+left unbound, and its coalesce figures read null).  With --metric NAME (an ExtendedDistanceMetric) the callers call
+nmn_hnsw_search_metric(nq = 1) under that metric instead, top_k taken in turn from 1, 10, 50, 100 (docs/hnsw.md §12)."""
 import argparse
 import json
 import os
@@ -173,8 +174,9 @@ def time_storage(gq, gd, Q, qd, k, s, args, metric):
     return out
 
 
-def time_callers(g, Q, counts, args):
-    """N threads, each calling g.search(one query, its k) --caller-calls times: throughput, a caller's median, the coalescer's counts"""
+def time_callers(g, Q, counts, args, xmetric=None):
+    """N threads, each calling g.search(one query, its k) --caller-calls times — with `xmetric`, g.search_metric(one query, its top_k,
+    xmetric) —: throughput, a caller's median, the coalescer's counts"""
     import threading
     ks = (1, 10, 50, 100)
     has_stats = hasattr(g._lib, "nmn_hnsw_coalesce_stats")  # (an older build has no coalescer)
@@ -193,7 +195,10 @@ def time_callers(g, Q, counts, args):
                     for j in range(per):
                         q = Q[(t * per + j) % len(Q)]
                         t0 = time.perf_counter()
-                        g.search(q, ks[(t + j) % len(ks)])
+                        if xmetric is not None:
+                            g.search_metric(q, ks[(t + j) % len(ks)], xmetric)
+                        else:
+                            g.search(q, ks[(t + j) % len(ks)])
                         lat[t].append(time.perf_counter() - t0)
                 except Exception as e:  # noqa: BLE001
                     errs.append(e)
@@ -307,7 +312,9 @@ def main():
                     "no_coalesce": bool(os.environ.get("NMN_HNSW_NO_COALESCE")), "caller_calls": args.caller_calls})
         del out["k"]
         with build_or_load(args.index_file, n, d, cfg, args.storage, out) as g:
-            out.update(time_callers(g, Q, [int(x) for x in args.callers.split(",")], args))
+            if xmetric is not None:
+                out["xmetric"] = xmetric.name
+            out.update(time_callers(g, Q, [int(x) for x in args.callers.split(",")], args, xmetric))
         print(json.dumps(out), flush=True)
         return
     if args.storage == "quantized":

@@ -5,7 +5,7 @@
 //   c++ -std=c++17 -O1 -g -fsanitize=address -I include -I neumann_amd/csrc tools/micro/hnsw_queue_mt.cpp -o tools/micro/hnsw_queue_mt -lpthread && tools/micro/hnsw_queue_mt
 //
 // The stand-in checks what the queue promises: one batch at a time; at most kBatchQueries queries in a batch unless it is one
-// call; every call is served exactly once, with its own answer (out_counts[i] = a
+// call; a call marked `alone` (a metric call with more than kShareCandMax candidates) is a batch of one; every call is served exactly once, with its own answer (out_counts[i] = a
 // function of the call's own k and query), also when a batch fails — then every call of that batch gets the status and the text.
 #include <atomic>
 #include <chrono>
@@ -18,7 +18,7 @@
 using namespace nmn;
 
 static std::atomic<int> running{0};
-static std::atomic<uint64_t> batches_run{0}, calls_served{0}, failed_batches{0};
+static std::atomic<uint64_t> batches_run{0}, calls_served{0}, failed_batches{0}, alone_served{0};
 static thread_local std::string tl_error;
 
 #define REQUIRE(c)                                                   \
@@ -34,6 +34,11 @@ static nmn_status fake_batch(const std::vector<HostWalk*>& batch) {
     uint64_t total = 0;
     for (const HostWalk* r : batch) total += r->nq;
     REQUIRE(batch.size() == 1 || total <= kBatchQueries);
+    for (const HostWalk* r : batch)
+        if (r->alone) {  // nobody rides with it, and it rides with nobody
+            REQUIRE(batch.size() == 1);
+            alone_served++;
+        }
     const uint64_t b = batches_run.fetch_add(1);
     nmn_status st = NMN_OK;
     if (b % 17 == 5) {  // a failing batch: nothing written, every call gets the status
@@ -73,6 +78,7 @@ int main() {
                 me.k = k.data();
                 me.kstride = 200;
                 me.out_counts = counts.data();
+                me.alone = (t * 7 + c) % 11 == 3;  // the calls that ride alone, from every thread
                 const nmn_status st = coalesce_walk(q, me, fake_batch, [] { return tl_error; });
                 if (st == NMN_OK) {
                     REQUIRE(me.evals == nq || me.done);  // (a rider's evals are written by the leader before done is set)
@@ -91,8 +97,12 @@ int main() {
     REQUIRE(!q.busy && q.waiting.empty());
     REQUIRE(q.batches > 0 && q.calls >= 2 * q.batches);
     REQUIRE(failed_batches.load() > 0 && failures_seen.load() >= failed_batches.load());
-    printf("hnsw_queue_mt ok: %llu calls in %llu batches (%llu merged batches carrying %llu calls), %llu failed batches, %llu failed calls\n",
+    uint64_t alone_made = 0;
+    for (int t = 0; t < threads; t++)
+        for (int c = 0; c < calls; c++) alone_made += (t * 7 + c) % 11 == 3 ? 1 : 0;
+    REQUIRE(alone_made > 0 && alone_served.load() == alone_made);
+    printf("hnsw_queue_mt ok: %llu calls in %llu batches (%llu merged batches carrying %llu calls, %llu calls alone), %llu failed batches, %llu failed calls\n",
            (unsigned long long)calls_served.load(), (unsigned long long)batches_run.load(), (unsigned long long)q.batches,
-           (unsigned long long)q.calls, (unsigned long long)failed_batches.load(), (unsigned long long)failures_seen.load());
+           (unsigned long long)q.calls, (unsigned long long)alone_served.load(), (unsigned long long)failed_batches.load(), (unsigned long long)failures_seen.load());
     return 0;
 }
