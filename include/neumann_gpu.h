@@ -656,6 +656,24 @@ nmn_status nmn_hnsw_search(nmn_hnsw* h, const float* queries, uint32_t nq, uint3
 nmn_status nmn_hnsw_search_multi(nmn_hnsw* h, const float* queries, uint32_t nq, const uint32_t* k, const uint32_t* ef,
                                  uint32_t kstride, uint64_t* out_ids, float* out_scores, uint32_t* out_counts,
                                  nmn_search_stats* stats);
+/* HNSWIndex::search_sparse_with_ef (hnsw.rs:2118-2166; ef == 0: config.ef_search, i.e. search_sparse): the walk of
+ * nmn_hnsw_search with distance_sparse (hnsw.rs:1175-1181) in place of distance_dense.  HOST buffers, CSR: query i is the
+ * (position, value) pairs [indptr[i], indptr[i + 1]) of positions / values, in any order, made a SparseVector of the handle's
+ * dimension as SparseVector::try_from_parts does (sparse_vector.rs:155-193) BEFORE anything is enqueued or written: a position >=
+ * nmn_hnsw_dim(h) is NMN_ERR_INVALID_ARGUMENT ("index {i} out of bounds for dimension {d}"), as is a decreasing indptr; values ==
+ * 0.0 (either sign) are dropped, NaN is kept, the rest is stably sorted by position, so duplicates survive in input order.
+ * On a dense handle Cosine and DotProduct score a row with SparseVector::dot_dense — ONE sequential f64 sum over the query's
+ * stored entries, cast to f32 — and Cosine takes the query's magnitude through f64 too (sparse_vector.rs:450-466, 548-559): the
+ * score bits differ from nmn_hnsw_search of the densified query, and a row costs O(stored entries), not O(dim).  Euclidean (either
+ * handle) and DotProduct on a quantized handle are bit for bit nmn_hnsw_search of Q.to_dense() (a duplicated position: the last
+ * wins); Cosine on a quantized handle is that with Q.magnitude() as the query's magnitude.  docs/hnsw.md §13.
+ * Outputs, sentinels, ef == 0, k == 0 (NMN_ERR_INVALID_TOP_K) and the empty index are nmn_hnsw_search's; stats: sweep_kind
+ * NMN_SWEEP_GRAPH, fallback_queries = queries the spill launch answered, rows_scanned by the handle's convention for dense queries.
+ * A query with more than 4096 stored entries (possible above 4096 dimensions, or with duplicates) is walked on the host.
+ * Not coalesced: concurrent callers take turns with each other and with the coalescer's batches; NMN_HNSW_HOST_SEARCH=1 applies. */
+nmn_status nmn_hnsw_search_sparse(nmn_hnsw* h, const uint64_t* indptr, const uint32_t* positions, const float* values,
+                                  uint32_t nq, uint32_t k, uint32_t ef, uint64_t* out_ids, float* out_scores,
+                                  uint32_t* out_counts, nmn_search_stats* stats);
 /* What the coalescer of nmn_hnsw_search / nmn_hnsw_search_multi / nmn_hnsw_search_metric / nmn_hnsw_search_metric_multi has done so far: batches that carried two or more calls, and
  * the calls in them (the meaning nmn_index_coalesce_stats and nmn_sharded_coalesce_stats give these counters). */
 nmn_status nmn_hnsw_coalesce_stats(nmn_hnsw* h, uint64_t* batches, uint64_t* calls);

@@ -22,6 +22,11 @@
 //       which the host keeps where a dense handle keeps its rows.  The two sides differ in bits; both are restated.
 //   nmn_hnsw_search_metric* (the end of this file): the walk with k = c, then the re-rank of its candidates under an extended
 //       metric and their stable ordering (nmn_xmetric.hip) — VectorEngine::search_with_hnsw_and_metric, vector_engine/src/lib.rs:2560-2619.
+//   nmn_hnsw_search_sparse: search_sparse_with_ef (hnsw.rs:2118-2166) — the same walk with distance_sparse (1175-1181).  The query
+//       is a SparseVector as try_from_parts makes it (sparse_vector.rs:155-193); on a dense handle Cosine / DotProduct score a row
+//       with dot_dense (450-466), ONE sequential f64 sum over the query's stored entries (each product exact in f64, each add
+//       rounded once, one cast; std's float Sum restated as a left-to-right fold from -0.0), and Cosine takes magnitude() (548-559)
+//       through f64; Euclidean, and every metric's dot on a quantized handle, go through to_dense() (400-406).  docs/hnsw.md §13.
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -49,6 +54,7 @@ constexpr uint32_t kNone = 0xFFFFFFFFu;
 constexpr uint32_t kLdsResultsMax = 1024;  // entries of the results heap a wave keeps in LDS (+1 for the push before the pop)
 constexpr uint32_t kLdsCandMax = 4096;     // entries of the candidate heap a wave keeps in LDS
 constexpr uint32_t kMaxDim = 8192;         // the query sits in LDS for the whole walk (32 KiB at most)
+constexpr uint32_t kSparseLdsEntries = 4096;  // stored entries of a sparse query a wave keeps in LDS, 8 bytes each: the same 32 KiB
 
 struct Ent {
     float d;
@@ -290,6 +296,12 @@ struct SearchArgs {
     const uint32_t* qk;
     const uint32_t* qef;
     uint32_t kstride, ccap_fixed;
+    // hnsw_search_kernel<.., QK != 0> (nmn_hnsw_search_sparse, docs/hnsw.md §13).  QK == 1: query i is the stored entries
+    // [sp_off[i], sp_off[i + 1]) of sp_ent, (position, value bits) pairs in SparseVector order, qlds / 2 of them at most; `queries`
+    // is not read.  QK != 0: qmag[i] = SparseVector::magnitude() of query i, taken through f64 on the host.
+    const uint64_t* sp_off;
+    const uint2* sp_ent;
+    const float* qmag;
 };
 
 // Entries of the candidate heap the first launch gives a query walking with `ef` (fixed: nmn_hnsw_set_heap_capacity, 0 = default).
@@ -393,6 +405,43 @@ __device__ __forceinline__ float pair_sum(const float* q, uint32_t dim, uint32_t
     return r;
 }
 
+// distance_sparse on a Dense row under Cosine / DotProduct (hnsw.rs:1069-1079, 1143-1145): SparseVector::dot_dense
+// (sparse_vector.rs:450-466) is ONE f64 chain over the query's stored entries in their order, from -0.0, each product exact in f64,
+// each addition rounded once, one cast to f32.  The same PAIR of lanes as pair_distance: lane h gathers row[pos] for the entries
+// 2t + h (the entries come from LDS, every pair reads the same two addresses; four gathers in flight per lane), forms its product,
+// and both lanes run the chain: even entry, then odd entry, the partner's product by lane exchange.  A slot past the last entry
+// contributes -0.0, which changes no sum (x + -0.0 == x for every x, -0.0 included).  Both lanes return the distance.
+__device__ __forceinline__ float sparse_distance(const float* __restrict__ row, float rowmag, const uint2* ent, uint32_t nnz, float qmag,
+                                                 int metric, uint32_t h) {
+    double acc = -0.0;
+    constexpr int PF = 4;
+    for (uint32_t t0 = 0; 2u * t0 < nnz; t0 += PF) {
+        uint2 e[PF];
+        float x[PF];
+        double pr[PF];
+#pragma unroll
+        for (int i = 0; i < PF; i++) {
+            const uint32_t idx = 2u * (t0 + (uint32_t)i) + h;
+            e[i] = idx < nnz ? ent[idx] : make_uint2(0u, 0u);
+        }
+#pragma unroll
+        for (int i = 0; i < PF; i++) x[i] = 2u * (t0 + (uint32_t)i) + h < nnz ? row[e[i].x] : 0.0f;
+#pragma unroll
+        for (int i = 0; i < PF; i++)
+            pr[i] = 2u * (t0 + (uint32_t)i) + h < nnz ? (double)__uint_as_float(e[i].y) * (double)x[i] : -0.0;
+#pragma unroll
+        for (int i = 0; i < PF; i++) {
+            const double other = __shfl_xor(pr[i], 1);
+            acc = acc + (h ? other : pr[i]);
+            acc = acc + (h ? pr[i] : other);
+        }
+    }
+    const float dot = (float)acc;
+    if (metric == NMN_METRIC_DOT_PRODUCT) return -dot;
+    if (rowmag == 0.0f || qmag == 0.0f) return 1.0f;
+    return 1.0f - dot / (rowmag * qmag);
+}
+
 // what a wave computes once per query: simd::magnitude (Cosine), and for quantized rows sum_y and sum_of_squares (Euclidean)
 struct QuerySide {
     float mag, sum, sq;
@@ -470,8 +519,13 @@ __device__ __forceinline__ float q8_distance(const uint8_t* __restrict__ row, co
 // Q8 == true: the rows are ScalarQuantizedVectors (codes + a record per row), scored by q8_distance.
 // PERQ == true: k and ef are the query's own (a.qk / a.qef, read once per query: a wave serves one query, so they are
 // wave-uniform), rows of the outputs are a.kstride apart.  PERQ == false is the kernel as it has always been.
-template <bool SPILL, bool Q8, bool PERQ>
+// QK: the query kind.  0: a dense query, everything above.  1 (dense rows, Cosine / DotProduct): the query is a SparseVector — its
+// stored entries sit in the query region of LDS as (u32 position, f32 value) pairs, rows are scored by sparse_distance, and the
+// query's magnitude is a.qmag[q].  2 (quantized rows): a dense query whose Cosine magnitude is a.qmag[q] instead of the
+// simd::magnitude the wave computes.  QK is a template parameter so that the QK == 0 instantiations stay the code they were.
+template <bool SPILL, bool Q8, bool PERQ, int QK = 0>
 __global__ __launch_bounds__(64) void hnsw_search_kernel(SearchArgs a) {
+    static_assert(QK == 0 || (QK == 1 && !Q8 && !PERQ) || (QK == 2 && Q8 && !PERQ), "query kinds: 1 on dense rows, 2 on quantized rows");
     extern __shared__ float4 smem4[];
     const GraphDev& g = a.g;
     const uint32_t lane = threadIdx.x, p = lane >> 1, h = lane & 1u;
@@ -494,7 +548,15 @@ __global__ __launch_bounds__(64) void hnsw_search_kernel(SearchArgs a) {
         const float* qg = a.queries + (size_t)q * g.dim;
         const float* qv = qs;
         __syncthreads();
-        for (uint32_t i = lane; i < a.qlds; i += 64) qs[i] = i < g.dim ? qg[i] : 0.0f;
+        uint32_t nnz = 0;
+        if constexpr (QK == 1) {
+            const uint64_t e0 = a.sp_off[q];
+            nnz = min((uint32_t)(a.sp_off[q + 1] - e0), a.qlds >> 1);  // (the host sized the region by the launch's largest count)
+            uint2* el = reinterpret_cast<uint2*>(qs);
+            for (uint32_t i = lane; i < nnz; i += 64) el[i] = a.sp_ent[e0 + i];
+        } else {
+            for (uint32_t i = lane; i < a.qlds; i += 64) qs[i] = i < g.dim ? qg[i] : 0.0f;
+        }
         uint32_t* vis = a.visited + (size_t)q * a.vwords;
         if (SPILL) {
             for (uint32_t w = lane; w < a.vwords; w += 64) vis[w] = 0u;
@@ -520,14 +582,21 @@ __global__ __launch_bounds__(64) void hnsw_search_kernel(SearchArgs a) {
             continue;
         }
         float qmag = 0.0f;
-        if (g.metric == NMN_METRIC_COSINE) qmag = d_sqrt(-pair_distance(qv, 0.f, qv, 0.f, g.dim, NMN_METRIC_DOT_PRODUCT, h));
+        if constexpr (QK == 0) {
+            if (g.metric == NMN_METRIC_COSINE) qmag = d_sqrt(-pair_distance(qv, 0.f, qv, 0.f, g.dim, NMN_METRIC_DOT_PRODUCT, h));
+        } else {
+            if (g.metric == NMN_METRIC_COSINE) qmag = a.qmag[q];
+        }
         QuerySide qside{qmag, 0.0f, 0.0f};
         if (Q8) {
             qside.sum = pair_sum(qv, g.dim, h);
             if (g.metric == NMN_METRIC_EUCLIDEAN) qside.sq = -pair_distance(qv, 0.f, qv, 0.f, g.dim, NMN_METRIC_DOT_PRODUCT, h);
         }
         auto row_distance = [&](uint32_t node) -> float {
-            if constexpr (Q8)
+            if constexpr (QK == 1)
+                return sparse_distance(g.corpus + (size_t)node * g.ld, g.norms[node], reinterpret_cast<const uint2*>(qv), nnz, qmag,
+                                       g.metric, h);
+            else if constexpr (Q8)
                 return q8_distance(g.codes + (size_t)node * g.ld8, g.rec[node], qv, qside, g.dim, g.metric, h);
             else
                 return pair_distance(g.corpus + (size_t)node * g.ld, g.norms[node], qv, qmag, g.dim, g.metric, h);
@@ -736,6 +805,7 @@ struct nmn_hnsw {
     std::mutex host_mu;
     hipStream_t host_stream = nullptr;
     DevBuf hq, hids, hsc, hcnt, hkef;
+    DevBuf hsp_off, hsp_ent, hqmag;  // nmn_hnsw_search_sparse: the launch's entry offsets, its (position, value) pairs, Q.magnitude() per query
     DevBuf hxmeta, hxsim, hxoids, hxosc, hxocnt, hxsort;  // a batch's metric slots (docs/hnsw.md §12): what their launches read and answer into
     // ... and what a batch of mixed k / ef passes through on the host (under host_mu): the queries gathered in launch order, k and ef
     // per query, the launch's rows before they are handed to their callers
@@ -836,16 +906,19 @@ HQ host_query(const nmn_hnsw* h, const float* q) {
     return hq;
 }
 
-uint32_t host_greedy(const nmn_hnsw* h, const float* q, const HQ& qmag, uint32_t entry, uint32_t layer, uint64_t* evals) {
+// The walk below is written over `dist(node)`, the query side's distance to a stored row: node_distance for a dense query,
+// sparse_node_distance for a SparseVector query (nmn_hnsw_search_sparse).
+template <class Dist>
+uint32_t host_greedy(const nmn_hnsw* h, const Dist& dist, uint32_t entry, uint32_t layer, uint64_t* evals) {
     uint32_t cur = entry;
-    float cur_d = node_distance(h, cur, q, qmag);
+    float cur_d = dist(cur);
     (*evals)++;
     for (;;) {
         const std::vector<uint32_t>& ids = h->nbr[cur][layer];  // (the list of the node the round started from)
         bool changed = false;
         uint32_t best = cur;
         for (uint32_t id : ids) {
-            const float d = node_distance(h, id, q, qmag);
+            const float d = dist(id);
             (*evals)++;
             if (d < cur_d) {
                 best = id;
@@ -860,14 +933,15 @@ uint32_t host_greedy(const nmn_hnsw* h, const float* q, const HQ& qmag, uint32_t
 }
 
 // search_layer: the results in the order the reference returns them (stable sort by distance of the heap's vector)
-void host_search_layer(const nmn_hnsw* h, const float* q, const HQ& qmag, uint32_t entry, uint64_t ef, uint32_t layer, HostVisited& vis,
+template <class Dist>
+void host_search_layer(const nmn_hnsw* h, const Dist& dist, uint32_t entry, uint64_t ef, uint32_t layer, HostVisited& vis,
                        std::vector<Ent>& out, uint64_t* evals) {
     static thread_local std::vector<Ent> cand, res;  // grown on demand, kept: a walk touches a few thousand entries of a graph of millions
     vis.begin(h->level.size());
     if (cand.size() < 1024) cand.resize(1024);
     if (res.size() < 1024) res.resize(1024);
     uint32_t cn = 0, rn = 0;
-    const float ed = node_distance(h, entry, q, qmag);
+    const float ed = dist(entry);
     (*evals)++;
     vis.insert(entry);
     heap_push<false>(cand.data(), cn, Ent{ed, entry});
@@ -877,7 +951,7 @@ void host_search_layer(const nmn_hnsw* h, const float* q, const HQ& qmag, uint32
         if (rn >= ef && cur.d > res[0].d) break;
         for (uint32_t id : h->nbr[cur.id][layer]) {
             if (!vis.insert(id)) continue;
-            const float d = node_distance(h, id, q, qmag);
+            const float d = dist(id);
             (*evals)++;
             const bool should_add = rn < ef || d < res[0].d;
             if (should_add) {
@@ -906,13 +980,14 @@ void host_insert_node(nmn_hnsw* h, uint32_t node_id, HostVisited& vis) {
     const uint32_t current_max = h->max_layer;
     const float* q = h->rows.data() + (size_t)node_id * h->dim;
     const HQ qmag = host_query(h, q);  // (a quantized node's own query is its to_dense(), hnsw.rs:1985: the row kept here)
+    const auto dist = [&](uint32_t node) { return node_distance(h, node, q, qmag); };
     uint64_t evals = 0;
     uint32_t cur = (uint32_t)h->entry;
-    for (uint32_t layer = current_max; layer >= node_level + 1; layer--) cur = host_greedy(h, q, qmag, cur, layer, &evals);
+    for (uint32_t layer = current_max; layer >= node_level + 1; layer--) cur = host_greedy(h, dist, cur, layer, &evals);
     std::vector<Ent> found;
     std::vector<std::pair<float, uint32_t>> wd;
     for (int layer = (int)std::min(node_level, current_max); layer >= 0; layer--) {
-        host_search_layer(h, q, qmag, cur, h->cfg.ef_construction, (uint32_t)layer, vis, found, &evals);
+        host_search_layer(h, dist, cur, h->cfg.ef_construction, (uint32_t)layer, vis, found, &evals);
         const uint32_t m = layer == 0 ? h->cfg.m0 : h->cfg.m;
         std::vector<uint32_t> selected;
         for (size_t i = 0; i < found.size() && i < m; i++) selected.push_back(found[i].id);
@@ -941,15 +1016,16 @@ void host_insert_node(nmn_hnsw* h, uint32_t node_id, HostVisited& vis) {
     }
 }
 
-void host_search_one(const nmn_hnsw* h, const float* q, uint32_t k, uint64_t ef, HostVisited& vis, uint64_t* ids, float* scores,
-                     uint32_t* count, uint64_t* evals) {
+// search_with_ef / search_sparse_with_ef (hnsw.rs:2069-2111, 2118-2166): one walk, the distance supplied
+template <class Dist>
+void host_walk_one(const nmn_hnsw* h, const Dist& dist, uint32_t k, uint64_t ef, HostVisited& vis, uint64_t* ids, float* scores,
+                   uint32_t* count, uint64_t* evals) {
     uint32_t c = 0;
     if (h->entry != ~0ull) {
-        const HQ qmag = host_query(h, q);
         uint32_t cur = (uint32_t)h->entry;
-        for (uint32_t layer = h->max_layer; layer >= 1; layer--) cur = host_greedy(h, q, qmag, cur, layer, evals);
+        for (uint32_t layer = h->max_layer; layer >= 1; layer--) cur = host_greedy(h, dist, cur, layer, evals);
         std::vector<Ent> found;
-        host_search_layer(h, q, qmag, cur, std::max<uint64_t>(ef, k), 0, vis, found, evals);
+        host_search_layer(h, dist, cur, std::max<uint64_t>(ef, k), 0, vis, found, evals);
         for (; c < found.size() && c < k; c++) {
             ids[c] = found[c].id;
             scores[c] = to_similarity(h->cfg.distance_metric, found[c].d);
@@ -960,6 +1036,118 @@ void host_search_one(const nmn_hnsw* h, const float* q, uint32_t k, uint64_t ef,
         ids[i] = ~0ull;
         scores[i] = -INFINITY;
     }
+}
+
+void host_search_one(const nmn_hnsw* h, const float* q, uint32_t k, uint64_t ef, HostVisited& vis, uint64_t* ids, float* scores,
+                     uint32_t* count, uint64_t* evals) {
+    const HQ qmag = host_query(h, q);
+    host_walk_one(h, [&](uint32_t node) { return node_distance(h, node, q, qmag); }, k, ef, vis, ids, scores, count, evals);
+}
+
+// ---- SparseVector queries (sparse_vector.rs:155-193, 400-406, 450-466, 548-559; docs/hnsw.md §13) --------------------------------
+// dot_dense: Iterator::sum::<f64>() of f64(val) * f64(dense[pos]) over the stored entries in order — a left-to-right fold from -0.0
+// (the convention of docs/hnsw.md §1 for std's float Sum) — then `as f32`
+inline float h_sparse_dot(const uint32_t* pos, const float* val, uint64_t nnz, const float* dense) {
+    double acc = -0.0;
+    for (uint64_t i = 0; i < nnz; i++) {
+        const double p = (double)val[i] * (double)dense[pos[i]];
+        acc = acc + p;
+    }
+    return (float)acc;
+}
+// magnitude: the same fold over f64(v) * f64(v), an f64 sqrt, then `as f32`
+inline float h_sparse_mag(const float* val, uint64_t nnz) {
+    double acc = -0.0;
+    for (uint64_t i = 0; i < nnz; i++) {
+        const double p = (double)val[i] * (double)val[i];
+        acc = acc + p;
+    }
+    return (float)std::sqrt(acc);
+}
+
+// The queries of one nmn_hnsw_search_sparse call as SparseVector::try_from_parts leaves them: entries with val == 0.0 (either sign)
+// dropped, NaN kept, the rest stably sorted by position (duplicates survive in input order).
+struct SparseQueries {
+    std::vector<uint64_t> off;  // [nq + 1]
+    std::vector<uint32_t> pos;
+    std::vector<float> val;
+    std::vector<float> mag;     // Q.magnitude() per query
+    uint64_t nnz(uint32_t q) const { return off[q + 1] - off[q]; }
+    void to_dense(uint32_t q, uint32_t dim, float* out) const {  // zeros, then the entries in order: the last of a position wins
+        std::fill(out, out + dim, 0.0f);
+        for (uint64_t i = off[q]; i < off[q + 1]; i++) out[pos[i]] = val[i];
+    }
+};
+
+nmn_status canonicalise_sparse(uint32_t dim, const uint64_t* indptr, const uint32_t* positions, const float* values, uint32_t nq,
+                               SparseQueries* out) {
+    for (uint32_t q = 0; q < nq; q++)
+        if (indptr[q + 1] < indptr[q]) return set_error(NMN_ERR_INVALID_ARGUMENT, "HNSW: indptr decreases");
+    if (indptr[nq] > indptr[0] && (!positions || !values)) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    out->off.assign(1, 0);
+    out->off.reserve((size_t)nq + 1);
+    out->mag.resize(nq);
+    std::vector<std::pair<uint32_t, float>> pairs;
+    for (uint32_t q = 0; q < nq; q++) {
+        pairs.clear();
+        for (uint64_t i = indptr[q]; i < indptr[q + 1]; i++) {
+            if (positions[i] >= dim) {  // SparseVectorError::IndexOutOfBounds, sparse_vector.rs:40-42
+                char buf[128];
+                snprintf(buf, sizeof buf, "index %u out of bounds for dimension %u", positions[i], dim);
+                return set_error(NMN_ERR_INVALID_ARGUMENT, buf);
+            }
+            if (values[i] != 0.0f) pairs.emplace_back(positions[i], values[i]);
+        }
+        std::stable_sort(pairs.begin(), pairs.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+        for (const auto& pr : pairs) {
+            out->pos.push_back(pr.first);
+            out->val.push_back(pr.second);
+        }
+        out->off.push_back(out->pos.size());
+        out->mag[q] = h_sparse_mag(out->val.data() + out->off[q], out->nnz(q));
+    }
+    return NMN_OK;
+}
+
+// How a sparse call is served (docs/hnsw.md §13): distance_sparse is the DENSE walk of Q.to_dense() under Euclidean on either
+// handle and under DotProduct on a quantized one; under Cosine on a quantized handle it is that walk with Q.magnitude() as the
+// query's magnitude; under Cosine / DotProduct on a dense handle it is dot_dense over the stored entries.
+enum SparseRoute { kSparseDensify = 0, kSparseGather = 1, kSparseDensifyMag = 2 };  // (the kernel's QK)
+SparseRoute sparse_route(const nmn_hnsw* h) {
+    const bool q8 = h->storage == NMN_HNSW_STORAGE_QUANTIZED;
+    if (h->cfg.distance_metric == NMN_METRIC_EUCLIDEAN) return kSparseDensify;
+    if (!q8) return kSparseGather;
+    return h->cfg.distance_metric == NMN_METRIC_COSINE ? kSparseDensifyMag : kSparseDensify;
+}
+
+// search_sparse_with_ef of query q on the host: the walk of host_search_one with distance_sparse (hnsw.rs:1175-1181)
+void host_search_one_sparse(const nmn_hnsw* h, const SparseQueries& sq, uint32_t q, uint32_t k, uint64_t ef, HostVisited& vis,
+                            uint64_t* ids, float* scores, uint32_t* count, uint64_t* evals) {
+    const SparseRoute route = sparse_route(h);
+    if (route == kSparseGather) {
+        const uint32_t* pos = sq.pos.data() + sq.off[q];
+        const float* val = sq.val.data() + sq.off[q];
+        const uint64_t nnz = sq.nnz(q);
+        const float qmag = sq.mag[q];
+        const int metric = h->cfg.distance_metric;
+        const auto dist = [&](uint32_t node) -> float {
+            const float dot = h_sparse_dot(pos, val, nnz, h->rows.data() + (size_t)node * h->dim);
+            if (metric == NMN_METRIC_DOT_PRODUCT) return -dot;
+            const float vmag = h->mags[node];
+            if (vmag == 0.0f || qmag == 0.0f) return 1.0f;
+            const float den = vmag * qmag;
+            const float sim = dot / den;
+            return 1.0f - sim;
+        };
+        host_walk_one(h, dist, k, ef, vis, ids, scores, count, evals);
+        return;
+    }
+    std::vector<float> dense(h->dim);
+    sq.to_dense(q, h->dim, dense.data());
+    HQ hq = host_query(h, dense.data());
+    if (route == kSparseDensifyMag) hq.mag = sq.mag[q];
+    const float* dq = dense.data();
+    host_walk_one(h, [&](uint32_t node) { return node_distance(h, node, dq, hq); }, k, ef, vis, ids, scores, count, evals);
 }
 
 nmn_status wait_in_flight(nmn_hnsw* h) {  // caller holds rw exclusively
@@ -1140,8 +1328,12 @@ SearchArgs graph_args(const nmn_hnsw* h, uint32_t n) {
 }
 
 template <bool SPILL>
-void launch_walk(bool q8, bool perq, uint32_t grid, size_t lds, hipStream_t s, const SearchArgs& a) {
-    if (q8 && perq)
+void launch_walk(bool q8, bool perq, int qkind, uint32_t grid, size_t lds, hipStream_t s, const SearchArgs& a) {
+    if (qkind == 1)
+        hipLaunchKernelGGL((hnsw_search_kernel<SPILL, false, false, 1>), dim3(grid), dim3(64), lds, s, a);
+    else if (qkind == 2)
+        hipLaunchKernelGGL((hnsw_search_kernel<SPILL, true, false, 2>), dim3(grid), dim3(64), lds, s, a);
+    else if (q8 && perq)
         hipLaunchKernelGGL((hnsw_search_kernel<SPILL, true, true>), dim3(grid), dim3(64), lds, s, a);
     else if (q8)
         hipLaunchKernelGGL((hnsw_search_kernel<SPILL, true, false>), dim3(grid), dim3(64), lds, s, a);
@@ -1161,6 +1353,13 @@ struct WalkShape {
     const uint32_t* qk = nullptr;
     const uint32_t* qef = nullptr;
     uint32_t kstride = 0, n_lds = 0, rcap_lds = 0, ef_lds = 0, rcap_all = 0;
+    // the query kind of hnsw_search_kernel (uniform launches only).  1: no dense queries — DEVICE arrays sp_off [nq + 1] / sp_ent,
+    // sp_max = the largest entry count of the call; 1 and 2: DEVICE array qmag [nq]
+    int qkind = 0;
+    const uint64_t* sp_off = nullptr;
+    const uint2* sp_ent = nullptr;
+    const float* qmag = nullptr;
+    uint32_t sp_max = 0;
 };
 
 uint32_t results_need(uint32_t ef_eff, uint32_t n) { return std::min<uint32_t>(ef_eff, std::max<uint32_t>(n, 1)) + 1; }
@@ -1179,8 +1378,11 @@ nmn_status enqueue_walk_locked(nmn_hnsw* h, nmn_hnsw::Scratch* sc, const float* 
     const uint32_t vwords = std::max<uint32_t>((n + 31) / 32, 1);
     const uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(nq, (256ull << 20) / ((uint64_t)vwords * 4)));
     // heaps of the first launch (LDS) and of the spill launch (global memory)
-    const uint32_t ccap = cand_cap(w.ef_lds, h->lds_ccap, h->dim, n);
-    const uint32_t qlds = (h->dim + 7u) & ~7u;
+    // floats of the query region: the dense query padded to 8, or the stored entries of the longest sparse query, 2 floats each
+    // (kSparseLdsEntries at most: no more than a dense query of 8192 dimensions, so cand_cap's rule for long queries carries over
+    // with the region's length in place of the dimension)
+    const uint32_t qlds = w.qkind == 1 ? std::max<uint32_t>(2u * w.sp_max, 2u) : (h->dim + 7u) & ~7u;
+    const uint32_t ccap = cand_cap(w.ef_lds, h->lds_ccap, w.qkind == 1 ? qlds : h->dim, n);
     const uint32_t s_rcap = w.rcap_all, s_ccap = std::max<uint32_t>(n, 1);
     const uint64_t region = (uint64_t)s_rcap + s_ccap;
     const uint32_t regions = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint32_t>(chunk, 64), (256ull << 20) / (region * sizeof(Ent))));
@@ -1202,7 +1404,10 @@ nmn_status enqueue_walk_locked(nmn_hnsw* h, nmn_hnsw::Scratch* sc, const float* 
     for (uint32_t q0 = 0; q0 < nq; q0 += chunk) {
         const uint32_t nb = std::min<uint32_t>(chunk, nq - q0);
         const uint32_t nl = w.n_lds > q0 ? std::min<uint32_t>(w.n_lds - q0, nb) : 0;  // the chunk's queries that start in LDS: its first nl
-        a.queries = q_dev + (size_t)q0 * h->dim;
+        a.queries = q_dev ? q_dev + (size_t)q0 * h->dim : nullptr;
+        a.sp_off = w.sp_off ? w.sp_off + q0 : nullptr;
+        a.sp_ent = w.sp_ent;
+        a.qmag = w.qmag ? w.qmag + q0 : nullptr;
         a.qk = w.qk ? w.qk + q0 : nullptr;
         a.qef = w.qef ? w.qef + q0 : nullptr;
         a.flags = (uint32_t*)sc->flags.p + q0;
@@ -1218,7 +1423,7 @@ nmn_status enqueue_walk_locked(nmn_hnsw* h, nmn_hnsw::Scratch* sc, const float* 
             a.rcap = w.rcap_lds;
             a.ccap = ccap;
             const size_t lds = fixed + ((size_t)a.rcap + a.ccap) * sizeof(Ent);
-            launch_walk<false>(q8, perq, nl, lds, s, a);
+            launch_walk<false>(q8, perq, w.qkind, nl, lds, s, a);
             HN_TRY(hipGetLastError());
         }
         if (nl < nb)  // results heaps no wave can keep in LDS: these queries go straight to the spill launch
@@ -1226,15 +1431,13 @@ nmn_status enqueue_walk_locked(nmn_hnsw* h, nmn_hnsw::Scratch* sc, const float* 
         a.nq = nb;
         a.rcap = s_rcap;
         a.ccap = s_ccap;
-        launch_walk<true>(q8, perq, std::min(regions, nb), fixed, s, a);
+        launch_walk<true>(q8, perq, w.qkind, std::min(regions, nb), fixed, s, a);
         HN_TRY(hipGetLastError());
     }
     return NMN_OK;
 }
 
-// The same k and ef for every query: the walk as nmn_hnsw_search_device and nmn_hnsw_search_metric* enqueue it.
-nmn_status enqueue_search_locked(nmn_hnsw* h, nmn_hnsw::Scratch* sc, const float* q_dev, uint32_t nq, uint32_t k, uint32_t ef,
-                                 uint64_t* o_ids, float* o_sc, uint32_t* o_cnt, hipStream_t s) {
+WalkShape uniform_shape(const nmn_hnsw* h, uint32_t nq, uint32_t k, uint32_t ef) {
     const uint32_t n = (uint32_t)h->level.size();
     WalkShape w;
     w.k = k;
@@ -1242,7 +1445,13 @@ nmn_status enqueue_search_locked(nmn_hnsw* h, nmn_hnsw::Scratch* sc, const float
     w.n_lds = results_fit_lds(h, w.ef, n) ? nq : 0;
     w.rcap_lds = w.rcap_all = results_need(w.ef, n);
     w.ef_lds = w.ef;
-    return enqueue_walk_locked(h, sc, q_dev, nq, w, o_ids, o_sc, o_cnt, s);
+    return w;
+}
+
+// The same k and ef for every query: the walk as nmn_hnsw_search_device and nmn_hnsw_search_metric* enqueue it.
+nmn_status enqueue_search_locked(nmn_hnsw* h, nmn_hnsw::Scratch* sc, const float* q_dev, uint32_t nq, uint32_t k, uint32_t ef,
+                                 uint64_t* o_ids, float* o_sc, uint32_t* o_cnt, hipStream_t s) {
+    return enqueue_walk_locked(h, sc, q_dev, nq, uniform_shape(h, nq, k, ef), o_ids, o_sc, o_cnt, s);
 }
 
 // The same for a caller that holds rw (shared) only.  *sc_out: the stream's scratch, whose flags / evals the host-buffer search
@@ -1436,6 +1645,7 @@ extern "C" nmn_status nmn_hnsw_destroy(nmn_hnsw* h) {
         drop(s->xsort);
     }
     for (DevBuf* b : {&h->d_l0, &h->d_l0cnt, &h->d_upidx, &h->d_up, &h->d_upcnt, &h->hq, &h->hids, &h->hsc, &h->hcnt, &h->hkef,
+                       &h->hsp_off, &h->hsp_ent, &h->hqmag,
                        &h->hxmeta, &h->hxsim, &h->hxoids, &h->hxosc, &h->hxocnt, &h->hxsort})
         drop(*b);
     if (h->host_stream) (void)hipStreamDestroy(h->host_stream);
@@ -2046,6 +2256,117 @@ extern "C" nmn_status nmn_hnsw_search_multi(nmn_hnsw* h, const float* queries, u
     me.out_scores = out_scores;
     me.out_counts = out_counts;
     return host_walk_call(h, me, stats);
+}
+
+// HNSWIndex::search_sparse_with_ef (hnsw.rs:2118-2166), docs/hnsw.md §13.  Not coalesced: the call takes rw (shared) and host_mu
+// for its duration and so takes turns with the batches of the coalescer.
+extern "C" nmn_status nmn_hnsw_search_sparse(nmn_hnsw* h, const uint64_t* indptr, const uint32_t* positions, const float* values,
+                                             uint32_t nq, uint32_t k, uint32_t ef, uint64_t* out_ids, float* out_scores,
+                                             uint32_t* out_counts, nmn_search_stats* stats) {
+    if (!h) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (k == 0) return set_error(NMN_ERR_INVALID_TOP_K, "k == 0");
+    if (stats) {
+        memset(stats, 0, sizeof *stats);
+        stats->scan_ms = stats->total_ms = -1.0f;
+    }
+    if (nq == 0) return NMN_OK;
+    if (!indptr || !out_ids || !out_scores || !out_counts) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    SparseQueries sq;  // every query as try_from_parts leaves it, before anything is enqueued or written
+    nmn_status st = canonicalise_sparse(h->dim, indptr, positions, values, nq, &sq);
+    if (st != NMN_OK) return st;
+    const bool on_host = host_search_forced();
+    const uint32_t dim = h->dim;
+    uint64_t evals = 0, spilled = 0;
+    static thread_local HostVisited vis;
+    std::shared_lock<std::shared_mutex> g(h->rw);
+    const uint64_t ef_eff = ef ? ef : h->cfg.ef_search;
+    const auto host_one = [&](uint32_t q, uint64_t* ev) {
+        host_search_one_sparse(h, sq, q, k, ef_eff, vis, out_ids + (size_t)q * k, out_scores + (size_t)q * k, out_counts + q, ev);
+    };
+    if (on_host) {
+        for (uint32_t q = 0; q < nq; q++) host_one(q, &evals);
+    } else {
+        std::lock_guard<std::mutex> hl(h->host_mu);  // the handle's own stream and staging, as a batch of the coalescer holds them
+        HN_TRY(hipSetDevice(h->device));
+        const SparseRoute route = sparse_route(h);
+        hipStream_t s = h->host_stream;
+        bool synced = true;  // (every earlier host call ended with a wait)
+        const hipStream_t none = (hipStream_t)-1;
+        HN_TRY(grow(h->hids, (size_t)nq * k * 8, none, &synced));
+        HN_TRY(grow(h->hsc, (size_t)nq * k * 4, none, &synced));
+        HN_TRY(grow(h->hcnt, (size_t)nq * 4, none, &synced));
+        WalkShape w = uniform_shape(h, nq, k, ef);
+        w.qkind = (int)route;
+        const float* q_dev = nullptr;
+        std::vector<uint64_t> l_off;  // kSparseGather: the launch's offsets — a query too long for LDS walks as an empty one there
+        std::vector<uint2> l_ent;     //   and is answered by the host below
+        if (route == kSparseGather) {
+            l_off.assign(1, 0);
+            l_off.reserve((size_t)nq + 1);
+            for (uint32_t q = 0; q < nq; q++) {
+                const uint64_t c = sq.nnz(q);
+                if (c <= kSparseLdsEntries) {
+                    for (uint64_t i = sq.off[q]; i < sq.off[q + 1]; i++) {
+                        uint32_t bits;
+                        memcpy(&bits, &sq.val[i], 4);
+                        l_ent.push_back(make_uint2(sq.pos[i], bits));
+                    }
+                    w.sp_max = std::max<uint32_t>(w.sp_max, (uint32_t)c);
+                }
+                l_off.push_back(l_ent.size());
+            }
+            HN_TRY(grow(h->hsp_off, l_off.size() * 8, none, &synced));
+            HN_TRY(grow(h->hsp_ent, std::max<size_t>(l_ent.size(), 1) * 8, none, &synced));
+            HN_TRY(hipMemcpyAsync(h->hsp_off.p, l_off.data(), l_off.size() * 8, hipMemcpyHostToDevice, s));
+            if (!l_ent.empty()) HN_TRY(hipMemcpyAsync(h->hsp_ent.p, l_ent.data(), l_ent.size() * 8, hipMemcpyHostToDevice, s));
+            w.sp_off = (const uint64_t*)h->hsp_off.p;
+            w.sp_ent = (const uint2*)h->hsp_ent.p;
+        } else {
+            h->st_q.resize((size_t)nq * dim);
+            for (uint32_t q = 0; q < nq; q++) sq.to_dense(q, dim, h->st_q.data() + (size_t)q * dim);
+            HN_TRY(grow(h->hq, (size_t)nq * dim * 4, none, &synced));
+            HN_TRY(hipMemcpyAsync(h->hq.p, h->st_q.data(), (size_t)nq * dim * 4, hipMemcpyHostToDevice, s));
+            q_dev = (const float*)h->hq.p;
+        }
+        if (route != kSparseDensify) {
+            HN_TRY(grow(h->hqmag, (size_t)nq * 4, none, &synced));
+            HN_TRY(hipMemcpyAsync(h->hqmag.p, sq.mag.data(), (size_t)nq * 4, hipMemcpyHostToDevice, s));
+            w.qmag = (const float*)h->hqmag.p;
+        }
+        nmn_hnsw::Scratch* sc = scratch_of(h, s);
+        {
+            std::lock_guard<std::mutex> slk(sc->mu);
+            st = enqueue_walk_locked(h, sc, q_dev, nq, w, (uint64_t*)h->hids.p, (float*)h->hsc.p, (uint32_t*)h->hcnt.p, s);
+            if (st != NMN_OK) return st;
+        }
+        std::vector<uint32_t> fl(nq), ev(nq);
+        HN_TRY(hipMemcpyAsync(out_ids, h->hids.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost, s));
+        HN_TRY(hipMemcpyAsync(out_scores, h->hsc.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, s));
+        HN_TRY(hipMemcpyAsync(out_counts, h->hcnt.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+        HN_TRY(hipMemcpyAsync(fl.data(), sc->flags.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+        HN_TRY(hipMemcpyAsync(ev.data(), sc->evals.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+        HN_TRY(hipStreamSynchronize(s));
+        for (uint32_t q = 0; q < nq; q++) {
+            const bool too_long = route == kSparseGather && sq.nnz(q) > kSparseLdsEntries;
+            if (too_long || fl[q] == 1u) {  // (flag 1 after the spill launch cannot happen while its heap holds n entries)
+                uint64_t e2 = 0;
+                host_one(q, &e2);
+                evals += e2;
+                if (!too_long) spilled++;
+            } else {
+                evals += ev[q];
+                if (fl[q] == 2u) spilled++;
+            }
+        }
+    }
+    if (stats) {
+        stats->rows_scanned = evals;
+        stats->bytes_scanned = h->storage == NMN_HNSW_STORAGE_QUANTIZED ? evals * (dim + 16ull) : evals * dim * 4;
+        stats->fallback_queries = spilled;
+        stats->sweep_kind = h->level.empty() ? NMN_SWEEP_NONE : NMN_SWEEP_GRAPH;
+        stats->sweep_launches = on_host ? 0 : 2;
+    }
+    return NMN_OK;
 }
 
 extern "C" nmn_status nmn_hnsw_coalesce_stats(nmn_hnsw* h, uint64_t* batches, uint64_t* calls) {

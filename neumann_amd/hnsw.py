@@ -289,6 +289,39 @@ class GpuHnsw:
                                                     C.c_void_p(counts.ctypes.data), C.byref(st)))
         return (ids, sc, counts, st) if with_stats else (ids, sc, counts)
 
+    @staticmethod
+    def sparse_from_dense(queries):
+        """SparseVector::from_dense (sparse_vector.rs:212-236) row by row -> CSR (indptr u64 [nq + 1], positions u32, values f32):
+        a value is stored iff it `!= 0.0` — both zeros are skipped, NaN is stored — in position order."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        keep = q != 0
+        indptr = np.zeros(q.shape[0] + 1, dtype=np.uint64)
+        indptr[1:] = np.cumsum(keep.sum(axis=1))
+        return indptr, np.nonzero(keep)[1].astype(np.uint32), q[keep]
+
+    def search_sparse(self, indptr, positions, values, k, ef=None, with_stats=False):
+        """HNSWIndex::search_sparse_with_ef per query (nmn_hnsw_search_sparse; ef None: ef_search).  Query i is the (position, value)
+        pairs [indptr[i], indptr[i + 1]) of `positions` / `values`, in any order; they are made a SparseVector as try_from_parts
+        does (zeros dropped, stably sorted by position; a position >= dim is refused).
+        -> (ids u64 [nq,k], scores f32 [nq,k], counts u32 [nq])"""
+        ip = np.ascontiguousarray(indptr, dtype=np.uint64).reshape(-1)
+        pos = np.ascontiguousarray(positions, dtype=np.uint32).reshape(-1)
+        val = np.ascontiguousarray(values, dtype=np.float32).reshape(-1)
+        if ip.size == 0 or pos.size != val.size or (ip.size and int(ip.max()) > pos.size):
+            raise _capi.NeumannGpuError(_capi.ERR_INVALID_ARGUMENT, "indptr [nq + 1] into positions / values of one length")
+        nq, k = ip.size - 1, int(k)
+        ids = np.empty((nq, max(k, 1)), dtype=np.uint64)
+        sc = np.empty((nq, max(k, 1)), dtype=np.float32)
+        counts = np.empty(nq, dtype=np.uint32)
+        st = _capi.SearchStats()
+        _capi.check(self._lib.nmn_hnsw_search_sparse(self._h, C.c_void_p(ip.ctypes.data), C.c_void_p(pos.ctypes.data),
+                                                     C.c_void_p(val.ctypes.data), nq, k, 0 if ef is None else int(ef),
+                                                     C.c_void_p(ids.ctypes.data), C.c_void_p(sc.ctypes.data),
+                                                     C.c_void_p(counts.ctypes.data), C.byref(st)))
+        return (ids, sc, counts, st) if with_stats else (ids, sc, counts)
+
     def coalesce_stats(self):
         """(batches that carried two or more concurrent calls, calls in them) — nmn_hnsw_coalesce_stats"""
         b, c = C.c_uint64(), C.c_uint64()

@@ -50,7 +50,15 @@ nmn_hnsw_coalesce_stats counted meanwhile (merged batches, the calls in them, ca
 --repeats.  With --storage quantized the handle is the quantized one (PATH is its file).  A/B legs are separate processes:
 NMN_HNSW_NO_COALESCE=1 makes callers take turns, NEUMANN_GPU_LIB=<an older build> is the baseline (entries that build lacks are
 left unbound, and its coalesce figures read null).  With --metric NAME (an ExtendedDistanceMetric) the callers call
-nmn_hnsw_search_metric(nq = 1) under that metric instead, top_k taken in turn from 1, 10, 50, 100 (docs/hnsw.md §12)."""
+nmn_hnsw_search_metric(nq = 1) under that metric instead, top_k taken in turn from 1, 10, 50, 100 (docs/hnsw.md §12).
+
+  python tools/hnsw_bench.py --rows 200000 --dim 128 --sparse-queries 0.8 --index-file PATH
+--sparse-queries FRACTION zeroes that share of every synthetic query's entries and times nmn_hnsw_search_sparse beside
+nmn_hnsw_search of the SAME (densified) queries, the two alternating call by call, at 1 / 64 / 1024 queries per call and ef 50 /
+200 (docs/hnsw.md §13): medians of --calls (a fifth of it at 1024 queries), spread over --repeats.  Both are host-buffer calls —
+nmn_hnsw_search_sparse has no device-buffer entry — so both figures are wall times of the whole call, copies included.  It also
+prints the stored entries per query, the evaluations per query and the queries the spill launch answered, and checks that the
+sparse call's device and host-walk answers are the same bits and, under Euclidean, the bits of the dense walk."""
 import argparse
 import json
 import os
@@ -232,6 +240,58 @@ def time_callers(g, Q, counts, args, xmetric=None):
     return out
 
 
+def time_sparse(g, Q, k, args):
+    """nmn_hnsw_search_sparse beside nmn_hnsw_search of the densified queries, host buffers, alternating call by call"""
+    rng = np.random.default_rng(0x5BA)
+    Q = Q.copy()
+    Q[rng.random(Q.shape) < args.sparse_queries] = 0.0
+    csr = g.sparse_from_dense(Q)
+    out = {"sparse_fraction": args.sparse_queries, "entries_per_query": round(float(csr[1].size) / Q.shape[0], 1)}
+
+    def part(nq):
+        e = int(csr[0][nq])
+        return csr[0][:nq + 1], csr[1][:e], csr[2][:e]
+
+    for ef in (50, 200):
+        r = {}
+        for nq in (1, 64, 1024):  # warm every shape
+            g.search_sparse(*part(nq), k, ef)
+            g.search(Q[:nq], k, ef)
+        ids, sc, cnt, st = g.search_sparse(*csr, k, ef, with_stats=True)
+        r["evals_per_query"] = round(st.rows_scanned / Q.shape[0], 1)
+        r["spilled_queries"] = int(st.fallback_queries)
+        dids, dsc, _ = g.search(Q, k, ef)
+        r["queries_whose_score_bits_differ_from_the_dense_walk"] = int((sc.view(np.uint32) != dsc.view(np.uint32)).any(axis=1).sum())
+        os.environ["NMN_HNSW_HOST_SEARCH"] = "1"
+        try:
+            hids, hsc, _ = g.search_sparse(*part(64), k, ef)
+        finally:
+            del os.environ["NMN_HNSW_HOST_SEARCH"]
+        r["device_and_host_walk_agree"] = bool(np.array_equal(hids, ids[:64]) and np.array_equal(hsc.view(np.uint32), sc[:64].view(np.uint32)))
+        if int(g.config.distance_metric) == 1:
+            r["equals_the_dense_walk"] = bool(np.array_equal(dids, ids) and np.array_equal(dsc.view(np.uint32), sc.view(np.uint32)))
+        reps = {}
+        for _ in range(args.repeats):
+            for nq, calls in ((1, args.calls), (64, args.calls), (1024, max(args.calls // 5, 5))):
+                p, qs = part(nq), Q[:nq]
+                ts, td = [], []
+                for _ in range(calls):
+                    t0 = time.perf_counter()
+                    g.search_sparse(*p, k, ef)
+                    t1 = time.perf_counter()
+                    g.search(qs, k, ef)
+                    t2 = time.perf_counter()
+                    ts.append(t1 - t0)
+                    td.append(t2 - t1)
+                reps.setdefault(f"sparse_ms_per_call_nq{nq}", []).append(float(np.median(ts)) * 1e3)
+                reps.setdefault(f"dense_ms_per_call_nq{nq}", []).append(float(np.median(td)) * 1e3)
+        for key, v in reps.items():
+            r[key] = round(float(np.median(v)), 5)
+            r[key + "_spread"] = round(float((max(v) - min(v)) / np.median(v)), 3)
+        out[f"ef{ef}"] = r
+    return out
+
+
 def build_or_load(path, n, d, cfg, storage, out, label=""):
     """the handle of the run: GpuHnsw.load(path) when the file exists; otherwise built by nmn_hnsw_insert and, with a path, saved
     and loaded back once.  Seconds and file bytes go to `out`."""
@@ -284,6 +344,8 @@ def main():
                     help="quantized: time the quantized walk beside the dense walk of the same corpus (docs/hnsw.md §9)")
     ap.add_argument("--callers", default=None, help="e.g. 1,16,64,128: time that many concurrent host callers (nq = 1, mixed k) and nothing else")
     ap.add_argument("--caller-calls", type=int, default=200, help="calls every caller thread makes per repetition")
+    ap.add_argument("--sparse-queries", type=float, default=None,
+                    help="zero this share of every query's entries and time nmn_hnsw_search_sparse beside nmn_hnsw_search (docs/hnsw.md §13)")
     ap.add_argument("--index-file", default=None,
                     help="load the index from this file when it exists; otherwise build, save it there and report build / save / load seconds")
     args = ap.parse_args()
@@ -315,6 +377,12 @@ def main():
             if xmetric is not None:
                 out["xmetric"] = xmetric.name
             out.update(time_callers(g, Q, [int(x) for x in args.callers.split(",")], args, xmetric))
+        print(json.dumps(out), flush=True)
+        return
+    if args.sparse_queries is not None:
+        out["storage"] = args.storage
+        with build_or_load(args.index_file, n, d, cfg, args.storage, out) as g:
+            out.update(time_sparse(g, Q, k, args))
         print(json.dumps(out), flush=True)
         return
     if args.storage == "quantized":
