@@ -670,11 +670,24 @@ nmn_status nmn_hnsw_search_multi(nmn_hnsw* h, const float* queries, uint32_t nq,
  * Outputs, sentinels, ef == 0, k == 0 (NMN_ERR_INVALID_TOP_K) and the empty index are nmn_hnsw_search's; stats: sweep_kind
  * NMN_SWEEP_GRAPH, fallback_queries = queries the spill launch answered, rows_scanned by the handle's convention for dense queries.
  * A query with more than 4096 stored entries (possible above 4096 dimensions, or with duplicates) is walked on the host.
- * Not coalesced: concurrent callers take turns with each other and with the coalescer's batches; NMN_HNSW_HOST_SEARCH=1 applies. */
+ * Coalesced with concurrent host callers like nmn_hnsw_search, dense, metric and sparse calls in one launch that carries a query
+ * kind per query (docs/hnsw.md §14); each caller receives exactly what it receives alone, stats included.  A call on a dense
+ * handle under Cosine / DotProduct shares no batch when the dimension is above 4096 or one of its queries has more than 2048 stored
+ * entries.  NMN_HNSW_NO_COALESCE=1 and NMN_HNSW_HOST_SEARCH=1 apply as for nmn_hnsw_search. */
 nmn_status nmn_hnsw_search_sparse(nmn_hnsw* h, const uint64_t* indptr, const uint32_t* positions, const float* values,
                                   uint32_t nq, uint32_t k, uint32_t ef, uint64_t* out_ids, float* out_scores,
                                   uint32_t* out_counts, nmn_search_stats* stats);
-/* What the coalescer of nmn_hnsw_search / nmn_hnsw_search_multi / nmn_hnsw_search_metric / nmn_hnsw_search_metric_multi has done so far: batches that carried two or more calls, and
+/* nmn_hnsw_search_sparse with a k and an ef per query, all in one launch: the CSR input and its checks are
+ * nmn_hnsw_search_sparse's (same errors, same texts, before anything is enqueued or written); k, ef, kstride, the outputs, their
+ * padding and the refusals are nmn_hnsw_search_multi's (k[i] == 0: NMN_ERR_INVALID_TOP_K, k[i] > kstride:
+ * NMN_ERR_INVALID_ARGUMENT; ef NULL, or an entry 0: config.ef_search).  The answer for query i is bit for bit what
+ * nmn_hnsw_search_sparse(h, q_i, 1, k[i], ef[i], ..) returns alone; stats are the sums of those calls'.  Dense and quantized
+ * handles, all three metrics; coalesced like nmn_hnsw_search_sparse; NMN_HNSW_HOST_SEARCH=1 applies. */
+nmn_status nmn_hnsw_search_sparse_multi(nmn_hnsw* h, const uint64_t* indptr, const uint32_t* positions, const float* values,
+                                        uint32_t nq, const uint32_t* k, const uint32_t* ef, uint32_t kstride,
+                                        uint64_t* out_ids, float* out_scores, uint32_t* out_counts, nmn_search_stats* stats);
+/* What the coalescer of nmn_hnsw_search / nmn_hnsw_search_multi / nmn_hnsw_search_metric / nmn_hnsw_search_metric_multi /
+ * nmn_hnsw_search_sparse / nmn_hnsw_search_sparse_multi has done so far: batches that carried two or more calls, and
  * the calls in them (the meaning nmn_index_coalesce_stats and nmn_sharded_coalesce_stats give these counters). */
 nmn_status nmn_hnsw_coalesce_stats(nmn_hnsw* h, uint64_t* batches, uint64_t* calls);
 /* The same with every buffer in DEVICE memory: enqueued on `stream` (NULL: the default stream), not waited for.  Two kernel

@@ -324,6 +324,41 @@ impl GpuHnswIndex {
             .collect())
     }
 
+    /// `HNSWIndex::search_sparse_with_ef` for several sparse queries in ONE launch, each with its own k and ef
+    /// (nmn_hnsw_search_sparse_multi; ef 0 = ef_search).  Query i is the (position, value) pairs `queries[i]`, in any order, made a
+    /// SparseVector of the index's dimension as `try_from_parts` does; a position out of bounds is refused before anything runs.
+    /// Answer i is bit for bit what `search_sparse_with_ef(q_i, k_i, ef_i)` returns alone.  Concurrent sparse callers ride the
+    /// coalescer's launches with every other host caller (docs/hnsw.md §14).
+    pub fn search_sparse_multi(&self, queries: &[&[(u32, f32)]], k: &[u32], ef: &[u32]) -> Result<Vec<Vec<(usize, f32)>>> {
+        let nq = queries.len();
+        if k.len() != nq || ef.len() != nq {
+            return Err(VectorError::ConfigurationError("one k and one ef per query".to_string()));
+        }
+        let mut indptr = Vec::with_capacity(nq + 1);
+        let (mut positions, mut values) = (Vec::new(), Vec::new());
+        indptr.push(0u64);
+        for q in queries {
+            for &(p, v) in q.iter() {
+                positions.push(p);
+                values.push(v);
+            }
+            indptr.push(positions.len() as u64);
+        }
+        let kstride = k.iter().copied().max().unwrap_or(1).max(1) as usize;
+        let mut ids = vec![u64::MAX; nq * kstride];
+        let mut scores = vec![f32::NEG_INFINITY; nq * kstride];
+        let mut counts = vec![0u32; nq];
+        let st = unsafe {
+            ffi::nmn_hnsw_search_sparse_multi(self.raw, indptr.as_ptr(), positions.as_ptr(), values.as_ptr(), nq as u32, k.as_ptr(),
+                                              ef.as_ptr(), kstride as u32, ids.as_mut_ptr(), scores.as_mut_ptr(), counts.as_mut_ptr(),
+                                              std::ptr::null_mut())
+        };
+        check(st, self.dim, self.dim)?;
+        Ok((0..nq)
+            .map(|i| (0..counts[i] as usize).map(|j| (ids[i * kstride + j] as usize, scores[i * kstride + j])).collect())
+            .collect())
+    }
+
     /// (batches that carried two or more concurrent calls, the calls in them) — nmn_hnsw_coalesce_stats.
     pub fn coalesce_stats(&self) -> (u64, u64) {
         let (mut b, mut c) = (0u64, 0u64);

@@ -224,6 +224,7 @@ SIGNATURES = {
     "nmn_hnsw_search_device": (C.c_int32, [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp]),
     "nmn_hnsw_search_multi": (C.c_int32, [vp, vp, C.c_uint32, vp, vp, C.c_uint32, vp, vp, vp, C.POINTER(SearchStats)]),
     "nmn_hnsw_search_sparse": (C.c_int32, [vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.POINTER(SearchStats)]),
+    "nmn_hnsw_search_sparse_multi": (C.c_int32, [vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, vp, vp, vp, C.POINTER(SearchStats)]),
     "nmn_hnsw_coalesce_stats": (C.c_int32, [vp, vp, vp]),
     "nmn_hnsw_set_heap_capacity": (C.c_int32, [vp, C.c_uint32, C.c_uint32]),
     "nmn_hnsw_vectors": (vp, [vp]),

@@ -27,6 +27,7 @@
 //       with dot_dense (450-466), ONE sequential f64 sum over the query's stored entries (each product exact in f64, each add
 //       rounded once, one cast; std's float Sum restated as a left-to-right fold from -0.0), and Cosine takes magnitude() (548-559)
 //       through f64; Euclidean, and every metric's dot on a quantized handle, go through to_dense() (400-406).  docs/hnsw.md §13.
+//   nmn_hnsw_search_sparse_multi: the same with a k and an ef per query; both ride the request coalescer, a query kind per slot (§14).
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -302,6 +303,12 @@ struct SearchArgs {
     const uint64_t* sp_off;
     const uint2* sp_ent;
     const float* qmag;
+    // hnsw_search_kernel<.., PERQ = true, QK = 3> (a batch of the coalescer that carries sparse calls, docs/hnsw.md §14): the kind
+    // of every query (0, 1 or 2 as above; sp_off / sp_ent / qmag as above, a query of kind 0 or 2 owning no entries) and the
+    // candidate limit it has in a launch of its own, computed by the host (a kind-1 query alone sizes its query region by its
+    // entries, not by the dimension).
+    const uint32_t* qkind;
+    const uint32_t* qccap;
 };
 
 // Entries of the candidate heap the first launch gives a query walking with `ef` (fixed: nmn_hnsw_set_heap_capacity, 0 = default).
@@ -522,10 +529,13 @@ __device__ __forceinline__ float q8_distance(const uint8_t* __restrict__ row, co
 // QK: the query kind.  0: a dense query, everything above.  1 (dense rows, Cosine / DotProduct): the query is a SparseVector — its
 // stored entries sit in the query region of LDS as (u32 position, f32 value) pairs, rows are scored by sparse_distance, and the
 // query's magnitude is a.qmag[q].  2 (quantized rows): a dense query whose Cosine magnitude is a.qmag[q] instead of the
-// simd::magnitude the wave computes.  QK is a template parameter so that the QK == 0 instantiations stay the code they were.
+// simd::magnitude the wave computes.  3 (PERQ only): the kind is the query's own, a.qkind[q] — 0 or 1 on dense rows, 0 or 2 on
+// quantized rows — and so is its candidate limit, a.qccap[q]; a wave serves one query, so every branch on the kind is
+// wave-uniform.  QK is a template parameter so that the QK == 0 instantiations stay the code they were.
 template <bool SPILL, bool Q8, bool PERQ, int QK = 0>
 __global__ __launch_bounds__(64) void hnsw_search_kernel(SearchArgs a) {
-    static_assert(QK == 0 || (QK == 1 && !Q8 && !PERQ) || (QK == 2 && Q8 && !PERQ), "query kinds: 1 on dense rows, 2 on quantized rows");
+    static_assert(QK == 0 || (QK == 1 && !Q8 && !PERQ) || (QK == 2 && Q8 && !PERQ) || (QK == 3 && PERQ),
+                  "query kinds: 1 on dense rows, 2 on quantized rows, 3 = a kind per query of a per-query launch");
     extern __shared__ float4 smem4[];
     const GraphDev& g = a.g;
     const uint32_t lane = threadIdx.x, p = lane >> 1, h = lane & 1u;
@@ -549,7 +559,14 @@ __global__ __launch_bounds__(64) void hnsw_search_kernel(SearchArgs a) {
         const float* qv = qs;
         __syncthreads();
         uint32_t nnz = 0;
-        if constexpr (QK == 1) {
+        bool entries = QK == 1;             // the query region holds stored entries, rows are scored by sparse_distance
+        bool mag_given = QK == 1 || QK == 2;  // the Cosine magnitude is a.qmag[q]
+        if constexpr (QK == 3) {
+            const uint32_t kind = a.qkind[q];
+            entries = !Q8 && kind == 1u;
+            mag_given = kind != 0u;
+        }
+        if (QK != 0 && QK != 2 && entries) {
             const uint64_t e0 = a.sp_off[q];
             nnz = min((uint32_t)(a.sp_off[q + 1] - e0), a.qlds >> 1);  // (the host sized the region by the launch's largest count)
             uint2* el = reinterpret_cast<uint2*>(qs);
@@ -566,7 +583,8 @@ __global__ __launch_bounds__(64) void hnsw_search_kernel(SearchArgs a) {
         const uint32_t k_q = PERQ && a.qk ? a.qk[q] : a.k;
         const uint32_t ef_q = PERQ && a.qef ? a.qef[q] : a.ef;
         const uint32_t kstride = PERQ ? a.kstride : a.k;
-        const uint32_t ccap_q = PERQ && !SPILL ? min(a.ccap, cand_cap(ef_q, a.ccap_fixed, g.dim, g.n)) : a.ccap;
+        const uint32_t ccap_q =
+            PERQ && !SPILL ? min(a.ccap, QK == 3 ? a.qccap[q] : cand_cap(ef_q, a.ccap_fixed, g.dim, g.n)) : a.ccap;
         uint64_t* o_ids = a.out_ids + (size_t)q * kstride;
         float* o_sc = a.out_scores + (size_t)q * kstride;
         if (g.n == 0 || g.entry == kNone) {  // hnsw.rs:2070-2073
@@ -582,7 +600,7 @@ __global__ __launch_bounds__(64) void hnsw_search_kernel(SearchArgs a) {
             continue;
         }
         float qmag = 0.0f;
-        if constexpr (QK == 0) {
+        if (QK == 0 || !mag_given) {
             if (g.metric == NMN_METRIC_COSINE) qmag = d_sqrt(-pair_distance(qv, 0.f, qv, 0.f, g.dim, NMN_METRIC_DOT_PRODUCT, h));
         } else {
             if (g.metric == NMN_METRIC_COSINE) qmag = a.qmag[q];
@@ -593,7 +611,7 @@ __global__ __launch_bounds__(64) void hnsw_search_kernel(SearchArgs a) {
             if (g.metric == NMN_METRIC_EUCLIDEAN) qside.sq = -pair_distance(qv, 0.f, qv, 0.f, g.dim, NMN_METRIC_DOT_PRODUCT, h);
         }
         auto row_distance = [&](uint32_t node) -> float {
-            if constexpr (QK == 1)
+            if (QK != 0 && QK != 2 && entries)
                 return sparse_distance(g.corpus + (size_t)node * g.ld, g.norms[node], reinterpret_cast<const uint2*>(qv), nnz, qmag,
                                        g.metric, h);
             else if constexpr (Q8)
@@ -805,7 +823,7 @@ struct nmn_hnsw {
     std::mutex host_mu;
     hipStream_t host_stream = nullptr;
     DevBuf hq, hids, hsc, hcnt, hkef;
-    DevBuf hsp_off, hsp_ent, hqmag;  // nmn_hnsw_search_sparse: the launch's entry offsets, its (position, value) pairs, Q.magnitude() per query
+    DevBuf hsp_off, hsp_ent, hqmag;  // sparse slots of a batch: the launch's entry offsets, its (position, value) pairs, Q.magnitude() per query
     DevBuf hxmeta, hxsim, hxoids, hxosc, hxocnt, hxsort;  // a batch's metric slots (docs/hnsw.md §12): what their launches read and answer into
     // ... and what a batch of mixed k / ef passes through on the host (under host_mu): the queries gathered in launch order, k and ef
     // per query, the launch's rows before they are handed to their callers
@@ -817,6 +835,10 @@ struct nmn_hnsw {
     std::vector<uint32_t> st_xmeta, st_xocnt;
     std::vector<uint64_t> st_xoids;
     std::vector<float> st_xosc;
+    // ... and a batch's sparse slots (docs/hnsw.md §14): the entries of the kind-1 queries as a CSR in launch order, Q.magnitude() per query
+    std::vector<uint64_t> st_spoff;
+    std::vector<uint2> st_spent;
+    std::vector<float> st_mag;
     // the request coalescer in front of it (docs/hnsw.md §11): one batch runs at a time, whoever arrives meanwhile waits here
     nmn::WalkQueue co;
 };
@@ -1066,7 +1088,10 @@ inline float h_sparse_mag(const float* val, uint64_t nnz) {
 }
 
 // The queries of one nmn_hnsw_search_sparse call as SparseVector::try_from_parts leaves them: entries with val == 0.0 (either sign)
-// dropped, NaN kept, the rest stably sorted by position (duplicates survive in input order).
+// dropped, NaN kept, the rest stably sorted by position (duplicates survive in input order).  (Named in nmn:: because a HostWalk
+// carries a pointer to it through the coalescer, nmn_hnsw_queue.h.)
+}  // namespace
+namespace nmn {
 struct SparseQueries {
     std::vector<uint64_t> off;  // [nq + 1]
     std::vector<uint32_t> pos;
@@ -1078,6 +1103,8 @@ struct SparseQueries {
         for (uint64_t i = off[q]; i < off[q + 1]; i++) out[pos[i]] = val[i];
     }
 };
+}  // namespace nmn
+namespace {
 
 nmn_status canonicalise_sparse(uint32_t dim, const uint64_t* indptr, const uint32_t* positions, const float* values, uint32_t nq,
                                SparseQueries* out) {
@@ -1329,7 +1356,11 @@ SearchArgs graph_args(const nmn_hnsw* h, uint32_t n) {
 
 template <bool SPILL>
 void launch_walk(bool q8, bool perq, int qkind, uint32_t grid, size_t lds, hipStream_t s, const SearchArgs& a) {
-    if (qkind == 1)
+    if (qkind == 3 && q8)
+        hipLaunchKernelGGL((hnsw_search_kernel<SPILL, true, true, 3>), dim3(grid), dim3(64), lds, s, a);
+    else if (qkind == 3)
+        hipLaunchKernelGGL((hnsw_search_kernel<SPILL, false, true, 3>), dim3(grid), dim3(64), lds, s, a);
+    else if (qkind == 1)
         hipLaunchKernelGGL((hnsw_search_kernel<SPILL, false, false, 1>), dim3(grid), dim3(64), lds, s, a);
     else if (qkind == 2)
         hipLaunchKernelGGL((hnsw_search_kernel<SPILL, true, false, 2>), dim3(grid), dim3(64), lds, s, a);
@@ -1353,13 +1384,17 @@ struct WalkShape {
     const uint32_t* qk = nullptr;
     const uint32_t* qef = nullptr;
     uint32_t kstride = 0, n_lds = 0, rcap_lds = 0, ef_lds = 0, rcap_all = 0;
-    // the query kind of hnsw_search_kernel (uniform launches only).  1: no dense queries — DEVICE arrays sp_off [nq + 1] / sp_ent,
-    // sp_max = the largest entry count of the call; 1 and 2: DEVICE array qmag [nq]
+    // the query kind of hnsw_search_kernel.  1 (uniform launches): no dense queries — DEVICE arrays sp_off [nq + 1] / sp_ent,
+    // sp_max = the largest entry count of the call; 1 and 2 (uniform launches): DEVICE array qmag [nq].  3 (per-query launches): all
+    // of these, and DEVICE arrays qkinds / qccap [nq], the kind of every query and its own candidate limit.
     int qkind = 0;
     const uint64_t* sp_off = nullptr;
     const uint2* sp_ent = nullptr;
     const float* qmag = nullptr;
     uint32_t sp_max = 0;
+    const uint32_t* qkinds = nullptr;
+    const uint32_t* qccap = nullptr;
+    bool sp_only = false;  // qkind 3: every query is kind 1, so the query region need not hold a dense query
 };
 
 uint32_t results_need(uint32_t ef_eff, uint32_t n) { return std::min<uint32_t>(ef_eff, std::max<uint32_t>(n, 1)) + 1; }
@@ -1381,8 +1416,13 @@ nmn_status enqueue_walk_locked(nmn_hnsw* h, nmn_hnsw::Scratch* sc, const float* 
     // floats of the query region: the dense query padded to 8, or the stored entries of the longest sparse query, 2 floats each
     // (kSparseLdsEntries at most: no more than a dense query of 8192 dimensions, so cand_cap's rule for long queries carries over
     // with the region's length in place of the dimension)
-    const uint32_t qlds = w.qkind == 1 ? std::max<uint32_t>(2u * w.sp_max, 2u) : (h->dim + 7u) & ~7u;
-    const uint32_t ccap = cand_cap(w.ef_lds, h->lds_ccap, w.qkind == 1 ? qlds : h->dim, n);
+    // (a launch with a kind per query holds either: the longer of the two — of the entries alone when no query of it is dense, so
+    // that a call of kind-1 queries only keeps the region, and with it the candidate limit, it has as a QK = 1 launch)
+    const uint32_t dim8 = (h->dim + 7u) & ~7u;
+    const uint32_t qlds = w.qkind == 1 || (w.qkind == 3 && w.sp_only) ? std::max<uint32_t>(2u * w.sp_max, 2u)
+                          : w.qkind == 3                              ? std::max<uint32_t>(dim8, 2u * w.sp_max)
+                                                                      : dim8;
+    const uint32_t ccap = cand_cap(w.ef_lds, h->lds_ccap, w.qkind == 1 || w.qkind == 3 ? qlds : h->dim, n);
     const uint32_t s_rcap = w.rcap_all, s_ccap = std::max<uint32_t>(n, 1);
     const uint64_t region = (uint64_t)s_rcap + s_ccap;
     const uint32_t regions = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint32_t>(chunk, 64), (256ull << 20) / (region * sizeof(Ent))));
@@ -1408,6 +1448,8 @@ nmn_status enqueue_walk_locked(nmn_hnsw* h, nmn_hnsw::Scratch* sc, const float* 
         a.sp_off = w.sp_off ? w.sp_off + q0 : nullptr;
         a.sp_ent = w.sp_ent;
         a.qmag = w.qmag ? w.qmag + q0 : nullptr;
+        a.qkind = w.qkinds ? w.qkinds + q0 : nullptr;
+        a.qccap = w.qccap ? w.qccap + q0 : nullptr;
         a.qk = w.qk ? w.qk + q0 : nullptr;
         a.qef = w.qef ? w.qef + q0 : nullptr;
         a.flags = (uint32_t*)sc->flags.p + q0;
@@ -1846,6 +1888,7 @@ struct Slot {
     uint32_t i, k, ef;       // what the query walks with (a metric query: k = its candidate count c, ef = max(ef_search, c))
     uint32_t top;            // a metric query's top_k
     const nmn_xmetric* xm;   // ... and its metric (nullptr: a plain walk)
+    uint32_t kind;           // the kernel's query kind: sparse_route for a query of a sparse call, 0 for every other
 };
 
 // A batch whose slots are all metric slots with one top_k and one metric (a lone nmn_hnsw_search_metric is one): the uniform chain
@@ -1944,26 +1987,31 @@ nmn_status run_metric_uniform(nmn_hnsw* h, const std::vector<HostWalk*>& batch, 
 // launch order (those that start in LDS first), and the launch's rows, kstride = the largest k apart, are handed out on the host.
 // Metric calls (docs/hnsw.md §12) ride the same walk with k = their candidate count; behind it, on the same stream, the per-query
 // re-rank and ordering run over the metric slots, and one read-back serves everybody.  A batch of metric slots with one top_k and
-// one metric is run_metric_uniform.  Takes rw (shared) and host_mu for the batch.  A failure is the whole batch's.
+// one metric is run_metric_uniform.  Sparse calls (§14) bring a query kind per slot, sparse_route's: a kind-0 slot is densified
+// here and is a dense query from then on; a batch with other kinds is the per-query launch with QK = 3, except the lone sparse
+// call with one k and one ef, which stays the uniform QK = 1 / QK = 2 launch.  Takes rw (shared) and host_mu for the batch.  A
+// failure is the whole batch's.
 // on_host (a metric call under NMN_HNSW_HOST_SEARCH=1, alone): the walks on the host, the re-rank on the device.
 nmn_status run_batch(nmn_hnsw* h, const std::vector<HostWalk*>& batch, bool on_host = false) {
     std::shared_lock<std::shared_mutex> g(h->rw);
     std::lock_guard<std::mutex> hl(h->host_mu);  // the insert's upload uses the same stream and staging
     HN_TRY(hipSetDevice(h->device));
     const uint32_t n = (uint32_t)h->level.size(), dim = h->dim;
+    const uint32_t route = (uint32_t)sparse_route(h);
     uint32_t N = 0;
     for (const HostWalk* r : batch) N += r->nq;
     std::vector<Slot> slot;  // launch order
     slot.reserve(N);
     auto slot_of = [&](HostWalk* r, uint32_t i) {
-        if (!r->xm) return Slot{r, i, r->k_of(i), r->ef_of(i, h->cfg.ef_search), 0, nullptr};
+        if (r->sp) return Slot{r, i, r->k_of(i), r->ef_of(i, h->cfg.ef_search), 0, nullptr, route};
+        if (!r->xm) return Slot{r, i, r->k_of(i), r->ef_of(i, h->cfg.ef_search), 0, nullptr, 0};
         const uint32_t c = (uint32_t)metric_candidates(h, r->k_of(i));  // here, under rw: an insert may have run since the call was checked
-        return Slot{r, i, c, std::max<uint32_t>(h->cfg.ef_search, c), r->k_of(i), &r->metric_of(i)};
+        return Slot{r, i, c, std::max<uint32_t>(h->cfg.ef_search, c), r->k_of(i), &r->metric_of(i), 0};
     };
     const Slot s0 = slot_of(batch[0], 0);
     const uint32_t k0 = s0.k, ef0 = s0.ef;
     const uint32_t row0 = s0.xm ? s0.top : k0;  // the callers' row length a uniform batch needs
-    bool uniform = true;
+    bool uniform = true, plain = true;  // plain: every slot is a dense query to the kernel (kind 0)
     uint32_t kmax = 0, M = 0, topmax = 0;
     for (HostWalk* r : batch) {
         r->evals = 0;
@@ -1974,6 +2022,7 @@ nmn_status run_batch(nmn_hnsw* h, const std::vector<HostWalk*>& batch, bool on_h
             const Slot sl = slot_of(r, i);
             if (sl.k != k0 || sl.ef != ef0 || sl.top != s0.top || !sl.xm != !s0.xm || (sl.xm && memcmp(sl.xm, s0.xm, sizeof(nmn_xmetric)) != 0))
                 uniform = false;
+            if (sl.kind != 0u) plain = false;
             kmax = std::max(kmax, sl.k);
             if (sl.xm) {
                 M++;
@@ -1983,10 +2032,14 @@ nmn_status run_batch(nmn_hnsw* h, const std::vector<HostWalk*>& batch, bool on_h
         }
     }
     if (uniform && M) return run_metric_uniform(h, batch, slot, on_host);
+    // one sparse call with one k and one ef keeps the uniform launch of its kind; every other batch with a kind-1 or kind-2 slot in
+    // it is the per-query launch, whatever its k and ef
+    const bool lone_sparse = uniform && !plain && batch.size() == 1;
+    const bool perq = !uniform || (!plain && !lone_sparse);
     hipStream_t s = h->host_stream;
     bool synced = true;  // (every earlier host call ended with a wait)
     const hipStream_t none = (hipStream_t)-1;
-    const uint32_t kstride = uniform ? k0 : kmax;
+    const uint32_t kstride = kmax;  // (a uniform batch: k0)
     HN_TRY(grow(h->hq, (size_t)N * dim * 4, none, &synced));
     HN_TRY(grow(h->hids, (size_t)N * kstride * 8, none, &synced));
     HN_TRY(grow(h->hsc, (size_t)N * kstride * 4, none, &synced));
@@ -1994,6 +2047,64 @@ nmn_status run_batch(nmn_hnsw* h, const std::vector<HostWalk*>& batch, bool on_h
     nmn_hnsw::Scratch* sc = scratch_of(h, s);
     std::vector<uint32_t> fl(N), ev(N);
     static thread_local HostVisited vis;
+    // a query with more stored entries than a wave keeps in LDS walks in the launch as an entry-less query and is answered by the host
+    auto too_long = [&](const Slot& x) { return x.kind == 1u && x.r->sp->nnz(x.i) > kSparseLdsEntries; };
+    auto host_one = [&](const Slot& x, uint64_t* ids, float* scs, uint32_t* cnt, uint64_t* e2) {
+        if (x.r->sp)
+            host_search_one_sparse(h, *x.r->sp, x.i, x.k, x.ef, vis, ids, scs, cnt, e2);
+        else
+            host_search_one(h, x.r->q + (size_t)x.i * dim, x.k, x.ef, vis, ids, scs, cnt, e2);
+    };
+    // The queries of the slots, in launch order, into the host staging and up: the dense form of every slot that is not kind 1
+    // (a sparse call's by to_dense) into hq, and, when a slot is not kind 0, the CSR of the kind-1 slots and Q.magnitude() of
+    // every sparse slot.  w gets what the kernel reads of them.
+    auto stage_queries = [&](WalkShape& w) -> nmn_status {
+        bool any_dense = false;  // (a launch of kind-1 queries only reads no dense query: nothing to fill or send)
+        for (const Slot& x : slot) any_dense = any_dense || x.kind != 1u;
+        if (any_dense) h->st_q.resize((size_t)N * dim);
+        h->st_spoff.assign(1, 0);
+        h->st_spent.clear();
+        h->st_mag.assign(N, 0.0f);
+        for (uint32_t j = 0; j < N; j++) {
+            const Slot& x = slot[j];
+            float* dq = h->st_q.data() + (size_t)j * dim;
+            if (x.kind == 1u) {
+                const SparseQueries& sq = *x.r->sp;
+                const uint64_t c = sq.nnz(x.i);
+                if (c <= kSparseLdsEntries) {
+                    for (uint64_t e = sq.off[x.i]; e < sq.off[x.i + 1]; e++) {
+                        uint32_t bits;
+                        memcpy(&bits, &sq.val[e], 4);
+                        h->st_spent.push_back(make_uint2(sq.pos[e], bits));
+                    }
+                    w.sp_max = std::max<uint32_t>(w.sp_max, (uint32_t)c);
+                }
+                if (any_dense) std::fill(dq, dq + dim, 0.0f);  // (not read: the launch takes this query from its entries)
+            } else if (x.r->sp) {
+                x.r->sp->to_dense(x.i, dim, dq);
+            } else {
+                memcpy(dq, x.r->q + (size_t)x.i * dim, (size_t)dim * 4);
+            }
+            if (x.kind != 0u) h->st_mag[j] = x.r->sp->mag[x.i];
+            h->st_spoff.push_back(h->st_spent.size());
+        }
+        if (any_dense) HN_TRY(hipMemcpyAsync(h->hq.p, h->st_q.data(), (size_t)N * dim * 4, hipMemcpyHostToDevice, s));
+        w.sp_only = !any_dense;
+        if (plain) return NMN_OK;
+        if (route == kSparseGather) {
+            HN_TRY(grow(h->hsp_off, h->st_spoff.size() * 8, none, &synced));
+            HN_TRY(grow(h->hsp_ent, std::max<size_t>(h->st_spent.size(), 1) * 8, none, &synced));
+            HN_TRY(hipMemcpyAsync(h->hsp_off.p, h->st_spoff.data(), h->st_spoff.size() * 8, hipMemcpyHostToDevice, s));
+            if (!h->st_spent.empty())
+                HN_TRY(hipMemcpyAsync(h->hsp_ent.p, h->st_spent.data(), h->st_spent.size() * 8, hipMemcpyHostToDevice, s));
+            w.sp_off = (const uint64_t*)h->hsp_off.p;
+            w.sp_ent = (const uint2*)h->hsp_ent.p;
+        }
+        HN_TRY(grow(h->hqmag, (size_t)N * 4, none, &synced));
+        HN_TRY(hipMemcpyAsync(h->hqmag.p, h->st_mag.data(), (size_t)N * 4, hipMemcpyHostToDevice, s));
+        w.qmag = (const float*)h->hqmag.p;
+        return NMN_OK;
+    };
     XmetricBatchPlan plan;
     auto metric_chain = [&]() -> nmn_status {  // behind whatever filled the walk's rows on s; the answers on their way back
         if (!M) return NMN_OK;
@@ -2006,19 +2117,37 @@ nmn_status run_batch(nmn_hnsw* h, const std::vector<HostWalk*>& batch, bool on_h
         HN_TRY(hipMemcpyAsync(h->st_xocnt.data(), h->hxocnt.p, (size_t)M * 4, hipMemcpyDeviceToHost, s));
         return NMN_OK;
     };
-    if (uniform) {
-        uint32_t off = 0;
-        for (const HostWalk* r : batch) {
-            HN_TRY(hipMemcpyAsync((float*)h->hq.p + (size_t)off * dim, r->q, (size_t)r->nq * dim * 4, hipMemcpyHostToDevice, s));
-            off += r->nq;
-        }
-        {
+    if (!perq) {
+        if (lone_sparse) {  // the launch of the call's kind, k and ef in the arguments
+            WalkShape w = uniform_shape(h, N, k0, ef0);
+            w.qkind = (int)route;
+            nmn_status st = stage_queries(w);
+            if (st != NMN_OK) return st;
+            std::lock_guard<std::mutex> slk(sc->mu);
+            st = enqueue_walk_locked(h, sc, route == kSparseGather ? nullptr : (const float*)h->hq.p, N, w, (uint64_t*)h->hids.p,
+                                     (float*)h->hsc.p, (uint32_t*)h->hcnt.p, s);
+            if (st != NMN_OK) return st;
+        } else {
+            bool densify = false;
+            for (const HostWalk* r : batch) densify = densify || r->sp;
+            if (densify) h->st_q.resize((size_t)N * dim);
+            uint32_t off = 0;
+            for (const HostWalk* r : batch) {
+                const float* src = r->q;
+                if (r->sp) {  // (kind 0: the dense walk of Q.to_dense())
+                    float* dq = h->st_q.data() + (size_t)off * dim;
+                    for (uint32_t i = 0; i < r->nq; i++) r->sp->to_dense(i, dim, dq + (size_t)i * dim);
+                    src = dq;
+                }
+                HN_TRY(hipMemcpyAsync((float*)h->hq.p + (size_t)off * dim, src, (size_t)r->nq * dim * 4, hipMemcpyHostToDevice, s));
+                off += r->nq;
+            }
             std::lock_guard<std::mutex> slk(sc->mu);
             nmn_status st = enqueue_search_locked(h, sc, (const float*)h->hq.p, N, k0, ef0, (uint64_t*)h->hids.p, (float*)h->hsc.p,
                                                   (uint32_t*)h->hcnt.p, s);
             if (st != NMN_OK) return st;
         }
-        off = 0;
+        uint32_t off = 0;
         for (const HostWalk* r : batch) {
             HN_TRY(hipMemcpyAsync(r->out_ids, (uint64_t*)h->hids.p + (size_t)off * k0, (size_t)r->nq * k0 * 8, hipMemcpyDeviceToHost, s));
             HN_TRY(hipMemcpyAsync(r->out_scores, (float*)h->hsc.p + (size_t)off * k0, (size_t)r->nq * k0 * 4, hipMemcpyDeviceToHost, s));
@@ -2030,14 +2159,21 @@ nmn_status run_batch(nmn_hnsw* h, const std::vector<HostWalk*>& batch, bool on_h
         std::stable_partition(slot.begin(), slot.end(), [&](const Slot& x) { return results_fit_lds(h, x.ef, n); });
         WalkShape w;
         w.kstride = kstride;
-        h->st_q.resize((size_t)N * dim);
-        h->st_kef.resize((size_t)2 * N);
+        // k and ef per query; with a kind per query (QK = 3) also the kind and the candidate limit the query has in a launch of its
+        // own: a kind-1 query alone sizes its query region by its entries (enqueue_walk_locked), every other by the dimension
+        const uint32_t per = plain ? 2u : 4u;
+        h->st_kef.resize((size_t)per * N);
         h->st_xitems.clear();
         for (uint32_t j = 0; j < N; j++) {
             const Slot& x = slot[j];
-            memcpy(h->st_q.data() + (size_t)j * dim, x.r->q + (size_t)x.i * dim, (size_t)dim * 4);
             h->st_kef[j] = x.k;
             h->st_kef[N + j] = x.ef;
+            if (!plain) {
+                uint32_t region = dim;
+                if (x.kind == 1u) region = too_long(x) ? 2u : std::max<uint32_t>(2u * (uint32_t)x.r->sp->nnz(x.i), 2u);
+                h->st_kef[2 * N + j] = x.kind;
+                h->st_kef[3 * N + j] = cand_cap(x.ef, h->lds_ccap, region, n);
+            }
             if (x.xm) h->st_xitems.push_back(XmetricBatchItem{j, x.k, x.top, *x.xm});
             const uint32_t need = results_need(x.ef, n);
             w.rcap_all = std::max(w.rcap_all, need);
@@ -2047,11 +2183,17 @@ nmn_status run_batch(nmn_hnsw* h, const std::vector<HostWalk*>& batch, bool on_h
                 w.ef_lds = std::max(w.ef_lds, x.ef);
             }
         }
-        HN_TRY(grow(h->hkef, (size_t)2 * N * 4, none, &synced));
+        HN_TRY(grow(h->hkef, (size_t)per * N * 4, none, &synced));
         w.qk = (const uint32_t*)h->hkef.p;
         w.qef = w.qk + N;
-        HN_TRY(hipMemcpyAsync(h->hq.p, h->st_q.data(), (size_t)N * dim * 4, hipMemcpyHostToDevice, s));
-        HN_TRY(hipMemcpyAsync(h->hkef.p, h->st_kef.data(), (size_t)2 * N * 4, hipMemcpyHostToDevice, s));
+        if (!plain) {
+            w.qkind = 3;
+            w.qkinds = w.qk + 2 * (size_t)N;
+            w.qccap = w.qk + 3 * (size_t)N;
+        }
+        nmn_status stq = stage_queries(w);
+        if (stq != NMN_OK) return stq;
+        HN_TRY(hipMemcpyAsync(h->hkef.p, h->st_kef.data(), (size_t)per * N * 4, hipMemcpyHostToDevice, s));
         // the metric slots: what the re-rank and ordering launches read, and the rows they answer into (row m = the m-th metric slot)
         if (M) {
             xmetric_batch_plan(h->st_xitems.data(), M, N, h->st_xmeta, plan);
@@ -2102,7 +2244,7 @@ nmn_status run_batch(nmn_hnsw* h, const std::vector<HostWalk*>& batch, bool on_h
         uint64_t* ids = h->st_ids.data() + (size_t)j * kstride;
         float* scs = h->st_sc.data() + (size_t)j * kstride;
         uint64_t e2 = 0;
-        host_search_one(h, x.r->q + (size_t)x.i * dim, x.k, x.ef, vis, ids, scs, &h->st_cnt[j], &e2);
+        host_one(x, ids, scs, &h->st_cnt[j], &e2);
         pad_row(ids, scs, x.k, kstride);
         ev[j] = (uint32_t)e2;
         HN_TRY(hipMemcpyAsync((uint64_t*)h->hids.p + (size_t)j * kstride, ids, (size_t)kstride * 8, hipMemcpyHostToDevice, s));
@@ -2128,15 +2270,17 @@ nmn_status run_batch(nmn_hnsw* h, const std::vector<HostWalk*>& batch, bool on_h
             r->rescored = std::max(r->rescored, std::min(h->st_cnt[j], x.k));
             if (!on_host && fl[j] != 0u) r->spilled++;
             m++;
-        } else if (fl[j] == 1u) {  // the spill launch could not answer it (cannot happen while its heap holds n entries): the host walk does
+        } else if (fl[j] == 1u || too_long(x)) {
+            // the spill launch could not answer it (cannot happen while its heap holds n entries), or its entries did not fit LDS:
+            // the host walk does, into the caller's row
             uint64_t e2 = 0;
-            host_search_one(h, r->q + (size_t)x.i * dim, x.k, x.ef, vis, ids, scs, r->out_counts + x.i, &e2);
+            host_one(x, ids, scs, r->out_counts + x.i, &e2);
             pad_row(ids, scs, x.k, r->kstride);
             ev[j] = (uint32_t)e2;
-            r->spilled++;
+            if (!too_long(x)) r->spilled++;
         } else {
             if (fl[j] == 2u) r->spilled++;
-            if (!uniform) {  // slots [count, kstride) of the launch's row hold the sentinels already; the caller's row may be longer
+            if (perq) {  // slots [count, kstride) of the launch's row hold the sentinels already; the caller's row may be longer
                 const uint32_t c = std::min(kstride, r->kstride);
                 memcpy(ids, h->st_ids.data() + (size_t)j * kstride, (size_t)c * 8);
                 memcpy(scs, h->st_sc.data() + (size_t)j * kstride, (size_t)c * 4);
@@ -2158,7 +2302,7 @@ nmn_status submit_walk(nmn_hnsw* h, HostWalk& me) {
     return st;
 }
 
-// nmn_hnsw_search and nmn_hnsw_search_multi behind their argument checks
+// nmn_hnsw_search, nmn_hnsw_search_multi, nmn_hnsw_search_sparse and nmn_hnsw_search_sparse_multi behind their argument checks
 nmn_status host_walk_call(nmn_hnsw* h, HostWalk& me, nmn_search_stats* stats) {
     const bool on_host = host_search_forced();
     if (on_host) {  // no turn to take: every caller walks on its own thread
@@ -2167,7 +2311,10 @@ nmn_status host_walk_call(nmn_hnsw* h, HostWalk& me, nmn_search_stats* stats) {
         for (uint32_t q = 0; q < me.nq; q++) {
             uint64_t* ids = me.out_ids + (size_t)q * me.kstride;
             float* scs = me.out_scores + (size_t)q * me.kstride;
-            host_search_one(h, me.q + (size_t)q * h->dim, me.k_of(q), me.ef_of(q, h->cfg.ef_search), vis, ids, scs, me.out_counts + q, &me.evals);
+            if (me.sp)
+                host_search_one_sparse(h, *me.sp, q, me.k_of(q), me.ef_of(q, h->cfg.ef_search), vis, ids, scs, me.out_counts + q, &me.evals);
+            else
+                host_search_one(h, me.q + (size_t)q * h->dim, me.k_of(q), me.ef_of(q, h->cfg.ef_search), vis, ids, scs, me.out_counts + q, &me.evals);
             pad_row(ids, scs, me.k_of(q), me.kstride);
         }
     } else {
@@ -2258,8 +2405,21 @@ extern "C" nmn_status nmn_hnsw_search_multi(nmn_hnsw* h, const float* queries, u
     return host_walk_call(h, me, stats);
 }
 
-// HNSWIndex::search_sparse_with_ef (hnsw.rs:2118-2166), docs/hnsw.md §13.  Not coalesced: the call takes rw (shared) and host_mu
-// for its duration and so takes turns with the batches of the coalescer.
+namespace {
+// A sparse call shares a batch only where that leaves every rider's candidate limit what it is alone (docs/hnsw.md §14): the query
+// region of a batch holds the longer of a dense query and the longest entry list, and cand_cap halves the limit above 4096 floats.
+// A kind-1 call alone sizes the region by its entries; so it rides alone when the dimension is above 4096 (the batch's region would
+// be long where its own may be short) or when one of its queries has more than 2048 entries (its region would be long for everybody).
+bool sparse_rides_alone(const nmn_hnsw* h, const SparseQueries& sq, uint32_t nq) {
+    if (sparse_route(h) != kSparseGather) return false;
+    if (h->dim > 4096u) return true;
+    for (uint32_t q = 0; q < nq; q++)
+        if (sq.nnz(q) > 2048u) return true;
+    return false;
+}
+}  // namespace
+
+// HNSWIndex::search_sparse_with_ef (hnsw.rs:2118-2166), docs/hnsw.md §13.  Through the coalescer like nmn_hnsw_search (§14).
 extern "C" nmn_status nmn_hnsw_search_sparse(nmn_hnsw* h, const uint64_t* indptr, const uint32_t* positions, const float* values,
                                              uint32_t nq, uint32_t k, uint32_t ef, uint64_t* out_ids, float* out_scores,
                                              uint32_t* out_counts, nmn_search_stats* stats) {
@@ -2271,102 +2431,51 @@ extern "C" nmn_status nmn_hnsw_search_sparse(nmn_hnsw* h, const uint64_t* indptr
     }
     if (nq == 0) return NMN_OK;
     if (!indptr || !out_ids || !out_scores || !out_counts) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
-    SparseQueries sq;  // every query as try_from_parts leaves it, before anything is enqueued or written
-    nmn_status st = canonicalise_sparse(h->dim, indptr, positions, values, nq, &sq);
+    SparseQueries sq;  // every query as try_from_parts leaves it, before the call joins a batch or anything is written
+    const nmn_status st = canonicalise_sparse(h->dim, indptr, positions, values, nq, &sq);
     if (st != NMN_OK) return st;
-    const bool on_host = host_search_forced();
-    const uint32_t dim = h->dim;
-    uint64_t evals = 0, spilled = 0;
-    static thread_local HostVisited vis;
-    std::shared_lock<std::shared_mutex> g(h->rw);
-    const uint64_t ef_eff = ef ? ef : h->cfg.ef_search;
-    const auto host_one = [&](uint32_t q, uint64_t* ev) {
-        host_search_one_sparse(h, sq, q, k, ef_eff, vis, out_ids + (size_t)q * k, out_scores + (size_t)q * k, out_counts + q, ev);
-    };
-    if (on_host) {
-        for (uint32_t q = 0; q < nq; q++) host_one(q, &evals);
-    } else {
-        std::lock_guard<std::mutex> hl(h->host_mu);  // the handle's own stream and staging, as a batch of the coalescer holds them
-        HN_TRY(hipSetDevice(h->device));
-        const SparseRoute route = sparse_route(h);
-        hipStream_t s = h->host_stream;
-        bool synced = true;  // (every earlier host call ended with a wait)
-        const hipStream_t none = (hipStream_t)-1;
-        HN_TRY(grow(h->hids, (size_t)nq * k * 8, none, &synced));
-        HN_TRY(grow(h->hsc, (size_t)nq * k * 4, none, &synced));
-        HN_TRY(grow(h->hcnt, (size_t)nq * 4, none, &synced));
-        WalkShape w = uniform_shape(h, nq, k, ef);
-        w.qkind = (int)route;
-        const float* q_dev = nullptr;
-        std::vector<uint64_t> l_off;  // kSparseGather: the launch's offsets — a query too long for LDS walks as an empty one there
-        std::vector<uint2> l_ent;     //   and is answered by the host below
-        if (route == kSparseGather) {
-            l_off.assign(1, 0);
-            l_off.reserve((size_t)nq + 1);
-            for (uint32_t q = 0; q < nq; q++) {
-                const uint64_t c = sq.nnz(q);
-                if (c <= kSparseLdsEntries) {
-                    for (uint64_t i = sq.off[q]; i < sq.off[q + 1]; i++) {
-                        uint32_t bits;
-                        memcpy(&bits, &sq.val[i], 4);
-                        l_ent.push_back(make_uint2(sq.pos[i], bits));
-                    }
-                    w.sp_max = std::max<uint32_t>(w.sp_max, (uint32_t)c);
-                }
-                l_off.push_back(l_ent.size());
-            }
-            HN_TRY(grow(h->hsp_off, l_off.size() * 8, none, &synced));
-            HN_TRY(grow(h->hsp_ent, std::max<size_t>(l_ent.size(), 1) * 8, none, &synced));
-            HN_TRY(hipMemcpyAsync(h->hsp_off.p, l_off.data(), l_off.size() * 8, hipMemcpyHostToDevice, s));
-            if (!l_ent.empty()) HN_TRY(hipMemcpyAsync(h->hsp_ent.p, l_ent.data(), l_ent.size() * 8, hipMemcpyHostToDevice, s));
-            w.sp_off = (const uint64_t*)h->hsp_off.p;
-            w.sp_ent = (const uint2*)h->hsp_ent.p;
-        } else {
-            h->st_q.resize((size_t)nq * dim);
-            for (uint32_t q = 0; q < nq; q++) sq.to_dense(q, dim, h->st_q.data() + (size_t)q * dim);
-            HN_TRY(grow(h->hq, (size_t)nq * dim * 4, none, &synced));
-            HN_TRY(hipMemcpyAsync(h->hq.p, h->st_q.data(), (size_t)nq * dim * 4, hipMemcpyHostToDevice, s));
-            q_dev = (const float*)h->hq.p;
-        }
-        if (route != kSparseDensify) {
-            HN_TRY(grow(h->hqmag, (size_t)nq * 4, none, &synced));
-            HN_TRY(hipMemcpyAsync(h->hqmag.p, sq.mag.data(), (size_t)nq * 4, hipMemcpyHostToDevice, s));
-            w.qmag = (const float*)h->hqmag.p;
-        }
-        nmn_hnsw::Scratch* sc = scratch_of(h, s);
-        {
-            std::lock_guard<std::mutex> slk(sc->mu);
-            st = enqueue_walk_locked(h, sc, q_dev, nq, w, (uint64_t*)h->hids.p, (float*)h->hsc.p, (uint32_t*)h->hcnt.p, s);
-            if (st != NMN_OK) return st;
-        }
-        std::vector<uint32_t> fl(nq), ev(nq);
-        HN_TRY(hipMemcpyAsync(out_ids, h->hids.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost, s));
-        HN_TRY(hipMemcpyAsync(out_scores, h->hsc.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, s));
-        HN_TRY(hipMemcpyAsync(out_counts, h->hcnt.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
-        HN_TRY(hipMemcpyAsync(fl.data(), sc->flags.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
-        HN_TRY(hipMemcpyAsync(ev.data(), sc->evals.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
-        HN_TRY(hipStreamSynchronize(s));
-        for (uint32_t q = 0; q < nq; q++) {
-            const bool too_long = route == kSparseGather && sq.nnz(q) > kSparseLdsEntries;
-            if (too_long || fl[q] == 1u) {  // (flag 1 after the spill launch cannot happen while its heap holds n entries)
-                uint64_t e2 = 0;
-                host_one(q, &e2);
-                evals += e2;
-                if (!too_long) spilled++;
-            } else {
-                evals += ev[q];
-                if (fl[q] == 2u) spilled++;
-            }
-        }
-    }
+    HostWalk me;
+    me.sp = &sq;
+    me.nq = nq;
+    me.k1 = me.kstride = k;
+    me.ef1 = ef;
+    me.alone = sparse_rides_alone(h, sq, nq);
+    me.out_ids = out_ids;
+    me.out_scores = out_scores;
+    me.out_counts = out_counts;
+    return host_walk_call(h, me, stats);
+}
+
+// The same with a k and an ef per query, as nmn_hnsw_search_multi has them: answer i is nmn_hnsw_search_sparse(q_i, 1, k[i], ef[i]).
+extern "C" nmn_status nmn_hnsw_search_sparse_multi(nmn_hnsw* h, const uint64_t* indptr, const uint32_t* positions, const float* values,
+                                                   uint32_t nq, const uint32_t* k, const uint32_t* ef, uint32_t kstride,
+                                                   uint64_t* out_ids, float* out_scores, uint32_t* out_counts, nmn_search_stats* stats) {
+    if (!h) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (kstride == 0) return set_error(NMN_ERR_INVALID_TOP_K, "kstride == 0");
     if (stats) {
-        stats->rows_scanned = evals;
-        stats->bytes_scanned = h->storage == NMN_HNSW_STORAGE_QUANTIZED ? evals * (dim + 16ull) : evals * dim * 4;
-        stats->fallback_queries = spilled;
-        stats->sweep_kind = h->level.empty() ? NMN_SWEEP_NONE : NMN_SWEEP_GRAPH;
-        stats->sweep_launches = on_host ? 0 : 2;
+        memset(stats, 0, sizeof *stats);
+        stats->scan_ms = stats->total_ms = -1.0f;
     }
-    return NMN_OK;
+    if (nq == 0) return NMN_OK;
+    if (!indptr || !k || !out_ids || !out_scores || !out_counts) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    for (uint32_t i = 0; i < nq; i++) {  // before the call joins a batch: a bad call fails alone, and nothing is written
+        if (k[i] == 0) return set_error(NMN_ERR_INVALID_TOP_K, "k == 0");
+        if (k[i] > kstride) return set_error(NMN_ERR_INVALID_ARGUMENT, "HNSW: k[i] above kstride, the row stride of the outputs");
+    }
+    SparseQueries sq;
+    const nmn_status st = canonicalise_sparse(h->dim, indptr, positions, values, nq, &sq);
+    if (st != NMN_OK) return st;
+    HostWalk me;
+    me.sp = &sq;
+    me.nq = nq;
+    me.k = k;
+    me.ef = ef;
+    me.kstride = kstride;
+    me.alone = sparse_rides_alone(h, sq, nq);
+    me.out_ids = out_ids;
+    me.out_scores = out_scores;
+    me.out_counts = out_counts;
+    return host_walk_call(h, me, stats);
 }
 
 extern "C" nmn_status nmn_hnsw_coalesce_stats(nmn_hnsw* h, uint64_t* batches, uint64_t* calls) {

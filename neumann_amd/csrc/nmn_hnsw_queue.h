@@ -17,10 +17,14 @@ constexpr uint32_t kShareCandMax = 4096;  // a metric call that asks for more ca
                                           // N x max k, and one huge caller must not size them for a thousand others
 constexpr uint32_t kBatchQueries = 1024;  // queries a coalesced batch carries at most: four waves per CU, the largest call §6 measured
 
+struct SparseQueries;  // the canonicalised queries of a sparse call (nmn_hnsw.hip); the queue only carries the pointer
+
 // One call of nmn_hnsw_search (k1 / ef1), nmn_hnsw_search_multi (k / ef per query), nmn_hnsw_search_metric (xm, one metric; k1 its
-// top_k) or nmn_hnsw_search_metric_multi (xm, xm_stride 1: a metric per query; k their top_k) on its way through the coalescer.
+// top_k), nmn_hnsw_search_metric_multi (xm, xm_stride 1: a metric per query; k their top_k), nmn_hnsw_search_sparse (sp; k1 / ef1) or
+// nmn_hnsw_search_sparse_multi (sp; k / ef per query) on its way through the coalescer.
 struct HostWalk {
     const float* q = nullptr;
+    const SparseQueries* sp = nullptr;  // a sparse call (docs/hnsw.md §14): query i is entry i of *sp, and q is null
     uint32_t nq = 0, k1 = 0, ef1 = 0, kstride = 0;
     const uint32_t* k = nullptr;
     const uint32_t* ef = nullptr;
@@ -29,7 +33,8 @@ struct HostWalk {
     uint32_t* out_counts = nullptr;
     const nmn_xmetric* xm = nullptr;  // a metric call (docs/hnsw.md §12): k_of(i) is query i's top_k, metric_of(i) its metric
     uint32_t xm_stride = 0;
-    bool alone = false;               // nobody rides with this call, and it rides with nobody (a metric call with c above kShareCandMax)
+    bool alone = false;               // nobody rides with this call, and it rides with nobody (a metric call with c above kShareCandMax;
+                                      // a sparse call whose entries would change the candidate limit of the others, §14)
     uint32_t rescored = 0;            // filled like evals: the largest candidate count re-ranked
     // filled by the leader of the batch this call rode in
     uint64_t evals = 0;

@@ -322,6 +322,33 @@ class GpuHnsw:
                                                      C.c_void_p(counts.ctypes.data), C.byref(st)))
         return (ids, sc, counts, st) if with_stats else (ids, sc, counts)
 
+    def search_sparse_multi(self, indptr, positions, values, k, ef=None, kstride=None, with_stats=False):
+        """`search_sparse` with a k and an ef per query in ONE launch (nmn_hnsw_search_sparse_multi).  The CSR is `search_sparse`'s;
+        `k`: one integer per query; `ef`: None (ef_search for all) or one per query, 0 = ef_search; `kstride`: row length of the
+        outputs (None: max(k)).
+        -> (ids u64 [nq,kstride], scores f32 [nq,kstride], counts u32 [nq]); row i is what search_sparse(q_i, k[i], ef[i]) answers."""
+        ip = np.ascontiguousarray(indptr, dtype=np.uint64).reshape(-1)
+        pos = np.ascontiguousarray(positions, dtype=np.uint32).reshape(-1)
+        val = np.ascontiguousarray(values, dtype=np.float32).reshape(-1)
+        if ip.size == 0 or pos.size != val.size or (ip.size and int(ip.max()) > pos.size):
+            raise _capi.NeumannGpuError(_capi.ERR_INVALID_ARGUMENT, "indptr [nq + 1] into positions / values of one length")
+        nq = ip.size - 1
+        kk = np.ascontiguousarray(k, dtype=np.uint32).reshape(-1)
+        ee = None if ef is None else np.ascontiguousarray(ef, dtype=np.uint32).reshape(-1)
+        if kk.size != nq or (ee is not None and ee.size != nq):
+            raise _capi.NeumannGpuError(_capi.ERR_INVALID_ARGUMENT, "one k (and one ef) per query")
+        ks = int(kk.max()) if kstride is None and nq else int(kstride or 1)
+        ids = np.empty((nq, max(ks, 1)), dtype=np.uint64)
+        sc = np.empty((nq, max(ks, 1)), dtype=np.float32)
+        counts = np.empty(nq, dtype=np.uint32)
+        st = _capi.SearchStats()
+        _capi.check(self._lib.nmn_hnsw_search_sparse_multi(self._h, C.c_void_p(ip.ctypes.data), C.c_void_p(pos.ctypes.data),
+                                                           C.c_void_p(val.ctypes.data), nq, C.c_void_p(kk.ctypes.data),
+                                                           C.c_void_p(ee.ctypes.data) if ee is not None else None, ks,
+                                                           C.c_void_p(ids.ctypes.data), C.c_void_p(sc.ctypes.data),
+                                                           C.c_void_p(counts.ctypes.data), C.byref(st)))
+        return (ids, sc, counts, st) if with_stats else (ids, sc, counts)
+
     def coalesce_stats(self):
         """(batches that carried two or more concurrent calls, calls in them) — nmn_hnsw_coalesce_stats"""
         b, c = C.c_uint64(), C.c_uint64()

@@ -58,7 +58,16 @@ nmn_hnsw_search of the SAME (densified) queries, the two alternating call by cal
 200 (docs/hnsw.md §13): medians of --calls (a fifth of it at 1024 queries), spread over --repeats.  Both are host-buffer calls —
 nmn_hnsw_search_sparse has no device-buffer entry — so both figures are wall times of the whole call, copies included.  It also
 prints the stored entries per query, the evaluations per query and the queries the spill launch answered, and checks that the
-sparse call's device and host-walk answers are the same bits and, under Euclidean, the bits of the dense walk."""
+sparse call's device and host-walk answers are the same bits and, under Euclidean, the bits of the dense walk.
+
+  python tools/hnsw_bench.py --rows 200000 --dim 128 --sparse-callers 64,128 --index-file PATH [--storage quantized]
+--sparse-callers times CONCURRENT sparse callers (docs/hnsw.md §14): for every T of the list, T threads behind a barrier, each making
+--caller-calls calls of nmn_hnsw_search_sparse with ONE query (--sparse-fraction of its entries zeroed, 0.8 by default: about a fifth
+of the dimension stored), k taken in turn from 1, 10, 50, 100.  The run alternates two legs, --repeats times: the build as it is, and
+the same build with NMN_HNSW_NO_COALESCE=1, where sparse callers take turns on the handle — what they did before they joined the
+coalescer.  Every leg is a fresh child process (this script again, with --sparse-leg) under its own time limit (--leg-timeout
+seconds); with --index-file the first leg builds and saves the index and every other leg loads it.  One JSON line per leg (queries_per_s,
+call_ms_median, merged batches and calls from nmn_hnsw_coalesce_stats), then one line with the medians and spreads of both legs."""
 import argparse
 import json
 import os
@@ -182,9 +191,10 @@ def time_storage(gq, gd, Q, qd, k, s, args, metric):
     return out
 
 
-def time_callers(g, Q, counts, args, xmetric=None):
+def time_callers(g, Q, counts, args, xmetric=None, sparse=None):
     """N threads, each calling g.search(one query, its k) --caller-calls times — with `xmetric`, g.search_metric(one query, its top_k,
-    xmetric) —: throughput, a caller's median, the coalescer's counts"""
+    xmetric); with `sparse` (one CSR per query of Q), g.search_sparse(that query, its k) —: throughput, a caller's median, the
+    coalescer's counts"""
     import threading
     ks = (1, 10, 50, 100)
     has_stats = hasattr(g._lib, "nmn_hnsw_coalesce_stats")  # (an older build has no coalescer)
@@ -203,7 +213,9 @@ def time_callers(g, Q, counts, args, xmetric=None):
                     for j in range(per):
                         q = Q[(t * per + j) % len(Q)]
                         t0 = time.perf_counter()
-                        if xmetric is not None:
+                        if sparse is not None:
+                            g.search_sparse(*sparse[(t * per + j) % len(Q)], ks[(t + j) % len(ks)])
+                        elif xmetric is not None:
                             g.search_metric(q, ks[(t + j) % len(ks)], xmetric)
                         else:
                             g.search(q, ks[(t + j) % len(ks)])
@@ -238,6 +250,39 @@ def time_callers(g, Q, counts, args, xmetric=None):
             r["merged_batches"] = r["merged_calls"] = None
         out[f"callers{N}"] = r
     return out
+
+
+def sparse_caller_legs(args):
+    """--sparse-callers: the two legs alternating, each a fresh child process with its own time limit; this process opens no GPU"""
+    import subprocess
+    argv = [sys.executable, os.path.abspath(__file__), "--sparse-leg"] + [a for a in sys.argv[1:] if a != "--sparse-leg"]
+    legs = {"coalesce": [], "no_coalesce": []}
+    for _ in range(args.repeats):
+        for leg in legs:
+            env = dict(os.environ)
+            env.pop("NMN_HNSW_NO_COALESCE", None)
+            if leg == "no_coalesce":
+                env["NMN_HNSW_NO_COALESCE"] = "1"
+            try:
+                r = subprocess.run(argv, env=env, capture_output=True, text=True, timeout=args.leg_timeout)
+            except subprocess.TimeoutExpired:
+                raise SystemExit(f"leg {leg} did not end within {args.leg_timeout} s")
+            if r.returncode != 0:
+                raise SystemExit(f"leg {leg} ended with {r.returncode}: {r.stderr[-2000:]}")
+            line = json.loads(r.stdout.strip().splitlines()[-1])
+            line["leg"] = leg
+            print(json.dumps(line), flush=True)
+            legs[leg].append(line)
+    out = {"summary": True, "rows": args.rows, "dim": args.dim, "storage": args.storage, "repeats": args.repeats}
+    for leg, lines in legs.items():
+        for key in [k for k in lines[0] if k.startswith("callers")]:
+            r = {}
+            for f in ("queries_per_s", "call_ms_median", "merged_batches", "merged_calls", "calls_per_merged_batch"):
+                v = [x[key][f] for x in lines]
+                r[f] = round(float(np.median(v)), 4)
+                r[f + "_spread"] = round(float((max(v) - min(v)) / max(np.median(v), 1e-12)), 3)
+            out[f"{leg}_{key}"] = r
+    print(json.dumps(out), flush=True)
 
 
 def time_sparse(g, Q, k, args):
@@ -346,9 +391,18 @@ def main():
     ap.add_argument("--caller-calls", type=int, default=200, help="calls every caller thread makes per repetition")
     ap.add_argument("--sparse-queries", type=float, default=None,
                     help="zero this share of every query's entries and time nmn_hnsw_search_sparse beside nmn_hnsw_search (docs/hnsw.md §13)")
+    ap.add_argument("--sparse-callers", default=None,
+                    help="e.g. 64,128: that many concurrent nmn_hnsw_search_sparse callers (one query each), with and without "
+                         "NMN_HNSW_NO_COALESCE=1, each leg a fresh child process (docs/hnsw.md §14)")
+    ap.add_argument("--sparse-fraction", type=float, default=0.8, help="--sparse-callers: the share of every query's entries that is zeroed")
+    ap.add_argument("--leg-timeout", type=float, default=900.0, help="--sparse-callers: seconds a leg's child process may take")
+    ap.add_argument("--sparse-leg", action="store_true", help="(one leg of --sparse-callers, in this process)")
     ap.add_argument("--index-file", default=None,
                     help="load the index from this file when it exists; otherwise build, save it there and report build / save / load seconds")
     args = ap.parse_args()
+    if args.sparse_callers and not args.sparse_leg:
+        sparse_caller_legs(args)
+        return
     if args.callers:  # an older build through NEUMANN_GPU_LIB: entries it lacks stay unbound instead of failing the load
         import ctypes
         from neumann_amd import _capi
@@ -377,6 +431,21 @@ def main():
             if xmetric is not None:
                 out["xmetric"] = xmetric.name
             out.update(time_callers(g, Q, [int(x) for x in args.callers.split(",")], args, xmetric))
+        print(json.dumps(out), flush=True)
+        return
+    if args.sparse_callers:  # one leg: repeats are the parent's, so one timed pass behind the warming one
+        out.update({"storage": args.storage, "no_coalesce": bool(os.environ.get("NMN_HNSW_NO_COALESCE")), "caller_calls": args.caller_calls,
+                    "sparse_fraction": args.sparse_fraction})
+        del out["k"]
+        Qs = Q.copy()
+        Qs[np.random.default_rng(0x5BA).random(Qs.shape) < args.sparse_fraction] = 0.0
+        args.repeats = 1
+        with build_or_load(args.index_file, n, d, cfg, args.storage, out) as g:
+            csr = g.sparse_from_dense(Qs)
+            per_query = [(np.array([0, int(csr[0][i + 1] - csr[0][i])], np.uint64), csr[1][int(csr[0][i]):int(csr[0][i + 1])],
+                          csr[2][int(csr[0][i]):int(csr[0][i + 1])]) for i in range(len(Qs))]
+            out["entries_per_query"] = round(float(csr[1].size) / len(Qs), 1)
+            out.update(time_callers(g, Qs, [int(x) for x in args.sparse_callers.split(",")], args, sparse=per_query))
         print(json.dumps(out), flush=True)
         return
     if args.sparse_queries is not None:

@@ -5,8 +5,11 @@
 //   c++ -std=c++17 -O1 -g -fsanitize=address -I include -I neumann_amd/csrc tools/micro/hnsw_queue_mt.cpp -o tools/micro/hnsw_queue_mt -lpthread && tools/micro/hnsw_queue_mt
 //
 // The stand-in checks what the queue promises: one batch at a time; at most kBatchQueries queries in a batch unless it is one
-// call; a call marked `alone` (a metric call with more than kShareCandMax candidates) is a batch of one; every call is served exactly once, with its own answer (out_counts[i] = a
-// function of the call's own k and query), also when a batch fails — then every call of that batch gets the status and the text.
+// call; a call marked `alone` (a metric call with more than kShareCandMax candidates, a sparse call that would change the others'
+// candidate limit) is a batch of one; every call is served exactly once, with its own answer (out_counts[i] = a function of the
+// call's own k and query), also when a batch fails — then every call of that batch gets the status and the text.  About one call in
+// five is a sparse one: HostWalk::sp set and q null, as nmn_hnsw_search_sparse[_multi] submit them; the stand-in batch reads such a
+// call's queries through sp and requires q to be null, and sparse and dense calls share batches.
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -15,10 +18,15 @@
 
 #include "nmn_hnsw_queue.h"
 
+// the queue carries a pointer to the call's canonicalised sparse queries and never looks inside: a stand-in with one value per query
+struct nmn::SparseQueries {
+    std::vector<float> v;
+};
+
 using namespace nmn;
 
 static std::atomic<int> running{0};
-static std::atomic<uint64_t> batches_run{0}, calls_served{0}, failed_batches{0}, alone_served{0};
+static std::atomic<uint64_t> batches_run{0}, calls_served{0}, failed_batches{0}, alone_served{0}, sparse_served{0}, mixed_batches{0};
 static thread_local std::string tl_error;
 
 #define REQUIRE(c)                                                   \
@@ -39,6 +47,16 @@ static nmn_status fake_batch(const std::vector<HostWalk*>& batch) {
             REQUIRE(batch.size() == 1);
             alone_served++;
         }
+    size_t sparse_here = 0;
+    for (const HostWalk* r : batch) {
+        REQUIRE(!r->sp != !r->q);  // a call brings dense queries or sparse ones, never both
+        if (r->sp) {
+            REQUIRE(r->sp->v.size() == r->nq);
+            sparse_here++;
+        }
+    }
+    sparse_served += sparse_here;
+    if (sparse_here && sparse_here < batch.size()) mixed_batches++;
     const uint64_t b = batches_run.fetch_add(1);
     nmn_status st = NMN_OK;
     if (b % 17 == 5) {  // a failing batch: nothing written, every call gets the status
@@ -47,7 +65,7 @@ static nmn_status fake_batch(const std::vector<HostWalk*>& batch) {
         st = NMN_ERR_INVALID_ARGUMENT;
     } else {
         for (HostWalk* r : batch) {
-            for (uint32_t i = 0; i < r->nq; i++) r->out_counts[i] = r->k_of(i) * 1000u + (uint32_t)r->q[i];
+            for (uint32_t i = 0; i < r->nq; i++) r->out_counts[i] = r->k_of(i) * 1000u + (uint32_t)(r->sp ? r->sp->v[i] : r->q[i]);
             r->evals = r->nq;
         }
     }
@@ -73,7 +91,13 @@ int main() {
                     k[i] = 1 + (uint32_t)((t + c + i) % 200);
                 }
                 HostWalk me;
-                me.q = query.data();
+                SparseQueries sq;
+                if ((t * 3 + c) % 5 == 1) {  // a sparse call: its queries behind sp, q null
+                    sq.v = query;
+                    me.sp = &sq;
+                } else {
+                    me.q = query.data();
+                }
                 me.nq = nq;
                 me.k = k.data();
                 me.kstride = 200;
@@ -101,8 +125,13 @@ int main() {
     for (int t = 0; t < threads; t++)
         for (int c = 0; c < calls; c++) alone_made += (t * 7 + c) % 11 == 3 ? 1 : 0;
     REQUIRE(alone_made > 0 && alone_served.load() == alone_made);
-    printf("hnsw_queue_mt ok: %llu calls in %llu batches (%llu merged batches carrying %llu calls, %llu calls alone), %llu failed batches, %llu failed calls\n",
+    uint64_t sparse_made = 0;
+    for (int t = 0; t < threads; t++)
+        for (int c = 0; c < calls; c++) sparse_made += (t * 3 + c) % 5 == 1 ? 1 : 0;
+    REQUIRE(sparse_made > 0 && sparse_served.load() == sparse_made && mixed_batches.load() > 0);
+    printf("hnsw_queue_mt ok: %llu calls in %llu batches (%llu merged batches carrying %llu calls, %llu calls alone, %llu sparse calls, %llu batches mixing sparse and dense calls), %llu failed batches, %llu failed calls\n",
            (unsigned long long)calls_served.load(), (unsigned long long)batches_run.load(), (unsigned long long)q.batches,
-           (unsigned long long)q.calls, (unsigned long long)alone_served.load(), (unsigned long long)failed_batches.load(), (unsigned long long)failures_seen.load());
+           (unsigned long long)q.calls, (unsigned long long)alone_served.load(), (unsigned long long)sparse_served.load(),
+           (unsigned long long)mixed_batches.load(), (unsigned long long)failed_batches.load(), (unsigned long long)failures_seen.load());
     return 0;
 }
