@@ -591,8 +591,9 @@ uint64_t nmn_ivf_hbm_bytes(nmn_ivf* ivf);
  * nmn_hnsw_load (index persistence, below) keep a built graph across restarts. */
 typedef struct nmn_hnsw nmn_hnsw;
 
-/* HNSWStorageStrategy (vector_engine/src/lib.rs:833-846).  Dense and Quantized are served, Auto (sparse storage) is refused
- * with NMN_ERR_CONFIGURATION.  The strategy's home is the build options, as in the reference: it is the `storage` argument of
+/* HNSWStorageStrategy (vector_engine/src/lib.rs:833-846).  Dense and Quantized are served, Auto as a STRATEGY is refused
+ * with NMN_ERR_CONFIGURATION (what HNSWIndex itself offers for sparse storage — insert_sparse, insert_auto — is served on a dense
+ * handle: nmn_hnsw_insert_sparse / nmn_hnsw_insert_auto below).  The strategy's home is the build options, as in the reference: it is the `storage` argument of
  * nmn_hnsw_create_with_storage (and nmn_hnsw_build_options.storage of neumann_engine.h).  nmn_hnsw_config.storage is the older
  * field: nmn_hnsw_create reads it and serves NMN_HNSW_STORAGE_DENSE only. */
 #define NMN_HNSW_STORAGE_DENSE 0
@@ -607,7 +608,7 @@ typedef struct nmn_hnsw_config {
     uint32_t ef_search;        /* 50 */
     double ml;                 /* level multiplier, 1 / ln(m) */
     uint64_t max_nodes;        /* 0 = unlimited; default 10 000 000 */
-    float sparsity_threshold;  /* carried, not acted on (dense storage only) */
+    float sparsity_threshold;  /* read by nmn_hnsw_insert_auto; every other entry carries it without acting on it */
     int32_t distance_metric;   /* HNSWDistanceMetric (hnsw.rs:135-159) = NMN_METRIC_COSINE / _EUCLIDEAN / _DOT_PRODUCT */
     int32_t storage;           /* NMN_HNSW_STORAGE_* */
     uint32_t reserved;         /* 0 */
@@ -629,6 +630,25 @@ nmn_status nmn_hnsw_destroy(nmn_hnsw* h);
  * NMN_ERR_CAPACITY, nmn_last_error() = "HNSW index at capacity: {current} nodes (limit: {limit})" (hnsw.rs:102-107).
  * Waits for the device searches in flight, then uploads the new adjacency. */
 nmn_status nmn_hnsw_insert(nmn_hnsw* h, const float* rows_host, uint64_t n, uint64_t* ids_out);
+/* HNSWIndex::insert_sparse (hnsw.rs:1660-1662) for each of the n CSR rows (HOST) in order: row i is the (position, value) pairs
+ * [indptr[i], indptr[i + 1]), made a SparseVector of the handle's dimension as try_from_parts makes it — nmn_hnsw_search_sparse's
+ * rules, errors and texts, checked for the whole batch before anything is inserted; duplicated positions survive in input order.
+ * The node is EmbeddingStorage::Sparse: the query side scores it with s.dot_dense(q) / s.dot(Q) and s.magnitude() — single f64
+ * chains over its stored entries — and the pruning side with the Sparse arms of distance_embeddings (hnsw.rs:2437-2459, 2554-2565,
+ * 2637-2643), so the graph and the score bits differ from those of nmn_hnsw_insert of the densified row (docs/hnsw.md §15).  Its
+ * row in nmn_hnsw_vectors(h) is to_dense() (the last entry of a duplicated position wins), node id == row as ever.  max_nodes, its
+ * text and the all-or-nothing batch are nmn_hnsw_insert's.  Dense handles only: a quantized handle is NMN_ERR_CONFIGURATION.
+ * Every search entry serves a handle that holds both kinds; a sparse QUERY is walked on the host when the metric is Euclidean or
+ * when the query or any sparse node holds a duplicated position.  nmn_hnsw_save refuses a handle with sparse nodes. */
+nmn_status nmn_hnsw_insert_sparse(nmn_hnsw* h, const uint64_t* indptr, const uint32_t* positions, const float* values, uint64_t n,
+                                  uint64_t* ids_out);
+/* HNSWIndex::insert_auto (hnsw.rs:1671-1680) per row (HOST, n x dim): nnz = the count of x != 0.0 (NaN counts), sparsity =
+ * 1.0f - (float)nnz / (float)dim; the row is Sparse(SparseVector::from_dense(row)) iff sparsity >= cfg.sparsity_threshold (a NaN
+ * threshold: never), Dense(row) otherwise.  Refusals as above. */
+nmn_status nmn_hnsw_insert_auto(nmn_hnsw* h, const float* rows_host, uint64_t n, uint64_t* ids_out);
+/* The stored entries of a node, in SparseVector order: *nnz = their count, UINT32_MAX for a Dense (or Quantized) node.
+ * positions_out / values_out ([cap], cap >= the count: NMN_ERR_BUFFER_TOO_SMALL otherwise) may both be NULL to ask for the count. */
+nmn_status nmn_hnsw_sparse_row(nmn_hnsw* h, uint64_t node, uint32_t* positions_out, float* values_out, uint32_t cap, uint32_t* nnz);
 uint64_t nmn_hnsw_len(const nmn_hnsw* h);          /* HNSWIndex::len, hnsw.rs:1620-1622 */
 uint32_t nmn_hnsw_dim(const nmn_hnsw* h);
 uint64_t nmn_hnsw_entry_point(const nmn_hnsw* h);  /* UINT64_MAX while empty (hnsw.rs:1581) */
@@ -702,7 +722,8 @@ nmn_status nmn_hnsw_set_heap_capacity(nmn_hnsw* h, uint32_t results, uint32_t ca
 /* The flat index holding the rows (exhaustive search over the same rows).  NULL on a quantized handle: it keeps no f32 rows on
  * the device. */
 nmn_index* nmn_hnsw_vectors(nmn_hnsw* h);
-/* Device memory the index holds: rows, magnitudes, mirrors, adjacency (dense); codes, records, adjacency (quantized). */
+/* Device memory the index holds: rows, magnitudes, mirrors, adjacency (dense; with sparse nodes also a 16-byte record per node
+ * and 8 bytes per stored entry); codes, records, adjacency (quantized). */
 uint64_t nmn_hnsw_hbm_bytes(nmn_hnsw* h);
 
 /* nmn_hnsw_create with the storage strategy of HNSWBuildOptions: `storage` is NMN_HNSW_STORAGE_*, cfg->storage is not read.
@@ -719,9 +740,12 @@ nmn_status nmn_hnsw_create_with_storage(const nmn_hnsw_config* cfg, int32_t stor
 int32_t nmn_hnsw_storage(const nmn_hnsw* h); /* NMN_HNSW_STORAGE_DENSE or _QUANTIZED */
 /* The ScalarQuantizedVector of a node: codes_out[dim], scale, min_val (each nullable).  Dense handle: NMN_ERR_CONFIGURATION. */
 nmn_status nmn_hnsw_quantized_row(nmn_hnsw* h, uint64_t node, uint8_t* codes_out, float* scale, float* min_val);
-/* HNSWIndex::get_vector: out[dim] = the row as inserted (dense) or dequantize() = code.mul_add(scale, min_val) (quantized). */
+/* HNSWIndex::get_vector: out[dim] = the row as inserted (dense), to_dense() of a sparse node, or dequantize() =
+ * code.mul_add(scale, min_val) (quantized). */
 nmn_status nmn_hnsw_get_vector(nmn_hnsw* h, uint64_t node, float* out);
-/* HNSWMemoryStats (hnsw.rs:2733-2768); embedding_bytes = 4 dim per dense node, 16 + dim per quantized node. */
+/* HNSWMemoryStats (hnsw.rs:2733-2768); embedding_bytes = 4 dim per dense node, 16 + dim per quantized node, 56 + 8 nnz per
+ * sparse node (size_of::<SparseVector>() on a 64-bit target plus both Vec capacities taken as their lengths — what a cloned
+ * vector has; std does not pin the capacity of a pushed one, docs/hnsw.md §15). */
 typedef struct nmn_hnsw_memstats {
     uint64_t total_nodes;
     uint64_t dense_count;

@@ -280,6 +280,49 @@ impl GpuHnswIndex {
         check(unsafe { ffi::nmn_hnsw_insert(self.raw, rows.as_ptr(), n, std::ptr::null_mut()) }, self.dim, self.dim)
     }
 
+    /// HNSWIndex::insert_sparse for every vector in order (nmn_hnsw_insert_sparse): vector i is the (position, value) pairs
+    /// `rows[i]`, in any order, made a SparseVector as try_from_parts makes it.  The node is stored Sparse and scored by
+    /// SparseVector's own arithmetic (docs/hnsw.md §15).  Dense handles only.
+    pub fn insert_sparse(&self, rows: &[Vec<(u32, f32)>]) -> Result<()> {
+        let mut indptr = Vec::with_capacity(rows.len() + 1);
+        let mut positions = Vec::new();
+        let mut values = Vec::new();
+        indptr.push(0u64);
+        for r in rows {
+            for &(p, v) in r {
+                positions.push(p);
+                values.push(v);
+            }
+            indptr.push(positions.len() as u64);
+        }
+        let st = unsafe {
+            ffi::nmn_hnsw_insert_sparse(self.raw, indptr.as_ptr(), positions.as_ptr(), values.as_ptr(), rows.len() as u64, std::ptr::null_mut())
+        };
+        check(st, self.dim, self.dim)
+    }
+
+    /// HNSWIndex::insert_auto for every row in order (nmn_hnsw_insert_auto): Sparse(from_dense(row)) where the share of zeros
+    /// reaches the config's sparsity_threshold, Dense otherwise.
+    pub fn insert_auto(&self, rows: &[f32]) -> Result<()> {
+        let n = (rows.len() / self.dim.max(1)) as u64;
+        check(unsafe { ffi::nmn_hnsw_insert_auto(self.raw, rows.as_ptr(), n, std::ptr::null_mut()) }, self.dim, self.dim)
+    }
+
+    /// The stored (position, value) entries of a Sparse node, None for a Dense one (nmn_hnsw_sparse_row).
+    pub fn sparse_row(&self, node: usize) -> Result<Option<Vec<(u32, f32)>>> {
+        let mut nnz = 0u32;
+        let st = unsafe { ffi::nmn_hnsw_sparse_row(self.raw, node as u64, std::ptr::null_mut(), std::ptr::null_mut(), 0, &mut nnz) };
+        check(st, self.dim, self.dim)?;
+        if nnz == u32::MAX {
+            return Ok(None);
+        }
+        let mut positions = vec![0u32; nnz as usize];
+        let mut values = vec![0f32; nnz as usize];
+        let st = unsafe { ffi::nmn_hnsw_sparse_row(self.raw, node as u64, positions.as_mut_ptr(), values.as_mut_ptr(), nnz, &mut nnz) };
+        check(st, self.dim, self.dim)?;
+        Ok(Some(positions.into_iter().zip(values).collect()))
+    }
+
     /// HNSWIndex::search: (node id, to_similarity(distance)), best first.
     pub fn search(&self, q: &[f32], k: usize) -> Result<Vec<(usize, f32)>> {
         if q.len() != self.dim {

@@ -214,6 +214,9 @@ SIGNATURES = {
     "nmn_hnsw_create": (C.c_int32, [C.POINTER(HnswConfig), C.c_uint32, C.c_uint64, C.c_int32, C.POINTER(vp)]),
     "nmn_hnsw_destroy": (C.c_int32, [vp]),
     "nmn_hnsw_insert": (C.c_int32, [vp, vp, C.c_uint64, vp]),
+    "nmn_hnsw_insert_sparse": (C.c_int32, [vp, vp, vp, vp, C.c_uint64, vp]),
+    "nmn_hnsw_insert_auto": (C.c_int32, [vp, vp, C.c_uint64, vp]),
+    "nmn_hnsw_sparse_row": (C.c_int32, [vp, C.c_uint64, vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]),
     "nmn_hnsw_len": (C.c_uint64, [vp]),
     "nmn_hnsw_dim": (C.c_uint32, [vp]),
     "nmn_hnsw_entry_point": (C.c_uint64, [vp]),

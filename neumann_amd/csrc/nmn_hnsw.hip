@@ -28,6 +28,10 @@
 //       rounded once, one cast; std's float Sum restated as a left-to-right fold from -0.0), and Cosine takes magnitude() (548-559)
 //       through f64; Euclidean, and every metric's dot on a quantized handle, go through to_dense() (400-406).  docs/hnsw.md §13.
 //   nmn_hnsw_search_sparse_multi: the same with a k and an ef per query; both ride the request coalescer, a query kind per slot (§14).
+//   nmn_hnsw_insert_sparse / nmn_hnsw_insert_auto (hnsw.rs:1660-1680): EmbeddingStorage::Sparse nodes beside Dense ones on a dense
+//       handle.  A sparse node is scored by SparseVector's own arithmetic — dot_dense / dot / magnitude / euclidean_distance /
+//       cosine_similarity / cosine_distance_dense, f64 chains over the stored entries — on the query side and on the pruning side;
+//       the host keeps a kind per node, the kernel a record per node and takes the MIX instantiations.  docs/hnsw.md §15.
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -309,6 +313,12 @@ struct SearchArgs {
     // entries, not by the dimension).
     const uint32_t* qkind;
     const uint32_t* qccap;
+    // hnsw_search_kernel<.., MIX = true> (a handle with EmbeddingStorage::Sparse nodes, docs/hnsw.md §15): a record per node —
+    // {entry offset low, high, nnz (kNone: a Dense node), bits of SparseVector::magnitude()} — and the (position, value bits) pairs
+    // of all sparse nodes.  qkind / qccap are nullable there: null means kind_u for every query and the launch's own candidate limit.
+    const uint4* nrec;
+    const uint2* nent;
+    uint32_t kind_u;
 };
 
 // Entries of the candidate heap the first launch gives a query walking with `ef` (fixed: nmn_hnsw_set_heap_capacity, 0 = default).
@@ -449,6 +459,90 @@ __device__ __forceinline__ float sparse_distance(const float* __restrict__ row, 
     return 1.0f - dot / (rowmag * qmag);
 }
 
+// distance_dense on a Sparse NODE under Cosine / DotProduct (hnsw.rs:1035-1045, 1136-1138): s.dot_dense(q), the same ONE f64
+// chain from -0.0, now over the NODE's stored entries — they come from HBM with 8-byte loads, q[pos] is gathered from the query in
+// LDS.  The lane mapping is sparse_distance's: lane h of the pair takes the entries 2t + h, four in flight, both lanes run the
+// chain in entry order.  nmag is s.magnitude() (through f64, from the node's record), qmag the query's.
+__device__ __forceinline__ float mix_dense_query(const uint2* __restrict__ ne, uint32_t nnz, float nmag, const float* q, float qmag,
+                                                 int metric, uint32_t h) {
+    double acc = -0.0;
+    constexpr int PF = 4;
+    for (uint32_t t0 = 0; 2u * t0 < nnz; t0 += PF) {
+        uint2 e[PF];
+        float x[PF];
+        double pr[PF];
+#pragma unroll
+        for (int i = 0; i < PF; i++) {
+            const uint32_t idx = 2u * (t0 + (uint32_t)i) + h;
+            e[i] = idx < nnz ? ne[idx] : make_uint2(0u, 0u);
+        }
+#pragma unroll
+        for (int i = 0; i < PF; i++) x[i] = 2u * (t0 + (uint32_t)i) + h < nnz ? q[e[i].x] : 0.0f;
+#pragma unroll
+        for (int i = 0; i < PF; i++)
+            pr[i] = 2u * (t0 + (uint32_t)i) + h < nnz ? (double)__uint_as_float(e[i].y) * (double)x[i] : -0.0;
+#pragma unroll
+        for (int i = 0; i < PF; i++) {
+            const double other = __shfl_xor(pr[i], 1);
+            acc = acc + (h ? other : pr[i]);
+            acc = acc + (h ? pr[i] : other);
+        }
+    }
+    const float dot = (float)acc;
+    if (metric == NMN_METRIC_DOT_PRODUCT) return -dot;
+    if (nmag == 0.0f || qmag == 0.0f) return 1.0f;
+    return 1.0f - dot / (nmag * qmag);
+}
+
+// distance_sparse on a Sparse NODE under Cosine / DotProduct (hnsw.rs:1069-1079, 1143-1145): s.dot(Q) is dot_f64
+// (sparse_vector.rs:419-443), a two-pointer merge whose f64 accumulator starts at +0.0.  When neither side holds a duplicated
+// position (the host routes every other case to its own walk) the merge is a lookup: for every node entry in order, the query entry
+// of the same position, found by binary search over the sorted entries in the query region of LDS.  A miss (and a slot past the
+// last entry) contributes +0.0 to a chain that starts at +0.0 and never becomes -0.0 (a product of two stored values is never a
+// zero in f64, and x + (-x) rounds to +0.0), so it changes nothing.  The same pair of lanes, the same order.
+__device__ __forceinline__ float mix_sparse_query(const uint2* __restrict__ ne, uint32_t nnz, float nmag, const uint2* qe, uint32_t qn,
+                                                  float qmag, int metric, uint32_t h) {
+    double acc = 0.0;
+    constexpr int PF = 4;
+    for (uint32_t t0 = 0; 2u * t0 < nnz; t0 += PF) {
+        uint2 e[PF];
+        double pr[PF];
+#pragma unroll
+        for (int i = 0; i < PF; i++) {
+            const uint32_t idx = 2u * (t0 + (uint32_t)i) + h;
+            e[i] = idx < nnz ? ne[idx] : make_uint2(0u, 0u);
+        }
+#pragma unroll
+        for (int i = 0; i < PF; i++) {
+            pr[i] = 0.0;
+            if (2u * (t0 + (uint32_t)i) + h < nnz) {
+                uint32_t lo = 0, hi = qn;
+                while (lo < hi) {
+                    const uint32_t mid = (lo + hi) >> 1;
+                    if (qe[mid].x < e[i].x)
+                        lo = mid + 1;
+                    else
+                        hi = mid;
+                }
+                if (lo < qn) {
+                    const uint2 qv = qe[lo];
+                    if (qv.x == e[i].x) pr[i] = (double)__uint_as_float(e[i].y) * (double)__uint_as_float(qv.y);
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < PF; i++) {
+            const double other = __shfl_xor(pr[i], 1);
+            acc = acc + (h ? other : pr[i]);
+            acc = acc + (h ? pr[i] : other);
+        }
+    }
+    const float dot = (float)acc;
+    if (metric == NMN_METRIC_DOT_PRODUCT) return -dot;
+    if (nmag == 0.0f || qmag == 0.0f) return 1.0f;
+    return 1.0f - dot / (nmag * qmag);
+}
+
 // what a wave computes once per query: simd::magnitude (Cosine), and for quantized rows sum_y and sum_of_squares (Euclidean)
 struct QuerySide {
     float mag, sum, sq;
@@ -532,10 +626,16 @@ __device__ __forceinline__ float q8_distance(const uint8_t* __restrict__ row, co
 // simd::magnitude the wave computes.  3 (PERQ only): the kind is the query's own, a.qkind[q] — 0 or 1 on dense rows, 0 or 2 on
 // quantized rows — and so is its candidate limit, a.qccap[q]; a wave serves one query, so every branch on the kind is
 // wave-uniform.  QK is a template parameter so that the QK == 0 instantiations stay the code they were.
-template <bool SPILL, bool Q8, bool PERQ, int QK = 0>
+// MIX (dense rows, PERQ, QK == 3; Cosine / DotProduct): the handle holds EmbeddingStorage::Sparse nodes.  row_distance reads the
+// node's record and scores a sparse node from its stored entries (mix_dense_query / mix_sparse_query); a Dense node keeps the
+// arithmetic above.  The two lanes of a pair score one node and agree on its kind; the pairs of one pass may not, so both sides run
+// under exec masks — the one lane-divergent branch of the scoring path.  These instantiations serve uniform launches as well
+// (a.qk / a.qef / a.qkind / a.qccap null).  MIX is a template parameter so that every other instantiation stays the code it was.
+template <bool SPILL, bool Q8, bool PERQ, int QK = 0, bool MIX = false>
 __global__ __launch_bounds__(64) void hnsw_search_kernel(SearchArgs a) {
     static_assert(QK == 0 || (QK == 1 && !Q8 && !PERQ) || (QK == 2 && Q8 && !PERQ) || (QK == 3 && PERQ),
                   "query kinds: 1 on dense rows, 2 on quantized rows, 3 = a kind per query of a per-query launch");
+    static_assert(!MIX || (!Q8 && PERQ && QK == 3), "sparse nodes: dense storage, the per-query form");
     extern __shared__ float4 smem4[];
     const GraphDev& g = a.g;
     const uint32_t lane = threadIdx.x, p = lane >> 1, h = lane & 1u;
@@ -562,7 +662,7 @@ __global__ __launch_bounds__(64) void hnsw_search_kernel(SearchArgs a) {
         bool entries = QK == 1;             // the query region holds stored entries, rows are scored by sparse_distance
         bool mag_given = QK == 1 || QK == 2;  // the Cosine magnitude is a.qmag[q]
         if constexpr (QK == 3) {
-            const uint32_t kind = a.qkind[q];
+            const uint32_t kind = MIX && !a.qkind ? a.kind_u : a.qkind[q];
             entries = !Q8 && kind == 1u;
             mag_given = kind != 0u;
         }
@@ -584,7 +684,8 @@ __global__ __launch_bounds__(64) void hnsw_search_kernel(SearchArgs a) {
         const uint32_t ef_q = PERQ && a.qef ? a.qef[q] : a.ef;
         const uint32_t kstride = PERQ ? a.kstride : a.k;
         const uint32_t ccap_q =
-            PERQ && !SPILL ? min(a.ccap, QK == 3 ? a.qccap[q] : cand_cap(ef_q, a.ccap_fixed, g.dim, g.n)) : a.ccap;
+            PERQ && !SPILL ? min(a.ccap, QK == 3 ? (MIX && !a.qccap ? a.ccap : a.qccap[q]) : cand_cap(ef_q, a.ccap_fixed, g.dim, g.n))
+                           : a.ccap;
         uint64_t* o_ids = a.out_ids + (size_t)q * kstride;
         float* o_sc = a.out_scores + (size_t)q * kstride;
         if (g.n == 0 || g.entry == kNone) {  // hnsw.rs:2070-2073
@@ -611,6 +712,15 @@ __global__ __launch_bounds__(64) void hnsw_search_kernel(SearchArgs a) {
             if (g.metric == NMN_METRIC_EUCLIDEAN) qside.sq = -pair_distance(qv, 0.f, qv, 0.f, g.dim, NMN_METRIC_DOT_PRODUCT, h);
         }
         auto row_distance = [&](uint32_t node) -> float {
+            if constexpr (MIX) {
+                const uint4 rec = a.nrec[node];
+                if (rec.z != kNone) {
+                    const uint2* ne = a.nent + (((uint64_t)rec.y << 32) | rec.x);
+                    const float nmag = __uint_as_float(rec.w);
+                    if (entries) return mix_sparse_query(ne, rec.z, nmag, reinterpret_cast<const uint2*>(qv), nnz, qmag, g.metric, h);
+                    return mix_dense_query(ne, rec.z, nmag, qv, qmag, g.metric, h);
+                }
+            }
             if (QK != 0 && QK != 2 && entries)
                 return sparse_distance(g.corpus + (size_t)node * g.ld, g.norms[node], reinterpret_cast<const uint2*>(qv), nnz, qmag,
                                        g.metric, h);
@@ -799,6 +909,15 @@ struct nmn_hnsw {
     void* d_codes = nullptr;  // [vec_cap][ld8] u8
     void* d_rec = nullptr;    // [vec_cap] float4 {scale, min_val, magnitude, squared_magnitude}
     uint32_t ld8 = 0;
+    // EmbeddingStorage::Sparse nodes of a dense handle (docs/hnsw.md §15).  Empty until the first one is inserted; from then on one
+    // slot per node: sp_nnz (kNone: a Dense node), sp_off into sp_pos / sp_val (the canonical entries), sp_mag64 = magnitude_f64().
+    // rows holds to_dense() of such a node, mags its SparseVector::magnitude() (what the query side divides by).
+    std::vector<uint32_t> sp_nnz;
+    std::vector<uint64_t> sp_off;
+    std::vector<double> sp_mag64;
+    std::vector<uint32_t> sp_pos;
+    std::vector<float> sp_val;
+    uint64_t n_sparse = 0, n_sparse_dup = 0;  // sparse nodes; those of them with a duplicated position
     std::vector<uint8_t> level;
     std::vector<std::vector<std::vector<uint32_t>>> nbr;  // [node][layer], id-ascending
     uint64_t entry = ~0ull;
@@ -806,6 +925,7 @@ struct nmn_hnsw {
     uint64_t rng = 42;  // hnsw.rs:1584
     // device side
     DevBuf d_l0, d_l0cnt, d_upidx, d_up, d_upcnt;
+    DevBuf d_nrec, d_nent;  // a handle with sparse nodes: the record per node and the entries of all sparse nodes (SearchArgs)
     uint32_t up_layers = 1, n_upper = 0;
     uint32_t lds_rcap = 0, lds_ccap = 0;  // nmn_hnsw_set_heap_capacity (0 = default)
     struct Scratch {
@@ -903,18 +1023,156 @@ struct HostVisited {
     }
 };
 
-// the query side: distance_dense(stored row `node`, q)
+// ---- SparseVector arithmetic on stored entries (sparse_vector.rs; docs/hnsw.md §13, §15) ------------------------------------------
+// dot_dense (450-466): Iterator::sum::<f64>() of f64(val) * f64(dense[pos]) over the stored entries in order — a left-to-right
+// fold from -0.0 (the convention of docs/hnsw.md §1 for std's float Sum); the caller casts
+inline double h_sparse_dot64(const uint32_t* pos, const float* val, uint64_t nnz, const float* dense) {
+    double acc = -0.0;
+    for (uint64_t i = 0; i < nnz; i++) {
+        const double p = (double)val[i] * (double)dense[pos[i]];
+        acc = acc + p;
+    }
+    return acc;
+}
+inline float h_sparse_dot(const uint32_t* pos, const float* val, uint64_t nnz, const float* dense) {
+    return (float)h_sparse_dot64(pos, val, nnz, dense);
+}
+// magnitude_f64 (554-559): the same fold over f64(v) * f64(v), an f64 sqrt; magnitude (548-551) is its cast
+inline double h_sparse_mag64(const float* val, uint64_t nnz) {
+    double acc = -0.0;
+    for (uint64_t i = 0; i < nnz; i++) {
+        const double p = (double)val[i] * (double)val[i];
+        acc = acc + p;
+    }
+    return std::sqrt(acc);
+}
+inline float h_sparse_mag(const float* val, uint64_t nnz) { return (float)h_sparse_mag64(val, nnz); }
+struct SpView {
+    const uint32_t* pos;
+    const float* val;
+    uint64_t nnz;
+};
+// dot_f64 (419-443): the two-pointer merge, the accumulator from +0.0 (`0.0_f64`, no Sum)
+inline double h_sparse_merge_dot64(const SpView& a, const SpView& b) {
+    double r = 0.0;
+    uint64_t i = 0, j = 0;
+    while (i < a.nnz && j < b.nnz) {
+        if (a.pos[i] == b.pos[j]) {
+            const double p = (double)a.val[i] * (double)b.val[j];
+            r = r + p;
+            i++;
+            j++;
+        } else if (a.pos[i] < b.pos[j]) {
+            i++;
+        } else {
+            j++;
+        }
+    }
+    return r;
+}
+// euclidean_distance (942-1006): the f64 union merge, sqrt, clamped to f32::MAX, cast
+inline float h_sparse_eucl(const SpView& a, const SpView& b) {
+    double sum = 0.0;
+    uint64_t i = 0, j = 0;
+    while (i < a.nnz || j < b.nnz) {
+        double d;
+        if (i >= a.nnz) {
+            d = (double)b.val[j++];
+        } else if (j >= b.nnz) {
+            d = (double)a.val[i++];
+        } else if (a.pos[i] == b.pos[j]) {
+            d = (double)a.val[i++] - (double)b.val[j++];
+        } else if (a.pos[i] < b.pos[j]) {
+            d = (double)a.val[i++];
+        } else {
+            d = -(double)b.val[j++];
+        }
+        const double p = d * d;
+        sum = sum + p;
+    }
+    const double dist = std::sqrt(sum);
+    return dist > (double)3.40282346638528859811704183484516925e+38f ? 3.40282346638528859811704183484516925e+38f : (float)dist;
+}
+
+inline bool node_is_sparse(const nmn_hnsw* h, uint32_t node) { return node < h->sp_nnz.size() && h->sp_nnz[node] != kNone; }
+inline SpView node_entries(const nmn_hnsw* h, uint32_t node) {
+    return SpView{h->sp_pos.data() + h->sp_off[node], h->sp_val.data() + h->sp_off[node], h->sp_nnz[node]};
+}
+
+// the query side: distance_dense(stored row `node`, q).  A Sparse node (hnsw.rs:1035-1045, 1084-1091, 1136-1138): s.dot_dense(q)
+// with s.magnitude() under Cosine / DotProduct, simd::euclidean_distance(s.to_dense(), q) — the row kept here — under Euclidean.
 inline float node_distance(const nmn_hnsw* h, uint32_t node, const float* q, const HQ& hq) {
     if (h->storage == NMN_HNSW_STORAGE_QUANTIZED)
         return h_q8_distance(h->cfg.distance_metric, h->codes.data() + (size_t)node * h->dim, h->qscale[node], h->qmin[node],
                              h->mags[node], h->qxsq[node], q, hq, h->dim);
-    return h_distance(h->cfg.distance_metric, h->rows.data() + (size_t)node * h->dim, h->mags[node], q, hq.mag, h->dim);
+    const int metric = h->cfg.distance_metric;
+    if (metric != NMN_METRIC_EUCLIDEAN && node_is_sparse(h, node)) {
+        const SpView s = node_entries(h, node);
+        const float dot = h_sparse_dot(s.pos, s.val, s.nnz, q);
+        if (metric == NMN_METRIC_DOT_PRODUCT) return -dot;
+        if (h->mags[node] == 0.0f || hq.mag == 0.0f) return 1.0f;
+        const float den = h->mags[node] * hq.mag;
+        const float sim = dot / den;
+        return 1.0f - sim;
+    }
+    return h_distance(metric, h->rows.data() + (size_t)node * h->dim, h->mags[node], q, hq.mag, h->dim);
+}
+// the query side for a SparseVector query Q on a Sparse node (hnsw.rs:1069-1079, 1108-1114, 1143-1145): s.dot(Q) with both
+// magnitude()s, s.euclidean_distance(Q)
+inline float sparse_node_sparse_query(const nmn_hnsw* h, uint32_t node, const SpView& Q, float qmag) {
+    const int metric = h->cfg.distance_metric;
+    const SpView s = node_entries(h, node);
+    if (metric == NMN_METRIC_EUCLIDEAN) return h_sparse_eucl(s, Q);
+    const float dot = (float)h_sparse_merge_dot64(s, Q);
+    if (metric == NMN_METRIC_DOT_PRODUCT) return -dot;
+    if (h->mags[node] == 0.0f || qmag == 0.0f) return 1.0f;
+    const float den = h->mags[node] * qmag;
+    const float sim = dot / den;
+    return 1.0f - sim;
 }
 // the pruning side: try_*_distance on two stored rows — dense arithmetic on the rows the host keeps (a quantized handle keeps the
-// dequantized rows and their simd::magnitude there: the (Quantized, Quantized) arms)
+// dequantized rows and their simd::magnitude there: the (Quantized, Quantized) arms).  With a Sparse node in the pair
+// (hnsw.rs:2453-2459, 2558-2565, 2641-2643): Sparse x Sparse is cosine_similarity (583-600) / euclidean_distance / dot; Dense x
+// Sparse, either order, is cosine_distance_dense (606-632) / simd::euclidean_distance on to_dense() / dot_dense.
 inline float pair_of_nodes_distance(const nmn_hnsw* h, uint32_t a, uint32_t b) {
-    return h_distance(h->cfg.distance_metric, h->rows.data() + (size_t)b * h->dim, h->mags[b], h->rows.data() + (size_t)a * h->dim,
-                      h->mags[a], h->dim);
+    const int metric = h->cfg.distance_metric;
+    const bool sa = node_is_sparse(h, a), sb = node_is_sparse(h, b);
+    if (sa && sb) {
+        const SpView x = node_entries(h, a), y = node_entries(h, b);
+        if (metric == NMN_METRIC_EUCLIDEAN) return h_sparse_eucl(x, y);
+        const double dot = h_sparse_merge_dot64(x, y);
+        if (metric == NMN_METRIC_DOT_PRODUCT) return -(float)dot;
+        float sim = 0.0f;
+        const double ma = h->sp_mag64[a], mb = h->sp_mag64[b];
+        if (!(ma == 0.0 || mb == 0.0)) {
+            const double den = ma * mb;
+            const double r = dot / den;
+            if (!(std::isnan(r) || std::isinf(r))) sim = (float)(r < -1.0 ? -1.0 : (r > 1.0 ? 1.0 : r));
+        }
+        return 1.0f - sim;
+    }
+    if ((sa || sb) && metric != NMN_METRIC_EUCLIDEAN) {
+        const uint32_t sn = sa ? a : b, dn = sa ? b : a;
+        const SpView s = node_entries(h, sn);
+        const float* v = h->rows.data() + (size_t)dn * h->dim;
+        const double dot = h_sparse_dot64(s.pos, s.val, s.nnz, v);
+        if (metric == NMN_METRIC_DOT_PRODUCT) return -(float)dot;
+        const double ms = h->sp_mag64[sn];
+        double acc = -0.0;  // the dense magnitude: a sequential f64 sum over every element
+        for (uint32_t i = 0; i < h->dim; i++) {
+            const double p = (double)v[i] * (double)v[i];
+            acc = acc + p;
+        }
+        const double md = std::sqrt(acc);
+        if (ms == 0.0 || md == 0.0) return 1.0f;
+        const double den = ms * md;
+        const double r = dot / den;
+        if (std::isnan(r) || std::isinf(r)) return 1.0f;
+        const double c = r < -1.0 ? -1.0 : (r > 1.0 ? 1.0 : r);
+        return (float)(1.0 - c);
+    }
+    return h_distance(metric, h->rows.data() + (size_t)b * h->dim, h->mags[b], h->rows.data() + (size_t)a * h->dim, h->mags[a],
+                      h->dim);
 }
 HQ host_query(const nmn_hnsw* h, const float* q) {
     HQ hq;
@@ -1067,25 +1325,7 @@ void host_search_one(const nmn_hnsw* h, const float* q, uint32_t k, uint64_t ef,
 }
 
 // ---- SparseVector queries (sparse_vector.rs:155-193, 400-406, 450-466, 548-559; docs/hnsw.md §13) --------------------------------
-// dot_dense: Iterator::sum::<f64>() of f64(val) * f64(dense[pos]) over the stored entries in order — a left-to-right fold from -0.0
-// (the convention of docs/hnsw.md §1 for std's float Sum) — then `as f32`
-inline float h_sparse_dot(const uint32_t* pos, const float* val, uint64_t nnz, const float* dense) {
-    double acc = -0.0;
-    for (uint64_t i = 0; i < nnz; i++) {
-        const double p = (double)val[i] * (double)dense[pos[i]];
-        acc = acc + p;
-    }
-    return (float)acc;
-}
-// magnitude: the same fold over f64(v) * f64(v), an f64 sqrt, then `as f32`
-inline float h_sparse_mag(const float* val, uint64_t nnz) {
-    double acc = -0.0;
-    for (uint64_t i = 0; i < nnz; i++) {
-        const double p = (double)val[i] * (double)val[i];
-        acc = acc + p;
-    }
-    return (float)std::sqrt(acc);
-}
+// dot_dense and magnitude are h_sparse_dot / h_sparse_mag above.
 
 // The queries of one nmn_hnsw_search_sparse call as SparseVector::try_from_parts leaves them: entries with val == 0.0 (either sign)
 // dropped, NaN kept, the rest stably sorted by position (duplicates survive in input order).  (Named in nmn:: because a HostWalk
@@ -1097,6 +1337,7 @@ struct SparseQueries {
     std::vector<uint32_t> pos;
     std::vector<float> val;
     std::vector<float> mag;     // Q.magnitude() per query
+    std::vector<uint8_t> dup;   // 1: the query holds a duplicated position
     uint64_t nnz(uint32_t q) const { return off[q + 1] - off[q]; }
     void to_dense(uint32_t q, uint32_t dim, float* out) const {  // zeros, then the entries in order: the last of a position wins
         std::fill(out, out + dim, 0.0f);
@@ -1114,6 +1355,7 @@ nmn_status canonicalise_sparse(uint32_t dim, const uint64_t* indptr, const uint3
     out->off.assign(1, 0);
     out->off.reserve((size_t)nq + 1);
     out->mag.resize(nq);
+    out->dup.assign(nq, 0);
     std::vector<std::pair<uint32_t, float>> pairs;
     for (uint32_t q = 0; q < nq; q++) {
         pairs.clear();
@@ -1126,9 +1368,10 @@ nmn_status canonicalise_sparse(uint32_t dim, const uint64_t* indptr, const uint3
             if (values[i] != 0.0f) pairs.emplace_back(positions[i], values[i]);
         }
         std::stable_sort(pairs.begin(), pairs.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
-        for (const auto& pr : pairs) {
-            out->pos.push_back(pr.first);
-            out->val.push_back(pr.second);
+        for (size_t i = 0; i < pairs.size(); i++) {
+            if (i && pairs[i].first == pairs[i - 1].first) out->dup[q] = 1;
+            out->pos.push_back(pairs[i].first);
+            out->val.push_back(pairs[i].second);
         }
         out->off.push_back(out->pos.size());
         out->mag[q] = h_sparse_mag(out->val.data() + out->off[q], out->nnz(q));
@@ -1157,7 +1400,9 @@ void host_search_one_sparse(const nmn_hnsw* h, const SparseQueries& sq, uint32_t
         const uint64_t nnz = sq.nnz(q);
         const float qmag = sq.mag[q];
         const int metric = h->cfg.distance_metric;
+        const SpView Q{pos, val, nnz};
         const auto dist = [&](uint32_t node) -> float {
+            if (node_is_sparse(h, node)) return sparse_node_sparse_query(h, node, Q, qmag);
             const float dot = h_sparse_dot(pos, val, nnz, h->rows.data() + (size_t)node * h->dim);
             if (metric == NMN_METRIC_DOT_PRODUCT) return -dot;
             const float vmag = h->mags[node];
@@ -1174,7 +1419,22 @@ void host_search_one_sparse(const nmn_hnsw* h, const SparseQueries& sq, uint32_t
     HQ hq = host_query(h, dense.data());
     if (route == kSparseDensifyMag) hq.mag = sq.mag[q];
     const float* dq = dense.data();
+    if (h->n_sparse && h->cfg.distance_metric == NMN_METRIC_EUCLIDEAN) {  // a Sparse node: s.euclidean_distance(Q), the union merge
+        const SpView Q{sq.pos.data() + sq.off[q], sq.val.data() + sq.off[q], sq.nnz(q)};
+        const auto dist = [&](uint32_t node) {
+            return node_is_sparse(h, node) ? sparse_node_sparse_query(h, node, Q, 0.0f) : node_distance(h, node, dq, hq);
+        };
+        host_walk_one(h, dist, k, ef, vis, ids, scores, count, evals);
+        return;
+    }
     host_walk_one(h, [&](uint32_t node) { return node_distance(h, node, dq, hq); }, k, ef, vis, ids, scores, count, evals);
+}
+
+// A sparse query the device does not walk on a handle with Sparse nodes (docs/hnsw.md §15): under Euclidean (the union merge), and
+// when the query or any Sparse node holds a duplicated position (dot_f64's merge is a lookup only without them).  The host answers.
+bool sparse_query_host_only(const nmn_hnsw* h, const SparseQueries& sq, uint32_t q) {
+    if (!h->n_sparse) return false;
+    return h->cfg.distance_metric == NMN_METRIC_EUCLIDEAN || h->n_sparse_dup > 0 || sq.dup[q] != 0;
 }
 
 nmn_status wait_in_flight(nmn_hnsw* h) {  // caller holds rw exclusively
@@ -1226,6 +1486,31 @@ nmn_status upload_graph(nmn_hnsw* h) {
     }
     h->up_layers = L;
     h->n_upper = n_upper;
+    if (h->n_sparse) {  // the record of every node and the entries of the sparse ones, in node order
+        std::vector<uint4> rec(n);
+        std::vector<uint2> ent;
+        ent.reserve(h->sp_pos.size());
+        for (size_t i = 0; i < n; i++) {
+            if (!node_is_sparse(h, (uint32_t)i)) {
+                rec[i] = make_uint4(0u, 0u, kNone, 0u);
+                continue;
+            }
+            const uint64_t off = ent.size();
+            uint32_t mbits;
+            memcpy(&mbits, &h->mags[i], 4);
+            rec[i] = make_uint4((uint32_t)off, (uint32_t)(off >> 32), h->sp_nnz[i], mbits);
+            const SpView s = node_entries(h, (uint32_t)i);
+            for (uint64_t e = 0; e < s.nnz; e++) {
+                uint32_t bits;
+                memcpy(&bits, &s.val[e], 4);
+                ent.push_back(make_uint2(s.pos[e], bits));
+            }
+        }
+        HN_TRY(grow(h->d_nrec, n * sizeof(uint4), none, &synced));
+        HN_TRY(grow(h->d_nent, std::max<size_t>(ent.size(), 1) * sizeof(uint2), none, &synced));
+        HN_TRY(hipMemcpy(h->d_nrec.p, rec.data(), n * sizeof(uint4), hipMemcpyHostToDevice));
+        if (!ent.empty()) HN_TRY(hipMemcpy(h->d_nent.p, ent.data(), ent.size() * sizeof(uint2), hipMemcpyHostToDevice));
+    }
     return NMN_OK;
 }
 
@@ -1355,8 +1640,10 @@ SearchArgs graph_args(const nmn_hnsw* h, uint32_t n) {
 }
 
 template <bool SPILL>
-void launch_walk(bool q8, bool perq, int qkind, uint32_t grid, size_t lds, hipStream_t s, const SearchArgs& a) {
-    if (qkind == 3 && q8)
+void launch_walk(bool q8, bool perq, int qkind, bool mix, uint32_t grid, size_t lds, hipStream_t s, const SearchArgs& a) {
+    if (mix)  // a handle with sparse nodes, Cosine / DotProduct: one form for uniform and per-query launches alike
+        hipLaunchKernelGGL((hnsw_search_kernel<SPILL, false, true, 3, true>), dim3(grid), dim3(64), lds, s, a);
+    else if (qkind == 3 && q8)
         hipLaunchKernelGGL((hnsw_search_kernel<SPILL, true, true, 3>), dim3(grid), dim3(64), lds, s, a);
     else if (qkind == 3)
         hipLaunchKernelGGL((hnsw_search_kernel<SPILL, false, true, 3>), dim3(grid), dim3(64), lds, s, a);
@@ -1441,6 +1728,11 @@ nmn_status enqueue_walk_locked(nmn_hnsw* h, nmn_hnsw::Scratch* sc, const float* 
     a.vwords = vwords;
     a.visited = (uint32_t*)sc->vis.p;
     a.spill = (Ent*)sc->spill.p;
+    // Sparse nodes are scored by their own arithmetic under Cosine / DotProduct only (Euclidean is the dense arithmetic on the rows)
+    const bool mix = !q8 && h->n_sparse > 0 && h->cfg.distance_metric != NMN_METRIC_EUCLIDEAN;
+    a.nrec = mix ? (const uint4*)h->d_nrec.p : nullptr;
+    a.nent = mix ? (const uint2*)h->d_nent.p : nullptr;
+    a.kind_u = w.qkind == 3 ? 0u : (uint32_t)w.qkind;
     for (uint32_t q0 = 0; q0 < nq; q0 += chunk) {
         const uint32_t nb = std::min<uint32_t>(chunk, nq - q0);
         const uint32_t nl = w.n_lds > q0 ? std::min<uint32_t>(w.n_lds - q0, nb) : 0;  // the chunk's queries that start in LDS: its first nl
@@ -1465,7 +1757,7 @@ nmn_status enqueue_walk_locked(nmn_hnsw* h, nmn_hnsw::Scratch* sc, const float* 
             a.rcap = w.rcap_lds;
             a.ccap = ccap;
             const size_t lds = fixed + ((size_t)a.rcap + a.ccap) * sizeof(Ent);
-            launch_walk<false>(q8, perq, w.qkind, nl, lds, s, a);
+            launch_walk<false>(q8, perq, w.qkind, mix, nl, lds, s, a);
             HN_TRY(hipGetLastError());
         }
         if (nl < nb)  // results heaps no wave can keep in LDS: these queries go straight to the spill launch
@@ -1473,7 +1765,7 @@ nmn_status enqueue_walk_locked(nmn_hnsw* h, nmn_hnsw::Scratch* sc, const float* 
         a.nq = nb;
         a.rcap = s_rcap;
         a.ccap = s_ccap;
-        launch_walk<true>(q8, perq, w.qkind, std::min(regions, nb), fixed, s, a);
+        launch_walk<true>(q8, perq, w.qkind, mix, std::min(regions, nb), fixed, s, a);
         HN_TRY(hipGetLastError());
     }
     return NMN_OK;
@@ -1686,7 +1978,7 @@ extern "C" nmn_status nmn_hnsw_destroy(nmn_hnsw* h) {
         drop(s->xsim);
         drop(s->xsort);
     }
-    for (DevBuf* b : {&h->d_l0, &h->d_l0cnt, &h->d_upidx, &h->d_up, &h->d_upcnt, &h->hq, &h->hids, &h->hsc, &h->hcnt, &h->hkef,
+    for (DevBuf* b : {&h->d_l0, &h->d_l0cnt, &h->d_upidx, &h->d_up, &h->d_upcnt, &h->d_nrec, &h->d_nent, &h->hq, &h->hids, &h->hsc, &h->hcnt, &h->hkef,
                        &h->hsp_off, &h->hsp_ent, &h->hqmag,
                        &h->hxmeta, &h->hxsim, &h->hxoids, &h->hxosc, &h->hxocnt, &h->hxsort})
         drop(*b);
@@ -1698,9 +1990,12 @@ extern "C" nmn_status nmn_hnsw_destroy(nmn_hnsw* h) {
     return NMN_OK;
 }
 
-extern "C" nmn_status nmn_hnsw_insert(nmn_hnsw* h, const float* rows_host, uint64_t n, uint64_t* ids_out) {
-    if (!h || (!rows_host && n)) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
-    if (n == 0) return NMN_OK;
+namespace {
+// nmn_hnsw_insert, nmn_hnsw_insert_sparse and nmn_hnsw_insert_auto behind their argument checks.  rows_host: the n rows as the
+// flat index keeps them (to_dense() of a Sparse node).  sp / sp_row (dense handle only, nullable): row i is EmbeddingStorage::Sparse
+// with the entries of sp's vector sp_row[i] when sp_row[i] >= 0, Dense otherwise.
+nmn_status insert_rows(nmn_hnsw* h, const float* rows_host, uint64_t n, const SparseQueries* sp, const int64_t* sp_row,
+                       uint64_t* ids_out) {
     std::unique_lock<std::shared_mutex> g(h->rw);
     const uint64_t have = h->level.size();
     if (h->cfg.max_nodes > 0 && have + n > h->cfg.max_nodes) {  // hnsw.rs:1947-1955, text of 102-107; the batch is all or nothing
@@ -1754,7 +2049,24 @@ extern "C" nmn_status nmn_hnsw_insert(nmn_hnsw* h, const float* rows_host, uint6
     }
     static thread_local HostVisited vis;
     for (uint64_t i = 0; i < n; i++) {
-        if (!q8) {
+        const bool sparse = sp && sp_row[i] >= 0;
+        if (sparse || h->n_sparse) {  // a kind per node from the first Sparse one on
+            h->sp_nnz.resize(have + i + 1, kNone);
+            h->sp_off.resize(have + i + 1, 0);
+            h->sp_mag64.resize(have + i + 1, 0.0);
+        }
+        if (sparse) {
+            const uint32_t r = (uint32_t)sp_row[i];
+            const uint64_t c = sp->nnz(r);
+            h->sp_nnz[have + i] = (uint32_t)c;
+            h->sp_off[have + i] = h->sp_pos.size();
+            h->sp_pos.insert(h->sp_pos.end(), sp->pos.begin() + sp->off[r], sp->pos.begin() + sp->off[r + 1]);
+            h->sp_val.insert(h->sp_val.end(), sp->val.begin() + sp->off[r], sp->val.begin() + sp->off[r + 1]);
+            h->sp_mag64[have + i] = h_sparse_mag64(sp->val.data() + sp->off[r], c);
+            h->mags.push_back(sp->mag[r]);  // SparseVector::magnitude(): what distance_dense / distance_sparse divide by
+            h->n_sparse++;
+            if (sp->dup[r]) h->n_sparse_dup++;
+        } else if (!q8) {
             const float* v = h->rows.data() + (have + i) * dim;
             h->mags.push_back(sqrtf(h_dot8(v, v, dim)));  // simd::magnitude, hnsw.rs:198-229
         }
@@ -1762,6 +2074,94 @@ extern "C" nmn_status nmn_hnsw_insert(nmn_hnsw* h, const float* rows_host, uint6
         if (ids_out) ids_out[i] = have + i;
     }
     return upload_graph(h);
+}
+
+nmn_status refuse_sparse_on_q8(const nmn_hnsw* h) {
+    if (h->storage == NMN_HNSW_STORAGE_DENSE) return NMN_OK;
+    return set_error(NMN_ERR_CONFIGURATION,
+                     "HNSW: sparse nodes are served on a dense handle only (the Quantized x Sparse arms are out of scope)");
+}
+}  // namespace
+
+extern "C" nmn_status nmn_hnsw_insert(nmn_hnsw* h, const float* rows_host, uint64_t n, uint64_t* ids_out) {
+    if (!h || (!rows_host && n)) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (n == 0) return NMN_OK;
+    return insert_rows(h, rows_host, n, nullptr, nullptr, ids_out);
+}
+
+// HNSWIndex::insert_sparse (hnsw.rs:1660-1662) for each of the n CSR rows, in order.  Every row is made a SparseVector as
+// try_from_parts makes it, for the whole batch, before anything is inserted.
+extern "C" nmn_status nmn_hnsw_insert_sparse(nmn_hnsw* h, const uint64_t* indptr, const uint32_t* positions, const float* values,
+                                             uint64_t n, uint64_t* ids_out) {
+    if (!h || (!indptr && n)) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    nmn_status st = refuse_sparse_on_q8(h);
+    if (st != NMN_OK) return st;
+    if (n == 0) return NMN_OK;
+    if (n >= (uint64_t)kNone) return set_error(NMN_ERR_CAPACITY, "HNSW: node ids are 32 bits on the device");
+    SparseQueries sv;
+    st = canonicalise_sparse(h->dim, indptr, positions, values, (uint32_t)n, &sv);
+    if (st != NMN_OK) return st;
+    std::vector<float> dense((size_t)n * h->dim);
+    std::vector<int64_t> row(n);
+    for (uint64_t i = 0; i < n; i++) {
+        sv.to_dense((uint32_t)i, h->dim, dense.data() + (size_t)i * h->dim);
+        row[i] = (int64_t)i;
+    }
+    return insert_rows(h, dense.data(), n, &sv, row.data(), ids_out);
+}
+
+// HNSWIndex::insert_auto (hnsw.rs:1671-1680) per row: Sparse(from_dense(row)) iff 1 - nnz / dim >= sparsity_threshold, in f32
+extern "C" nmn_status nmn_hnsw_insert_auto(nmn_hnsw* h, const float* rows_host, uint64_t n, uint64_t* ids_out) {
+    if (!h || (!rows_host && n)) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    nmn_status st = refuse_sparse_on_q8(h);
+    if (st != NMN_OK) return st;
+    if (n == 0) return NMN_OK;
+    const uint32_t dim = h->dim;
+    const float threshold = h->cfg.sparsity_threshold;
+    SparseQueries sv;
+    sv.off.assign(1, 0);
+    std::vector<float> dense(rows_host, rows_host + (size_t)n * dim);
+    std::vector<int64_t> row(n, -1);
+    for (uint64_t i = 0; i < n; i++) {
+        float* v = dense.data() + (size_t)i * dim;
+        uint32_t nnz = 0;
+        for (uint32_t j = 0; j < dim; j++) nnz += v[j] != 0.0f ? 1u : 0u;  // (NaN counts)
+        const float ratio = (float)nnz / (float)dim;
+        const float sparsity = 1.0f - ratio;
+        if (!(sparsity >= threshold)) continue;  // (a NaN threshold: Dense)
+        row[i] = (int64_t)sv.mag.size();
+        for (uint32_t j = 0; j < dim; j++) {  // try_from_dense, sparse_vector.rs:212-236; the row kept is to_dense(): -0.0 becomes +0.0
+            if (v[j] != 0.0f) {
+                sv.pos.push_back(j);
+                sv.val.push_back(v[j]);
+            } else {
+                v[j] = 0.0f;
+            }
+        }
+        sv.off.push_back(sv.pos.size());
+        sv.mag.push_back(h_sparse_mag(sv.val.data() + sv.off[sv.mag.size()], sv.off.back() - sv.off[sv.mag.size()]));
+        sv.dup.push_back(0);
+    }
+    return insert_rows(h, dense.data(), n, &sv, row.data(), ids_out);
+}
+
+// The stored entries of a node: *nnz = their count, UINT32_MAX for a Dense (or Quantized) node; positions_out / values_out nullable
+extern "C" nmn_status nmn_hnsw_sparse_row(nmn_hnsw* h, uint64_t node, uint32_t* positions_out, float* values_out, uint32_t cap,
+                                          uint32_t* nnz) {
+    if (!h || !nnz) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    std::shared_lock<std::shared_mutex> g(h->rw);
+    if (node >= h->level.size()) return set_error(NMN_ERR_NOT_FOUND, "HNSW: no such node");
+    if (!node_is_sparse(h, (uint32_t)node)) {
+        *nnz = UINT32_MAX;
+        return NMN_OK;
+    }
+    const SpView s = node_entries(h, (uint32_t)node);
+    *nnz = (uint32_t)s.nnz;
+    if (!positions_out && !values_out) return NMN_OK;
+    if (cap < s.nnz) return set_error(NMN_ERR_BUFFER_TOO_SMALL, "nmn_hnsw_sparse_row");
+    if (positions_out && s.nnz) memcpy(positions_out, s.pos, s.nnz * 4);
+    if (values_out && s.nnz) memcpy(values_out, s.val, s.nnz * 4);
+    return NMN_OK;
 }
 
 extern "C" uint64_t nmn_hnsw_len(const nmn_hnsw* h) { return h ? h->level.size() : 0; }
@@ -1802,8 +2202,11 @@ extern "C" nmn_status nmn_hnsw_memory_stats(nmn_hnsw* h, nmn_hnsw_memstats* out)
         out->quantized_count = n;
         out->embedding_bytes = n * (16ull + h->dim);
     } else {
-        out->dense_count = n;
-        out->embedding_bytes = n * 4ull * h->dim;
+        // a Sparse node: SparseVector::memory_bytes (sparse_vector.rs:1064-1068) = size_of::<SparseVector>() (56 on a 64-bit
+        // target) + 4 capacity + 4 capacity, the capacities taken as the lengths (what a cloned vector has; docs/hnsw.md §15)
+        out->sparse_count = h->n_sparse;
+        out->dense_count = n - h->n_sparse;
+        out->embedding_bytes = (n - h->n_sparse) * 4ull * h->dim + h->n_sparse * 56ull + 8ull * h->sp_pos.size();
     }
     return NMN_OK;
 }
@@ -1844,7 +2247,7 @@ extern "C" nmn_status nmn_hnsw_set_heap_capacity(nmn_hnsw* h, uint32_t results, 
 extern "C" uint64_t nmn_hnsw_hbm_bytes(nmn_hnsw* h) {
     if (!h) return 0;
     std::shared_lock<std::shared_mutex> g(h->rw);
-    uint64_t t = h->d_l0.cap + h->d_l0cnt.cap + h->d_upidx.cap + h->d_up.cap + h->d_upcnt.cap;
+    uint64_t t = h->d_l0.cap + h->d_l0cnt.cap + h->d_upidx.cap + h->d_up.cap + h->d_upcnt.cap + h->d_nrec.cap + h->d_nent.cap;
     uint64_t a = 0, b = 0, c = 0;
     if (h->vectors && nmn_index_hbm_bytes(h->vectors, &a, &b, &c) == NMN_OK) t += a + b + c;
     if (h->d_codes) t += std::max<uint64_t>(h->vec_cap * h->ld8, 256) + std::max<uint64_t>(h->vec_cap * 16, 256);
@@ -2048,7 +2451,10 @@ nmn_status run_batch(nmn_hnsw* h, const std::vector<HostWalk*>& batch, bool on_h
     std::vector<uint32_t> fl(N), ev(N);
     static thread_local HostVisited vis;
     // a query with more stored entries than a wave keeps in LDS walks in the launch as an entry-less query and is answered by the host
-    auto too_long = [&](const Slot& x) { return x.kind == 1u && x.r->sp->nnz(x.i) > kSparseLdsEntries; };
+    // ... and so is a sparse query the device does not walk on a handle with Sparse nodes (sparse_query_host_only)
+    auto too_long = [&](const Slot& x) {
+        return (x.kind == 1u && x.r->sp->nnz(x.i) > kSparseLdsEntries) || (x.r->sp && sparse_query_host_only(h, *x.r->sp, x.i));
+    };
     auto host_one = [&](const Slot& x, uint64_t* ids, float* scs, uint32_t* cnt, uint64_t* e2) {
         if (x.r->sp)
             host_search_one_sparse(h, *x.r->sp, x.i, x.k, x.ef, vis, ids, scs, cnt, e2);
@@ -2071,7 +2477,7 @@ nmn_status run_batch(nmn_hnsw* h, const std::vector<HostWalk*>& batch, bool on_h
             if (x.kind == 1u) {
                 const SparseQueries& sq = *x.r->sp;
                 const uint64_t c = sq.nnz(x.i);
-                if (c <= kSparseLdsEntries) {
+                if (!too_long(x)) {
                     for (uint64_t e = sq.off[x.i]; e < sq.off[x.i + 1]; e++) {
                         uint32_t bits;
                         memcpy(&bits, &sq.val[e], 4);
@@ -2277,6 +2683,9 @@ nmn_status run_batch(nmn_hnsw* h, const std::vector<HostWalk*>& batch, bool on_h
             host_one(x, ids, scs, r->out_counts + x.i, &e2);
             pad_row(ids, scs, x.k, r->kstride);
             ev[j] = (uint32_t)e2;
+            // (a query the device does not walk on a handle with sparse nodes keeps the dense handle's count: the kernel carries
+            // the entry's distance from layer to layer, one evaluation fewer per upper layer than the reference makes)
+            if (x.r->sp && sparse_query_host_only(h, *x.r->sp, x.i) && n) ev[j] -= h->max_layer;
             if (!too_long(x)) r->spilled++;
         } else {
             if (fl[j] == 2u) r->spilled++;
@@ -2575,6 +2984,10 @@ extern "C" nmn_status nmn_hnsw_search_metric_multi(nmn_hnsw* h, const float* que
 
 static_assert(sizeof(nmn_hnsw_config) == 48, "nmn_hnsw_config is part of the file format");
 
+static const char* const kSaveSparseRefusal =
+    "HNSW: the index holds sparse nodes (nmn_hnsw_insert_sparse / nmn_hnsw_insert_auto) and index file format version 1 has no place "
+    "for their stored entries; saving it would lose them";
+
 namespace {
 
 constexpr uint64_t kGraphFixed = 48 + 8 + 8 + 4 + 4;  // config, rng, entry_point, max_layer, n_upper
@@ -2631,6 +3044,7 @@ namespace nmn {
 
 nmn_status persist_write_hnsw(nmn_hnsw* h, FILE* fp, const char* path) {
     std::shared_lock<std::shared_mutex> g(h->rw);  // searches may run, inserts wait
+    if (h->n_sparse) return set_error(NMN_ERR_CONFIGURATION, kSaveSparseRefusal);
     const uint64_t n = h->level.size();
     const uint32_t dim = h->dim;
     const bool q8 = h->storage == NMN_HNSW_STORAGE_QUANTIZED;
@@ -2871,6 +3285,10 @@ extern "C" nmn_status nmn_hnsw_get_config(const nmn_hnsw* h, nmn_hnsw_config* ou
 
 extern "C" nmn_status nmn_hnsw_save(nmn_hnsw* h, const char* path) {
     if (!h || !path) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    {
+        std::shared_lock<std::shared_mutex> g(h->rw);
+        if (h->n_sparse) return set_error(NMN_ERR_CONFIGURATION, kSaveSparseRefusal);  // before the file is touched
+    }
     FILE* fp = fopen(path, "wb");
     if (!fp) return persist_io_error("cannot create", path);
     nmn_status st = persist_write_hnsw(h, fp, path);

@@ -200,6 +200,45 @@ class GpuHnsw:
         _capi.check(self._lib.nmn_hnsw_insert(self._h, C.c_void_p(r.ctypes.data), r.shape[0], C.c_void_p(ids.ctypes.data)))
         return ids
 
+    def insert_sparse(self, indptr, positions, values):
+        """HNSWIndex::insert_sparse for each CSR row in order (nmn_hnsw_insert_sparse); returns the node ids.  Row i is the
+        (position, value) pairs [indptr[i], indptr[i + 1]), made a SparseVector as try_from_parts does (`search_sparse`'s rules);
+        the node is stored Sparse and scored by SparseVector's own arithmetic (docs/hnsw.md §15).  Dense handles only."""
+        ip = np.ascontiguousarray(indptr, dtype=np.uint64).reshape(-1)
+        pos = np.ascontiguousarray(positions, dtype=np.uint32).reshape(-1)
+        val = np.ascontiguousarray(values, dtype=np.float32).reshape(-1)
+        if ip.size == 0 or pos.size != val.size or (ip.size and int(ip.max()) > pos.size):
+            raise _capi.NeumannGpuError(_capi.ERR_INVALID_ARGUMENT, "indptr [n + 1] into positions / values of one length")
+        n = ip.size - 1
+        ids = np.empty(n, dtype=np.uint64)
+        _capi.check(self._lib.nmn_hnsw_insert_sparse(self._h, C.c_void_p(ip.ctypes.data), C.c_void_p(pos.ctypes.data),
+                                                     C.c_void_p(val.ctypes.data), n, C.c_void_p(ids.ctypes.data)))
+        return ids
+
+    def insert_auto(self, rows):
+        """HNSWIndex::insert_auto for each row in order (nmn_hnsw_insert_auto): a row whose share of zeros reaches
+        config.sparsity_threshold is stored Sparse(from_dense(row)), every other Dense; returns the node ids."""
+        r = np.ascontiguousarray(rows, dtype=np.float32)
+        if r.ndim == 1:
+            r = r[None, :]
+        if r.shape[1] != self.dim:
+            raise _capi.NeumannGpuError(_capi.ERR_DIMENSION_MISMATCH, f"expected {self.dim}, got {r.shape[1]}")
+        ids = np.empty(r.shape[0], dtype=np.uint64)
+        _capi.check(self._lib.nmn_hnsw_insert_auto(self._h, C.c_void_p(r.ctypes.data), r.shape[0], C.c_void_p(ids.ctypes.data)))
+        return ids
+
+    def sparse_row(self, node):
+        """the stored entries of a Sparse node -> (positions u32, values f32), in SparseVector order; None for a Dense node"""
+        nnz = C.c_uint32()
+        _capi.check(self._lib.nmn_hnsw_sparse_row(self._h, int(node), None, None, 0, C.byref(nnz)))
+        if nnz.value == 0xFFFFFFFF:
+            return None
+        pos = np.empty(nnz.value, dtype=np.uint32)
+        val = np.empty(nnz.value, dtype=np.float32)
+        _capi.check(self._lib.nmn_hnsw_sparse_row(self._h, int(node), C.c_void_p(pos.ctypes.data), C.c_void_p(val.ctypes.data),
+                                                  nnz.value, C.byref(nnz)))
+        return pos, val
+
     def levels(self):
         out = np.empty(len(self), dtype=np.uint32)
         _capi.check(self._lib.nmn_hnsw_levels(self._h, C.c_void_p(out.ctypes.data), out.size))
@@ -232,7 +271,7 @@ class GpuHnsw:
         return codes, np.float32(scale.value), np.float32(mn.value)
 
     def get_vector(self, node):
-        """HNSWIndex::get_vector: the row as inserted (dense) or dequantize() (quantized)"""
+        """HNSWIndex::get_vector: the row as inserted (dense), to_dense() of a sparse node, or dequantize() (quantized)"""
         out = np.empty(self.dim, dtype=np.float32)
         _capi.check(self._lib.nmn_hnsw_get_vector(self._h, int(node), C.c_void_p(out.ctypes.data)))
         return out

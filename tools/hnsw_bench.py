@@ -337,6 +337,97 @@ def time_sparse(g, Q, k, args):
     return out
 
 
+def time_mixed(n, d, cfg, Q, k, args, out):
+    """--sparse-node-fraction F (docs/hnsw.md §15): a handle where a share F of the rows is inserted Sparse (70 % of the elements of
+    such a row zeroed, the others doubled) beside an all-dense handle over the to_dense() rows, both built here; search_device and
+    search_sparse of either, alternating call by call; the mixed handle's device, host-buffer and host-walk answers compared bit
+    for bit."""
+    import torch
+    from neumann_amd import GpuHnsw, synth_rows
+    rng = np.random.default_rng(0x15A)
+    F = args.sparse_node_fraction
+    with GpuHnsw(d, cfg, capacity_hint=n) as gm, GpuHnsw(d, cfg, capacity_hint=n) as gd:
+        t0 = time.perf_counter()
+        step = 10_000
+        for r0 in range(0, n, step):
+            rows = synth_rows(0x2F6, r0, min(step, n - r0), d).copy()
+            sparse = rng.random(len(rows)) < F
+            rows[sparse] = np.where(rng.random((int(sparse.sum()), d)) < 0.7, np.float32(0), rows[sparse] * np.float32(2))
+            i = 0
+            while i < len(rows):  # runs of one kind, in row order
+                j = i
+                while j < len(rows) and sparse[j] == sparse[i]:
+                    j += 1
+                if sparse[i]:
+                    gm.insert_sparse(*gm.sparse_from_dense(rows[i:j]))
+                else:
+                    gm.insert(rows[i:j])
+                i = j
+            gd.insert(rows)  # (to_dense(from_dense(row)) is the row: synth rows hold no -0.0)
+            print(f"built {min(r0 + step, n)} nodes of both handles in {time.perf_counter() - t0:.1f} s", file=sys.stderr, flush=True)
+        out["build_s_both"] = round(time.perf_counter() - t0, 1)
+        ms = gm.memory_stats()
+        out.update({"sparse_node_fraction": F, "sparse_nodes": ms["sparse_count"], "dense_nodes": ms["dense_count"],
+                    "hbm_bytes_mixed": gm.hbm_bytes, "hbm_bytes_dense": gd.hbm_bytes})
+        Qs = Q.copy()
+        Qs[rng.random(Qs.shape) < 0.8] = 0.0
+        csr = gm.sparse_from_dense(Qs)
+        qd = torch.from_numpy(Q).cuda()
+
+        def part(nq):
+            e = int(csr[0][nq])
+            return csr[0][:nq + 1], csr[1][:e], csr[2][:e]
+
+        def host(res):
+            torch.cuda.synchronize()
+            return res[0].cpu().numpy().view(np.uint64), res[1].cpu().numpy(), res[2].cpu().numpy().astype(np.uint32)
+
+        def same(a, b):
+            return bool(np.array_equal(a[0], b[0]) and np.array_equal(a[1].view(np.uint32), b[1].view(np.uint32)) and np.array_equal(a[2], b[2]))
+
+        ef = 50
+        dev_ans = host(gm.search_device(qd[:64], k, ef))
+        buf_ans = gm.search(Q[:64], k, ef)
+        sp_ans = gm.search_sparse(*part(64), k, ef)
+        os.environ["NMN_HNSW_HOST_SEARCH"] = "1"
+        try:
+            walk_ans = gm.search(Q[:64], k, ef)
+            walk_sp = gm.search_sparse(*part(64), k, ef)
+        finally:
+            del os.environ["NMN_HNSW_HOST_SEARCH"]
+        out["device_and_host_buffer_agree"] = same(dev_ans, buf_ans)
+        out["device_and_host_walk_agree"] = same(buf_ans, walk_ans)
+        out["sparse_device_and_host_walk_agree"] = same(sp_ans, walk_sp)
+        dd = gd.search(Q[:64], k, ef)
+        out["answers_that_differ_from_the_all_dense_handle"] = int(((buf_ans[0] != dd[0]) | (buf_ans[1].view(np.uint32) != dd[1].view(np.uint32))).any(axis=1).sum())
+        reps = {}
+        for nq in (1, 64, 1024):  # warm every shape
+            for g in (gm, gd):
+                g.search_device(qd[:nq], k, ef)
+                g.search_sparse(*part(nq), k, ef)
+        torch.cuda.synchronize()
+        for _ in range(args.repeats):
+            for nq, calls in ((1, args.calls), (64, args.calls), (1024, max(args.calls // 5, 5))):
+                p, q = part(nq), qd[:nq]
+                t = {"mixed_device": [], "dense_device": [], "mixed_sparse": [], "dense_sparse": []}
+                for _ in range(calls):
+                    for name, g in (("mixed", gm), ("dense", gd)):
+                        t0 = time.perf_counter()
+                        g.search_device(q, k, ef)
+                        torch.cuda.synchronize()
+                        t1 = time.perf_counter()
+                        g.search_sparse(*p, k, ef)
+                        t2 = time.perf_counter()
+                        t[name + "_device"].append(t1 - t0)
+                        t[name + "_sparse"].append(t2 - t1)
+                for name, v in t.items():
+                    reps.setdefault(f"{name}_ms_per_call_nq{nq}", []).append(float(np.median(v)) * 1e3)
+        for key, v in reps.items():
+            out[key] = round(float(np.median(v)), 5)
+            out[key + "_spread"] = round(float((max(v) - min(v)) / np.median(v)), 3)
+    return out
+
+
 def build_or_load(path, n, d, cfg, storage, out, label=""):
     """the handle of the run: GpuHnsw.load(path) when the file exists; otherwise built by nmn_hnsw_insert and, with a path, saved
     and loaded back once.  Seconds and file bytes go to `out`."""
@@ -397,6 +488,9 @@ def main():
     ap.add_argument("--sparse-fraction", type=float, default=0.8, help="--sparse-callers: the share of every query's entries that is zeroed")
     ap.add_argument("--leg-timeout", type=float, default=900.0, help="--sparse-callers: seconds a leg's child process may take")
     ap.add_argument("--sparse-leg", action="store_true", help="(one leg of --sparse-callers, in this process)")
+    ap.add_argument("--sparse-node-fraction", type=float, default=None,
+                    help="insert this share of the rows Sparse (nmn_hnsw_insert_sparse) and time search_device / search_sparse of the "
+                         "mixed handle beside an all-dense handle over the to_dense() rows (docs/hnsw.md §15)")
     ap.add_argument("--index-file", default=None,
                     help="load the index from this file when it exists; otherwise build, save it there and report build / save / load seconds")
     args = ap.parse_args()
@@ -447,6 +541,9 @@ def main():
             out["entries_per_query"] = round(float(csr[1].size) / len(Qs), 1)
             out.update(time_callers(g, Qs, [int(x) for x in args.sparse_callers.split(",")], args, sparse=per_query))
         print(json.dumps(out), flush=True)
+        return
+    if args.sparse_node_fraction is not None:
+        print(json.dumps(time_mixed(n, d, cfg, Q, k, args, out)), flush=True)
         return
     if args.sparse_queries is not None:
         out["storage"] = args.storage
