@@ -73,9 +73,11 @@ def stored(A, q, sweep):
     return At, qt
 
 
-def model(A, q, metric, sweep):
+def model(A, q, metric, sweep, maxima=None):
     """Approximate scores of every row and the claimed collection threshold as a function of the k-th approximate score.
-    Returns dict(approx f64 [n], threshold callable, rho_v, e_abs, worst_rel_row, worst_abs_row)."""
+    Returns dict(approx f64 [n], threshold callable, rho_v, e_abs, worst_rel_row, worst_abs_row).
+    maxima = (rho_v, e_abs, max_norm): what the shard has MEASURED, where that is not what A's own rows give — the stale
+    maxima of a shard whose writes did not raise them (written_attack); an entry of None keeps A's own."""
     A64, q64 = A.astype(np.float64), q.astype(np.float64)
     d = A.shape[1]
     At, qt = stored(A, q, sweep)
@@ -91,6 +93,8 @@ def model(A, q, metric, sweep):
         rho_v, e_abs = 3.95e-3, 3.95e-3 * V
     else:
         rho_v, e_abs = rel.max(), en.max() * 1.0005
+        if maxima is not None:
+            rho_v, e_abs, V = (own if m is None else m for m, own in zip(maxima, (rho_v, e_abs, V)))
     eq = np.sqrt(((q64 - qt) ** 2).sum()) * 1.0005
     rho_q = eq / qn if qf != "f32" else 0.0
     split = 2.0 * rho_v + (2.0 * rho_q * (1.0 + rho_v) * 1.0005 if qf != "f32" else 0.0)
@@ -197,6 +201,18 @@ def _lin_levels(steps, count=256, first=0):
 
 
 # ---------------------------------------------------------------------------------------------- the constructions
+# the margin's own space: scores, or for the Euclidean score 1 / (1 + d) the (negated) distance or squared distance
+_SPACES = {"score": lambda s: s, "dist": lambda s: 1.0 - 1.0 / s, "dist2": lambda s: -(1.0 / s - 1.0) ** 2}
+
+
+def _measure(m, pos, k):
+    """(every row's approximate score, the k-th best decoy's, the collection threshold under it) of a model(), in the margin's
+    own space.  pos: the planted rows, target first."""
+    nat = _SPACES[m["space"]]
+    a_k = np.sort(m["approx"][pos[1:]])[::-1][k - 1]          # the k-th best decoy in the mirror
+    return nat(m["approx"]), nat(a_k), nat(m["threshold"](a_k))
+
+
 def _finish(name, A, q, metric, rows, planted, exact, sweeps, floor, fmt, q_exact, note=""):
     """Plant, model and measure: the common tail of every construction."""
     A[rows] = planted
@@ -204,8 +220,6 @@ def _finish(name, A, q, metric, rows, planted, exact, sweeps, floor, fmt, q_exac
     info = dict(name=name, metric=metric, target=int(rows[0]), decoys=rows[1:].copy(), exact_scores=exact, floor=floor,
                 sweeps=sweeps, row_format=fmt, query_exact=q_exact, note=note, B=np.arange(NB), G=np.arange(NB, A.shape[1]))
     sharp = {}
-    # the margin's own space: scores, or for the Euclidean score 1 / (1 + d) the (negated) distance or squared distance
-    spaces = {"score": lambda s: s, "dist": lambda s: 1.0 - 1.0 / s, "dist2": lambda s: -(1.0 / s - 1.0) ** 2}
     # (a large shard is modelled on its planted rows and a sample of the bulk)
     sub = np.arange(A.shape[0]) if A.shape[0] <= 65536 else np.unique(np.concatenate([rows, np.arange(4096)]))
     pos = np.searchsorted(sub, rows)
@@ -213,13 +227,10 @@ def _finish(name, A, q, metric, rows, planted, exact, sweeps, floor, fmt, q_exac
     bulk[pos] = False
     for sw in sweeps:
         m = model(A[sub], q, metric, sw)
-        nat = spaces[m["space"]]
-        a_k = np.sort(m["approx"][pos[1:]])[::-1][k - 1]          # the k-th best decoy in the mirror
-        a, thr = nat(m["approx"]), nat(m["threshold"](a_k))
-        a_k = nat(a_k)
+        a, a_k, thr = _measure(m, pos, k)
         sharp[sw] = dict(space=m["space"], sharpness=(a_k - a[pos[0]]) / (a_k - thr), E=(a_k - thr) / 2.0, a_k=a_k, a_target=a[pos[0]],
                          a_decoys=a[pos[1:]], best_bulk=a[bulk].max() if bulk.any() else -np.inf, rho_v=m["rho_v"], rho_q=m["rho_q"],
-                         worst_rows=tuple(int(sub[m[w]]) for w in ("worst_rel_row", "worst_abs_row", "worst_norm_row")))
+                         e_abs=m["e_abs"], max_norm=m["max_norm"], worst_rows=tuple(int(sub[m[w]]) for w in ("worst_rel_row", "worst_abs_row", "worst_norm_row")))
     info["by_sweep"] = sharp
     if floor is None:          # both_i8: what the better of its two parts, the rows', allows
         info["floor"] = 0.95 * min(v["rho_v"] / (v["rho_v"] + v["rho_q"] * (1.0 + v["rho_v"])) for v in sharp.values())
@@ -391,3 +402,49 @@ def build(name, metric, **kw):
     if key not in _memo:
         _memo[key] = BUILDERS[name](metric, **kw)
     return _memo[key]
+
+
+# ---------------------------------------------------------------------------------------------- attacks that arrive by write
+# (name, metric, keyword arguments, the model()'s sweep): every construction tests/test_gpu_write_paths.py writes into a shard
+# whose mirror and error maxima already exist.  The f32 matrix-core sweep over a shard that holds a complete bf16 mirror
+# takes that mirror's MEASURED maxima (search_enqueue) and rounds the rows as the mirror does: the mfma_bf16 model is its own.
+WRITTEN_CASES = [("rows_bf16", COS, {}, "valu_bf16"), ("rows_bf16", DOT, {}, "valu_bf16"), ("rows_bf16", L2, {}, "valu_bf16"),
+                 ("rows_bf16", COS, {}, "mfma_bf16"), ("rows_bf16", L2, {}, "mfma_bf16"),
+                 ("rows_i8", COS, {}, "valu_i8"), ("rows_i8", DOT, {}, "valu_i8"), ("rows_i8", L2, {}, "valu_i8"),
+                 ("rows_i8", DOT, {}, "mfma_i8"), ("rows_i8", COS, {"planes": 1}, "mfma_i8_one")]
+_memo_written = {}
+
+
+def written_attack(name, metric, **kw):
+    """(B, A, q, k, planted, info): A is build(name, metric, **kw); B is A before its planted rows arrive — each planted slot
+    holds a copy of the bulk row next to it (planted rows sit in tiles of their own, so a neighbour is bulk).  A shard that
+    is uploaded as B, searched, and then has A's planted rows WRITTEN into it must end with A's mirror and A's error maxima.
+    info (a copy of A's) gains, per modelled sweep,
+      stale_sharpness      (k-th decoy - target) / the margin claimed from B's rho_v, e_abs and max_norm: above 1 the target
+                           is outside a margin whose maxima no write has raised;
+      stale_err_sharpness  the same with B's rho_v and e_abs but A's max_norm (the magnitudes are kept by another word);
+      stale_maxima         B's (rho_v, e_abs, max_norm).
+    Built once per argument set and shared: callers must not modify what they get."""
+    key = (name, metric, tuple(sorted(kw.items())))
+    if key in _memo_written:
+        return _memo_written[key]
+    A, q, k, _, planted, info = build(name, metric, **kw)
+    assert A.shape[0] <= 65536
+    B = A.copy()
+    own = set(planted.tolist())
+    for r in planted:
+        nb = int(r) + 1 if int(r) + 1 < A.shape[0] else int(r) - 1
+        assert nb not in own and nb // 64 == int(r) // 64
+        B[r] = A[nb]
+    info = dict(info, stale_sharpness={}, stale_err_sharpness={}, stale_maxima={})
+    for sw in info["sweeps"]:
+        if SWEEPS[sw][0] == "bf16_apriori":          # nothing measured, nothing to go stale
+            continue
+        mb = model(B, q, metric, sw)
+        stale = (mb["rho_v"], mb["e_abs"], mb["max_norm"])
+        info["stale_maxima"][sw] = stale
+        for field, maxima in (("stale_sharpness", stale), ("stale_err_sharpness", (stale[0], stale[1], None))):
+            a, a_k, thr = _measure(model(A, q, metric, sw, maxima=maxima), planted, k)
+            info[field][sw] = (a_k - a[planted[0]]) / (a_k - thr)
+    _memo_written[key] = (B, A, q, k, planted, info)
+    return _memo_written[key]

@@ -4,7 +4,8 @@ byte per corpus element — and the answer must still be the reference's, bit fo
 the measured quantization error in the candidate margin plus the exact rescore; what these tests attack is exactly that:
 every supported row length and metric, bitmaps dense and sparse, near-ties and duplicates around the cut, rows the
 quantization serves badly (one huge element: the margin becomes useless and the sweep must notice), non-finite rows,
-overwrites and appends after the mirror exists."""
+overwrites and appends after the mirror exists (one shape here; every write path, mirror mode and error maximum:
+tests/test_gpu_write_paths.py)."""
 import numpy as np
 import pytest
 

@@ -133,3 +133,56 @@ def test_bulk_is_out_of_the_way(case):
     bulk = np.ones(A.shape[0], bool)
     bulk[rows] = False
     assert exact[bulk].max() < exact[rows].min()
+
+
+# ---------------------------------------------------------------------------------------------- attacks that arrive by write
+W_IDS = [f"{n}-{'cos l2 dot'.split()[m]}{'-1plane' if kw.get('planes') == 1 else ''}-{sw}" for n, m, kw, sw in ma.WRITTEN_CASES]
+
+
+@pytest.mark.parametrize("name,metric,kw,sweep", ma.WRITTEN_CASES, ids=W_IDS)
+def test_a_stale_margin_loses_the_written_target_and_the_true_one_keeps_it(name, metric, kw, sweep):
+    """written_attack: the shard before its planted rows arrive (B) measures smaller maxima than the planted rows need.  With B's
+    maxima the target lies OUTSIDE the claimed margin (stale_sharpness > 1: a write that did not raise them loses it), with A's
+    own it lies inside (floor <= sharpness < 1) — for all three stale maxima and for the two error maxima alone."""
+    B, A, q, k, planted, info = ma.written_attack(name, metric, **kw)
+    A0 = ma.build(name, metric, **kw)[0]
+    assert A is A0 and B is not A and B.dtype == F and B.shape == A.shape
+    v = info["by_sweep"][sweep]
+    stale, stale_err = info["stale_sharpness"][sweep], info["stale_err_sharpness"][sweep]
+    rho_b, e_b, v_b = info["stale_maxima"][sweep]
+    print(f"{name} metric {metric} {sweep}: sharpness {v['sharpness']:.4f}, stale {stale:.3f}, stale errors only {stale_err:.3f}; "
+          f"rho_v {rho_b:.4g} -> {v['rho_v']:.4g}, e_abs {e_b:.4g} -> {v['e_abs']:.4g}, max norm {v_b:.4g} -> {v['max_norm']:.4g}")
+    assert info["floor"] <= v["sharpness"] < 1.0
+    assert stale > 1.0 and stale_err > 1.0
+    assert rho_b < v["rho_v"] and e_b < v["e_abs"] and v_b <= v["max_norm"]
+    # B is A off the planted rows, and bulk on them: none of them is among B's best, and the bulk's best is where it was
+    off = np.ones(A.shape[0], bool)
+    off[planted] = False
+    assert np.array_equal(B[off], A[off])
+    for r in planted:
+        nb = int(r) + 1 if int(r) + 1 < A.shape[0] else int(r) - 1
+        assert off[nb] and np.array_equal(B[r], A[nb])
+    er, _ = oc.search(B, q, planted.size, metric, nthreads=8, partial=True, native=True)
+    ea = oc.scores_all(A, q, metric, nthreads=8)
+    eb = oc.scores_all(B, q, metric, nthreads=8)
+    assert eb.max() == ea[off].max() < ea[planted].min() and er.size == planted.size
+    # one write of the run [first planted row, last planted row] carries every planted row and nothing else that differs
+    lo, hi = int(planted.min()), int(planted.max())
+    C = B.copy()
+    C[lo:hi + 1] = A[lo:hi + 1]
+    assert np.array_equal(C, A)
+
+
+def test_model_takes_stale_maxima_only_where_it_is_given_them():
+    A, q, k, metric, rows, info = ma.build("rows_i8", ma.DOT)
+    m = ma.model(A, q, metric, "valu_i8")
+    same = ma.model(A, q, metric, "valu_i8", maxima=(None, None, None))
+    assert (same["rho_v"], same["e_abs"], same["max_norm"]) == (m["rho_v"], m["e_abs"], m["max_norm"])
+    half = ma.model(A, q, metric, "valu_i8", maxima=(m["rho_v"] / 2, None, None))
+    tau = float(np.sort(m["approx"])[-k])
+    assert np.array_equal(half["approx"], m["approx"]) and half["rho_v"] == m["rho_v"] / 2
+    assert tau - half["threshold"](tau) < 0.51 * (tau - m["threshold"](tau)), "the rows' rho_v is (almost) the whole margin"
+    # the a-priori bound reads no measurement: stale maxima do not reach it
+    A2, q2, _, _, _, _ = ma.build("rows_bf16", ma.COS)
+    ap = ma.model(A2, q2, ma.COS, "mfma_f32", maxima=(0.0, 0.0, 0.0))
+    assert ap["rho_v"] == 3.95e-3
