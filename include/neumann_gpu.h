@@ -723,7 +723,7 @@ nmn_status nmn_hnsw_set_heap_capacity(nmn_hnsw* h, uint32_t results, uint32_t ca
  * the device. */
 nmn_index* nmn_hnsw_vectors(nmn_hnsw* h);
 /* Device memory the index holds: rows, magnitudes, mirrors, adjacency (dense; with sparse nodes also a 16-byte record per node
- * and 8 bytes per stored entry); codes, records, adjacency (quantized). */
+ * and 8 bytes per stored entry); codes, records, adjacency (quantized); the live mask, one bit per node. */
 uint64_t nmn_hnsw_hbm_bytes(nmn_hnsw* h);
 
 /* nmn_hnsw_create with the storage strategy of HNSWBuildOptions: `storage` is NMN_HNSW_STORAGE_*, cfg->storage is not read.
@@ -831,6 +831,49 @@ nmn_status nmn_hnsw_search_metric_multi(nmn_hnsw* h, const float* queries, uint3
 nmn_status nmn_hnsw_search_metric_device(nmn_hnsw* h, const float* queries_dev, uint32_t nq, uint32_t top_k,
                                          const nmn_xmetric* metric, uint64_t* out_ids_dev, float* out_scores_dev,
                                          uint32_t* out_counts_dev, void* stream);
+
+/* ---- CacheIndex::search_with_metric behind the walk (tensor_cache/src/index.rs:186-375; docs/hnsw.md §16) ------ */
+
+/* The live mask: one bit per node, on the host and in HBM beside the adjacency.  A new node is live.  Sets (live != 0) or clears
+ * the bits of nodes[0 .. n) under the lock nmn_hnsw_insert takes, with the same wait for the device searches in flight, and
+ * sends the touched words again.  A node at or past nmn_hnsw_len: NMN_ERR_NOT_FOUND, nothing flipped.  Only nmn_hnsw_cache_search*
+ * read the mask: every other entry ignores it and launches exactly what it launches without.  nmn_hnsw_save does NOT store the
+ * mask (a loaded handle has every node live); nmn_hnsw_hbm_bytes counts it. */
+nmn_status nmn_hnsw_set_node_mask(nmn_hnsw* h, const uint64_t* nodes, uint64_t n, int32_t live);
+/* 1: the node's bit is set, 0: cleared, -1: no such node. */
+int32_t nmn_hnsw_node_live(nmn_hnsw* h, uint64_t node);
+/* CacheIndex::search_with_metric (index.rs:186-272) with node ids in place of keys, on a dense-strategy handle:
+ * c = max(3 k, 10) in 64 bits (204), served as min(c, len); index.search(query, c) under the handle's OWN HNSW metric (layer 0
+ * runs with max(ef_search, c)), the walk's scores dropped; a candidate whose live bit is cleared is dropped (223-226); every other
+ * is scored as metric.to_similarity(metric.compute(from_dense(query), stored)) where `stored` is from_dense(row) for a Dense node
+ * and the stored entries AS THEY ARE for a Sparse node (229-246: a duplicated position pairs the i-th duplicate with the i-th,
+ * which is not what its to_dense() row scores); kept iff similarity >= threshold in f32 (248: NaN on either side fails, equality
+ * passes); stable sort by similarity descending, truncated to k (256-262).  queries HOST nq x dim; out_ids nq x k NODE ids
+ * (unused = UINT64_MAX), out_scores nq x k similarities (unused = -inf), out_counts nq.  Empty index: counts 0.
+ * Refused before anything is enqueued or written: a quantized handle NMN_ERR_CONFIGURATION (a CacheIndex never holds quantized
+ * nodes), an unknown kind NMN_ERR_CONFIGURATION, k == 0 NMN_ERR_INVALID_TOP_K (the rule of nmn_hnsw_search_metric; the key
+ * layer answers k == 0 itself).  Angular / Geodesic: the acos rule of nmn_index_score_rows_xmetric.
+ * stats: rows_scanned and fallback_queries are the walk's, candidates_rescored = the most candidates of one query.
+ * It joins the coalescer of nmn_hnsw_search: concurrent callers of any host-buffer search leave as one walk; the re-rank and the
+ * ordering behind it carry kind, weights, top_k, threshold and the filter flag per query.  A call whose c is above 4 096 runs
+ * alone.  NMN_HNSW_HOST_SEARCH=1 and NMN_HNSW_NO_COALESCE=1 act as for nmn_hnsw_search_metric. */
+nmn_status nmn_hnsw_cache_search(nmn_hnsw* h, const float* queries, uint32_t nq, uint32_t k, float threshold,
+                                 const nmn_xmetric* metric, uint64_t* out_ids, float* out_scores, uint32_t* out_counts,
+                                 nmn_search_stats* stats);
+/* CacheIndex::search_sparse_with_metric (index.rs:291-375): the same with index.search_sparse(query, c), and the query's own
+ * entries go into compute().  The CSR, its canonicalisation, errors and texts are nmn_hnsw_search_sparse's.  The walk is that
+ * entry's (on the host where docs/hnsw.md §15 routes it there); its candidate ids are then uploaded for the device re-rank and
+ * ordering.  A query without a duplicated position is re-ranked as its to_dense() row (the same bits), one with a duplicate on
+ * its entries.  Runs alone: it does not share a batch. */
+nmn_status nmn_hnsw_cache_search_sparse(nmn_hnsw* h, const uint64_t* indptr, const uint32_t* positions, const float* values,
+                                        uint32_t nq, uint32_t k, float threshold, const nmn_xmetric* metric, uint64_t* out_ids,
+                                        float* out_scores, uint32_t* out_counts, nmn_search_stats* stats);
+/* nmn_hnsw_cache_search with every buffer in DEVICE memory, enqueued on `stream` and not waited for, like
+ * nmn_hnsw_search_metric_device: the walk's launches, the dense re-rank, on a handle with sparse nodes the merge re-rank, and the
+ * filtered ordering (above min(NMN_XMETRIC_SORT_FROM, 16 384) candidates the large-k sort, query by query); nothing is read back. */
+nmn_status nmn_hnsw_cache_search_device(nmn_hnsw* h, const float* queries_dev, uint32_t nq, uint32_t k, float threshold,
+                                        const nmn_xmetric* metric, uint64_t* out_ids_dev, float* out_scores_dev,
+                                        uint32_t* out_counts_dev, void* stream);
 
 /* ---- persistence of the device layout ----------------------------------- */
 

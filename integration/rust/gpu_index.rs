@@ -402,6 +402,65 @@ impl GpuHnswIndex {
             .collect())
     }
 
+    /// Sets (`live`) or clears the live bits of `nodes` (nmn_hnsw_set_node_mask).  Only `cache_search*` read the mask.
+    pub fn set_node_mask(&self, nodes: &[u64], live: bool) -> Result<()> {
+        let st = unsafe { ffi::nmn_hnsw_set_node_mask(self.raw, nodes.as_ptr(), nodes.len() as u64, live as i32) };
+        check(st, self.dim, self.dim)
+    }
+
+    /// The node's live bit; None for a node the index does not hold (nmn_hnsw_node_live).
+    pub fn node_live(&self, node: usize) -> Option<bool> {
+        match unsafe { ffi::nmn_hnsw_node_live(self.raw, node as u64) } {
+            0 => Some(false),
+            1 => Some(true),
+            _ => None,
+        }
+    }
+
+    /// `CacheIndex::search_with_metric` with node ids in place of keys (nmn_hnsw_cache_search): max(3k, 10) candidates from the walk,
+    /// dead nodes dropped, every other re-scored under `metric` on its stored form, kept iff similarity >= threshold, best first,
+    /// at most k.  Concurrent callers ride the coalescer's launches (docs/hnsw.md §16).  k == 0 answers empty here, as the
+    /// reference's key layer does.
+    pub fn cache_search(&self, q: &[f32], k: usize, threshold: f32, metric: &crate::ExtendedDistanceMetric) -> Result<Vec<(usize, f32)>> {
+        if q.len() != self.dim {
+            return Err(VectorError::DimensionMismatch { expected: self.dim, got: q.len() });
+        }
+        if k == 0 {
+            return Ok(Vec::new());
+        }
+        let m = ffi::nmn_xmetric::from(metric);
+        let mut ids = vec![u64::MAX; k];
+        let mut scores = vec![f32::NEG_INFINITY; k];
+        let mut n = 0u32;
+        let st = unsafe {
+            ffi::nmn_hnsw_cache_search(self.raw, q.as_ptr(), 1, k as u32, threshold, &m, ids.as_mut_ptr(), scores.as_mut_ptr(), &mut n,
+                                       std::ptr::null_mut())
+        };
+        check(st, self.dim, q.len())?;
+        Ok(ids.into_iter().zip(scores).take(n as usize).map(|(r, s)| (r as usize, s)).collect())
+    }
+
+    /// `CacheIndex::search_sparse_with_metric` with node ids in place of keys (nmn_hnsw_cache_search_sparse).  `q`: (position,
+    /// value) pairs in any order, made a SparseVector as `try_from_parts` does.
+    pub fn cache_search_sparse(&self, q: &[(u32, f32)], k: usize, threshold: f32, metric: &crate::ExtendedDistanceMetric) -> Result<Vec<(usize, f32)>> {
+        if k == 0 {
+            return Ok(Vec::new());
+        }
+        let indptr = [0u64, q.len() as u64];
+        let positions: Vec<u32> = q.iter().map(|e| e.0).collect();
+        let values: Vec<f32> = q.iter().map(|e| e.1).collect();
+        let m = ffi::nmn_xmetric::from(metric);
+        let mut ids = vec![u64::MAX; k];
+        let mut scores = vec![f32::NEG_INFINITY; k];
+        let mut n = 0u32;
+        let st = unsafe {
+            ffi::nmn_hnsw_cache_search_sparse(self.raw, indptr.as_ptr(), positions.as_ptr(), values.as_ptr(), 1, k as u32, threshold, &m,
+                                              ids.as_mut_ptr(), scores.as_mut_ptr(), &mut n, std::ptr::null_mut())
+        };
+        check(st, self.dim, self.dim)?;
+        Ok(ids.into_iter().zip(scores).take(n as usize).map(|(r, s)| (r as usize, s)).collect())
+    }
+
     /// (batches that carried two or more concurrent calls, the calls in them) — nmn_hnsw_coalesce_stats.
     pub fn coalesce_stats(&self) -> (u64, u64) {
         let (mut b, mut c) = (0u64, 0u64);

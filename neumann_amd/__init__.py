@@ -11,5 +11,6 @@ from .flat_index import (DistanceMetric, GpuFlatIndex, merge_topk_device, merge_
 from .sharded import GpuShardedIndex  # noqa: F401,E402
 from .hnsw import GpuHnsw, HNSWBuildOptions, HNSWConfig  # noqa: F401,E402
 from .xmetric import ExtendedDistanceMetric, GeometricConfig  # noqa: F401,E402
+from .cache_index import CacheIndex  # noqa: F401,E402
 
 __version__ = "0.3.0"

@@ -251,6 +251,13 @@ SIGNATURES = {
                                            C.POINTER(SearchStats)]),
     "nmn_hnsw_search_metric_multi": (C.c_int32, [vp, vp, C.c_uint32, vp, vp, C.c_uint32, vp, vp, vp, C.POINTER(SearchStats)]),
     "nmn_hnsw_search_metric_device": (C.c_int32, [vp, vp, C.c_uint32, C.c_uint32, C.POINTER(XMetric), vp, vp, vp, vp]),
+    "nmn_hnsw_set_node_mask": (C.c_int32, [vp, vp, C.c_uint64, C.c_int32]),
+    "nmn_hnsw_node_live": (C.c_int32, [vp, C.c_uint64]),
+    "nmn_hnsw_cache_search": (C.c_int32, [vp, vp, C.c_uint32, C.c_uint32, C.c_float, C.POINTER(XMetric), vp, vp, vp,
+                                          C.POINTER(SearchStats)]),
+    "nmn_hnsw_cache_search_sparse": (C.c_int32, [vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_float, C.POINTER(XMetric), vp, vp, vp,
+                                                 C.POINTER(SearchStats)]),
+    "nmn_hnsw_cache_search_device": (C.c_int32, [vp, vp, C.c_uint32, C.c_uint32, C.c_float, C.POINTER(XMetric), vp, vp, vp, vp]),
     "nmn_index_save": (C.c_int32, [vp, C.c_char_p]),
     "nmn_index_load": (C.c_int32, [C.c_char_p, C.POINTER(IndexDesc), C.c_uint64, C.c_uint64, C.POINTER(vp)]),
     "nmn_ivf_save": (C.c_int32, [vp, C.c_char_p]),

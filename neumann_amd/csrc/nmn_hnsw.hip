@@ -926,6 +926,11 @@ struct nmn_hnsw {
     // device side
     DevBuf d_l0, d_l0cnt, d_upidx, d_up, d_upcnt;
     DevBuf d_nrec, d_nent;  // a handle with sparse nodes: the record per node and the entries of all sparse nodes (SearchArgs)
+    // the live mask (docs/hnsw.md §16): one bit per node, here and in HBM beside the adjacency.  A new node is live;
+    // nmn_hnsw_set_node_mask flips bits.  Only nmn_hnsw_cache_search* read it.  live_n: the nodes that have their bit.
+    std::vector<uint32_t> live;
+    uint64_t live_n = 0;
+    DevBuf d_live;
     uint32_t up_layers = 1, n_upper = 0;
     uint32_t lds_rcap = 0, lds_ccap = 0;  // nmn_hnsw_set_heap_capacity (0 = default)
     struct Scratch {
@@ -1486,6 +1491,12 @@ nmn_status upload_graph(nmn_hnsw* h) {
     }
     h->up_layers = L;
     h->n_upper = n_upper;
+    // the live mask: every node that came since the last upload is live (an insert, a load — the file does not hold the mask)
+    h->live.resize((n + 31) / 32, 0u);
+    for (uint64_t i = h->live_n; i < n; i++) h->live[i >> 5] |= 1u << (i & 31);
+    h->live_n = n;
+    HN_TRY(grow(h->d_live, h->live.size() * 4, none, &synced));
+    if (n) HN_TRY(hipMemcpy(h->d_live.p, h->live.data(), h->live.size() * 4, hipMemcpyHostToDevice));
     if (h->n_sparse) {  // the record of every node and the entries of the sparse ones, in node order
         std::vector<uint4> rec(n);
         std::vector<uint2> ent;
@@ -1805,16 +1816,35 @@ uint64_t metric_candidates(const nmn_hnsw* h, uint32_t top_k) {
     return std::min<uint64_t>(c, std::max<uint64_t>(h->level.size(), 1));
 }
 
+// CacheIndex::search_with_metric's candidate count (tensor_cache/src/index.rs:204): max(3k, 10) in 64 bits, served as min(c, len) like
+// the one above (index.search(query, c) walks layer 0 with max(ef_search, c))
+uint64_t cache_candidates(const nmn_hnsw* h, uint32_t top_k) {
+    const uint64_t c = std::max<uint64_t>(3ull * top_k, 10);
+    return std::min<uint64_t>(c, std::max<uint64_t>(h->level.size(), 1));
+}
+
+// What the re-rank and ordering of a cache call read of the handle (docs/hnsw.md §16).  Caller holds rw.
+XmetricFilter cache_filter(const nmn_hnsw* h, float threshold) {
+    XmetricFilter f;
+    f.live = (const uint32_t*)h->d_live.p;
+    f.threshold = threshold;
+    if (h->n_sparse) {
+        f.nrec = (const uint4*)h->d_nrec.p;
+        f.nent = (const uint2*)h->d_nent.p;
+    }
+    return f;
+}
+
 // The candidate block of the stream's scratch grown for nq x c.  Caller holds rw (shared) and sc->mu, and keeps sc->mu until the
 // last launch that reads the block is enqueued: the block belongs to ONE call at a time (another caller on the same stream would
 // overwrite the candidates, or free the block under a launch being prepared).
-nmn_status metric_scratch(nmn_hnsw::Scratch* sc, hipStream_t s, uint32_t nq, uint32_t c, uint32_t top_k) {
+nmn_status metric_scratch(nmn_hnsw::Scratch* sc, hipStream_t s, uint32_t nq, uint32_t c, uint32_t top_k, bool filtered = false) {
     bool synced = false;
     HN_TRY(grow(sc->xids, (size_t)nq * c * 8, s, &synced));
     HN_TRY(grow(sc->xsc, (size_t)nq * c * 4, s, &synced));
     HN_TRY(grow(sc->xsim, (size_t)nq * c * 4, s, &synced));
     HN_TRY(grow(sc->xcnt, (size_t)nq * 4, s, &synced));
-    const size_t sort_bytes = xmetric_order_scratch_bytes(c, top_k);
+    const size_t sort_bytes = xmetric_order_scratch_bytes(c, top_k, filtered);
     sc->xsort_use = sort_bytes != 0;
     HN_TRY(grow(sc->xsort, sort_bytes, s, &synced));
     return NMN_OK;
@@ -1822,10 +1852,11 @@ nmn_status metric_scratch(nmn_hnsw::Scratch* sc, hipStream_t s, uint32_t nq, uin
 
 // The re-rank and the ordering of the candidate block in sc, behind whatever filled it on s.  Caller holds sc->mu.
 nmn_status enqueue_rerank(nmn_hnsw* h, nmn_hnsw::Scratch* sc, const float* q_dev, uint32_t nq, uint32_t c, uint32_t top_k,
-                          const nmn_xmetric& m, uint64_t* o_ids, float* o_sc, uint32_t* o_cnt, hipStream_t s) {
+                          const nmn_xmetric& m, uint64_t* o_ids, float* o_sc, uint32_t* o_cnt, hipStream_t s,
+                          const XmetricFilter* filter = nullptr) {
     HN_TRY(launch_xmetric_rerank(h->vectors ? h->vectors->corpus : nullptr, h->vectors ? h->vectors->ld : 0, h->dim, h->level.size(),
                                  q_dev, nq, c, (const uint64_t*)sc->xids.p, (const uint32_t*)sc->xcnt.p, m, top_k, (float*)sc->xsim.p,
-                                 o_ids, o_sc, o_cnt, sc->xsort_use ? sc->xsort.p : nullptr, s));
+                                 o_ids, o_sc, o_cnt, sc->xsort_use ? sc->xsort.p : nullptr, s, filter));
     return NMN_OK;
 }
 
@@ -1978,7 +2009,7 @@ extern "C" nmn_status nmn_hnsw_destroy(nmn_hnsw* h) {
         drop(s->xsim);
         drop(s->xsort);
     }
-    for (DevBuf* b : {&h->d_l0, &h->d_l0cnt, &h->d_upidx, &h->d_up, &h->d_upcnt, &h->d_nrec, &h->d_nent, &h->hq, &h->hids, &h->hsc, &h->hcnt, &h->hkef,
+    for (DevBuf* b : {&h->d_l0, &h->d_l0cnt, &h->d_upidx, &h->d_up, &h->d_upcnt, &h->d_nrec, &h->d_nent, &h->d_live, &h->hq, &h->hids, &h->hsc, &h->hcnt, &h->hkef,
                        &h->hsp_off, &h->hsp_ent, &h->hqmag,
                        &h->hxmeta, &h->hxsim, &h->hxoids, &h->hxosc, &h->hxocnt, &h->hxsort})
         drop(*b);
@@ -2247,7 +2278,7 @@ extern "C" nmn_status nmn_hnsw_set_heap_capacity(nmn_hnsw* h, uint32_t results, 
 extern "C" uint64_t nmn_hnsw_hbm_bytes(nmn_hnsw* h) {
     if (!h) return 0;
     std::shared_lock<std::shared_mutex> g(h->rw);
-    uint64_t t = h->d_l0.cap + h->d_l0cnt.cap + h->d_upidx.cap + h->d_up.cap + h->d_upcnt.cap + h->d_nrec.cap + h->d_nent.cap;
+    uint64_t t = h->d_l0.cap + h->d_l0cnt.cap + h->d_upidx.cap + h->d_up.cap + h->d_upcnt.cap + h->d_nrec.cap + h->d_nent.cap + h->d_live.cap;
     uint64_t a = 0, b = 0, c = 0;
     if (h->vectors && nmn_index_hbm_bytes(h->vectors, &a, &b, &c) == NMN_OK) t += a + b + c;
     if (h->d_codes) t += std::max<uint64_t>(h->vec_cap * h->ld8, 256) + std::max<uint64_t>(h->vec_cap * 16, 256);
@@ -2292,6 +2323,8 @@ struct Slot {
     uint32_t top;            // a metric query's top_k
     const nmn_xmetric* xm;   // ... and its metric (nullptr: a plain walk)
     uint32_t kind;           // the kernel's query kind: sparse_route for a query of a sparse call, 0 for every other
+    bool filt = false;       // a cache query (docs/hnsw.md §16): k is the 3k rule's count, the ordering is the filtered one ...
+    float thr = 0.0f;        // ... with this threshold
 };
 
 // A batch whose slots are all metric slots with one top_k and one metric (a lone nmn_hnsw_search_metric is one): the uniform chain
@@ -2300,6 +2333,8 @@ struct Slot {
 nmn_status run_metric_uniform(nmn_hnsw* h, const std::vector<HostWalk*>& batch, const std::vector<Slot>& slot, bool on_host) {
     const uint32_t N = (uint32_t)slot.size(), dim = h->dim, top_k = slot[0].top, c = slot[0].k;
     const nmn_xmetric& metric = *slot[0].xm;
+    const XmetricFilter flt = cache_filter(h, slot[0].thr);
+    const XmetricFilter* filter = slot[0].filt ? &flt : nullptr;
     hipStream_t s = h->host_stream;
     bool synced = true;  // (every earlier host call ended with a wait)
     const hipStream_t none = (hipStream_t)-1;
@@ -2311,7 +2346,7 @@ nmn_status run_metric_uniform(nmn_hnsw* h, const std::vector<HostWalk*>& batch, 
     // is read back and, should a query stay flagged, filled again
     nmn_hnsw::Scratch* sc = scratch_of(h, s);
     std::lock_guard<std::mutex> slk(sc->mu);
-    nmn_status st = metric_scratch(sc, s, N, c, top_k);
+    nmn_status st = metric_scratch(sc, s, N, c, top_k, filter != nullptr);
     if (st != NMN_OK) return st;
     uint32_t off = 0;
     for (const HostWalk* r : batch) {
@@ -2350,7 +2385,7 @@ nmn_status run_metric_uniform(nmn_hnsw* h, const std::vector<HostWalk*>& batch, 
         st = enqueue_search_locked(h, sc, (const float*)h->hq.p, N, c, 0, (uint64_t*)sc->xids.p, (float*)sc->xsc.p, (uint32_t*)sc->xcnt.p, s);
         if (st != NMN_OK) return st;
     }
-    st = enqueue_rerank(h, sc, (const float*)h->hq.p, N, c, top_k, metric, (uint64_t*)h->hids.p, (float*)h->hsc.p, (uint32_t*)h->hcnt.p, s);
+    st = enqueue_rerank(h, sc, (const float*)h->hq.p, N, c, top_k, metric, (uint64_t*)h->hids.p, (float*)h->hsc.p, (uint32_t*)h->hcnt.p, s, filter);
     if (st != NMN_OK) return st;
     if ((st = hand_out()) != NMN_OK) return st;
     if (!on_host) {
@@ -2370,7 +2405,7 @@ nmn_status run_metric_uniform(nmn_hnsw* h, const std::vector<HostWalk*>& batch, 
             if (fl[q] == 1u) host_walk(q);
         HN_TRY(hipMemcpyAsync(sc->xids.p, cid.data(), (size_t)N * c * 8, hipMemcpyHostToDevice, s));
         HN_TRY(hipMemcpyAsync(sc->xcnt.p, ccnt.data(), (size_t)N * 4, hipMemcpyHostToDevice, s));
-        st = enqueue_rerank(h, sc, (const float*)h->hq.p, N, c, top_k, metric, (uint64_t*)h->hids.p, (float*)h->hsc.p, (uint32_t*)h->hcnt.p, s);
+        st = enqueue_rerank(h, sc, (const float*)h->hq.p, N, c, top_k, metric, (uint64_t*)h->hids.p, (float*)h->hsc.p, (uint32_t*)h->hcnt.p, s, filter);
         if (st != NMN_OK) return st;
         if ((st = hand_out()) != NMN_OK) return st;
         HN_TRY(hipStreamSynchronize(s));
@@ -2394,6 +2429,8 @@ nmn_status run_metric_uniform(nmn_hnsw* h, const std::vector<HostWalk*>& batch, 
 // here and is a dense query from then on; a batch with other kinds is the per-query launch with QK = 3, except the lone sparse
 // call with one k and one ef, which stays the uniform QK = 1 / QK = 2 launch.  Takes rw (shared) and host_mu for the batch.  A
 // failure is the whole batch's.
+// Cache calls (§16) are metric calls whose candidate count is the 3k rule's and whose slots carry a threshold and the filter flag: the
+// merge re-rank of their Sparse-node candidates and the filtered ordering run behind the dense re-rank, per query like it.
 // on_host (a metric call under NMN_HNSW_HOST_SEARCH=1, alone): the walks on the host, the re-rank on the device.
 nmn_status run_batch(nmn_hnsw* h, const std::vector<HostWalk*>& batch, bool on_host = false) {
     std::shared_lock<std::shared_mutex> g(h->rw);
@@ -2408,14 +2445,16 @@ nmn_status run_batch(nmn_hnsw* h, const std::vector<HostWalk*>& batch, bool on_h
     auto slot_of = [&](HostWalk* r, uint32_t i) {
         if (r->sp) return Slot{r, i, r->k_of(i), r->ef_of(i, h->cfg.ef_search), 0, nullptr, route};
         if (!r->xm) return Slot{r, i, r->k_of(i), r->ef_of(i, h->cfg.ef_search), 0, nullptr, 0};
-        const uint32_t c = (uint32_t)metric_candidates(h, r->k_of(i));  // here, under rw: an insert may have run since the call was checked
-        return Slot{r, i, c, std::max<uint32_t>(h->cfg.ef_search, c), r->k_of(i), &r->metric_of(i), 0};
+        // here, under rw: an insert may have run since the call was checked
+        const uint32_t c = (uint32_t)(r->filter ? cache_candidates(h, r->k_of(i)) : metric_candidates(h, r->k_of(i)));
+        return Slot{r, i, c, std::max<uint32_t>(h->cfg.ef_search, c), r->k_of(i), &r->metric_of(i), 0, r->filter, r->threshold};
     };
     const Slot s0 = slot_of(batch[0], 0);
     const uint32_t k0 = s0.k, ef0 = s0.ef;
     const uint32_t row0 = s0.xm ? s0.top : k0;  // the callers' row length a uniform batch needs
     bool uniform = true, plain = true;  // plain: every slot is a dense query to the kernel (kind 0)
     uint32_t kmax = 0, M = 0, topmax = 0;
+    bool any_filter = false;
     for (HostWalk* r : batch) {
         r->evals = 0;
         r->spilled = 0;
@@ -2425,6 +2464,8 @@ nmn_status run_batch(nmn_hnsw* h, const std::vector<HostWalk*>& batch, bool on_h
             const Slot sl = slot_of(r, i);
             if (sl.k != k0 || sl.ef != ef0 || sl.top != s0.top || !sl.xm != !s0.xm || (sl.xm && memcmp(sl.xm, s0.xm, sizeof(nmn_xmetric)) != 0))
                 uniform = false;
+            if (sl.filt != s0.filt || (sl.filt && memcmp(&sl.thr, &s0.thr, 4) != 0)) uniform = false;  // (thresholds agree bit for bit)
+            any_filter = any_filter || sl.filt;
             if (sl.kind != 0u) plain = false;
             kmax = std::max(kmax, sl.k);
             if (sl.xm) {
@@ -2512,12 +2553,13 @@ nmn_status run_batch(nmn_hnsw* h, const std::vector<HostWalk*>& batch, bool on_h
         return NMN_OK;
     };
     XmetricBatchPlan plan;
+    const XmetricFilter flt = cache_filter(h, 0.0f);  // (a threshold per item)
     auto metric_chain = [&]() -> nmn_status {  // behind whatever filled the walk's rows on s; the answers on their way back
         if (!M) return NMN_OK;
         HN_TRY(launch_xmetric_rerank_batch(h->vectors ? h->vectors->corpus : nullptr, h->vectors ? h->vectors->ld : 0, dim, n,
                                            (const float*)h->hq.p, kstride, (const uint64_t*)h->hids.p, (const uint32_t*)h->hcnt.p, plan,
                                            (const uint32_t*)h->hxmeta.p, (float*)h->hxsim.p, topmax, (uint64_t*)h->hxoids.p,
-                                           (float*)h->hxosc.p, (uint32_t*)h->hxocnt.p, h->hxsort.p, s));
+                                           (float*)h->hxosc.p, (uint32_t*)h->hxocnt.p, h->hxsort.p, s, any_filter ? &flt : nullptr));
         HN_TRY(hipMemcpyAsync(h->st_xoids.data(), h->hxoids.p, (size_t)M * topmax * 8, hipMemcpyDeviceToHost, s));
         HN_TRY(hipMemcpyAsync(h->st_xosc.data(), h->hxosc.p, (size_t)M * topmax * 4, hipMemcpyDeviceToHost, s));
         HN_TRY(hipMemcpyAsync(h->st_xocnt.data(), h->hxocnt.p, (size_t)M * 4, hipMemcpyDeviceToHost, s));
@@ -2580,7 +2622,7 @@ nmn_status run_batch(nmn_hnsw* h, const std::vector<HostWalk*>& batch, bool on_h
                 h->st_kef[2 * N + j] = x.kind;
                 h->st_kef[3 * N + j] = cand_cap(x.ef, h->lds_ccap, region, n);
             }
-            if (x.xm) h->st_xitems.push_back(XmetricBatchItem{j, x.k, x.top, *x.xm});
+            if (x.xm) h->st_xitems.push_back(XmetricBatchItem{j, x.k, x.top, *x.xm, x.thr, x.filt ? 1u : 0u});
             const uint32_t need = results_need(x.ef, n);
             w.rcap_all = std::max(w.rcap_all, need);
             if (results_fit_lds(h, x.ef, n)) {
@@ -2741,14 +2783,15 @@ nmn_status host_walk_call(nmn_hnsw* h, HostWalk& me, nmn_search_stats* stats) {
     return NMN_OK;
 }
 
-// nmn_hnsw_search_metric and nmn_hnsw_search_metric_multi behind their argument checks
+// nmn_hnsw_search_metric, nmn_hnsw_search_metric_multi and nmn_hnsw_cache_search behind their argument checks
 nmn_status metric_walk_call(nmn_hnsw* h, HostWalk& me, nmn_search_stats* stats) {
     const bool on_host = host_search_forced();
     bool empty;
     {
         std::shared_lock<std::shared_mutex> g(h->rw);
         empty = h->level.empty();
-        for (uint32_t i = 0; i < me.nq && !me.alone; i++) me.alone = metric_candidates(h, me.k_of(i)) > kShareCandMax;
+        for (uint32_t i = 0; i < me.nq && !me.alone; i++)
+            me.alone = (me.filter ? cache_candidates(h, me.k_of(i)) : metric_candidates(h, me.k_of(i))) > kShareCandMax;
     }
     // the host walk has no turn to take at the queue, but the re-rank runs on the handle's own stream: run_batch, alone
     const nmn_status st = on_host ? run_batch(h, std::vector<HostWalk*>{&me}, true) : submit_walk(h, me);
@@ -2972,6 +3015,210 @@ extern "C" nmn_status nmn_hnsw_search_metric_multi(nmn_hnsw* h, const float* que
     me.out_scores = out_scores;
     me.out_counts = out_counts;
     return metric_walk_call(h, me, stats);
+}
+
+// ---- CacheIndex::search_with_metric behind the walk (tensor_cache/src/index.rs:186-375; docs/hnsw.md §16) ---------------------------
+namespace {
+nmn_status check_cache_call(nmn_hnsw* h, uint32_t k, const nmn_xmetric* m) {
+    if (!h || !m) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (h->storage != NMN_HNSW_STORAGE_DENSE)
+        return set_error(NMN_ERR_CONFIGURATION,
+                         "HNSW: nmn_hnsw_cache_search re-scores the stored form of its candidates, and a CacheIndex never holds "
+                         "quantized nodes (a dense-strategy handle only)");
+    if (!xmetric_valid(m)) return set_error(NMN_ERR_CONFIGURATION, "unknown extended distance metric");
+    if (k == 0) return set_error(NMN_ERR_INVALID_TOP_K, "k == 0");
+    return NMN_OK;
+}
+void clear_stats(nmn_search_stats* stats) {
+    if (!stats) return;
+    memset(stats, 0, sizeof *stats);
+    stats->scan_ms = stats->total_ms = -1.0f;
+}
+}  // namespace
+
+extern "C" nmn_status nmn_hnsw_set_node_mask(nmn_hnsw* h, const uint64_t* nodes, uint64_t n, int32_t live) {
+    if (!h || (!nodes && n)) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (n == 0) return NMN_OK;
+    std::unique_lock<std::shared_mutex> g(h->rw);
+    for (uint64_t i = 0; i < n; i++)  // before anything is flipped: the call is all or nothing
+        if (nodes[i] >= h->live_n) return set_error(NMN_ERR_NOT_FOUND, "HNSW: node out of range");
+    HN_TRY(hipSetDevice(h->device));
+    nmn_status st = wait_in_flight(h);  // the searches in flight read the words about to change
+    if (st != NMN_OK) return st;
+    {
+        std::lock_guard<std::mutex> hl(h->host_mu);
+        HN_TRY(hipStreamSynchronize(h->host_stream));
+    }
+    std::vector<uint64_t> words(n);
+    for (uint64_t i = 0; i < n; i++) {
+        const uint64_t w = nodes[i] >> 5;
+        const uint32_t bit = 1u << (nodes[i] & 31);
+        if (live)
+            h->live[w] |= bit;
+        else
+            h->live[w] &= ~bit;
+        words[i] = w;
+    }
+    std::sort(words.begin(), words.end());
+    words.erase(std::unique(words.begin(), words.end()), words.end());
+    for (size_t i = 0; i < words.size();) {  // the touched words again, run by run
+        size_t j = i + 1;
+        while (j < words.size() && words[j] == words[j - 1] + 1) j++;
+        HN_TRY(hipMemcpy((uint32_t*)h->d_live.p + words[i], h->live.data() + words[i], (j - i) * 4, hipMemcpyHostToDevice));
+        i = j;
+    }
+    return NMN_OK;
+}
+
+extern "C" int32_t nmn_hnsw_node_live(nmn_hnsw* h, uint64_t node) {
+    if (!h) return -1;
+    std::shared_lock<std::shared_mutex> g(h->rw);
+    if (node >= h->live_n) return -1;
+    return (int32_t)((h->live[node >> 5] >> (node & 31)) & 1u);
+}
+
+extern "C" nmn_status nmn_hnsw_cache_search(nmn_hnsw* h, const float* queries, uint32_t nq, uint32_t k, float threshold,
+                                            const nmn_xmetric* metric, uint64_t* out_ids, float* out_scores, uint32_t* out_counts,
+                                            nmn_search_stats* stats) {
+    nmn_status st = check_cache_call(h, k, metric);
+    if (st != NMN_OK) return st;
+    clear_stats(stats);
+    if (nq == 0) return NMN_OK;
+    if (!queries || !out_ids || !out_scores || !out_counts) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    HostWalk me;  // through the coalescer like nmn_hnsw_search_metric; a lone call is the uniform chain with the filtered ordering
+    me.q = queries;
+    me.nq = nq;
+    me.k1 = me.kstride = k;
+    me.xm = metric;
+    me.filter = true;
+    me.threshold = threshold;
+    me.out_ids = out_ids;
+    me.out_scores = out_scores;
+    me.out_counts = out_counts;
+    return metric_walk_call(h, me, stats);
+}
+
+extern "C" nmn_status nmn_hnsw_cache_search_device(nmn_hnsw* h, const float* queries_dev, uint32_t nq, uint32_t k, float threshold,
+                                                   const nmn_xmetric* metric, uint64_t* out_ids_dev, float* out_scores_dev,
+                                                   uint32_t* out_counts_dev, void* stream) {
+    nmn_status st = check_cache_call(h, k, metric);
+    if (st != NMN_OK) return st;
+    if (nq == 0) return NMN_OK;
+    if (!queries_dev || !out_ids_dev || !out_scores_dev || !out_counts_dev) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    std::shared_lock<std::shared_mutex> g(h->rw);
+    const uint32_t c = (uint32_t)cache_candidates(h, k);
+    HN_TRY(hipSetDevice(h->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    nmn_hnsw::Scratch* sc = scratch_of(h, s);
+    const XmetricFilter flt = cache_filter(h, threshold);
+    {
+        std::lock_guard<std::mutex> slk(sc->mu);  // grow, walk, both re-ranks and the ordering as one unit on this stream
+        st = metric_scratch(sc, s, nq, c, k, true);
+        if (st != NMN_OK) return st;
+        st = enqueue_search_locked(h, sc, queries_dev, nq, c, 0, (uint64_t*)sc->xids.p, (float*)sc->xsc.p, (uint32_t*)sc->xcnt.p, s);
+        if (st != NMN_OK) return st;
+        st = enqueue_rerank(h, sc, queries_dev, nq, c, k, *metric, out_ids_dev, out_scores_dev, out_counts_dev, s, &flt);
+        if (st != NMN_OK) return st;
+    }
+    return record_search(h, s);
+}
+
+// CacheIndex::search_sparse_with_metric (index.rs:291-375).  An `alone` call in two steps: the walk is nmn_hnsw_search_sparse's own
+// for c candidates (on the device or, where §15 says so, on the host), whose ids then go up for the device re-rank and the filtered
+// ordering.  The dense re-rank runs on Q.to_dense(); a query with a duplicated position is scored by the merge kernel on its entries.
+extern "C" nmn_status nmn_hnsw_cache_search_sparse(nmn_hnsw* h, const uint64_t* indptr, const uint32_t* positions, const float* values,
+                                                   uint32_t nq, uint32_t k, float threshold, const nmn_xmetric* metric,
+                                                   uint64_t* out_ids, float* out_scores, uint32_t* out_counts, nmn_search_stats* stats) {
+    nmn_status st = check_cache_call(h, k, metric);
+    if (st != NMN_OK) return st;
+    clear_stats(stats);
+    if (nq == 0) return NMN_OK;
+    if (!indptr || !out_ids || !out_scores || !out_counts) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    SparseQueries sq;  // every query as try_from_parts leaves it, before anything is walked or written
+    st = canonicalise_sparse(h->dim, indptr, positions, values, nq, &sq);
+    if (st != NMN_OK) return st;
+    uint32_t c;
+    {
+        std::shared_lock<std::shared_mutex> g(h->rw);
+        c = (uint32_t)cache_candidates(h, k);
+    }
+    std::vector<uint64_t> cid((size_t)nq * c);
+    std::vector<float> csc((size_t)nq * c);
+    std::vector<uint32_t> ccnt(nq);
+    HostWalk me;
+    me.sp = &sq;
+    me.nq = nq;
+    me.k1 = me.kstride = c;
+    me.alone = true;
+    me.out_ids = cid.data();
+    me.out_scores = csc.data();
+    me.out_counts = ccnt.data();
+    nmn_search_stats ws;
+    st = host_walk_call(h, me, &ws);
+    if (st != NMN_OK) return st;
+    const uint32_t dim = h->dim;
+    uint32_t rescored = 0;
+    {
+        std::shared_lock<std::shared_mutex> g(h->rw);
+        std::lock_guard<std::mutex> hl(h->host_mu);
+        HN_TRY(hipSetDevice(h->device));
+        hipStream_t s = h->host_stream;
+        bool synced = true;  // (every earlier host call ended with a wait)
+        const hipStream_t none = (hipStream_t)-1;
+        HN_TRY(grow(h->hq, (size_t)nq * dim * 4, none, &synced));
+        HN_TRY(grow(h->hids, (size_t)nq * k * 8, none, &synced));
+        HN_TRY(grow(h->hsc, (size_t)nq * k * 4, none, &synced));
+        HN_TRY(grow(h->hcnt, (size_t)nq * 4, none, &synced));
+        nmn_hnsw::Scratch* sc = scratch_of(h, s);
+        std::lock_guard<std::mutex> slk(sc->mu);
+        st = metric_scratch(sc, s, nq, c, k, true);
+        if (st != NMN_OK) return st;
+        h->st_q.resize((size_t)nq * dim);
+        h->st_spoff.assign(1, 0);
+        h->st_spent.clear();
+        h->st_kef.assign(nq, 0u);
+        bool any_dup = false;
+        for (uint32_t q = 0; q < nq; q++) {
+            sq.to_dense(q, dim, h->st_q.data() + (size_t)q * dim);
+            if (sq.dup[q]) {  // its own entries go up: the merge kernel scores every candidate of it
+                any_dup = true;
+                h->st_kef[q] = 1u;
+                for (uint64_t e = sq.off[q]; e < sq.off[q + 1]; e++) {
+                    uint32_t bits;
+                    memcpy(&bits, &sq.val[e], 4);
+                    h->st_spent.push_back(make_uint2(sq.pos[e], bits));
+                }
+            }
+            h->st_spoff.push_back(h->st_spent.size());
+            rescored = std::max(rescored, std::min(ccnt[q], c));
+        }
+        XmetricFilter flt = cache_filter(h, threshold);
+        HN_TRY(hipMemcpyAsync(h->hq.p, h->st_q.data(), (size_t)nq * dim * 4, hipMemcpyHostToDevice, s));
+        HN_TRY(hipMemcpyAsync(sc->xids.p, cid.data(), (size_t)nq * c * 8, hipMemcpyHostToDevice, s));
+        HN_TRY(hipMemcpyAsync(sc->xcnt.p, ccnt.data(), (size_t)nq * 4, hipMemcpyHostToDevice, s));
+        if (any_dup) {
+            HN_TRY(grow(h->hsp_off, h->st_spoff.size() * 8, none, &synced));
+            HN_TRY(grow(h->hsp_ent, std::max<size_t>(h->st_spent.size(), 1) * 8, none, &synced));
+            HN_TRY(grow(h->hkef, (size_t)nq * 4, none, &synced));
+            HN_TRY(hipMemcpyAsync(h->hsp_off.p, h->st_spoff.data(), h->st_spoff.size() * 8, hipMemcpyHostToDevice, s));
+            HN_TRY(hipMemcpyAsync(h->hsp_ent.p, h->st_spent.data(), h->st_spent.size() * 8, hipMemcpyHostToDevice, s));
+            HN_TRY(hipMemcpyAsync(h->hkef.p, h->st_kef.data(), (size_t)nq * 4, hipMemcpyHostToDevice, s));
+            flt.q_off = (const uint64_t*)h->hsp_off.p;
+            flt.q_ent = (const uint2*)h->hsp_ent.p;
+            flt.q_use = (const uint32_t*)h->hkef.p;
+        }
+        st = enqueue_rerank(h, sc, (const float*)h->hq.p, nq, c, k, *metric, (uint64_t*)h->hids.p, (float*)h->hsc.p, (uint32_t*)h->hcnt.p, s, &flt);
+        if (st != NMN_OK) return st;
+        HN_TRY(hipMemcpyAsync(out_ids, h->hids.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost, s));
+        HN_TRY(hipMemcpyAsync(out_scores, h->hsc.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, s));
+        HN_TRY(hipMemcpyAsync(out_counts, h->hcnt.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+        HN_TRY(hipStreamSynchronize(s));
+    }
+    if (stats) {
+        *stats = ws;
+        stats->candidates_rescored = rescored;
+    }
+    return NMN_OK;
 }
 
 // ---- persistence (docs/hnsw.md §10) ----------------------------------------------------------------------------------------------

@@ -21,7 +21,8 @@ struct SparseQueries;  // the canonicalised queries of a sparse call (nmn_hnsw.h
 
 // One call of nmn_hnsw_search (k1 / ef1), nmn_hnsw_search_multi (k / ef per query), nmn_hnsw_search_metric (xm, one metric; k1 its
 // top_k), nmn_hnsw_search_metric_multi (xm, xm_stride 1: a metric per query; k their top_k), nmn_hnsw_search_sparse (sp; k1 / ef1) or
-// nmn_hnsw_search_sparse_multi (sp; k / ef per query) on its way through the coalescer.
+// nmn_hnsw_search_sparse_multi (sp; k / ef per query) or nmn_hnsw_cache_search (xm, filter, threshold; k1 its top_k) on its way through
+// the coalescer.
 struct HostWalk {
     const float* q = nullptr;
     const SparseQueries* sp = nullptr;  // a sparse call (docs/hnsw.md §14): query i is entry i of *sp, and q is null
@@ -33,6 +34,8 @@ struct HostWalk {
     uint32_t* out_counts = nullptr;
     const nmn_xmetric* xm = nullptr;  // a metric call (docs/hnsw.md §12): k_of(i) is query i's top_k, metric_of(i) its metric
     uint32_t xm_stride = 0;
+    bool filter = false;              // a cache call (docs/hnsw.md §16; xm set): the candidate count is the 3k rule's, the ordering keeps
+    float threshold = 0.0f;           // only live nodes whose similarity >= threshold
     bool alone = false;               // nobody rides with this call, and it rides with nobody (a metric call with c above kShareCandMax;
                                       // a sparse call whose entries would change the candidate limit of the others, §14)
     uint32_t rescored = 0;            // filled like evals: the largest candidate count re-ranked

@@ -476,12 +476,29 @@ hipError_t launch_ivf_flat_scan(const float* queries, uint32_t dim, const float*
 // first top_k of it to out_* (unused slots UINT64_MAX / -inf).  Two launches, nothing read back.  Above 16 384 candidates the
 // ordering goes query by query through the large-k sort instead: xmetric_order_scratch_bytes(c, top_k) decides it, once per call
 // (0: the rank count, order_scratch NULL; otherwise order_scratch holds that many bytes and its presence selects the sort).
+//
+// CacheIndex::search_with_metric behind the walk (docs/hnsw.md §16), `filter` non-null: a candidate takes part in the ordering iff
+// its id is in bounds, its bit of `live` is set and its similarity >= threshold (in f32; NaN on either side fails); out_counts is
+// min(participants, top_k).  A candidate that is a Sparse node (nrec / nent, the §15 record and entries; nullable on a handle
+// without sparse nodes) is scored by xmetric_merge_kernel on its stored entries, behind the dense re-rank and over its slot of sim.
+// q_off / q_ent / q_use (nullable): query q with q_use[q] != 0 brings the entries [q_off[q], q_off[q + 1]) of q_ent instead of its
+// dense row (a sparse query with a duplicated position), and the merge kernel scores every candidate of it.
+// The filtered ordering takes the sort above min(NMN_XMETRIC_SORT_FROM, 16 384) candidates: xmetric_order_scratch_bytes(.., true).
+struct XmetricFilter {
+    const uint32_t* live = nullptr;  // one bit per node: bit (id & 31) of word id >> 5
+    float threshold = 0.0f;          // (a coalesced batch: XmetricBatchItem::threshold)
+    const uint4* nrec = nullptr;
+    const uint2* nent = nullptr;
+    const uint64_t* q_off = nullptr;
+    const uint2* q_ent = nullptr;
+    const uint32_t* q_use = nullptr;
+};
 bool xmetric_valid(const nmn_xmetric* m);
-size_t xmetric_order_scratch_bytes(uint32_t c, uint32_t top_k);
+size_t xmetric_order_scratch_bytes(uint32_t c, uint32_t top_k, bool filtered = false);
 hipError_t launch_xmetric_rerank(const float* rows, uint32_t ld, uint32_t dim, uint64_t n_rows, const float* queries, uint32_t nq,
                                  uint32_t c, const uint64_t* cand_ids, const uint32_t* cand_counts, const nmn_xmetric& m,
                                  uint32_t top_k, float* sim, uint64_t* out_ids, float* out_scores, uint32_t* out_counts,
-                                 void* order_scratch, hipStream_t s);
+                                 void* order_scratch, hipStream_t s, const XmetricFilter* filter = nullptr);
 
 // The same for a coalesced batch whose queries bring their own top_k and metric (docs/hnsw.md §12).  The batch's N queries sit where
 // a per-query walk left them: candidate rows kstride apart, the walk's counts.  items[m] (m < M) names the metric queries: q its
@@ -489,9 +506,14 @@ hipError_t launch_xmetric_rerank(const float* rows, uint32_t ld, uint32_t dim, u
 // the launches read (meta, to be copied to the device as they are); the launches then are at most one re-rank per family present,
 // one rank-count ordering, and the large-k sort for every query with c above the sort threshold, alone.  Output row m is
 // out_stride long; the sort writes only its first top_k slots (the caller pads the rest).  sim: N x kstride floats.
+// A cache query (docs/hnsw.md §16) is an item with filter != 0 and its threshold: the filtered ordering (and the filtered sort) orders
+// it, the merge kernel re-scores its Sparse-node candidates; `filter` (live, nrec, nent; its threshold and q_* are not read) must then
+// be given to the launch.  The items without it run exactly the launches they have always run.
 struct XmetricBatchItem {
     uint32_t q, c, top_k;
     nmn_xmetric m;
+    float threshold = 0.0f;
+    uint32_t filter = 0;
 };
 struct XmetricBatchPlan {
     const XmetricBatchItem* items = nullptr;
@@ -500,13 +522,15 @@ struct XmetricBatchPlan {
     uint32_t fam_c[6] = {};    // the longest candidate list among them
     uint32_t rank_len = 0;     // max(c, top_k) over the queries the rank count orders (0: none)
     size_t sort_bytes = 0;     // scratch of the large-k sort (0: no query takes it)
+    uint32_t fam_fc[6] = {};   // the longest candidate list among the family's cache queries (0: none)
+    uint32_t frank_len = 0;    // rank_len of the cache queries the filtered rank count orders (0: none)
 };
 void xmetric_batch_plan(const XmetricBatchItem* items, uint32_t M, uint32_t N, std::vector<uint32_t>& meta, XmetricBatchPlan& plan);
 hipError_t launch_xmetric_rerank_batch(const float* rows, uint32_t ld, uint32_t dim, uint64_t n_rows, const float* queries,
                                        uint32_t kstride, const uint64_t* cand_ids, const uint32_t* cand_counts,
                                        const XmetricBatchPlan& plan, const uint32_t* meta_dev, float* sim, uint32_t out_stride,
                                        uint64_t* out_ids, float* out_scores, uint32_t* out_counts, void* sort_scratch_dev,
-                                       hipStream_t s);
+                                       hipStream_t s, const XmetricFilter* filter = nullptr);
 
 // synthetic data
 hipError_t launch_synth_fill(float* corpus, uint32_t ld, uint32_t dim, uint64_t seed, uint64_t global_row0,

@@ -353,10 +353,238 @@ __global__ __launch_bounds__(256) void xmetric_order_kernel(std::conditional_t<P
     if (blockIdx.x == 0 && threadIdx.x == 0) p.out_counts[o] = n_out;
 }
 
+constexpr uint32_t kRankMax = 16384;  // c x c comparisons a query up to here
+
+// ---- CacheIndex::search_with_metric behind the walk (tensor_cache/src/index.rs:186-375; docs/hnsw.md §16) ---------------------------
+// A candidate that is an EmbeddingStorage::Sparse node is scored on its stored entries as they are (index.rs:229-246), and a sparse
+// query on its own (335-349): SparseVector's two-pointer walks (sparse_vector.rs:419-443, 816-1059), which pair the i-th duplicate
+// of a position with the i-th and so differ from the dense loop above as soon as a position is stored twice.  One lane walks one
+// (query, candidate) pair; the loops are lane-divergent and hold no cross-lane operation.
+constexpr uint32_t kNoEntries = 0xFFFFFFFFu;  // nrec[node].z of a Dense node
+
+// One side of a pair: an entry list in position order, or a dense row read as SparseVector::from_dense reads it (the positions with
+// x != 0.0, NaN among them).
+struct EntryCursor {
+    const uint2* ent;
+    const float* dense;
+    uint32_t i, n;
+    __device__ __forceinline__ void settle() {
+        if (!ent)
+            while (i < n && !(dense[i] != 0.0f)) i++;
+    }
+    __device__ __forceinline__ bool more() const { return i < n; }
+    __device__ __forceinline__ uint32_t pos() const { return ent ? ent[i].x : i; }
+    __device__ __forceinline__ float val() const { return ent ? __uint_as_float(ent[i].y) : dense[i]; }
+    __device__ __forceinline__ void next() {
+        i++;
+        settle();
+    }
+};
+
+// The union walk of euclidean_distance_squared_f64 / manhattan_distance / weighted_jaccard (964-1005, 1013-1052, 886-928) over a and b.
+// The intersection walks of dot_f64 / jaccard_index / overlap_coefficient (419-443, 824-838, 857-871) make the same comparisons while
+// both sides last and meet no equal pair afterwards, so their sums are this walk's Equal arm; magnitude_f64 (553-559) adds a side's
+// squares in that side's own order, which is the order this walk consumes them in.  Every sum the chain family CH needs, in one pass.
+template <int CH>
+__device__ __forceinline__ PairSums merge_pass(EntryCursor a, EntryCursor b, double* sa_out, uint32_t* na_out) {
+    PairSums r{0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0u, 0u};
+    constexpr bool kDot = CH == kChCos || CH == kChComposite;
+    constexpr bool kSd = CH == kChEucl || CH == kChComposite;
+    double sa = 0.0;
+    uint32_t na = 0;
+    a.settle();
+    b.settle();
+    while (a.more() || b.more()) {
+        const uint32_t pa = a.more() ? a.pos() : 0xFFFFFFFFu, pb = b.more() ? b.pos() : 0xFFFFFFFFu;  // (a position is below dim)
+        const bool ta = a.more() && pa <= pb, tb = b.more() && pb <= pa;  // Less: a alone; Greater: b alone; Equal: both
+        const double xd = ta ? (double)a.val() : 0.0, yd = tb ? (double)b.val() : 0.0;
+        if (ta) {
+            na++;
+            if (kDot) sa = sa + xd * xd;
+            a.next();
+        }
+        if (tb) {
+            r.nb++;
+            if (kDot) r.sb = r.sb + yd * yd;
+            b.next();
+        }
+        if (ta && tb) {
+            r.inter++;
+            if (kDot) r.dot = r.dot + xd * yd;
+        }
+        if (kSd || CH == kChManh) {
+            const double d = xd - yd;
+            if (kSd) r.sd = r.sd + d * d;
+            if (CH == kChManh) r.man = r.man + __builtin_fabs(d);
+        }
+        if (CH == kChWJ) {
+            const double ax = __builtin_fabs(xd), ay = __builtin_fabs(yd);
+            r.wmin = r.wmin + (ax < ay ? ax : ay);
+            r.wmax = r.wmax + (ax > ay ? ax : ay);
+        }
+    }
+    *sa_out = sa;
+    *na_out = na;
+    return r;
+}
+
+struct MergeArgs {
+    const float* rows;       // row r at rows + r * ld
+    const float* queries;    // [.][dim] (not read for a query that brings entries)
+    const uint4* nrec;       // [n_rows] {entry offset lo, hi, entries or kNoEntries, .} (nullable: no Sparse node)
+    const uint2* nent;       // (position, value bits) of every Sparse node
+    const uint64_t* q_off;   // queries that bring entries (nullable, with q_ent and q_use)
+    const uint2* q_ent;
+    const uint32_t* q_use;
+    const uint64_t* ids;     // [.][stride]
+    const uint32_t* counts;  // [.]
+    float* sim;              // [.][stride]
+    // a coalesced batch (qsel non-null): workgroup row y serves query qsel[y] if qflt says it is a cache query, under its own metric
+    const uint32_t* qsel;
+    const uint32_t* qflt;
+    const int* qkind;
+    const float* qcw;
+    const float* qsw;
+    const float* qmw;
+    uint64_t n_rows;
+    uint32_t ld, dim, stride;
+    int kind;
+    float cw, sw, mw;
+};
+
+// sim[q][e] of every candidate that is a Sparse node, and of every candidate of a query that brings entries.  The other slots are
+// xmetric_rerank_kernel's and are not touched.  An id out of bounds of such a query scores NaN, as there.
+template <int CH>
+__global__ __launch_bounds__(256) void xmetric_merge_kernel(MergeArgs p) {
+    uint32_t q = blockIdx.y;
+    int kind = p.kind;
+    float cw = p.cw, sw = p.sw, mw = p.mw;
+    if (p.qsel) {
+        q = p.qsel[blockIdx.y];
+        if (!p.qflt[q]) return;
+        kind = p.qkind[q];
+        cw = p.qcw[q];
+        sw = p.qsw[q];
+        mw = p.qmw[q];
+    }
+    const uint32_t count = min(p.counts[q], p.stride);
+    const uint32_t e = blockIdx.x * 256u + threadIdx.x;
+    if (e >= count) return;
+    const size_t o = (size_t)q * p.stride + e;
+    const uint64_t id = p.ids[o];
+    const bool q_entries = p.q_use && p.q_use[q] != 0u;
+    if (id >= p.n_rows) {
+        if (q_entries) p.sim[o] = xm_to_similarity(kind, __int_as_float(0x7FC00000));
+        return;
+    }
+    const uint4 rec = p.nrec ? p.nrec[id] : make_uint4(0u, 0u, kNoEntries, 0u);
+    const bool sparse = rec.z != kNoEntries;
+    if (!sparse && !q_entries) return;
+    EntryCursor a, b;
+    if (q_entries) {
+        a.ent = p.q_ent + p.q_off[q];
+        a.dense = nullptr;
+        a.n = (uint32_t)(p.q_off[q + 1] - p.q_off[q]);
+    } else {
+        a.ent = nullptr;
+        a.dense = p.queries + (size_t)q * p.dim;
+        a.n = p.dim;
+    }
+    if (sparse) {
+        b.ent = p.nent + (((uint64_t)rec.y << 32) | rec.x);
+        b.dense = nullptr;
+        b.n = rec.z;
+    } else {
+        b.ent = nullptr;
+        b.dense = p.rows + (size_t)id * p.ld;
+        b.n = p.dim;
+    }
+    a.i = b.i = 0u;
+    double sa;
+    uint32_t na;
+    const PairSums s = merge_pass<CH>(a, b, &sa, &na);
+    const float raw = finish_pair(kind, s, __builtin_sqrt(sa), na, cw, sw, mw);
+    p.sim[o] = xm_to_similarity(kind, raw);
+}
+
+// The filtered ordering (index.rs:222-262): xmetric_order_kernel's rule, rank of e = #{j : s_j > s_e} + #{j < e : s_j == s_e}, over the
+// PARTICIPANTS only — the entries whose id is in bounds, whose node is live (node_to_key has it, 223-226) and whose similarity
+// >= threshold in f32 (248; a NaN on either side fails).  out_counts = min(participants, top_k).  At most kRankMax candidates.
+struct OrderFArgs {
+    const float* sim;        // [.][in_stride]
+    const uint64_t* ids;     // [.][in_stride]
+    const uint32_t* counts;  // [.]
+    const uint32_t* live;    // one bit per node
+    uint64_t* out_ids;       // [gridDim.y][out_stride]
+    float* out_scores;
+    uint32_t* out_counts;    // [gridDim.y]
+    // a coalesced batch (qsel non-null), by output row y: the query, its top_k (0: not this kernel's) and its threshold
+    const uint32_t* qsel;
+    const uint32_t* qtop;
+    const float* qthr;
+    uint64_t n_nodes;
+    uint32_t in_stride, out_stride, top_k;
+    float threshold;
+};
+__device__ __forceinline__ bool takes_part(uint64_t id, float s, float thr, const uint32_t* __restrict__ live, uint64_t n_nodes) {
+    if (id >= n_nodes) return false;
+    return ((live[id >> 5] >> (uint32_t)(id & 31u)) & 1u) != 0u && s >= thr;
+}
+__global__ __launch_bounds__(256) void xmetric_order_filtered_kernel(OrderFArgs p) {
+    __shared__ uint64_t s_part[kRankMax / 64];  // the participants of the query, one bit per entry
+    uint32_t q = blockIdx.y, top_k = p.top_k;
+    const uint32_t o = blockIdx.y;
+    float thr = p.threshold;
+    if (p.qsel) {
+        q = p.qsel[o];
+        top_k = p.qtop[o];
+        if (top_k == 0u) return;  // (the whole workgroup)
+        thr = p.qthr[o];
+    }
+    const uint32_t count = min(min(p.counts[q], p.in_stride), kRankMax);
+    const float* s = p.sim + (size_t)q * p.in_stride;
+    const uint64_t* ids = p.ids + (size_t)q * p.in_stride;
+    uint64_t* o_ids = p.out_ids + (size_t)o * p.out_stride;
+    float* o_sc = p.out_scores + (size_t)o * p.out_stride;
+    for (uint32_t base = 0; base < count; base += 256u) {  // (uniform: every wave casts every ballot)
+        const uint32_t e = base + threadIdx.x;
+        const bool part = e < count && takes_part(ids[e], s[e], thr, p.live, p.n_nodes);
+        const uint64_t b = __ballot(part);
+        if ((threadIdx.x & 63u) == 0u) s_part[(base >> 6) + (threadIdx.x >> 6)] = b;
+    }
+    __syncthreads();
+    const uint32_t words = ((count + 255u) >> 8) << 2;
+    uint32_t n_part = 0;
+    for (uint32_t w = 0; w < words; w++) n_part += (uint32_t)__popcll(s_part[w]);
+    const uint32_t stride = gridDim.x * 256u;
+    for (uint32_t e = blockIdx.x * 256u + threadIdx.x; e < count; e += stride) {
+        if (((s_part[e >> 6] >> (e & 63u)) & 1ull) == 0ull) continue;
+        const float se = s[e];
+        uint32_t rank = 0;
+        for (uint32_t w = 0; w < words; w++) {
+            uint64_t m = s_part[w];
+            while (m) {
+                const uint32_t j = (w << 6) + (uint32_t)__ffsll((unsigned long long)m) - 1u;
+                m &= m - 1ull;
+                rank += ranks_before(s[j], j, se, e) ? 1u : 0u;
+            }
+        }
+        if (rank < top_k) {
+            o_ids[rank] = ids[e];
+            o_sc[rank] = se;
+        }
+    }
+    const uint32_t n_out = min(n_part, top_k);
+    for (uint32_t i = n_out + blockIdx.x * 256u + threadIdx.x; i < p.out_stride; i += stride) {
+        o_ids[i] = ~0ull;
+        o_sc[i] = __int_as_float(0xFF800000u);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) p.out_counts[o] = n_out;
+}
+
 // ---- more candidates than the rank count should order: the large-k sort (nmn_sortk.hip) --------------------------------------
 // Its composite keys order by (score descending with -0.0 == +0.0, NaN last, position ascending): the same permutation as
 // ranks_before, for one query per call.
-constexpr uint32_t kRankMax = 16384;  // c x c comparisons a query up to here
 uint32_t sort_from() {  // NMN_XMETRIC_SORT_FROM=<c>: the sort orders every call with more than c candidates (A/B runs, same bits);
                         // read once per call, by xmetric_order_scratch_bytes — the launcher follows what that returned
     const char* e = getenv("NMN_XMETRIC_SORT_FROM");
@@ -368,6 +596,18 @@ __global__ __launch_bounds__(256) void xmetric_sort_prep_kernel(const float* __r
     for (uint32_t e = blockIdx.x * 256u + threadIdx.x; e < c; e += gridDim.x * 256u) {
         const float v = sim[e];
         bits[e] = e < count ? (v != v ? 0x7FC00000u : f2u(v)) : kScoreSentinelBits;
+    }
+}
+// The same for the filtered ordering: an entry that does not take part is the sentinel, so the sort's own count (the keys before the
+// first sentinel, reduced on the device) is the number of participants.  (A participant's score is never NaN.)
+__global__ __launch_bounds__(256) void xmetric_sort_prep_filtered_kernel(const float* __restrict__ sim, const uint64_t* __restrict__ ids,
+                                                                         const uint32_t* __restrict__ count_q, uint32_t c,
+                                                                         const uint32_t* __restrict__ live, uint64_t n_nodes, float thr,
+                                                                         uint32_t* __restrict__ bits) {
+    const uint32_t count = min(*count_q, c);
+    for (uint32_t e = blockIdx.x * 256u + threadIdx.x; e < c; e += gridDim.x * 256u) {
+        const float v = sim[e];
+        bits[e] = e < count && takes_part(ids[e], v, thr, live, n_nodes) ? f2u(v) : kScoreSentinelBits;
     }
 }
 __global__ __launch_bounds__(256) void xmetric_sort_gather_kernel(const uint64_t* __restrict__ pos, const float* __restrict__ sim,
@@ -413,16 +653,39 @@ hipError_t launch_rerank(const RerankArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
+template <int CH>
+void launch_merge_ch(const dim3& grid, hipStream_t s, const MergeArgs& a) {
+    hipLaunchKernelGGL(xmetric_merge_kernel<CH>, grid, dim3(256), 0, s, a);
+}
+hipError_t launch_merge(int family, uint32_t c, uint32_t rows, const MergeArgs& a, hipStream_t s) {
+    if (rows == 0 || c == 0) return hipSuccess;
+    const dim3 grid((c + 255u) / 256u, rows);
+    switch (family) {
+        case kChCos: launch_merge_ch<kChCos>(grid, s, a); break;
+        case kChSet: launch_merge_ch<kChSet>(grid, s, a); break;
+        case kChWJ: launch_merge_ch<kChWJ>(grid, s, a); break;
+        case kChEucl: launch_merge_ch<kChEucl>(grid, s, a); break;
+        case kChManh: launch_merge_ch<kChManh>(grid, s, a); break;
+        default: launch_merge_ch<kChComposite>(grid, s, a); break;
+    }
+    return hipGetLastError();
+}
+// the filtered ordering keeps its participants in LDS, kRankMax bits: above that the sort, whatever NMN_XMETRIC_SORT_FROM says
+uint32_t sort_from_filtered(uint32_t from) { return std::min(from, kRankMax); }
+
 }  // namespace
 
-size_t xmetric_order_scratch_bytes(uint32_t c, uint32_t top_k) { return c > sort_from() ? sort_scratch(nullptr, c, top_k).bytes : 0; }
+size_t xmetric_order_scratch_bytes(uint32_t c, uint32_t top_k, bool filtered) {
+    const uint32_t from = filtered ? sort_from_filtered(sort_from()) : sort_from();
+    return c > from ? sort_scratch(nullptr, c, top_k).bytes : 0;
+}
 
 bool xmetric_valid(const nmn_xmetric* m) { return m && m->kind >= NMN_XMETRIC_COSINE && m->kind <= NMN_XMETRIC_COMPOSITE; }
 
 hipError_t launch_xmetric_rerank(const float* rows, uint32_t ld, uint32_t dim, uint64_t n_rows, const float* queries, uint32_t nq,
                                  uint32_t c, const uint64_t* cand_ids, const uint32_t* cand_counts, const nmn_xmetric& m,
                                  uint32_t top_k, float* sim, uint64_t* out_ids, float* out_scores, uint32_t* out_counts,
-                                 void* order_scratch, hipStream_t s) {
+                                 void* order_scratch, hipStream_t s, const XmetricFilter* filter) {
     if (nq == 0) return hipSuccess;
     RerankArgs a{};
     a.rows = rows;
@@ -443,6 +706,60 @@ hipError_t launch_xmetric_rerank(const float* rows, uint32_t ld, uint32_t dim, u
     a.mw = m.magnitude_weight;
     hipError_t e = launch_rerank(a, s);
     if (e != hipSuccess) return e;
+    if (filter) {  // docs/hnsw.md §16: the merge re-rank over the slots that are its own, then the filtered ordering
+        if (filter->nrec || filter->q_use) {
+            MergeArgs g{};
+            g.rows = rows;
+            g.queries = queries;
+            g.nrec = filter->nrec;
+            g.nent = filter->nent;
+            g.q_off = filter->q_off;
+            g.q_ent = filter->q_ent;
+            g.q_use = filter->q_use;
+            g.ids = cand_ids;
+            g.counts = cand_counts;
+            g.sim = sim;
+            g.n_rows = n_rows;
+            g.ld = ld;
+            g.dim = dim;
+            g.stride = c;
+            g.kind = m.kind;
+            g.cw = m.cosine_weight;
+            g.sw = m.structural_weight;
+            g.mw = m.magnitude_weight;
+            if ((e = launch_merge(chains_of(m.kind), c, nq, g, s)) != hipSuccess) return e;
+        }
+        if (order_scratch) {  // (xmetric_order_scratch_bytes(c, top_k, true) said so)
+            const SortScratch w = sort_scratch(order_scratch, c, top_k);
+            const uint32_t gc = std::min<uint32_t>((c + 255u) / 256u, 4096u), gk = std::min<uint32_t>((top_k + 255u) / 256u, 4096u);
+            for (uint32_t q = 0; q < nq; q++) {
+                const float* sim_q = sim + (size_t)q * c;
+                const uint64_t* ids_q = cand_ids + (size_t)q * c;
+                hipLaunchKernelGGL(xmetric_sort_prep_filtered_kernel, dim3(gc), dim3(256), 0, s, sim_q, ids_q, cand_counts + q, c,
+                                   filter->live, n_rows, filter->threshold, w.bits);
+                e = launch_largek(w.bits, c, w.keys, top_k, 0, w.pos, w.scores, out_counts + q, s);
+                if (e != hipSuccess) return e;
+                hipLaunchKernelGGL(xmetric_sort_gather_kernel, dim3(gk), dim3(256), 0, s, w.pos, sim_q, ids_q, c, top_k,
+                                   out_ids + (size_t)q * top_k, out_scores + (size_t)q * top_k);
+            }
+            return hipGetLastError();
+        }
+        OrderFArgs o{};
+        o.sim = sim;
+        o.ids = cand_ids;
+        o.counts = cand_counts;
+        o.live = filter->live;
+        o.out_ids = out_ids;
+        o.out_scores = out_scores;
+        o.out_counts = out_counts;
+        o.n_nodes = n_rows;
+        o.in_stride = c;
+        o.out_stride = o.top_k = top_k;
+        o.threshold = filter->threshold;
+        const uint32_t gx = std::max<uint32_t>(1, std::min<uint32_t>((std::max(c, top_k) + 255u) / 256u, 1024u));
+        hipLaunchKernelGGL(xmetric_order_filtered_kernel, dim3(gx, nq), dim3(256), 0, s, o);
+        return hipGetLastError();
+    }
     if (order_scratch) {  // query by query through the large-k sort (the caller's xmetric_order_scratch_bytes said so)
         const SortScratch w = sort_scratch(order_scratch, c, top_k);
         const uint32_t gc = std::min<uint32_t>((c + 255u) / 256u, 4096u), gk = std::min<uint32_t>((top_k + 255u) / 256u, 4096u);
@@ -464,18 +781,24 @@ hipError_t launch_xmetric_rerank(const float* rows, uint32_t ld, uint32_t dim, u
 
 // ---- a coalesced batch: a top_k and a metric per query (docs/hnsw.md §12) ------------------------------------------------------------
 // meta (u32 words, host staging and device copy alike): msel[M] | qtop[M] | fsel[M] | kind[N] | cw[N] | sw[N] | mw[N] — msel: the
-// metric queries in output-row order, qtop: their top_k (0: ordered by the sort), fsel: the same queries grouped by chain family.
+// metric queries in output-row order, qtop: their top_k (0: ordered by the sort, or a cache query), fsel: the same queries grouped by
+// chain family.
 void xmetric_batch_plan(const XmetricBatchItem* items, uint32_t M, uint32_t N, std::vector<uint32_t>& meta, XmetricBatchPlan& plan) {
     plan = XmetricBatchPlan{};
     plan.items = items;
     plan.N = N;
     plan.M = M;
-    meta.assign((size_t)3 * M + (size_t)4 * N, 0u);
+    meta.assign((size_t)5 * M + (size_t)5 * N, 0u);
     uint32_t* msel = meta.data();
     uint32_t* qtop = msel + M;
     uint32_t* fsel = qtop + M;
     uint32_t* kind = fsel + M;
     uint32_t* w[3] = {kind + N, kind + 2 * (size_t)N, kind + 3 * (size_t)N};
+    // ... and behind them, for the cache queries (§16): ftop[M] | fthr[M] | qflt[N] — the filtered ordering's top_k (0: not a cache
+    // query, or the sort's) and threshold by output row, and by query whether it is a cache query
+    uint32_t* ftop = kind + 4 * (size_t)N;
+    uint32_t* fthr = ftop + M;
+    uint32_t* qflt = fthr + M;
     const uint32_t from = plan.sort_from = sort_from();  // read once per batch; the launcher follows the plan
     uint32_t fam_n[kChComposite + 1] = {};
     for (uint32_t m = 0; m < M; m++) fam_n[chains_of(items[m].m.kind)]++;
@@ -485,9 +808,15 @@ void xmetric_batch_plan(const XmetricBatchItem* items, uint32_t M, uint32_t N, s
     for (uint32_t m = 0; m < M; m++) {
         const XmetricBatchItem& it = items[m];
         const int f = chains_of(it.m.kind);
-        const bool sorted = it.c > from;
+        const bool sorted = it.c > (it.filter ? sort_from_filtered(from) : from);
         msel[m] = it.q;
-        qtop[m] = sorted ? 0u : it.top_k;
+        qtop[m] = sorted || it.filter ? 0u : it.top_k;
+        if (it.filter) {
+            ftop[m] = sorted ? 0u : it.top_k;
+            memcpy(&fthr[m], &it.threshold, 4);
+            qflt[it.q] = 1u;
+            plan.fam_fc[f] = std::max(plan.fam_fc[f], it.c);
+        }
         fsel[fill[f]++] = it.q;
         plan.fam_c[f] = std::max(plan.fam_c[f], it.c);
         kind[it.q] = (uint32_t)it.m.kind;
@@ -496,6 +825,8 @@ void xmetric_batch_plan(const XmetricBatchItem* items, uint32_t M, uint32_t N, s
         memcpy(&w[2][it.q], &it.m.magnitude_weight, 4);
         if (sorted)
             plan.sort_bytes = std::max(plan.sort_bytes, sort_scratch(nullptr, it.c, it.top_k).bytes);
+        else if (it.filter)
+            plan.frank_len = std::max(plan.frank_len, std::max(it.c, it.top_k));
         else
             plan.rank_len = std::max(plan.rank_len, std::max(it.c, it.top_k));
     }
@@ -505,7 +836,7 @@ hipError_t launch_xmetric_rerank_batch(const float* rows, uint32_t ld, uint32_t 
                                        uint32_t kstride, const uint64_t* cand_ids, const uint32_t* cand_counts,
                                        const XmetricBatchPlan& plan, const uint32_t* meta_dev, float* sim, uint32_t out_stride,
                                        uint64_t* out_ids, float* out_scores, uint32_t* out_counts, void* sort_scratch_dev,
-                                       hipStream_t s) {
+                                       hipStream_t s, const XmetricFilter* filter) {
     const uint32_t M = plan.M, N = plan.N;
     if (M == 0) return hipSuccess;
     const uint32_t* msel = meta_dev;
@@ -543,6 +874,55 @@ hipError_t launch_xmetric_rerank_batch(const float* rows, uint32_t ld, uint32_t 
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
+    const uint32_t* ftop = fsel + M + 4 * (size_t)N;
+    const float* fthr = reinterpret_cast<const float*>(ftop + M);
+    const uint32_t* qflt = ftop + 2 * (size_t)M;
+    if (filter && filter->nrec) {  // the cache queries' Sparse-node candidates, family by family like the dense re-rank before them
+        MergeArgs g{};
+        g.rows = rows;
+        g.queries = queries;
+        g.nrec = filter->nrec;
+        g.nent = filter->nent;
+        g.ids = cand_ids;
+        g.counts = cand_counts;
+        g.sim = sim;
+        g.qflt = qflt;
+        g.qkind = a.qkind;
+        g.qcw = a.qcw;
+        g.qsw = a.qsw;
+        g.qmw = a.qmw;
+        g.n_rows = n_rows;
+        g.ld = ld;
+        g.dim = dim;
+        g.stride = kstride;
+        for (int f = 0; f <= kChComposite; f++) {
+            if (plan.fam_fc[f] == 0) continue;
+            g.qsel = fsel + plan.fam_off[f];
+            const hipError_t e = launch_merge(f, plan.fam_fc[f], plan.fam_off[f + 1] - plan.fam_off[f], g, s);
+            if (e != hipSuccess) return e;
+        }
+    }
+    if (plan.frank_len) {  // every cache query the filtered rank count orders, in one launch
+        if (!filter) return hipErrorInvalidValue;
+        OrderFArgs o{};
+        o.sim = sim;
+        o.ids = cand_ids;
+        o.counts = cand_counts;
+        o.live = filter->live;
+        o.out_ids = out_ids;
+        o.out_scores = out_scores;
+        o.out_counts = out_counts;
+        o.qsel = msel;
+        o.qtop = ftop;
+        o.qthr = fthr;
+        o.n_nodes = n_rows;
+        o.in_stride = kstride;
+        o.out_stride = out_stride;
+        const uint32_t gx = std::max<uint32_t>(1, std::min<uint32_t>((std::max(plan.frank_len, out_stride) + 255u) / 256u, 1024u));
+        hipLaunchKernelGGL(xmetric_order_filtered_kernel, dim3(gx, M), dim3(256), 0, s, o);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
     if (plan.rank_len) {  // every query the rank count orders, in one launch (the sorted ones' workgroups leave at once)
         OrderArgsQ o{};
         o.sim = sim;
@@ -563,11 +943,16 @@ hipError_t launch_xmetric_rerank_batch(const float* rows, uint32_t ld, uint32_t 
     if (plan.sort_bytes) {  // more candidates than the rank count should order: each such query alone, exactly as in a lone call
         for (uint32_t m = 0; m < M; m++) {
             const XmetricBatchItem& it = plan.items[m];
-            if (it.c <= plan.sort_from) continue;
+            if (it.c <= (it.filter ? sort_from_filtered(plan.sort_from) : plan.sort_from)) continue;
             const SortScratch w = sort_scratch(sort_scratch_dev, it.c, it.top_k);
             const uint32_t gc = std::min<uint32_t>((it.c + 255u) / 256u, 4096u), gk = std::min<uint32_t>((it.top_k + 255u) / 256u, 4096u);
             const float* sim_q = sim + (size_t)it.q * kstride;
-            hipLaunchKernelGGL(xmetric_sort_prep_kernel, dim3(gc), dim3(256), 0, s, sim_q, cand_counts + it.q, it.c, w.bits);
+            if (it.filter) {
+                if (!filter) return hipErrorInvalidValue;
+                hipLaunchKernelGGL(xmetric_sort_prep_filtered_kernel, dim3(gc), dim3(256), 0, s, sim_q, cand_ids + (size_t)it.q * kstride,
+                                   cand_counts + it.q, it.c, filter->live, n_rows, it.threshold, w.bits);
+            } else
+                hipLaunchKernelGGL(xmetric_sort_prep_kernel, dim3(gc), dim3(256), 0, s, sim_q, cand_counts + it.q, it.c, w.bits);
             const hipError_t e = launch_largek(w.bits, it.c, w.keys, it.top_k, 0, w.pos, w.scores, out_counts + m, s);
             if (e != hipSuccess) return e;
             hipLaunchKernelGGL(xmetric_sort_gather_kernel, dim3(gk), dim3(256), 0, s, w.pos, sim_q, cand_ids + (size_t)it.q * kstride, it.c,

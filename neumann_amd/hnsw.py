@@ -493,3 +493,83 @@ class GpuHnsw:
             self._h, C.c_void_p(queries_t.data_ptr()), nq, k, C.byref(m), C.c_void_p(ids.data_ptr()), C.c_void_p(sc.data_ptr()),
             C.c_void_p(counts.data_ptr()), _stream_ptr(stream)))
         return ids, sc, counts
+
+    def set_node_mask(self, nodes, live):
+        """nmn_hnsw_set_node_mask: set (`live` true) or clear the live bits of `nodes`.  A new node is live; only `cache_search*`
+        read the mask, and `save` does not store it."""
+        nn = np.ascontiguousarray(nodes, dtype=np.uint64).reshape(-1)
+        _capi.check(self._lib.nmn_hnsw_set_node_mask(self._h, C.c_void_p(nn.ctypes.data), nn.size, 1 if live else 0))
+
+    def node_live(self, node):
+        """the node's live bit (nmn_hnsw_node_live); None for a node the index does not hold"""
+        r = int(self._lib.nmn_hnsw_node_live(self._h, int(node)))
+        return None if r < 0 else bool(r)
+
+    def cache_search(self, queries, k, threshold, metric, with_stats=False):
+        """CacheIndex::search_with_metric's steps per query with node ids in place of keys (nmn_hnsw_cache_search; docs/hnsw.md
+        §16): c = max(3k, 10) candidates from the walk, dead nodes dropped, every other re-scored under `metric` on its stored form
+        (a Sparse node by its own entries), kept iff similarity >= threshold, the first k of the stable descending order.
+        -> (ids u64 [nq,k], similarities f32 [nq,k], counts u32 [nq])"""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.shape[1] != self.dim:
+            raise _capi.NeumannGpuError(_capi.ERR_DIMENSION_MISMATCH, f"expected {self.dim}, got {q.shape[1]}")
+        nq, k = q.shape[0], int(k)
+        ids = np.empty((nq, max(k, 1)), dtype=np.uint64)
+        sc = np.empty((nq, max(k, 1)), dtype=np.float32)
+        counts = np.empty(nq, dtype=np.uint32)
+        st = _capi.SearchStats()
+        m = metric._c()
+        _capi.check(self._lib.nmn_hnsw_cache_search(self._h, C.c_void_p(q.ctypes.data), nq, k, float(threshold), C.byref(m),
+                                                    C.c_void_p(ids.ctypes.data), C.c_void_p(sc.ctypes.data),
+                                                    C.c_void_p(counts.ctypes.data), C.byref(st)))
+        return (ids, sc, counts, st) if with_stats else (ids, sc, counts)
+
+    def cache_search_sparse(self, indptr, positions, values, k, threshold, metric, with_stats=False):
+        """CacheIndex::search_sparse_with_metric per query (nmn_hnsw_cache_search_sparse): `cache_search` behind
+        `search_sparse`'s walk, the query's own entries scored.  The CSR is `search_sparse`'s.
+        -> (ids u64 [nq,k], similarities f32 [nq,k], counts u32 [nq])"""
+        ip = np.ascontiguousarray(indptr, dtype=np.uint64).reshape(-1)
+        pos = np.ascontiguousarray(positions, dtype=np.uint32).reshape(-1)
+        val = np.ascontiguousarray(values, dtype=np.float32).reshape(-1)
+        if ip.size == 0 or pos.size != val.size or (ip.size and int(ip.max()) > pos.size):
+            raise _capi.NeumannGpuError(_capi.ERR_INVALID_ARGUMENT, "indptr [nq + 1] into positions / values of one length")
+        nq, k = ip.size - 1, int(k)
+        ids = np.empty((nq, max(k, 1)), dtype=np.uint64)
+        sc = np.empty((nq, max(k, 1)), dtype=np.float32)
+        counts = np.empty(nq, dtype=np.uint32)
+        st = _capi.SearchStats()
+        m = metric._c()
+        _capi.check(self._lib.nmn_hnsw_cache_search_sparse(self._h, C.c_void_p(ip.ctypes.data), C.c_void_p(pos.ctypes.data),
+                                                           C.c_void_p(val.ctypes.data), nq, k, float(threshold), C.byref(m),
+                                                           C.c_void_p(ids.ctypes.data), C.c_void_p(sc.ctypes.data),
+                                                           C.c_void_p(counts.ctypes.data), C.byref(st)))
+        return (ids, sc, counts, st) if with_stats else (ids, sc, counts)
+
+    def cache_search_device(self, queries_t, k, threshold, metric, out=None, stream=None):
+        """`cache_search` with torch device tensors, in stream order (nmn_hnsw_cache_search_device); same conventions as
+        `search_device`."""
+        import torch
+
+        if not (isinstance(queries_t, torch.Tensor) and queries_t.is_cuda):
+            raise _capi.NeumannGpuError(_capi.ERR_INVALID_ARGUMENT, "queries must be a device tensor")
+        if queries_t.dtype != torch.float32 or not queries_t.is_contiguous():
+            raise _capi.NeumannGpuError(_capi.ERR_INVALID_ARGUMENT, "queries must be contiguous float32")
+        if queries_t.dim() == 1:
+            queries_t = queries_t[None, :]
+        nq, k = queries_t.shape[0], int(k)
+        if queries_t.shape[1] != self.dim:
+            raise _capi.NeumannGpuError(_capi.ERR_DIMENSION_MISMATCH, f"expected {self.dim}")
+        if out is None:
+            kk = max(k, 1)
+            ids = torch.empty((nq, kk), dtype=torch.int64, device=queries_t.device)
+            sc = torch.empty((nq, kk), dtype=torch.float32, device=queries_t.device)
+            counts = torch.empty((nq,), dtype=torch.int32, device=queries_t.device)
+        else:
+            ids, sc, counts = out
+        m = metric._c()
+        _capi.check(self._lib.nmn_hnsw_cache_search_device(
+            self._h, C.c_void_p(queries_t.data_ptr()), nq, k, float(threshold), C.byref(m), C.c_void_p(ids.data_ptr()),
+            C.c_void_p(sc.data_ptr()), C.c_void_p(counts.data_ptr()), _stream_ptr(stream)))
+        return ids, sc, counts

@@ -67,7 +67,13 @@ of the dimension stored), k taken in turn from 1, 10, 50, 100.  The run alternat
 the same build with NMN_HNSW_NO_COALESCE=1, where sparse callers take turns on the handle — what they did before they joined the
 coalescer.  Every leg is a fresh child process (this script again, with --sparse-leg) under its own time limit (--leg-timeout
 seconds); with --index-file the first leg builds and saves the index and every other leg loads it.  One JSON line per leg (queries_per_s,
-call_ms_median, merged batches and calls from nmn_hnsw_coalesce_stats), then one line with the medians and spreads of both legs."""
+call_ms_median, merged batches and calls from nmn_hnsw_coalesce_stats), then one line with the medians and spreads of both legs.
+
+  python tools/hnsw_bench.py --rows 200000 --dim 128 --cache-callers 64,128 [--cache-metric cosine] --index-file PATH
+--cache-callers times CONCURRENT semantic-cache lookups (docs/hnsw.md §16): for every T of the list, T threads behind a barrier, each
+making --caller-calls calls of nmn_hnsw_cache_search with ONE query, k = 1 and threshold 0.9 under --cache-metric — the call
+CacheIndex::search_with_metric makes for every lookup.  The legs are --sparse-callers': this build, and this build under
+NMN_HNSW_NO_COALESCE=1, alternating, each a fresh child process (this script again, with --cache-leg) under --leg-timeout."""
 import argparse
 import json
 import os
@@ -191,10 +197,10 @@ def time_storage(gq, gd, Q, qd, k, s, args, metric):
     return out
 
 
-def time_callers(g, Q, counts, args, xmetric=None, sparse=None):
+def time_callers(g, Q, counts, args, xmetric=None, sparse=None, cache=None):
     """N threads, each calling g.search(one query, its k) --caller-calls times — with `xmetric`, g.search_metric(one query, its top_k,
-    xmetric); with `sparse` (one CSR per query of Q), g.search_sparse(that query, its k) —: throughput, a caller's median, the
-    coalescer's counts"""
+    xmetric); with `sparse` (one CSR per query of Q), g.search_sparse(that query, its k); with `cache` (an ExtendedDistanceMetric),
+    g.cache_search(one query, 1, 0.9, cache) —: throughput, a caller's median, the coalescer's counts"""
     import threading
     ks = (1, 10, 50, 100)
     has_stats = hasattr(g._lib, "nmn_hnsw_coalesce_stats")  # (an older build has no coalescer)
@@ -213,7 +219,9 @@ def time_callers(g, Q, counts, args, xmetric=None, sparse=None):
                     for j in range(per):
                         q = Q[(t * per + j) % len(Q)]
                         t0 = time.perf_counter()
-                        if sparse is not None:
+                        if cache is not None:
+                            g.cache_search(q, 1, 0.9, cache)
+                        elif sparse is not None:
                             g.search_sparse(*sparse[(t * per + j) % len(Q)], ks[(t + j) % len(ks)])
                         elif xmetric is not None:
                             g.search_metric(q, ks[(t + j) % len(ks)], xmetric)
@@ -252,10 +260,11 @@ def time_callers(g, Q, counts, args, xmetric=None, sparse=None):
     return out
 
 
-def sparse_caller_legs(args):
-    """--sparse-callers: the two legs alternating, each a fresh child process with its own time limit; this process opens no GPU"""
+def sparse_caller_legs(args, flag="--sparse-leg"):
+    """--sparse-callers / --cache-callers: the two legs alternating, each a fresh child process with its own time limit; this process
+    opens no GPU"""
     import subprocess
-    argv = [sys.executable, os.path.abspath(__file__), "--sparse-leg"] + [a for a in sys.argv[1:] if a != "--sparse-leg"]
+    argv = [sys.executable, os.path.abspath(__file__), flag] + [a for a in sys.argv[1:] if a != flag]
     legs = {"coalesce": [], "no_coalesce": []}
     for _ in range(args.repeats):
         for leg in legs:
@@ -488,6 +497,11 @@ def main():
     ap.add_argument("--sparse-fraction", type=float, default=0.8, help="--sparse-callers: the share of every query's entries that is zeroed")
     ap.add_argument("--leg-timeout", type=float, default=900.0, help="--sparse-callers: seconds a leg's child process may take")
     ap.add_argument("--sparse-leg", action="store_true", help="(one leg of --sparse-callers, in this process)")
+    ap.add_argument("--cache-callers", default=None,
+                    help="e.g. 64,128: that many concurrent nmn_hnsw_cache_search callers (one query, k = 1, threshold 0.9), with and "
+                         "without NMN_HNSW_NO_COALESCE=1, each leg a fresh child process (docs/hnsw.md §16)")
+    ap.add_argument("--cache-metric", default="cosine", help="--cache-callers: the ExtendedDistanceMetric of the re-rank, by name")
+    ap.add_argument("--cache-leg", action="store_true", help="(one leg of --cache-callers, in this process)")
     ap.add_argument("--sparse-node-fraction", type=float, default=None,
                     help="insert this share of the rows Sparse (nmn_hnsw_insert_sparse) and time search_device / search_sparse of the "
                          "mixed handle beside an all-dense handle over the to_dense() rows (docs/hnsw.md §15)")
@@ -496,6 +510,9 @@ def main():
     args = ap.parse_args()
     if args.sparse_callers and not args.sparse_leg:
         sparse_caller_legs(args)
+        return
+    if args.cache_callers and not args.cache_leg:
+        sparse_caller_legs(args, "--cache-leg")
         return
     if args.callers:  # an older build through NEUMANN_GPU_LIB: entries it lacks stay unbound instead of failing the load
         import ctypes
@@ -525,6 +542,15 @@ def main():
             if xmetric is not None:
                 out["xmetric"] = xmetric.name
             out.update(time_callers(g, Q, [int(x) for x in args.callers.split(",")], args, xmetric))
+        print(json.dumps(out), flush=True)
+        return
+    if args.cache_callers:  # one leg: repeats are the parent's, so one timed pass behind the warming one
+        cache_metric = ExtendedDistanceMetric.from_name(args.cache_metric)
+        out.update({"storage": "dense", "no_coalesce": bool(os.environ.get("NMN_HNSW_NO_COALESCE")), "caller_calls": args.caller_calls,
+                    "cache_metric": cache_metric.name, "k": 1, "threshold": 0.9})
+        args.repeats = 1
+        with build_or_load(args.index_file, n, d, cfg, "dense", out) as g:
+            out.update(time_callers(g, Q, [int(x) for x in args.cache_callers.split(",")], args, cache=cache_metric))
         print(json.dumps(out), flush=True)
         return
     if args.sparse_callers:  # one leg: repeats are the parent's, so one timed pass behind the warming one

@@ -9,7 +9,9 @@
 // candidate limit) is a batch of one; every call is served exactly once, with its own answer (out_counts[i] = a function of the
 // call's own k and query), also when a batch fails — then every call of that batch gets the status and the text.  About one call in
 // five is a sparse one: HostWalk::sp set and q null, as nmn_hnsw_search_sparse[_multi] submit them; the stand-in batch reads such a
-// call's queries through sp and requires q to be null, and sparse and dense calls share batches.
+// call's queries through sp and requires q to be null, and sparse and dense calls share batches.  About one call in ten is a cache
+// call (docs/hnsw.md §16): HostWalk::xm, filter and threshold set as nmn_hnsw_cache_search submits them; the stand-in batch requires
+// the flag to come with a metric and dense queries, and checks that the threshold it reads is the one the caller wrote for that call.
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -26,7 +28,7 @@ struct nmn::SparseQueries {
 using namespace nmn;
 
 static std::atomic<int> running{0};
-static std::atomic<uint64_t> batches_run{0}, calls_served{0}, failed_batches{0}, alone_served{0}, sparse_served{0}, mixed_batches{0};
+static std::atomic<uint64_t> batches_run{0}, calls_served{0}, failed_batches{0}, alone_served{0}, sparse_served{0}, mixed_batches{0}, cache_served{0}, cache_mixed{0};
 static thread_local std::string tl_error;
 
 #define REQUIRE(c)                                                   \
@@ -56,6 +58,15 @@ static nmn_status fake_batch(const std::vector<HostWalk*>& batch) {
         }
     }
     sparse_served += sparse_here;
+    size_t cache_here = 0;
+    for (const HostWalk* r : batch) {
+        if (!r->filter) continue;
+        REQUIRE(r->xm && r->q && !r->sp);                              // a cache call is a metric call with dense queries
+        REQUIRE(r->threshold == 0.5f + (float)((uint32_t)r->q[0] % 7));  // ... and carries its own threshold
+        cache_here++;
+    }
+    cache_served += cache_here;
+    if (cache_here && cache_here < batch.size()) cache_mixed++;
     if (sparse_here && sparse_here < batch.size()) mixed_batches++;
     const uint64_t b = batches_run.fetch_add(1);
     nmn_status st = NMN_OK;
@@ -98,6 +109,12 @@ int main() {
                 } else {
                     me.q = query.data();
                 }
+                const nmn_xmetric cosine{NMN_XMETRIC_COSINE, 0.0f, 0.0f, 0.0f};
+                if (!me.sp && (t * 5 + c) % 10 == 4) {  // a cache call: a metric, the filter flag and a threshold of its own
+                    me.xm = &cosine;
+                    me.filter = true;
+                    me.threshold = 0.5f + (float)((uint32_t)query[0] % 7);
+                }
                 me.nq = nq;
                 me.k = k.data();
                 me.kstride = 200;
@@ -129,6 +146,12 @@ int main() {
     for (int t = 0; t < threads; t++)
         for (int c = 0; c < calls; c++) sparse_made += (t * 3 + c) % 5 == 1 ? 1 : 0;
     REQUIRE(sparse_made > 0 && sparse_served.load() == sparse_made && mixed_batches.load() > 0);
+    uint64_t cache_made = 0;
+    for (int t = 0; t < threads; t++)
+        for (int c = 0; c < calls; c++) cache_made += ((t * 3 + c) % 5 != 1 && (t * 5 + c) % 10 == 4) ? 1 : 0;
+    REQUIRE(cache_made > 0 && cache_served.load() == cache_made && cache_mixed.load() > 0);
+    printf("hnsw_queue_mt cache calls: %llu, in %llu batches with other kinds of call\n", (unsigned long long)cache_made,
+           (unsigned long long)cache_mixed.load());
     printf("hnsw_queue_mt ok: %llu calls in %llu batches (%llu merged batches carrying %llu calls, %llu calls alone, %llu sparse calls, %llu batches mixing sparse and dense calls), %llu failed batches, %llu failed calls\n",
            (unsigned long long)calls_served.load(), (unsigned long long)batches_run.load(), (unsigned long long)q.batches,
            (unsigned long long)q.calls, (unsigned long long)alone_served.load(), (unsigned long long)sparse_served.load(),
