@@ -761,6 +761,54 @@ nmn_status nmn_hnsw_memory_stats(nmn_hnsw* h, nmn_hnsw_memstats* out);
 /* The handle's HNSWConfig; `storage` = the handle's strategy (nmn_hnsw_storage), `reserved` 0.  What nmn_hnsw_load read from a file. */
 nmn_status nmn_hnsw_get_config(const nmn_hnsw* h, nmn_hnsw_config* out);
 
+/* ---- tensor-train vectors: TT queries and insert_tt_vector (docs/hnsw.md §17) ----------------------------------------- */
+
+/* A TTVector (tensor_compress/src/tensor_train.rs:267-281) crosses this interface as its parts.  One call carries nq trains of
+ * ONE shape: shape[n_cores], ranks [nq][n_cores + 1] (a row per train), and one flat `cores` array into which core_off[nq + 1]
+ * indexes: train q is cores[core_off[q] .. core_off[q + 1]), its cores back to back, core k being ranks[k] x shape[k] x ranks[k + 1]
+ * floats, row-major, as TTCore::get indexes them (tensor_train.rs:240-243).  A train is well formed when n_cores is in 1..8, every
+ * shape[k] >= 1, every rank >= 1, ranks[0] == ranks[n_cores] == 1, and core_off[q + 1] - core_off[q] is the sum of the core sizes;
+ * the product of the shape (2^31 at most) is the vector's dimension.  Anything else is NMN_ERR_INVALID_ARGUMENT before anything is
+ * enqueued or written, the text naming the query and the rule (the reference's panics and ignored tails are not restated).
+ *
+ * nmn_tt_reconstruct: out_rows[nq][dim] = tt_reconstruct (tensor_train.rs:401-436) of every train, bit for bit.
+ * nmn_tt_norm: out_norms[nq] = tt_norm (440-474), the raw norm, bit for bit.
+ * HOST buffers, synchronous, stateless, on the current device: one launch, a workgroup per train with everything in LDS.  A train
+ * above the LDS limits (nmn_tt_limits: a rank above max_rank, more than max_storage core floats, or an intermediate level
+ * shape[0] .. shape[k] x ranks[k + 1] above max_level floats) is prepared by the host restatement of the same loops, same bits;
+ * NMN_HNSW_HOST_SEARCH=1 sends every train there. */
+nmn_status nmn_tt_reconstruct(const uint32_t* shape, uint32_t n_cores, const uint32_t* ranks, const uint64_t* core_off,
+                              const float* cores, uint32_t nq, float* out_rows);
+nmn_status nmn_tt_norm(const uint32_t* shape, uint32_t n_cores, const uint32_t* ranks, const uint64_t* core_off, const float* cores,
+                       uint32_t nq, float* out_norms);
+nmn_status nmn_tt_limits(uint32_t* max_cores, uint32_t* max_rank, uint32_t* max_storage, uint32_t* max_level); /* each nullable */
+
+/* HNSWIndex::search_tt_with_ef (hnsw.rs:1811-1841) per train: query_norm = tt_norm once, then search_layer_greedy_tt (2238-2272)
+ * and search_layer_tt_native (1845-1903) with cosine_distance_tt_with_norm (1196-1221) — on a Dense, Sparse or Quantized node
+ * 1 - dot_with_tt / (magnitude() * query_norm) with the query reconstructed (919-948), 1.0 when query_norm < 1e-10 or the node's
+ * magnitude is 0.  The metric is Cosine WHATEVER the handle's distance_metric is, and the score is 1 - distance.  The trains are
+ * prepared on the GPU (nmn_tt_reconstruct's kernel, one launch for the call) and walked by the kernel of nmn_hnsw_search with the
+ * query's magnitude given.  The product of the shape must be nmn_hnsw_dim(h) (NMN_ERR_DIMENSION_MISMATCH).  HOST buffers,
+ * synchronous; outputs, sentinels, ef == 0, k == 0 and the empty index are nmn_hnsw_search's; stats by the handle's convention.
+ * Dense handles (sparse nodes included, under every metric) and quantized handles.  Not coalesced: concurrent callers take turns.
+ * NMN_HNSW_HOST_SEARCH=1: host preparation and host walk, same bits.  A train whose norm is NaN is walked by the host. */
+nmn_status nmn_hnsw_search_tt(nmn_hnsw* h, const uint32_t* shape, uint32_t n_cores, const uint32_t* ranks, const uint64_t* core_off,
+                              const float* cores, uint32_t nq, uint32_t k, uint32_t ef, uint64_t* out_ids, float* out_scores,
+                              uint32_t* out_counts, nmn_search_stats* stats);
+/* The same with the core data, the queries and the results in DEVICE memory, enqueued on `stream` and not waited for, nothing read
+ * back (nmn_hnsw_search_device's contract).  ONE rank vector ranks[n_cores + 1] for the whole call, HOST memory, read before the
+ * call returns; cores_dev is [nq][storage], storage = the sum of the core sizes.  The preparation runs on `stream` in front of the
+ * walk, into the stream's scratch.  A train above the LDS limits is NMN_ERR_INVALID_ARGUMENT (there is no host to fall back to).
+ * A train whose norm is NaN gives NaN distances, which the heaps do not order: its row of the outputs is unspecified. */
+nmn_status nmn_hnsw_search_tt_device(nmn_hnsw* h, const uint32_t* shape, uint32_t n_cores, const uint32_t* ranks,
+                                     const float* cores_dev, uint32_t nq, uint32_t k, uint32_t ef, uint64_t* out_ids_dev,
+                                     float* out_scores_dev, uint32_t* out_counts_dev, void* stream);
+/* HNSWIndex::insert_tt_vector (hnsw.rs:1755-1759) for each of the n trains in order: the batch is reconstructed
+ * (nmn_tt_reconstruct) and takes nmn_hnsw_insert's path — Dense nodes; max_nodes, its text and the all-or-nothing batch are that
+ * entry's.  Dense handles only: a quantized handle is NMN_ERR_CONFIGURATION. */
+nmn_status nmn_hnsw_insert_tt(nmn_hnsw* h, const uint32_t* shape, uint32_t n_cores, const uint32_t* ranks, const uint64_t* core_off,
+                              const float* cores, uint64_t n, uint64_t* ids_out);
+
 /* ---- extended distance metrics: the re-rank of search_with_hnsw_and_metric ------------------------------------ */
 
 /* `tensor_store::DistanceMetric` (tensor_store/src/distance.rs:13-52), the ExtendedDistanceMetric of vector_engine.  Both

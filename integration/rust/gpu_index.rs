@@ -338,6 +338,44 @@ impl GpuHnswIndex {
         Ok(ids.into_iter().zip(scores).take(n as usize).map(|(r, s)| (r as usize, s)).collect())
     }
 
+    /// One TTVector as the C entries take it: (shape, ranks, every core's data back to back) of `tensor_compress::TTVector`.
+    fn tt_parts(tt: &tensor_compress::TTVector) -> (Vec<u32>, Vec<u32>, Vec<f32>) {
+        let shape: Vec<u32> = tt.shape.iter().map(|&n| n as u32).collect();
+        let mut ranks = vec![1u32];
+        let mut cores = Vec::new();
+        for c in &tt.cores {
+            ranks.push(c.shape.2 as u32);
+            cores.extend_from_slice(&c.data);
+        }
+        (shape, ranks, cores)
+    }
+
+    /// HNSWIndex::search_tt_with_ef (nmn_hnsw_search_tt; ef 0 = ef_search): the train is reconstructed and its norm taken on the
+    /// GPU, the walk scores under Cosine whatever the index's metric is (docs/hnsw.md §17).  (node id, 1 - distance), best first.
+    pub fn search_tt(&self, tt: &tensor_compress::TTVector, k: usize, ef: usize) -> Result<Vec<(usize, f32)>> {
+        let (shape, ranks, cores) = Self::tt_parts(tt);
+        let off = [0u64, cores.len() as u64];
+        let mut ids = vec![u64::MAX; k];
+        let mut scores = vec![f32::NEG_INFINITY; k];
+        let mut n = 0u32;
+        let st = unsafe {
+            ffi::nmn_hnsw_search_tt(self.raw, shape.as_ptr(), shape.len() as u32, ranks.as_ptr(), off.as_ptr(), cores.as_ptr(), 1, k as u32,
+                                    ef as u32, ids.as_mut_ptr(), scores.as_mut_ptr(), &mut n, std::ptr::null_mut())
+        };
+        check(st, self.dim, shape.iter().map(|&x| x as usize).product())?;
+        Ok(ids.into_iter().zip(scores).take(n as usize).map(|(r, s)| (r as usize, s)).collect())
+    }
+
+    /// HNSWIndex::insert_tt_vector (nmn_hnsw_insert_tt): reconstructed on the GPU, inserted as a Dense node.
+    pub fn insert_tt(&self, tt: &tensor_compress::TTVector) -> Result<()> {
+        let (shape, ranks, cores) = Self::tt_parts(tt);
+        let off = [0u64, cores.len() as u64];
+        let st = unsafe {
+            ffi::nmn_hnsw_insert_tt(self.raw, shape.as_ptr(), shape.len() as u32, ranks.as_ptr(), off.as_ptr(), cores.as_ptr(), 1, std::ptr::null_mut())
+        };
+        check(st, self.dim, shape.iter().map(|&x| x as usize).product())
+    }
+
     /// `search` for several queries in ONE launch, each with its own k and ef (nmn_hnsw_search_multi; ef 0 = ef_search).  Answer i is
     /// bit for bit what `search_with_ef(q_i, k_i, ef_i)` returns alone.  Concurrent callers of `search` / `search_multi` are
     /// coalesced into such launches by the library (docs/hnsw.md §11).

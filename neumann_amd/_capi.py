@@ -239,6 +239,13 @@ SIGNATURES = {
     "nmn_hnsw_get_vector": (C.c_int32, [vp, C.c_uint64, vp]),
     "nmn_hnsw_memory_stats": (C.c_int32, [vp, C.POINTER(HnswMemStats)]),
     "nmn_hnsw_get_config": (C.c_int32, [vp, C.POINTER(HnswConfig)]),
+    "nmn_tt_reconstruct": (C.c_int32, [vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp]),
+    "nmn_tt_norm": (C.c_int32, [vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp]),
+    "nmn_tt_limits": (C.c_int32, [u32p, u32p, u32p, u32p]),
+    "nmn_hnsw_search_tt": (C.c_int32, [vp, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp,
+                                       C.POINTER(SearchStats)]),
+    "nmn_hnsw_search_tt_device": (C.c_int32, [vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp]),
+    "nmn_hnsw_insert_tt": (C.c_int32, [vp, vp, C.c_uint32, vp, vp, vp, C.c_uint64, vp]),
     "nmn_xmetric_geometric_default": (None, [C.POINTER(XMetric)]),
     "nmn_xmetric_geometric_angular_heavy": (None, [C.POINTER(XMetric)]),
     "nmn_xmetric_geometric_structural_heavy": (None, [C.POINTER(XMetric)]),

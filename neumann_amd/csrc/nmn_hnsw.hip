@@ -32,6 +32,10 @@
 //       handle.  A sparse node is scored by SparseVector's own arithmetic — dot_dense / dot / magnitude / euclidean_distance /
 //       cosine_similarity / cosine_distance_dense, f64 chains over the stored entries — on the query side and on the pruning side;
 //       the host keeps a kind per node, the kernel a record per node and takes the MIX instantiations.  docs/hnsw.md §15.
+//   nmn_hnsw_search_tt / nmn_hnsw_search_tt_device (hnsw.rs:1811-1903, 2238-2272): search_tt_with_ef — the same walk with
+//       cosine_distance_tt_with_norm (1196-1221): the query reconstructed and its tt_norm taken by nmn_tt.hip, then Cosine on every
+//       handle with that norm as the query's magnitude, the kernel's kind 2.  nmn_hnsw_insert_tt: insert_tt_vector (1755-1759).
+//       docs/hnsw.md §17.
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -49,6 +53,7 @@
 #include "nmn_index.h"
 #include "nmn_internal.h"
 #include "nmn_hnsw_queue.h"
+#include "nmn_tt.h"
 
 #pragma clang fp contract(off)
 
@@ -939,6 +944,7 @@ struct nmn_hnsw {
         DevBuf vis, flags, evals, spill;
         bool xsort_use = false;  // this call's ordering goes through the large-k sort (xmetric_order_scratch_bytes != 0)
         DevBuf xids, xsc, xcnt, xsim, xsort;  // nmn_hnsw_search_metric*: the walk's nq x c candidate block, its re-rank scores, the sort's scratch
+        DevBuf ttq, ttmag, ttkind;  // nmn_hnsw_search_tt*: the reconstructed queries, their magnitudes, kind and candidate limit per query
     };
     std::vector<std::unique_ptr<Scratch>> scratch;
     std::vector<hipEvent_t> ev_pending, ev_free;
@@ -950,6 +956,7 @@ struct nmn_hnsw {
     DevBuf hq, hids, hsc, hcnt, hkef;
     DevBuf hsp_off, hsp_ent, hqmag;  // sparse slots of a batch: the launch's entry offsets, its (position, value) pairs, Q.magnitude() per query
     DevBuf hxmeta, hxsim, hxoids, hxosc, hxocnt, hxsort;  // a batch's metric slots (docs/hnsw.md §12): what their launches read and answer into
+    DevBuf htt_cores, htt_ranks, htt_off, htt_skip;  // nmn_hnsw_search_tt: the call's trains as the preparation kernel reads them
     // ... and what a batch of mixed k / ef passes through on the host (under host_mu): the queries gathered in launch order, k and ef
     // per query, the launch's rows before they are handed to their callers
     std::vector<float> st_q;
@@ -1304,7 +1311,7 @@ void host_insert_node(nmn_hnsw* h, uint32_t node_id, HostVisited& vis) {
 // search_with_ef / search_sparse_with_ef (hnsw.rs:2069-2111, 2118-2166): one walk, the distance supplied
 template <class Dist>
 void host_walk_one(const nmn_hnsw* h, const Dist& dist, uint32_t k, uint64_t ef, HostVisited& vis, uint64_t* ids, float* scores,
-                   uint32_t* count, uint64_t* evals) {
+                   uint32_t* count, uint64_t* evals, int score_metric = -1) {  // (score_metric -1: the handle's)
     uint32_t c = 0;
     if (h->entry != ~0ull) {
         uint32_t cur = (uint32_t)h->entry;
@@ -1313,7 +1320,7 @@ void host_walk_one(const nmn_hnsw* h, const Dist& dist, uint32_t k, uint64_t ef,
         host_search_layer(h, dist, cur, std::max<uint64_t>(ef, k), 0, vis, found, evals);
         for (; c < found.size() && c < k; c++) {
             ids[c] = found[c].id;
-            scores[c] = to_similarity(h->cfg.distance_metric, found[c].d);
+            scores[c] = to_similarity(score_metric < 0 ? h->cfg.distance_metric : score_metric, found[c].d);
         }
     }
     *count = c;
@@ -1693,6 +1700,8 @@ struct WalkShape {
     const uint32_t* qkinds = nullptr;
     const uint32_t* qccap = nullptr;
     bool sp_only = false;  // qkind 3: every query is kind 1, so the query region need not hold a dense query
+    // TT queries (docs/hnsw.md §17): the launch scores under Cosine whatever the handle's metric is (cosine_distance_tt_with_norm)
+    bool cosine = false;
 };
 
 uint32_t results_need(uint32_t ef_eff, uint32_t n) { return std::min<uint32_t>(ef_eff, std::max<uint32_t>(n, 1)) + 1; }
@@ -1740,7 +1749,9 @@ nmn_status enqueue_walk_locked(nmn_hnsw* h, nmn_hnsw::Scratch* sc, const float* 
     a.visited = (uint32_t*)sc->vis.p;
     a.spill = (Ent*)sc->spill.p;
     // Sparse nodes are scored by their own arithmetic under Cosine / DotProduct only (Euclidean is the dense arithmetic on the rows)
-    const bool mix = !q8 && h->n_sparse > 0 && h->cfg.distance_metric != NMN_METRIC_EUCLIDEAN;
+    const int metric = w.cosine ? NMN_METRIC_COSINE : h->cfg.distance_metric;
+    a.g.metric = metric;
+    const bool mix = !q8 && h->n_sparse > 0 && metric != NMN_METRIC_EUCLIDEAN;
     a.nrec = mix ? (const uint4*)h->d_nrec.p : nullptr;
     a.nent = mix ? (const uint2*)h->d_nent.p : nullptr;
     a.kind_u = w.qkind == 3 ? 0u : (uint32_t)w.qkind;
@@ -2008,10 +2019,14 @@ extern "C" nmn_status nmn_hnsw_destroy(nmn_hnsw* h) {
         drop(s->xcnt);
         drop(s->xsim);
         drop(s->xsort);
+        drop(s->ttq);
+        drop(s->ttmag);
+        drop(s->ttkind);
     }
     for (DevBuf* b : {&h->d_l0, &h->d_l0cnt, &h->d_upidx, &h->d_up, &h->d_upcnt, &h->d_nrec, &h->d_nent, &h->d_live, &h->hq, &h->hids, &h->hsc, &h->hcnt, &h->hkef,
                        &h->hsp_off, &h->hsp_ent, &h->hqmag,
-                       &h->hxmeta, &h->hxsim, &h->hxoids, &h->hxosc, &h->hxocnt, &h->hxsort})
+                       &h->hxmeta, &h->hxsim, &h->hxoids, &h->hxosc, &h->hxocnt, &h->hxsort, &h->htt_cores, &h->htt_ranks, &h->htt_off,
+                       &h->htt_skip})
         drop(*b);
     if (h->host_stream) (void)hipStreamDestroy(h->host_stream);
     if (h->vectors) nmn_index_destroy(h->vectors);
@@ -3219,6 +3234,238 @@ extern "C" nmn_status nmn_hnsw_cache_search_sparse(nmn_hnsw* h, const uint64_t* 
         stats->candidates_rescored = rescored;
     }
     return NMN_OK;
+}
+
+// ---- tensor-train queries and insert_tt_vector (hnsw.rs:1196-1221, 1755-1759, 1811-1903, 2238-2272; docs/hnsw.md §17) ---------------
+namespace {
+
+// cosine_distance_tt_with_norm on a node that is not stored as TT (hnsw.rs:1210-1219): q = tt_reconstruct(query), qmag = the
+// walk's magnitude of the query (tt_norm, 0.0 when it is below 1e-10: the `== 0.0` tests below then return the reference's 1.0).
+// Dense: simd::dot_product and simd::magnitude; Sparse: dot_dense and SparseVector::magnitude(); Quantized: dot_dense and
+// magnitude_immutable — Cosine on every handle.
+inline float tt_node_distance(const nmn_hnsw* h, uint32_t node, const float* q, float qmag, float qsum) {
+    if (h->storage == NMN_HNSW_STORAGE_QUANTIZED) {
+        HQ hq;
+        hq.mag = qmag;
+        hq.sum = qsum;
+        return h_q8_distance(NMN_METRIC_COSINE, h->codes.data() + (size_t)node * h->dim, h->qscale[node], h->qmin[node], h->mags[node],
+                             h->qxsq[node], q, hq, h->dim);
+    }
+    if (node_is_sparse(h, node)) {
+        const SpView s = node_entries(h, node);
+        const float dot = h_sparse_dot(s.pos, s.val, s.nnz, q);
+        if (h->mags[node] == 0.0f || qmag == 0.0f) return 1.0f;
+        const float den = h->mags[node] * qmag;
+        const float sim = dot / den;
+        return 1.0f - sim;
+    }
+    return h_distance(NMN_METRIC_COSINE, h->rows.data() + (size_t)node * h->dim, h->mags[node], q, qmag, h->dim);
+}
+
+// search_tt_with_ef of one prepared train on the host
+void host_search_one_tt(const nmn_hnsw* h, const float* q, float norm, uint32_t k, uint64_t ef, HostVisited& vis, uint64_t* ids,
+                        float* scores, uint32_t* count, uint64_t* evals) {
+    const float qmag = tt_walk_magnitude(norm);
+    const float qsum = h->storage == NMN_HNSW_STORAGE_QUANTIZED ? h_sum8(q, h->dim) : 0.0f;
+    host_walk_one(h, [&](uint32_t node) { return tt_node_distance(h, node, q, qmag, qsum); }, k, ef, vis, ids, scores, count, evals,
+                  NMN_METRIC_COSINE);
+}
+
+// The walk of nq prepared TT queries on s: q_dev [nq][dim] the reconstructions, mag_dev [nq] their magnitudes.  The kernel already
+// knows "a dense query whose Cosine magnitude is given": kind 2.  A quantized handle takes the QK = 2 launch; a handle with Sparse
+// nodes the MIX launch with kind 2 for every query (mix_dense_query with the given magnitude), under every metric of the handle;
+// a dense handle the per-query form QK = 3 on dense rows with a kind array of 2s (entries = false, mag_given = true) — no
+// instantiation is added.  Caller holds rw (shared) and sc->mu.
+nmn_status enqueue_tt_walk_locked(nmn_hnsw* h, nmn_hnsw::Scratch* sc, const float* q_dev, const float* mag_dev, uint32_t nq, uint32_t k,
+                                  uint32_t ef, uint64_t* o_ids, float* o_sc, uint32_t* o_cnt, hipStream_t s) {
+    WalkShape w = uniform_shape(h, nq, k, ef);
+    w.cosine = true;
+    w.qmag = mag_dev;
+    if (h->storage == NMN_HNSW_STORAGE_QUANTIZED || h->n_sparse > 0) {
+        w.qkind = 2;
+    } else {
+        bool synced = false;
+        HN_TRY(grow(sc->ttkind, (size_t)nq * 8, s, &synced));
+        uint32_t* kinds = (uint32_t*)sc->ttkind.p;
+        const uint32_t dim8 = (h->dim + 7u) & ~7u;
+        const uint32_t ccap = cand_cap(w.ef_lds, h->lds_ccap, dim8, (uint32_t)h->level.size());  // (enqueue_walk_locked's own)
+        HN_TRY(hipMemsetD32Async((hipDeviceptr_t)kinds, 2, nq, s));
+        HN_TRY(hipMemsetD32Async((hipDeviceptr_t)(kinds + nq), (int)ccap, nq, s));
+        w.qkind = 3;
+        w.kstride = k;
+        w.qkinds = kinds;
+        w.qccap = kinds + nq;
+    }
+    return enqueue_walk_locked(h, sc, q_dev, nq, w, o_ids, o_sc, o_cnt, s);
+}
+
+nmn_status tt_dim_check(const nmn_hnsw* h, const TTBatch& b) {
+    if (b.dim == h->dim) return NMN_OK;
+    char buf[160];
+    snprintf(buf, sizeof buf, "TT: the product of the shape is %llu, the index holds vectors of dimension %u", (unsigned long long)b.dim,
+             h->dim);
+    return set_error(NMN_ERR_DIMENSION_MISMATCH, buf);
+}
+
+}  // namespace
+
+extern "C" nmn_status nmn_hnsw_search_tt(nmn_hnsw* h, const uint32_t* shape, uint32_t n_cores, const uint32_t* ranks,
+                                         const uint64_t* core_off, const float* cores, uint32_t nq, uint32_t k, uint32_t ef,
+                                         uint64_t* out_ids, float* out_scores, uint32_t* out_counts, nmn_search_stats* stats) {
+    if (!h) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (k == 0) return set_error(NMN_ERR_INVALID_TOP_K, "k == 0");
+    if (stats) {
+        memset(stats, 0, sizeof *stats);
+        stats->scan_ms = stats->total_ms = -1.0f;
+    }
+    if (nq == 0) return NMN_OK;
+    if (!core_off || !out_ids || !out_scores || !out_counts) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    TTBatch b;
+    nmn_status st = tt_check(shape, n_cores, ranks, true, core_off, nq, true, &b);
+    if (st != NMN_OK) return st;
+    if (core_off[nq] > core_off[0] && !cores) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if ((st = tt_dim_check(h, b)) != NMN_OK) return st;
+    b.cores = cores;
+    const bool on_host = host_search_forced();
+    const uint32_t dim = h->dim;
+    uint64_t evals = 0;
+    uint32_t spilled = 0;
+    static thread_local HostVisited vis;
+    std::vector<float> hrow(dim);
+    auto host_one = [&](uint32_t q) {  // preparation and walk of train q on the host, into the caller's row
+        tt_reconstruct_host(shape, n_cores, b.ranks_of(q), cores + core_off[q], hrow.data());
+        const float norm = tt_norm_host(shape, n_cores, b.ranks_of(q), cores + core_off[q]);
+        host_search_one_tt(h, hrow.data(), norm, k, ef ? ef : h->cfg.ef_search, vis, out_ids + (size_t)q * k, out_scores + (size_t)q * k,
+                           out_counts + q, &evals);
+    };
+    std::shared_lock<std::shared_mutex> g(h->rw);
+    if (on_host) {
+        for (uint32_t q = 0; q < nq; q++) host_one(q);
+    } else {
+        std::lock_guard<std::mutex> hl(h->host_mu);  // callers take turns, as NMN_HNSW_NO_COALESCE=1 callers do
+        HN_TRY(hipSetDevice(h->device));
+        hipStream_t s = h->host_stream;
+        bool synced = true;  // (every earlier host call ended with a wait)
+        const hipStream_t none = (hipStream_t)-1;
+        const uint64_t c0 = core_off[0], cn = core_off[nq] - c0;
+        const size_t rk = (size_t)nq * (n_cores + 1);
+        std::vector<uint64_t> off(core_off, core_off + nq + 1);
+        for (uint64_t& o : off) o -= c0;
+        HN_TRY(grow(h->htt_cores, std::max<size_t>(cn * 4, 4), none, &synced));
+        HN_TRY(grow(h->htt_ranks, rk * 4, none, &synced));
+        HN_TRY(grow(h->htt_off, (size_t)(nq + 1) * 8, none, &synced));
+        HN_TRY(grow(h->htt_skip, nq, none, &synced));
+        HN_TRY(grow(h->hids, (size_t)nq * k * 8, none, &synced));
+        HN_TRY(grow(h->hsc, (size_t)nq * k * 4, none, &synced));
+        HN_TRY(grow(h->hcnt, (size_t)nq * 4, none, &synced));
+        if (cn) HN_TRY(hipMemcpyAsync(h->htt_cores.p, cores + c0, cn * 4, hipMemcpyHostToDevice, s));
+        HN_TRY(hipMemcpyAsync(h->htt_ranks.p, ranks, rk * 4, hipMemcpyHostToDevice, s));
+        HN_TRY(hipMemcpyAsync(h->htt_off.p, off.data(), (size_t)(nq + 1) * 8, hipMemcpyHostToDevice, s));
+        HN_TRY(hipMemcpyAsync(h->htt_skip.p, b.on_host.data(), nq, hipMemcpyHostToDevice, s));
+        nmn_hnsw::Scratch* sc = scratch_of(h, s);
+        std::vector<float> mags(nq), big_rows;
+        std::vector<uint32_t> fl(nq), ev(nq);
+        {
+            std::lock_guard<std::mutex> slk(sc->mu);
+            bool ssynced = false;
+            HN_TRY(grow(sc->ttq, (size_t)nq * dim * 4, s, &ssynced));
+            HN_TRY(grow(sc->ttmag, (size_t)nq * 4, s, &ssynced));
+            HN_TRY(launch_tt_prepare(b, (const float*)h->htt_cores.p, (const uint32_t*)h->htt_ranks.p, (const uint64_t*)h->htt_off.p,
+                                     (const uint8_t*)h->htt_skip.p, (float*)sc->ttq.p, nullptr, (float*)sc->ttmag.p, s));
+            if (b.n_on_host) {  // trains above the LDS limits: the host restatement, behind the launch into the rows it skipped
+                big_rows.resize((size_t)b.n_on_host * dim);
+                uint32_t j = 0;
+                for (uint32_t q = 0; q < nq; q++) {
+                    if (!b.on_host[q]) continue;
+                    float* row = big_rows.data() + (size_t)j++ * dim;
+                    tt_reconstruct_host(shape, n_cores, b.ranks_of(q), cores + core_off[q], row);
+                    mags[q] = tt_walk_magnitude(tt_norm_host(shape, n_cores, b.ranks_of(q), cores + core_off[q]));
+                    HN_TRY(hipMemcpyAsync((float*)sc->ttq.p + (size_t)q * dim, row, (size_t)dim * 4, hipMemcpyHostToDevice, s));
+                    HN_TRY(hipMemcpyAsync((float*)sc->ttmag.p + q, &mags[q], 4, hipMemcpyHostToDevice, s));
+                }
+            }
+            st = enqueue_tt_walk_locked(h, sc, (const float*)sc->ttq.p, (const float*)sc->ttmag.p, nq, k, ef, (uint64_t*)h->hids.p,
+                                        (float*)h->hsc.p, (uint32_t*)h->hcnt.p, s);
+            if (st != NMN_OK) return st;
+            HN_TRY(hipMemcpyAsync(out_ids, h->hids.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost, s));
+            HN_TRY(hipMemcpyAsync(out_scores, h->hsc.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, s));
+            HN_TRY(hipMemcpyAsync(out_counts, h->hcnt.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+            HN_TRY(hipMemcpyAsync(mags.data(), sc->ttmag.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+            HN_TRY(hipMemcpyAsync(fl.data(), sc->flags.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+            HN_TRY(hipMemcpyAsync(ev.data(), sc->evals.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+            HN_TRY(hipStreamSynchronize(s));
+        }
+        for (uint32_t q = 0; q < nq; q++) {
+            // a NaN norm gives NaN distances, which the kernel's rank sort does not place: the host walk answers (its heaps and its
+            // stable sort are the ones every walk is held to); so it does for a query the spill launch could not answer
+            if (fl[q] == 1u || std::isnan(mags[q])) {
+                host_one(q);
+                if (fl[q] == 1u) spilled++;
+            } else {
+                evals += ev[q];
+                if (fl[q] == 2u) spilled++;
+            }
+        }
+    }
+    if (stats) {
+        stats->rows_scanned = evals;
+        stats->bytes_scanned = h->storage == NMN_HNSW_STORAGE_QUANTIZED ? evals * (h->dim + 16ull) : evals * h->dim * 4;
+        stats->fallback_queries = spilled;
+        stats->sweep_kind = h->level.empty() ? NMN_SWEEP_NONE : NMN_SWEEP_GRAPH;
+        stats->sweep_launches = on_host ? 0 : 3;  // the preparation and the walk's two
+    }
+    return NMN_OK;
+}
+
+extern "C" nmn_status nmn_hnsw_search_tt_device(nmn_hnsw* h, const uint32_t* shape, uint32_t n_cores, const uint32_t* ranks,
+                                                const float* cores_dev, uint32_t nq, uint32_t k, uint32_t ef, uint64_t* out_ids_dev,
+                                                float* out_scores_dev, uint32_t* out_counts_dev, void* stream) {
+    if (!h) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (k == 0) return set_error(NMN_ERR_INVALID_TOP_K, "k == 0");
+    if (nq == 0) return NMN_OK;
+    if (!cores_dev || !out_ids_dev || !out_scores_dev || !out_counts_dev) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    TTBatch b;
+    nmn_status st = tt_check(shape, n_cores, ranks, false, nullptr, nq, false, &b);
+    if (st != NMN_OK) return st;
+    if (b.n_on_host)
+        return set_error(NMN_ERR_INVALID_ARGUMENT,
+                         "TT: the train is above the LDS limits of the device path (nmn_tt_limits); nmn_hnsw_search_tt prepares it on the host");
+    if ((st = tt_dim_check(h, b)) != NMN_OK) return st;
+    std::shared_lock<std::shared_mutex> g(h->rw);
+    HN_TRY(hipSetDevice(h->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    nmn_hnsw::Scratch* sc = scratch_of(h, s);
+    {
+        std::lock_guard<std::mutex> slk(sc->mu);
+        bool synced = false;
+        HN_TRY(grow(sc->ttq, (size_t)nq * h->dim * 4, s, &synced));
+        HN_TRY(grow(sc->ttmag, (size_t)nq * 4, s, &synced));
+        HN_TRY(launch_tt_prepare(b, cores_dev, nullptr, nullptr, nullptr, (float*)sc->ttq.p, nullptr, (float*)sc->ttmag.p, s));
+        st = enqueue_tt_walk_locked(h, sc, (const float*)sc->ttq.p, (const float*)sc->ttmag.p, nq, k, ef, out_ids_dev, out_scores_dev,
+                                    out_counts_dev, s);
+        if (st != NMN_OK) return st;
+    }
+    return record_search(h, s);
+}
+
+extern "C" nmn_status nmn_hnsw_insert_tt(nmn_hnsw* h, const uint32_t* shape, uint32_t n_cores, const uint32_t* ranks,
+                                         const uint64_t* core_off, const float* cores, uint64_t n, uint64_t* ids_out) {
+    if (!h || (!core_off && n)) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (h->storage != NMN_HNSW_STORAGE_DENSE)
+        return set_error(NMN_ERR_CONFIGURATION,
+                         "HNSW: insert_tt_vector makes Dense nodes, which are served on a dense handle only (insert the reconstruction "
+                         "with nmn_hnsw_insert to quantize it)");
+    if (n == 0) return NMN_OK;
+    if (n >= (uint64_t)kNone) return set_error(NMN_ERR_CAPACITY, "HNSW: node ids are 32 bits on the device");
+    TTBatch b;
+    nmn_status st = tt_check(shape, n_cores, ranks, true, core_off, (uint32_t)n, true, &b);
+    if (st != NMN_OK) return st;
+    if ((st = tt_dim_check(h, b)) != NMN_OK) return st;
+    HN_TRY(hipSetDevice(h->device));
+    std::vector<float> rows((size_t)n * h->dim);
+    st = nmn_tt_reconstruct(shape, n_cores, ranks, core_off, cores, (uint32_t)n, rows.data());
+    if (st != NMN_OK) return st;
+    return insert_rows(h, rows.data(), n, nullptr, nullptr, ids_out);
 }
 
 // ---- persistence (docs/hnsw.md §10) ----------------------------------------------------------------------------------------------

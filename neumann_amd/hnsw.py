@@ -421,6 +421,68 @@ class GpuHnsw:
             C.c_void_p(sc.data_ptr()), C.c_void_p(counts.data_ptr()), _stream_ptr(stream)))
         return ids, sc, counts
 
+    def search_tt(self, tts, k, ef=None, with_stats=False):
+        """HNSWIndex::search_tt_with_ef per train (nmn_hnsw_search_tt; ef None: ef_search).  `tts`: one neumann_amd.tt.TTVector or
+        several of one shape whose product is the index's dimension.  The trains are reconstructed and their norms taken on the
+        GPU; the walk scores under Cosine whatever the index's metric is, the score is 1 - distance (docs/hnsw.md §17).
+        -> (ids u64 [nq,k], scores f32 [nq,k], counts u32 [nq])"""
+        from . import tt as _tt
+        shape, ranks, off, cores = _tt.pack(tts)
+        nq, k = ranks.shape[0], int(k)
+        ids = np.empty((nq, max(k, 1)), dtype=np.uint64)
+        sc = np.empty((nq, max(k, 1)), dtype=np.float32)
+        counts = np.empty(nq, dtype=np.uint32)
+        st = _capi.SearchStats()
+        _capi.check(self._lib.nmn_hnsw_search_tt(self._h, C.c_void_p(shape.ctypes.data), shape.size, C.c_void_p(ranks.ctypes.data),
+                                                 C.c_void_p(off.ctypes.data), C.c_void_p(cores.ctypes.data), nq, k,
+                                                 0 if ef is None else int(ef), C.c_void_p(ids.ctypes.data),
+                                                 C.c_void_p(sc.ctypes.data), C.c_void_p(counts.ctypes.data), C.byref(st)))
+        return (ids, sc, counts, st) if with_stats else (ids, sc, counts)
+
+    def search_tt_device(self, shape, ranks, cores_t, k, ef=None, out=None, stream=None):
+        """`search_tt` with the core data in a torch device tensor, in stream order (nmn_hnsw_search_tt_device): `cores_t` is
+        float32 [nq, storage] — every train's cores back to back — and ONE rank vector `ranks` [len(shape) + 1] serves the whole
+        call.  Preparation and walk are enqueued on `stream` (None: torch's current stream); nothing is read back.  Returns
+        (ids int64 [nq,k], -1 = unused slot; scores f32 [nq,k]; counts int32 [nq]) like `search_device`."""
+        import torch
+
+        if not (isinstance(cores_t, torch.Tensor) and cores_t.is_cuda):
+            raise _capi.NeumannGpuError(_capi.ERR_INVALID_ARGUMENT, "cores must be a device tensor")
+        if cores_t.dtype != torch.float32 or not cores_t.is_contiguous() or cores_t.dim() != 2:
+            raise _capi.NeumannGpuError(_capi.ERR_INVALID_ARGUMENT, "cores must be contiguous float32 [nq, storage]")
+        sh = np.ascontiguousarray(shape, dtype=np.uint32).reshape(-1)
+        rk = np.ascontiguousarray(ranks, dtype=np.uint32).reshape(-1)
+        if rk.size != sh.size + 1:
+            raise _capi.NeumannGpuError(_capi.ERR_INVALID_ARGUMENT, "TT: ranks is [n_cores + 1]")
+        storage = int(sum(int(rk[i]) * int(sh[i]) * int(rk[i + 1]) for i in range(sh.size)))
+        if cores_t.shape[1] != storage:
+            raise _capi.NeumannGpuError(_capi.ERR_INVALID_ARGUMENT, f"TT: a train of these ranks holds {storage} floats")
+        nq, k = cores_t.shape[0], int(k)
+        if out is None:
+            kk = max(k, 1)
+            ids = torch.empty((nq, kk), dtype=torch.int64, device=cores_t.device)
+            sc = torch.empty((nq, kk), dtype=torch.float32, device=cores_t.device)
+            counts = torch.empty((nq,), dtype=torch.int32, device=cores_t.device)
+        else:
+            ids, sc, counts = out
+        _capi.check(self._lib.nmn_hnsw_search_tt_device(
+            self._h, C.c_void_p(sh.ctypes.data), sh.size, C.c_void_p(rk.ctypes.data), C.c_void_p(cores_t.data_ptr()), nq, k,
+            0 if ef is None else int(ef), C.c_void_p(ids.data_ptr()), C.c_void_p(sc.data_ptr()), C.c_void_p(counts.data_ptr()),
+            _stream_ptr(stream)))
+        return ids, sc, counts
+
+    def insert_tt(self, tts):
+        """HNSWIndex::insert_tt_vector for each train in order (nmn_hnsw_insert_tt): reconstructed on the GPU, inserted as Dense
+        nodes by `insert`'s path; returns the node ids.  Dense handles only."""
+        from . import tt as _tt
+        shape, ranks, off, cores = _tt.pack(tts)
+        n = ranks.shape[0]
+        ids = np.empty(n, dtype=np.uint64)
+        _capi.check(self._lib.nmn_hnsw_insert_tt(self._h, C.c_void_p(shape.ctypes.data), shape.size, C.c_void_p(ranks.ctypes.data),
+                                                 C.c_void_p(off.ctypes.data), C.c_void_p(cores.ctypes.data), n,
+                                                 C.c_void_p(ids.ctypes.data)))
+        return ids
+
     def search_metric(self, queries, top_k, metric, with_stats=False):
         """search_with_hnsw_and_metric's steps per query (nmn_hnsw_search_metric): c = max(2 top_k, 10) candidates from the walk,
         re-ranked under `metric` (an ExtendedDistanceMetric), the first top_k of the stable descending order.

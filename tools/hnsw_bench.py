@@ -474,6 +474,64 @@ def build_or_load(path, n, d, cfg, storage, out, label=""):
     return g
 
 
+def time_tt(g, k, args):
+    """--tt-queries SHAPE:RANK (docs/hnsw.md §17): 1024 Gaussian trains of that shape with every inner rank RANK.  search_tt_device
+    (preparation + walk) against search_device of the same number of dense queries — the trains' reconstructions — on the same
+    handle and stream, alternating call by call, each call between two events; the difference is the preparation's cost.  Device,
+    host-buffer and host-walk answers of the first 64 trains must be the same bits."""
+    import torch
+    from neumann_amd import TTVector, tt_reconstruct
+    shape_s, rank_s = args.tt_queries.split(":")
+    shape = [int(x) for x in shape_s.split(",")]
+    ranks = [1] + [int(rank_s)] * (len(shape) - 1) + [1]
+    sizes = [ranks[i] * shape[i] * ranks[i + 1] for i in range(len(shape))]
+    rng = np.random.default_rng(0x77B)
+    cores = rng.standard_normal((1024, sum(sizes))).astype(np.float32)
+    cuts = np.cumsum([0] + sizes)
+    tts = [TTVector(shape, ranks, [row[cuts[i]:cuts[i + 1]] for i in range(len(shape))]) for row in cores]
+    Q = tt_reconstruct(tts)
+    s = torch.cuda.Stream()
+    cd, qd = torch.from_numpy(cores).cuda(), torch.from_numpy(Q).cuda()
+    r = {"tt_shape": shape, "tt_ranks": ranks, "core_floats": int(sum(sizes))}
+    dev = {}
+    for nq in (1, 64, 1024):
+        dev[nq] = tuple((torch.empty((nq, k), dtype=torch.int64, device="cuda"), torch.empty((nq, k), dtype=torch.float32, device="cuda"),
+                         torch.empty((nq,), dtype=torch.int32, device="cuda")) for _ in range(2))
+        g.search_tt_device(shape, ranks, cd[:nq], k, 50, out=dev[nq][0], stream=s)
+        g.search_device(qd[:nq], k, 50, out=dev[nq][1], stream=s)
+    s.synchronize()
+    ids, sc, _ = g.search_tt(tts[:64], k, 50)
+    same = np.array_equal(dev[64][0][0].cpu().numpy().view(np.uint64), ids) and \
+        np.array_equal(dev[64][0][1].cpu().numpy().view(np.uint32), sc.view(np.uint32))
+    os.environ["NMN_HNSW_HOST_SEARCH"] = "1"
+    try:
+        hids, hsc, _ = g.search_tt(tts[:64], k, 50)
+    finally:
+        del os.environ["NMN_HNSW_HOST_SEARCH"]
+    same = same and np.array_equal(hids, ids) and np.array_equal(hsc.view(np.uint32), sc.view(np.uint32))
+    r["device_host_buffer_and_host_walk_agree"] = bool(same)
+    if not same:
+        raise SystemExit("search_tt_device, search_tt and the host walk disagree")
+    for nq, calls in ((1, args.calls), (64, args.calls), (1024, max(args.calls // 5, 5))):
+        tt_ev, de_ev = [], []
+        for _ in range(calls):
+            e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+            e0.record(s)
+            g.search_tt_device(shape, ranks, cd[:nq], k, 50, out=dev[nq][0], stream=s)
+            e1.record(s)
+            g.search_device(qd[:nq], k, 50, out=dev[nq][1], stream=s)
+            e2.record(s)
+            tt_ev.append((e0, e1))
+            de_ev.append((e1, e2))
+        s.synchronize()
+        t_tt = np.array([a.elapsed_time(b) for a, b in tt_ev])
+        t_de = np.array([a.elapsed_time(b) for a, b in de_ev])
+        r[f"nq{nq}"] = {"calls": calls, "tt_call_ms": round(float(np.median(t_tt)), 5), "dense_call_ms": round(float(np.median(t_de)), 5),
+                        "preparation_call_ms": round(float(np.median(t_tt - t_de)), 5),
+                        "preparation_call_ms_p10_p90": [round(float(x), 5) for x in np.percentile(t_tt - t_de, [10, 90])]}
+    return r
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1_000_000)
@@ -505,6 +563,9 @@ def main():
     ap.add_argument("--sparse-node-fraction", type=float, default=None,
                     help="insert this share of the rows Sparse (nmn_hnsw_insert_sparse) and time search_device / search_sparse of the "
                          "mixed handle beside an all-dense handle over the to_dense() rows (docs/hnsw.md §15)")
+    ap.add_argument("--tt-queries", default=None,
+                    help="SHAPE:RANK, e.g. 4,4,8:8 — time search_tt_device against search_device with as many dense queries on the "
+                         "same handle, alternating call by call (docs/hnsw.md §17); one repetition per process")
     ap.add_argument("--index-file", default=None,
                     help="load the index from this file when it exists; otherwise build, save it there and report build / save / load seconds")
     args = ap.parse_args()
@@ -570,6 +631,12 @@ def main():
         return
     if args.sparse_node_fraction is not None:
         print(json.dumps(time_mixed(n, d, cfg, Q, k, args, out)), flush=True)
+        return
+    if args.tt_queries is not None:
+        out["storage"] = args.storage
+        with build_or_load(args.index_file, n, d, cfg, args.storage, out) as g:
+            out.update(time_tt(g, k, args))
+        print(json.dumps(out), flush=True)
         return
     if args.sparse_queries is not None:
         out["storage"] = args.storage
