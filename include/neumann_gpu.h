@@ -130,6 +130,12 @@ const char* nmn_last_error(void);
 /* Library version "major.minor.patch". */
 const char* nmn_version(void);
 
+/* Which form of the candidate selection the searches of this process took: launches of nmn::select_kernel since the library was
+ * loaded, out[0] the flat path (shards of <= 16 384 tiles), out[1] the split selection (lone callers, k <= 256, 16 385 .. 262 144
+ * tiles), out[2] the three-level walk (everything else; NMN_NO_FLAT_SELECT=1 / NMN_NO_SPLIT_SELECT=1 send the other two there).
+ * Process-wide, all shards and devices together; one launch serves all queries of a pass.  For tests and A/B runs. */
+nmn_status nmn_select_form_counts(uint64_t* out);
+
 /* Allocate one shard: corpus[capacity_rows][ld] f32 row-major (ld = dim rounded up to 8, or to the next multiple of 128 if that is at most 1/8 more; zero
  * padded), norms[capacity_rows] f32.  Replaces the per-row `TensorStore` reads of the hot loop
  * (vector_engine/src/lib.rs:2121-2138; tensor_store/src/lib.rs:948-963) by one resident matrix. */

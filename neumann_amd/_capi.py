@@ -136,6 +136,7 @@ SIGNATURES = {
     "nmn_last_error": (C.c_char_p, []),
     "nmn_version": (C.c_char_p, []),
     "nmn_sweep_kind_str": (C.c_char_p, [C.c_uint32]),
+    "nmn_select_form_counts": (C.c_int32, [u64p]),
     "nmn_index_create": (C.c_int32, [C.POINTER(IndexDesc), C.POINTER(vp)]),
     "nmn_index_destroy": (C.c_int32, [vp]),
     "nmn_index_upload": (C.c_int32, [vp, vp, C.c_uint64, C.c_uint64]),
@@ -352,3 +353,10 @@ def check(status):
     if status != OK:
         detail = load().nmn_last_error().decode(errors="replace")
         raise NeumannGpuError(status, detail)
+
+
+def select_form_counts():
+    """(flat, split, walk): launches of select_kernel by form since the library was loaded (nmn_select_form_counts)."""
+    out = (C.c_uint64 * 3)()
+    check(load().nmn_select_form_counts(out))
+    return tuple(int(x) for x in out)

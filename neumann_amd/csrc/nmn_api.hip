@@ -439,6 +439,12 @@ extern "C" const char* nmn_sweep_kind_str(uint32_t kind) {
 extern "C" const char* nmn_last_error(void) { return g_last_error.c_str(); }
 extern "C" const char* nmn_version(void) { return "0.3.0"; }
 
+extern "C" nmn_status nmn_select_form_counts(uint64_t* out) {
+    if (!out) return fail_arg(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    select_form_counts(out);
+    return NMN_OK;
+}
+
 extern "C" nmn_status nmn_index_create(const nmn_index_desc* d, nmn_index** out) {
     if (!d || !out) return fail_arg(NMN_ERR_INVALID_ARGUMENT, "null argument");
     *out = nullptr;

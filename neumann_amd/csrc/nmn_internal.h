@@ -284,6 +284,7 @@ struct SelectParams {
     uint32_t* split_ctr;       // [nq][4]: [0] parts arrived at the bound, [2..3] one 64-bit word (parts finished << 32 | candidates reserved); zero between launches
 };
 hipError_t launch_select(const SelectParams& p, hipStream_t s);
+void select_form_counts(uint64_t out[3]);  // launches of select_kernel by form since load: flat path, split selection, three-level walk
 hipError_t launch_count_untrusted(const float* norms, uint64_t n_rows, uint32_t* out, hipStream_t s);
 // per query: skip_key[q] = margin_key(k-th largest of the sampled tile maxima) (kKeyNaN if fewer than k are valid)
 // (combine_max: keep the larger of the bound already in skip_key and the new one)

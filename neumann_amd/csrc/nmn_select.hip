@@ -6,6 +6,7 @@
 // (query_router/src/distributed.rs:413-433).  Order everywhere: score descending, ties by ascending
 // row id; NaN scores last.
 #include <algorithm>
+#include <atomic>
 #include <type_traits>
 
 #include "nmn_select_dev.h"
@@ -954,6 +955,9 @@ __global__ void __launch_bounds__(kSelThreads) select_kernel(SelectParams p) {
     }
 }
 
+// launches of select_kernel since the library was loaded, by form: [0] flat path, [1] split selection, [2] three-level walk
+static std::atomic<uint64_t> g_select_forms[3];
+
 hipError_t launch_select(const SelectParams& p, hipStream_t s) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(select_kernel),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSelectLds);
@@ -967,8 +971,14 @@ hipError_t launch_select(const SelectParams& p, hipStream_t s) {
     const uint32_t parts = (p.n_tiles + kFlatTiles - 1) / kFlatTiles;
     pf.split = (!no_flat && !no_split && p.split_sg && p.split_ctr && p.nq <= 4 && p.k <= kFlatGroupK && !p.k_extra && parts >= 2 && parts <= 16 &&
                 (p.tmax_stride & 3ull) == 0ull) ? parts : 0u;
+    // which form this launch takes, counted for nmn_select_form_counts (kernel: S > 1 the split, p.flat && n_tiles <= kFlatTiles the flat path)
+    g_select_forms[pf.split ? 1 : (pf.flat && p.n_tiles <= kFlatTiles) ? 0 : 2].fetch_add(1, std::memory_order_relaxed);
     hipLaunchKernelGGL(select_kernel, dim3(p.nq * (pf.split ? pf.split : 1u)), dim3(kSelThreads), kSelectLds, s, pf);
     return hipGetLastError();
+}
+
+void select_form_counts(uint64_t out[3]) {
+    for (int i = 0; i < 3; i++) out[i] = g_select_forms[i].load(std::memory_order_relaxed);
 }
 
 // ---- crowd path: the rows within the margin, when there are more than cand_cap of them ---------------

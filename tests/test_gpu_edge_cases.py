@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle_c as oc
+from tests import _corpora
 
 pytestmark = pytest.mark.gpu
 U64_MAX = np.uint64(0xFFFFFFFFFFFFFFFF)
@@ -30,8 +31,7 @@ def check(idx, A, Q, k, metric, mask=None, row_base=0):
 def test_all_rows_identical_ties_by_row(metric):
     from neumann_amd import GpuFlatIndex
     n, d = 5000, 24
-    A = np.tile(np.linspace(-1, 1, d, dtype=np.float32), (n, 1))
-    q = np.linspace(1, 2, d, dtype=np.float32)
+    A, q = _corpora.identical_rows(n, d)
     with GpuFlatIndex(d, n, single_launch=False) as idx:   # (the pipeline) default cand_cap 4096 < 5000 tied rows -> exact fallback
         idx.upload(A)
         st = check(idx, A, q, 10, metric)
@@ -430,8 +430,7 @@ def test_large_shard_exact_fallback_uses_the_device_wide_select(metric):
     from neumann_amd import GpuFlatIndex
     n, d = 300_000, 32
     rng = np.random.default_rng(31 + metric)
-    A = np.tile(np.linspace(-1, 1, d, dtype=np.float32), (n, 1))
-    q = np.linspace(1, 2, d, dtype=np.float32)
+    A, q = _corpora.identical_rows(n, d)
     with GpuFlatIndex(d, n) as idx:
         idx.upload(A)
         st = check(idx, A, q, 10, metric)

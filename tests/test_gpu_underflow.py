@@ -13,12 +13,13 @@ import numpy as np
 import pytest
 
 from oracle import oracle_c as oc
+from tests import _corpora as shared
 
 pytestmark = pytest.mark.gpu
 F = np.float32
 U64_MAX = np.uint64(0xFFFFFFFFFFFFFFFF)
 N, D = 270_000, 256          # >= 4096 tiles (ring), stride a multiple of 256 (8-bit matrix-core sweep)
-STRADDLE = (F(2.5e-23), F(4e-23))
+STRADDLE = shared.STRADDLE
 
 # (mirror mode, queries per call, bitmap?) -> the sweep that must serve it on the control corpus
 SWEEPS = [(0, 1, False, "ring_f32"), (0, 1, True, "valu_f32"), (0, 2, False, "valu_f32"), (2, 1, False, "valu_bf16"),
@@ -86,9 +87,7 @@ def _queries(rng, A, tiny_row):
 
 
 def _straddle_rows(rng, m, d=D):
-    """m rows of +-2.5e-23 / +-4e-23 (squares subnormal: the stored magnitude is far below the true one)."""
-    v = np.where(rng.random((m, d)) < 0.8, STRADDLE[0], STRADDLE[1]).astype(F)
-    return (v * rng.choice(np.array([-1, 1], F), (m, d))).astype(F)
+    return shared.straddle_rows(rng, m, d)
 
 
 def _control():
@@ -104,19 +103,15 @@ def _corpora():
     for s in (1e-12, 1e-19, 1e-21, 1e-22, 1e-30, 1e-44):
         yield f"scale {s:g}", (base * F(s)).astype(F), 11
     # straddle: every row tiny; 400 near-ties of one row (one element swapped between 2.5e-23 and 4e-23) around the cut
-    A = _straddle_rows(rng, N)
-    tie = rng.choice(N, 400, replace=False)
-    A[tie] = A[tie[0]]
-    cols = rng.integers(0, D, 400)
-    A[tie, cols] = np.where(np.abs(A[tie, cols]) == STRADDLE[0], STRADDLE[1], STRADDLE[0]) * np.sign(A[tie, cols])
-    yield "straddle", A.astype(F), int(tie[1])
+    A, tie = shared.straddle_corpus(rng, N, D)
+    yield "straddle", A, int(tie[1])
     # mixed: normal rows plus planted tiny rows whose inflated cosines (> 1) belong in the normal queries' top k
     A = base.copy()
     Q0 = _queries(np.random.default_rng(0x0DF2), A, 0)
     plant = rng.choice(np.arange(8, N), 3 * 60, replace=False)
     for j, qi in enumerate((0, 5, 6)):
         rows = plant[60 * j: 60 * (j + 1)]
-        A[rows] = (np.abs(_straddle_rows(rng, rows.size)) * np.sign(Q0[qi])).astype(F)
+        A[rows] = shared.tiny_rows_along(rng, Q0[qi], rows.size)
     yield "mixed", A, int(plant[0])
     # the upper end: +-1e6 everywhere (the reference fuzz target's bound), a few rows near 2e19 (|v|^2 overflows: |v| = inf)
     A = rng.uniform(-1e6, 1e6, (N, D)).astype(F)
