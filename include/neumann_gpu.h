@@ -605,6 +605,7 @@ typedef struct nmn_hnsw nmn_hnsw;
 #define NMN_HNSW_STORAGE_DENSE 0
 #define NMN_HNSW_STORAGE_AUTO 1
 #define NMN_HNSW_STORAGE_QUANTIZED 2
+#define NMN_HNSW_STORAGE_BINARY 3 /* EmbeddingStorage::Binary nodes (no HNSWStorageStrategy makes them): nmn_hnsw_create_binary */
 
 /* HNSWConfig (hnsw.rs:1434-1463). */
 typedef struct nmn_hnsw_config {
@@ -725,11 +726,12 @@ nmn_status nmn_hnsw_search_device(nmn_hnsw* h, const float* queries_dev, uint32_
 /* Entries of the results / candidate heaps a wave keeps in LDS (0 = default: 1024 results, 1024 .. 4096 candidates by ef).
  * Smaller heaps leave more LDS per workgroup; a query that outgrows them is answered by the spill launch, same bits. */
 nmn_status nmn_hnsw_set_heap_capacity(nmn_hnsw* h, uint32_t results, uint32_t candidates);
-/* The flat index holding the rows (exhaustive search over the same rows).  NULL on a quantized handle: it keeps no f32 rows on
- * the device. */
+/* The flat index holding the rows (exhaustive search over the same rows).  NULL on a quantized or binary handle: it keeps no f32
+ * rows on the device. */
 nmn_index* nmn_hnsw_vectors(nmn_hnsw* h);
 /* Device memory the index holds: rows, magnitudes, mirrors, adjacency (dense; with sparse nodes also a 16-byte record per node
- * and 8 bytes per stored entry); codes, records, adjacency (quantized); the live mask, one bit per node. */
+ * and 8 bytes per stored entry); codes, records, adjacency (quantized); words, adjacency (binary); the live mask, one bit per
+ * node. */
 uint64_t nmn_hnsw_hbm_bytes(nmn_hnsw* h);
 
 /* nmn_hnsw_create with the storage strategy of HNSWBuildOptions: `storage` is NMN_HNSW_STORAGE_*, cfg->storage is not read.
@@ -743,14 +745,31 @@ uint64_t nmn_hnsw_hbm_bytes(nmn_hnsw* h);
  * AUTO: NMN_ERR_CONFIGURATION.  A handle has one strategy. */
 nmn_status nmn_hnsw_create_with_storage(const nmn_hnsw_config* cfg, int32_t storage, uint32_t dim, uint64_t capacity_hint,
                                         int32_t device, nmn_hnsw** out);
-int32_t nmn_hnsw_storage(const nmn_hnsw* h); /* NMN_HNSW_STORAGE_DENSE or _QUANTIZED */
+int32_t nmn_hnsw_storage(const nmn_hnsw* h); /* NMN_HNSW_STORAGE_DENSE, _QUANTIZED or _BINARY */
+/* A handle whose every node is EmbeddingStorage::Binary(BinaryVector::from_dense(row, threshold)) (hnsw.rs:579;
+ * binary_quantization.rs:83-99), inserted as insert_embedding does; `binary_threshold` is NMN_BINARY_SIGN / _MEAN / _MEDIAN.
+ * nmn_hnsw_create_with_storage(.., NMN_HNSW_STORAGE_BINARY, ..) is the same with Sign.  A row is one bit per dimension, resident
+ * in HBM as n x ldw u64 words (ldw = ceil(dim / 64) rounded up to 2: 16-byte rows, the padding zero) beside the adjacency; no f32
+ * rows and no record per row live on the device, nmn_hnsw_vectors is NULL.  Searches and insertion score a row against a query on
+ * to_dense(), +1.0 for a set bit and -1.0 otherwise (157-166): simd::dot_product / euclidean_distance, and under Cosine
+ * 1 - dot / (sqrt(dim as f32) * |q|) (hnsw.rs:801-805, 981-984, 1098-1101); pruning under Cosine is the Hamming formula
+ * 1 - (1 - hamming / dim) (2516-2518), under Euclidean / DotProduct the dense arithmetic on both to_dense() rows.  Same graph,
+ * ids and score bits as the reference (docs/hnsw.md §18).  Served: nmn_hnsw_insert, nmn_hnsw_search, _search_multi,
+ * _search_device, the accessors.  Refused with NMN_ERR_CONFIGURATION: nmn_hnsw_search_metric*, _search_sparse*, _search_tt*,
+ * _cache_search*, _set_node_mask, _insert_sparse / _auto / _tt, _quantized_row, _save. */
+nmn_status nmn_hnsw_create_binary(const nmn_hnsw_config* cfg, int32_t binary_threshold, uint32_t dim, uint64_t capacity_hint,
+                                  int32_t device, nmn_hnsw** out);
+int32_t nmn_hnsw_binary_threshold(const nmn_hnsw* h); /* NMN_BINARY_*; -1 when the handle's storage is not Binary */
+/* The BinaryVector of a node: words_out[ceil(dim / 64)] (nullable; cap_words = its capacity), padding bits zero.  Any other
+ * handle: NMN_ERR_CONFIGURATION. */
+nmn_status nmn_hnsw_binary_row(nmn_hnsw* h, uint64_t node, uint64_t* words_out, uint32_t cap_words);
 /* The ScalarQuantizedVector of a node: codes_out[dim], scale, min_val (each nullable).  Dense handle: NMN_ERR_CONFIGURATION. */
 nmn_status nmn_hnsw_quantized_row(nmn_hnsw* h, uint64_t node, uint8_t* codes_out, float* scale, float* min_val);
 /* HNSWIndex::get_vector: out[dim] = the row as inserted (dense), to_dense() of a sparse node, or dequantize() =
- * code.mul_add(scale, min_val) (quantized). */
+ * code.mul_add(scale, min_val) (quantized), or to_dense() = +1.0 / -1.0 per bit (binary). */
 nmn_status nmn_hnsw_get_vector(nmn_hnsw* h, uint64_t node, float* out);
-/* HNSWMemoryStats (hnsw.rs:2733-2768); embedding_bytes = 4 dim per dense node, 16 + dim per quantized node, 56 + 8 nnz per
- * sparse node (size_of::<SparseVector>() on a 64-bit target plus both Vec capacities taken as their lengths — what a cloned
+/* HNSWMemoryStats (hnsw.rs:2733-2768); embedding_bytes = 4 dim per dense node, 16 + dim per quantized node, 8 ceil(dim / 64)
+ * per binary node (binary_quantization.rs:174-179), 56 + 8 nnz per sparse node (size_of::<SparseVector>() on a 64-bit target plus both Vec capacities taken as their lengths — what a cloned
  * vector has; std does not pin the capacity of a pushed one, docs/hnsw.md §15). */
 typedef struct nmn_hnsw_memstats {
     uint64_t total_nodes;

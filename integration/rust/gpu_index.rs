@@ -270,6 +270,24 @@ impl GpuHnswIndex {
         Ok(Self { raw, dim })
     }
 
+    /// An index whose every node is EmbeddingStorage::Binary(BinaryVector::from_dense(row, threshold)) (nmn_hnsw_create_binary,
+    /// docs/hnsw.md §18): `threshold` is ffi::NMN_BINARY_SIGN / _MEAN / _MEDIAN.  `insert` and `search` work as on every handle;
+    /// sparse, TT, metric and cache searches, the node mask and `save` are refused with a configuration error.
+    pub fn new_binary(dim: usize, cfg: &ffi::nmn_hnsw_config, threshold: i32, capacity_hint: usize, device: i32) -> Result<Self> {
+        let mut raw = std::ptr::null_mut();
+        let st = unsafe { ffi::nmn_hnsw_create_binary(cfg, threshold, dim as u32, capacity_hint as u64, device, &mut raw) };
+        check(st, dim, dim)?;
+        Ok(Self { raw, dim })
+    }
+
+    /// The BinaryVector words of a node of a binary index (nmn_hnsw_binary_row): ceil(dim / 64) of them, padding bits zero.
+    pub fn binary_row(&self, node: usize) -> Result<Vec<u64>> {
+        let mut words = vec![0u64; self.dim.div_ceil(64)];
+        let st = unsafe { ffi::nmn_hnsw_binary_row(self.raw, node as u64, words.as_mut_ptr(), words.len() as u32) };
+        check(st, self.dim, self.dim)?;
+        Ok(words)
+    }
+
     pub fn len(&self) -> usize {
         unsafe { ffi::nmn_hnsw_len(self.raw) as usize }
     }

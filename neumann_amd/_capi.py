@@ -95,7 +95,7 @@ class HnswConfig(C.Structure):
                 ("distance_metric", C.c_int32), ("storage", C.c_int32), ("reserved", C.c_uint32)]
 
 
-HNSW_STORAGE_DENSE, HNSW_STORAGE_AUTO, HNSW_STORAGE_QUANTIZED = range(3)
+HNSW_STORAGE_DENSE, HNSW_STORAGE_AUTO, HNSW_STORAGE_QUANTIZED, HNSW_STORAGE_BINARY = range(4)
 
 
 class HnswBuildOptions(C.Structure):
@@ -237,6 +237,9 @@ SIGNATURES = {
                                                  C.POINTER(vp)]),
     "nmn_hnsw_storage": (C.c_int32, [vp]),
     "nmn_hnsw_quantized_row": (C.c_int32, [vp, C.c_uint64, vp, f32p, f32p]),
+    "nmn_hnsw_create_binary": (C.c_int32, [C.POINTER(HnswConfig), C.c_int32, C.c_uint32, C.c_uint64, C.c_int32, C.POINTER(vp)]),
+    "nmn_hnsw_binary_threshold": (C.c_int32, [vp]),
+    "nmn_hnsw_binary_row": (C.c_int32, [vp, C.c_uint64, vp, C.c_uint32]),
     "nmn_hnsw_get_vector": (C.c_int32, [vp, C.c_uint64, vp]),
     "nmn_hnsw_memory_stats": (C.c_int32, [vp, C.POINTER(HnswMemStats)]),
     "nmn_hnsw_get_config": (C.c_int32, [vp, C.POINTER(HnswConfig)]),

@@ -36,6 +36,12 @@
 //       cosine_distance_tt_with_norm (1196-1221): the query reconstructed and its tt_norm taken by nmn_tt.hip, then Cosine on every
 //       handle with that norm as the query's magnitude, the kernel's kind 2.  nmn_hnsw_insert_tt: insert_tt_vector (1755-1759).
 //       docs/hnsw.md §17.
+//   nmn_hnsw_create_binary: every node is EmbeddingStorage::Binary(BinaryVector::from_dense(v, threshold)) (hnsw.rs:579,
+//       binary_quantization.rs:83-99).  The query side is the dense arithmetic on to_dense() — +1.0 for a set bit, -1.0 otherwise
+//       (157-166) — with sqrt(dim as f32) as the row's magnitude (hnsw.rs:801-805, 981-984, 1098-1101); the pruning side under
+//       Cosine is 1 - similarity() = 1 - (1 - hamming / dim) on the words (2516-2518, binary_quantization.rs:137-142), under
+//       Euclidean / DotProduct the dense arithmetic on both to_dense() rows (2605-2609, 2680-2684).  The host keeps the words and
+//       the +-1 row per node, the device the words alone; the kernel takes the BIN instantiations.  docs/hnsw.md §18.
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -271,11 +277,58 @@ inline float h_q8_distance(int metric, const uint8_t* code, float scale, float m
     return 1.0f - sim;
 }
 
+// ---- BinaryVector on the host (binary_quantization.rs:41-99, 123-166) -----------------------------------------------------------
+// BinaryThreshold::compute: Sign 0.0; Mean `iter().sum::<f32>() / len as f32` (the fold from -0.0 of docs/hnsw.md §1); Median the
+// sorted row's middle element, or f32::midpoint of the two middle ones = ((a as f64 + b as f64) / 2) as f32 (docs/ivf.md §3.10b).
+// from_dense: bit i of word i / 64 = v[i] > threshold; the padding bits of the last word stay zero.  NaN rows are out of scope.
+inline float h_bin_threshold(const float* v, uint32_t dim, int method, std::vector<float>& tmp) {
+    if (method == NMN_BINARY_MEAN) {
+        float s = -0.0f;
+        for (uint32_t i = 0; i < dim; i++) s = s + v[i];
+        return s / (float)dim;
+    }
+    if (method == NMN_BINARY_MEDIAN) {
+        tmp.assign(v, v + dim);
+        std::stable_sort(tmp.begin(), tmp.end());
+        const uint32_t mid = dim / 2;
+        if (dim % 2 == 0) return (float)(((double)tmp[mid - 1] + (double)tmp[mid]) / 2.0);
+        return tmp[mid];
+    }
+    return 0.0f;
+}
+inline void h_bin_from_dense(const float* v, uint32_t dim, int method, uint64_t* words, float* pm1, std::vector<float>& tmp) {
+    const float t = h_bin_threshold(v, dim, method, tmp);
+    const uint32_t W = (dim + 63u) / 64u;
+    for (uint32_t w = 0; w < W; w++) words[w] = 0;
+    for (uint32_t i = 0; i < dim; i++) {
+        const bool bit = v[i] > t;
+        if (bit) words[i >> 6] |= 1ull << (i & 63u);
+        pm1[i] = bit ? 1.0f : -1.0f;  // to_dense()
+    }
+}
+inline uint32_t h_bin_hamming(const uint64_t* a, const uint64_t* b, uint32_t W) {
+    uint32_t hd = 0;
+    for (uint32_t w = 0; w < W; w++) hd += (uint32_t)__builtin_popcountll(a[w] ^ b[w]);
+    return hd;
+}
+// EmbeddingStorage::distance_dense on a Binary row (hnsw.rs:1035-1045 with 801-805 and 981-984; 1098-1101; 1136-1138): `pm1` is
+// to_dense(), sqrt_dim = (dimension as f32).sqrt(), the row's magnitude whatever its bits (never 0)
+inline float h_bin_distance(int metric, const float* pm1, float sqrt_dim, const float* q, float qmag, uint32_t dim) {
+    if (metric == NMN_METRIC_EUCLIDEAN) return h_eucl8(pm1, q, dim);
+    const float dot = h_dot8(pm1, q, dim);
+    if (metric == NMN_METRIC_DOT_PRODUCT) return -dot;
+    if (qmag == 0.0f) return 1.0f;
+    const float den = sqrt_dim * qmag;
+    const float sim = dot / den;
+    return 1.0f - sim;
+}
+
 // ---- device graph --------------------------------------------------------------------------------------------------------------
 struct GraphDev {
     const float* corpus;    // the flat index's rows, stride ld
     const float* norms;     // simd::magnitude of every row (ingest kernels)
-    const uint8_t* codes;   // quantized handle: the codes, stride ld8 (dim rounded up to 16, the padding zero)
+    const uint8_t* codes;   // quantized handle: the codes, stride ld8 (dim rounded up to 16, the padding zero); binary handle: the
+                            // BinaryVector words, stride ld8 bytes (ceil(dim / 64) words rounded up to 2, the padding zero)
     const float4* rec;      // quantized handle: {scale, min_val, simd::magnitude(dequantize()), squared_magnitude()} per row
     const uint32_t* l0;     // [n][m0] layer-0 neighbour slots, id-ascending
     const uint32_t* l0cnt;  // [n]
@@ -618,6 +671,111 @@ __device__ __forceinline__ float q8_distance(const uint8_t* __restrict__ row, co
     return 1.0f - dot / (rec.z * qs.mag);
 }
 
+// One whole chunk of a Binary row for a lane's four chains: `nb` holds the INVERTED bits of elements 8c + 4h .. 8c + 4h + 3 at
+// bit positions s .. s + 3, y the query's four elements.  Dot: (+-1.0) * q is q with its sign kept or flipped, exactly — the sign
+// bit is flipped where the row's bit is clear, no multiply.  Euclidean: d = (+-1.0) - q, then d * d rounded and added, unfused.
+template <bool EU>
+__device__ __forceinline__ void bin_chunk(float& a0, float& a1, float& a2, float& a3, uint32_t nb, uint32_t s, const float4 y) {
+    const uint32_t f0 = (nb << (31u - s)) & 0x80000000u, f1 = (nb << (30u - s)) & 0x80000000u;
+    const uint32_t f2 = (nb << (29u - s)) & 0x80000000u, f3 = (nb << (28u - s)) & 0x80000000u;
+    if (EU) {
+        const float d0 = __uint_as_float(0x3F800000u | f0) - y.x, d1 = __uint_as_float(0x3F800000u | f1) - y.y;
+        const float d2 = __uint_as_float(0x3F800000u | f2) - y.z, d3 = __uint_as_float(0x3F800000u | f3) - y.w;
+        a0 = a0 + d0 * d0;
+        a1 = a1 + d1 * d1;
+        a2 = a2 + d2 * d2;
+        a3 = a3 + d3 * d3;
+    } else {
+        a0 = a0 + __uint_as_float(__float_as_uint(y.x) ^ f0);
+        a1 = a1 + __uint_as_float(__float_as_uint(y.y) ^ f1);
+        a2 = a2 + __uint_as_float(__float_as_uint(y.z) ^ f2);
+        a3 = a3 + __uint_as_float(__float_as_uint(y.w) ^ f3);
+    }
+}
+
+// One 16-byte load of a Binary row: chunks 0 .. lim - 1 of its sixteen (FULL: all of them, no test), a dword — four chunks — per
+// turn of a loop that is NOT unrolled, to keep the code short: the dword is picked by wave-uniform selects.
+template <bool EU, bool FULL>
+__device__ __forceinline__ void bin_load16(float& a0, float& a1, float& a2, float& a3, const uint4 x, uint32_t lim, uint32_t sh,
+                                           const float4* qj) {
+#pragma unroll 1
+    for (uint32_t d = 0; d < 4u; d++) {
+        if (!FULL && 4u * d >= lim) break;
+        const uint32_t nb = ~(d == 0u ? x.x : (d == 1u ? x.y : (d == 2u ? x.z : x.w)));
+        const float4* qd = qj + 8u * d;
+#pragma unroll
+        for (uint32_t b = 0; b < 4u; b++)
+            if (FULL || 4u * d + b < lim) bin_chunk<EU>(a0, a1, a2, a3, nb, 8u * b + sh, qd[2u * b]);
+    }
+}
+
+// distance_dense on a BinaryVector row, by the same PAIR of lanes as pair_distance.  One 16-byte load carries 128 bits, sixteen
+// chunks of eight; both lanes of the pair issue it (one address, one request) and lane h takes bits 8c + 4h .. 8c + 4h + 3 of every
+// chunk c, its four chains, in ascending c.  `full` loads hold sixteen whole chunks each and run PF at a time without a test per
+// chunk; the one load after them (when dim is no multiple of 128) holds the remaining whole chunks and the tail bits, is issued
+// before the others, and is walked under the test `chunk < rem` — dim is wave-uniform, so the test is a scalar branch and a chunk
+// past the last whole one contributes NOTHING: no term is formed for it (what masking the query to +0.0 would give the dot, and what
+// Euclidean needs, where (-1 - 0)^2 = 1).  A 128-dimension row is the single load of the first pass.  The scalar tail follows the
+// lane sum, bit by bit.  Both lanes return the sum.
+template <bool EU>
+__device__ __forceinline__ float bin_sum(const uint8_t* __restrict__ row, const float* q, uint32_t dim, uint32_t h) {
+    const uint32_t chunks = dim >> 3, full = chunks >> 4, rem = chunks & 15u;
+    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
+    const uint4* r16 = reinterpret_cast<const uint4*>(row);
+    const float4* q4 = reinterpret_cast<const float4*>(q + 4u * h);
+    const uint4 zu = make_uint4(0u, 0u, 0u, 0u);
+    const uint32_t sh = 4u * h;
+    uint4 xr = zu;
+    if ((dim & 127u) != 0u) xr = r16[full];  // (the row's last 16 bytes: ld8 = 16 ceil(dim / 128))
+    constexpr int PF = 4;
+    for (uint32_t j0 = 0; j0 < full; j0 += PF) {
+        uint4 x[PF];
+#pragma unroll
+        for (int i = 0; i < PF; i++) x[i] = j0 + (uint32_t)i < full ? r16[j0 + (uint32_t)i] : zu;
+#pragma unroll
+        for (int i = 0; i < PF; i++) {
+            const uint32_t j = j0 + (uint32_t)i;
+            if (j < full) bin_load16<EU, true>(a0, a1, a2, a3, x[i], 16u, sh, q4 + 32u * j);
+        }
+    }
+    if (rem) bin_load16<EU, false>(a0, a1, a2, a3, xr, rem, sh, q4 + 32u * full);
+    const float b0 = __shfl_xor(a0, 1), b1 = __shfl_xor(a1, 1), b2 = __shfl_xor(a2, 1), b3 = __shfl_xor(a3, 1);
+    float r = -0.0f;
+    r = r + (h ? b0 : a0);
+    r = r + (h ? b1 : a1);
+    r = r + (h ? b2 : a2);
+    r = r + (h ? b3 : a3);
+    r = r + (h ? a0 : b0);
+    r = r + (h ? a1 : b1);
+    r = r + (h ? a2 : b2);
+    r = r + (h ? a3 : b3);
+    const uint32_t tail = dim & 7u;
+    if (tail) {  // byte `rem` of the last load: the bits of elements 8 chunks .. dim - 1
+        const uint32_t dw = rem >> 2;
+        const uint32_t wv = dw == 0u ? xr.x : (dw == 1u ? xr.y : (dw == 2u ? xr.z : xr.w));
+        const uint32_t tb = wv >> (8u * (rem & 3u));
+        for (uint32_t t = 0; t < tail; t++) {
+            const float e = ((tb >> t) & 1u) ? 1.0f : -1.0f;
+            const float y = q[8u * chunks + t];
+            if (EU) {
+                const float d = e - y;
+                r = r + d * d;
+            } else {
+                r = r + (e > 0.0f ? y : -y);
+            }
+        }
+    }
+    return r;
+}
+__device__ __forceinline__ float bin_distance(const uint8_t* __restrict__ row, const float* q, float qmag, float sqrt_dim, uint32_t dim,
+                                              int metric, uint32_t h) {
+    if (metric == NMN_METRIC_EUCLIDEAN) return d_sqrt(bin_sum<true>(row, q, dim, h));
+    const float r = bin_sum<false>(row, q, dim, h);
+    if (metric == NMN_METRIC_DOT_PRODUCT) return -r;
+    if (qmag == 0.0f) return 1.0f;
+    return 1.0f - r / (sqrt_dim * qmag);
+}
+
 // One query per wave (one wave per workgroup).  SPILL == false: both heaps in LDS; a query whose candidate heap fills up is flagged
 // and left.  SPILL == true: workgroup b answers the flagged queries b, b + grid, ... from scratch with both heaps in its region of
 // global memory (candidates: n entries, the proven bound — nothing is pushed twice).
@@ -636,11 +794,14 @@ __device__ __forceinline__ float q8_distance(const uint8_t* __restrict__ row, co
 // arithmetic above.  The two lanes of a pair score one node and agree on its kind; the pairs of one pass may not, so both sides run
 // under exec masks — the one lane-divergent branch of the scoring path.  These instantiations serve uniform launches as well
 // (a.qk / a.qef / a.qkind / a.qccap null).  MIX is a template parameter so that every other instantiation stays the code it was.
-template <bool SPILL, bool Q8, bool PERQ, int QK = 0, bool MIX = false>
+// BIN (dense queries only: QK == 0): the rows are BinaryVectors — g.codes holds their words, g.ld8 apart — scored by bin_distance;
+// nothing else of the walk changes.  BIN is a template parameter for the same reason.
+template <bool SPILL, bool Q8, bool PERQ, int QK = 0, bool MIX = false, bool BIN = false>
 __global__ __launch_bounds__(64) void hnsw_search_kernel(SearchArgs a) {
     static_assert(QK == 0 || (QK == 1 && !Q8 && !PERQ) || (QK == 2 && Q8 && !PERQ) || (QK == 3 && PERQ),
                   "query kinds: 1 on dense rows, 2 on quantized rows, 3 = a kind per query of a per-query launch");
     static_assert(!MIX || (!Q8 && PERQ && QK == 3), "sparse nodes: dense storage, the per-query form");
+    static_assert(!BIN || (!Q8 && QK == 0 && !MIX), "binary rows: dense queries, a storage of their own");
     extern __shared__ float4 smem4[];
     const GraphDev& g = a.g;
     const uint32_t lane = threadIdx.x, p = lane >> 1, h = lane & 1u;
@@ -716,7 +877,10 @@ __global__ __launch_bounds__(64) void hnsw_search_kernel(SearchArgs a) {
             qside.sum = pair_sum(qv, g.dim, h);
             if (g.metric == NMN_METRIC_EUCLIDEAN) qside.sq = -pair_distance(qv, 0.f, qv, 0.f, g.dim, NMN_METRIC_DOT_PRODUCT, h);
         }
+        float sqrt_dim = 0.0f;
+        if constexpr (BIN) sqrt_dim = d_sqrt((float)g.dim);  // (dimension as f32).sqrt(), hnsw.rs:981-984
         auto row_distance = [&](uint32_t node) -> float {
+            if constexpr (BIN) return bin_distance(g.codes + (size_t)node * g.ld8, qv, qmag, sqrt_dim, g.dim, g.metric, h);
             if constexpr (MIX) {
                 const uint4 rec = a.nrec[node];
                 if (rec.z != kNone) {
@@ -735,9 +899,9 @@ __global__ __launch_bounds__(64) void hnsw_search_kernel(SearchArgs a) {
                 return pair_distance(g.corpus + (size_t)node * g.ld, g.norms[node], qv, qmag, g.dim, g.metric, h);
         };
         // distance evaluations.  The reference scores the entry of every search_layer* call again (one per greedy layer, one for
-        // search_layer); this kernel carries the distance along.  A quantized handle counts the evaluations the reference makes,
+        // search_layer); this kernel carries the distance along.  A quantized or binary handle counts the evaluations the reference makes,
         // as the host walk does; a dense handle keeps the count it has always reported.
-        uint32_t evals = Q8 ? g.max_layer + 1u : 1u;
+        uint32_t evals = Q8 || BIN ? g.max_layer + 1u : 1u;
         // greedy descent, hnsw.rs:2086-2092 / 2170-2200
         uint32_t cur = g.entry;
         float cur_d = row_distance(cur);
@@ -914,6 +1078,13 @@ struct nmn_hnsw {
     void* d_codes = nullptr;  // [vec_cap][ld8] u8
     void* d_rec = nullptr;    // [vec_cap] float4 {scale, min_val, magnitude, squared_magnitude}
     uint32_t ld8 = 0;
+    // binary handle: BinaryVector per row — words [n][bin_w], bin_w = ceil(dim / 64); rows holds to_dense(), the +-1 row (what a
+    // quantized handle keeps its dequantized row for: the node's own query and the Euclidean / DotProduct pruning).  On the device
+    // d_codes holds the words, ld8 = 16 ceil(dim / 128) bytes apart; d_rec stays null.
+    std::vector<uint64_t> bwords;
+    uint32_t bin_w = 0;
+    int bin_method = NMN_BINARY_SIGN;
+    float sqrt_dim = 0.0f;  // (dimension as f32).sqrt(): every Binary row's magnitude, hnsw.rs:981-984
     // EmbeddingStorage::Sparse nodes of a dense handle (docs/hnsw.md §15).  Empty until the first one is inserted; from then on one
     // slot per node: sp_nnz (kNone: a Dense node), sp_off into sp_pos / sp_val (the canonical entries), sp_mag64 = magnitude_f64().
     // rows holds to_dense() of such a node, mags its SparseVector::magnitude() (what the query side divides by).
@@ -1118,6 +1289,8 @@ inline float node_distance(const nmn_hnsw* h, uint32_t node, const float* q, con
         return h_q8_distance(h->cfg.distance_metric, h->codes.data() + (size_t)node * h->dim, h->qscale[node], h->qmin[node],
                              h->mags[node], h->qxsq[node], q, hq, h->dim);
     const int metric = h->cfg.distance_metric;
+    if (h->storage == NMN_HNSW_STORAGE_BINARY)
+        return h_bin_distance(metric, h->rows.data() + (size_t)node * h->dim, h->sqrt_dim, q, hq.mag, h->dim);
     if (metric != NMN_METRIC_EUCLIDEAN && node_is_sparse(h, node)) {
         const SpView s = node_entries(h, node);
         const float dot = h_sparse_dot(s.pos, s.val, s.nnz, q);
@@ -1146,8 +1319,16 @@ inline float sparse_node_sparse_query(const nmn_hnsw* h, uint32_t node, const Sp
 // dequantized rows and their simd::magnitude there: the (Quantized, Quantized) arms).  With a Sparse node in the pair
 // (hnsw.rs:2453-2459, 2558-2565, 2641-2643): Sparse x Sparse is cosine_similarity (583-600) / euclidean_distance / dot; Dense x
 // Sparse, either order, is cosine_distance_dense (606-632) / simd::euclidean_distance on to_dense() / dot_dense.
+// Binary x Binary: Cosine is 1.0 - ba.similarity(bb) = 1.0 - (1.0 - hamming as f32 / dimension as f32) on the words (hnsw.rs:2516-2518,
+// binary_quantization.rs:137-142) — NOT the query side's formula; Euclidean / DotProduct are the dense arithmetic on the +-1 rows.
 inline float pair_of_nodes_distance(const nmn_hnsw* h, uint32_t a, uint32_t b) {
     const int metric = h->cfg.distance_metric;
+    if (h->storage == NMN_HNSW_STORAGE_BINARY && metric == NMN_METRIC_COSINE) {
+        const uint32_t hd = h_bin_hamming(h->bwords.data() + (size_t)a * h->bin_w, h->bwords.data() + (size_t)b * h->bin_w, h->bin_w);
+        const float ratio = (float)hd / (float)h->dim;
+        const float sim = 1.0f - ratio;
+        return 1.0f - sim;
+    }
     const bool sa = node_is_sparse(h, a), sb = node_is_sparse(h, b);
     if (sa && sb) {
         const SpView x = node_entries(h, a), y = node_entries(h, b);
@@ -1536,6 +1717,13 @@ nmn_status upload_graph(nmn_hnsw* h) {
 nmn_status upload_codes(nmn_hnsw* h, uint64_t first, uint64_t count) {
     if (count == 0) return NMN_OK;
     const uint32_t dim = h->dim, ld8 = h->ld8;
+    if (h->storage == NMN_HNSW_STORAGE_BINARY) {  // the words alone, the padding word (an odd count) zero
+        std::vector<uint8_t> stage((size_t)count * ld8, 0);
+        for (uint64_t i = 0; i < count; i++)
+            memcpy(stage.data() + (size_t)i * ld8, h->bwords.data() + (size_t)(first + i) * h->bin_w, (size_t)h->bin_w * 8);
+        HN_TRY(hipMemcpy((uint8_t*)h->d_codes + (size_t)first * ld8, stage.data(), stage.size(), hipMemcpyHostToDevice));
+        return NMN_OK;
+    }
     std::vector<uint8_t> stage((size_t)count * ld8, 0);
     std::vector<float> rec((size_t)count * 4);
     for (uint64_t i = 0; i < count; i++) {
@@ -1555,10 +1743,12 @@ nmn_status upload_codes(nmn_hnsw* h, uint64_t first, uint64_t count) {
 nmn_status alloc_codes(nmn_hnsw* h, uint64_t cap, uint64_t have) {
     void *nc = nullptr, *nr = nullptr;
     HN_TRY(hipMalloc(&nc, std::max<size_t>((size_t)cap * h->ld8, 256)));
-    hipError_t e = hipMalloc(&nr, std::max<size_t>((size_t)cap * 16, 256));
-    if (e != hipSuccess) {
-        (void)hipFree(nc);
-        return set_error_hip(e, "hipMalloc");
+    if (h->storage == NMN_HNSW_STORAGE_QUANTIZED) {  // (a binary handle keeps no record per row)
+        hipError_t e = hipMalloc(&nr, std::max<size_t>((size_t)cap * 16, 256));
+        if (e != hipSuccess) {
+            (void)hipFree(nc);
+            return set_error_hip(e, "hipMalloc");
+        }
     }
     if (h->d_codes) (void)hipFree(h->d_codes);
     if (h->d_rec) (void)hipFree(h->d_rec);
@@ -1573,7 +1763,7 @@ nmn_status ensure_vectors(nmn_hnsw* h, uint64_t need) {
     uint64_t cap = std::max<uint64_t>(h->vec_cap, 1024);
     while (cap < need) cap *= 2;
     if (h->cfg.max_nodes > 0) cap = std::min<uint64_t>(cap, std::max<uint64_t>(h->cfg.max_nodes, need));
-    if (h->storage == NMN_HNSW_STORAGE_QUANTIZED) return alloc_codes(h, cap, h->level.size());
+    if (h->storage != NMN_HNSW_STORAGE_DENSE) return alloc_codes(h, cap, h->level.size());
     nmn_index_desc d{};
     d.dim = h->dim;
     d.capacity_rows = cap;
@@ -1658,8 +1848,12 @@ SearchArgs graph_args(const nmn_hnsw* h, uint32_t n) {
 }
 
 template <bool SPILL>
-void launch_walk(bool q8, bool perq, int qkind, bool mix, uint32_t grid, size_t lds, hipStream_t s, const SearchArgs& a) {
-    if (mix)  // a handle with sparse nodes, Cosine / DotProduct: one form for uniform and per-query launches alike
+void launch_walk(bool q8, bool bin, bool perq, int qkind, bool mix, uint32_t grid, size_t lds, hipStream_t s, const SearchArgs& a) {
+    if (bin && perq)  // binary rows: dense queries only (every other query form is refused before it gets here)
+        hipLaunchKernelGGL((hnsw_search_kernel<SPILL, false, true, 0, false, true>), dim3(grid), dim3(64), lds, s, a);
+    else if (bin)
+        hipLaunchKernelGGL((hnsw_search_kernel<SPILL, false, false, 0, false, true>), dim3(grid), dim3(64), lds, s, a);
+    else if (mix)  // a handle with sparse nodes, Cosine / DotProduct: one form for uniform and per-query launches alike
         hipLaunchKernelGGL((hnsw_search_kernel<SPILL, false, true, 3, true>), dim3(grid), dim3(64), lds, s, a);
     else if (qkind == 3 && q8)
         hipLaunchKernelGGL((hnsw_search_kernel<SPILL, true, true, 3>), dim3(grid), dim3(64), lds, s, a);
@@ -1739,7 +1933,8 @@ nmn_status enqueue_walk_locked(nmn_hnsw* h, nmn_hnsw::Scratch* sc, const float* 
     HN_TRY(grow(sc->evals, (size_t)nq * 4, s, &synced));
     HN_TRY(grow(sc->spill, (size_t)regions * region * sizeof(Ent), s, &synced));
     SearchArgs a = graph_args(h, n);
-    const bool q8 = h->storage == NMN_HNSW_STORAGE_QUANTIZED;
+    const bool q8 = h->storage == NMN_HNSW_STORAGE_QUANTIZED, bin = h->storage == NMN_HNSW_STORAGE_BINARY;
+    if (bin && w.qkind != 0) return set_error(NMN_ERR_CONFIGURATION, "HNSW: a Binary-storage handle walks dense queries only");
     a.k = w.k;
     a.ef = w.ef;
     a.kstride = kstride;
@@ -1751,7 +1946,7 @@ nmn_status enqueue_walk_locked(nmn_hnsw* h, nmn_hnsw::Scratch* sc, const float* 
     // Sparse nodes are scored by their own arithmetic under Cosine / DotProduct only (Euclidean is the dense arithmetic on the rows)
     const int metric = w.cosine ? NMN_METRIC_COSINE : h->cfg.distance_metric;
     a.g.metric = metric;
-    const bool mix = !q8 && h->n_sparse > 0 && metric != NMN_METRIC_EUCLIDEAN;
+    const bool mix = !q8 && !bin && h->n_sparse > 0 && metric != NMN_METRIC_EUCLIDEAN;
     a.nrec = mix ? (const uint4*)h->d_nrec.p : nullptr;
     a.nent = mix ? (const uint2*)h->d_nent.p : nullptr;
     a.kind_u = w.qkind == 3 ? 0u : (uint32_t)w.qkind;
@@ -1779,7 +1974,7 @@ nmn_status enqueue_walk_locked(nmn_hnsw* h, nmn_hnsw::Scratch* sc, const float* 
             a.rcap = w.rcap_lds;
             a.ccap = ccap;
             const size_t lds = fixed + ((size_t)a.rcap + a.ccap) * sizeof(Ent);
-            launch_walk<false>(q8, perq, w.qkind, mix, nl, lds, s, a);
+            launch_walk<false>(q8, bin, perq, w.qkind, mix, nl, lds, s, a);
             HN_TRY(hipGetLastError());
         }
         if (nl < nb)  // results heaps no wave can keep in LDS: these queries go straight to the spill launch
@@ -1787,7 +1982,7 @@ nmn_status enqueue_walk_locked(nmn_hnsw* h, nmn_hnsw::Scratch* sc, const float* 
         a.nq = nb;
         a.rcap = s_rcap;
         a.ccap = s_ccap;
-        launch_walk<true>(q8, perq, w.qkind, mix, std::min(regions, nb), fixed, s, a);
+        launch_walk<true>(q8, bin, perq, w.qkind, mix, std::min(regions, nb), fixed, s, a);
         HN_TRY(hipGetLastError());
     }
     return NMN_OK;
@@ -1819,6 +2014,17 @@ nmn_status enqueue_search(nmn_hnsw* h, const float* q_dev, uint32_t nq, uint32_t
     std::lock_guard<std::mutex> slk(sc->mu);
     return enqueue_search_locked(h, sc, q_dev, nq, k, ef, o_ids, o_sc, o_cnt, s);
 }
+
+// What a Binary-storage handle does not serve (docs/hnsw.md §18): refused before anything is written or enqueued.
+nmn_status refuse_binary(const nmn_hnsw* h, const char* entry, const char* why) {
+    if (h->storage != NMN_HNSW_STORAGE_BINARY) return NMN_OK;
+    char buf[256];
+    snprintf(buf, sizeof buf, "HNSW: %s is not served on a handle with Binary storage (%s)", entry, why);
+    return set_error(NMN_ERR_CONFIGURATION, buf);
+}
+constexpr const char* kBinNoRows = "it keeps one bit per dimension and no f32 rows on the device";
+constexpr const char* kBinQueries = "Binary rows are walked with dense queries only";
+constexpr const char* kBinNodes = "a binary handle holds Binary nodes only";
 
 // search_with_hnsw_and_metric's candidate count (lib.rs:2578), served as min(c, len): search_layer runs with max(ef_search, c) and any
 // ef >= len keeps every node the walk reaches (the rule nmn_engine_search_with_hnsw applies to k)
@@ -1875,6 +2081,7 @@ nmn_status check_metric_call(nmn_hnsw* h, uint32_t top_k, const nmn_xmetric* m) 
     if (!h || !m) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
     if (!xmetric_valid(m)) return set_error(NMN_ERR_CONFIGURATION, "unknown extended distance metric");
     if (top_k == 0) return set_error(NMN_ERR_INVALID_TOP_K, "top_k == 0");
+    if (const nmn_status sb = refuse_binary(h, "nmn_hnsw_search_metric", kBinNoRows); sb != NMN_OK) return sb;
     if (h->storage != NMN_HNSW_STORAGE_DENSE)
         return set_error(NMN_ERR_CONFIGURATION,
                          "HNSW: nmn_hnsw_search_metric re-ranks with the rows of nmn_hnsw_vectors(h), and a quantized handle keeps no f32 "
@@ -1936,7 +2143,7 @@ nmn_status create_handle(const nmn_hnsw_config* cfg, int storage, uint32_t dim, 
     h->vec_cap = 0;
     const uint64_t cap_rows = cfg->max_nodes > 0 ? std::min<uint64_t>(std::max<uint64_t>(capacity_hint, 1), cfg->max_nodes)
                                                  : std::max<uint64_t>(capacity_hint, 1);
-    if (storage == NMN_HNSW_STORAGE_QUANTIZED) {
+    if (storage != NMN_HNSW_STORAGE_DENSE) {
         int ndev = 0;
         if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
             (void)hipGetLastError();
@@ -1948,6 +2155,11 @@ nmn_status create_handle(const nmn_hnsw_config* cfg, int storage, uint32_t dim, 
         HN_TRY(hipSetDevice(dev));
         h->device = dev;
         h->ld8 = (dim + 15u) & ~15u;
+        if (storage == NMN_HNSW_STORAGE_BINARY) {
+            h->bin_w = (dim + 63u) / 64u;
+            h->ld8 = 16u * ((dim + 127u) / 128u);  // ldw = bin_w rounded up to 2 words: 16-byte rows
+            h->sqrt_dim = sqrtf((float)dim);
+        }
         st = alloc_codes(h.get(), cap_rows, 0);
         if (st != NMN_OK) {
             if (h->d_codes) (void)hipFree(h->d_codes);
@@ -1993,11 +2205,25 @@ extern "C" nmn_status nmn_hnsw_create_with_storage(const nmn_hnsw_config* cfg, i
     *out = nullptr;
     if (storage == NMN_HNSW_STORAGE_AUTO)
         return set_error(NMN_ERR_CONFIGURATION, "HNSW: HNSWStorageStrategy::Auto (sparse storage) is not served; Dense and Quantized are");
-    if (storage != NMN_HNSW_STORAGE_DENSE && storage != NMN_HNSW_STORAGE_QUANTIZED)
+    if (storage != NMN_HNSW_STORAGE_DENSE && storage != NMN_HNSW_STORAGE_QUANTIZED && storage != NMN_HNSW_STORAGE_BINARY)
         return set_error(NMN_ERR_CONFIGURATION, "HNSW: unknown storage strategy");
     nmn_hnsw_config c = *cfg;
     c.storage = NMN_HNSW_STORAGE_DENSE;  // (the old field plays no part here)
-    return create_handle(&c, storage, dim, capacity_hint, device, out);
+    return create_handle(&c, storage, dim, capacity_hint, device, out);  // (Binary: BinaryThreshold::Sign)
+}
+
+// Every node EmbeddingStorage::Binary(BinaryVector::from_dense(row, threshold)), docs/hnsw.md §18
+extern "C" nmn_status nmn_hnsw_create_binary(const nmn_hnsw_config* cfg, int32_t binary_threshold, uint32_t dim, uint64_t capacity_hint,
+                                             int32_t device, nmn_hnsw** out) {
+    if (!cfg || !out) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    *out = nullptr;
+    if (binary_threshold < NMN_BINARY_SIGN || binary_threshold > NMN_BINARY_MEDIAN)
+        return set_error(NMN_ERR_CONFIGURATION, "HNSW: binary_threshold must be NMN_BINARY_SIGN, _MEAN or _MEDIAN");
+    nmn_hnsw_config c = *cfg;
+    c.storage = NMN_HNSW_STORAGE_DENSE;
+    const nmn_status st = create_handle(&c, NMN_HNSW_STORAGE_BINARY, dim, capacity_hint, device, out);
+    if (st == NMN_OK) (*out)->bin_method = binary_threshold;
+    return st;
 }
 
 extern "C" nmn_status nmn_hnsw_destroy(nmn_hnsw* h) {
@@ -2058,9 +2284,18 @@ nmn_status insert_rows(nmn_hnsw* h, const float* rows_host, uint64_t n, const Sp
         std::lock_guard<std::mutex> hl(h->host_mu);
         HN_TRY(hipStreamSynchronize(h->host_stream));
     }
-    const bool q8 = h->storage == NMN_HNSW_STORAGE_QUANTIZED;
+    const bool q8 = h->storage == NMN_HNSW_STORAGE_QUANTIZED, bin = h->storage == NMN_HNSW_STORAGE_BINARY;
     const uint32_t dim = h->dim;
-    if (q8) {  // insert_quantized, hnsw.rs:1711-1714: from_dense; what the host keeps as the row is dequantize()
+    if (bin) {  // insert_embedding(Binary(from_dense(row, threshold))); what the host keeps as the row is to_dense()
+        h->rows.resize((have + n) * dim);
+        h->bwords.resize((have + n) * h->bin_w);
+        h->mags.resize(have + n, h->sqrt_dim);
+        std::vector<float> tmp;
+        for (uint64_t r = have; r < have + n; r++)
+            h_bin_from_dense(rows_host + (r - have) * dim, dim, h->bin_method, h->bwords.data() + r * h->bin_w, h->rows.data() + r * dim, tmp);
+        st = ensure_vectors(h, have + n);
+        if (st == NMN_OK && have + n <= h->vec_cap) st = upload_codes(h, have, n);
+    } else if (q8) {  // insert_quantized, hnsw.rs:1711-1714: from_dense; what the host keeps as the row is dequantize()
         h->rows.resize((have + n) * dim);
         h->codes.resize((have + n) * dim);
         h->qscale.resize(have + n);
@@ -2084,6 +2319,10 @@ nmn_status insert_rows(nmn_hnsw* h, const float* rows_host, uint64_t n, const Sp
     }
     if (st != NMN_OK) {
         h->rows.resize(have * dim);
+        if (bin) {
+            h->bwords.resize(have * h->bin_w);
+            h->mags.resize(have);
+        }
         if (q8) {
             h->codes.resize(have * dim);
             h->qscale.resize(have);
@@ -2112,7 +2351,7 @@ nmn_status insert_rows(nmn_hnsw* h, const float* rows_host, uint64_t n, const Sp
             h->mags.push_back(sp->mag[r]);  // SparseVector::magnitude(): what distance_dense / distance_sparse divide by
             h->n_sparse++;
             if (sp->dup[r]) h->n_sparse_dup++;
-        } else if (!q8) {
+        } else if (!q8 && !bin) {
             const float* v = h->rows.data() + (have + i) * dim;
             h->mags.push_back(sqrtf(h_dot8(v, v, dim)));  // simd::magnitude, hnsw.rs:198-229
         }
@@ -2124,6 +2363,7 @@ nmn_status insert_rows(nmn_hnsw* h, const float* rows_host, uint64_t n, const Sp
 
 nmn_status refuse_sparse_on_q8(const nmn_hnsw* h) {
     if (h->storage == NMN_HNSW_STORAGE_DENSE) return NMN_OK;
+    if (const nmn_status sb = refuse_binary(h, "nmn_hnsw_insert_sparse / nmn_hnsw_insert_auto", kBinNodes); sb != NMN_OK) return sb;
     return set_error(NMN_ERR_CONFIGURATION,
                      "HNSW: sparse nodes are served on a dense handle only (the Quantized x Sparse arms are out of scope)");
 }
@@ -2216,9 +2456,24 @@ extern "C" uint64_t nmn_hnsw_entry_point(const nmn_hnsw* h) { return h ? h->entr
 extern "C" uint32_t nmn_hnsw_max_layer(const nmn_hnsw* h) { return h ? h->max_layer : 0; }
 extern "C" nmn_index* nmn_hnsw_vectors(nmn_hnsw* h) { return h ? h->vectors : nullptr; }
 extern "C" int32_t nmn_hnsw_storage(const nmn_hnsw* h) { return h ? h->storage : -1; }
+extern "C" int32_t nmn_hnsw_binary_threshold(const nmn_hnsw* h) {
+    return h && h->storage == NMN_HNSW_STORAGE_BINARY ? h->bin_method : -1;
+}
+
+extern "C" nmn_status nmn_hnsw_binary_row(nmn_hnsw* h, uint64_t node, uint64_t* words_out, uint32_t cap_words) {
+    if (!h) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    std::shared_lock<std::shared_mutex> g(h->rw);
+    if (h->storage != NMN_HNSW_STORAGE_BINARY) return set_error(NMN_ERR_CONFIGURATION, "HNSW: the handle's storage is not Binary");
+    if (node >= h->level.size()) return set_error(NMN_ERR_NOT_FOUND, "HNSW: no such node");
+    if (!words_out) return NMN_OK;
+    if (cap_words < h->bin_w) return set_error(NMN_ERR_BUFFER_TOO_SMALL, "nmn_hnsw_binary_row");
+    memcpy(words_out, h->bwords.data() + node * h->bin_w, (size_t)h->bin_w * 8);
+    return NMN_OK;
+}
 
 extern "C" nmn_status nmn_hnsw_quantized_row(nmn_hnsw* h, uint64_t node, uint8_t* codes_out, float* scale, float* min_val) {
     if (!h) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (const nmn_status sb = refuse_binary(h, "nmn_hnsw_quantized_row", "nmn_hnsw_binary_row returns its words"); sb != NMN_OK) return sb;
     std::shared_lock<std::shared_mutex> g(h->rw);
     if (h->storage != NMN_HNSW_STORAGE_QUANTIZED) return set_error(NMN_ERR_CONFIGURATION, "HNSW: the handle's storage is not Quantized");
     if (node >= h->level.size()) return set_error(NMN_ERR_NOT_FOUND, "HNSW: no such node");
@@ -2228,7 +2483,7 @@ extern "C" nmn_status nmn_hnsw_quantized_row(nmn_hnsw* h, uint64_t node, uint8_t
     return NMN_OK;
 }
 
-// HNSWIndex::get_vector: the row as stored (Dense), dequantize() (Quantized)
+// HNSWIndex::get_vector: the row as stored (Dense), dequantize() (Quantized), to_dense() (Binary)
 extern "C" nmn_status nmn_hnsw_get_vector(nmn_hnsw* h, uint64_t node, float* out) {
     if (!h || !out) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
     std::shared_lock<std::shared_mutex> g(h->rw);
@@ -2247,6 +2502,9 @@ extern "C" nmn_status nmn_hnsw_memory_stats(nmn_hnsw* h, nmn_hnsw_memstats* out)
     if (h->storage == NMN_HNSW_STORAGE_QUANTIZED) {
         out->quantized_count = n;
         out->embedding_bytes = n * (16ull + h->dim);
+    } else if (h->storage == NMN_HNSW_STORAGE_BINARY) {  // BinaryVector::memory_bytes, binary_quantization.rs:174-179
+        out->binary_count = n;
+        out->embedding_bytes = n * 8ull * h->bin_w;
     } else {
         // a Sparse node: SparseVector::memory_bytes (sparse_vector.rs:1064-1068) = size_of::<SparseVector>() (56 on a 64-bit
         // target) + 4 capacity + 4 capacity, the capacities taken as the lengths (what a cloned vector has; docs/hnsw.md §15)
@@ -2296,7 +2554,8 @@ extern "C" uint64_t nmn_hnsw_hbm_bytes(nmn_hnsw* h) {
     uint64_t t = h->d_l0.cap + h->d_l0cnt.cap + h->d_upidx.cap + h->d_up.cap + h->d_upcnt.cap + h->d_nrec.cap + h->d_nent.cap + h->d_live.cap;
     uint64_t a = 0, b = 0, c = 0;
     if (h->vectors && nmn_index_hbm_bytes(h->vectors, &a, &b, &c) == NMN_OK) t += a + b + c;
-    if (h->d_codes) t += std::max<uint64_t>(h->vec_cap * h->ld8, 256) + std::max<uint64_t>(h->vec_cap * 16, 256);
+    if (h->d_codes) t += std::max<uint64_t>(h->vec_cap * h->ld8, 256);
+    if (h->d_rec) t += std::max<uint64_t>(h->vec_cap * 16, 256);
     return t;
 }
 
@@ -2789,7 +3048,9 @@ nmn_status host_walk_call(nmn_hnsw* h, HostWalk& me, nmn_search_stats* stats) {
     }
     if (stats) {
         stats->rows_scanned = me.evals;
-        stats->bytes_scanned = h->storage == NMN_HNSW_STORAGE_QUANTIZED ? me.evals * (h->dim + 16ull) : me.evals * h->dim * 4;
+        stats->bytes_scanned = h->storage == NMN_HNSW_STORAGE_QUANTIZED ? me.evals * (h->dim + 16ull)
+                               : h->storage == NMN_HNSW_STORAGE_BINARY  ? me.evals * 8ull * h->bin_w
+                                                                         : me.evals * h->dim * 4;
         stats->fallback_queries = me.spilled;
         std::shared_lock<std::shared_mutex> g(h->rw);
         stats->sweep_kind = h->level.empty() ? NMN_SWEEP_NONE : NMN_SWEEP_GRAPH;
@@ -2891,6 +3152,7 @@ extern "C" nmn_status nmn_hnsw_search_sparse(nmn_hnsw* h, const uint64_t* indptr
                                              uint32_t nq, uint32_t k, uint32_t ef, uint64_t* out_ids, float* out_scores,
                                              uint32_t* out_counts, nmn_search_stats* stats) {
     if (!h) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (const nmn_status sb = refuse_binary(h, "nmn_hnsw_search_sparse", kBinQueries); sb != NMN_OK) return sb;
     if (k == 0) return set_error(NMN_ERR_INVALID_TOP_K, "k == 0");
     if (stats) {
         memset(stats, 0, sizeof *stats);
@@ -2918,6 +3180,7 @@ extern "C" nmn_status nmn_hnsw_search_sparse_multi(nmn_hnsw* h, const uint64_t* 
                                                    uint32_t nq, const uint32_t* k, const uint32_t* ef, uint32_t kstride,
                                                    uint64_t* out_ids, float* out_scores, uint32_t* out_counts, nmn_search_stats* stats) {
     if (!h) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (const nmn_status sb = refuse_binary(h, "nmn_hnsw_search_sparse_multi", kBinQueries); sb != NMN_OK) return sb;
     if (kstride == 0) return set_error(NMN_ERR_INVALID_TOP_K, "kstride == 0");
     if (stats) {
         memset(stats, 0, sizeof *stats);
@@ -3036,6 +3299,7 @@ extern "C" nmn_status nmn_hnsw_search_metric_multi(nmn_hnsw* h, const float* que
 namespace {
 nmn_status check_cache_call(nmn_hnsw* h, uint32_t k, const nmn_xmetric* m) {
     if (!h || !m) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (const nmn_status sb = refuse_binary(h, "nmn_hnsw_cache_search", kBinNoRows); sb != NMN_OK) return sb;
     if (h->storage != NMN_HNSW_STORAGE_DENSE)
         return set_error(NMN_ERR_CONFIGURATION,
                          "HNSW: nmn_hnsw_cache_search re-scores the stored form of its candidates, and a CacheIndex never holds "
@@ -3053,6 +3317,7 @@ void clear_stats(nmn_search_stats* stats) {
 
 extern "C" nmn_status nmn_hnsw_set_node_mask(nmn_hnsw* h, const uint64_t* nodes, uint64_t n, int32_t live) {
     if (!h || (!nodes && n)) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (const nmn_status sb = refuse_binary(h, "nmn_hnsw_set_node_mask", "only nmn_hnsw_cache_search reads the mask"); sb != NMN_OK) return sb;
     if (n == 0) return NMN_OK;
     std::unique_lock<std::shared_mutex> g(h->rw);
     for (uint64_t i = 0; i < n; i++)  // before anything is flipped: the call is all or nothing
@@ -3313,6 +3578,7 @@ extern "C" nmn_status nmn_hnsw_search_tt(nmn_hnsw* h, const uint32_t* shape, uin
                                          const uint64_t* core_off, const float* cores, uint32_t nq, uint32_t k, uint32_t ef,
                                          uint64_t* out_ids, float* out_scores, uint32_t* out_counts, nmn_search_stats* stats) {
     if (!h) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (const nmn_status sb = refuse_binary(h, "nmn_hnsw_search_tt", kBinQueries); sb != NMN_OK) return sb;
     if (k == 0) return set_error(NMN_ERR_INVALID_TOP_K, "k == 0");
     if (stats) {
         memset(stats, 0, sizeof *stats);
@@ -3421,6 +3687,7 @@ extern "C" nmn_status nmn_hnsw_search_tt_device(nmn_hnsw* h, const uint32_t* sha
                                                 const float* cores_dev, uint32_t nq, uint32_t k, uint32_t ef, uint64_t* out_ids_dev,
                                                 float* out_scores_dev, uint32_t* out_counts_dev, void* stream) {
     if (!h) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (const nmn_status sb = refuse_binary(h, "nmn_hnsw_search_tt_device", kBinQueries); sb != NMN_OK) return sb;
     if (k == 0) return set_error(NMN_ERR_INVALID_TOP_K, "k == 0");
     if (nq == 0) return NMN_OK;
     if (!cores_dev || !out_ids_dev || !out_scores_dev || !out_counts_dev) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
@@ -3451,6 +3718,7 @@ extern "C" nmn_status nmn_hnsw_search_tt_device(nmn_hnsw* h, const uint32_t* sha
 extern "C" nmn_status nmn_hnsw_insert_tt(nmn_hnsw* h, const uint32_t* shape, uint32_t n_cores, const uint32_t* ranks,
                                          const uint64_t* core_off, const float* cores, uint64_t n, uint64_t* ids_out) {
     if (!h || (!core_off && n)) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (const nmn_status sb = refuse_binary(h, "nmn_hnsw_insert_tt", kBinNodes); sb != NMN_OK) return sb;
     if (h->storage != NMN_HNSW_STORAGE_DENSE)
         return set_error(NMN_ERR_CONFIGURATION,
                          "HNSW: insert_tt_vector makes Dense nodes, which are served on a dense handle only (insert the reconstruction "
@@ -3779,6 +4047,7 @@ extern "C" nmn_status nmn_hnsw_get_config(const nmn_hnsw* h, nmn_hnsw_config* ou
 
 extern "C" nmn_status nmn_hnsw_save(nmn_hnsw* h, const char* path) {
     if (!h || !path) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (const nmn_status sb = refuse_binary(h, "nmn_hnsw_save", "the file format has no Binary rows section yet"); sb != NMN_OK) return sb;
     {
         std::shared_lock<std::shared_mutex> g(h->rw);
         if (h->n_sparse) return set_error(NMN_ERR_CONFIGURATION, kSaveSparseRefusal);  // before the file is touched

@@ -62,7 +62,9 @@ class HNSWConfig:
                    sparsity_threshold=c.sparsity_threshold, max_nodes=c.max_nodes, distance_metric=c.distance_metric)
 
 
-_STORAGE = {"dense": _capi.HNSW_STORAGE_DENSE, "auto": _capi.HNSW_STORAGE_AUTO, "quantized": _capi.HNSW_STORAGE_QUANTIZED}
+_STORAGE = {"dense": _capi.HNSW_STORAGE_DENSE, "auto": _capi.HNSW_STORAGE_AUTO, "quantized": _capi.HNSW_STORAGE_QUANTIZED,
+            "binary": _capi.HNSW_STORAGE_BINARY}
+_BINARY_THRESHOLD = {"sign": _capi.BINARY_SIGN, "mean": _capi.BINARY_MEAN, "median": _capi.BINARY_MEDIAN}
 
 
 def _storage_code(storage):
@@ -111,17 +113,28 @@ class HNSWBuildOptions:
 
 
 class GpuHnsw:
-    def __init__(self, dim, config=None, capacity_hint=0, device=-1, storage=None):
+    def __init__(self, dim, config=None, capacity_hint=0, device=-1, storage=None, binary_threshold=None):
         """storage None: nmn_hnsw_create (config.storage, dense only).  storage "dense" / "quantized": the strategy of
-        HNSWBuildOptions through nmn_hnsw_create_with_storage (config.storage is not read; "auto" is refused)."""
+        HNSWBuildOptions through nmn_hnsw_create_with_storage (config.storage is not read; "auto" is refused).  storage "binary":
+        every node EmbeddingStorage::Binary(BinaryVector::from_dense(row, threshold)) through nmn_hnsw_create_binary,
+        binary_threshold "sign" (the default), "mean" or "median" (docs/hnsw.md §18)."""
         self._lib = _capi.load()
         self._h = None
         self.config = config or HNSWConfig()
         self.dim = int(dim)
         cfg = self.config._c()
         h = C.c_void_p()
+        if binary_threshold is not None and storage != "binary":
+            raise _capi.NeumannGpuError(_capi.ERR_CONFIGURATION, "binary_threshold goes with storage='binary'")
         if storage is None:
             _capi.check(self._lib.nmn_hnsw_create(C.byref(cfg), self.dim, int(capacity_hint), int(device), C.byref(h)))
+        elif storage == "binary":
+            try:
+                method = _BINARY_THRESHOLD[binary_threshold or "sign"]
+            except KeyError:
+                raise _capi.NeumannGpuError(_capi.ERR_CONFIGURATION, f"unknown binary threshold {binary_threshold!r}")
+            cfg.storage = _capi.HNSW_STORAGE_DENSE
+            _capi.check(self._lib.nmn_hnsw_create_binary(C.byref(cfg), method, self.dim, int(capacity_hint), int(device), C.byref(h)))
         else:
             cfg.storage = _capi.HNSW_STORAGE_DENSE
             _capi.check(self._lib.nmn_hnsw_create_with_storage(C.byref(cfg), _storage_code(storage), self.dim, int(capacity_hint),
@@ -253,13 +266,13 @@ class GpuHnsw:
         return out[:cnt.value].copy()
 
     def vectors(self):
-        """the flat index holding the rows (node id == row), valid until the next insert; None on a quantized handle"""
+        """the flat index holding the rows (node id == row), valid until the next insert; None on a quantized or binary handle"""
         v = self._lib.nmn_hnsw_vectors(self._h)
         return GpuFlatIndex._view(v, self) if v else None
 
     @property
     def storage(self):
-        """"dense" or "quantized": the handle's one storage strategy"""
+        """"dense", "quantized" or "binary": the handle's one storage"""
         code = int(self._lib.nmn_hnsw_storage(self._h))
         return {v: k for k, v in _STORAGE.items()}[code]
 
@@ -270,8 +283,21 @@ class GpuHnsw:
         _capi.check(self._lib.nmn_hnsw_quantized_row(self._h, int(node), C.c_void_p(codes.ctypes.data), C.byref(scale), C.byref(mn)))
         return codes, np.float32(scale.value), np.float32(mn.value)
 
+    @property
+    def binary_threshold(self):
+        """"sign", "mean" or "median" on a binary handle, None on any other"""
+        code = int(self._lib.nmn_hnsw_binary_threshold(self._h))
+        return {v: k for k, v in _BINARY_THRESHOLD.items()}.get(code)
+
+    def binary_row(self, node):
+        """the node's BinaryVector -> u64 words [ceil(dim / 64)], bit i of word i // 64 = element i above the threshold"""
+        words = np.empty((self.dim + 63) // 64, dtype=np.uint64)
+        _capi.check(self._lib.nmn_hnsw_binary_row(self._h, int(node), C.c_void_p(words.ctypes.data), words.size))
+        return words
+
     def get_vector(self, node):
-        """HNSWIndex::get_vector: the row as inserted (dense), to_dense() of a sparse node, or dequantize() (quantized)"""
+        """HNSWIndex::get_vector: the row as inserted (dense), to_dense() of a sparse node, dequantize() (quantized), or the
+        +1.0 / -1.0 row of to_dense() (binary)"""
         out = np.empty(self.dim, dtype=np.float32)
         _capi.check(self._lib.nmn_hnsw_get_vector(self._h, int(node), C.c_void_p(out.ctypes.data)))
         return out

@@ -29,11 +29,14 @@ call: medians of --calls (a fifth of it at 1024 queries), spread over --repeats 
 --launch-calls N then makes N search_metric_device calls and nothing else.
 
   python tools/hnsw_bench.py --rows 200000 --dim 768 --storage quantized
+  python tools/hnsw_bench.py --rows 200000 --dim 128 --storage binary [--binary-threshold sign|mean|median]
 builds the corpus twice — a quantized handle (HNSWStorageStrategy::Quantized, docs/hnsw.md §9) and a dense one — and times the
 quantized walk beside the dense walk OF THE SAME RUN, the two alternating call by call: nmn_hnsw_search_device under HIP events at
 1 / 64 / 1024 queries per call and a lone host-buffer nmn_hnsw_search call, ef 50 and 200, medians of --calls, spread over
 --repeats.  It prints both handles' hbm_bytes, build times, evaluations per query and recall@10 of each against the exhaustive
 search over the f32 rows, and checks that the quantized handle's device, host-buffer and host-walk answers are the same bits.
+With --storage binary the binary handle (EmbeddingStorage::Binary nodes, docs/hnsw.md §18) stands in the quantized one's place and
+the keys say "bin"; it has no file form and is built every run, --index-file then names the DENSE handle's file.
 
   python tools/hnsw_bench.py --rows 1000000 --dim 128 --index-file /data/hnsw_1m_128.idx
 With --index-file the run stops paying for builds (docs/hnsw.md §10): when PATH exists the handle is GpuHnsw.load(PATH) and the
@@ -128,8 +131,8 @@ def time_rerank(g, xmetric, Q, qd, k, s, args):
     return r
 
 
-def time_storage(gq, gd, Q, qd, k, s, args, metric):
-    """the quantized walk beside the dense walk of the same corpus, alternating call by call"""
+def time_storage(gq, gd, Q, qd, k, s, args, metric, tag="q8"):
+    """the quantized (tag "q8") or binary (tag "bin") walk beside the dense walk of the same corpus, alternating call by call"""
     import torch
     out = {}
     flat = gd.vectors()
@@ -145,14 +148,14 @@ def time_storage(gq, gd, Q, qd, k, s, args, metric):
             gq.search(Q[:nq], k, ef)
             gd.search(Q[:nq], k, ef)
         s.synchronize()
-        for name, g, b in (("q8", gq, 0), ("dense", gd, 1)):
+        for name, g, b in ((tag, gq, 0), ("dense", gd, 1)):
             ids, sc, cnt, st = g.search(Q, k, ef, with_stats=True)
             r[f"{name}_evals_per_query"] = round(st.rows_scanned / len(Q), 1)
             r[f"{name}_spilled_queries"] = int(st.fallback_queries)
             r[f"{name}_recall_at_{k}"] = round(float(np.mean([len(set(a.tolist()) & set(e.tolist())) / k for a, e in zip(ids, ex_rows)])), 4)
             same = np.array_equal(bufs[1024][b][0].cpu().numpy().view(np.uint64), ids) and \
                 np.array_equal(bufs[1024][b][1].cpu().numpy().view(np.uint32), sc.view(np.uint32))
-            if name == "q8":
+            if name == tag:
                 os.environ["NMN_HNSW_HOST_SEARCH"] = "1"
                 try:
                     hids, hsc, _ = g.search(Q[:64], k, ef)
@@ -163,7 +166,7 @@ def time_storage(gq, gd, Q, qd, k, s, args, metric):
         reps = {}
         for _ in range(args.repeats):
             for nq, calls in ((1, args.calls), (64, args.calls), (1024, max(args.calls // 5, 5))):
-                ev = {"q8": [], "dense": []}
+                ev = {tag: [], "dense": []}
                 for _ in range(calls):
                     e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
                     e[0].record(s)
@@ -172,7 +175,7 @@ def time_storage(gq, gd, Q, qd, k, s, args, metric):
                     e[2].record(s)
                     gd.search_device(qd[:nq], k, ef, out=bufs[nq][1], stream=s)
                     e[3].record(s)
-                    ev["q8"].append((e[0], e[1]))
+                    ev[tag].append((e[0], e[1]))
                     ev["dense"].append((e[2], e[3]))
                 s.synchronize()
                 for name in ev:
@@ -186,13 +189,13 @@ def time_storage(gq, gd, Q, qd, k, s, args, metric):
                 t2 = time.perf_counter()
                 tq.append(t1 - t0)
                 td.append(t2 - t1)
-            reps.setdefault("q8_gpu_ms_nq1", []).append(float(np.median(tq)) * 1e3)
+            reps.setdefault(f"{tag}_gpu_ms_nq1", []).append(float(np.median(tq)) * 1e3)
             reps.setdefault("dense_gpu_ms_nq1", []).append(float(np.median(td)) * 1e3)
         for key, v in reps.items():
             r[key] = round(float(np.median(v)), 5)
             r[key + "_spread"] = round(float((max(v) - min(v)) / np.median(v)), 3)
         for nq in (1, 64, 1024):
-            r[f"q8_over_dense_nq{nq}"] = round(r[f"q8_dev_ms_per_query_nq{nq}"] / r[f"dense_dev_ms_per_query_nq{nq}"], 3)
+            r[f"{tag}_over_dense_nq{nq}"] = round(r[f"{tag}_dev_ms_per_query_nq{nq}"] / r[f"dense_dev_ms_per_query_nq{nq}"], 3)
         out[f"ef{ef}"] = r
     return out
 
@@ -437,9 +440,9 @@ def time_mixed(n, d, cfg, Q, k, args, out):
     return out
 
 
-def build_or_load(path, n, d, cfg, storage, out, label=""):
+def build_or_load(path, n, d, cfg, storage, out, label="", binary_threshold=None):
     """the handle of the run: GpuHnsw.load(path) when the file exists; otherwise built by nmn_hnsw_insert and, with a path, saved
-    and loaded back once.  Seconds and file bytes go to `out`."""
+    and loaded back once.  Seconds and file bytes go to `out`.  (A binary handle is always built: it has no file form, path None.)"""
     from neumann_amd import GpuHnsw, synth_rows
     pre = f"{label}_" if label else ""
     if path and os.path.exists(path):
@@ -454,7 +457,7 @@ def build_or_load(path, n, d, cfg, storage, out, label=""):
             raise SystemExit(f"{path} holds another index: (rows, dim, storage, m, m0, ef_construction, ef_search, metric) = {have}, asked for {want}")
         print(f"{pre}loaded {n} nodes from {path} in {out[pre + 'load_s']} s", file=sys.stderr, flush=True)
         return g
-    g = GpuHnsw(d, cfg, capacity_hint=n, storage=storage)
+    g = GpuHnsw(d, cfg, capacity_hint=n, storage=storage, binary_threshold=binary_threshold)
     t0 = time.perf_counter()
     step = 50_000
     for r0 in range(0, n, step):
@@ -543,8 +546,9 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--launch-calls", type=int, default=None)
-    ap.add_argument("--storage", default="dense", choices=["dense", "quantized"],
-                    help="quantized: time the quantized walk beside the dense walk of the same corpus (docs/hnsw.md §9)")
+    ap.add_argument("--storage", default="dense", choices=["dense", "quantized", "binary"],
+                    help="quantized / binary: time that walk beside the dense walk of the same corpus (docs/hnsw.md §9, §18)")
+    ap.add_argument("--binary-threshold", default="sign", choices=["sign", "mean", "median"], help="--storage binary: the BinaryThreshold")
     ap.add_argument("--callers", default=None, help="e.g. 1,16,64,128: time that many concurrent host callers (nq = 1, mixed k) and nothing else")
     ap.add_argument("--caller-calls", type=int, default=200, help="calls every caller thread makes per repetition")
     ap.add_argument("--sparse-queries", type=float, default=None,
@@ -652,6 +656,16 @@ def main():
                 out[f"{name}_hbm_bytes"], out[f"{name}_max_layer"] = g.hbm_bytes, g.max_layer
             s = torch.cuda.Stream()
             out.update(time_storage(gq, gd, Q, torch.from_numpy(Q).cuda(), k, s, args, metric))
+        print(json.dumps(out), flush=True)
+        return
+    if args.storage == "binary":  # the binary handle is built every run (no file form); --index-file names the DENSE handle's file
+        out.update({"storage": "binary", "binary_threshold": args.binary_threshold})
+        with build_or_load(None, n, d, cfg, "binary", out, "bin", args.binary_threshold) as gb, \
+                build_or_load(args.index_file, n, d, cfg, "dense", out, "dense") as gd:
+            for name, g in (("bin", gb), ("dense", gd)):
+                out[f"{name}_hbm_bytes"], out[f"{name}_max_layer"] = g.hbm_bytes, g.max_layer
+            s = torch.cuda.Stream()
+            out.update(time_storage(gb, gd, Q, torch.from_numpy(Q).cuda(), k, s, args, metric, "bin"))
         print(json.dumps(out), flush=True)
         return
     with build_or_load(args.index_file, n, d, cfg, "dense", out) as g:
