@@ -726,6 +726,39 @@ nmn_status nmn_hnsw_search_device(nmn_hnsw* h, const float* queries_dev, uint32_
 /* Entries of the results / candidate heaps a wave keeps in LDS (0 = default: 1024 results, 1024 .. 4096 candidates by ef).
  * Smaller heaps leave more LDS per workgroup; a query that outgrows them is answered by the spill launch, same bits. */
 nmn_status nmn_hnsw_set_heap_capacity(nmn_hnsw* h, uint32_t results, uint32_t candidates);
+/* nmn_hnsw_insert with the searches of try_insert_embedding (hnsw.rs:1936-2051) walked on the GPU, many new nodes per launch
+ * (docs/hnsw.md §19).  The levels of all n rows are drawn first, in order; then batches of consecutive nodes are walked against
+ * the graph as it is at launch, and the host commits them in order (the same connect-and-prune code), taking a node's device walk
+ * only when no neighbour list that walk read has been assigned since the launch, and walking the node itself otherwise.  The
+ * graph, the ids and the generator state are nmn_hnsw_insert's, list for list; arguments, NMN_ERR_CAPACITY, its text and the
+ * all-or-nothing batch are nmn_hnsw_insert's too.  Walked on the device: a dense handle without sparse nodes, ef_construction
+ * <= 1024, a results heap (nmn_hnsw_set_heap_capacity) of at least ef_construction + 1 entries, once the graph holds min_nodes
+ * nodes, in a call that leaves the device at least four rows; every other node takes the host's walk, with the same result.  A device error during a batch sends the remaining rows of
+ * the call down the host's path.  NMN_HNSW_BULK_BUILD=1 (read at every call) routes nmn_hnsw_insert through this entry. */
+nmn_status nmn_hnsw_insert_bulk(nmn_hnsw* h, const float* rows_host, uint64_t n, uint64_t* ids_out);
+/* How nmn_hnsw_insert_bulk (hnsw.rs:1936-2051 in batches) cuts its batches; never what it builds.  batch: nodes per launch, 1 ..
+ * 1024 (a batch also ends behind the first node whose level exceeds the graph's top layer); 0 = adaptive, from 8, doubled up to 256
+ * after a batch of which at most a quarter was walked again on the host, halved down to 4 after one of which half or more was.
+ * min_nodes: the graph size from which the device walks (0 = 100 000, below which the host's walk was measured faster). */
+nmn_status nmn_hnsw_set_bulk_policy(nmn_hnsw* h, uint32_t batch, uint32_t min_nodes);
+/* Counters of nmn_hnsw_insert_bulk (hnsw.rs:1936-2051 in batches), cumulative per handle: launches; nodes walked on the device;
+ * of those, the walks taken (accepted), walked again because a list they read had been assigned (conflicts) or because the
+ * candidate heap or the read list filled (overflowed) — accepted + conflicts + overflowed == walks; nodes that never went to the
+ * device (host_nodes); neighbour lists sent to the device between batches (patched_lists). */
+typedef struct nmn_hnsw_bulk_stats {
+    uint64_t batches;
+    uint64_t walks;
+    uint64_t accepted;
+    uint64_t conflicts;
+    uint64_t overflowed;
+    uint64_t host_nodes;
+    uint64_t patched_lists;
+} nmn_hnsw_bulk_stats;
+nmn_status nmn_hnsw_get_bulk_stats(nmn_hnsw* h, nmn_hnsw_bulk_stats* out);
+/* The batches of the LAST nmn_hnsw_insert_bulk call (hnsw.rs:1936-2051 in batches), five floats each: nodes walked, nodes walked
+ * again on the host, milliseconds of the walk launch (with its read-back), of validation and commits, of the patch.  *count
+ * receives the number of batches; out (nullable) the first min(cap, *count) records. */
+nmn_status nmn_hnsw_get_bulk_trace(nmn_hnsw* h, float* out, uint64_t cap, uint64_t* count);
 /* The flat index holding the rows (exhaustive search over the same rows).  NULL on a quantized or binary handle: it keeps no f32
  * rows on the device. */
 nmn_index* nmn_hnsw_vectors(nmn_hnsw* h);

@@ -109,6 +109,12 @@ class HnswMemStats(C.Structure):
                                           "quantized_count", "pq_count", "binary_count", "embedding_bytes")]
 
 
+class HnswBulkStats(C.Structure):
+    """nmn_hnsw_bulk_stats: the counters of nmn_hnsw_insert_bulk, cumulative per handle."""
+    _fields_ = [(n, C.c_uint64) for n in ("batches", "walks", "accepted", "conflicts", "overflowed", "host_nodes",
+                                          "patched_lists")]
+
+
 class XMetric(C.Structure):
     """nmn_xmetric (tensor_store::DistanceMetric, tensor_store/src/distance.rs:13-52; the weights are GeometricConfig, 115-125)."""
     _fields_ = [("kind", C.c_int32), ("cosine_weight", C.c_float), ("structural_weight", C.c_float),
@@ -215,6 +221,10 @@ SIGNATURES = {
     "nmn_hnsw_create": (C.c_int32, [C.POINTER(HnswConfig), C.c_uint32, C.c_uint64, C.c_int32, C.POINTER(vp)]),
     "nmn_hnsw_destroy": (C.c_int32, [vp]),
     "nmn_hnsw_insert": (C.c_int32, [vp, vp, C.c_uint64, vp]),
+    "nmn_hnsw_insert_bulk": (C.c_int32, [vp, vp, C.c_uint64, vp]),
+    "nmn_hnsw_set_bulk_policy": (C.c_int32, [vp, C.c_uint32, C.c_uint32]),
+    "nmn_hnsw_get_bulk_stats": (C.c_int32, [vp, C.POINTER(HnswBulkStats)]),
+    "nmn_hnsw_get_bulk_trace": (C.c_int32, [vp, vp, C.c_uint64, u64p]),
     "nmn_hnsw_insert_sparse": (C.c_int32, [vp, vp, vp, vp, C.c_uint64, vp]),
     "nmn_hnsw_insert_auto": (C.c_int32, [vp, vp, C.c_uint64, vp]),
     "nmn_hnsw_sparse_row": (C.c_int32, [vp, C.c_uint64, vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]),

@@ -44,6 +44,7 @@
 //       the +-1 row per node, the device the words alone; the kernel takes the BIN instantiations.  docs/hnsw.md §18.
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <cmath>
 #include <condition_variable>
 #include <cstdio>
@@ -70,6 +71,9 @@ constexpr uint32_t kNone = 0xFFFFFFFFu;
 constexpr uint32_t kLdsResultsMax = 1024;  // entries of the results heap a wave keeps in LDS (+1 for the push before the pop)
 constexpr uint32_t kLdsCandMax = 4096;     // entries of the candidate heap a wave keeps in LDS
 constexpr uint32_t kMaxDim = 8192;         // the query sits in LDS for the whole walk (32 KiB at most)
+constexpr uint32_t kBulkMinRows = 4;       // rows a call must leave for the device to be walked there (the adaptive policy's smallest batch)
+constexpr uint32_t kBulkMinNodes = 100000;  // the graph size from which the device walks by default: the measured break-even (docs/hnsw.md §19.5)
+constexpr uint32_t kBulkBatchMax = 1024;   // nodes of one hnsw_insert_walk_kernel launch (nmn_hnsw_set_bulk_policy)
 constexpr uint32_t kSparseLdsEntries = 4096;  // stored entries of a sparse query a wave keeps in LDS, 8 bytes each: the same 32 KiB
 
 struct Ent {
@@ -1051,6 +1055,262 @@ __global__ __launch_bounds__(64) void hnsw_search_kernel(SearchArgs a) {
     }
 }
 
+// ---- the build walk (nmn_hnsw_insert_bulk, docs/hnsw.md §19) ----------------------------------------------------------------------
+// What try_insert_embedding (hnsw.rs:1936-2051) SEARCHES for one new node, against the graph as it sits in HBM at launch: the
+// greedy descent above the node's level, then search_layer with ef_construction on every layer from min(level, max_layer) down,
+// the first sorted result of a layer the entry of the next.  Nothing is committed here: the host takes the selections of a walk
+// only when none of the lists it read has been assigned since the launch, so the kernel also reports which lists it read.
+struct InsertArgs {
+    GraphDev g;             // the snapshot: n nodes, its entry and max_layer; `up` laid out at the call's final up_layers
+    const uint8_t* levels;  // the levels of the call's rows: node id has levels[id - lv_base]
+    uint32_t lv_base;
+    uint32_t first, nb;     // the batch: nodes first .. first + nb - 1, their rows already in g.corpus
+    uint32_t ef, rcap, ccap, qlds;
+    uint32_t* visited;      // [nb][vwords]
+    uint32_t vwords;
+    uint32_t sel_stride;    // m0 + max_layer * m: layer 0's selections first, layer l >= 1 at m0 + (l - 1) * m
+    uint32_t rd_cap;
+    uint32_t* status;       // [nb] 0 = walked, 1 = the candidate heap or the read list filled: the host walks this node
+    uint32_t* selcnt;       // [nb][max_layer + 1] min(m or m0, found) per searched layer
+    uint32_t* rdend;        // [nb][max_layer + 1] end of the layer's reads in the node's read list; the layers run max_layer .. 0
+    uint32_t* sel;          // [nb][sel_stride] the first selcnt ids of search_layer's result, in its stable order
+    uint32_t* reads;        // [nb][rd_cap] the nodes whose list at the layer was read: greedy's round starts, search_layer's pops
+};
+
+// One new node per wave (one wave per workgroup), the walk of hnsw_search_kernel<false, false, false> with three changes: the
+// query is the node's own row, search_layer runs on the upper layers too (their lists through up_idx), and a fresh visited set and
+// empty heaps per layer.  Only lane 0 touches the heaps and the read list.
+__global__ __launch_bounds__(64) void hnsw_insert_walk_kernel(InsertArgs a) {
+    extern __shared__ float4 smem4[];
+    const GraphDev& g = a.g;
+    const uint32_t lane = threadIdx.x, p = lane >> 1, h = lane & 1u;
+    float* qs = reinterpret_cast<float*>(smem4);
+    uint32_t* stage_id = reinterpret_cast<uint32_t*>(qs + a.qlds);
+    float* stage_d = reinterpret_cast<float*>(stage_id + 32);
+    // [0] done, [1] current node, [2] overflow, [3] results, [4] / [5] the first sorted result and its distance
+    uint32_t* ctrl = reinterpret_cast<uint32_t*>(stage_d + 32);
+    Ent* R = reinterpret_cast<Ent*>(ctrl + 8);
+    Ent* Cn = R + a.rcap;
+    const uint32_t layers = g.max_layer + 1u;
+    for (uint32_t b = blockIdx.x; b < a.nb; b += gridDim.x) {
+        const uint32_t id = a.first + b;
+        const uint32_t lq = a.levels[id - a.lv_base];
+        const float* qg = g.corpus + (size_t)id * g.ld;
+        const float* qv = qs;
+        __syncthreads();
+        for (uint32_t i = lane; i < a.qlds; i += 64) qs[i] = i < g.dim ? qg[i] : 0.0f;
+        if (lane == 0) ctrl[2] = 0;
+        uint32_t* vis = a.visited + (size_t)b * a.vwords;
+        uint32_t* rd = a.reads + (size_t)b * a.rd_cap;
+        uint32_t* o_end = a.rdend + (size_t)b * layers;
+        __syncthreads();
+        float qmag = 0.0f;
+        if (g.metric == NMN_METRIC_COSINE) qmag = d_sqrt(-pair_distance(qv, 0.f, qv, 0.f, g.dim, NMN_METRIC_DOT_PRODUCT, h));
+        auto row_distance = [&](uint32_t node) -> float {
+            return pair_distance(g.corpus + (size_t)node * g.ld, g.norms[node], qv, qmag, g.dim, g.metric, h);
+        };
+        uint32_t nrd = 0;  // entries of the read list (every lane counts through the descent, lane 0 alone after it)
+        bool overflow = false;
+        // greedy descent on the layers above the node's level, hnsw.rs:1989-1992 / 2170-2200
+        uint32_t cur = g.entry;
+        float cur_d = row_distance(cur);
+        for (uint32_t layer = g.max_layer; layer > lq && !overflow; layer--) {
+            for (;;) {
+                if (nrd == a.rd_cap) {
+                    overflow = true;
+                    break;
+                }
+                if (lane == 0) rd[nrd] = cur;
+                nrd++;
+                const uint32_t ui = g.up_idx[cur];
+                const size_t slot = (size_t)ui * g.up_layers + (layer - 1);
+                const uint32_t cnt = ui == kNone ? 0u : g.upcnt[slot];
+                const uint32_t* base = g.up + slot * g.m;
+                uint32_t best = cur;
+                float best_d = cur_d;
+                for (uint32_t j0 = 0; j0 < cnt; j0 += 32) {
+                    const uint32_t j = j0 + p;
+                    uint32_t nid = kNone;
+                    float d = 0.0f;
+                    if (j < cnt) {
+                        nid = base[j];
+                        d = row_distance(nid);
+                    }
+                    __syncthreads();
+                    if (h == 0) {
+                        stage_id[p] = nid;
+                        stage_d[p] = d;
+                    }
+                    __syncthreads();
+                    const uint32_t lim = min(32u, cnt - j0);
+                    for (uint32_t t = 0; t < lim; t++) {
+                        const float dt = stage_d[t];
+                        if (dt < best_d) {
+                            best = stage_id[t];
+                            best_d = dt;
+                        }
+                    }
+                }
+                if (best == cur) break;
+                cur = best;
+                cur_d = best_d;
+            }
+            if (lane == 0) o_end[layer] = nrd;
+        }
+        // search_layer with ef_construction per layer, hnsw.rs:1994-2044 / 2276-2335
+        for (int layer = (int)min(lq, g.max_layer); layer >= 0 && !overflow; layer--) {
+            for (uint32_t w = lane; w < a.vwords; w += 64) vis[w] = 0u;  // a fresh visited set per call
+            __threadfence();
+            __syncthreads();
+            uint32_t rn = 0, cn = 0;  // (lane 0's are the real ones): both heaps start empty
+            if (lane == 0) {
+                atomicOr(&vis[cur >> 5], 1u << (cur & 31u));
+                heap_push<false>(Cn, cn, Ent{cur_d, cur});
+                heap_push<true>(R, rn, Ent{cur_d, cur});
+            }
+            for (;;) {
+                __syncthreads();
+                if (lane == 0) {
+                    uint32_t done = 0, c = 0;
+                    if (cn == 0) {
+                        done = 1;
+                    } else {
+                        const Ent e = heap_pop<false>(Cn, cn);
+                        c = e.id;
+                        if (rn >= a.ef && e.d > R[0].d) {
+                            done = 1;
+                        } else if (nrd == a.rd_cap) {
+                            ctrl[2] = 1;
+                            done = 1;
+                        } else {
+                            rd[nrd++] = c;
+                        }
+                    }
+                    ctrl[0] = done;
+                    ctrl[1] = c;
+                }
+                __syncthreads();
+                if (ctrl[0]) break;
+                const uint32_t c = ctrl[1];
+                uint32_t cnt;
+                const uint32_t* base;
+                if (layer == 0) {
+                    cnt = g.l0cnt[c];
+                    base = g.l0 + (size_t)c * g.m0;
+                } else {
+                    const uint32_t ui = g.up_idx[c];
+                    const size_t slot = (size_t)ui * g.up_layers + (uint32_t)(layer - 1);
+                    cnt = ui == kNone ? 0u : g.upcnt[slot];
+                    base = g.up + slot * g.m;
+                }
+                for (uint32_t j0 = 0; j0 < cnt; j0 += 32) {
+                    const uint32_t j = j0 + p;
+                    uint32_t nid = kNone;
+                    float d = 0.0f;
+                    if (j < cnt) {
+                        nid = base[j];
+                        uint32_t seen = 0;
+                        if (h == 0) seen = (atomicOr(&vis[nid >> 5], 1u << (nid & 31u)) >> (nid & 31u)) & 1u;
+                        seen = __shfl(seen, (int)(lane & ~1u));
+                        if (seen)
+                            nid = kNone;
+                        else
+                            d = row_distance(nid);
+                    }
+                    if (h == 0) {
+                        stage_id[p] = nid;
+                        stage_d[p] = d;
+                    }
+                    __syncthreads();
+                    if (lane == 0) {
+                        const uint32_t lim = min(32u, cnt - j0);
+                        for (uint32_t t = 0; t < lim; t++) {
+                            const uint32_t nid_t = stage_id[t];
+                            if (nid_t == kNone) continue;
+                            const float dt = stage_d[t];
+                            const bool should_add = rn < a.ef || dt < R[0].d;
+                            if (should_add) {
+                                if (cn == a.ccap) {
+                                    ctrl[2] = 1;
+                                    break;
+                                }
+                                heap_push<false>(Cn, cn, Ent{dt, nid_t});
+                                heap_push<true>(R, rn, Ent{dt, nid_t});
+                                while (rn > a.ef) (void)heap_pop<true>(R, rn);
+                            }
+                        }
+                    }
+                    __syncthreads();
+                    if (ctrl[2]) break;
+                }
+                if (ctrl[2]) break;
+            }
+            if (ctrl[2]) {
+                overflow = true;
+                break;
+            }
+            if (lane == 0) ctrl[3] = rn;
+            __syncthreads();
+            const uint32_t n_res = ctrl[3];
+            const uint32_t m_l = layer == 0 ? g.m0 : g.m;
+            uint32_t* o_sel = a.sel + (size_t)b * a.sel_stride + (layer == 0 ? 0u : g.m0 + (uint32_t)(layer - 1) * g.m);
+            // the stable sort by distance of the vector order as ranks (hnsw_search_kernel); only the first m_l are used
+            for (uint32_t e = lane; e < n_res; e += 64) {
+                const Ent me = R[e];
+                uint32_t rank = 0;
+                for (uint32_t j = 0; j < n_res; j++) {
+                    const float dj = R[j].d;
+                    rank += (dj < me.d || (dj == me.d && j < e)) ? 1u : 0u;
+                }
+                if (rank < m_l) o_sel[rank] = me.id;
+                if (rank == 0) {  // `current_node = neighbors[0].id`, its distance carried along
+                    ctrl[4] = me.id;
+                    ctrl[5] = __float_as_uint(me.d);
+                }
+            }
+            if (lane == 0) {
+                a.selcnt[(size_t)b * layers + (uint32_t)layer] = min(m_l, n_res);
+                o_end[layer] = nrd;
+            }
+            __syncthreads();
+            cur = ctrl[4];
+            cur_d = __uint_as_float(ctrl[5]);
+        }
+        if (lane == 0) a.status[b] = overflow ? 1u : 0u;
+    }
+}
+
+// The lists the host's commits assigned since the last launch, scattered into the adjacency in HBM: a record of `stride` words per
+// workgroup turn — {kind, slot, count, ids ...}.  kind 0: layer-0 list of node `slot`; 1: upper list at slot `slot` of up / upcnt;
+// 2: up_idx[slot] = count.  The host sends every list once per batch, so no two records of a launch share a target.
+struct PatchArgs {
+    uint32_t* l0;
+    uint32_t* l0cnt;
+    uint32_t* up_idx;
+    uint32_t* up;
+    uint32_t* upcnt;
+    const uint32_t* rec;
+    uint32_t nrec, stride, m, m0;
+    uint64_t nodes, up_slots;  // what the arrays were allocated for
+};
+__global__ __launch_bounds__(64) void hnsw_patch_kernel(PatchArgs a) {
+    for (uint32_t r = blockIdx.x; r < a.nrec; r += gridDim.x) {
+        const uint32_t* rec = a.rec + (size_t)r * a.stride;
+        const uint32_t kind = rec[0], slot = rec[1], cnt = rec[2];
+        if (kind == 0u) {
+            if (slot >= a.nodes || cnt > a.m0) continue;
+            for (uint32_t t = threadIdx.x; t < a.m0; t += 64) a.l0[(size_t)slot * a.m0 + t] = t < cnt ? rec[3 + t] : kNone;
+            if (threadIdx.x == 0) a.l0cnt[slot] = cnt;
+        } else if (kind == 1u) {
+            if (slot >= a.up_slots || cnt > a.m) continue;
+            for (uint32_t t = threadIdx.x; t < a.m; t += 64) a.up[(size_t)slot * a.m + t] = t < cnt ? rec[3 + t] : kNone;
+            if (threadIdx.x == 0) a.upcnt[slot] = cnt;
+        } else if (slot < a.nodes && threadIdx.x == 0) {
+            a.up_idx[slot] = cnt;
+        }
+    }
+}
+
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
@@ -1109,6 +1369,13 @@ struct nmn_hnsw {
     DevBuf d_live;
     uint32_t up_layers = 1, n_upper = 0;
     uint32_t lds_rcap = 0, lds_ccap = 0;  // nmn_hnsw_set_heap_capacity (0 = default)
+    // nmn_hnsw_insert_bulk (docs/hnsw.md §19): the policy, the adaptive batch size as the last call left it, the counters, the
+    // batches of the last call as {walks, not accepted, walk ms, validation + commit ms, patch ms}, and the device side of a call
+    uint32_t bulk_batch = 0, bulk_min_nodes = 0;  // nmn_hnsw_set_bulk_policy (0 = default)
+    uint32_t bulk_b = 8;
+    nmn_hnsw_bulk_stats bulk_stats{};
+    std::vector<float> bulk_trace;
+    DevBuf bk_lv, bk_vis, bk_out, bk_patch;
     struct Scratch {
         hipStream_t stream = nullptr;
         std::mutex mu;
@@ -1441,8 +1708,42 @@ void host_search_layer(const nmn_hnsw* h, const Dist& dist, uint32_t entry, uint
 }
 
 // try_insert_embedding, hnsw.rs:1936-2051 (the row and its magnitude are already in h->rows / h->mags)
-void host_insert_node(nmn_hnsw* h, uint32_t node_id, HostVisited& vis) {
-    const uint32_t node_level = next_level(h);
+// The insert is split into what it searches and what it commits (docs/hnsw.md §19): nmn_hnsw_insert runs the two interleaved per
+// layer, as the reference does; nmn_hnsw_insert_bulk may take a layer's `selected` from the device's walk instead of searching.
+// `mark(node, layer)` is told every list a commit assigns — the new node's own, and that of every selected neighbour, pruned or not.
+struct NoMark {
+    void operator()(uint32_t, uint32_t) {}
+};
+
+// hnsw.rs:2005-2040: connect the new node to `selected` on `layer`, prune every back link list that outgrew m / m0
+template <class Mark>
+void host_commit_layer(nmn_hnsw* h, uint32_t node_id, uint32_t layer, const std::vector<uint32_t>& selected,
+                       std::vector<std::pair<float, uint32_t>>& wd, Mark& mark) {
+    const uint32_t m = layer == 0 ? h->cfg.m0 : h->cfg.m;
+    {
+        std::vector<uint32_t>& mine = h->nbr[node_id][layer];
+        mine.insert(mine.end(), selected.begin(), selected.end());
+        std::sort(mine.begin(), mine.end());
+        mark(node_id, layer);
+    }
+    for (uint32_t nb : selected) {
+        std::vector<uint32_t>& lst = h->nbr[nb][layer];
+        lst.insert(std::upper_bound(lst.begin(), lst.end(), node_id), node_id);  // push + sort: stays id-ascending
+        mark(nb, layer);
+        if (lst.size() > m) {
+            wd.clear();
+            for (uint32_t id : lst) wd.emplace_back(pair_of_nodes_distance(h, nb, id), id);
+            std::stable_sort(wd.begin(), wd.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
+            lst.clear();
+            for (size_t i = 0; i < m; i++) lst.push_back(wd[i].second);
+            std::sort(lst.begin(), lst.end());
+        }
+    }
+}
+
+// try_insert_embedding after random_level, hnsw.rs:1957-2051 (the row and its magnitude are already in h->rows / h->mags)
+template <class Mark>
+void host_insert_node_at(nmn_hnsw* h, uint32_t node_id, uint32_t node_level, HostVisited& vis, Mark& mark) {
     h->level.push_back((uint8_t)node_level);
     h->nbr.emplace_back(node_level + 1);
     if (h->entry == ~0ull) {
@@ -1464,24 +1765,36 @@ void host_insert_node(nmn_hnsw* h, uint32_t node_id, HostVisited& vis) {
         const uint32_t m = layer == 0 ? h->cfg.m0 : h->cfg.m;
         std::vector<uint32_t> selected;
         for (size_t i = 0; i < found.size() && i < m; i++) selected.push_back(found[i].id);
-        {
-            std::vector<uint32_t>& mine = h->nbr[node_id][layer];
-            mine.insert(mine.end(), selected.begin(), selected.end());
-            std::sort(mine.begin(), mine.end());
-        }
-        for (uint32_t nb : selected) {
-            std::vector<uint32_t>& lst = h->nbr[nb][layer];
-            lst.insert(std::upper_bound(lst.begin(), lst.end(), node_id), node_id);  // push + sort: stays id-ascending
-            if (lst.size() > m) {
-                wd.clear();
-                for (uint32_t id : lst) wd.emplace_back(pair_of_nodes_distance(h, nb, id), id);
-                std::stable_sort(wd.begin(), wd.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
-                lst.clear();
-                for (size_t i = 0; i < m; i++) lst.push_back(wd[i].second);
-                std::sort(lst.begin(), lst.end());
-            }
-        }
+        host_commit_layer(h, node_id, (uint32_t)layer, selected, wd, mark);
         if (!found.empty()) cur = found[0].id;
+    }
+    if (node_level > current_max) {
+        h->entry = node_id;
+        h->max_layer = node_level;
+    }
+}
+
+// try_insert_embedding, hnsw.rs:1936-2051
+void host_insert_node(nmn_hnsw* h, uint32_t node_id, HostVisited& vis) {
+    const uint32_t node_level = next_level(h);
+    NoMark none;
+    host_insert_node_at(h, node_id, node_level, vis, none);
+}
+
+// The same node with the searches already done by hnsw_insert_walk_kernel: sel / selcnt as the kernel wrote them for this node
+// (layer 0's ids first, layer l >= 1 at m0 + (l - 1) m).  The index is not empty.
+template <class Mark>
+void host_commit_walked(nmn_hnsw* h, uint32_t node_id, uint32_t node_level, const uint32_t* sel, const uint32_t* selcnt,
+                        Mark& mark) {
+    h->level.push_back((uint8_t)node_level);
+    h->nbr.emplace_back(node_level + 1);
+    const uint32_t current_max = h->max_layer;
+    std::vector<std::pair<float, uint32_t>> wd;
+    std::vector<uint32_t> selected;
+    for (int layer = (int)std::min(node_level, current_max); layer >= 0; layer--) {
+        const uint32_t* ids = sel + (layer == 0 ? 0u : h->cfg.m0 + (uint32_t)(layer - 1) * h->cfg.m);
+        selected.assign(ids, ids + selcnt[layer]);
+        host_commit_layer(h, node_id, (uint32_t)layer, selected, wd, mark);
     }
     if (node_level > current_max) {
         h->entry = node_id;
@@ -1641,16 +1954,21 @@ nmn_status wait_in_flight(nmn_hnsw* h) {  // caller holds rw exclusively
 }
 
 // the adjacency as it sits in HBM: layer 0 [n][m0] + counts, upper layers [n_upper][up_layers][m] + counts + a row per node
-nmn_status upload_graph(nmn_hnsw* h) {
-    const size_t n = h->level.size();
+// reserve_n / reserve_upper / layers (nmn_hnsw_insert_bulk, docs/hnsw.md §19): the arrays sized and laid out for a graph of that
+// many nodes, upper nodes and upper layers — the slots past the present graph empty — so that hnsw_patch_kernel can fill them in
+nmn_status upload_graph(nmn_hnsw* h, size_t reserve_n = 0, uint32_t reserve_upper = 0, uint32_t layers = 0) {
+    const size_t n_now = h->level.size();
+    const size_t n = std::max(n_now, reserve_n);
     const uint32_t m = h->cfg.m, m0 = h->cfg.m0;
     std::vector<uint32_t> l0(n * (size_t)m0, kNone), l0cnt(n), upidx(n, kNone);
     uint32_t n_upper = 0;
-    for (size_t i = 0; i < n; i++)
+    for (size_t i = 0; i < n_now; i++)
         if (h->level[i] > 0) upidx[i] = n_upper++;
-    const uint32_t L = std::max<uint32_t>(h->max_layer, 1);
+    const uint32_t n_upper_now = n_upper;
+    n_upper = std::max(n_upper, reserve_upper);
+    const uint32_t L = std::max<uint32_t>(std::max<uint32_t>(h->max_layer, 1), layers);
     std::vector<uint32_t> up((size_t)n_upper * L * m, kNone), upcnt((size_t)n_upper * L, 0);
-    for (size_t i = 0; i < n; i++) {
+    for (size_t i = 0; i < n_now; i++) {
         const auto& a = h->nbr[i][0];
         l0cnt[i] = (uint32_t)a.size();
         std::copy(a.begin(), a.end(), l0.begin() + i * m0);
@@ -1678,7 +1996,8 @@ nmn_status upload_graph(nmn_hnsw* h) {
         HN_TRY(hipMemcpy(h->d_upcnt.p, upcnt.data(), upcnt.size() * 4, hipMemcpyHostToDevice));
     }
     h->up_layers = L;
-    h->n_upper = n_upper;
+    h->n_upper = n_upper_now;
+    if (reserve_n) return NMN_OK;  // (the upload that ends the call does the rest)
     // the live mask: every node that came since the last upload is live (an insert, a load — the file does not hold the mask)
     h->live.resize((n + 31) / 32, 0u);
     for (uint64_t i = h->live_n; i < n; i++) h->live[i >> 5] |= 1u << (i & 31);
@@ -2249,7 +2568,7 @@ extern "C" nmn_status nmn_hnsw_destroy(nmn_hnsw* h) {
         drop(s->ttmag);
         drop(s->ttkind);
     }
-    for (DevBuf* b : {&h->d_l0, &h->d_l0cnt, &h->d_upidx, &h->d_up, &h->d_upcnt, &h->d_nrec, &h->d_nent, &h->d_live, &h->hq, &h->hids, &h->hsc, &h->hcnt, &h->hkef,
+    for (DevBuf* b : {&h->d_l0, &h->d_l0cnt, &h->d_upidx, &h->d_up, &h->d_upcnt, &h->d_nrec, &h->d_nent, &h->d_live, &h->bk_lv, &h->bk_vis, &h->bk_out, &h->bk_patch, &h->hq, &h->hids, &h->hsc, &h->hcnt, &h->hkef,
                        &h->hsp_off, &h->hsp_ent, &h->hqmag,
                        &h->hxmeta, &h->hxsim, &h->hxoids, &h->hxosc, &h->hxocnt, &h->hxsort, &h->htt_cores, &h->htt_ranks, &h->htt_off,
                        &h->htt_skip})
@@ -2263,11 +2582,282 @@ extern "C" nmn_status nmn_hnsw_destroy(nmn_hnsw* h) {
 }
 
 namespace {
+// ---- nmn_hnsw_insert_bulk (docs/hnsw.md §19) ---------------------------------------------------------------------------------------
+// The device side of one call: which upper slot every node has, and which lists the commits of the running batch have assigned —
+// a stamp per list holding the number of the batch that last assigned it (layer 0 by node, the upper layers by slot of `up`).
+struct BulkCall {
+    std::vector<uint32_t> upidx, stamp0, stamp_up;
+    std::vector<std::pair<uint32_t, uint32_t>> dirty;  // the lists stamped by this batch, once each: what the patch sends
+    uint32_t batch_no = 0, layers = 1, n_upper = 0;
+    uint32_t& stamp(uint32_t node, uint32_t layer) {
+        return layer == 0 ? stamp0[node] : stamp_up[(size_t)upidx[node] * layers + (layer - 1)];
+    }
+    void operator()(uint32_t node, uint32_t layer) {
+        uint32_t& s = stamp(node, layer);
+        if (s != batch_no) {
+            s = batch_no;
+            dirty.emplace_back(node, layer);
+        }
+    }
+    bool assigned(uint32_t node, uint32_t layer) {  // (an id no list can hold counts as assigned: the host walks that node)
+        if (node >= stamp0.size() || (layer > 0 && (upidx[node] == kNone || layer > layers))) return true;
+        return stamp(node, layer) == batch_no;
+    }
+};
+
+double ms_since(const std::chrono::steady_clock::time_point& t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// Whether the device walks for this handle at all, and with which heaps (the search kernel's LDS rule with ef = ef_construction)
+bool bulk_eligible(const nmn_hnsw* h) {
+    const uint32_t efc = h->cfg.ef_construction;
+    if (h->storage != NMN_HNSW_STORAGE_DENSE || h->n_sparse || !h->vectors) return false;
+    if (efc == 0 || efc > kLdsResultsMax) return false;
+    if (h->lds_rcap && h->lds_rcap < efc + 1) return false;
+    return true;
+}
+
+// One batch: launch, read back.  Caller holds rw exclusively and host_mu.  On return `out` holds status [nb], selcnt [nb][layers],
+// rdend [nb][layers], sel [nb][sel_stride], reads [nb][rd_cap].
+hipError_t bulk_walk(nmn_hnsw* h, uint64_t call_first, uint32_t first, uint32_t nb, uint32_t rd_cap, std::vector<uint32_t>& out) {
+    const uint32_t n = (uint32_t)h->level.size(), efc = h->cfg.ef_construction;
+    InsertArgs a{};
+    a.g = graph_args(h, n).g;
+    const uint32_t layers = a.g.max_layer + 1;
+    a.levels = (const uint8_t*)h->bk_lv.p;
+    a.lv_base = (uint32_t)call_first;
+    a.first = first;
+    a.nb = nb;
+    a.ef = efc;
+    a.rcap = results_need(efc, n);
+    a.ccap = cand_cap(efc, h->lds_ccap, h->dim, n);
+    a.qlds = (h->dim + 7u) & ~7u;
+    a.vwords = std::max<uint32_t>((n + 31) / 32, 1);
+    a.sel_stride = a.g.m0 + a.g.max_layer * a.g.m;
+    a.rd_cap = rd_cap;
+    const size_t words = (size_t)nb * (1 + 2 * (size_t)layers + a.sel_stride + rd_cap);
+    bool synced = false;
+    hipStream_t s = h->host_stream;
+    hipError_t e = grow(h->bk_vis, (size_t)nb * a.vwords * 4, s, &synced);
+    if (e == hipSuccess) e = grow(h->bk_out, words * 4, s, &synced);
+    if (e != hipSuccess) return e;
+    a.visited = (uint32_t*)h->bk_vis.p;
+    a.status = (uint32_t*)h->bk_out.p;
+    a.selcnt = a.status + nb;
+    a.rdend = a.selcnt + (size_t)nb * layers;
+    a.sel = a.rdend + (size_t)nb * layers;
+    a.reads = a.sel + (size_t)nb * a.sel_stride;
+    const size_t lds = (size_t)a.qlds * 4 + 32 * 4 + 32 * 4 + 8 * 4 + ((size_t)a.rcap + a.ccap) * sizeof(Ent);
+    if (lds > 64 * 1024) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(hnsw_insert_walk_kernel, dim3(nb), dim3(64), lds, s, a);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    out.resize(words);
+    e = hipMemcpyAsync(out.data(), h->bk_out.p, words * 4, hipMemcpyDeviceToHost, s);
+    if (e != hipSuccess) return e;
+    return hipStreamSynchronize(s);
+}
+
+// The lists of `bc.dirty` (and the upper slots of the batch's new nodes, `new_upper`) as records of hnsw_patch_kernel, sent and
+// scattered behind whatever is on the stream; the next walk launch is enqueued behind the scatter.
+hipError_t bulk_patch(nmn_hnsw* h, const BulkCall& bc, const std::vector<uint32_t>& new_upper, size_t nodes_cap, size_t upper_cap,
+                      std::vector<uint32_t>& stage) {
+    const uint32_t m = h->cfg.m, m0 = h->cfg.m0, stride = 3 + std::max(m, m0);
+    const size_t nrec = bc.dirty.size() + new_upper.size();
+    if (nrec == 0) return hipSuccess;
+    stage.assign(nrec * stride, kNone);
+    size_t r = 0;
+    for (uint32_t node : new_upper) {  // (first: a list record below may target the slot)
+        uint32_t* rec = stage.data() + r++ * stride;
+        rec[0] = 2u;
+        rec[1] = node;
+        rec[2] = bc.upidx[node];
+    }
+    for (const auto& d : bc.dirty) {
+        uint32_t* rec = stage.data() + r++ * stride;
+        const std::vector<uint32_t>& lst = h->nbr[d.first][d.second];
+        rec[0] = d.second == 0 ? 0u : 1u;
+        rec[1] = d.second == 0 ? d.first : (uint32_t)((size_t)bc.upidx[d.first] * bc.layers + (d.second - 1));
+        rec[2] = (uint32_t)lst.size();
+        std::copy(lst.begin(), lst.end(), rec + 3);
+    }
+    bool synced = false;
+    hipStream_t s = h->host_stream;
+    hipError_t e = grow(h->bk_patch, stage.size() * 4, s, &synced);
+    if (e != hipSuccess) return e;
+    e = hipMemcpyAsync(h->bk_patch.p, stage.data(), stage.size() * 4, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) return e;
+    PatchArgs a{};
+    a.l0 = (uint32_t*)h->d_l0.p;
+    a.l0cnt = (uint32_t*)h->d_l0cnt.p;
+    a.up_idx = (uint32_t*)h->d_upidx.p;
+    a.up = (uint32_t*)h->d_up.p;
+    a.upcnt = (uint32_t*)h->d_upcnt.p;
+    a.rec = (const uint32_t*)h->bk_patch.p;
+    a.nrec = (uint32_t)nrec;
+    a.stride = stride;
+    a.m = m;
+    a.m0 = m0;
+    a.nodes = nodes_cap;
+    a.up_slots = upper_cap * bc.layers;
+    hipLaunchKernelGGL(hnsw_patch_kernel, dim3((uint32_t)std::min<size_t>(nrec, 65535)), dim3(64), 0, s, a);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return hipStreamSynchronize(s);  // (`stage` is pageable and reused; the wait is also what the patch time of the trace measures)
+}
+
+// The n rows [have, have + n) of a dense-query insert, already in h->rows and on the device: levels first, then batches.
+// Caller (insert_rows) holds rw exclusively and has waited for every search in flight.
+void bulk_insert_nodes(nmn_hnsw* h, uint64_t have, uint64_t n, HostVisited& vis, uint64_t* ids_out) {
+    const bool q8 = h->storage == NMN_HNSW_STORAGE_QUANTIZED, bin = h->storage == NMN_HNSW_STORAGE_BINARY;
+    const uint32_t dim = h->dim;
+    std::vector<uint8_t> lv(n);
+    for (uint64_t i = 0; i < n; i++) lv[i] = (uint8_t)next_level(h);  // random_level once per insert, in order (hnsw.rs:1957)
+    h->bulk_trace.clear();
+    nmn_hnsw_bulk_stats& st = h->bulk_stats;
+    auto prelude = [&](uint64_t i) {  // what insert_rows does for a Dense row before the node is linked
+        if (h->n_sparse) {
+            h->sp_nnz.resize(have + i + 1, kNone);
+            h->sp_off.resize(have + i + 1, 0);
+            h->sp_mag64.resize(have + i + 1, 0.0);
+        }
+        if (!q8 && !bin) {
+            const float* v = h->rows.data() + (have + i) * dim;
+            h->mags.push_back(sqrtf(h_dot8(v, v, dim)));
+        }
+        if (ids_out) ids_out[i] = have + i;
+    };
+    uint64_t i = 0;
+    NoMark none;
+    const uint64_t min_nodes = h->bulk_min_nodes ? h->bulk_min_nodes : kBulkMinNodes;
+    const bool eligible = bulk_eligible(h);
+    // the host's path: an ineligible handle, the first node of an empty index, a graph below min_nodes, and a call that leaves the
+    // device fewer than kBulkMinRows rows — a launch waits one walk's latency, several host walks long (docs/hnsw.md §19.5), and
+    // the device phase uploads the whole adjacency once more
+    while (i < n && (!eligible || h->entry == ~0ull || h->level.size() < min_nodes || n - i < kBulkMinRows)) {
+        prelude(i);
+        host_insert_node_at(h, (uint32_t)(have + i), lv[i], vis, none);
+        st.host_nodes++;
+        i++;
+    }
+    if (i == n) return;
+    // the device side of the call, sized once: everything below is known from the levels
+    std::lock_guard<std::mutex> hl(h->host_mu);
+    BulkCall bc;
+    const size_t n_final = have + n;
+    bc.upidx.assign(n_final, kNone);
+    for (size_t k = 0; k < h->level.size(); k++)
+        if (h->level[k] > 0) bc.upidx[k] = bc.n_upper++;
+    uint32_t upper_final = bc.n_upper, top = h->max_layer;
+    for (uint64_t k = i; k < n; k++) {
+        upper_final += lv[k] > 0 ? 1u : 0u;
+        top = std::max<uint32_t>(top, lv[k]);
+    }
+    bc.layers = std::max<uint32_t>(top, 1);
+    bc.stamp0.assign(n_final, 0u);
+    bc.stamp_up.assign((size_t)upper_final * bc.layers, 0u);
+    const uint32_t rd_cap = 4 * h->cfg.ef_construction + 256;
+    bool device = upload_graph(h, n_final, upper_final, bc.layers) == NMN_OK;
+    if (device) {
+        bool synced = true;
+        device = grow(h->bk_lv, (size_t)n, (hipStream_t)-1, &synced) == hipSuccess &&
+                 hipMemcpy(h->bk_lv.p, lv.data(), (size_t)n, hipMemcpyHostToDevice) == hipSuccess;
+    }
+    std::vector<uint32_t> out, stage, new_upper;
+    while (i < n && device) {
+        uint32_t nb = (uint32_t)std::min<uint64_t>(h->bulk_batch ? h->bulk_batch : h->bulk_b, n - i);
+        const uint32_t launch_max = h->max_layer;
+        for (uint32_t j = 0; j < nb; j++)
+            if (lv[i + j] > launch_max) {  // its commit moves the entry point: the batch ends behind it
+                nb = j + 1;
+                break;
+            }
+        bc.batch_no++;
+        bc.dirty.clear();
+        new_upper.clear();
+        auto t0 = std::chrono::steady_clock::now();
+        if (bulk_walk(h, have, (uint32_t)(have + i), nb, rd_cap, out) != hipSuccess) {
+            device = false;
+            break;
+        }
+        const float walk_ms = (float)ms_since(t0);
+        t0 = std::chrono::steady_clock::now();
+        const uint32_t layers = launch_max + 1, sel_stride = h->cfg.m0 + launch_max * h->cfg.m;
+        const uint32_t* status = out.data();
+        const uint32_t* selcnt = status + nb;
+        const uint32_t* rdend = selcnt + (size_t)nb * layers;
+        const uint32_t* sel = rdend + (size_t)nb * layers;
+        const uint32_t* reads = sel + (size_t)nb * sel_stride;
+        uint32_t redone = 0;
+        for (uint32_t j = 0; j < nb; j++) {
+            const uint32_t node = (uint32_t)(have + i + j), level = lv[i + j];
+            prelude(i + j);
+            if (level > 0) {
+                bc.upidx[node] = bc.n_upper++;
+                new_upper.push_back(node);
+            }
+            bool take = status[j] == 0u;
+            if (!take) {
+                st.overflowed++;
+            } else {  // the walk stands iff no list it read has been assigned since the launch
+                const uint32_t* rd = reads + (size_t)j * rd_cap;
+                uint32_t at = 0;
+                for (int layer = (int)launch_max; layer >= 0 && take; layer--) {
+                    const uint32_t end = std::min(rdend[(size_t)j * layers + (uint32_t)layer], rd_cap);
+                    for (; at < end; at++)
+                        if (bc.assigned(rd[at], (uint32_t)layer)) {
+                            take = false;
+                            break;
+                        }
+                }
+                if (take)
+                    st.accepted++;
+                else
+                    st.conflicts++;
+            }
+            if (take) {
+                host_commit_walked(h, node, level, sel + (size_t)j * sel_stride, selcnt + (size_t)j * layers, bc);
+            } else {
+                host_insert_node_at(h, node, level, vis, bc);
+                redone++;
+            }
+        }
+        st.batches++;
+        st.walks += nb;
+        i += nb;
+        const float commit_ms = (float)ms_since(t0);
+        t0 = std::chrono::steady_clock::now();
+        if (i < n) {
+            if (bulk_patch(h, bc, new_upper, n_final, upper_final, stage) != hipSuccess)
+                device = false;
+            else
+                st.patched_lists += bc.dirty.size();
+        }
+        if (h->bulk_trace.size() < (5u << 20)) {
+            const float rec[5] = {(float)nb, (float)redone, walk_ms, commit_ms, (float)ms_since(t0)};
+            h->bulk_trace.insert(h->bulk_trace.end(), rec, rec + 5);
+        }
+        if (!h->bulk_batch) {  // the adaptive policy: statistics only, never the graph
+            if (4 * redone <= nb)
+                h->bulk_b = std::min<uint32_t>(2 * h->bulk_b, 256);
+            else if (2 * redone >= nb)
+                h->bulk_b = std::max<uint32_t>(h->bulk_b / 2, 4);
+        }
+    }
+    if (!device) (void)hipGetLastError();
+    for (; i < n; i++) {  // a device error: the rest of the call on the host; whole nodes only, either way
+        prelude(i);
+        host_insert_node_at(h, (uint32_t)(have + i), lv[i], vis, none);
+        st.host_nodes++;
+    }
+}
+
 // nmn_hnsw_insert, nmn_hnsw_insert_sparse and nmn_hnsw_insert_auto behind their argument checks.  rows_host: the n rows as the
 // flat index keeps them (to_dense() of a Sparse node).  sp / sp_row (dense handle only, nullable): row i is EmbeddingStorage::Sparse
 // with the entries of sp's vector sp_row[i] when sp_row[i] >= 0, Dense otherwise.
 nmn_status insert_rows(nmn_hnsw* h, const float* rows_host, uint64_t n, const SparseQueries* sp, const int64_t* sp_row,
-                       uint64_t* ids_out) {
+                       uint64_t* ids_out, bool bulk = false) {
     std::unique_lock<std::shared_mutex> g(h->rw);
     const uint64_t have = h->level.size();
     if (h->cfg.max_nodes > 0 && have + n > h->cfg.max_nodes) {  // hnsw.rs:1947-1955, text of 102-107; the batch is all or nothing
@@ -2333,6 +2923,10 @@ nmn_status insert_rows(nmn_hnsw* h, const float* rows_host, uint64_t n, const Sp
         return st;
     }
     static thread_local HostVisited vis;
+    if (bulk) {
+        bulk_insert_nodes(h, have, n, vis, ids_out);
+        return upload_graph(h);
+    }
     for (uint64_t i = 0; i < n; i++) {
         const bool sparse = sp && sp_row[i] >= 0;
         if (sparse || h->n_sparse) {  // a kind per node from the first Sparse one on
@@ -2372,7 +2966,39 @@ nmn_status refuse_sparse_on_q8(const nmn_hnsw* h) {
 extern "C" nmn_status nmn_hnsw_insert(nmn_hnsw* h, const float* rows_host, uint64_t n, uint64_t* ids_out) {
     if (!h || (!rows_host && n)) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
     if (n == 0) return NMN_OK;
-    return insert_rows(h, rows_host, n, nullptr, nullptr, ids_out);
+    const char* e = getenv("NMN_HNSW_BULK_BUILD");  // read at every call; the graph is the same either way (docs/hnsw.md §19)
+    return insert_rows(h, rows_host, n, nullptr, nullptr, ids_out, e && e[0] == '1');
+}
+
+extern "C" nmn_status nmn_hnsw_insert_bulk(nmn_hnsw* h, const float* rows_host, uint64_t n, uint64_t* ids_out) {
+    if (!h || (!rows_host && n)) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (n == 0) return NMN_OK;
+    return insert_rows(h, rows_host, n, nullptr, nullptr, ids_out, true);
+}
+
+extern "C" nmn_status nmn_hnsw_set_bulk_policy(nmn_hnsw* h, uint32_t batch, uint32_t min_nodes) {
+    if (!h) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (batch > kBulkBatchMax) return set_error(NMN_ERR_INVALID_ARGUMENT, "HNSW: a bulk batch holds 1024 nodes at most");
+    std::unique_lock<std::shared_mutex> g(h->rw);
+    h->bulk_batch = batch;
+    h->bulk_min_nodes = min_nodes;
+    return NMN_OK;
+}
+
+extern "C" nmn_status nmn_hnsw_get_bulk_stats(nmn_hnsw* h, nmn_hnsw_bulk_stats* out) {
+    if (!h || !out) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    std::shared_lock<std::shared_mutex> g(h->rw);
+    *out = h->bulk_stats;
+    return NMN_OK;
+}
+
+extern "C" nmn_status nmn_hnsw_get_bulk_trace(nmn_hnsw* h, float* out, uint64_t cap, uint64_t* count) {
+    if (!h || !count) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    std::shared_lock<std::shared_mutex> g(h->rw);
+    const uint64_t nrec = h->bulk_trace.size() / 5;
+    *count = nrec;
+    if (out) memcpy(out, h->bulk_trace.data(), (size_t)std::min(cap, nrec) * 5 * sizeof(float));
+    return NMN_OK;
 }
 
 // HNSWIndex::insert_sparse (hnsw.rs:1660-1662) for each of the n CSR rows, in order.  Every row is made a SparseVector as
@@ -2552,6 +3178,7 @@ extern "C" uint64_t nmn_hnsw_hbm_bytes(nmn_hnsw* h) {
     if (!h) return 0;
     std::shared_lock<std::shared_mutex> g(h->rw);
     uint64_t t = h->d_l0.cap + h->d_l0cnt.cap + h->d_upidx.cap + h->d_up.cap + h->d_upcnt.cap + h->d_nrec.cap + h->d_nent.cap + h->d_live.cap;
+    t += h->bk_lv.cap + h->bk_vis.cap + h->bk_out.cap + h->bk_patch.cap;  // (what nmn_hnsw_insert_bulk keeps between calls)
     uint64_t a = 0, b = 0, c = 0;
     if (h->vectors && nmn_index_hbm_bytes(h->vectors, &a, &b, &c) == NMN_OK) t += a + b + c;
     if (h->d_codes) t += std::max<uint64_t>(h->vec_cap * h->ld8, 256);

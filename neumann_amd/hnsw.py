@@ -213,6 +213,40 @@ class GpuHnsw:
         _capi.check(self._lib.nmn_hnsw_insert(self._h, C.c_void_p(r.ctypes.data), r.shape[0], C.c_void_p(ids.ctypes.data)))
         return ids
 
+    def insert_bulk(self, rows):
+        """`insert` with the searches of every new node walked on the GPU, a batch of nodes per launch, and committed on the host
+        in order (nmn_hnsw_insert_bulk, docs/hnsw.md §19): the same graph, ids and generator state; returns the node ids."""
+        r = np.ascontiguousarray(rows, dtype=np.float32)
+        if r.ndim == 1:
+            r = r[None, :]
+        if r.shape[1] != self.dim:
+            raise _capi.NeumannGpuError(_capi.ERR_DIMENSION_MISMATCH, f"expected {self.dim}, got {r.shape[1]}")
+        ids = np.empty(r.shape[0], dtype=np.uint64)
+        _capi.check(self._lib.nmn_hnsw_insert_bulk(self._h, C.c_void_p(r.ctypes.data), r.shape[0], C.c_void_p(ids.ctypes.data)))
+        return ids
+
+    def set_bulk_policy(self, batch=0, min_nodes=0):
+        """how `insert_bulk` cuts its batches, never what it builds: nodes per launch (0 = adaptive, 8 at first, 4 .. 256) and
+        the graph size from which the device walks (0 = 100 000)"""
+        _capi.check(self._lib.nmn_hnsw_set_bulk_policy(self._h, int(batch), int(min_nodes)))
+
+    def bulk_stats(self):
+        """counters of `insert_bulk`, cumulative per handle, as a dict: batches, walks, accepted, conflicts, overflowed
+        (accepted + conflicts + overflowed == walks), host_nodes, patched_lists"""
+        st = _capi.HnswBulkStats()
+        _capi.check(self._lib.nmn_hnsw_get_bulk_stats(self._h, C.byref(st)))
+        return {n: int(getattr(st, n)) for n, _ in st._fields_}
+
+    def bulk_trace(self):
+        """the batches of the last `insert_bulk` call -> f32 [batches, 5]: nodes walked, nodes walked again on the host,
+        milliseconds of the walk launch, of validation and commits, of the patch"""
+        cnt = C.c_uint64()
+        _capi.check(self._lib.nmn_hnsw_get_bulk_trace(self._h, None, 0, C.byref(cnt)))
+        out = np.empty((cnt.value, 5), dtype=np.float32)
+        if cnt.value:
+            _capi.check(self._lib.nmn_hnsw_get_bulk_trace(self._h, C.c_void_p(out.ctypes.data), cnt.value, C.byref(cnt)))
+        return out
+
     def insert_sparse(self, indptr, positions, values):
         """HNSWIndex::insert_sparse for each CSR row in order (nmn_hnsw_insert_sparse); returns the node ids.  Row i is the
         (position, value) pairs [indptr[i], indptr[i + 1]), made a SparseVector as try_from_parts does (`search_sparse`'s rules);

@@ -76,7 +76,15 @@ call_ms_median, merged batches and calls from nmn_hnsw_coalesce_stats), then one
 --cache-callers times CONCURRENT semantic-cache lookups (docs/hnsw.md §16): for every T of the list, T threads behind a barrier, each
 making --caller-calls calls of nmn_hnsw_cache_search with ONE query, k = 1 and threshold 0.9 under --cache-metric — the call
 CacheIndex::search_with_metric makes for every lookup.  The legs are --sparse-callers': this build, and this build under
-NMN_HNSW_NO_COALESCE=1, alternating, each a fresh child process (this script again, with --cache-leg) under --leg-timeout."""
+NMN_HNSW_NO_COALESCE=1, alternating, each a fresh child process (this script again, with --cache-leg) under --leg-timeout.
+
+  python tools/hnsw_bench.py --rows 200000 --dim 128 --bulk-build [--bulk-policy BATCH,MIN_NODES]
+--bulk-build times the BUILD and nothing else (docs/hnsw.md §19): --repeats legs, each a fresh child process (this script again,
+with --bulk-leg) under --leg-timeout that builds the same rows with nmn_hnsw_insert and with nmn_hnsw_insert_bulk on fresh
+handles in 50 000-row calls — the order of the two alternating leg by leg — saves both and ends the run unless the two files are
+byte-equal.  One JSON line per leg: insert_build_s and bulk_build_s, the seconds of every call of either (the graph grows from call
+to call), nmn_hnsw_get_bulk_stats, the accepted share, the batch-size trace (a histogram, and its first runs run-length coded)
+and the split of the bulk build into walk launches, validation plus commits, and patches; then one line with medians and spreads."""
 import argparse
 import json
 import os
@@ -295,6 +303,92 @@ def sparse_caller_legs(args, flag="--sparse-leg"):
                 r[f + "_spread"] = round(float((max(v) - min(v)) / max(np.median(v), 1e-12)), 3)
             out[f"{leg}_{key}"] = r
     print(json.dumps(out), flush=True)
+
+
+def bulk_build_legs(args):
+    """--bulk-build: `repeats` legs, each a fresh child process with its own time limit that builds the same rows with
+    nmn_hnsw_insert and with nmn_hnsw_insert_bulk (the order alternating leg by leg); this process opens no GPU"""
+    import subprocess
+    argv = [sys.executable, os.path.abspath(__file__), "--bulk-leg"] + [a for a in sys.argv[1:] if a != "--bulk-leg"]
+    lines = []
+    for i in range(args.repeats):
+        try:
+            r = subprocess.run(argv + (["--bulk-first"] if i % 2 else []), stdout=subprocess.PIPE, text=True, timeout=args.leg_timeout)
+        except subprocess.TimeoutExpired:
+            raise SystemExit(f"leg {i} did not end within {args.leg_timeout} s")
+        if r.returncode != 0:
+            raise SystemExit(f"leg {i} ended with {r.returncode}")
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+    out = {"summary": True, "rows": args.rows, "dim": args.dim, "preset": args.preset, "metric": args.metric, "repeats": args.repeats,
+           "bulk_policy": args.bulk_policy, "files_byte_equal": all(x["files_byte_equal"] for x in lines)}
+    for f in ("insert_build_s", "bulk_build_s", "walk_s", "commit_s", "patch_s", "accepted_share"):
+        v = [x[f] for x in lines]
+        out[f] = round(float(np.median(v)), 3)
+        out[f + "_spread"] = round(float((max(v) - min(v)) / max(np.median(v), 1e-12)), 3)
+    out["speedup_of_medians"] = round(out["insert_build_s"] / max(out["bulk_build_s"], 1e-9), 3)
+    print(json.dumps(out), flush=True)
+
+
+def bulk_build_leg(n, d, cfg, args, out):
+    """one leg of --bulk-build: both builds on fresh handles in 50 000-row calls, the two saved files compared byte for byte"""
+    import filecmp
+    import tempfile
+    from neumann_amd import GpuHnsw, synth_rows
+    step = 50_000
+    tmp = tempfile.mkdtemp(prefix="hnsw_bulk_")
+    paths = {}
+    try:
+        for which in (("bulk", "insert") if args.bulk_first else ("insert", "bulk")):
+            trace, call_s = [], []
+            with GpuHnsw(d, cfg, capacity_hint=n) as g:
+                t0 = time.perf_counter()
+                for r0 in range(0, n, step):
+                    rows = synth_rows(0x2F6, r0, min(step, n - r0), d)
+                    t1 = time.perf_counter()
+                    if which == "bulk":
+                        g.set_bulk_policy(*[int(x) for x in args.bulk_policy.split(",")])
+                        g.insert_bulk(rows)
+                        trace.append(g.bulk_trace())
+                    else:
+                        g.insert(rows)
+                    call_s.append(round(time.perf_counter() - t1, 2))
+                    print(f"{which}: built {min(r0 + step, n)} nodes in {time.perf_counter() - t0:.1f} s", file=sys.stderr, flush=True)
+                out[which + "_build_s"] = round(time.perf_counter() - t0, 2)
+                out[which + "_call_s"] = call_s  # seconds of every 50 000-row call: the graph grows from call to call
+                if which == "bulk":
+                    out["bulk_call_accepted_share"] = [round(float((t[:, 0] - t[:, 1]).sum() / max(t[:, 0].sum(), 1)), 3) for t in trace]
+                    out["bulk_call_mean_batch"] = [round(float(t[:, 0].mean()), 1) if len(t) else 0.0 for t in trace]
+                    out["bulk_call_walk_s"] = [round(float(t[:, 2].sum()) / 1e3, 2) for t in trace]
+                    st = g.bulk_stats()
+                    tr = np.concatenate(trace) if trace else np.zeros((0, 5), np.float32)
+                    out["bulk_stats"] = st
+                    out["accepted_share"] = round(st["accepted"] / max(st["walks"], 1), 4)
+                    out["walk_s"], out["commit_s"], out["patch_s"] = (round(float(tr[:, c].sum()) / 1e3, 3) for c in (2, 3, 4))
+                    sizes = tr[:, 0].astype(int)
+                    out["batch_size_histogram"] = {str(int(b)): int((sizes == b).sum()) for b in np.unique(sizes)}
+                    runs = []  # the trace run-length coded: [size, batches in a row]
+                    for b in sizes.tolist():
+                        if runs and runs[-1][0] == b:
+                            runs[-1][1] += 1
+                        else:
+                            runs.append([b, 1])
+                    out["batch_size_runs"] = runs[:48]
+                    out["batch_size_runs_total"] = len(runs)
+                paths[which] = os.path.join(tmp, which + ".idx")
+                g.save(paths[which])
+        out["files_byte_equal"] = filecmp.cmp(paths["insert"], paths["bulk"], shallow=False)
+        out["index_file_bytes"] = os.path.getsize(paths["bulk"])
+    finally:
+        for pth in paths.values():
+            if os.path.exists(pth):
+                os.remove(pth)
+        os.rmdir(tmp)
+    if not out["files_byte_equal"]:
+        print(json.dumps(out), flush=True)
+        raise SystemExit("--bulk-build: the two saved indexes differ")
+    return out
 
 
 def time_sparse(g, Q, k, args):
@@ -572,7 +666,17 @@ def main():
                          "same handle, alternating call by call (docs/hnsw.md §17); one repetition per process")
     ap.add_argument("--index-file", default=None,
                     help="load the index from this file when it exists; otherwise build, save it there and report build / save / load seconds")
+    ap.add_argument("--bulk-build", action="store_true",
+                    help="build the same rows with nmn_hnsw_insert and with nmn_hnsw_insert_bulk on fresh handles, check the saved files "
+                         "byte-equal, and report both build_s, the bulk counters and the batch-size trace (docs/hnsw.md §19); "
+                         "--repeats legs, each a fresh child process under --leg-timeout")
+    ap.add_argument("--bulk-leg", action="store_true", help="(one leg of --bulk-build, in this process)")
+    ap.add_argument("--bulk-first", action="store_true", help="(--bulk-leg: the bulk build before the sequential one)")
+    ap.add_argument("--bulk-policy", default="0,0", help="--bulk-build: batch,min_nodes of nmn_hnsw_set_bulk_policy (0 = default)")
     args = ap.parse_args()
+    if args.bulk_build and not args.bulk_leg:
+        bulk_build_legs(args)
+        return
     if args.sparse_callers and not args.sparse_leg:
         sparse_caller_legs(args)
         return
@@ -599,6 +703,10 @@ def main():
     metric = DistanceMetric(args.metric)
     Q = synth_rows(0x2F8, 0, 1024, d)
     out = {"rows": n, "dim": d, "preset": args.preset, "metric": args.metric, "k": k}
+    if args.bulk_build:
+        del out["k"]
+        print(json.dumps(bulk_build_leg(n, d, cfg, args, out)), flush=True)
+        return
     if args.callers:
         out.update({"storage": args.storage, "lib": os.environ.get("NEUMANN_GPU_LIB", "default"),
                     "no_coalesce": bool(os.environ.get("NMN_HNSW_NO_COALESCE")), "caller_calls": args.caller_calls})
