@@ -35,6 +35,9 @@ SOURCES = {
     "nmn_kmeans.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     "nmn_ivf_codec.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     "nmn_hnsw.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
+    "nmn_hnsw_kernels.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
+    "nmn_hnsw_build.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
+    "nmn_hnsw_file.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     "nmn_xmetric.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     "nmn_tt.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     "nmn_api.hip": [],
@@ -43,7 +46,8 @@ SOURCES = {
     "nmn_engine.cpp": ["-ffp-contract=off"],
     "nmn_cache_index.cpp": ["-ffp-contract=off"],
 }
-HEADERS = ["nmn_internal.h", "nmn_index.h", "nmn_scan_mfma_kernel.h", "nmn_persist.h", "nmn_select_dev.h", "nmn_hnsw_queue.h", "nmn_tt.h", os.path.join("..", "..", "include", "neumann_gpu.h"),
+HEADERS = ["nmn_internal.h", "nmn_index.h", "nmn_scan_mfma_kernel.h", "nmn_persist.h", "nmn_select_dev.h", "nmn_hnsw_queue.h", "nmn_tt.h",
+           "nmn_hnsw_arith.h", "nmn_hnsw_kernels.h", "nmn_hnsw_handle.h", "nmn_hnsw_host.h", os.path.join("..", "..", "include", "neumann_gpu.h"),
            os.path.join("..", "..", "include", "neumann_engine.h"), os.path.join("..", "..", "include", "neumann_cache.h")]
 
 
@@ -88,7 +92,7 @@ def build(force=False, verbose=False):
         return r.stderr
 
     if jobs:
-        with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 4)) as ex:
+        with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 4, 16)) as ex:
             for warn in ex.map(run, jobs):
                 if verbose and warn.strip():
                     print(warn)

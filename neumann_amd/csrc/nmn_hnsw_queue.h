@@ -17,7 +17,7 @@ constexpr uint32_t kShareCandMax = 4096;  // a metric call that asks for more ca
                                           // N x max k, and one huge caller must not size them for a thousand others
 constexpr uint32_t kBatchQueries = 1024;  // queries a coalesced batch carries at most: four waves per CU, the largest call §6 measured
 
-struct SparseQueries;  // the canonicalised queries of a sparse call (nmn_hnsw.hip); the queue only carries the pointer
+struct SparseQueries;  // the canonicalised queries of a sparse call (nmn_hnsw_handle.h); the queue only carries the pointer
 
 // One call of nmn_hnsw_search (k1 / ef1), nmn_hnsw_search_multi (k / ef per query), nmn_hnsw_search_metric (xm, one metric; k1 its
 // top_k), nmn_hnsw_search_metric_multi (xm, xm_stride 1: a metric per query; k their top_k), nmn_hnsw_search_sparse (sp; k1 / ef1) or

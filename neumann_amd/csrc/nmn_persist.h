@@ -1,4 +1,4 @@
-// nmn_persist.h — on-disk sections shared by nmn_persist.hip (flat shard), nmn_ivf.hip (IVF), nmn_hnsw.hip (HNSW) and nmn_engine.cpp
+// nmn_persist.h — on-disk sections shared by nmn_persist.hip (flat shard), nmn_ivf.hip (IVF), nmn_hnsw_file.hip (HNSW) and nmn_engine.cpp
 // (a collection's keys + metadata around a shard section).  Internal: never installed.
 #pragma once
 #include <cstdio>

@@ -74,6 +74,44 @@ def _storage_code(storage):
         raise _capi.NeumannGpuError(_capi.ERR_CONFIGURATION, f"unknown HNSW storage strategy {storage!r}")
 
 
+def _csr(indptr, positions, values, n):
+    """the CSR triple of a sparse call as contiguous (indptr u64, positions u32, values f32); `n`: what the message calls the row count"""
+    ip = np.ascontiguousarray(indptr, dtype=np.uint64).reshape(-1)
+    pos = np.ascontiguousarray(positions, dtype=np.uint32).reshape(-1)
+    val = np.ascontiguousarray(values, dtype=np.float32).reshape(-1)
+    if ip.size == 0 or pos.size != val.size or (ip.size and int(ip.max()) > pos.size):
+        raise _capi.NeumannGpuError(_capi.ERR_INVALID_ARGUMENT, f"indptr [{n} + 1] into positions / values of one length")
+    return ip, pos, val
+
+
+def _per_query(k, ef, kstride, nq, what):
+    """the arrays of a _multi call -> (k u32 [nq], ef u32 [nq] or None, kstride: max(k) when None); `what`: the message of a wrong length"""
+    kk = np.ascontiguousarray(k, dtype=np.uint32).reshape(-1)
+    ee = None if ef is None else np.ascontiguousarray(ef, dtype=np.uint32).reshape(-1)
+    if kk.size != nq or (ee is not None and ee.size != nq):
+        raise _capi.NeumannGpuError(_capi.ERR_INVALID_ARGUMENT, what)
+    return kk, ee, int(kk.max()) if kstride is None and nq else int(kstride or 1)
+
+
+def _host_out(nq, k):
+    """what a host call answers into: (ids u64 [nq,k], scores f32 [nq,k], counts u32 [nq], stats), a row at least one slot long"""
+    kk = max(k, 1)
+    return (np.empty((nq, kk), dtype=np.uint64), np.empty((nq, kk), dtype=np.float32), np.empty(nq, dtype=np.uint32),
+            _capi.SearchStats())
+
+
+def _device_out(out, nq, k, device):
+    """`out` of a _device call, or (ids int64 [nq,k], scores f32 [nq,k], counts int32 [nq]) allocated on `device`"""
+    import torch
+
+    if out is not None:
+        ids, sc, counts = out
+        return ids, sc, counts
+    kk = max(k, 1)
+    return (torch.empty((nq, kk), dtype=torch.int64, device=device), torch.empty((nq, kk), dtype=torch.float32, device=device),
+            torch.empty((nq,), dtype=torch.int32, device=device))
+
+
 class HNSWBuildOptions:
     """HNSWBuildOptions (vector_engine/src/lib.rs:848-932): a storage strategy ("dense", "auto", "quantized") and an HNSWConfig."""
 
@@ -202,13 +240,33 @@ class GpuHnsw:
     def hbm_bytes(self):
         return int(self._lib.nmn_hnsw_hbm_bytes(self._h))
 
-    def insert(self, rows):
-        """HNSWIndex::insert for each row in order; returns the node ids."""
+    def _rows(self, rows):
+        """rows or queries -> contiguous f32 [n, dim] (a single one: [1, dim]), the dimension checked"""
         r = np.ascontiguousarray(rows, dtype=np.float32)
         if r.ndim == 1:
             r = r[None, :]
         if r.shape[1] != self.dim:
             raise _capi.NeumannGpuError(_capi.ERR_DIMENSION_MISMATCH, f"expected {self.dim}, got {r.shape[1]}")
+        return r
+
+    def _device_queries(self, queries_t, k):
+        """the queries of a _device call checked -> (contiguous f32 device tensor [nq, dim], nq, int(k))"""
+        import torch
+
+        if not (isinstance(queries_t, torch.Tensor) and queries_t.is_cuda):
+            raise _capi.NeumannGpuError(_capi.ERR_INVALID_ARGUMENT, "queries must be a device tensor")
+        if queries_t.dtype != torch.float32 or not queries_t.is_contiguous():
+            raise _capi.NeumannGpuError(_capi.ERR_INVALID_ARGUMENT, "queries must be contiguous float32")
+        if queries_t.dim() == 1:
+            queries_t = queries_t[None, :]
+        nq, k = queries_t.shape[0], int(k)
+        if queries_t.shape[1] != self.dim:
+            raise _capi.NeumannGpuError(_capi.ERR_DIMENSION_MISMATCH, f"expected {self.dim}")
+        return queries_t, nq, k
+
+    def insert(self, rows):
+        """HNSWIndex::insert for each row in order; returns the node ids."""
+        r = self._rows(rows)
         ids = np.empty(r.shape[0], dtype=np.uint64)
         _capi.check(self._lib.nmn_hnsw_insert(self._h, C.c_void_p(r.ctypes.data), r.shape[0], C.c_void_p(ids.ctypes.data)))
         return ids
@@ -216,11 +274,7 @@ class GpuHnsw:
     def insert_bulk(self, rows):
         """`insert` with the searches of every new node walked on the GPU, a batch of nodes per launch, and committed on the host
         in order (nmn_hnsw_insert_bulk, docs/hnsw.md §19): the same graph, ids and generator state; returns the node ids."""
-        r = np.ascontiguousarray(rows, dtype=np.float32)
-        if r.ndim == 1:
-            r = r[None, :]
-        if r.shape[1] != self.dim:
-            raise _capi.NeumannGpuError(_capi.ERR_DIMENSION_MISMATCH, f"expected {self.dim}, got {r.shape[1]}")
+        r = self._rows(rows)
         ids = np.empty(r.shape[0], dtype=np.uint64)
         _capi.check(self._lib.nmn_hnsw_insert_bulk(self._h, C.c_void_p(r.ctypes.data), r.shape[0], C.c_void_p(ids.ctypes.data)))
         return ids
@@ -251,11 +305,7 @@ class GpuHnsw:
         """HNSWIndex::insert_sparse for each CSR row in order (nmn_hnsw_insert_sparse); returns the node ids.  Row i is the
         (position, value) pairs [indptr[i], indptr[i + 1]), made a SparseVector as try_from_parts does (`search_sparse`'s rules);
         the node is stored Sparse and scored by SparseVector's own arithmetic (docs/hnsw.md §15).  Dense handles only."""
-        ip = np.ascontiguousarray(indptr, dtype=np.uint64).reshape(-1)
-        pos = np.ascontiguousarray(positions, dtype=np.uint32).reshape(-1)
-        val = np.ascontiguousarray(values, dtype=np.float32).reshape(-1)
-        if ip.size == 0 or pos.size != val.size or (ip.size and int(ip.max()) > pos.size):
-            raise _capi.NeumannGpuError(_capi.ERR_INVALID_ARGUMENT, "indptr [n + 1] into positions / values of one length")
+        ip, pos, val = _csr(indptr, positions, values, "n")
         n = ip.size - 1
         ids = np.empty(n, dtype=np.uint64)
         _capi.check(self._lib.nmn_hnsw_insert_sparse(self._h, C.c_void_p(ip.ctypes.data), C.c_void_p(pos.ctypes.data),
@@ -265,11 +315,7 @@ class GpuHnsw:
     def insert_auto(self, rows):
         """HNSWIndex::insert_auto for each row in order (nmn_hnsw_insert_auto): a row whose share of zeros reaches
         config.sparsity_threshold is stored Sparse(from_dense(row)), every other Dense; returns the node ids."""
-        r = np.ascontiguousarray(rows, dtype=np.float32)
-        if r.ndim == 1:
-            r = r[None, :]
-        if r.shape[1] != self.dim:
-            raise _capi.NeumannGpuError(_capi.ERR_DIMENSION_MISMATCH, f"expected {self.dim}, got {r.shape[1]}")
+        r = self._rows(rows)
         ids = np.empty(r.shape[0], dtype=np.uint64)
         _capi.check(self._lib.nmn_hnsw_insert_auto(self._h, C.c_void_p(r.ctypes.data), r.shape[0], C.c_void_p(ids.ctypes.data)))
         return ids
@@ -348,16 +394,9 @@ class GpuHnsw:
 
     def search(self, queries, k, ef=None, with_stats=False):
         """-> (ids u64 [nq,k], scores f32 [nq,k], counts u32 [nq]); HNSWIndex::search_with_ef per query (ef None: ef_search)."""
-        q = np.ascontiguousarray(queries, dtype=np.float32)
-        if q.ndim == 1:
-            q = q[None, :]
-        if q.shape[1] != self.dim:
-            raise _capi.NeumannGpuError(_capi.ERR_DIMENSION_MISMATCH, f"expected {self.dim}, got {q.shape[1]}")
+        q = self._rows(queries)
         nq, k = q.shape[0], int(k)
-        ids = np.empty((nq, max(k, 1)), dtype=np.uint64)
-        sc = np.empty((nq, max(k, 1)), dtype=np.float32)
-        counts = np.empty(nq, dtype=np.uint32)
-        st = _capi.SearchStats()
+        ids, sc, counts, st = _host_out(nq, k)
         _capi.check(self._lib.nmn_hnsw_search(self._h, C.c_void_p(q.ctypes.data), nq, k, 0 if ef is None else int(ef),
                                               C.c_void_p(ids.ctypes.data), C.c_void_p(sc.ctypes.data),
                                               C.c_void_p(counts.ctypes.data), C.byref(st)))
@@ -367,21 +406,10 @@ class GpuHnsw:
         """`search` with a k and an ef per query in ONE launch (nmn_hnsw_search_multi).  `k`: one integer per query; `ef`: None
         (ef_search for all) or one per query, 0 = ef_search; `kstride`: row length of the outputs (None: max(k)).
         -> (ids u64 [nq,kstride], scores f32 [nq,kstride], counts u32 [nq]); row i is what search(q_i, k[i], ef[i]) answers."""
-        q = np.ascontiguousarray(queries, dtype=np.float32)
-        if q.ndim == 1:
-            q = q[None, :]
-        if q.shape[1] != self.dim:
-            raise _capi.NeumannGpuError(_capi.ERR_DIMENSION_MISMATCH, f"expected {self.dim}, got {q.shape[1]}")
+        q = self._rows(queries)
         nq = q.shape[0]
-        kk = np.ascontiguousarray(k, dtype=np.uint32).reshape(-1)
-        ee = None if ef is None else np.ascontiguousarray(ef, dtype=np.uint32).reshape(-1)
-        if kk.size != nq or (ee is not None and ee.size != nq):
-            raise _capi.NeumannGpuError(_capi.ERR_INVALID_ARGUMENT, "one k (and one ef) per query")
-        ks = int(kk.max()) if kstride is None and nq else int(kstride or 1)
-        ids = np.empty((nq, max(ks, 1)), dtype=np.uint64)
-        sc = np.empty((nq, max(ks, 1)), dtype=np.float32)
-        counts = np.empty(nq, dtype=np.uint32)
-        st = _capi.SearchStats()
+        kk, ee, ks = _per_query(k, ef, kstride, nq, "one k (and one ef) per query")
+        ids, sc, counts, st = _host_out(nq, ks)
         _capi.check(self._lib.nmn_hnsw_search_multi(self._h, C.c_void_p(q.ctypes.data), nq, C.c_void_p(kk.ctypes.data),
                                                     C.c_void_p(ee.ctypes.data) if ee is not None else None, ks,
                                                     C.c_void_p(ids.ctypes.data), C.c_void_p(sc.ctypes.data),
@@ -405,16 +433,9 @@ class GpuHnsw:
         pairs [indptr[i], indptr[i + 1]) of `positions` / `values`, in any order; they are made a SparseVector as try_from_parts
         does (zeros dropped, stably sorted by position; a position >= dim is refused).
         -> (ids u64 [nq,k], scores f32 [nq,k], counts u32 [nq])"""
-        ip = np.ascontiguousarray(indptr, dtype=np.uint64).reshape(-1)
-        pos = np.ascontiguousarray(positions, dtype=np.uint32).reshape(-1)
-        val = np.ascontiguousarray(values, dtype=np.float32).reshape(-1)
-        if ip.size == 0 or pos.size != val.size or (ip.size and int(ip.max()) > pos.size):
-            raise _capi.NeumannGpuError(_capi.ERR_INVALID_ARGUMENT, "indptr [nq + 1] into positions / values of one length")
+        ip, pos, val = _csr(indptr, positions, values, "nq")
         nq, k = ip.size - 1, int(k)
-        ids = np.empty((nq, max(k, 1)), dtype=np.uint64)
-        sc = np.empty((nq, max(k, 1)), dtype=np.float32)
-        counts = np.empty(nq, dtype=np.uint32)
-        st = _capi.SearchStats()
+        ids, sc, counts, st = _host_out(nq, k)
         _capi.check(self._lib.nmn_hnsw_search_sparse(self._h, C.c_void_p(ip.ctypes.data), C.c_void_p(pos.ctypes.data),
                                                      C.c_void_p(val.ctypes.data), nq, k, 0 if ef is None else int(ef),
                                                      C.c_void_p(ids.ctypes.data), C.c_void_p(sc.ctypes.data),
@@ -426,21 +447,10 @@ class GpuHnsw:
         `k`: one integer per query; `ef`: None (ef_search for all) or one per query, 0 = ef_search; `kstride`: row length of the
         outputs (None: max(k)).
         -> (ids u64 [nq,kstride], scores f32 [nq,kstride], counts u32 [nq]); row i is what search_sparse(q_i, k[i], ef[i]) answers."""
-        ip = np.ascontiguousarray(indptr, dtype=np.uint64).reshape(-1)
-        pos = np.ascontiguousarray(positions, dtype=np.uint32).reshape(-1)
-        val = np.ascontiguousarray(values, dtype=np.float32).reshape(-1)
-        if ip.size == 0 or pos.size != val.size or (ip.size and int(ip.max()) > pos.size):
-            raise _capi.NeumannGpuError(_capi.ERR_INVALID_ARGUMENT, "indptr [nq + 1] into positions / values of one length")
+        ip, pos, val = _csr(indptr, positions, values, "nq")
         nq = ip.size - 1
-        kk = np.ascontiguousarray(k, dtype=np.uint32).reshape(-1)
-        ee = None if ef is None else np.ascontiguousarray(ef, dtype=np.uint32).reshape(-1)
-        if kk.size != nq or (ee is not None and ee.size != nq):
-            raise _capi.NeumannGpuError(_capi.ERR_INVALID_ARGUMENT, "one k (and one ef) per query")
-        ks = int(kk.max()) if kstride is None and nq else int(kstride or 1)
-        ids = np.empty((nq, max(ks, 1)), dtype=np.uint64)
-        sc = np.empty((nq, max(ks, 1)), dtype=np.float32)
-        counts = np.empty(nq, dtype=np.uint32)
-        st = _capi.SearchStats()
+        kk, ee, ks = _per_query(k, ef, kstride, nq, "one k (and one ef) per query")
+        ids, sc, counts, st = _host_out(nq, ks)
         _capi.check(self._lib.nmn_hnsw_search_sparse_multi(self._h, C.c_void_p(ip.ctypes.data), C.c_void_p(pos.ctypes.data),
                                                            C.c_void_p(val.ctypes.data), nq, C.c_void_p(kk.ctypes.data),
                                                            C.c_void_p(ee.ctypes.data) if ee is not None else None, ks,
@@ -458,24 +468,8 @@ class GpuHnsw:
         """`search` with torch device tensors, in stream order (nmn_hnsw_search_device): enqueued on `stream` (None: torch's
         current stream), returns without waiting.  Returns (ids int64 [nq,k] holding the u64 bit pattern, -1 = unused slot;
         scores f32 [nq,k]; counts int32 [nq]), allocated on the queries' device unless `out` supplies them."""
-        import torch
-
-        if not (isinstance(queries_t, torch.Tensor) and queries_t.is_cuda):
-            raise _capi.NeumannGpuError(_capi.ERR_INVALID_ARGUMENT, "queries must be a device tensor")
-        if queries_t.dtype != torch.float32 or not queries_t.is_contiguous():
-            raise _capi.NeumannGpuError(_capi.ERR_INVALID_ARGUMENT, "queries must be contiguous float32")
-        if queries_t.dim() == 1:
-            queries_t = queries_t[None, :]
-        nq, k = queries_t.shape[0], int(k)
-        if queries_t.shape[1] != self.dim:
-            raise _capi.NeumannGpuError(_capi.ERR_DIMENSION_MISMATCH, f"expected {self.dim}")
-        if out is None:
-            kk = max(k, 1)
-            ids = torch.empty((nq, kk), dtype=torch.int64, device=queries_t.device)
-            sc = torch.empty((nq, kk), dtype=torch.float32, device=queries_t.device)
-            counts = torch.empty((nq,), dtype=torch.int32, device=queries_t.device)
-        else:
-            ids, sc, counts = out
+        queries_t, nq, k = self._device_queries(queries_t, k)
+        ids, sc, counts = _device_out(out, nq, k, queries_t.device)
         _capi.check(self._lib.nmn_hnsw_search_device(
             self._h, C.c_void_p(queries_t.data_ptr()), nq, k, 0 if ef is None else int(ef), C.c_void_p(ids.data_ptr()),
             C.c_void_p(sc.data_ptr()), C.c_void_p(counts.data_ptr()), _stream_ptr(stream)))
@@ -489,10 +483,7 @@ class GpuHnsw:
         from . import tt as _tt
         shape, ranks, off, cores = _tt.pack(tts)
         nq, k = ranks.shape[0], int(k)
-        ids = np.empty((nq, max(k, 1)), dtype=np.uint64)
-        sc = np.empty((nq, max(k, 1)), dtype=np.float32)
-        counts = np.empty(nq, dtype=np.uint32)
-        st = _capi.SearchStats()
+        ids, sc, counts, st = _host_out(nq, k)
         _capi.check(self._lib.nmn_hnsw_search_tt(self._h, C.c_void_p(shape.ctypes.data), shape.size, C.c_void_p(ranks.ctypes.data),
                                                  C.c_void_p(off.ctypes.data), C.c_void_p(cores.ctypes.data), nq, k,
                                                  0 if ef is None else int(ef), C.c_void_p(ids.ctypes.data),
@@ -518,13 +509,7 @@ class GpuHnsw:
         if cores_t.shape[1] != storage:
             raise _capi.NeumannGpuError(_capi.ERR_INVALID_ARGUMENT, f"TT: a train of these ranks holds {storage} floats")
         nq, k = cores_t.shape[0], int(k)
-        if out is None:
-            kk = max(k, 1)
-            ids = torch.empty((nq, kk), dtype=torch.int64, device=cores_t.device)
-            sc = torch.empty((nq, kk), dtype=torch.float32, device=cores_t.device)
-            counts = torch.empty((nq,), dtype=torch.int32, device=cores_t.device)
-        else:
-            ids, sc, counts = out
+        ids, sc, counts = _device_out(out, nq, k, cores_t.device)
         _capi.check(self._lib.nmn_hnsw_search_tt_device(
             self._h, C.c_void_p(sh.ctypes.data), sh.size, C.c_void_p(rk.ctypes.data), C.c_void_p(cores_t.data_ptr()), nq, k,
             0 if ef is None else int(ef), C.c_void_p(ids.data_ptr()), C.c_void_p(sc.data_ptr()), C.c_void_p(counts.data_ptr()),
@@ -547,16 +532,9 @@ class GpuHnsw:
         """search_with_hnsw_and_metric's steps per query (nmn_hnsw_search_metric): c = max(2 top_k, 10) candidates from the walk,
         re-ranked under `metric` (an ExtendedDistanceMetric), the first top_k of the stable descending order.
         -> (ids u64 [nq,top_k], scores f32 [nq,top_k], counts u32 [nq])"""
-        q = np.ascontiguousarray(queries, dtype=np.float32)
-        if q.ndim == 1:
-            q = q[None, :]
-        if q.shape[1] != self.dim:
-            raise _capi.NeumannGpuError(_capi.ERR_DIMENSION_MISMATCH, f"expected {self.dim}, got {q.shape[1]}")
+        q = self._rows(queries)
         nq, k = q.shape[0], int(top_k)
-        ids = np.empty((nq, max(k, 1)), dtype=np.uint64)
-        sc = np.empty((nq, max(k, 1)), dtype=np.float32)
-        counts = np.empty(nq, dtype=np.uint32)
-        st = _capi.SearchStats()
+        ids, sc, counts, st = _host_out(nq, k)
         m = metric._c()
         _capi.check(self._lib.nmn_hnsw_search_metric(self._h, C.c_void_p(q.ctypes.data), nq, k, C.byref(m),
                                                      C.c_void_p(ids.ctypes.data), C.c_void_p(sc.ctypes.data),
@@ -568,22 +546,14 @@ class GpuHnsw:
         per query; `metrics`: one ExtendedDistanceMetric per query; `kstride`: row length of the outputs (None: max(top_k)).
         -> (ids u64 [nq,kstride], scores f32 [nq,kstride], counts u32 [nq]); row i is what search_metric(q_i, top_k[i],
         metrics[i]) answers."""
-        q = np.ascontiguousarray(queries, dtype=np.float32)
-        if q.ndim == 1:
-            q = q[None, :]
-        if q.shape[1] != self.dim:
-            raise _capi.NeumannGpuError(_capi.ERR_DIMENSION_MISMATCH, f"expected {self.dim}, got {q.shape[1]}")
+        q = self._rows(queries)
         nq = q.shape[0]
-        kk = np.ascontiguousarray(top_k, dtype=np.uint32).reshape(-1)
         metrics = list(metrics)
-        if kk.size != nq or len(metrics) != nq:
+        kk, _, ks = _per_query(top_k, None, kstride, nq, "one top_k and one metric per query")
+        if len(metrics) != nq:
             raise _capi.NeumannGpuError(_capi.ERR_INVALID_ARGUMENT, "one top_k and one metric per query")
         mm = (_capi.XMetric * max(nq, 1))(*[m._c() for m in metrics])
-        ks = int(kk.max()) if kstride is None and nq else int(kstride or 1)
-        ids = np.empty((nq, max(ks, 1)), dtype=np.uint64)
-        sc = np.empty((nq, max(ks, 1)), dtype=np.float32)
-        counts = np.empty(nq, dtype=np.uint32)
-        st = _capi.SearchStats()
+        ids, sc, counts, st = _host_out(nq, ks)
         _capi.check(self._lib.nmn_hnsw_search_metric_multi(self._h, C.c_void_p(q.ctypes.data), nq, C.c_void_p(kk.ctypes.data),
                                                            C.cast(mm, C.c_void_p), ks, C.c_void_p(ids.ctypes.data),
                                                            C.c_void_p(sc.ctypes.data), C.c_void_p(counts.ctypes.data), C.byref(st)))
@@ -592,24 +562,8 @@ class GpuHnsw:
     def search_metric_device(self, queries_t, top_k, metric, out=None, stream=None):
         """`search_metric` with torch device tensors, in stream order (nmn_hnsw_search_metric_device); same conventions as
         `search_device`."""
-        import torch
-
-        if not (isinstance(queries_t, torch.Tensor) and queries_t.is_cuda):
-            raise _capi.NeumannGpuError(_capi.ERR_INVALID_ARGUMENT, "queries must be a device tensor")
-        if queries_t.dtype != torch.float32 or not queries_t.is_contiguous():
-            raise _capi.NeumannGpuError(_capi.ERR_INVALID_ARGUMENT, "queries must be contiguous float32")
-        if queries_t.dim() == 1:
-            queries_t = queries_t[None, :]
-        nq, k = queries_t.shape[0], int(top_k)
-        if queries_t.shape[1] != self.dim:
-            raise _capi.NeumannGpuError(_capi.ERR_DIMENSION_MISMATCH, f"expected {self.dim}")
-        if out is None:
-            kk = max(k, 1)
-            ids = torch.empty((nq, kk), dtype=torch.int64, device=queries_t.device)
-            sc = torch.empty((nq, kk), dtype=torch.float32, device=queries_t.device)
-            counts = torch.empty((nq,), dtype=torch.int32, device=queries_t.device)
-        else:
-            ids, sc, counts = out
+        queries_t, nq, k = self._device_queries(queries_t, top_k)
+        ids, sc, counts = _device_out(out, nq, k, queries_t.device)
         m = metric._c()
         _capi.check(self._lib.nmn_hnsw_search_metric_device(
             self._h, C.c_void_p(queries_t.data_ptr()), nq, k, C.byref(m), C.c_void_p(ids.data_ptr()), C.c_void_p(sc.data_ptr()),
@@ -632,16 +586,9 @@ class GpuHnsw:
         §16): c = max(3k, 10) candidates from the walk, dead nodes dropped, every other re-scored under `metric` on its stored form
         (a Sparse node by its own entries), kept iff similarity >= threshold, the first k of the stable descending order.
         -> (ids u64 [nq,k], similarities f32 [nq,k], counts u32 [nq])"""
-        q = np.ascontiguousarray(queries, dtype=np.float32)
-        if q.ndim == 1:
-            q = q[None, :]
-        if q.shape[1] != self.dim:
-            raise _capi.NeumannGpuError(_capi.ERR_DIMENSION_MISMATCH, f"expected {self.dim}, got {q.shape[1]}")
+        q = self._rows(queries)
         nq, k = q.shape[0], int(k)
-        ids = np.empty((nq, max(k, 1)), dtype=np.uint64)
-        sc = np.empty((nq, max(k, 1)), dtype=np.float32)
-        counts = np.empty(nq, dtype=np.uint32)
-        st = _capi.SearchStats()
+        ids, sc, counts, st = _host_out(nq, k)
         m = metric._c()
         _capi.check(self._lib.nmn_hnsw_cache_search(self._h, C.c_void_p(q.ctypes.data), nq, k, float(threshold), C.byref(m),
                                                     C.c_void_p(ids.ctypes.data), C.c_void_p(sc.ctypes.data),
@@ -652,16 +599,9 @@ class GpuHnsw:
         """CacheIndex::search_sparse_with_metric per query (nmn_hnsw_cache_search_sparse): `cache_search` behind
         `search_sparse`'s walk, the query's own entries scored.  The CSR is `search_sparse`'s.
         -> (ids u64 [nq,k], similarities f32 [nq,k], counts u32 [nq])"""
-        ip = np.ascontiguousarray(indptr, dtype=np.uint64).reshape(-1)
-        pos = np.ascontiguousarray(positions, dtype=np.uint32).reshape(-1)
-        val = np.ascontiguousarray(values, dtype=np.float32).reshape(-1)
-        if ip.size == 0 or pos.size != val.size or (ip.size and int(ip.max()) > pos.size):
-            raise _capi.NeumannGpuError(_capi.ERR_INVALID_ARGUMENT, "indptr [nq + 1] into positions / values of one length")
+        ip, pos, val = _csr(indptr, positions, values, "nq")
         nq, k = ip.size - 1, int(k)
-        ids = np.empty((nq, max(k, 1)), dtype=np.uint64)
-        sc = np.empty((nq, max(k, 1)), dtype=np.float32)
-        counts = np.empty(nq, dtype=np.uint32)
-        st = _capi.SearchStats()
+        ids, sc, counts, st = _host_out(nq, k)
         m = metric._c()
         _capi.check(self._lib.nmn_hnsw_cache_search_sparse(self._h, C.c_void_p(ip.ctypes.data), C.c_void_p(pos.ctypes.data),
                                                            C.c_void_p(val.ctypes.data), nq, k, float(threshold), C.byref(m),
@@ -672,24 +612,8 @@ class GpuHnsw:
     def cache_search_device(self, queries_t, k, threshold, metric, out=None, stream=None):
         """`cache_search` with torch device tensors, in stream order (nmn_hnsw_cache_search_device); same conventions as
         `search_device`."""
-        import torch
-
-        if not (isinstance(queries_t, torch.Tensor) and queries_t.is_cuda):
-            raise _capi.NeumannGpuError(_capi.ERR_INVALID_ARGUMENT, "queries must be a device tensor")
-        if queries_t.dtype != torch.float32 or not queries_t.is_contiguous():
-            raise _capi.NeumannGpuError(_capi.ERR_INVALID_ARGUMENT, "queries must be contiguous float32")
-        if queries_t.dim() == 1:
-            queries_t = queries_t[None, :]
-        nq, k = queries_t.shape[0], int(k)
-        if queries_t.shape[1] != self.dim:
-            raise _capi.NeumannGpuError(_capi.ERR_DIMENSION_MISMATCH, f"expected {self.dim}")
-        if out is None:
-            kk = max(k, 1)
-            ids = torch.empty((nq, kk), dtype=torch.int64, device=queries_t.device)
-            sc = torch.empty((nq, kk), dtype=torch.float32, device=queries_t.device)
-            counts = torch.empty((nq,), dtype=torch.int32, device=queries_t.device)
-        else:
-            ids, sc, counts = out
+        queries_t, nq, k = self._device_queries(queries_t, k)
+        ids, sc, counts = _device_out(out, nq, k, queries_t.device)
         m = metric._c()
         _capi.check(self._lib.nmn_hnsw_cache_search_device(
             self._h, C.c_void_p(queries_t.data_ptr()), nq, k, float(threshold), C.byref(m), C.c_void_p(ids.data_ptr()),
