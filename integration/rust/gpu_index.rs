@@ -2,7 +2,7 @@
 //! `GpuFlatIndex` = one row-range shard on one GPU, `GpuShardedIndex` = one logical index over several GPUs of a node.
 //! Written against the reference's own types (`DistanceMetric`, `VectorError`, `Result`, lib.rs:148-260); this image has
 //! no Rust toolchain, so the file is not compiled here — the C ABI it calls is exercised by tests/ through ctypes and by
-//! nmn_engine.cpp.
+//! nmn_engine.cpp and the nmn_engine_*.cpp files beside it.
 #![allow(unsafe_code)]
 use std::ffi::{CStr, CString};
 use std::path::Path;
@@ -86,7 +86,7 @@ impl GpuFlatIndex {
         let desc = ffi::nmn_index_desc {
             dim: u32::try_from(dim).map_err(|_| VectorError::ConfigurationError("dimension exceeds u32".into()))?,
             flags: 0,
-            capacity_rows: n + n / 4 + 1024, // spare rows for appends (Mirror in nmn_engine.cpp)
+            capacity_rows: n + n / 4 + 1024, // spare rows for appends (Mirror in nmn_engine_internal.h; get_mirror in nmn_engine_mirror.cpp)
             row_base: 0,
             device,
             cand_cap: 0,

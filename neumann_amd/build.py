@@ -44,10 +44,13 @@ SOURCES = {
     "nmn_sharded.hip": [],
     "nmn_persist.hip": [],
     "nmn_engine.cpp": ["-ffp-contract=off"],
+    "nmn_engine_filter.cpp": ["-ffp-contract=off"],
+    "nmn_engine_mirror.cpp": ["-ffp-contract=off"],
+    "nmn_engine_persist.cpp": ["-ffp-contract=off"],
     "nmn_cache_index.cpp": ["-ffp-contract=off"],
 }
 HEADERS = ["nmn_internal.h", "nmn_index.h", "nmn_scan_mfma_kernel.h", "nmn_persist.h", "nmn_select_dev.h", "nmn_hnsw_queue.h", "nmn_tt.h",
-           "nmn_hnsw_arith.h", "nmn_hnsw_kernels.h", "nmn_hnsw_handle.h", "nmn_hnsw_host.h", os.path.join("..", "..", "include", "neumann_gpu.h"),
+           "nmn_hnsw_arith.h", "nmn_hnsw_kernels.h", "nmn_hnsw_handle.h", "nmn_hnsw_host.h", "nmn_engine_internal.h", "nmn_engine_json.h", os.path.join("..", "..", "include", "neumann_gpu.h"),
            os.path.join("..", "..", "include", "neumann_engine.h"), os.path.join("..", "..", "include", "neumann_cache.h")]
 
 

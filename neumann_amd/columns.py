@@ -1,7 +1,7 @@
 """Columnar metadata + WHERE-predicate programs on the GPU (include/neumann_gpu.h, `nmn_columns_*`).
 
 `GpuColumns` is the thin host wrapper of the C ABI the engine's pre-filter path drives
-(neumann_amd/csrc/nmn_engine.cpp: columns_build / compile_filter / pre_filter_search): typed
+(neumann_amd/csrc/nmn_engine_mirror.cpp: columns_build / pre_filter_search; nmn_engine_filter.cpp: compile_filter): typed
 (kind, payload) cells per row and field in HBM, a postfix predicate program evaluated by one kernel,
 the selection bitmap left in device memory for the masked scan.  It replaces the per-key
 `store.get` + `evaluate_filter` of the reference (vector_engine/src/lib.rs:3526-3530, 3582-3630).

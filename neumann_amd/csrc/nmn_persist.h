@@ -1,5 +1,5 @@
-// nmn_persist.h — on-disk sections shared by nmn_persist.hip (flat shard), nmn_ivf.hip (IVF), nmn_hnsw_file.hip (HNSW) and nmn_engine.cpp
-// (a collection's keys + metadata around a shard section).  Internal: never installed.
+// nmn_persist.h — on-disk sections shared by nmn_persist.hip (flat shard), nmn_ivf.hip (IVF), nmn_hnsw_file.hip (HNSW) and
+// nmn_engine_persist.cpp (a collection's keys + metadata around a shard section).  Internal: never installed.
 #pragma once
 #include <cstdio>
 

@@ -6,7 +6,7 @@
 // default; checked at 3831-3840 and 3847-3856).  What the GPU path adds to that is the matrix itself: the rows of a
 // shard exactly as they sit in HBM (row-major f32, the stride removed) plus their reference-order magnitudes, so that a
 // restart fills a shard with sequential reads and bulk H2D copies instead of per-key `store_embedding` calls.  Keys,
-// metadata and collection config stay in the engine's file (nmn_engine.cpp: save_index_binary wraps this section).
+// metadata and collection config stay in the engine's file (nmn_engine_persist.cpp: save_index_binary wraps this section).
 //
 // File = Header (64 bytes, little endian) | rows x dim f32, tightly packed | rows f32 magnitudes.
 // The bf16 mirror is not stored: it is a pure function of the rows (8.6 ms for 10M x 768) and is rebuilt on the first

@@ -479,6 +479,71 @@ def test_search_filtered_in_collection(E):  # lib.rs:7935-8000
     assert engine.search_filtered_in_collection("test", [0.0, 0.0], 10, FC.TRUE) == []
 
 
+def test_filtered_entries_differ_where_the_reference_does(E):
+    """search_similar_filtered (lib.rs:3438-3579) and search_filtered_in_collection (lib.rs:1708-1813) are two functions in the
+    reference, and they disagree in a few places; each is held here on three vectors of dimension 4."""
+    FC, FS = E.FilterCondition, E.FilteredSearchConfig
+    rows = {"a": [1.0, 0.0, 0.0, 0.0], "b": [0.0, 1.0, 0.0, 0.0], "c": [0.6, 0.8, 0.0, 0.0]}
+
+    def filled(config=None):
+        engine = E.VectorEngine(config) if config else E.VectorEngine()
+        engine.create_collection("euclid", E.VectorCollectionConfig().with_dimension(4).with_metric(E.DistanceMetric.Euclidean))
+        for key, v in rows.items():
+            engine.store_embedding_with_metadata(key, v, {"g": 1})
+            engine.store_in_collection_with_metadata("euclid", key, v, {"g": 1})
+        return engine
+
+    # max_dimension: checked by the default entry, not by the collection entry
+    engine = E.VectorEngine(E.VectorEngineConfig(max_dimension=2))
+    with pytest.raises(E.VectorError) as e:
+        engine.search_similar_filtered([1.0, 0.0, 0.0], 3, FC.TRUE)
+    assert e.value.kind == "DimensionMismatch" and str(e.value) == "Dimension mismatch: expected 2, got 3"
+    assert engine.search_filtered_in_collection("nosuch", [1.0, 0.0, 0.0], 3, FC.TRUE) == []
+
+    # Auto: the default entry sends True to the post-filter unsampled; the collection entry samples it like any condition
+    # (selectivity 1.0 < 2.0 -> the pre-filter, whose predicate runs on the device)
+    engine = filled()
+    auto = FS(E.FilterStrategy.Auto, selectivity_threshold=2.0)
+    assert [r.key for r in engine.search_similar_filtered(rows["a"], 3, FC.TRUE, auto)] == ["a", "c", "b"]
+    assert engine.device_filter_evals() == 0
+    assert [r.key for r in engine.search_filtered_in_collection("euclid", rows["a"], 3, FC.TRUE, auto)] == ["a", "c", "b"]
+    assert engine.device_filter_evals() == 1
+    assert len(engine.search_similar_filtered(rows["a"], 3, FC.Exists("g"), auto)) == 3  # any other condition is sampled there too
+    assert engine.device_filter_evals() == 2
+
+    # the post arm ranks by the collection's metric, the pre arm by cosine, in the collection entry; the default entry is cosine
+    q = [2.0, 0.0, 0.0, 0.0]
+    post = engine.search_filtered_in_collection("euclid", q, 1, FC.TRUE, FS.post_filter())
+    assert post[0].key == "a" and abs(post[0].score - 0.5) < 1e-6      # 1 / (1 + |q - a|)
+    pre = engine.search_filtered_in_collection("euclid", q, 1, FC.TRUE, FS.pre_filter())
+    assert pre[0].key == "a" and abs(pre[0].score - 1.0) < 1e-6
+    for cfg in (FS.post_filter(), FS.pre_filter()):
+        r = engine.search_similar_filtered(q, 1, FC.TRUE, cfg)
+        assert r[0].key == "a" and abs(r[0].score - 1.0) < 1e-6
+
+    # the collection entry checks the configured dimension before anything else that can fail
+    expired = filled(E.VectorEngineConfig(search_timeout=0.0))
+    with pytest.raises(E.VectorError) as e:
+        expired.search_filtered_in_collection("euclid", [1.0, 0.0, 0.0], 3, FC.TRUE)
+    assert e.value.kind == "DimensionMismatch" and str(e.value) == "Dimension mismatch: expected 4, got 3"
+    # an expired deadline: each entry names itself when the strategy has been chosen, under every strategy
+    for cfg in (None, FS.pre_filter(), FS.post_filter()):
+        with pytest.raises(E.VectorError) as e:
+            expired.search_similar_filtered(rows["a"], 3, FC.Eq("g", 1), cfg)
+        assert e.value.kind == "SearchTimeout" and str(e.value) == "search timeout: search_similar_filtered exceeded 0ms"
+        with pytest.raises(E.VectorError) as e:
+            expired.search_filtered_in_collection("euclid", rows["a"], 3, FC.Eq("g", 1), cfg)
+        assert e.value.kind == "SearchTimeout" and str(e.value) == "search timeout: search_filtered_in_collection exceeded 0ms"
+        # ... and a zero-magnitude query: the default entry tests it per arm, after that deadline, so the deadline wins; the
+        # collection entry answers an absent collection and a zero query with nothing before it looks at the clock
+        with pytest.raises(E.VectorError) as e:
+            expired.search_similar_filtered([0.0] * 4, 3, FC.Eq("g", 1), cfg)
+        assert str(e.value) == "search timeout: search_similar_filtered exceeded 0ms"
+        assert expired.search_filtered_in_collection("euclid", [0.0] * 4, 3, FC.Eq("g", 1), cfg) == []
+        assert expired.search_filtered_in_collection("nosuch", rows["a"], 3, FC.Eq("g", 1), cfg) == []
+    assert expired.mirror_builds() == 0 and expired.device_filter_evals() == 0
+
+
 def test_top_k_beyond_4096_returns_the_full_ranking(E):
     """The reference sorts every score and truncates (lib.rs:2026-2034): any top_k is legal."""
     rng = np.random.default_rng(8)

@@ -7,7 +7,7 @@ Part 1: 10M rows x 3 metadata columns resident in HBM; predicates of 1..5 leaves
 evaluation (program upload + kernel + count read-back, what the engine pays per filtered query) and
 the algorithmic bytes the leaves read (1 B kind + 8 B payload per row and leaf, 1 B for Exists).
 Part 2: the host evaluator the device path replaces — the C++ port of evaluate_filter
-(nmn_engine.cpp, following vector_engine/src/lib.rs:3592-3670) walking every entry, timed through
+(nmn_engine_filter.cpp, following vector_engine/src/lib.rs:3592-3670) walking every entry, timed through
 `count_matching` — against the engine's device pre-filter on the same store.
 Prints one JSON object."""
 import argparse
