@@ -867,6 +867,86 @@ nmn_status nmn_hnsw_search_tt_device(nmn_hnsw* h, const uint32_t* shape, uint32_
 nmn_status nmn_hnsw_insert_tt(nmn_hnsw* h, const uint32_t* shape, uint32_t n_cores, const uint32_t* ranks, const uint64_t* core_off,
                               const float* cores, uint64_t n, uint64_t* ids_out);
 
+/* ---- tt_decompose: from a dense vector and a TTConfig to a train (docs/hnsw.md §21) --------------------------------------- */
+
+/* A TTConfig (tensor_train.rs:41-49) crosses this interface as its parts: shape[n_cores], max_rank, tolerance.
+ * nmn_tt_config_for_dim: TTConfig::for_dim, ::high_compression and ::high_accuracy (tensor_train.rs:77-126) with optimal_shape and
+ * factorize_balanced (130-199; the f64 log2 and pow are the host libm's).  shape_out holds up to 8 modes.  dim == 0 is the
+ * reference's EmptyVector: NMN_ERR_INVALID_ARGUMENT, "empty vector". */
+#define NMN_TT_PRESET_FOR_DIM 0u          /* max_rank 8,  tolerance 1e-4 */
+#define NMN_TT_PRESET_HIGH_COMPRESSION 1u /* max_rank 4,  tolerance 1e-2 */
+#define NMN_TT_PRESET_HIGH_ACCURACY 2u    /* max_rank 16, tolerance 1e-6 */
+nmn_status nmn_tt_config_for_dim(uint64_t dim, uint32_t preset, uint32_t* shape_out, uint32_t* n_cores_out, uint32_t* max_rank_out,
+                                 float* tolerance_out);
+/* The slot of one train under a config, in floats: the sum of b[k] * shape[k] * b[k + 1] over the worst-case ranks b[0] = 1,
+ * b[k + 1] = min(max_rank, b[k] * shape[k], shape[k + 1] * .. * shape[n_cores - 1]), b[n_cores] = 1.  No train tt_decompose
+ * returns under the config is larger.  0 for a config the entries below refuse. */
+uint64_t nmn_tt_max_storage(const uint32_t* shape, uint32_t n_cores, uint32_t max_rank);
+
+/* Per-vector status of nmn_tt_decompose */
+#define NMN_TT_OK 0u           /* Ok(TTVector) */
+#define NMN_TT_EMPTY_MATRIX 1u /* Err(TTError::Decompose(DecomposeError::EmptyMatrix)): a step's rank was 0 with another SVD to come */
+
+/* tt_decompose (tensor_compress/src/tensor_train.rs:315-397) of n vectors of `dim` floats under one config, bit for bit: the TT-SVD
+ * sweep over left_unfold_for_tt (decompose.rs:559-570), svd_truncated (398-466: power iteration with deflation, 470-550 and
+ * 344-387, or the randomized range finder with gaussian_matrix 271-294 and qr_orthonormalize 298-340), matmul (197-216), dot, norm
+ * and normalize (220-239), frobenius_norm (76-78) — every product and sum in the reference's order and rounding.  The three
+ * argument errors of tt_decompose refuse the whole call with NMN_ERR_INVALID_ARGUMENT and the reference's Display text: dim == 0
+ * ("empty vector"), a shape whose product is not dim ("dimension D cannot be reshaped to [..] (product: P)") and max_rank < 1
+ * ("invalid TT-rank: must be >= 1"); so does an n_cores outside 1..8 (this library's).  The tolerance is not checked, as
+ * tt_decompose does not check it.  EmptyMatrix is a status of one vector, not a failure of the call.
+ * status_out[n]; ranks_out[n][n_cores + 1] (all 0 where the status is not NMN_TT_OK; a two-core train may carry ranks {1, 0, 1});
+ * cores_out (nullable: status and ranks only) receives the trains of the Ok vectors back to back, core_off_out[n + 1] indexing them
+ * as nmn_tt_reconstruct, nmn_tt_norm and nmn_hnsw_search_tt take them (a failed vector has an empty range).  cores_cap is in floats:
+ * n * nmn_tt_max_storage always suffices, less is NMN_ERR_INVALID_ARGUMENT only if the trains do not fit (nothing is written then).
+ * HOST buffers, synchronous, stateless, on the current device: one launch, a wave per vector with the vector's whole state in LDS.
+ * The host restatement of the same loops (same bits) takes a call whose config is above the device's limits
+ * (nmn_tt_decompose_lds_floats), a call of fewer than NMN_TT_DECOMPOSE_MIN vectors (environment, read at every call; default 320,
+ * the measured crossover against the host's 16 threads) and every call under NMN_HNSW_HOST_SEARCH=1.  The choice never depends on the vectors.
+ * NaN and infinite inputs are not refused and are outside the bit-level promise. */
+nmn_status nmn_tt_decompose(const float* vectors, uint64_t n, uint64_t dim, const uint32_t* shape, uint32_t n_cores, uint32_t max_rank,
+                            float tolerance, uint32_t* status_out, uint32_t* ranks_out, uint64_t* core_off_out, float* cores_out,
+                            uint64_t cores_cap);
+/* The same with the vectors and every output in DEVICE memory, enqueued on `stream` and not waited for, nothing read back.  The
+ * trains stay in their slots: train q starts at q * nmn_tt_max_storage (cores_cap >= n * that), core_off_dev[n + 1] (nullable)
+ * receives q * nmn_tt_max_storage, ranks_dev carries each train's own ranks — what tt_prepare's per-query ranks read.  cores_dev
+ * nullable: status and ranks only.  There is no host to fall back to: a config above the limits is NMN_ERR_INVALID_ARGUMENT.  The
+ * first call of a config on a device uploads its Gaussian matrices (made on the host, kept for the life of the process). */
+nmn_status nmn_tt_decompose_device(const float* vectors_dev, uint64_t n, uint64_t dim, const uint32_t* shape, uint32_t n_cores,
+                                   uint32_t max_rank, float tolerance, uint32_t* status_dev, uint32_t* ranks_dev,
+                                   uint64_t* core_off_dev, float* cores_dev, uint64_t cores_cap, void* stream);
+/* What the device path serves: at most max_cores modes, no worst-case rank above max_rank, and a config whose LDS need
+ * (nmn_tt_decompose_lds_floats: the unfolding, U, V, the u and v columns and, where a step can take the randomized path, the
+ * Gaussian matrix, Q and B — sized from the worst-case ranks, never from a vector) is at most max_lds_floats; max_dim is the largest
+ * dimension any shape can bring under that.  Each pointer nullable. */
+nmn_status nmn_tt_decompose_limits(uint32_t* max_cores, uint32_t* max_rank, uint32_t* max_dim, uint32_t* max_lds_floats);
+/* The LDS floats a config needs on the device; UINT64_MAX for a config above the limits, 0 for one the entries refuse */
+uint64_t nmn_tt_decompose_lds_floats(const uint32_t* shape, uint32_t n_cores, uint32_t max_rank);
+
+/* HNSWIndex::search_tt (hnsw.rs:1796-1801) per query: tt_decompose(query, config); Ok: search_tt_with_ef(tt, k, ef_search) — what
+ * nmn_hnsw_search_tt returns for the train nmn_tt_decompose makes, Cosine whatever the handle's metric; Err of any kind:
+ * search(query, k) — what nmn_hnsw_search returns, under the handle's metric.  The three argument errors of tt_decompose therefore
+ * make the whole call a plain dense search.  queries[nq][dim], dim == nmn_hnsw_dim(h) (NMN_ERR_DIMENSION_MISMATCH).  Divergence: a
+ * two-core train whose middle rank is 0 is Ok in the reference (its tt_norm is 0, so every distance is 1.0); here it is
+ * refused as nmn_hnsw_search_tt refuses it, NMN_ERR_INVALID_ARGUMENT "TT: query Q: every rank must be >= 1", before anything is
+ * written.  HOST buffers, synchronous; the decomposition is nmn_tt_decompose's (its routing), the two searches are those entries'
+ * (their handles, storages and host routing), each with its own wait; stats are the sums of the two.  There is no device-buffer
+ * form: the fallback rule cannot be honoured without reading the status back (docs/hnsw.md §21). */
+nmn_status nmn_hnsw_search_tt_dense(nmn_hnsw* h, const float* queries, uint32_t nq, uint64_t dim, const uint32_t* shape,
+                                    uint32_t n_cores, uint32_t max_rank, float tolerance, uint32_t k, uint64_t* out_ids,
+                                    float* out_scores, uint32_t* out_counts, nmn_search_stats* stats);
+/* HNSWIndex::insert_tt (hnsw.rs:1740-1749) and insert_batch_tt (1769-1790): every vector is decomposed (status only); if any
+ * decomposition is an Err nothing is inserted and the call is NMN_ERR_INVALID_ARGUMENT with the reference's text,
+ * "TT decomposition failed: {e:?}" or "Batch TT decomposition failed: {e:?}" with the Debug form of the TTError (EmptyVector,
+ * ShapeMismatch { dim: .., shape: [..], product: .. }, InvalidRank, Decompose(EmptyMatrix)); the batch's text is followed by
+ * " (vector I)", I the lowest failing index — the reference's sequential branch reports exactly that one, its rayon branch any.
+ * Otherwise the vectors take nmn_hnsw_insert's path as Dense nodes: max_nodes, its text and the all-or-nothing batch are that
+ * entry's.  Dense handles only: a quantized or binary handle is NMN_ERR_CONFIGURATION.  An empty batch returns NMN_OK and no ids. */
+nmn_status nmn_hnsw_insert_tt_dense(nmn_hnsw* h, const float* vector, uint64_t dim, const uint32_t* shape, uint32_t n_cores,
+                                    uint32_t max_rank, float tolerance, uint64_t* id_out);
+nmn_status nmn_hnsw_insert_batch_tt(nmn_hnsw* h, const float* vectors, uint64_t n, uint64_t dim, const uint32_t* shape,
+                                    uint32_t n_cores, uint32_t max_rank, float tolerance, uint64_t* ids_out);
+
 /* ---- extended distance metrics: the re-rank of search_with_hnsw_and_metric ------------------------------------ */
 
 /* `tensor_store::DistanceMetric` (tensor_store/src/distance.rs:13-52), the ExtendedDistanceMetric of vector_engine.  Both

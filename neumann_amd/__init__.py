@@ -12,6 +12,6 @@ from .sharded import GpuShardedIndex  # noqa: F401,E402
 from .hnsw import GpuHnsw, HNSWBuildOptions, HNSWConfig  # noqa: F401,E402
 from .xmetric import ExtendedDistanceMetric, GeometricConfig  # noqa: F401,E402
 from .cache_index import CacheIndex  # noqa: F401,E402
-from .tt import TTVector, tt_norm, tt_reconstruct  # noqa: F401,E402
+from .tt import TTConfig, TTVector, tt_decompose, tt_norm, tt_reconstruct  # noqa: F401,E402
 
 __version__ = "0.3.0"

@@ -260,6 +260,17 @@ SIGNATURES = {
                                        C.POINTER(SearchStats)]),
     "nmn_hnsw_search_tt_device": (C.c_int32, [vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp]),
     "nmn_hnsw_insert_tt": (C.c_int32, [vp, vp, C.c_uint32, vp, vp, vp, C.c_uint64, vp]),
+    "nmn_tt_config_for_dim": (C.c_int32, [C.c_uint64, C.c_uint32, u32p, u32p, u32p, C.POINTER(C.c_float)]),
+    "nmn_tt_max_storage": (C.c_uint64, [vp, C.c_uint32, C.c_uint32]),
+    "nmn_tt_decompose": (C.c_int32, [vp, C.c_uint64, C.c_uint64, vp, C.c_uint32, C.c_uint32, C.c_float, vp, vp, vp, vp, C.c_uint64]),
+    "nmn_tt_decompose_device": (C.c_int32, [vp, C.c_uint64, C.c_uint64, vp, C.c_uint32, C.c_uint32, C.c_float, vp, vp, vp, vp,
+                                            C.c_uint64, vp]),
+    "nmn_tt_decompose_limits": (C.c_int32, [u32p, u32p, u32p, u32p]),
+    "nmn_tt_decompose_lds_floats": (C.c_uint64, [vp, C.c_uint32, C.c_uint32]),
+    "nmn_hnsw_search_tt_dense": (C.c_int32, [vp, vp, C.c_uint32, C.c_uint64, vp, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, vp,
+                                             vp, vp, C.POINTER(SearchStats)]),
+    "nmn_hnsw_insert_tt_dense": (C.c_int32, [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint32, C.c_float, vp]),
+    "nmn_hnsw_insert_batch_tt": (C.c_int32, [vp, vp, C.c_uint64, C.c_uint64, vp, C.c_uint32, C.c_uint32, C.c_float, vp]),
     "nmn_xmetric_geometric_default": (None, [C.POINTER(XMetric)]),
     "nmn_xmetric_geometric_angular_heavy": (None, [C.POINTER(XMetric)]),
     "nmn_xmetric_geometric_structural_heavy": (None, [C.POINTER(XMetric)]),

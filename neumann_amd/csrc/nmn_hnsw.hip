@@ -1842,3 +1842,149 @@ extern "C" nmn_status nmn_hnsw_insert_tt(nmn_hnsw* h, const uint32_t* shape, uin
     if (st != NMN_OK) return st;
     return insert_rows(h, rows.data(), n, nullptr, nullptr, ids_out);
 }
+
+namespace {
+
+nmn_status dense_dim_check(const nmn_hnsw* h, uint64_t dim) {
+    if (dim == h->dim) return NMN_OK;
+    char buf[160];
+    snprintf(buf, sizeof buf, "HNSW: the vectors have %llu dimensions, the index holds vectors of dimension %u", (unsigned long long)dim,
+             h->dim);
+    return set_error(NMN_ERR_DIMENSION_MISMATCH, buf);
+}
+
+}  // namespace
+
+extern "C" nmn_status nmn_hnsw_search_tt_dense(nmn_hnsw* h, const float* queries, uint32_t nq, uint64_t dim, const uint32_t* shape,
+                                               uint32_t n_cores, uint32_t max_rank, float tolerance, uint32_t k, uint64_t* out_ids,
+                                               float* out_scores, uint32_t* out_counts, nmn_search_stats* stats) {
+    if (!h) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (const nmn_status sb = refuse_binary(h, "nmn_hnsw_search_tt_dense", kBinQueries); sb != NMN_OK) return sb;
+    if (k == 0) return set_error(NMN_ERR_INVALID_TOP_K, "k == 0");
+    clear_stats(stats);
+    if (nq == 0) return NMN_OK;
+    if (!queries || !out_ids || !out_scores || !out_counts) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    nmn_status st = dense_dim_check(h, dim);
+    if (st != NMN_OK) return st;
+    TTDecConfig c;
+    if (tt_dec_config(dim, shape, n_cores, max_rank, tolerance, &c, nullptr, 0) != NMN_OK)  // Err for every query: search(query, k)
+        return nmn_hnsw_search(h, queries, nq, k, 0, out_ids, out_scores, out_counts, stats);
+    HN_TRY(hipSetDevice(h->device));
+    std::vector<uint32_t> status(nq), ranks((size_t)nq * (n_cores + 1));
+    std::vector<uint64_t> off(nq + 1);
+    std::vector<float> cores((size_t)nq * c.slot);
+    st = nmn_tt_decompose(queries, nq, dim, shape, n_cores, max_rank, tolerance, status.data(), ranks.data(), off.data(), cores.data(),
+                          cores.size());
+    if (st != NMN_OK) return st;
+    std::vector<uint32_t> tt_q, dense_q;
+    for (uint32_t q = 0; q < nq; q++) {
+        if (status[q] != kTTStatusOk) {
+            dense_q.push_back(q);
+            continue;
+        }
+        for (uint32_t i = 1; i < n_cores; i++)
+            if (ranks[(size_t)q * (n_cores + 1) + i] < 1) {
+                char buf[120];
+                snprintf(buf, sizeof buf, "TT: query %u: every rank must be >= 1", q);
+                return set_error(NMN_ERR_INVALID_ARGUMENT, buf);
+            }
+        tt_q.push_back(q);
+    }
+    nmn_search_stats part{}, sum{};
+    auto add = [&](bool first) {
+        sum.rows_scanned += part.rows_scanned;
+        sum.bytes_scanned += part.bytes_scanned;
+        sum.fallback_queries += part.fallback_queries;
+        sum.sweep_launches += part.sweep_launches;
+        if (first || sum.sweep_kind == NMN_SWEEP_NONE) sum.sweep_kind = part.sweep_kind;
+    };
+    const size_t m1 = tt_q.size(), m2 = dense_q.size();
+    std::vector<uint64_t> ids(std::max(m1, m2) * k);
+    std::vector<float> sc(std::max(m1, m2) * k);
+    std::vector<uint32_t> cnt(std::max(m1, m2));
+    auto scatter = [&](const std::vector<uint32_t>& which) {
+        for (size_t j = 0; j < which.size(); j++) {
+            memcpy(out_ids + (size_t)which[j] * k, ids.data() + j * k, (size_t)k * 8);
+            memcpy(out_scores + (size_t)which[j] * k, sc.data() + j * k, (size_t)k * 4);
+            out_counts[which[j]] = cnt[j];
+        }
+    };
+    if (m1) {  // the Ok queries: search_tt_with_ef of their trains, the ranks and core ranges of those queries gathered
+        std::vector<uint32_t> r1(m1 * (n_cores + 1));
+        std::vector<uint64_t> o1(m1 + 1, 0);
+        std::vector<float> c1;
+        for (size_t j = 0; j < m1; j++) {
+            const uint32_t q = tt_q[j];
+            memcpy(r1.data() + j * (n_cores + 1), ranks.data() + (size_t)q * (n_cores + 1), (n_cores + 1) * 4);
+            c1.insert(c1.end(), cores.begin() + off[q], cores.begin() + off[q + 1]);
+            o1[j + 1] = c1.size();
+        }
+        st = nmn_hnsw_search_tt(h, shape, n_cores, r1.data(), o1.data(), c1.data(), (uint32_t)m1, k, 0, ids.data(), sc.data(), cnt.data(),
+                                &part);
+        if (st != NMN_OK) return st;
+        add(true);
+        scatter(tt_q);
+    }
+    if (m2) {  // the Err queries: search(query, k) under the handle's metric
+        std::vector<float> rows(m2 * dim);
+        for (size_t j = 0; j < m2; j++) memcpy(rows.data() + j * dim, queries + (size_t)dense_q[j] * dim, dim * 4);
+        st = nmn_hnsw_search(h, rows.data(), (uint32_t)m2, k, 0, ids.data(), sc.data(), cnt.data(), &part);
+        if (st != NMN_OK) return st;
+        add(m1 == 0);
+        scatter(dense_q);
+    }
+    if (stats) *stats = sum;
+    return NMN_OK;
+}
+
+namespace {
+
+// insert_tt / insert_batch_tt: every vector decomposed for its status, then nmn_hnsw_insert's path
+nmn_status insert_dense_validated(nmn_hnsw* h, const char* entry, const char* prefix, bool batch, const float* vectors, uint64_t n,
+                                  uint64_t dim, const uint32_t* shape, uint32_t n_cores, uint32_t max_rank, float tolerance,
+                                  uint64_t* ids_out) {
+    if (!h) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (const nmn_status sb = refuse_binary(h, entry, kBinNodes); sb != NMN_OK) return sb;
+    if (h->storage != NMN_HNSW_STORAGE_DENSE)
+        return set_error(NMN_ERR_CONFIGURATION,
+                         "HNSW: insert_tt makes Dense nodes, which are served on a dense handle only (nmn_hnsw_insert quantizes a row)");
+    if (n == 0) return NMN_OK;
+    if (!vectors) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (n >= (uint64_t)kNone) return set_error(NMN_ERR_CAPACITY, "HNSW: node ids are 32 bits on the device");
+    char text[600], debug[400];
+    auto failed = [&](uint64_t q) {
+        if (batch)
+            snprintf(text, sizeof text, "%s: %s (vector %llu)", prefix, debug, (unsigned long long)q);
+        else
+            snprintf(text, sizeof text, "%s: %s", prefix, debug);
+        return set_error(NMN_ERR_INVALID_ARGUMENT, text);
+    };
+    TTDecConfig c;
+    if (tt_dec_config(dim, shape, n_cores, max_rank, tolerance, &c, debug, sizeof debug) != NMN_OK) return failed(0);
+    nmn_status st = dense_dim_check(h, dim);
+    if (st != NMN_OK) return st;
+    HN_TRY(hipSetDevice(h->device));
+    std::vector<uint32_t> status(n), ranks((size_t)n * (n_cores + 1));
+    st = nmn_tt_decompose(vectors, n, dim, shape, n_cores, max_rank, tolerance, status.data(), ranks.data(), nullptr, nullptr, 0);
+    if (st != NMN_OK) return st;
+    for (uint64_t q = 0; q < n; q++)
+        if (status[q] != kTTStatusOk) {
+            snprintf(debug, sizeof debug, "Decompose(EmptyMatrix)");
+            return failed(q);
+        }
+    return insert_rows(h, vectors, n, nullptr, nullptr, ids_out);
+}
+
+}  // namespace
+
+extern "C" nmn_status nmn_hnsw_insert_tt_dense(nmn_hnsw* h, const float* vector, uint64_t dim, const uint32_t* shape, uint32_t n_cores,
+                                               uint32_t max_rank, float tolerance, uint64_t* id_out) {
+    return insert_dense_validated(h, "nmn_hnsw_insert_tt_dense", "TT decomposition failed", false, vector, 1, dim, shape, n_cores, max_rank,
+                                  tolerance, id_out);
+}
+
+extern "C" nmn_status nmn_hnsw_insert_batch_tt(nmn_hnsw* h, const float* vectors, uint64_t n, uint64_t dim, const uint32_t* shape,
+                                               uint32_t n_cores, uint32_t max_rank, float tolerance, uint64_t* ids_out) {
+    return insert_dense_validated(h, "nmn_hnsw_insert_batch_tt", "Batch TT decomposition failed", true, vectors, n, dim, shape, n_cores,
+                                  max_rank, tolerance, ids_out);
+}

@@ -57,4 +57,48 @@ inline float tt_walk_magnitude(float norm) { return norm < 1e-10f ? 0.0f : norm;
 hipError_t launch_tt_prepare(const TTBatch& b, const float* cores_dev, const uint32_t* ranks_dev, const uint64_t* core_off_dev,
                              const uint8_t* skip_dev, float* rows_dev, float* norms_dev, float* mags_dev, hipStream_t s);
 
+// ---- tt_decompose (tensor_train.rs:315-397), docs/hnsw.md §21 ----------------------------------------------------------------
+
+// The device path of tt_decompose keeps one vector's whole state in the dynamic LDS of its workgroup; a config is served there when
+// tt_decompose_lds_floats(config) <= kTTDecMaxLdsFloats (64 KiB, the most a workgroup may ask for without an attribute, two such
+// workgroups on the 160 KiB of a CU) and no worst-case rank is above kTTDecMaxRank.
+constexpr uint32_t kTTDecMaxLdsFloats = 16384;
+constexpr uint32_t kTTDecMaxRank = 64;
+constexpr uint32_t kTTDecGridMax = 4096;     // workgroups of one launch (NMN_TT_DECOMPOSE_GRID), the vectors beyond in a stride loop
+constexpr uint32_t kTTDecThreads = 64;       // one wave owns a vector (NMN_TT_DECOMPOSE_THREADS: 64, 128 or 256), docs/hnsw.md §21
+constexpr uint32_t kTTDecMinDefault = 320;   // NMN_TT_DECOMPOSE_MIN: calls of fewer vectors are decomposed by the host (measured, §21)
+constexpr uint32_t kTTStatusOk = 0, kTTStatusEmptyMatrix = 1;
+
+// One call's config, checked (tt_decompose's own three checks are the entries'): the worst-case ranks
+// rb[k + 1] = min(max_rank, rb[k] * shape[k], shape[k + 1] * .. * shape[n_cores - 1]) and the slot of one train.
+struct TTDecConfig {
+    uint32_t n_cores = 0, max_rank = 0;
+    float tolerance = 0.0f;
+    uint64_t dim = 0;
+    uint32_t shape[kTTMaxCores] = {};
+    uint32_t rb[kTTMaxCores + 1] = {};
+    uint64_t slot = 0;        // sum of rb[k] * shape[k] * rb[k + 1]: nmn_tt_max_storage
+    uint64_t lds_floats = 0;  // what tt_decompose_kernel needs for this config
+    bool on_device() const;   // within the limits above
+};
+// NMN_ERR_INVALID_ARGUMENT with the reference's Display text for tt_decompose's three argument errors (dim == 0: "empty vector"; the
+// product of the shape != dim: "dimension .. cannot be reshaped to .."; max_rank < 1: "invalid TT-rank: must be >= 1"), and for an
+// n_cores outside 1..8.  `debug` (nullable) receives the Debug form of the TTError.
+nmn_status tt_dec_config(uint64_t dim, const uint32_t* shape, uint32_t n_cores, uint32_t max_rank, float tolerance, TTDecConfig* c,
+                         char* debug, size_t debug_cap);
+
+// tt_decompose of one vector on the host, the reference's loops restated: ranks_out [n_cores + 1] (zeros when the status is
+// EmptyMatrix), cores_out nullable (status only), the cores back to back.  Returns kTTStatusOk or kTTStatusEmptyMatrix.
+uint32_t tt_decompose_host(const TTDecConfig& c, const float* vector, uint32_t* ranks_out, float* cores_out);
+// n vectors: the host restatement on up to `threads` threads (the vectors are independent); slots at q * c.slot
+void tt_decompose_host_batch(const TTDecConfig& c, const float* vectors, uint64_t n, uint32_t* status, uint32_t* ranks, float* cores,
+                             unsigned threads);
+// true: this call of n vectors goes to the host (NMN_HNSW_HOST_SEARCH=1, a config above the limits, n < NMN_TT_DECOMPOSE_MIN)
+bool tt_decompose_on_host(const TTDecConfig& c, uint64_t n);
+// One launch on `s` over n vectors in DEVICE memory: status_dev [n], ranks_dev [n][n_cores + 1], cores_dev nullable (status only),
+// train q at q * c.slot.  The config must be on_device().  The Gaussian matrices of the randomized path are made on the host once
+// per config and device and kept.  core_off_dev nullable: [n + 1], q * c.slot.
+nmn_status launch_tt_decompose(const TTDecConfig& c, const float* vectors_dev, uint64_t n, uint32_t* status_dev, uint32_t* ranks_dev,
+                               float* cores_dev, uint64_t* core_off_dev, hipStream_t s);
+
 }  // namespace nmn

@@ -16,6 +16,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
+#include <thread>
 #include <vector>
 
 #include "nmn_internal.h"
@@ -322,7 +324,866 @@ nmn_status tt_public(const uint32_t* shape, uint32_t n_cores, const uint32_t* ra
 }
 
 }  // namespace
+
+// ---- tt_decompose (tensor_train.rs:315-397) -------------------------------------------------------------------------------------
+//
+// Reference order restated below, host and device (decompose.rs; docs/hnsw.md §21):
+//   dot, frobenius_norm and the u = A v / v = A^T u sums of power_iteration are Iterator::sum::<f32>(): a left-to-right fold from
+//       -0.0.  matmul's `let mut sum = 0.0` starts at +0.0.  Every product and every add is rounded on its own.
+//   normalize: n = sqrt(dot(v, v)); x /= n (a true division) only when n > 1e-10f.
+//   power_iteration: v_i = ((i * 7 + 3) % 13) as f32 / 13.0 - 0.5, normalised; at most 20 rounds of u = A v, normalize (its norm is
+//       new_sigma), v = A^T u, normalize; |new_sigma - sigma| < 1e-6f * max(sigma, 1.0) returns new_sigma, the 20th round sigma.
+//   svd_power_iteration: abs_tol = tolerance * frobenius_norm(A); per rank: sigma < abs_tol breaks (0 < 0 does not), otherwise
+//       a[i][j] -= (sigma * u[i]) * v[j].
+//   svd_truncated: rows > 32 && cols > 32 && 2 rank < min(rows, cols) takes the randomized path: Omega = gaussian_matrix(cols,
+//       rank + min(5, min(rows, cols) - rank), rows * 31 + cols), Y = A Omega, Q = modified Gram-Schmidt of Y's columns (a column
+//       whose norm is not above 1e-10f is dropped), B = Q^T A, the power-iteration SVD of B, U = Q U_B.
+//   tt_decompose: core k = U (left n_k rows, new_rank columns), the next unfolding s[r] * vt[r][j]; the last core is what is left.
+// NaN and infinite inputs are not refused and are outside the bit-level promise (max, the comparisons and libm differ there).
+
+bool TTDecConfig::on_device() const {
+    if (lds_floats > kTTDecMaxLdsFloats || dim > (1u << 20)) return false;
+    for (uint32_t k = 0; k <= n_cores; k++)
+        if (rb[k] > kTTDecMaxRank) return false;
+    return true;
+}
+
+namespace {
+
+struct RandomizedStep {
+    bool taken;
+    uint32_t rank, target;
+};
+// svd_truncated's choice (decompose.rs:407-418) for an unfolding of rows x cols
+RandomizedStep randomized_step(uint64_t rows, uint64_t cols, uint64_t max_rank) {
+    const uint64_t mn = std::min(rows, cols), rank = std::min(max_rank, mn);
+    RandomizedStep r{rows > 32 && cols > 32 && rank * 2 < mn, (uint32_t)rank, 0};
+    if (r.taken) r.target = (uint32_t)(rank + std::min<uint64_t>(5, mn - rank));
+    return r;
+}
+
+struct TTDecLayout {  // offsets in floats into the dynamic LDS of tt_decompose_kernel
+    uint32_t oA, oU, oV, oS, oUr, oUn, oVr, oVn, oB, oQ, oOm, total;
+};
+
+TTDecLayout dec_layout(const TTDecConfig& c) {
+    uint64_t mA = 1, mU = 1, mV = 1, mRows = 1, mCols = 1, mRank = 1, mB = 0, mQ = 0, mOm = 0;
+    uint64_t rem = c.dim;
+    for (uint32_t k = 0; k + 1 < c.n_cores; k++) {
+        rem /= c.shape[k];
+        const uint64_t rows = (uint64_t)c.rb[k] * c.shape[k], cols = rem, ld = cols | 1;
+        mA = std::max(mA, rows * ld);
+        mU = std::max(mU, rows * c.rb[k + 1]);
+        mV = std::max(mV, c.rb[k + 1] * cols);
+        mRows = std::max(mRows, rows);
+        mCols = std::max(mCols, cols);
+        mRank = std::max<uint64_t>(mRank, c.rb[k + 1]);
+        for (uint64_t l = 1; l <= c.rb[k]; l++) {
+            const RandomizedStep r = randomized_step(l * c.shape[k], cols, c.max_rank);
+            if (!r.taken) continue;
+            mB = std::max(mB, r.target * ld);
+            mQ = std::max(mQ, l * c.shape[k] * r.target);
+            mOm = std::max(mOm, cols * r.target);
+        }
+    }
+    const uint64_t sizes[11] = {mA, mU, mV, mRank, mRows, mRows, mCols, mCols, mB, mQ, mOm};
+    uint32_t off[12];
+    uint64_t at = 0;
+    for (int i = 0; i < 11; i++) {
+        off[i] = (uint32_t)std::min<uint64_t>(at, 1u << 30);
+        at += sizes[i];
+    }
+    off[11] = (uint32_t)std::min<uint64_t>(at, 1u << 30);
+    return {off[0], off[1], off[2], off[3], off[4], off[5], off[6], off[7], off[8], off[9], off[10], off[11]};
+}
+
+}  // namespace
+
+nmn_status tt_dec_config(uint64_t dim, const uint32_t* shape, uint32_t n_cores, uint32_t max_rank, float tolerance, TTDecConfig* c,
+                         char* debug, size_t debug_cap) {
+    auto dbg = [&](const char* t) {
+        if (debug && debug_cap) snprintf(debug, debug_cap, "%s", t);
+    };
+    if (dim == 0) {
+        dbg("EmptyVector");
+        return set_error(NMN_ERR_INVALID_ARGUMENT, "empty vector");
+    }
+    if (n_cores < 1 || n_cores > kTTMaxCores || !shape) {
+        dbg("InvalidShape");
+        return set_error(NMN_ERR_INVALID_ARGUMENT, "TT: n_cores must be 1..8");
+    }
+    unsigned __int128 product = 1;
+    for (uint32_t k = 0; k < n_cores; k++) product = std::min<unsigned __int128>(product * shape[k], (unsigned __int128)1 << 100);
+    if (product != dim) {
+        char list[160], text[400];
+        size_t at = 0;
+        for (uint32_t k = 0; k < n_cores; k++)
+            at += (size_t)snprintf(list + at, sizeof list - at, k ? ", %u" : "%u", shape[k]);
+        const unsigned long long pr = product > ~0ull ? ~0ull : (unsigned long long)product;
+        snprintf(text, sizeof text, "ShapeMismatch { dim: %llu, shape: [%s], product: %llu }", (unsigned long long)dim, list, pr);
+        dbg(text);
+        snprintf(text, sizeof text, "dimension %llu cannot be reshaped to [%s] (product: %llu)", (unsigned long long)dim, list, pr);
+        return set_error(NMN_ERR_INVALID_ARGUMENT, text);
+    }
+    if (max_rank < 1) {
+        dbg("InvalidRank");
+        return set_error(NMN_ERR_INVALID_ARGUMENT, "invalid TT-rank: must be >= 1");
+    }
+    if (dim > (1ull << 31)) {
+        dbg("InvalidShape");
+        return set_error(NMN_ERR_INVALID_ARGUMENT, "TT: the product of the shape is above 2^31");
+    }
+    c->n_cores = n_cores;
+    c->max_rank = max_rank;
+    c->tolerance = tolerance;
+    c->dim = dim;
+    memcpy(c->shape, shape, n_cores * sizeof(uint32_t));
+    c->rb[0] = 1;
+    uint64_t rem = dim;
+    for (uint32_t k = 0; k + 1 < n_cores; k++) {
+        rem /= shape[k];
+        c->rb[k + 1] = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(max_rank, (uint64_t)c->rb[k] * shape[k]), rem);
+    }
+    c->rb[n_cores] = 1;
+    c->slot = 0;
+    for (uint32_t k = 0; k < n_cores; k++) c->slot += (uint64_t)c->rb[k] * shape[k] * c->rb[k + 1];
+    c->lds_floats = dec_layout(*c).total;
+    return NMN_OK;
+}
+
+namespace {
+
+// ---- the host restatement ----
+
+float normalize_host(float* v, size_t n) {
+    float s = -0.0f;
+    for (size_t i = 0; i < n; i++) {
+        const float p = v[i] * v[i];
+        s = s + p;
+    }
+    const float nr = sqrtf(s);
+    if (nr > 1e-10f)
+        for (size_t i = 0; i < n; i++) v[i] = v[i] / nr;
+    return nr;
+}
+
+float power_iteration_host(const float* a, size_t rows, size_t cols, float* u, float* v) {
+    for (size_t j = 0; j < cols; j++) v[j] = (float)((j * 7 + 3) % 13) / 13.0f - 0.5f;
+    normalize_host(v, cols);
+    float sigma = 0.0f;
+    for (int it = 0; it < 20; it++) {
+        for (size_t i = 0; i < rows; i++) {
+            float s = -0.0f;
+            for (size_t j = 0; j < cols; j++) {
+                const float p = a[i * cols + j] * v[j];
+                s = s + p;
+            }
+            u[i] = s;
+        }
+        const float new_sigma = normalize_host(u, rows);
+        for (size_t j = 0; j < cols; j++) {
+            float s = -0.0f;
+            for (size_t i = 0; i < rows; i++) {
+                const float p = a[i * cols + j] * u[i];
+                s = s + p;
+            }
+            v[j] = s;
+        }
+        normalize_host(v, cols);
+        const float bound = 1e-6f * (sigma > 1.0f ? sigma : 1.0f);
+        if (fabsf(new_sigma - sigma) < bound) return new_sigma;
+        sigma = new_sigma;
+    }
+    return sigma;
+}
+
+// svd_power_iteration of m (rows x cols, deflated in place): U [rows][rank] row-major, S, Vt [rank][cols]; returns the rank
+size_t svd_power_host(float* m, size_t rows, size_t cols, size_t max_rank, float tolerance, std::vector<float>& U, std::vector<float>& S,
+                      std::vector<float>& Vt) {
+    const size_t rank = std::min(max_rank, std::min(rows, cols));
+    float fs = -0.0f;
+    for (size_t i = 0; i < rows * cols; i++) {
+        const float p = m[i] * m[i];
+        fs = fs + p;
+    }
+    const float abs_tol = tolerance * sqrtf(fs);
+    std::vector<float> u(rows), v(cols), ucols;
+    S.clear();
+    Vt.clear();
+    for (size_t c = 0; c < rank; c++) {
+        const float sigma = power_iteration_host(m, rows, cols, u.data(), v.data());
+        if (sigma < abs_tol) break;
+        S.push_back(sigma);
+        ucols.insert(ucols.end(), u.begin(), u.end());
+        Vt.insert(Vt.end(), v.begin(), v.end());
+        for (size_t i = 0; i < rows; i++) {
+            const float su = sigma * u[i];
+            for (size_t j = 0; j < cols; j++) {
+                const float p = su * v[j];
+                m[i * cols + j] = m[i * cols + j] - p;
+            }
+        }
+    }
+    const size_t got = S.size();
+    U.assign(rows * got, 0.0f);
+    for (size_t c = 0; c < got; c++)
+        for (size_t i = 0; i < rows; i++) U[i * got + c] = ucols[c * rows + i];
+    return got;
+}
+
+// gaussian_matrix (decompose.rs:271-294) with the platform's logf, cosf and sinf, which is what Rust's std calls
+std::vector<float> gaussian_matrix_host(size_t rows, size_t cols, uint64_t seed) {
+    uint64_t state = seed + 1;
+    auto next = [&]() {
+        state = state * 6364136223846793005ull + 1442695040888963407ull;
+        return (float)(state >> 40) / 16777216.0f;
+    };
+    const size_t total = rows * cols;
+    std::vector<float> data;
+    data.reserve(total + 1);
+    const float two_pi = 2.0f * 3.14159274101257324f;
+    while (data.size() < total) {
+        const float d1 = next();
+        const float u1 = d1 > 1e-10f ? d1 : 1e-10f;
+        const float u2 = next();
+        const float r = sqrtf(-2.0f * ::logf(u1));
+        const float theta = two_pi * u2;
+        data.push_back(r * ::cosf(theta));
+        if (data.size() < total) data.push_back(r * ::sinf(theta));
+    }
+    return data;
+}
+
+// c[i][j] = ((+0.0 + a[i][0] b[0][j]) + a[i][1] b[1][j]) + ..  (matmul, decompose.rs:197-216)
+void matmul_host(const float* a, const float* b, size_t n, size_t inner, size_t m, float* c) {
+    for (size_t i = 0; i < n; i++)
+        for (size_t j = 0; j < m; j++) {
+            float s = 0.0f;
+            for (size_t k = 0; k < inner; k++) {
+                const float p = a[i * inner + k] * b[k * m + j];
+                s = s + p;
+            }
+            c[i * m + j] = s;
+        }
+}
+
+size_t svd_truncated_host(std::vector<float>& m, size_t rows, size_t cols, size_t max_rank, float tolerance, std::vector<float>& U,
+                          std::vector<float>& S, std::vector<float>& Vt) {
+    const RandomizedStep rs = randomized_step(rows, cols, max_rank);
+    if (!rs.taken) return svd_power_host(m.data(), rows, cols, max_rank, tolerance, U, S, Vt);
+    const size_t t = rs.target;
+    const std::vector<float> omega = gaussian_matrix_host(cols, t, (uint64_t)rows * 31 + cols);
+    std::vector<float> y(rows * t);
+    matmul_host(m.data(), omega.data(), rows, cols, t, y.data());
+    std::vector<std::vector<float>> q;  // qr_orthonormalize: modified Gram-Schmidt over the columns
+    std::vector<float> col(rows);
+    for (size_t j = 0; j < t; j++) {
+        for (size_t i = 0; i < rows; i++) col[i] = y[i * t + j];
+        for (const std::vector<float>& qc : q) {
+            float proj = -0.0f;
+            for (size_t i = 0; i < rows; i++) {
+                const float p = col[i] * qc[i];
+                proj = proj + p;
+            }
+            for (size_t i = 0; i < rows; i++) {
+                const float p = proj * qc[i];
+                col[i] = col[i] - p;
+            }
+        }
+        if (normalize_host(col.data(), rows) > 1e-10f) q.push_back(col);
+    }
+    S.clear();
+    U.clear();
+    Vt.clear();
+    const size_t r = q.size();
+    if (r == 0) return 0;
+    std::vector<float> basis(rows * r), basis_t(r * rows), projected(r * cols), us;
+    for (size_t c = 0; c < r; c++)
+        for (size_t i = 0; i < rows; i++) basis[i * r + c] = basis_t[c * rows + i] = q[c][i];
+    matmul_host(basis_t.data(), m.data(), r, rows, cols, projected.data());
+    const size_t got = svd_power_host(projected.data(), r, cols, rs.rank, tolerance, us, S, Vt);
+    if (got == 0) return 0;
+    U.assign(rows * got, 0.0f);
+    matmul_host(basis.data(), us.data(), rows, r, got, U.data());
+    return got;
+}
+
+}  // namespace
+
+uint32_t tt_decompose_host(const TTDecConfig& c, const float* vector, uint32_t* ranks_out, float* cores_out) {
+    const uint32_t n = c.n_cores;
+    std::vector<float> cur(vector, vector + c.dim), U, S, Vt;
+    size_t left = 1, rem = c.dim, coff = 0;
+    ranks_out[0] = 1;
+    for (uint32_t k = 0; k + 1 < n; k++) {
+        const size_t mode = c.shape[k], rows = left * mode;
+        rem /= mode;
+        if (cur.empty()) {  // a rank of 0 with another SVD to come: svd_truncated's EmptyMatrix
+            for (uint32_t i = 0; i <= n; i++) ranks_out[i] = 0;
+            return kTTStatusEmptyMatrix;
+        }
+        const size_t got = svd_truncated_host(cur, rows, rem, c.max_rank, c.tolerance, U, S, Vt);
+        const size_t new_rank = std::min<size_t>(got, c.max_rank);
+        ranks_out[k + 1] = (uint32_t)new_rank;
+        if (cores_out)
+            for (size_t row = 0; row < rows; row++)
+                for (size_t r = 0; r < new_rank; r++) cores_out[coff + row * new_rank + r] = U[row * got + r];
+        coff += rows * new_rank;
+        cur.assign(new_rank * rem, 0.0f);
+        for (size_t r = 0; r < new_rank; r++)
+            for (size_t j = 0; j < rem; j++) cur[r * rem + j] = S[r] * Vt[r * rem + j];
+        left = new_rank;
+    }
+    ranks_out[n] = 1;
+    if (cores_out)
+        for (size_t i = 0; i < cur.size(); i++) cores_out[coff + i] = cur[i];
+    return kTTStatusOk;
+}
+
+void tt_decompose_host_batch(const TTDecConfig& c, const float* vectors, uint64_t n, uint32_t* status, uint32_t* ranks, float* cores,
+                             unsigned threads) {
+    auto work = [&](uint64_t lo, uint64_t hi) {
+        for (uint64_t q = lo; q < hi; q++)
+            status[q] = tt_decompose_host(c, vectors + q * c.dim, ranks + q * (c.n_cores + 1), cores ? cores + q * c.slot : nullptr);
+    };
+    threads = (unsigned)std::min<uint64_t>(std::max(threads, 1u), std::max<uint64_t>(n / 4, 1));
+    if (threads <= 1) return work(0, n);
+    std::vector<std::thread> pool;
+    for (unsigned t = 0; t < threads; t++) pool.emplace_back(work, n * t / threads, n * (t + 1) / threads);
+    for (std::thread& t : pool) t.join();
+}
+
+namespace {
+
+uint32_t env_u32(const char* name, uint32_t dflt) {
+    const char* e = getenv(name);
+    if (!e || !*e) return dflt;
+    char* end = nullptr;
+    const unsigned long long v = strtoull(e, &end, 10);
+    if (end == e) return dflt;
+    return (uint32_t)std::min<unsigned long long>(v, 0xFFFFFFFFull);
+}
+
+}  // namespace
+
+bool tt_decompose_on_host(const TTDecConfig& c, uint64_t n) {
+    return host_forced() || !c.on_device() || n < env_u32("NMN_TT_DECOMPOSE_MIN", kTTDecMinDefault);
+}
+
+namespace {
+
+// ---- the kernel ----
+
+struct TTDecArgs {
+    uint32_t n_cores, max_rank, dim;
+    float tolerance;
+    uint64_t n, slot;
+    uint32_t shape[kTTMaxCores];
+    const float* vectors;     // [n][dim]
+    uint32_t* status;         // [n]
+    uint32_t* ranks;          // [n][n_cores + 1]
+    float* cores;             // nullable: status only
+    uint64_t* core_off;       // nullable: [n + 1] = q * slot
+    const uint32_t* om_off;   // [n_cores][kTTDecMaxRank + 1]: where the Gaussian matrix of step k with left rank l starts in om
+    const float* om;
+    TTDecLayout o;
+};
+
+// v / n where n = sqrt(dot(v, v)) > 1e-10f, v as it is otherwise: every thread folds the whole chain from LDS (broadcast reads),
+// then the threads divide an element each.  raw is visible on entry, out on return.
+__device__ float dec_normalize(const float* raw, float* out, uint32_t n) {
+    float s = -0.0f;
+    for (uint32_t i = 0; i < n; i++) {
+        const float p = raw[i] * raw[i];
+        s = s + p;
+    }
+    const float nr = __builtin_sqrtf(s);
+    const bool divide = nr > 1e-10f;
+    for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) out[i] = divide ? raw[i] / nr : raw[i];
+    __syncthreads();
+    return nr;
+}
+
+// power_iteration of m (rows x cols, leading dimension ld): a thread per row of u and per column of v, each its own chain;
+// returns sigma (the same value in every thread), u in un and v in vn
+__device__ float dec_power_iteration(const float* m, uint32_t rows, uint32_t cols, uint32_t ld, float* ur, float* un, float* vr,
+                                     float* vn) {
+    const uint32_t tid = threadIdx.x, T = blockDim.x;
+    for (uint32_t j = tid; j < cols; j += T) vr[j] = (float)((j * 7u + 3u) % 13u) / 13.0f - 0.5f;
+    __syncthreads();
+    dec_normalize(vr, vn, cols);
+    float sigma = 0.0f;
+    for (int it = 0; it < 20; it++) {
+        for (uint32_t i = tid; i < rows; i += T) {
+            const float* row = m + (size_t)i * ld;
+            float s = -0.0f;
+            for (uint32_t j = 0; j < cols; j++) {
+                const float p = row[j] * vn[j];
+                s = s + p;
+            }
+            ur[i] = s;
+        }
+        __syncthreads();
+        const float new_sigma = dec_normalize(ur, un, rows);
+        for (uint32_t j = tid; j < cols; j += T) {
+            float s = -0.0f;
+            for (uint32_t i = 0; i < rows; i++) {
+                const float p = m[(size_t)i * ld + j] * un[i];
+                s = s + p;
+            }
+            vr[j] = s;
+        }
+        __syncthreads();
+        dec_normalize(vr, vn, cols);
+        const float bound = 1e-6f * (sigma > 1.0f ? sigma : 1.0f);
+        if (__builtin_fabsf(new_sigma - sigma) < bound) return new_sigma;
+        sigma = new_sigma;
+    }
+    return sigma;
+}
+
+// svd_power_iteration of m, deflated in place: U column-major (column c at U + c * rows), V row-major [rank][cols], S; returns the
+// rank.  m is visible on entry; U, V and S are visible on return.
+__device__ uint32_t dec_svd_power(float* m, uint32_t rows, uint32_t cols, uint32_t ld, uint32_t max_rank, float tolerance, float* U,
+                                  float* V, float* S, float* ur, float* un, float* vr, float* vn) {
+    const uint32_t tid = threadIdx.x, T = blockDim.x;
+    const uint32_t rank = min(max_rank, min(rows, cols));
+    float fs = -0.0f;
+    for (uint32_t i = 0; i < rows; i++)
+        for (uint32_t j = 0; j < cols; j++) {
+            const float x = m[(size_t)i * ld + j];
+            const float p = x * x;
+            fs = fs + p;
+        }
+    const float abs_tol = tolerance * __builtin_sqrtf(fs);
+    uint32_t got = 0;
+    for (uint32_t c = 0; c < rank; c++) {
+        const float sigma = dec_power_iteration(m, rows, cols, ld, ur, un, vr, vn);
+        if (sigma < abs_tol) break;
+        for (uint32_t i = tid; i < rows; i += T) U[(size_t)got * rows + i] = un[i];
+        for (uint32_t j = tid; j < cols; j += T) V[(size_t)got * cols + j] = vn[j];
+        if (tid == 0) S[got] = sigma;
+        for (uint32_t e = tid; e < rows * cols; e += T) {
+            const uint32_t i = e / cols, j = e - i * cols;
+            const float su = sigma * un[i];
+            const float p = su * vn[j];
+            m[(size_t)i * ld + j] = m[(size_t)i * ld + j] - p;
+        }
+        got++;
+        __syncthreads();
+    }
+    return got;
+}
+
+// One workgroup owns one vector at a time, the vectors beyond the grid in a stride loop; the vector's whole state is in dynamic LDS
+// (TTDecLayout).  No chain is split: the threads share out only the outputs the reference computes independently — the rows of u,
+// the columns of v, the elements of a deflation, the outputs of a matmul, the elements of a Gram-Schmidt update — and the
+// sequential norms and dots are folded by every thread from LDS.  Every branch below is taken by the whole workgroup.
+__global__ __launch_bounds__(256) void tt_decompose_kernel(TTDecArgs a) {
+    extern __shared__ float lds[];
+    float *A = lds + a.o.oA, *U = lds + a.o.oU, *V = lds + a.o.oV, *S = lds + a.o.oS, *ur = lds + a.o.oUr, *un = lds + a.o.oUn,
+          *vr = lds + a.o.oVr, *vn = lds + a.o.oVn, *B = lds + a.o.oB, *Q = lds + a.o.oQ, *Om = lds + a.o.oOm;
+    const uint32_t tid = threadIdx.x, T = blockDim.x, n = a.n_cores;
+    for (uint64_t q = blockIdx.x; q < a.n; q += gridDim.x) {
+        const float* vec = a.vectors + q * a.dim;
+        float* core = a.cores ? a.cores + q * a.slot : nullptr;
+        uint32_t* rk = a.ranks + q * (n + 1);
+        if (tid == 0 && a.core_off) {
+            a.core_off[q] = q * a.slot;
+            if (q + 1 == a.n) a.core_off[a.n] = a.n * a.slot;
+        }
+        __syncthreads();  // the readers of the previous vector are done
+        uint32_t left = 1, rem = a.dim / a.shape[0], coff = 0;
+        bool empty = false;
+        if (n == 1) {
+            if (core)
+                for (uint32_t e = tid; e < a.dim; e += T) core[e] = vec[e];
+        } else {
+            const uint32_t ld0 = rem | 1u;
+            for (uint32_t e = tid; e < a.dim; e += T) A[(size_t)(e / rem) * ld0 + e % rem] = vec[e];
+        }
+        if (tid == 0) rk[0] = 1;
+        for (uint32_t k = 0; k + 1 < n; k++) {
+            const uint32_t mode = a.shape[k], rows = left * mode, cols = rem, ld = cols | 1u;
+            __syncthreads();
+            const uint32_t mn = min(rows, cols), rank = min(a.max_rank, mn);
+            const float* Uf = U;  // column-major, column c at Uf + c * rows
+            uint32_t got;
+            if (!(rows > 32 && cols > 32 && rank * 2 < mn)) {
+                got = dec_svd_power(A, rows, cols, ld, a.max_rank, a.tolerance, U, V, S, ur, un, vr, vn);
+            } else {
+                const uint32_t t = rank + min(5u, mn - rank);
+                const float* om = a.om + a.om_off[k * (kTTDecMaxRank + 1) + left];
+                for (uint32_t e = tid; e < cols * t; e += T) Om[e] = om[e];
+                __syncthreads();
+                for (uint32_t e = tid; e < rows * t; e += T) {  // Y = A Omega, column-major into Q
+                    const uint32_t c = e / rows, i = e - c * rows;
+                    float s = 0.0f;
+                    for (uint32_t kk = 0; kk < cols; kk++) {
+                        const float p = A[(size_t)i * ld + kk] * Om[kk * t + c];
+                        s = s + p;
+                    }
+                    Q[e] = s;
+                }
+                __syncthreads();
+                uint32_t nq = 0;  // modified Gram-Schmidt, the kept columns packed to the front of Q
+                for (uint32_t j = 0; j < t; j++) {
+                    float* col = Q + (size_t)j * rows;
+                    for (uint32_t pq = 0; pq < nq; pq++) {
+                        const float* qc = Q + (size_t)pq * rows;
+                        float proj = -0.0f;
+                        for (uint32_t i = 0; i < rows; i++) {
+                            const float p = col[i] * qc[i];
+                            proj = proj + p;
+                        }
+                        __syncthreads();
+                        for (uint32_t i = tid; i < rows; i += T) {
+                            const float p = proj * qc[i];
+                            col[i] = col[i] - p;
+                        }
+                        __syncthreads();
+                    }
+                    float s = -0.0f;
+                    for (uint32_t i = 0; i < rows; i++) {
+                        const float p = col[i] * col[i];
+                        s = s + p;
+                    }
+                    const float nr = __builtin_sqrtf(s);
+                    __syncthreads();
+                    if (nr > 1e-10f) {
+                        float* dst = Q + (size_t)nq * rows;
+                        for (uint32_t i = tid; i < rows; i += T) dst[i] = col[i] / nr;
+                        nq++;
+                    }
+                    __syncthreads();
+                }
+                got = 0;
+                if (nq) {
+                    for (uint32_t e = tid; e < nq * cols; e += T) {  // B = Q^T A
+                        const uint32_t pq = e / cols, j = e - pq * cols;
+                        float s = 0.0f;
+                        for (uint32_t kk = 0; kk < rows; kk++) {
+                            const float p = Q[(size_t)pq * rows + kk] * A[(size_t)kk * ld + j];
+                            s = s + p;
+                        }
+                        B[(size_t)pq * ld + j] = s;
+                    }
+                    __syncthreads();
+                    got = dec_svd_power(B, nq, cols, ld, rank, a.tolerance, U, V, S, ur, un, vr, vn);
+                    for (uint32_t e = tid; e < rows * got; e += T) {  // U = Q U_B, into A: the unfolding is dead
+                        const uint32_t c = e / rows, i = e - c * rows;
+                        float s = 0.0f;
+                        for (uint32_t kk = 0; kk < nq; kk++) {
+                            const float p = Q[(size_t)kk * rows + i] * U[(size_t)c * nq + kk];
+                            s = s + p;
+                        }
+                        A[e] = s;
+                    }
+                    __syncthreads();
+                    Uf = A;
+                }
+            }
+            const uint32_t new_rank = min(got, a.max_rank);
+            if (tid == 0) rk[k + 1] = new_rank;
+            if (new_rank == 0 && k + 2 < n) {  // the next unfolding is empty: svd_truncated's EmptyMatrix
+                empty = true;
+                break;
+            }
+            if (core)
+                for (uint32_t e = tid; e < rows * new_rank; e += T) {
+                    const uint32_t row = e / new_rank, r = e - row * new_rank;
+                    core[coff + e] = Uf[(size_t)r * rows + row];
+                }
+            coff += rows * new_rank;
+            const uint32_t total = new_rank * cols;
+            if (k + 2 == n) {  // what is left is the last core
+                if (core)
+                    for (uint32_t e = tid; e < total; e += T) core[coff + e] = S[e / cols] * V[e];
+            } else {
+                const uint32_t ncols = cols / a.shape[k + 1], nld = ncols | 1u;
+                __syncthreads();  // Uf may be in A
+                for (uint32_t e = tid; e < total; e += T) A[(size_t)(e / ncols) * nld + e % ncols] = S[e / cols] * V[e];
+            }
+            left = new_rank;
+            rem = cols / a.shape[k + 1];
+        }
+        if (tid == 0) {
+            if (empty) {
+                for (uint32_t i = 0; i <= n; i++) rk[i] = 0;
+            } else {
+                rk[n] = 1;
+            }
+            a.status[q] = empty ? kTTStatusEmptyMatrix : kTTStatusOk;
+        }
+    }
+}
+
+// The Gaussian matrices of one config, made on the host (logf, cosf and sinf are the host libm's, as in the reference) and kept on
+// the device for the life of the process: [n_cores][kTTDecMaxRank + 1] offsets, then the matrices.
+struct DevOmega {
+    int device;
+    uint32_t n_cores, max_rank, shape[kTTMaxCores];
+    uint32_t* off;
+    float* data;
+};
+std::mutex g_omega_mu;
+std::vector<DevOmega> g_omega;
+
+nmn_status omega_for(const TTDecConfig& c, const DevOmega** out) {
+    int dev = 0;
+    TT_TRY(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lk(g_omega_mu);
+    for (const DevOmega& o : g_omega)
+        if (o.device == dev && o.n_cores == c.n_cores && o.max_rank == c.max_rank && !memcmp(o.shape, c.shape, sizeof o.shape)) {
+            *out = &o;
+            return NMN_OK;
+        }
+    const size_t table = (size_t)c.n_cores * (kTTDecMaxRank + 1);
+    std::vector<uint32_t> off(table, 0);
+    std::vector<float> data(1, 0.0f);
+    uint64_t rem = c.dim;
+    for (uint32_t k = 0; k + 1 < c.n_cores; k++) {
+        rem /= c.shape[k];
+        for (uint32_t l = 1; l <= c.rb[k]; l++) {
+            const uint64_t rows = (uint64_t)l * c.shape[k];
+            const RandomizedStep r = randomized_step(rows, rem, c.max_rank);
+            if (!r.taken) continue;
+            const std::vector<float> g = gaussian_matrix_host(rem, r.target, rows * 31 + rem);
+            off[k * (kTTDecMaxRank + 1) + l] = (uint32_t)data.size();
+            data.insert(data.end(), g.begin(), g.end());
+        }
+    }
+    DevOmega o{};
+    o.device = dev;
+    o.n_cores = c.n_cores;
+    o.max_rank = c.max_rank;
+    memcpy(o.shape, c.shape, sizeof o.shape);
+    TT_TRY(hipMalloc((void**)&o.off, table * 4));
+    if (hipError_t e = hipMalloc((void**)&o.data, data.size() * 4); e != hipSuccess) {
+        (void)hipFree(o.off);
+        return set_error_hip(e, "hipMalloc");
+    }
+    hipError_t e = hipMemcpy(o.off, off.data(), table * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(o.data, data.data(), data.size() * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(o.off);
+        (void)hipFree(o.data);
+        return set_error_hip(e, "hipMemcpy");
+    }
+    g_omega.reserve(64);
+    g_omega.push_back(o);
+    *out = &g_omega.back();
+    return NMN_OK;
+}
+
+}  // namespace
+
+nmn_status launch_tt_decompose(const TTDecConfig& c, const float* vectors_dev, uint64_t n, uint32_t* status_dev, uint32_t* ranks_dev,
+                               float* cores_dev, uint64_t* core_off_dev, hipStream_t s) {
+    if (n == 0) return NMN_OK;
+    if (!c.on_device()) return set_error(NMN_ERR_INVALID_ARGUMENT, "TT: the config is above the limits of the device's tt_decompose");
+    const DevOmega* om = nullptr;
+    nmn_status st = omega_for(c, &om);
+    if (st != NMN_OK) return st;
+    TTDecArgs a{};
+    a.n_cores = c.n_cores;
+    a.max_rank = c.max_rank;
+    a.dim = (uint32_t)c.dim;
+    a.tolerance = c.tolerance;
+    a.n = n;
+    a.slot = c.slot;
+    memcpy(a.shape, c.shape, sizeof a.shape);
+    a.vectors = vectors_dev;
+    a.status = status_dev;
+    a.ranks = ranks_dev;
+    a.cores = cores_dev;
+    a.core_off = core_off_dev;
+    a.om_off = om->off;
+    a.om = om->data;
+    a.o = dec_layout(c);
+    uint32_t threads = env_u32("NMN_TT_DECOMPOSE_THREADS", kTTDecThreads);
+    if (threads != 64 && threads != 128 && threads != 256) threads = kTTDecThreads;
+    const uint32_t grid_max = std::max(env_u32("NMN_TT_DECOMPOSE_GRID", kTTDecGridMax), 1u);
+    hipLaunchKernelGGL(tt_decompose_kernel, dim3((uint32_t)std::min<uint64_t>(n, grid_max)), dim3(threads), a.o.total * sizeof(float), s, a);
+    TT_TRY(hipGetLastError());
+    return NMN_OK;
+}
+
+namespace {
+
+// TTConfig::for_dim's shape (tensor_train.rs:130-199): the table, then factorize_balanced with the host libm's f64 log2 and pow
+std::vector<uint32_t> optimal_shape(uint64_t dim) {
+    switch (dim) {
+        case 64: return {4, 4, 4};
+        case 128: return {4, 4, 8};
+        case 256: return {4, 8, 8};
+        case 384: return {4, 8, 12};
+        case 512: return {8, 8, 8};
+        case 768: return {8, 8, 12};
+        case 1024: return {8, 8, 16};
+        case 1536: return {8, 12, 16};
+        case 2048: return {8, 16, 16};
+        case 3072: return {8, 16, 24};
+        case 4096: return {8, 8, 8, 8};
+        case 8192: return {8, 8, 8, 16};
+    }
+    if (dim == 1) return {1};
+    const double log_n = ceil(log2((double)dim));
+    const uint64_t target_factors = std::min<uint64_t>(std::max<uint64_t>((uint64_t)log_n, 2), 6);
+    const uint64_t target_size = (uint64_t)pow((double)dim, 1.0 / (double)target_factors);
+    std::vector<uint32_t> factors;
+    uint64_t remaining = dim;
+    for (uint64_t it = 0; it + 1 < target_factors; it++) {
+        uint64_t best = 1;
+        for (uint64_t f = std::max<uint64_t>(target_size, 2); f >= 2; f--)
+            if (remaining % f == 0) {
+                best = f;
+                break;
+            }
+        if (best == 1) {
+            for (uint64_t f = 2; f * f <= remaining; f++)  // (the smallest factor; a prime's is itself)
+                if (remaining % f == 0) {
+                    best = f;
+                    break;
+                }
+            if (best == 1) best = remaining;
+        }
+        factors.push_back((uint32_t)best);
+        remaining /= best;
+        if (remaining == 1) break;
+    }
+    if (remaining > 1) factors.push_back((uint32_t)remaining);
+    std::sort(factors.begin(), factors.end());
+    return factors;
+}
+
+}  // namespace
 }  // namespace nmn
+
+extern "C" nmn_status nmn_tt_config_for_dim(uint64_t dim, uint32_t preset, uint32_t* shape_out, uint32_t* n_cores_out,
+                                            uint32_t* max_rank_out, float* tolerance_out) {
+    if (dim == 0) return nmn::set_error(NMN_ERR_INVALID_ARGUMENT, "empty vector");
+    if (dim > 0xFFFFFFFFull) return nmn::set_error(NMN_ERR_INVALID_ARGUMENT, "TT: dim above 2^32");
+    if (preset > NMN_TT_PRESET_HIGH_ACCURACY) return nmn::set_error(NMN_ERR_INVALID_ARGUMENT, "TT: unknown preset");
+    if (!shape_out || !n_cores_out) return nmn::set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    const std::vector<uint32_t> shape = nmn::optimal_shape(dim);
+    for (size_t k = 0; k < shape.size(); k++) shape_out[k] = shape[k];
+    *n_cores_out = (uint32_t)shape.size();
+    static const uint32_t rank[3] = {8, 4, 16};
+    static const float tol[3] = {1e-4f, 1e-2f, 1e-6f};
+    if (max_rank_out) *max_rank_out = rank[preset];
+    if (tolerance_out) *tolerance_out = tol[preset];
+    return NMN_OK;
+}
+
+extern "C" uint64_t nmn_tt_max_storage(const uint32_t* shape, uint32_t n_cores, uint32_t max_rank) {
+    if (!shape || n_cores < 1 || n_cores > nmn::kTTMaxCores || max_rank < 1) return 0;
+    unsigned __int128 dim = 1;
+    for (uint32_t k = 0; k < n_cores; k++) dim *= shape[k];
+    if (dim == 0 || dim > (1ull << 31)) return 0;
+    nmn::TTDecConfig c;
+    if (nmn::tt_dec_config((uint64_t)dim, shape, n_cores, max_rank, 1e-4f, &c, nullptr, 0) != NMN_OK) return 0;
+    return c.slot;
+}
+
+extern "C" nmn_status nmn_tt_decompose_limits(uint32_t* max_cores, uint32_t* max_rank, uint32_t* max_dim, uint32_t* max_lds_floats) {
+    if (max_cores) *max_cores = nmn::kTTMaxCores;
+    if (max_rank) *max_rank = nmn::kTTDecMaxRank;
+    if (max_dim) *max_dim = nmn::kTTDecMaxLdsFloats - 1;  // the first unfolding alone, padded, must fit
+    if (max_lds_floats) *max_lds_floats = nmn::kTTDecMaxLdsFloats;
+    return NMN_OK;
+}
+
+extern "C" uint64_t nmn_tt_decompose_lds_floats(const uint32_t* shape, uint32_t n_cores, uint32_t max_rank) {
+    if (!shape || n_cores < 1 || n_cores > nmn::kTTMaxCores || max_rank < 1) return 0;
+    unsigned __int128 dim = 1;
+    for (uint32_t k = 0; k < n_cores; k++) dim *= shape[k];
+    if (dim == 0 || dim > (1ull << 31)) return 0;
+    nmn::TTDecConfig c;
+    if (nmn::tt_dec_config((uint64_t)dim, shape, n_cores, max_rank, 1e-4f, &c, nullptr, 0) != NMN_OK) return 0;
+    return c.on_device() ? c.lds_floats : ~0ull;
+}
+
+extern "C" nmn_status nmn_tt_decompose(const float* vectors, uint64_t n, uint64_t dim, const uint32_t* shape, uint32_t n_cores,
+                                       uint32_t max_rank, float tolerance, uint32_t* status_out, uint32_t* ranks_out,
+                                       uint64_t* core_off_out, float* cores_out, uint64_t cores_cap) {
+    using namespace nmn;
+    TTDecConfig c;
+    nmn_status st = tt_dec_config(dim, shape, n_cores, max_rank, tolerance, &c, nullptr, 0);
+    if (st != NMN_OK) return st;
+    if (n == 0) return NMN_OK;
+    if (!vectors || !status_out || !ranks_out || (cores_out && !core_off_out)) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (n > (1ull << 31)) return set_error(NMN_ERR_INVALID_ARGUMENT, "TT: more than 2^31 vectors");
+    const size_t rk = (size_t)n * (n_cores + 1);
+    std::vector<float> slots(cores_out ? (size_t)n * c.slot : 0);
+    std::vector<uint32_t> status(n), ranks(rk);
+    if (tt_decompose_on_host(c, n)) {
+        tt_decompose_host_batch(c, vectors, n, status.data(), ranks.data(), cores_out ? slots.data() : nullptr,
+                                env_u32("NMN_TT_DECOMPOSE_HOST_THREADS", 16));
+    } else {
+        float *d_vec = nullptr, *d_cores = nullptr;
+        uint32_t *d_status = nullptr, *d_ranks = nullptr;
+        auto body = [&]() -> nmn_status {
+            TT_TRY(hipMalloc((void**)&d_vec, (size_t)n * dim * 4));
+            TT_TRY(hipMalloc((void**)&d_status, (size_t)n * 4));
+            TT_TRY(hipMalloc((void**)&d_ranks, rk * 4));
+            if (cores_out) TT_TRY(hipMalloc((void**)&d_cores, std::max<size_t>(slots.size() * 4, 256)));
+            TT_TRY(hipMemcpy(d_vec, vectors, (size_t)n * dim * 4, hipMemcpyHostToDevice));
+            nmn_status l = launch_tt_decompose(c, d_vec, n, d_status, d_ranks, d_cores, nullptr, nullptr);
+            if (l != NMN_OK) return l;
+            TT_TRY(hipDeviceSynchronize());
+            TT_TRY(hipMemcpy(status.data(), d_status, (size_t)n * 4, hipMemcpyDeviceToHost));
+            TT_TRY(hipMemcpy(ranks.data(), d_ranks, rk * 4, hipMemcpyDeviceToHost));
+            if (cores_out && !slots.empty()) TT_TRY(hipMemcpy(slots.data(), d_cores, slots.size() * 4, hipMemcpyDeviceToHost));
+            return NMN_OK;
+        };
+        st = body();
+        for (void* p : {(void*)d_vec, (void*)d_cores, (void*)d_status, (void*)d_ranks})
+            if (p) (void)hipFree(p);
+        if (st != NMN_OK) return st;
+    }
+    // the trains leave their slots for a packed array: core_off as nmn_tt_reconstruct, nmn_tt_norm and nmn_hnsw_search_tt take it
+    uint64_t total = 0;
+    std::vector<uint64_t> sizes(n, 0);
+    for (uint64_t q = 0; q < n; q++) {
+        if (status[q] != kTTStatusOk) continue;
+        const uint32_t* r = ranks.data() + q * (n_cores + 1);
+        for (uint32_t k = 0; k < n_cores; k++) sizes[q] += (uint64_t)r[k] * shape[k] * r[k + 1];
+        total += sizes[q];
+    }
+    if (cores_out && total > cores_cap) {
+        char text[160];
+        snprintf(text, sizeof text, "TT: cores_cap is %llu floats, the trains need %llu (n * nmn_tt_max_storage always suffices)",
+                 (unsigned long long)cores_cap, (unsigned long long)total);
+        return set_error(NMN_ERR_INVALID_ARGUMENT, text);
+    }
+    memcpy(status_out, status.data(), (size_t)n * 4);
+    memcpy(ranks_out, ranks.data(), rk * 4);
+    if (core_off_out) {
+        core_off_out[0] = 0;
+        for (uint64_t q = 0; q < n; q++) {
+            if (cores_out && sizes[q]) memcpy(cores_out + core_off_out[q], slots.data() + q * c.slot, sizes[q] * 4);
+            core_off_out[q + 1] = core_off_out[q] + sizes[q];
+        }
+    }
+    return NMN_OK;
+}
+
+extern "C" nmn_status nmn_tt_decompose_device(const float* vectors_dev, uint64_t n, uint64_t dim, const uint32_t* shape,
+                                              uint32_t n_cores, uint32_t max_rank, float tolerance, uint32_t* status_dev,
+                                              uint32_t* ranks_dev, uint64_t* core_off_dev, float* cores_dev, uint64_t cores_cap,
+                                              void* stream) {
+    using namespace nmn;
+    TTDecConfig c;
+    nmn_status st = tt_dec_config(dim, shape, n_cores, max_rank, tolerance, &c, nullptr, 0);
+    if (st != NMN_OK) return st;
+    if (n == 0) return NMN_OK;
+    if (!vectors_dev || !status_dev || !ranks_dev) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (n > (1ull << 31)) return set_error(NMN_ERR_INVALID_ARGUMENT, "TT: more than 2^31 vectors");
+    if (cores_dev && cores_cap / c.slot < n) return set_error(NMN_ERR_INVALID_ARGUMENT, "TT: cores_cap is below n * nmn_tt_max_storage");
+    return launch_tt_decompose(c, vectors_dev, n, status_dev, ranks_dev, cores_dev, cores_dev ? core_off_dev : nullptr,
+                               (hipStream_t)stream);
+}
 
 extern "C" nmn_status nmn_tt_reconstruct(const uint32_t* shape, uint32_t n_cores, const uint32_t* ranks, const uint64_t* core_off,
                                          const float* cores, uint32_t nq, float* out_rows) {

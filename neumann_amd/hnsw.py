@@ -528,6 +528,44 @@ class GpuHnsw:
                                                  C.c_void_p(ids.ctypes.data)))
         return ids
 
+    def search_tt_dense(self, queries, k, config, with_stats=False):
+        """HNSWIndex::search_tt per query (nmn_hnsw_search_tt_dense): the query is decomposed under `config` (a
+        neumann_amd.tt.TTConfig); an Ok train is answered as `search_tt` answers it (Cosine, ef_search), an Err of any kind as
+        `search` answers the dense query under the index's metric (docs/hnsw.md §21).
+        -> (ids u64 [nq,k], scores f32 [nq,k], counts u32 [nq])"""
+        q = self._rows(queries)
+        nq, k = q.shape[0], int(k)
+        sh, r, tol = config._c()
+        ids, sc, counts, st = _host_out(nq, k)
+        _capi.check(self._lib.nmn_hnsw_search_tt_dense(self._h, C.c_void_p(q.ctypes.data), nq, q.shape[1], C.c_void_p(sh.ctypes.data),
+                                                       sh.size, r, tol, k, C.c_void_p(ids.ctypes.data), C.c_void_p(sc.ctypes.data),
+                                                       C.c_void_p(counts.ctypes.data), C.byref(st)))
+        return (ids, sc, counts, st) if with_stats else (ids, sc, counts)
+
+    def insert_tt_dense(self, vector, config):
+        """HNSWIndex::insert_tt (nmn_hnsw_insert_tt_dense): the vector is decomposed under `config` to validate it and inserted
+        as a Dense node by `insert`'s path; returns the node id.  Dense handles only."""
+        v = np.ascontiguousarray(vector, dtype=np.float32).reshape(-1)
+        sh, r, tol = config._c()
+        out = C.c_uint64()
+        _capi.check(self._lib.nmn_hnsw_insert_tt_dense(self._h, C.c_void_p(v.ctypes.data), v.size, C.c_void_p(sh.ctypes.data), sh.size,
+                                                       r, tol, C.byref(out)))
+        return int(out.value)
+
+    def insert_batch_tt(self, vectors, config):
+        """HNSWIndex::insert_batch_tt (nmn_hnsw_insert_batch_tt): every vector is decomposed under `config`; if any decomposition
+        fails nothing is inserted and the error names the lowest failing index; returns the node ids (none for an empty batch)."""
+        v = np.ascontiguousarray(vectors, dtype=np.float32)
+        if v.size == 0:
+            return np.empty(0, dtype=np.uint64)
+        if v.ndim != 2:
+            raise _capi.NeumannGpuError(_capi.ERR_INVALID_ARGUMENT, "vectors must be [n, dim]")
+        sh, r, tol = config._c()
+        ids = np.empty(v.shape[0], dtype=np.uint64)
+        _capi.check(self._lib.nmn_hnsw_insert_batch_tt(self._h, C.c_void_p(v.ctypes.data), v.shape[0], v.shape[1],
+                                                       C.c_void_p(sh.ctypes.data), sh.size, r, tol, C.c_void_p(ids.ctypes.data)))
+        return ids
+
     def search_metric(self, queries, top_k, metric, with_stats=False):
         """search_with_hnsw_and_metric's steps per query (nmn_hnsw_search_metric): c = max(2 top_k, 10) candidates from the walk,
         re-ranked under `metric` (an ExtendedDistanceMetric), the first top_k of the stable descending order.

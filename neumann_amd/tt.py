@@ -2,7 +2,8 @@
 
 `TTVector` carries what `tensor_compress::TTVector` (tensor_compress/src/tensor_train.rs:267-281) carries — a shape, the ranks and
 the cores — and validates as the C entries do; `tt_reconstruct` / `tt_norm` run tt_reconstruct (401-436) and tt_norm (440-474) on the
-GPU, bit for bit.  Decomposing a vector (tt_decompose, a truncated SVD) is the caller's: this module takes cores."""
+GPU, bit for bit.  `TTConfig` and `tt_decompose` are tensor_compress's (41-126, 315-397): from a dense vector and a config to a
+train, bit for bit (nmn_tt_decompose, docs/hnsw.md §21)."""
 import ctypes as C
 
 import numpy as np
@@ -45,6 +46,18 @@ class TTVector:
             if a.size != self.ranks[k] * self.shape[k] * self.ranks[k + 1]:
                 raise _bad(f"TT: core {k} must hold ranks[k] * shape[k] * ranks[k + 1] floats")
             self.cores.append(a.reshape(self.ranks[k], self.shape[k], self.ranks[k + 1]))
+
+    @classmethod
+    def _from_decompose(cls, shape, ranks, flat):
+        """what nmn_tt_decompose returned: taken as it is (a two-core train may carry a rank of 0, which the entries that take
+        trains refuse)"""
+        t = cls.__new__(cls)
+        t.shape, t.ranks, t.cores, at = list(shape), [int(r) for r in ranks], [], 0
+        for k, n in enumerate(t.shape):
+            size = t.ranks[k] * n * t.ranks[k + 1]
+            t.cores.append(np.array(flat[at:at + size], dtype=np.float32).reshape(t.ranks[k], n, t.ranks[k + 1]))
+            at += size
+        return t
 
     @property
     def dim(self):
@@ -95,4 +108,126 @@ def tt_norm(tts):
     nq = ranks.shape[0]
     out = np.empty(nq, dtype=np.float32)
     _capi.check(_capi.load().nmn_tt_norm(_p(shape), shape.size, _p(ranks), _p(off), _p(cores), nq, _p(out)))
+    return out
+
+
+PRESETS = {"for_dim": 0, "high_compression": 1, "high_accuracy": 2}
+
+
+class TTConfig:
+    """tensor_compress::TTConfig (tensor_train.rs:41-49): the shape a vector is folded into, the largest TT-rank, and the relative
+    tolerance at which the SVD of a step stops."""
+
+    def __init__(self, shape, max_rank=8, tolerance=1e-4):
+        self.shape = [int(x) for x in shape]
+        self.max_rank = int(max_rank)
+        self.tolerance = float(np.float32(tolerance))
+
+    def __repr__(self):
+        return f"TTConfig(shape={self.shape}, max_rank={self.max_rank}, tolerance={self.tolerance})"
+
+    def __eq__(self, other):
+        return isinstance(other, TTConfig) and (self.shape, self.max_rank, self.tolerance) == (other.shape, other.max_rank, other.tolerance)
+
+    @classmethod
+    def _preset(cls, dim, preset):
+        shape = (C.c_uint32 * 8)()
+        n, r, t = C.c_uint32(), C.c_uint32(), C.c_float()
+        _capi.check(_capi.load().nmn_tt_config_for_dim(int(dim), PRESETS[preset], shape, C.byref(n), C.byref(r), C.byref(t)))
+        return cls(list(shape[:n.value]), r.value, t.value)
+
+    @classmethod
+    def for_dim(cls, dim):
+        """TTConfig::for_dim (77-89): optimal_shape(dim), max_rank 8, tolerance 1e-4"""
+        return cls._preset(dim, "for_dim")
+
+    @classmethod
+    def high_compression(cls, dim):
+        """TTConfig::high_compression (95-107): max_rank 4, tolerance 1e-2"""
+        return cls._preset(dim, "high_compression")
+
+    @classmethod
+    def high_accuracy(cls, dim):
+        """TTConfig::high_accuracy (113-125): max_rank 16, tolerance 1e-6"""
+        return cls._preset(dim, "high_accuracy")
+
+    def validate(self):
+        """TTConfig::validate (56-70), its Display texts; tt_decompose itself does not call it"""
+        if not self.shape:
+            raise _bad("invalid shape: empty shape")
+        if 0 in self.shape:
+            raise _bad("invalid shape: shape contains zero")
+        if self.max_rank < 1:
+            raise _bad("invalid TT-rank: must be >= 1")
+        t = self.tolerance
+        if not (t > 0.0 and t <= 1.0):
+            raise _bad(f"invalid tolerance: {t} (must be 0 < tol <= 1)")
+
+    @property
+    def max_storage(self):
+        """the slot of one train in floats (nmn_tt_max_storage)"""
+        sh = np.asarray(self.shape, dtype=np.uint32)
+        return int(_capi.load().nmn_tt_max_storage(_p(sh), sh.size, max(self.max_rank, 0)))
+
+    def _c(self):
+        if self.max_rank < 0 or any(n < 0 for n in self.shape):
+            raise _bad("invalid TT-rank: must be >= 1" if self.max_rank < 0 else "invalid shape: negative mode")
+        return np.asarray(self.shape, dtype=np.uint32), self.max_rank, C.c_float(self.tolerance)
+
+
+class TTDecomposeError(_capi.NeumannGpuError):
+    """one vector's Err of tt_decompose; `kind` is the Debug form of the reference's TTError"""
+
+    def __init__(self, kind, text):
+        super().__init__(_capi.ERR_INVALID_ARGUMENT, text)
+        self.kind = kind
+
+
+def decompose_limits():
+    """(max_cores, max_rank, max_dim, max_lds_floats): what the device path of tt_decompose serves (nmn_tt_decompose_limits); a
+    config is served there when `decompose_lds_floats` is at most max_lds_floats"""
+    v = [C.c_uint32() for _ in range(4)]
+    _capi.check(_capi.load().nmn_tt_decompose_limits(*[C.byref(x) for x in v]))
+    return tuple(int(x.value) for x in v)
+
+
+def decompose_lds_floats(config):
+    """the LDS floats `config` needs on the device, None when it is above the limits (nmn_tt_decompose_lds_floats)"""
+    sh, r, _ = config._c()
+    v = int(_capi.load().nmn_tt_decompose_lds_floats(_p(sh), sh.size, r))
+    return None if v == 2 ** 64 - 1 else v
+
+
+def tt_decompose_raw(vectors, config, want_cores=True):
+    """nmn_tt_decompose as it is -> (status u32 [n], ranks u32 [n][d + 1], core_off u64 [n + 1], cores f32)"""
+    v = np.ascontiguousarray(vectors, dtype=np.float32)
+    if v.ndim == 1:
+        v = v[None, :]
+    sh, r, tol = config._c()
+    n, dim = v.shape
+    status = np.zeros(n, dtype=np.uint32)
+    ranks = np.zeros((n, sh.size + 1), dtype=np.uint32)
+    off = np.zeros(n + 1, dtype=np.uint64)
+    cap = n * int(_capi.load().nmn_tt_max_storage(_p(sh), sh.size, r)) if want_cores else 0
+    cores = np.zeros(max(cap, 1), dtype=np.float32)
+    _capi.check(_capi.load().nmn_tt_decompose(_p(v), n, dim, _p(sh), sh.size, r, tol, _p(status), _p(ranks), _p(off),
+                                              _p(cores) if want_cores else None, cap))
+    return status, ranks, off, cores[:int(off[n])]
+
+
+def tt_decompose(vectors, config, return_status=False):
+    """tt_decompose (tensor_train.rs:315-397) of one vector [dim] or several [n][dim] under `config`, bit for bit -> a list of
+    TTVector.  A vector whose decomposition is an Err (Decompose(EmptyMatrix)) raises TTDecomposeError; with return_status=True the
+    list holds that error in the vector's slot instead.  An empty vector, a shape whose product is not the dimension and
+    max_rank < 1 refuse the call with the reference's text."""
+    status, ranks, off, cores = tt_decompose_raw(vectors, config)
+    out = []
+    for q in range(status.size):
+        if status[q] == 0:
+            out.append(TTVector._from_decompose(config.shape, ranks[q], cores[int(off[q]):int(off[q + 1])]))
+            continue
+        err = TTDecomposeError("Decompose(EmptyMatrix)", f"TT: vector {q}: decomposition error: empty matrix")
+        if not return_status:
+            raise err
+        out.append(err)
     return out
