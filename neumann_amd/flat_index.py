@@ -179,9 +179,9 @@ class GpuFlatIndex:
                                                      _ptr(out_rows), _ptr(out_scores), _ptr(out_counts), None))
         return out_rows, out_scores, out_counts
 
-    def search_pred(self, columns, ops, consts, queries, k, metric=DistanceMetric.Cosine):
+    def search_pred(self, columns, ops, consts, queries, k, metric=DistanceMetric.Cosine, with_stats=False):
         """Filtered search in one call: evaluate the predicate program over `columns` (a GpuColumns covering this
-        shard's rows) and search what it selects.  Returns (rows, scores, counts, selected)."""
+        shard's rows) and search what it selects.  Returns (rows, scores, counts, selected[, stats])."""
         from ._capi import PredOp
         q = _f32(queries)
         if q.ndim == 1:
@@ -195,10 +195,13 @@ class GpuFlatIndex:
         out_scores = np.empty((nq, max(k, 1)), dtype=np.float32)
         out_counts = np.empty(nq, dtype=np.uint32)
         sel = C.c_uint64()
+        stats = _capi.SearchStats()
         _capi.check(self._lib.nmn_index_search_pred(self._h, columns._h, arr, len(ops),
                                                     C.c_void_p(cs.ctypes.data) if cs.size else None, cs.size, _ptr(q), nq, k,
                                                     int(metric), _ptr(out_rows), _ptr(out_scores), _ptr(out_counts),
-                                                    C.byref(sel), None))
+                                                    C.byref(sel), C.byref(stats) if with_stats else None))
+        if with_stats:
+            return out_rows, out_scores, out_counts, int(sel.value), stats
         return out_rows, out_scores, out_counts, int(sel.value)
 
     def search_device(self, queries_t, k, metric=DistanceMetric.Cosine, mask_t=None, out=None, stream=None):
