@@ -723,6 +723,39 @@ nmn_status nmn_hnsw_coalesce_stats(nmn_hnsw* h, uint64_t* batches, uint64_t* cal
  * nmn_hnsw_destroy wait for the searches in flight. */
 nmn_status nmn_hnsw_search_device(nmn_hnsw* h, const float* queries_dev, uint32_t nq, uint32_t k, uint32_t ef,
                                   uint64_t* out_ids_dev, float* out_scores_dev, uint32_t* out_counts_dev, void* stream);
+/* SparseVector::try_from_parts (sparse_vector.rs:155-193), magnitude (548-559) and to_dense (400-406) of nq CSR queries that sit
+ * in DEVICE memory, bit for bit what nmn_hnsw_search_sparse makes of them on the host (docs/hnsw.md §22): indptr_dev [nq + 1],
+ * positions_dev / values_dev [nnz_total].  nnz_total and max_nnz are HOST scalars: the entries the two arrays hold, and the
+ * caller's bound on the raw entries of one query — at most 4096 (above: NMN_ERR_INVALID_ARGUMENT), 0 = min(dim, 4096); dim is
+ * 1 .. 8192.  Per query: entries with val == 0.0 (either sign) dropped, NaN kept, the rest stably sorted by position (duplicates
+ * survive in input order).  out_off_dev [nq + 1]: the kept entries of query q are [off[q], off[q + 1]) of out_entries_dev
+ * [nnz_total][2], pairs of {position, value bits}; out_mag_dev [nq]: ONE f64 chain from -0.0 over the kept values in that order,
+ * one f64 sqrt, one cast; out_dup_dev [nq] (nullable): 1 iff two kept entries share a position; out_dense_dev [nq][dim]
+ * (nullable): zeros, then the entries in order, the last of a duplicated position wins.  out_status_dev [nq], the first rule that
+ * fails: 2 — indptr[q + 1] < indptr[q], the range not within the nnz_total entries, or more than max_nnz raw entries; 1 — a raw
+ * entry whose position is >= dim (checked before its value is looked at); 0 — served.  A query with a status is canonicalised as
+ * the entry-less query: count 0, that query's magnitude, a zero row.  Whatever the arrays hold, nothing outside them is read or
+ * written (a query whose kept entries no longer fit out_entries_dev, possible only where ranges overlap behind a decreasing
+ * indptr, is status 2 as well).  Three launches on `stream` of `device` (negative: the current one), not waited for, nothing read
+ * back. */
+nmn_status nmn_sparse_canonicalise_device(uint32_t dim, const uint64_t* indptr_dev, const uint32_t* positions_dev,
+                                          const float* values_dev, uint32_t nq, uint64_t nnz_total, uint32_t max_nnz,
+                                          uint64_t* out_off_dev, uint32_t* out_entries_dev, float* out_mag_dev, uint32_t* out_dup_dev,
+                                          float* out_dense_dev, uint32_t* out_status_dev, int32_t device, void* stream);
+/* nmn_hnsw_search_sparse with the CSR and every output in DEVICE memory, under nmn_hnsw_search_device's contract: enqueued on
+ * `stream`, not waited for, nothing read back, a shape the stream has served before allocates nothing; nmn_hnsw_insert and
+ * nmn_hnsw_destroy wait for it.  The CSR, nnz_total and max_nnz are nmn_sparse_canonicalise_device's, whose three launches run in
+ * front of the walk's; the walk is routed as nmn_hnsw_search_sparse routes it, and a served query's ids, score bits and count are
+ * that entry's.  out_status_dev [nq] (nullable): 0 served, 1 / 2 as above, 3 — a query with a duplicated position on a handle
+ * with sparse nodes (only the device knows it has one; the host entry walks it on the host).  A query with a status is walked as
+ * the entry-less query and a closing launch makes its row count 0, ids UINT64_MAX, scores -inf; the other rows are untouched.
+ * k == 0, nq == 0, ef == 0 and the empty index are nmn_hnsw_search_sparse's.  NMN_ERR_CONFIGURATION before anything is enqueued
+ * or written, because the host entry answers these from the host: a Binary handle; a handle with sparse nodes under Euclidean; a
+ * handle with a sparse node that holds a duplicated position.  On every other handle duplicated positions are served. */
+nmn_status nmn_hnsw_search_sparse_device(nmn_hnsw* h, const uint64_t* indptr_dev, const uint32_t* positions_dev,
+                                         const float* values_dev, uint32_t nq, uint64_t nnz_total, uint32_t max_nnz, uint32_t k,
+                                         uint32_t ef, uint64_t* out_ids_dev, float* out_scores_dev, uint32_t* out_counts_dev,
+                                         uint32_t* out_status_dev, void* stream);
 /* Entries of the results / candidate heaps a wave keeps in LDS (0 = default: 1024 results, 1024 .. 4096 candidates by ef).
  * Smaller heaps leave more LDS per workgroup; a query that outgrows them is answered by the spill launch, same bits. */
 nmn_status nmn_hnsw_set_heap_capacity(nmn_hnsw* h, uint32_t results, uint32_t candidates);
@@ -1060,6 +1093,15 @@ nmn_status nmn_hnsw_cache_search_sparse(nmn_hnsw* h, const uint64_t* indptr, con
 nmn_status nmn_hnsw_cache_search_device(nmn_hnsw* h, const float* queries_dev, uint32_t nq, uint32_t k, float threshold,
                                         const nmn_xmetric* metric, uint64_t* out_ids_dev, float* out_scores_dev,
                                         uint32_t* out_counts_dev, void* stream);
+/* nmn_hnsw_cache_search_sparse as ONE stream-ordered chain, every buffer in DEVICE memory, no host round trip: the canonicaliser
+ * (nmn_sparse_canonicalise_device), the sparse walk for c candidates, the re-rank on the to_dense() rows — a query with a
+ * duplicated position on its own entries, by the merge kernel — the filtered ordering, and the launch that gives the queries with
+ * a status their sentinel rows.  Answers are nmn_hnsw_cache_search_sparse's bit for bit.  The CSR arguments, the statuses and the
+ * three refusals are nmn_hnsw_search_sparse_device's; the other refusals are nmn_hnsw_cache_search's. */
+nmn_status nmn_hnsw_cache_search_sparse_device(nmn_hnsw* h, const uint64_t* indptr_dev, const uint32_t* positions_dev,
+                                               const float* values_dev, uint32_t nq, uint64_t nnz_total, uint32_t max_nnz, uint32_t k,
+                                               float threshold, const nmn_xmetric* metric, uint64_t* out_ids_dev,
+                                               float* out_scores_dev, uint32_t* out_counts_dev, uint32_t* out_status_dev, void* stream);
 
 /* ---- persistence of the device layout ----------------------------------- */
 

@@ -236,6 +236,10 @@ SIGNATURES = {
     "nmn_hnsw_neighbors": (C.c_int32, [vp, C.c_uint64, C.c_uint32, vp, C.c_uint32, u32p]),
     "nmn_hnsw_search": (C.c_int32, [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.POINTER(SearchStats)]),
     "nmn_hnsw_search_device": (C.c_int32, [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp]),
+    "nmn_sparse_canonicalise_device": (C.c_int32, [C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp, vp,
+                                                   C.c_int32, vp]),
+    "nmn_hnsw_search_sparse_device": (C.c_int32, [vp, vp, vp, vp, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp,
+                                                  vp, vp]),
     "nmn_hnsw_search_multi": (C.c_int32, [vp, vp, C.c_uint32, vp, vp, C.c_uint32, vp, vp, vp, C.POINTER(SearchStats)]),
     "nmn_hnsw_search_sparse": (C.c_int32, [vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.POINTER(SearchStats)]),
     "nmn_hnsw_search_sparse_multi": (C.c_int32, [vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, vp, vp, vp, C.POINTER(SearchStats)]),
@@ -290,6 +294,8 @@ SIGNATURES = {
     "nmn_hnsw_cache_search_sparse": (C.c_int32, [vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_float, C.POINTER(XMetric), vp, vp, vp,
                                                  C.POINTER(SearchStats)]),
     "nmn_hnsw_cache_search_device": (C.c_int32, [vp, vp, C.c_uint32, C.c_uint32, C.c_float, C.POINTER(XMetric), vp, vp, vp, vp]),
+    "nmn_hnsw_cache_search_sparse_device": (C.c_int32, [vp, vp, vp, vp, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_float,
+                                                        C.POINTER(XMetric), vp, vp, vp, vp, vp]),
     "nmn_index_save": (C.c_int32, [vp, C.c_char_p]),
     "nmn_index_load": (C.c_int32, [C.c_char_p, C.POINTER(IndexDesc), C.c_uint64, C.c_uint64, C.POINTER(vp)]),
     "nmn_ivf_save": (C.c_int32, [vp, C.c_char_p]),

@@ -40,6 +40,7 @@ SOURCES = {
     "nmn_hnsw_file.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     "nmn_xmetric.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     "nmn_tt.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
+    "nmn_sparse_canon.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     "nmn_api.hip": [],
     "nmn_sharded.hip": [],
     "nmn_persist.hip": [],

@@ -11,6 +11,7 @@
 //   nmn_hnsw_host.h         the host's distances to a node and the walk templates that build and search both instantiate
 //   nmn_hnsw_build.hip      the host insert, the uploads, the bulk build, the insert entry points
 //   nmn_hnsw_file.hip       save, load
+//   nmn_sparse_canon.hip    sparse queries in device memory canonicalised on the GPU (free of the handle, like nmn_tt.hip)
 //
 // Reference order restated here (docs/hnsw.md has the long form):
 //   simd::dot_product / sum_of_squares / euclidean_distance (hnsw.rs:168-261): eight accumulator chains over whole chunks of
@@ -37,6 +38,8 @@
 //       rounded once, one cast; std's float Sum restated as a left-to-right fold from -0.0), and Cosine takes magnitude() (548-559)
 //       through f64; Euclidean, and every metric's dot on a quantized handle, go through to_dense() (400-406).  docs/hnsw.md §13.
 //   nmn_hnsw_search_sparse_multi: the same with a k and an ef per query; both ride the request coalescer, a query kind per slot (§14).
+//   nmn_hnsw_search_sparse_device / nmn_hnsw_cache_search_sparse_device: the CSR in DEVICE memory, made SparseVectors by
+//       nmn_sparse_canon.hip on the caller's stream, then the same walk (and §16's re-rank) with nothing read back.  docs/hnsw.md §22.
 //   nmn_hnsw_insert_sparse / nmn_hnsw_insert_auto (hnsw.rs:1660-1680): EmbeddingStorage::Sparse nodes beside Dense ones on a dense
 //       handle.  A sparse node is scored by SparseVector's own arithmetic — dot_dense / dot / magnitude / euclidean_distance /
 //       cosine_similarity / cosine_distance_dense, f64 chains over the stored entries — on the query side and on the pruning side;
@@ -570,6 +573,7 @@ extern "C" nmn_status nmn_hnsw_destroy(nmn_hnsw* h) {
         drop(s->ttq);
         drop(s->ttmag);
         drop(s->ttkind);
+        for (DevBuf* b : {&s->sq_off, &s->sq_ent, &s->sq_mag, &s->sq_dup, &s->sq_dense, &s->sq_status}) drop(*b);
     }
     for (DevBuf* b : {&h->d_l0, &h->d_l0cnt, &h->d_upidx, &h->d_up, &h->d_upcnt, &h->d_nrec, &h->d_nent, &h->d_live, &h->bk_lv, &h->bk_vis, &h->bk_out, &h->bk_patch, &h->hq, &h->hids, &h->hsc, &h->hcnt, &h->hkef,
                        &h->hsp_off, &h->hsp_ent, &h->hqmag,
@@ -1609,6 +1613,149 @@ extern "C" nmn_status nmn_hnsw_cache_search_sparse(nmn_hnsw* h, const uint64_t* 
         stats->candidates_rescored = rescored;
     }
     return NMN_OK;
+}
+
+// ---- sparse queries in DEVICE memory (docs/hnsw.md §22) ------------------------------------------------------------------------------
+namespace {
+
+// What the host entries route to the host's walk (sparse_query_host_only) and a stream-ordered entry therefore cannot serve: known
+// from the handle alone, refused before anything is enqueued.  (The third case, a QUERY with a duplicated position on a handle with
+// sparse nodes, only the device sees: status 3.)  Caller holds rw.
+nmn_status refuse_sparse_device(const nmn_hnsw* h, const char* entry) {
+    if (!h->n_sparse) return NMN_OK;
+    char buf[320];
+    if (h->cfg.distance_metric == NMN_METRIC_EUCLIDEAN) {
+        snprintf(buf, sizeof buf,
+                 "HNSW: %s is not served on a handle with sparse nodes under Euclidean (the union merge is walked on the host: the "
+                 "host-buffer entry serves it)", entry);
+        return set_error(NMN_ERR_CONFIGURATION, buf);
+    }
+    if (h->n_sparse_dup > 0) {
+        snprintf(buf, sizeof buf,
+                 "HNSW: %s is not served on a handle with a sparse node that holds a duplicated position (the merge with it is walked "
+                 "on the host: the host-buffer entry serves it)", entry);
+        return set_error(NMN_ERR_CONFIGURATION, buf);
+    }
+    return NMN_OK;
+}
+
+// The canonicaliser on s into the stream's scratch: offsets, entries, magnitudes, duplicate flags, with `dense` the to_dense() rows,
+// the statuses into status_dev (null: the scratch's own; *status: where they are).  Caller holds rw (shared) and sc->mu.
+nmn_status enqueue_canon_locked(nmn_hnsw* h, nmn_hnsw::Scratch* sc, const uint64_t* indptr_dev, const uint32_t* positions_dev,
+                                const float* values_dev, uint32_t nq, uint64_t nnz_total, uint32_t max_nnz, bool dense,
+                                uint32_t* status_dev, const uint32_t** status, hipStream_t s) {
+    bool synced = false;
+    HN_TRY(grow(sc->sq_off, ((size_t)nq + 1) * 8, s, &synced));
+    HN_TRY(grow(sc->sq_ent, std::max<size_t>(nnz_total, 1) * 8, s, &synced));
+    HN_TRY(grow(sc->sq_mag, (size_t)nq * 4, s, &synced));
+    HN_TRY(grow(sc->sq_dup, (size_t)nq * 4, s, &synced));
+    if (dense) HN_TRY(grow(sc->sq_dense, (size_t)nq * h->dim * 4, s, &synced));
+    if (!status_dev) {
+        HN_TRY(grow(sc->sq_status, (size_t)nq * 4, s, &synced));
+        status_dev = (uint32_t*)sc->sq_status.p;
+    }
+    *status = status_dev;
+    // on a handle with sparse nodes (Cosine / DotProduct by now) a query with a duplicated position is not walked: status 3
+    return launch_sparse_canon(h->dim, indptr_dev, positions_dev, values_dev, nq, nnz_total, max_nnz, h->n_sparse > 0,
+                               (uint64_t*)sc->sq_off.p, (uint32_t*)sc->sq_ent.p, (float*)sc->sq_mag.p, (uint32_t*)sc->sq_dup.p,
+                               dense ? (float*)sc->sq_dense.p : nullptr, status_dev, s);
+}
+
+// The walk of the canonical queries in the stream's scratch, routed as sparse_route says: the launch a lone nmn_hnsw_search_sparse
+// call makes, its query region sized by the caller's bound instead of the call's largest count (no answer depends on it: cand_cap).
+nmn_status enqueue_sparse_walk_locked(nmn_hnsw* h, nmn_hnsw::Scratch* sc, uint32_t nq, uint32_t k, uint32_t ef, uint32_t max_nnz,
+                                      uint64_t* o_ids, float* o_sc, uint32_t* o_cnt, hipStream_t s) {
+    const SparseRoute route = sparse_route(h);
+    WalkShape w = uniform_shape(h, nq, k, ef);
+    w.qkind = (int)route;
+    if (route != kSparseDensify) w.qmag = (const float*)sc->sq_mag.p;
+    if (route == kSparseGather) {
+        w.sp_off = (const uint64_t*)sc->sq_off.p;
+        w.sp_ent = (const uint2*)sc->sq_ent.p;
+        w.sp_max = max_nnz;
+    }
+    return enqueue_walk_locked(h, sc, route == kSparseGather ? nullptr : (const float*)sc->sq_dense.p, nq, w, o_ids, o_sc, o_cnt, s);
+}
+
+bool sparse_csr_null(const uint64_t* indptr_dev, const uint32_t* positions_dev, const float* values_dev, uint64_t nnz_total) {
+    return !indptr_dev || (nnz_total && (!positions_dev || !values_dev));
+}
+
+}  // namespace
+
+// nmn_hnsw_search_sparse with the CSR and every output in DEVICE memory (docs/hnsw.md §22): the canonicaliser's three launches, the
+// walk's two per chunk, and one that gives the queries with a status their sentinel rows.
+extern "C" nmn_status nmn_hnsw_search_sparse_device(nmn_hnsw* h, const uint64_t* indptr_dev, const uint32_t* positions_dev,
+                                                    const float* values_dev, uint32_t nq, uint64_t nnz_total, uint32_t max_nnz, uint32_t k,
+                                                    uint32_t ef, uint64_t* out_ids_dev, float* out_scores_dev, uint32_t* out_counts_dev,
+                                                    uint32_t* out_status_dev, void* stream) {
+    uint32_t mx = 0;
+    if (const nmn_status sm = sparse_max_nnz(h ? h->dim : 0, max_nnz, &mx); sm != NMN_OK) return sm;
+    if (!h) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (const nmn_status sb = refuse_binary(h, "nmn_hnsw_search_sparse_device", kBinQueries); sb != NMN_OK) return sb;
+    if (k == 0) return set_error(NMN_ERR_INVALID_TOP_K, "k == 0");
+    if (nq == 0) return NMN_OK;
+    if (sparse_csr_null(indptr_dev, positions_dev, values_dev, nnz_total) || !out_ids_dev || !out_scores_dev || !out_counts_dev)
+        return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    std::shared_lock<std::shared_mutex> g(h->rw);
+    if (const nmn_status sr = refuse_sparse_device(h, "nmn_hnsw_search_sparse_device"); sr != NMN_OK) return sr;
+    HN_TRY(hipSetDevice(h->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    nmn_hnsw::Scratch* sc = scratch_of(h, s);
+    {
+        std::lock_guard<std::mutex> slk(sc->mu);  // grow, canonicalise, walk and the status rows as one unit on this stream
+        const uint32_t* status = nullptr;
+        nmn_status st = enqueue_canon_locked(h, sc, indptr_dev, positions_dev, values_dev, nq, nnz_total, mx,
+                                             sparse_route(h) != kSparseGather, out_status_dev, &status, s);
+        if (st != NMN_OK) return st;
+        st = enqueue_sparse_walk_locked(h, sc, nq, k, ef, mx, out_ids_dev, out_scores_dev, out_counts_dev, s);
+        if (st != NMN_OK) return st;
+        st = launch_sparse_status_rows(status, nq, k, out_ids_dev, out_scores_dev, out_counts_dev, s);
+        if (st != NMN_OK) return st;
+    }
+    return record_search(h, s);
+}
+
+// nmn_hnsw_cache_search_sparse as one stream-ordered chain (docs/hnsw.md §22): canonicalise, the sparse walk for c candidates into
+// the stream's candidate block, the re-rank on the to_dense() rows — a query with a duplicated position on its own entries, where
+// the canonicaliser left them — the filtered ordering, the status rows.
+extern "C" nmn_status nmn_hnsw_cache_search_sparse_device(nmn_hnsw* h, const uint64_t* indptr_dev, const uint32_t* positions_dev,
+                                                          const float* values_dev, uint32_t nq, uint64_t nnz_total, uint32_t max_nnz,
+                                                          uint32_t k, float threshold, const nmn_xmetric* metric, uint64_t* out_ids_dev,
+                                                          float* out_scores_dev, uint32_t* out_counts_dev, uint32_t* out_status_dev,
+                                                          void* stream) {
+    uint32_t mx = 0;
+    if (const nmn_status sm = sparse_max_nnz(h ? h->dim : 0, max_nnz, &mx); sm != NMN_OK) return sm;
+    nmn_status st = check_cache_call(h, k, metric);
+    if (st != NMN_OK) return st;
+    if (nq == 0) return NMN_OK;
+    if (sparse_csr_null(indptr_dev, positions_dev, values_dev, nnz_total) || !out_ids_dev || !out_scores_dev || !out_counts_dev)
+        return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    std::shared_lock<std::shared_mutex> g(h->rw);
+    if (const nmn_status sr = refuse_sparse_device(h, "nmn_hnsw_cache_search_sparse_device"); sr != NMN_OK) return sr;
+    const uint32_t c = (uint32_t)cache_candidates(h, k);
+    HN_TRY(hipSetDevice(h->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    nmn_hnsw::Scratch* sc = scratch_of(h, s);
+    {
+        std::lock_guard<std::mutex> slk(sc->mu);
+        st = metric_scratch(sc, s, nq, c, k, true);
+        if (st != NMN_OK) return st;
+        const uint32_t* status = nullptr;
+        st = enqueue_canon_locked(h, sc, indptr_dev, positions_dev, values_dev, nq, nnz_total, mx, true, out_status_dev, &status, s);
+        if (st != NMN_OK) return st;
+        st = enqueue_sparse_walk_locked(h, sc, nq, c, 0, mx, (uint64_t*)sc->xids.p, (float*)sc->xsc.p, (uint32_t*)sc->xcnt.p, s);
+        if (st != NMN_OK) return st;
+        XmetricFilter flt = cache_filter(h, threshold);
+        flt.q_off = (const uint64_t*)sc->sq_off.p;
+        flt.q_ent = (const uint2*)sc->sq_ent.p;
+        flt.q_use = (const uint32_t*)sc->sq_dup.p;
+        st = enqueue_rerank(h, sc, (const float*)sc->sq_dense.p, nq, c, k, *metric, out_ids_dev, out_scores_dev, out_counts_dev, s, &flt);
+        if (st != NMN_OK) return st;
+        st = launch_sparse_status_rows(status, nq, k, out_ids_dev, out_scores_dev, out_counts_dev, s);
+        if (st != NMN_OK) return st;
+    }
+    return record_search(h, s);
 }
 
 // ---- tensor-train queries and insert_tt_vector (hnsw.rs:1196-1221, 1755-1759, 1811-1903, 2238-2272; docs/hnsw.md §17) ---------------

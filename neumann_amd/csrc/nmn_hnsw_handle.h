@@ -99,6 +99,9 @@ struct nmn_hnsw {
         bool xsort_use = false;  // this call's ordering goes through the large-k sort (xmetric_order_scratch_bytes != 0)
         DevBuf xids, xsc, xcnt, xsim, xsort;  // nmn_hnsw_search_metric*: the walk's nq x c candidate block, its re-rank scores, the sort's scratch
         DevBuf ttq, ttmag, ttkind;  // nmn_hnsw_search_tt*: the reconstructed queries, their magnitudes, kind and candidate limit per query
+        // nmn_hnsw_search_sparse_device / nmn_hnsw_cache_search_sparse_device (docs/hnsw.md §22): what the canonicaliser leaves of the
+        // call's queries — offsets [nq + 1], packed (position, value bits) pairs, magnitudes, duplicate flags, to_dense() rows, statuses
+        DevBuf sq_off, sq_ent, sq_mag, sq_dup, sq_dense, sq_status;
     };
     std::vector<std::unique_ptr<Scratch>> scratch;
     std::vector<hipEvent_t> ev_pending, ev_free;
@@ -173,6 +176,17 @@ nmn_status create_handle(const nmn_hnsw_config* cfg, int storage, uint32_t dim, 
 nmn_status canonicalise_sparse(uint32_t dim, const uint64_t* indptr, const uint32_t* positions, const float* values, uint32_t nq,
                                SparseQueries* out);
 nmn_status wait_in_flight(nmn_hnsw* h);
+// nmn_sparse_canon.hip (docs/hnsw.md §22).  The canonicaliser: three launches on s over a CSR in DEVICE memory, max_nnz already
+// resolved by sparse_max_nnz; entries_dev holds nnz_total (position, value bits) pairs; dup_dev / dense_dev nullable; refuse_dup: a
+// query with a duplicated position gets status 3 and is canonicalised as the entry-less query like every other status.
+nmn_status launch_sparse_canon(uint32_t dim, const uint64_t* indptr_dev, const uint32_t* positions_dev, const float* values_dev,
+                               uint32_t nq, uint64_t nnz_total, uint32_t max_nnz, bool refuse_dup, uint64_t* off_dev, uint32_t* entries_dev,
+                               float* mag_dev, uint32_t* dup_dev, float* dense_dev, uint32_t* status_dev, hipStream_t s);
+// One launch: the rows [k] of the queries whose status is not 0 become count 0, ids UINT64_MAX, scores -inf.
+nmn_status launch_sparse_status_rows(const uint32_t* status_dev, uint32_t nq, uint32_t k, uint64_t* ids_dev, float* scores_dev,
+                                     uint32_t* counts_dev, hipStream_t s);
+// max_nnz as the entries take it: above kSparseLdsEntries NMN_ERR_INVALID_ARGUMENT, 0 = min(dim, kSparseLdsEntries)
+nmn_status sparse_max_nnz(uint32_t dim, uint32_t max_nnz, uint32_t* out);
 nmn_status upload_graph(nmn_hnsw* h, size_t reserve_n = 0, uint32_t reserve_upper = 0, uint32_t layers = 0);
 nmn_status upload_codes(nmn_hnsw* h, uint64_t first, uint64_t count);
 nmn_status alloc_codes(nmn_hnsw* h, uint64_t cap, uint64_t have);

@@ -112,6 +112,56 @@ def _device_out(out, nq, k, device):
             torch.empty((nq,), dtype=torch.int32, device=device))
 
 
+def _device_csr(indptr_t, positions_t, values_t):
+    """the CSR of a sparse _device call checked -> (indptr, positions, values, nq, nnz_total): contiguous device tensors, int64
+    indptr [nq + 1] read as u64, int32 positions read as u32, float32 values of the same length"""
+    import torch
+
+    for t, dt, what in ((indptr_t, torch.int64, "indptr must be a contiguous int64 device tensor [nq + 1]"),
+                        (positions_t, torch.int32, "positions must be a contiguous int32 device tensor"),
+                        (values_t, torch.float32, "values must be a contiguous float32 device tensor")):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.is_contiguous() and t.dim() == 1):
+            raise _capi.NeumannGpuError(_capi.ERR_INVALID_ARGUMENT, what)
+    if indptr_t.numel() < 1 or positions_t.numel() != values_t.numel():
+        raise _capi.NeumannGpuError(_capi.ERR_INVALID_ARGUMENT, "indptr is [nq + 1]; positions and values have one length")
+    return indptr_t, positions_t, values_t, indptr_t.numel() - 1, positions_t.numel()
+
+
+def _device_status(status, nq, device):
+    """`status` of a sparse _device call (int32 [nq]), or one allocated on `device`"""
+    import torch
+
+    return status if status is not None else torch.empty((nq,), dtype=torch.int32, device=device)
+
+
+def sparse_canonicalise_device(dim, indptr_t, positions_t, values_t, max_nnz=None, dense=True, stream=None):
+    """SparseVector::try_from_parts, magnitude and to_dense of CSR queries in torch device tensors, in stream order
+    (nmn_sparse_canonicalise_device; docs/hnsw.md §22): int64 `indptr_t` [nq + 1] read as u64, int32 `positions_t` read as u32,
+    float32 `values_t`; `max_nnz`: the bound on one query's raw entries (None: min(dim, 4096)).  Enqueued on `stream` (None:
+    torch's current stream), nothing is read back.  Returns a dict of device tensors: off int64 [nq + 1], entries int32 [nnz, 2]
+    ({position, value bits}, the first off[nq] rows are written), mag f32 [nq], dup int32 [nq], dense f32 [nq, dim] (None with
+    `dense` false), status int32 [nq] (0 served, 1 a position >= dim, 2 the range or the count)."""
+    import torch
+
+    ip, pos, val, nq, nnz = _device_csr(indptr_t, positions_t, values_t)
+    dev, dim = ip.device, int(dim)
+    out = {
+        "off": torch.empty((nq + 1,), dtype=torch.int64, device=dev),
+        "entries": torch.empty((max(nnz, 1), 2), dtype=torch.int32, device=dev),
+        "mag": torch.empty((nq,), dtype=torch.float32, device=dev),
+        "dup": torch.empty((nq,), dtype=torch.int32, device=dev),
+        "dense": torch.empty((nq, dim), dtype=torch.float32, device=dev) if dense else None,
+        "status": torch.empty((nq,), dtype=torch.int32, device=dev),
+    }
+    _capi.check(_capi.load().nmn_sparse_canonicalise_device(
+        dim, C.c_void_p(ip.data_ptr()), C.c_void_p(pos.data_ptr()), C.c_void_p(val.data_ptr()), nq, nnz,
+        0 if max_nnz is None else int(max_nnz), C.c_void_p(out["off"].data_ptr()), C.c_void_p(out["entries"].data_ptr()),
+        C.c_void_p(out["mag"].data_ptr()), C.c_void_p(out["dup"].data_ptr()),
+        C.c_void_p(out["dense"].data_ptr()) if dense else None, C.c_void_p(out["status"].data_ptr()),
+        dev.index if dev.index is not None else -1, _stream_ptr(stream)))
+    return out
+
+
 class HNSWBuildOptions:
     """HNSWBuildOptions (vector_engine/src/lib.rs:848-932): a storage strategy ("dense", "auto", "quantized") and an HNSWConfig."""
 
@@ -475,6 +525,23 @@ class GpuHnsw:
             C.c_void_p(sc.data_ptr()), C.c_void_p(counts.data_ptr()), _stream_ptr(stream)))
         return ids, sc, counts
 
+    def search_sparse_device(self, indptr_t, positions_t, values_t, k, ef=None, max_nnz=None, out=None, status=None, stream=None):
+        """`search_sparse` with torch device tensors, in stream order (nmn_hnsw_search_sparse_device; docs/hnsw.md §22): int64
+        `indptr_t` [nq + 1] read as u64, int32 `positions_t` read as u32, float32 `values_t`, canonicalised on the GPU; `max_nnz`:
+        the bound on one query's raw entries, at most 4096 (None: min(dim, 4096)).  Enqueued on `stream` (None: torch's current
+        stream), returns without waiting.  Returns (ids, scores, counts, status): the first three as `search_device` returns them
+        (`out` supplies them), status int32 [nq] (`status` supplies it): 0 served, 1 a position >= dim, 2 the range or the count,
+        3 a duplicated position on an index with sparse nodes — the row of a query with a status is count 0 with the sentinels."""
+        ip, pos, val, nq, nnz = _device_csr(indptr_t, positions_t, values_t)
+        k = int(k)
+        ids, sc, counts = _device_out(out, nq, k, ip.device)
+        status = _device_status(status, nq, ip.device)
+        _capi.check(self._lib.nmn_hnsw_search_sparse_device(
+            self._h, C.c_void_p(ip.data_ptr()), C.c_void_p(pos.data_ptr()), C.c_void_p(val.data_ptr()), nq, nnz,
+            0 if max_nnz is None else int(max_nnz), k, 0 if ef is None else int(ef), C.c_void_p(ids.data_ptr()),
+            C.c_void_p(sc.data_ptr()), C.c_void_p(counts.data_ptr()), C.c_void_p(status.data_ptr()), _stream_ptr(stream)))
+        return ids, sc, counts, status
+
     def search_tt(self, tts, k, ef=None, with_stats=False):
         """HNSWIndex::search_tt_with_ef per train (nmn_hnsw_search_tt; ef None: ef_search).  `tts`: one neumann_amd.tt.TTVector or
         several of one shape whose product is the index's dimension.  The trains are reconstructed and their norms taken on the
@@ -646,6 +713,21 @@ class GpuHnsw:
                                                            C.c_void_p(ids.ctypes.data), C.c_void_p(sc.ctypes.data),
                                                            C.c_void_p(counts.ctypes.data), C.byref(st)))
         return (ids, sc, counts, st) if with_stats else (ids, sc, counts)
+
+    def cache_search_sparse_device(self, indptr_t, positions_t, values_t, k, threshold, metric, max_nnz=None, out=None, status=None,
+                                   stream=None):
+        """`cache_search_sparse` with torch device tensors as ONE stream-ordered chain (nmn_hnsw_cache_search_sparse_device): the
+        CSR, `max_nnz`, the returned (ids, similarities, counts, status) and the statuses are `search_sparse_device`'s."""
+        ip, pos, val, nq, nnz = _device_csr(indptr_t, positions_t, values_t)
+        k = int(k)
+        ids, sc, counts = _device_out(out, nq, k, ip.device)
+        status = _device_status(status, nq, ip.device)
+        m = metric._c()
+        _capi.check(self._lib.nmn_hnsw_cache_search_sparse_device(
+            self._h, C.c_void_p(ip.data_ptr()), C.c_void_p(pos.data_ptr()), C.c_void_p(val.data_ptr()), nq, nnz,
+            0 if max_nnz is None else int(max_nnz), k, float(threshold), C.byref(m), C.c_void_p(ids.data_ptr()),
+            C.c_void_p(sc.data_ptr()), C.c_void_p(counts.data_ptr()), C.c_void_p(status.data_ptr()), _stream_ptr(stream)))
+        return ids, sc, counts, status
 
     def cache_search_device(self, queries_t, k, threshold, metric, out=None, stream=None):
         """`cache_search` with torch device tensors, in stream order (nmn_hnsw_cache_search_device); same conventions as

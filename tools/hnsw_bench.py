@@ -58,10 +58,18 @@ nmn_hnsw_search_metric(nq = 1) under that metric instead, top_k taken in turn fr
   python tools/hnsw_bench.py --rows 200000 --dim 128 --sparse-queries 0.8 --index-file PATH
 --sparse-queries FRACTION zeroes that share of every synthetic query's entries and times nmn_hnsw_search_sparse beside
 nmn_hnsw_search of the SAME (densified) queries, the two alternating call by call, at 1 / 64 / 1024 queries per call and ef 50 /
-200 (docs/hnsw.md §13): medians of --calls (a fifth of it at 1024 queries), spread over --repeats.  Both are host-buffer calls —
-nmn_hnsw_search_sparse has no device-buffer entry — so both figures are wall times of the whole call, copies included.  It also
+200 (docs/hnsw.md §13): medians of --calls (a fifth of it at 1024 queries), spread over --repeats.  Both are host-buffer calls,
+so both figures are wall times of the whole call, copies included (--sparse-device times the device-buffer entry).  It also
 prints the stored entries per query, the evaluations per query and the queries the spill launch answered, and checks that the
 sparse call's device and host-walk answers are the same bits and, under Euclidean, the bits of the dense walk.
+
+  timeout -k 10 900 python tools/hnsw_bench.py --rows 200000 --dim 128 --sparse-device --index-file PATH   # once per repetition
+--sparse-device times nmn_hnsw_search_sparse_device (docs/hnsw.md §22) on the queries of --sparse-queries' recipe (--sparse-fraction
+of every entry zeroed, 0.8 by default) held as a CSR in device memory, at 1 / 64 / 1024 queries per call, k = --k, ef 50.  Three calls
+alternate call by call on the same handle: search_sparse_device between two events, search_device of the densified queries
+between two events — the walk without the canonicaliser and the kind-1 scoring — and the host-buffer search_sparse by wall time;
+medians of --calls.  One repetition per process: run it --repeats times, each under its own time limit, and take the spread over
+the lines.  It ends the run unless the device and host answers of the first 64 queries are the same bits.
 
   python tools/hnsw_bench.py --rows 200000 --dim 128 --sparse-callers 64,128 --index-file PATH [--storage quantized]
 --sparse-callers times CONCURRENT sparse callers (docs/hnsw.md §14): for every T of the list, T threads behind a barrier, each making
@@ -629,6 +637,70 @@ def time_tt(g, k, args):
     return r
 
 
+def time_sparse_device(g, Q, k, args):
+    """--sparse-device (docs/hnsw.md §22): the queries of --sparse-queries' recipe (--sparse-fraction of every entry zeroed) as a CSR
+    in device memory.  Three calls alternate call by call on the same handle: search_sparse_device between two events, search_device
+    of the densified queries between two events — the walk without the new stage — and the host-buffer search_sparse by wall time.
+    ef 50.  The device and host answers of the first 64 queries must be the same bits."""
+    import torch
+    rng = np.random.default_rng(0x5BA)
+    Q = Q.copy()
+    Q[rng.random(Q.shape) < args.sparse_fraction] = 0.0
+    csr = g.sparse_from_dense(Q)
+    ef = 50
+    r = {"sparse_fraction": args.sparse_fraction, "entries_per_query": round(float(csr[1].size) / Q.shape[0], 1), "ef": ef}
+
+    def part(nq):
+        e = int(csr[0][nq])
+        return csr[0][:nq + 1], csr[1][:e], csr[2][:e]
+
+    s = torch.cuda.Stream()
+    qd = torch.from_numpy(Q).cuda()
+    dev, dcsr = {}, {}
+    for nq in (1, 64, 1024):  # warm every shape
+        ip, pos, val = part(nq)
+        dcsr[nq] = (torch.from_numpy(ip.astype(np.int64)).cuda(), torch.from_numpy(pos.view(np.int32)).cuda(), torch.from_numpy(val).cuda())
+        dev[nq] = tuple((torch.empty((nq, k), dtype=torch.int64, device="cuda"), torch.empty((nq, k), dtype=torch.float32, device="cuda"),
+                         torch.empty((nq,), dtype=torch.int32, device="cuda")) for _ in range(2))
+        dev[nq] += (torch.empty((nq,), dtype=torch.int32, device="cuda"),)
+        g.search_sparse_device(*dcsr[nq], k, ef, out=dev[nq][0], status=dev[nq][2], stream=s)
+        g.search_device(qd[:nq], k, ef, out=dev[nq][1], stream=s)
+        g.search_sparse(*part(nq), k, ef)
+    s.synchronize()
+    ids, sc, cnt = g.search_sparse(*part(64), k, ef)
+    same = np.array_equal(dev[64][0][0].cpu().numpy().view(np.uint64), ids) and \
+        np.array_equal(dev[64][0][1].cpu().numpy().view(np.uint32), sc.view(np.uint32)) and \
+        np.array_equal(dev[64][0][2].cpu().numpy().view(np.uint32), cnt) and not bool(dev[64][2].any())
+    r["device_and_host_entries_agree"] = bool(same)
+    if not same:
+        raise SystemExit("search_sparse_device and search_sparse disagree")
+    for nq, calls in ((1, args.calls), (64, args.calls), (1024, args.calls)):
+        p = part(nq)
+        sp_ev, de_ev, host = [], [], []
+        for _ in range(calls):
+            e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+            e0.record(s)
+            g.search_sparse_device(*dcsr[nq], k, ef, out=dev[nq][0], status=dev[nq][2], stream=s)
+            e1.record(s)
+            g.search_device(qd[:nq], k, ef, out=dev[nq][1], stream=s)
+            e2.record(s)
+            s.synchronize()
+            t0 = time.perf_counter()
+            g.search_sparse(*p, k, ef)
+            host.append((time.perf_counter() - t0) * 1e3)
+            sp_ev.append((e0, e1))
+            de_ev.append((e1, e2))
+        t_sp = np.array([a.elapsed_time(b) for a, b in sp_ev])
+        t_de = np.array([a.elapsed_time(b) for a, b in de_ev])
+        r[f"nq{nq}"] = {"calls": calls, "sparse_device_call_ms": round(float(np.median(t_sp)), 5),
+                        "dense_device_call_ms": round(float(np.median(t_de)), 5),
+                        "sparse_minus_dense_call_ms": round(float(np.median(t_sp - t_de)), 5),
+                        "sparse_minus_dense_call_ms_p10_p90": [round(float(x), 5) for x in np.percentile(t_sp - t_de, [10, 90])],
+                        "host_entry_call_ms": round(float(np.median(host)), 5),
+                        "host_entry_over_sparse_device": round(float(np.median(host) / np.median(t_sp)), 3)}
+    return r
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1_000_000)
@@ -661,6 +733,9 @@ def main():
     ap.add_argument("--sparse-node-fraction", type=float, default=None,
                     help="insert this share of the rows Sparse (nmn_hnsw_insert_sparse) and time search_device / search_sparse of the "
                          "mixed handle beside an all-dense handle over the to_dense() rows (docs/hnsw.md §15)")
+    ap.add_argument("--sparse-device", action="store_true",
+                    help="time search_sparse_device against search_device of the densified queries and the host-buffer search_sparse, "
+                         "alternating call by call (docs/hnsw.md §22); --sparse-fraction of every entry zeroed; one repetition per process")
     ap.add_argument("--tt-queries", default=None,
                     help="SHAPE:RANK, e.g. 4,4,8:8 — time search_tt_device against search_device with as many dense queries on the "
                          "same handle, alternating call by call (docs/hnsw.md §17); one repetition per process")
@@ -748,6 +823,12 @@ def main():
         out["storage"] = args.storage
         with build_or_load(args.index_file, n, d, cfg, args.storage, out) as g:
             out.update(time_tt(g, k, args))
+        print(json.dumps(out), flush=True)
+        return
+    if args.sparse_device:
+        out["storage"] = args.storage
+        with build_or_load(args.index_file, n, d, cfg, args.storage, out) as g:
+            out.update(time_sparse_device(g, Q, k, args))
         print(json.dumps(out), flush=True)
         return
     if args.sparse_queries is not None:
