@@ -956,6 +956,57 @@ nmn_status nmn_tt_decompose_limits(uint32_t* max_cores, uint32_t* max_rank, uint
 /* The LDS floats a config needs on the device; UINT64_MAX for a config above the limits, 0 for one the entries refuse */
 uint64_t nmn_tt_decompose_lds_floats(const uint32_t* shape, uint32_t n_cores, uint32_t max_rank);
 
+/* ---- tt_dot_product, tt_cosine_similarity, tt_euclidean_distance: trains compared without reconstruction (docs/hnsw.md §23) - */
+
+#define NMN_TT_SIM_DOT 0u       /* tt_dot_product (tensor_train.rs:480-516) */
+#define NMN_TT_SIM_COSINE 1u    /* tt_cosine_similarity (522-532): 0.0 when either tt_norm is < 1e-10, else dot / (norm_a * norm_b) */
+#define NMN_TT_SIM_EUCLIDEAN 2u /* tt_euclidean_distance (539-546): sqrt(max(fma(-2, dot_ab, dot_aa + dot_bb), 0)); a NaN gives 0.0 */
+
+/* out[nq][nt]: out[i][j] = the reference's function of (query i, target j), in that argument order, bit for bit — the Gram
+ * contraction new_gram[x r2b + y] = one chain from +0.0 over k, ia, ib of sum + ((gram[ia r1b + ib] * A[ia,k,x]) * B[ib,k,y]), every
+ * product and add rounded on its own; tt_dot_product(a, b) and tt_dot_product(b, a) differ in bits, and so do both from the dense
+ * dot of the reconstructions.  Each set crosses as nmn_tt_norm's arguments and is checked by its rules (NMN_ERR_INVALID_ARGUMENT,
+ * the text naming the set, the train and the rule); sets whose n_cores or modes differ are the reference's IncompatibleShapes:
+ * NMN_ERR_INVALID_ARGUMENT, "incompatible TT shapes for operation" (the batch forms of the reference fail as a whole in the same
+ * way); an unknown op is NMN_ERR_INVALID_ARGUMENT.  Nothing is written on any error; nq == 0 or nt == 0 returns NMN_OK and writes
+ * nothing.  tt_dot_product(t, t) — the chain tt_norm runs before its square root — is computed once per train per call, never once
+ * per pair.  HOST buffers, synchronous, stateless, on the current device: a workgroup stages one query's cores in LDS, each of its
+ * waves walks one (query, target) pair at a time, the lanes sharing out the outputs of a Gram matrix; no chain is split.  A pair
+ * with a train above nmn_tt_limits (max_cores, max_rank, max_storage; max_level does not apply) is computed by the host
+ * restatement of the same loops, same bits; so is every pair under NMN_HNSW_HOST_SEARCH=1 and every call of fewer than
+ * NMN_TT_SIMILARITY_MIN pairs (environment, read at every call; default 32, the measured crossover).  The choice never depends on a core's value. */
+nmn_status nmn_tt_similarity(uint32_t op, const uint32_t* shape_q, uint32_t n_cores_q, const uint32_t* ranks_q,
+                             const uint64_t* core_off_q, const float* cores_q, uint32_t nq, const uint32_t* shape_t,
+                             uint32_t n_cores_t, const uint32_t* ranks_t, const uint64_t* core_off_t, const float* cores_t, uint32_t nt,
+                             float* out);
+/* out[i] = tt_dot_product(t_i, t_i); sqrt(out[i]) has the bits of nmn_tt_norm.  HOST buffers, nmn_tt_similarity's checks and routing
+ * (NMN_TT_SIMILARITY_MIN counts trains here). */
+nmn_status nmn_tt_self_dot(const uint32_t* shape, uint32_t n_cores, const uint32_t* ranks, const uint64_t* core_off, const float* cores,
+                           uint32_t n, float* out);
+/* The same with every array but `shape` in DEVICE memory, enqueued on `stream` and not waited for, nothing read back, nothing
+ * allocated — the layout nmn_tt_decompose_device leaves: ranks_dev [n][n_cores + 1] per train; train i's cores at core_off_dev[i]
+ * (core_off_dev [n + 1]) or, when core_off_dev is null, at i * stride; no train holds more than `stride` floats (its slot:
+ * nmn_tt_max_storage of the config) and cores_dev holds n * stride floats; status_dev [n] nullable (nmn_tt_decompose_device's).
+ * n_cores above 8, a mode of 0 and a stride of 0 or above nmn_tt_limits' max_storage are NMN_ERR_INVALID_ARGUMENT: there is no host
+ * to fall back to.  The ranks cannot be checked by the host, so the kernel checks them before it reads through them.  A train is
+ * BAD when its status is not NMN_TT_OK, ranks[0] or ranks[n_cores] is not 1, a rank is 0 or above nmn_tt_limits' max_rank, its
+ * core floats are more than `stride` (or than core_off_dev[i + 1] - core_off_dev[i]), or they would leave the n * stride floats of
+ * cores_dev.  A bad train leaves the quiet NaN 0x7FC00000 in every output it takes part in; no load or store leaves the buffers
+ * described here. */
+nmn_status nmn_tt_self_dot_device(const uint32_t* shape, uint32_t n_cores, const uint32_t* ranks_dev, const uint64_t* core_off_dev,
+                                  const float* cores_dev, uint64_t stride, const uint32_t* status_dev, uint32_t n, float* out_dev,
+                                  void* stream);
+/* nmn_tt_similarity on two sets in DEVICE memory, each as nmn_tt_self_dot_device takes it: out_dev[nq][nt].  self_q_dev [nq] and
+ * self_t_dev [nt] are what nmn_tt_self_dot_device wrote for the sets — required for NMN_TT_SIM_COSINE and NMN_TT_SIM_EUCLIDEAN,
+ * ignored for NMN_TT_SIM_DOT — so targets that stay resident pay for their self dots once, not once per call (TTVectorCached,
+ * tensor_store/src/hnsw.rs:276-289).  Enqueued on `stream`, not waited for, nothing read back, nothing allocated. */
+nmn_status nmn_tt_similarity_device(uint32_t op, const uint32_t* shape, uint32_t n_cores, const uint32_t* ranks_q_dev,
+                                    const uint64_t* core_off_q_dev, const float* cores_q_dev, uint64_t stride_q,
+                                    const uint32_t* status_q_dev, uint32_t nq, const uint32_t* ranks_t_dev,
+                                    const uint64_t* core_off_t_dev, const float* cores_t_dev, uint64_t stride_t,
+                                    const uint32_t* status_t_dev, uint32_t nt, const float* self_q_dev, const float* self_t_dev,
+                                    float* out_dev, void* stream);
+
 /* HNSWIndex::search_tt (hnsw.rs:1796-1801) per query: tt_decompose(query, config); Ok: search_tt_with_ef(tt, k, ef_search) — what
  * nmn_hnsw_search_tt returns for the train nmn_tt_decompose makes, Cosine whatever the handle's metric; Err of any kind:
  * search(query, k) — what nmn_hnsw_search returns, under the handle's metric.  The three argument errors of tt_decompose therefore

@@ -271,6 +271,11 @@ SIGNATURES = {
                                             C.c_uint64, vp]),
     "nmn_tt_decompose_limits": (C.c_int32, [u32p, u32p, u32p, u32p]),
     "nmn_tt_decompose_lds_floats": (C.c_uint64, [vp, C.c_uint32, C.c_uint32]),
+    "nmn_tt_similarity": (C.c_int32, [C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp]),
+    "nmn_tt_self_dot": (C.c_int32, [vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp]),
+    "nmn_tt_self_dot_device": (C.c_int32, [vp, C.c_uint32, vp, vp, vp, C.c_uint64, vp, C.c_uint32, vp, vp]),
+    "nmn_tt_similarity_device": (C.c_int32, [C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_uint64, vp, C.c_uint32, vp, vp, vp, C.c_uint64,
+                                             vp, C.c_uint32, vp, vp, vp, vp]),
     "nmn_hnsw_search_tt_dense": (C.c_int32, [vp, vp, C.c_uint32, C.c_uint64, vp, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, vp,
                                              vp, vp, C.POINTER(SearchStats)]),
     "nmn_hnsw_insert_tt_dense": (C.c_int32, [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint32, C.c_float, vp]),

@@ -101,4 +101,38 @@ bool tt_decompose_on_host(const TTDecConfig& c, uint64_t n);
 nmn_status launch_tt_decompose(const TTDecConfig& c, const float* vectors_dev, uint64_t n, uint32_t* status_dev, uint32_t* ranks_dev,
                                float* cores_dev, uint64_t* core_off_dev, hipStream_t s);
 
+// ---- tt_dot_product, tt_cosine_similarity, tt_euclidean_distance (tensor_train.rs:480-546), docs/hnsw.md §23 -------------------
+
+// The device path compares trains within kTTMaxCores, kTTMaxRank and kTTMaxStorage (kTTMaxLevel does not apply: nothing is
+// reconstructed).  A workgroup keeps one query's cores and, per wave, two Gram matrices in dynamic LDS, under the 64 KiB a
+// workgroup may ask for without an attribute.
+constexpr uint32_t kTTSimMaxLdsFloats = 16368;  // (16 floats short of 64 KiB: the kernel's static LDS)
+constexpr uint32_t kTTSimGridMax = 2048;        // workgroups of one launch (NMN_TT_SIMILARITY_GRID), the work beyond in a stride loop
+constexpr uint32_t kTTSimMinDefault = 32;       // NMN_TT_SIMILARITY_MIN: calls of fewer pairs are the host's (measured, docs/hnsw.md §23)
+
+// tt_dot_product of two trains of one shape on the host, the reference's loops restated; with a == b the chain of tt_norm
+float tt_dot_host(const uint32_t* shape, uint32_t n_cores, const uint32_t* ranks_a, const float* cores_a, const uint32_t* ranks_b,
+                  const float* cores_b);
+
+// One set of n trains in DEVICE memory: per-train ranks [n][n_cores + 1]; train i's cores at core_off_dev[i] (core_off_dev [n + 1]),
+// or at i * stride when core_off_dev is null; no train holds more than `stride` floats and the buffer holds `cap`.  status_dev
+// (nullable): NMN_TT_OK per good train.  skip_dev (nullable): 1 = nothing this train takes part in is computed or written.
+// max_rank: the largest rank of any train that is not skipped, kTTMaxRank when the host cannot know.  The kernels check every
+// train against all of this before they read through its ranks; a train that fails leaves the quiet NaN 0x7FC00000.
+struct TTSimSet {
+    const uint32_t* ranks_dev = nullptr;
+    const uint64_t* core_off_dev = nullptr;
+    const float* cores_dev = nullptr;
+    const uint32_t* status_dev = nullptr;
+    const uint8_t* skip_dev = nullptr;
+    uint64_t stride = 0, cap = 0;
+    uint32_t n = 0, max_rank = kTTMaxRank;
+};
+// out_dev[i] = tt_dot_product(t_i, t_i), one launch on `s`
+hipError_t launch_tt_self_dot(const uint32_t* shape, uint32_t n_cores, const TTSimSet& set, float* out_dev, hipStream_t s);
+// out_dev[q.n][t.n] = op (NMN_TT_SIM_*) of (query i, target j), one launch on `s`; self_*_dev: what launch_tt_self_dot wrote, read
+// for cosine and Euclidean only
+hipError_t launch_tt_similarity(uint32_t op, const uint32_t* shape, uint32_t n_cores, const TTSimSet& q, const TTSimSet& t,
+                                const float* self_q_dev, const float* self_t_dev, float* out_dev, hipStream_t s);
+
 }  // namespace nmn

@@ -1,6 +1,7 @@
 // nmn_tt.hip — tensor-train vectors prepared on the GPU: tt_reconstruct (tensor_compress/src/tensor_train.rs:401-436) and tt_norm
 // (440-474), bit for bit, for the TT queries of the HNSW walk (HNSWIndex::search_tt_with_ef, tensor_store/src/hnsw.rs:1811-1841)
-// and for insert_tt_vector (1755-1759).  docs/hnsw.md §17.
+// and for insert_tt_vector (1755-1759).  docs/hnsw.md §17.  Further down: tt_decompose (§21) and the comparisons of trains without
+// reconstruction — tt_dot_product, tt_cosine_similarity, tt_euclidean_distance (480-546), §23.
 // THIS TRANSLATION UNIT IS BUILT WITH -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt (build.py), host and device.
 //
 // Reference order restated here:
@@ -1009,6 +1010,295 @@ nmn_status launch_tt_decompose(const TTDecConfig& c, const float* vectors_dev, u
     return NMN_OK;
 }
 
+// ---- tt_dot_product, tt_cosine_similarity, tt_euclidean_distance (tensor_train.rs:480-546) ---------------------------------------
+//
+// Reference order restated below, host and device (docs/hnsw.md §23):
+//   tt_dot_product(a, b): gram = [1.0]; per pair of cores (r1a, n, r2a) and (r1b, n, r2b), new_gram[x r2b + y] is ONE chain from
+//       +0.0 over k, then ia, then ib of sum + ((gram[ia r1b + ib] * A[ia,k,x]) * B[ib,k,y]); the result is gram[0].  With a == b it
+//       is the chain tt_norm runs before its square root.
+//   tt_cosine_similarity: 0.0 when sqrt(dot(a,a)) or sqrt(dot(b,b)) is < 1e-10f (a NaN is not), else dot / (norm_a * norm_b).
+//   tt_euclidean_distance: sqrt(max(fma(-2, dot_ab, dot_aa + dot_bb), 0.0)), the fma fused; f32::max drops a NaN: NaN gives 0.0.
+
+float tt_dot_host(const uint32_t* shape, uint32_t n_cores, const uint32_t* ranks_a, const float* cores_a, const uint32_t* ranks_b,
+                  const float* cores_b) {
+    std::vector<float> gram(1, 1.0f), ng;
+    const float *A = cores_a, *B = cores_b;
+    for (uint32_t k = 0; k < n_cores; k++) {
+        const uint64_t r1a = ranks_a[k], r2a = ranks_a[k + 1], r1b = ranks_b[k], r2b = ranks_b[k + 1], n = shape[k];
+        ng.assign(r2a * r2b, 0.0f);
+        for (uint64_t x = 0; x < r2a; x++)
+            for (uint64_t y = 0; y < r2b; y++) {
+                float sum = 0.0f;
+                for (uint64_t kk = 0; kk < n; kk++)
+                    for (uint64_t ia = 0; ia < r1a; ia++)
+                        for (uint64_t ib = 0; ib < r1b; ib++) {
+                            const float t = gram[ia * r1b + ib] * A[(ia * n + kk) * r2a + x];
+                            const float p = t * B[(ib * n + kk) * r2b + y];
+                            sum = sum + p;
+                        }
+                ng[x * r2b + y] = sum;
+            }
+        gram.swap(ng);
+        A += r1a * n * r2a;
+        B += r1b * n * r2b;
+    }
+    return gram[0];
+}
+
+namespace {
+
+// what the three functions make of dot(a, b), dot(a, a) and dot(b, b)
+__host__ __device__ inline float tt_sim_finish(uint32_t op, float dot, float self_a, float self_b) {
+    if (op == NMN_TT_SIM_DOT) return dot;
+    if (op == NMN_TT_SIM_COSINE) {
+        const float na = __builtin_sqrtf(self_a), nb = __builtin_sqrtf(self_b);
+        if (na < 1e-10f || nb < 1e-10f) return 0.0f;
+        const float d = na * nb;
+        return dot / d;
+    }
+    const float s = self_a + self_b;
+    const float sq = __builtin_fmaf(-2.0f, dot, s);
+    return __builtin_sqrtf(sq > 0.0f ? sq : 0.0f);  // max(sq, 0.0): a NaN and every value <= 0 give +0.0 (sq is never -0.0)
+}
+
+struct TTSet {  // one set of trains in DEVICE memory
+    const uint32_t* ranks;     // [n][n_cores + 1]
+    const uint64_t* core_off;  // nullable: train i starts at i * stride
+    const float* cores;        // cap floats
+    const uint32_t* status;    // nullable: a train whose status is not NMN_TT_OK is bad
+    const uint8_t* skip;       // nullable: 1 = the host computes what this train takes part in
+    uint64_t stride, cap;
+    uint32_t n, max_rank;      // no rank of a good train is above max_rank (kTTMaxRank at most)
+};
+
+struct TTSimArgs {
+    uint32_t op, n_cores;
+    uint32_t shape[kTTMaxCores];
+    TTSet q, t;
+    const float *self_q, *self_t;  // null for NMN_TT_SIM_DOT
+    float* out;                    // [nq][nt]; tt_self_dot_kernel: [t.n]
+    uint32_t chunk, n_chunks;      // targets per work item (a multiple of the workgroup's waves), chunks per query
+    uint32_t qcap, gcap;           // LDS floats for the query's cores, and for ONE Gram matrix of one wave
+};
+
+constexpr uint32_t kTTBadBits = 0x7FC00000u;  // what a bad train leaves in every output it takes part in
+
+// The ranks of train i come from device memory: nothing is read through them before this has passed.  Bad: a status that is not
+// NMN_TT_OK, end ranks that are not 1, a rank of 0 or above the set's max_rank, more core floats than `lim` (the slot, at most
+// kTTMaxStorage), or core data that would leave the `cap` floats of the set's buffer.  *off: where the train's cores start.
+__device__ bool tt_train_ok(const TTSet& s, uint32_t i, uint32_t n_cores, const uint32_t* shape, uint64_t lim, uint64_t* off) {
+    const uint32_t* r = s.ranks + (size_t)i * (n_cores + 1);
+    bool ok = !s.status || s.status[i] == kTTStatusOk;
+    uint32_t r1 = r[0];
+    ok = ok && r1 == 1;
+    uint64_t storage = 0;
+    for (uint32_t k = 0; k < n_cores; k++) {
+        const uint32_t r2 = r[k + 1];
+        ok = ok && r2 >= 1 && r2 <= s.max_rank;
+        if (ok) storage += (uint64_t)r1 * shape[k] * r2;  // (r1, r2 <= 32 here: no overflow)
+        ok = ok && storage <= lim;
+        r1 = r2;
+    }
+    ok = ok && r1 == 1;
+    uint64_t o = (uint64_t)i * s.stride;
+    if (s.core_off) {
+        const uint64_t lo = s.core_off[i], hi = s.core_off[i + 1];
+        ok = ok && hi >= lo && storage <= hi - lo;
+        o = lo;
+    }
+    ok = ok && o <= s.cap && storage <= s.cap - o;
+    *off = o;
+    return ok;
+}
+
+// One core step of one pair by one wave: the lanes share out the r2a * r2b outputs, each output one sequential chain.  A, B: the
+// pair's k-th cores; gram: r1a * r1b floats in LDS; nxt: r2a * r2b floats in LDS.
+__device__ __forceinline__ void tt_gram_step(const float* __restrict__ A, const float* __restrict__ B, const float* gram, float* nxt,
+                                             uint32_t r1a, uint32_t r2a, uint32_t r1b, uint32_t r2b, uint32_t n, uint32_t lane) {
+    for (uint32_t o = lane; o < r2a * r2b; o += 64) {
+        const uint32_t x = o / r2b, y = o - x * r2b;
+        float sum = 0.0f;
+        for (uint32_t kk = 0; kk < n; kk++)
+            for (uint32_t ia = 0; ia < r1a; ia++) {
+                const float ga = A[(ia * n + kk) * r2a + x];
+                for (uint32_t ib = 0; ib < r1b; ib++) {
+                    const float t = gram[ia * r1b + ib] * ga;
+                    const float p = t * B[(ib * n + kk) * r2b + y];
+                    sum = sum + p;
+                }
+            }
+        nxt[o] = sum;
+    }
+}
+
+// Dynamic LDS of both kernels, in floats: [qcap] the query's cores (tt_similarity_kernel only), then per wave two Gram matrices of
+// gcap floats and the wave's train's ranks.
+constexpr uint32_t kTTSimRankSlots = kTTMaxCores + 1;
+
+// One workgroup takes one work item at a time — a query and a chunk of the targets — the items beyond the grid in a stride loop.
+// The query's cores are staged in LDS once per item; then every wave owns one target at a time and walks the cores of its pair,
+// the target's cores read from global memory.  No chain is split.  Every barrier is reached by the whole workgroup: the trips of
+// the target loop and the core loop do not depend on the wave.
+__global__ __launch_bounds__(256) void tt_similarity_kernel(TTSimArgs a) {
+    extern __shared__ float lds[];
+    __shared__ uint32_t s_ra[kTTSimRankSlots];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, waves = blockDim.x >> 6;
+    float* s_core = lds;
+    float* s_gram = lds + a.qcap + (size_t)wave * (2 * a.gcap + kTTSimRankSlots);
+    uint32_t* s_rb = (uint32_t*)(s_gram + 2 * a.gcap);
+    const uint32_t n = a.n_cores, nt = a.t.n;
+    const uint64_t lim_q = a.q.stride < a.qcap ? a.q.stride : a.qcap;
+    const uint64_t lim_t = a.t.stride < kTTMaxStorage ? a.t.stride : kTTMaxStorage;
+    const float bad = __uint_as_float(kTTBadBits);
+    const uint64_t items = (uint64_t)a.q.n * a.n_chunks;
+    for (uint64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const uint32_t q = (uint32_t)(item / a.n_chunks), t0 = (uint32_t)(item - (uint64_t)q * a.n_chunks) * a.chunk;
+        if (a.q.skip && a.q.skip[q]) continue;  // (the same for every thread of the workgroup)
+        const uint32_t t_end = nt - t0 < a.chunk ? nt : t0 + a.chunk;
+        uint64_t off_q;
+        const bool ok_q = tt_train_ok(a.q, q, n, a.shape, lim_q, &off_q);
+        __syncthreads();  // the readers of the previous item are done
+        if (ok_q) {
+            if (tid <= n) s_ra[tid] = a.q.ranks[(size_t)q * (n + 1) + tid];
+            __syncthreads();
+            uint32_t storage = 0;
+            for (uint32_t k = 0; k < n; k++) storage += s_ra[k] * a.shape[k] * s_ra[k + 1];
+            const float* src = a.q.cores + off_q;
+            for (uint32_t i = tid; i < storage; i += blockDim.x) s_core[i] = src[i];
+        }
+        const float self_q = a.self_q && ok_q ? a.self_q[q] : 0.0f;
+        for (uint32_t tb = t0; tb < t_end; tb += waves) {
+            const uint32_t t = tb + wave;
+            const bool mine = t < t_end && !(a.t.skip && a.t.skip[t]);
+            uint64_t off_t = 0;
+            const bool ok = mine && ok_q && tt_train_ok(a.t, t, n, a.shape, lim_t, &off_t);
+            if (ok) {
+                if (lane <= n) s_rb[lane] = a.t.ranks[(size_t)t * (n + 1) + lane];
+                if (lane == 0) s_gram[0] = 1.0f;  // gram = [1.0]
+            }
+            uint32_t ca = 0, cb = 0;
+            for (uint32_t k = 0; k < n; k++) {
+                __syncthreads();
+                if (ok) {
+                    const uint32_t r1a = s_ra[k], r2a = s_ra[k + 1], r1b = s_rb[k], r2b = s_rb[k + 1], m = a.shape[k];
+                    const uint32_t cur = k & 1u;
+                    tt_gram_step(s_core + ca, a.t.cores + off_t + cb, s_gram + cur * a.gcap, s_gram + (cur ^ 1u) * a.gcap, r1a, r2a, r1b,
+                                 r2b, m, lane);
+                    ca += r1a * m * r2a;
+                    cb += r1b * m * r2b;
+                }
+            }
+            __syncthreads();
+            if (mine && lane == 0) {
+                float v = bad;
+                if (ok) v = tt_sim_finish(a.op, s_gram[(n & 1u) * a.gcap], self_q, a.self_t ? a.self_t[t] : 0.0f);
+                a.out[(size_t)q * nt + t] = v;
+            }
+            __syncthreads();  // the wave's ranks and gram[0] are free for the next target
+        }
+    }
+}
+
+// out[i] = tt_dot_product(t_i, t_i): a wave per train, groups of the workgroup's waves in a stride loop, both operands read from
+// global memory.  A bad train's self dot is the quiet NaN.
+__global__ __launch_bounds__(256) void tt_self_dot_kernel(TTSimArgs a) {
+    extern __shared__ float lds[];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, waves = blockDim.x >> 6;
+    float* s_gram = lds + (size_t)wave * (2 * a.gcap + kTTSimRankSlots);
+    uint32_t* s_r = (uint32_t*)(s_gram + 2 * a.gcap);
+    const uint32_t n = a.n_cores, nt = a.t.n;
+    const uint64_t lim = a.t.stride < kTTMaxStorage ? a.t.stride : kTTMaxStorage;
+    for (uint64_t tb = (uint64_t)blockIdx.x * waves; tb < nt; tb += (uint64_t)gridDim.x * waves) {
+        const uint32_t t = (uint32_t)tb + wave;
+        const bool mine = t < nt && !(a.t.skip && a.t.skip[t]);
+        uint64_t off = 0;
+        const bool ok = mine && tt_train_ok(a.t, t, n, a.shape, lim, &off);
+        if (ok) {
+            if (lane <= n) s_r[lane] = a.t.ranks[(size_t)t * (n + 1) + lane];
+            if (lane == 0) s_gram[0] = 1.0f;
+        }
+        uint32_t c = 0;
+        for (uint32_t k = 0; k < n; k++) {
+            __syncthreads();
+            if (ok) {
+                const uint32_t r1 = s_r[k], r2 = s_r[k + 1], m = a.shape[k], cur = k & 1u;
+                const float* G = a.t.cores + off + c;
+                tt_gram_step(G, G, s_gram + cur * a.gcap, s_gram + (cur ^ 1u) * a.gcap, r1, r2, r1, r2, m, lane);
+                c += r1 * m * r2;
+            }
+        }
+        __syncthreads();
+        if (mine && lane == 0) a.out[t] = ok ? s_gram[(n & 1u) * a.gcap] : __uint_as_float(kTTBadBits);
+        __syncthreads();
+    }
+}
+
+// The workgroup shape of one launch: as many waves (4 at most) as the LDS of one workgroup holds Gram pairs beside the query's cores
+struct TTSimShape {
+    uint32_t waves, lds_bytes;
+};
+TTSimShape sim_shape(uint32_t qcap, uint32_t gcap) {
+    const uint32_t per_wave = 2 * gcap + kTTSimRankSlots;
+    const uint32_t waves = std::min<uint32_t>(4, (kTTSimMaxLdsFloats - qcap) / per_wave);
+    return {waves, (qcap + waves * per_wave) * (uint32_t)sizeof(float)};
+}
+
+uint32_t sim_grid_max() { return std::max(env_u32("NMN_TT_SIMILARITY_GRID", kTTSimGridMax), 1u); }
+
+void fill_set(TTSet* s, const TTSimSet& in) {
+    s->ranks = in.ranks_dev;
+    s->core_off = in.core_off_dev;
+    s->cores = in.cores_dev;
+    s->status = in.status_dev;
+    s->skip = in.skip_dev;
+    s->stride = in.stride;
+    s->cap = in.cap;
+    s->n = in.n;
+    s->max_rank = std::min(std::max(in.max_rank, 1u), kTTMaxRank);
+}
+
+}  // namespace
+
+hipError_t launch_tt_self_dot(const uint32_t* shape, uint32_t n_cores, const TTSimSet& set, float* out_dev, hipStream_t s) {
+    if (set.n == 0) return hipSuccess;
+    TTSimArgs a{};
+    a.n_cores = n_cores;
+    memcpy(a.shape, shape, n_cores * sizeof(uint32_t));
+    fill_set(&a.t, set);
+    a.out = out_dev;
+    a.gcap = a.t.max_rank * a.t.max_rank;
+    const TTSimShape ws = sim_shape(0, a.gcap);
+    const uint32_t groups = (set.n + ws.waves - 1) / ws.waves;
+    hipLaunchKernelGGL(tt_self_dot_kernel, dim3(std::min(groups, sim_grid_max())), dim3(ws.waves * 64), ws.lds_bytes, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_tt_similarity(uint32_t op, const uint32_t* shape, uint32_t n_cores, const TTSimSet& q, const TTSimSet& t,
+                                const float* self_q_dev, const float* self_t_dev, float* out_dev, hipStream_t s) {
+    if (q.n == 0 || t.n == 0) return hipSuccess;
+    TTSimArgs a{};
+    a.op = op;
+    a.n_cores = n_cores;
+    memcpy(a.shape, shape, n_cores * sizeof(uint32_t));
+    fill_set(&a.q, q);
+    fill_set(&a.t, t);
+    a.self_q = op == NMN_TT_SIM_DOT ? nullptr : self_q_dev;
+    a.self_t = op == NMN_TT_SIM_DOT ? nullptr : self_t_dev;
+    a.out = out_dev;
+    a.qcap = (uint32_t)std::min<uint64_t>(q.stride, kTTMaxStorage);
+    a.gcap = a.q.max_rank * a.t.max_rank;
+    const TTSimShape ws = sim_shape(a.qcap, a.gcap);
+    // about grid_max work items: every query's targets in chunks of a multiple of the waves
+    const uint32_t grid_max = sim_grid_max();
+    const uint32_t per_query = std::max(grid_max / q.n, 1u);
+    const uint64_t chunk = ((uint64_t)(t.n + per_query - 1) / per_query + ws.waves - 1) / ws.waves * ws.waves;
+    a.chunk = (uint32_t)std::min<uint64_t>(chunk, 0xFFFFFF00u);
+    a.n_chunks = (uint32_t)(((uint64_t)t.n + a.chunk - 1) / a.chunk);
+    const uint64_t items = (uint64_t)q.n * a.n_chunks;
+    hipLaunchKernelGGL(tt_similarity_kernel, dim3((uint32_t)std::min<uint64_t>(items, grid_max)), dim3(ws.waves * 64), ws.lds_bytes, s, a);
+    return hipGetLastError();
+}
+
 namespace {
 
 // TTConfig::for_dim's shape (tensor_train.rs:130-199): the table, then factorize_balanced with the host libm's f64 log2 and pow
@@ -1195,6 +1485,311 @@ extern "C" nmn_status nmn_tt_norm(const uint32_t* shape, uint32_t n_cores, const
                                   const float* cores, uint32_t nq, float* out_norms) {
     if (nq && !out_norms) return nmn::set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
     return nmn::tt_public(shape, n_cores, ranks, core_off, cores, nq, nullptr, out_norms);
+}
+
+namespace nmn {
+namespace {
+
+// One set of a host-buffer similarity call, checked: which trains the kernels take and which the host restatement (`big`: a rank
+// above kTTMaxRank or more than kTTMaxStorage core floats; every train when the call goes to the host)
+struct TTHostSet {
+    const uint32_t* shape = nullptr;
+    uint32_t n_cores = 0, n = 0;
+    const uint32_t* ranks = nullptr;
+    const uint64_t* core_off = nullptr;
+    const float* cores = nullptr;
+    std::vector<uint8_t> big;
+    uint32_t n_big = 0, max_rank = 1;
+    uint64_t max_storage = 1;  // over the trains the kernels take
+    const uint32_t* ranks_of(uint32_t i) const { return ranks + (size_t)i * (n_cores + 1); }
+    const float* cores_of(uint32_t i) const { return cores + core_off[i]; }
+    float self_dot(uint32_t i) const { return tt_dot_host(shape, n_cores, ranks_of(i), cores_of(i), ranks_of(i), cores_of(i)); }
+};
+
+nmn_status sim_check_set(const char* name, const uint32_t* shape, uint32_t n_cores, const uint32_t* ranks, const uint64_t* core_off,
+                         const float* cores, uint32_t n, TTHostSet* s) {
+    char buf[320];
+    if (!core_off) {
+        snprintf(buf, sizeof buf, "TT similarity: %s set: null argument", name);
+        return set_error(NMN_ERR_INVALID_ARGUMENT, buf);
+    }
+    TTBatch b;
+    const nmn_status st = tt_check(shape, n_cores, ranks, true, core_off, n, false, &b);
+    if (st != NMN_OK) {  // tt_check's text names the train and the rule; the set is named here
+        const char* e = nmn_last_error();
+        const bool one = !strncmp(e, "TT: query ", 10);
+        snprintf(buf, sizeof buf, one ? "TT similarity: %s set: train %s" : "TT similarity: %s set: %s", name, one ? e + 10 : e);
+        return set_error(st, buf);
+    }
+    if (core_off[n] > core_off[0] && !cores) {
+        snprintf(buf, sizeof buf, "TT similarity: %s set: null argument", name);
+        return set_error(NMN_ERR_INVALID_ARGUMENT, buf);
+    }
+    s->shape = shape;
+    s->n_cores = n_cores;
+    s->n = n;
+    s->ranks = ranks;
+    s->core_off = core_off;
+    s->cores = cores;
+    s->big.assign(n, 0);
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t* r = s->ranks_of(i);
+        uint32_t top = 1;
+        for (uint32_t k = 0; k <= n_cores; k++) top = std::max(top, r[k]);
+        const uint64_t storage = core_off[i + 1] - core_off[i];
+        if (top > kTTMaxRank || storage > kTTMaxStorage) {
+            s->big[i] = 1;
+            s->n_big++;
+        } else {
+            s->max_rank = std::max(s->max_rank, top);
+            s->max_storage = std::max(s->max_storage, storage);
+        }
+    }
+    return NMN_OK;
+}
+
+void all_to_host(TTHostSet* s) {
+    s->big.assign(s->n, 1);
+    s->n_big = s->n;
+}
+
+// fn(lo, hi) over [0, n) on up to NMN_TT_SIMILARITY_HOST_THREADS threads (16), four items a thread at the least
+template <class F>
+void sim_host_for(uint64_t n, F fn) {
+    const uint64_t threads = std::min<uint64_t>(std::max(env_u32("NMN_TT_SIMILARITY_HOST_THREADS", 16), 1u), std::max<uint64_t>(n / 4, 1));
+    if (threads <= 1) return fn((uint64_t)0, n);
+    std::vector<std::thread> pool;
+    for (uint64_t t = 0; t < threads; t++) pool.emplace_back(fn, n * t / threads, n * (t + 1) / threads);
+    for (std::thread& t : pool) t.join();
+}
+
+// The device copy of one host set: the cores from core_off[0] on, the offsets rebased, skip = big
+struct TTDevSet {
+    float *cores = nullptr, *self = nullptr;
+    uint32_t* ranks = nullptr;
+    uint64_t* off = nullptr;
+    uint8_t* skip = nullptr;
+    TTSimSet set;
+    ~TTDevSet() {
+        for (void* p : {(void*)cores, (void*)self, (void*)ranks, (void*)off, (void*)skip})
+            if (p) (void)hipFree(p);
+    }
+    nmn_status upload(const TTHostSet& h, bool want_self) {
+        const uint64_t c0 = h.core_off[0], cn = h.core_off[h.n] - c0;
+        const size_t rk = (size_t)h.n * (h.n_cores + 1);
+        std::vector<uint64_t> o(h.core_off, h.core_off + h.n + 1);
+        for (uint64_t& x : o) x -= c0;
+        TT_TRY(hipMalloc((void**)&cores, std::max<size_t>(cn * 4, 256)));
+        TT_TRY(hipMalloc((void**)&ranks, rk * 4));
+        TT_TRY(hipMalloc((void**)&off, (size_t)(h.n + 1) * 8));
+        TT_TRY(hipMalloc((void**)&skip, h.n));
+        if (want_self) TT_TRY(hipMalloc((void**)&self, (size_t)h.n * 4));
+        if (cn) TT_TRY(hipMemcpy(cores, h.cores + c0, cn * 4, hipMemcpyHostToDevice));
+        TT_TRY(hipMemcpy(ranks, h.ranks, rk * 4, hipMemcpyHostToDevice));
+        TT_TRY(hipMemcpy(off, o.data(), (size_t)(h.n + 1) * 8, hipMemcpyHostToDevice));
+        TT_TRY(hipMemcpy(skip, h.big.data(), h.n, hipMemcpyHostToDevice));
+        set.ranks_dev = ranks;
+        set.core_off_dev = off;
+        set.cores_dev = cores;
+        set.skip_dev = h.n_big ? skip : nullptr;
+        set.stride = h.max_storage;
+        set.cap = cn;
+        set.n = h.n;
+        set.max_rank = h.max_rank;
+        return NMN_OK;
+    }
+};
+
+bool sim_on_host(uint64_t work) { return host_forced() || work < env_u32("NMN_TT_SIMILARITY_MIN", kTTSimMinDefault); }
+
+// self[i] = tt_dot_product(t_i, t_i) for every train of the set: the kernel's trains from d (already launched into d.self on the
+// null stream and waited for), the others by the host restatement
+nmn_status sim_collect_self(const TTHostSet& h, const TTDevSet* d, std::vector<float>* self) {
+    self->assign(h.n, 0.0f);
+    if (d && h.n_big < h.n) TT_TRY(hipMemcpy(self->data(), d->self, (size_t)h.n * 4, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> todo;
+    for (uint32_t i = 0; i < h.n; i++)
+        if (h.big[i]) todo.push_back(i);
+    sim_host_for(todo.size(), [&](uint64_t lo, uint64_t hi) {
+        for (uint64_t j = lo; j < hi; j++) (*self)[todo[j]] = h.self_dot(todo[j]);
+    });
+    return NMN_OK;
+}
+
+nmn_status sim_run(uint32_t op, TTHostSet& Q, TTHostSet& T, float* out) {
+    const uint64_t pairs = (uint64_t)Q.n * T.n;
+    const bool need_self = op != NMN_TT_SIM_DOT;
+    if (sim_on_host(pairs)) {
+        all_to_host(&Q);
+        all_to_host(&T);
+    }
+    const bool device = Q.n_big < Q.n && T.n_big < T.n;
+    if (!device) {  // one set has no train for the kernel: there is no pair for it, so the self dots are the host's as well
+        all_to_host(&Q);
+        all_to_host(&T);
+    }
+    std::vector<float> res(pairs), self_q, self_t;
+    TTDevSet dq, dt;
+    if (device) {
+        nmn_status st = dq.upload(Q, need_self);
+        if (st == NMN_OK) st = dt.upload(T, need_self);
+        if (st != NMN_OK) return st;
+        float* d_out = nullptr;
+        auto body = [&]() -> nmn_status {
+            TT_TRY(hipMalloc((void**)&d_out, pairs * 4));
+            if (need_self) {
+                TT_TRY(launch_tt_self_dot(Q.shape, Q.n_cores, dq.set, dq.self, nullptr));
+                TT_TRY(launch_tt_self_dot(Q.shape, Q.n_cores, dt.set, dt.self, nullptr));
+            }
+            TT_TRY(launch_tt_similarity(op, Q.shape, Q.n_cores, dq.set, dt.set, dq.self, dt.self, d_out, nullptr));
+            TT_TRY(hipDeviceSynchronize());
+            TT_TRY(hipMemcpy(res.data(), d_out, pairs * 4, hipMemcpyDeviceToHost));
+            return NMN_OK;
+        };
+        const nmn_status st2 = body();
+        if (d_out) (void)hipFree(d_out);
+        if (st2 != NMN_OK) return st2;
+    }
+    if (Q.n_big || T.n_big) {  // the pairs a train above the limits takes part in: the host restatement, same bits
+        if (need_self) {
+            nmn_status st = sim_collect_self(Q, device ? &dq : nullptr, &self_q);
+            if (st == NMN_OK) st = sim_collect_self(T, device ? &dt : nullptr, &self_t);
+            if (st != NMN_OK) return st;
+        }
+        std::vector<uint64_t> todo;
+        for (uint32_t i = 0; i < Q.n; i++)
+            for (uint32_t j = 0; j < T.n; j++)
+                if (Q.big[i] || T.big[j]) todo.push_back((uint64_t)i * T.n + j);
+        sim_host_for(todo.size(), [&](uint64_t lo, uint64_t hi) {
+            for (uint64_t p = lo; p < hi; p++) {
+                const uint32_t i = (uint32_t)(todo[p] / T.n), j = (uint32_t)(todo[p] % T.n);
+                const float dot = tt_dot_host(Q.shape, Q.n_cores, Q.ranks_of(i), Q.cores_of(i), T.ranks_of(j), T.cores_of(j));
+                res[todo[p]] = tt_sim_finish(op, dot, need_self ? self_q[i] : 0.0f, need_self ? self_t[j] : 0.0f);
+            }
+        });
+    }
+    memcpy(out, res.data(), pairs * 4);
+    return NMN_OK;
+}
+
+nmn_status self_dot_run(TTHostSet& S, float* out) {
+    if (sim_on_host(S.n)) all_to_host(&S);
+    std::vector<float> self;
+    TTDevSet d;
+    const bool device = S.n_big < S.n;
+    if (device) {
+        const nmn_status st = d.upload(S, true);
+        if (st != NMN_OK) return st;
+        TT_TRY(launch_tt_self_dot(S.shape, S.n_cores, d.set, d.self, nullptr));
+        TT_TRY(hipDeviceSynchronize());
+    }
+    const nmn_status st = sim_collect_self(S, device ? &d : nullptr, &self);
+    if (st != NMN_OK) return st;
+    memcpy(out, self.data(), (size_t)S.n * 4);
+    return NMN_OK;
+}
+
+// what the device entries can check of one set on the host
+nmn_status sim_device_set(const char* name, const uint32_t* ranks_dev, const uint64_t* core_off_dev, const float* cores_dev,
+                          uint64_t stride, const uint32_t* status_dev, uint32_t n, TTSimSet* s) {
+    char buf[160];
+    if (!ranks_dev || !cores_dev) {
+        snprintf(buf, sizeof buf, "TT similarity: %s set: null argument", name);
+        return set_error(NMN_ERR_INVALID_ARGUMENT, buf);
+    }
+    if (stride < 1 || stride > kTTMaxStorage) {
+        snprintf(buf, sizeof buf, "TT similarity: %s set: stride must be 1..%u floats (nmn_tt_limits)", name, kTTMaxStorage);
+        return set_error(NMN_ERR_INVALID_ARGUMENT, buf);
+    }
+    s->ranks_dev = ranks_dev;
+    s->core_off_dev = core_off_dev;
+    s->cores_dev = cores_dev;
+    s->status_dev = status_dev;
+    s->stride = stride;
+    s->cap = (uint64_t)n * stride;
+    s->n = n;
+    s->max_rank = kTTMaxRank;
+    return NMN_OK;
+}
+
+nmn_status sim_device_shape(const uint32_t* shape, uint32_t n_cores) {
+    if (n_cores < 1 || n_cores > kTTMaxCores) return set_error(NMN_ERR_INVALID_ARGUMENT, "TT: n_cores must be 1..8");
+    if (!shape) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    for (uint32_t k = 0; k < n_cores; k++)
+        if (shape[k] < 1) return set_error(NMN_ERR_INVALID_ARGUMENT, "TT: every mode of the shape must be >= 1");
+    return NMN_OK;
+}
+
+constexpr uint32_t kTTSimMaxTrains = 1u << 31;
+
+}  // namespace
+}  // namespace nmn
+
+extern "C" nmn_status nmn_tt_similarity(uint32_t op, const uint32_t* shape_q, uint32_t n_cores_q, const uint32_t* ranks_q,
+                                        const uint64_t* core_off_q, const float* cores_q, uint32_t nq, const uint32_t* shape_t,
+                                        uint32_t n_cores_t, const uint32_t* ranks_t, const uint64_t* core_off_t, const float* cores_t,
+                                        uint32_t nt, float* out) {
+    using namespace nmn;
+    if (op > NMN_TT_SIM_EUCLIDEAN) return set_error(NMN_ERR_INVALID_ARGUMENT, "TT similarity: unknown op");
+    if (nq == 0 || nt == 0) return NMN_OK;
+    if (!out) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (nq > kTTSimMaxTrains || nt > kTTSimMaxTrains) return set_error(NMN_ERR_INVALID_ARGUMENT, "TT similarity: more than 2^31 trains in a set");
+    TTHostSet Q, T;
+    nmn_status st = sim_check_set("query", shape_q, n_cores_q, ranks_q, core_off_q, cores_q, nq, &Q);
+    if (st == NMN_OK) st = sim_check_set("target", shape_t, n_cores_t, ranks_t, core_off_t, cores_t, nt, &T);
+    if (st != NMN_OK) return st;
+    if (n_cores_q != n_cores_t || memcmp(shape_q, shape_t, n_cores_q * sizeof(uint32_t)))
+        return set_error(NMN_ERR_INVALID_ARGUMENT, "incompatible TT shapes for operation");
+    return sim_run(op, Q, T, out);
+}
+
+extern "C" nmn_status nmn_tt_self_dot(const uint32_t* shape, uint32_t n_cores, const uint32_t* ranks, const uint64_t* core_off,
+                                      const float* cores, uint32_t n, float* out) {
+    using namespace nmn;
+    if (n == 0) return NMN_OK;
+    if (!out) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (n > kTTSimMaxTrains) return set_error(NMN_ERR_INVALID_ARGUMENT, "TT similarity: more than 2^31 trains in a set");
+    TTHostSet S;
+    const nmn_status st = sim_check_set("train", shape, n_cores, ranks, core_off, cores, n, &S);
+    if (st != NMN_OK) return st;
+    return self_dot_run(S, out);
+}
+
+extern "C" nmn_status nmn_tt_self_dot_device(const uint32_t* shape, uint32_t n_cores, const uint32_t* ranks_dev,
+                                             const uint64_t* core_off_dev, const float* cores_dev, uint64_t stride,
+                                             const uint32_t* status_dev, uint32_t n, float* out_dev, void* stream) {
+    using namespace nmn;
+    nmn_status st = sim_device_shape(shape, n_cores);
+    if (st != NMN_OK) return st;
+    if (n == 0) return NMN_OK;
+    if (!out_dev) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (n > kTTSimMaxTrains) return set_error(NMN_ERR_INVALID_ARGUMENT, "TT similarity: more than 2^31 trains in a set");
+    TTSimSet s;
+    st = sim_device_set("train", ranks_dev, core_off_dev, cores_dev, stride, status_dev, n, &s);
+    if (st != NMN_OK) return st;
+    TT_TRY(launch_tt_self_dot(shape, n_cores, s, out_dev, (hipStream_t)stream));
+    return NMN_OK;
+}
+
+extern "C" nmn_status nmn_tt_similarity_device(uint32_t op, const uint32_t* shape, uint32_t n_cores, const uint32_t* ranks_q_dev,
+                                               const uint64_t* core_off_q_dev, const float* cores_q_dev, uint64_t stride_q,
+                                               const uint32_t* status_q_dev, uint32_t nq, const uint32_t* ranks_t_dev,
+                                               const uint64_t* core_off_t_dev, const float* cores_t_dev, uint64_t stride_t,
+                                               const uint32_t* status_t_dev, uint32_t nt, const float* self_q_dev,
+                                               const float* self_t_dev, float* out_dev, void* stream) {
+    using namespace nmn;
+    if (op > NMN_TT_SIM_EUCLIDEAN) return set_error(NMN_ERR_INVALID_ARGUMENT, "TT similarity: unknown op");
+    nmn_status st = sim_device_shape(shape, n_cores);
+    if (st != NMN_OK) return st;
+    if (nq == 0 || nt == 0) return NMN_OK;
+    if (!out_dev || (op != NMN_TT_SIM_DOT && (!self_q_dev || !self_t_dev))) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (nq > kTTSimMaxTrains || nt > kTTSimMaxTrains) return set_error(NMN_ERR_INVALID_ARGUMENT, "TT similarity: more than 2^31 trains in a set");
+    TTSimSet q, t;
+    st = sim_device_set("query", ranks_q_dev, core_off_q_dev, cores_q_dev, stride_q, status_q_dev, nq, &q);
+    if (st == NMN_OK) st = sim_device_set("target", ranks_t_dev, core_off_t_dev, cores_t_dev, stride_t, status_t_dev, nt, &t);
+    if (st != NMN_OK) return st;
+    TT_TRY(launch_tt_similarity(op, shape, n_cores, q, t, self_q_dev, self_t_dev, out_dev, (hipStream_t)stream));
+    return NMN_OK;
 }
 
 extern "C" nmn_status nmn_tt_limits(uint32_t* max_cores, uint32_t* max_rank, uint32_t* max_storage, uint32_t* max_level) {

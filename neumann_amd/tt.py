@@ -111,6 +111,118 @@ def tt_norm(tts):
     return out
 
 
+# ---- tt_dot_product, tt_cosine_similarity, tt_euclidean_distance (tensor_train.rs:480-546, 591-646), docs/hnsw.md §23 ----------
+SIM_DOT, SIM_COSINE, SIM_EUCLIDEAN = 0, 1, 2
+SIM_OPS = {"dot": SIM_DOT, "cosine": SIM_COSINE, "euclidean": SIM_EUCLIDEAN}
+INCOMPATIBLE_SHAPES = "incompatible TT shapes for operation"   # Display of TTError::IncompatibleShapes
+
+
+def _trains(x):
+    return [x] if isinstance(x, TTVector) else list(x)
+
+
+def tt_similarity(op, queries, targets):
+    """-> f32 [nq][nt]: out[i][j] = tt_dot_product / tt_cosine_similarity / tt_euclidean_distance of (queries[i], targets[j]), bit
+    for bit (nmn_tt_similarity).  op: "dot", "cosine", "euclidean" or an NMN_TT_SIM_* value.  Trains of another shape raise with the
+    reference's text, as the first failing pair would."""
+    op = SIM_OPS.get(op, op)
+    qs, ts = _trains(queries), _trains(targets)
+    if any(t.shape != qs[0].shape for t in qs + ts if qs):
+        raise _bad(INCOMPATIBLE_SHAPES)
+    out = np.empty((len(qs), len(ts)), dtype=np.float32)
+    if not qs or not ts:
+        if op not in (SIM_DOT, SIM_COSINE, SIM_EUCLIDEAN):
+            raise _bad("TT similarity: unknown op")
+        return out
+    sq, rq, oq, cq = pack(qs)
+    st, rt, ot, ct = pack(ts)
+    _capi.check(_capi.load().nmn_tt_similarity(int(op), _p(sq), sq.size, _p(rq), _p(oq), _p(cq), len(qs), _p(st), st.size, _p(rt), _p(ot),
+                                               _p(ct), len(ts), _p(out)))
+    return out
+
+
+def tt_self_dot(tts):
+    """-> f32 [n]: tt_dot_product(t, t) of every train, the value tt_norm takes the square root of (nmn_tt_self_dot)"""
+    shape, ranks, off, cores = pack(tts)
+    out = np.empty(ranks.shape[0], dtype=np.float32)
+    _capi.check(_capi.load().nmn_tt_self_dot(_p(shape), shape.size, _p(ranks), _p(off), _p(cores), ranks.shape[0], _p(out)))
+    return out
+
+
+def tt_dot_product(a, b):
+    """tt_dot_product (tensor_train.rs:480-516) -> float"""
+    return float(tt_similarity(SIM_DOT, a, b)[0, 0])
+
+
+def tt_cosine_similarity(a, b):
+    """tt_cosine_similarity (522-532) -> float"""
+    return float(tt_similarity(SIM_COSINE, a, b)[0, 0])
+
+
+def tt_euclidean_distance(a, b):
+    """tt_euclidean_distance (539-546) -> float"""
+    return float(tt_similarity(SIM_EUCLIDEAN, a, b)[0, 0])
+
+
+def tt_dot_product_batch(query, targets):
+    """tt_dot_product_batch (614-623) -> f32 [len(targets)]; one target of another shape fails the whole call"""
+    return tt_similarity(SIM_DOT, query, list(targets))[0]
+
+
+def tt_cosine_similarity_batch(query, targets):
+    """tt_cosine_similarity_batch (591-606)"""
+    return tt_similarity(SIM_COSINE, query, list(targets))[0]
+
+
+def tt_euclidean_distance_batch(query, targets):
+    """tt_euclidean_distance_batch (631-646)"""
+    return tt_similarity(SIM_EUCLIDEAN, query, list(targets))[0]
+
+
+class TTDeviceSet:
+    """n trains of one shape in device memory (torch tensors), as nmn_tt_decompose_device leaves them: ranks int32 [n][d + 1], cores
+    f32 [n * stride], train i at core_off[i] (int64 [n + 1]) or at i * stride; status int32 [n] or None."""
+
+    def __init__(self, ranks, cores, stride, core_off=None, status=None):
+        self.ranks, self.cores, self.stride, self.core_off, self.status = ranks, cores, int(stride), core_off, status
+        self.n = int(ranks.shape[0])
+        if cores.numel() < self.n * self.stride:
+            raise _bad("TT similarity: cores must hold n * stride floats")
+
+    def _args(self):
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+        return ptr(self.ranks), ptr(self.core_off), ptr(self.cores), self.stride, ptr(self.status), self.n
+
+
+def _stream(stream):
+    import torch
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream if stream is None else stream)
+
+
+def tt_self_dot_device(shape, trains, out=None, stream=None):
+    """nmn_tt_self_dot_device: enqueued on the stream, not waited for -> f32 tensor [n] on the device"""
+    import torch
+    sh = np.asarray(shape, dtype=np.uint32)
+    if out is None:
+        out = torch.empty(trains.n, dtype=torch.float32, device=trains.cores.device)
+    _capi.check(_capi.load().nmn_tt_self_dot_device(_p(sh), sh.size, *trains._args(), C.c_void_p(out.data_ptr()), _stream(stream)))
+    return out
+
+
+def tt_similarity_device(op, shape, queries, targets, self_q=None, self_t=None, out=None, stream=None):
+    """nmn_tt_similarity_device on two TTDeviceSets: enqueued on the stream, not waited for -> f32 tensor [nq][nt] on the device.
+    self_q / self_t: what tt_self_dot_device returned for the sets (cosine and Euclidean need both)."""
+    import torch
+    op = SIM_OPS.get(op, op)
+    sh = np.asarray(shape, dtype=np.uint32)
+    if out is None:
+        out = torch.empty((queries.n, targets.n), dtype=torch.float32, device=queries.cores.device)
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+    _capi.check(_capi.load().nmn_tt_similarity_device(int(op), _p(sh), sh.size, *queries._args(), *targets._args(), ptr(self_q),
+                                                      ptr(self_t), C.c_void_p(out.data_ptr()), _stream(stream)))
+    return out
+
+
 PRESETS = {"for_dim": 0, "high_compression": 1, "high_accuracy": 2}
 
 
