@@ -1206,7 +1206,9 @@ extern "C" nmn_status nmn_ivf_search(nmn_ivf* ivf, const float* queries, uint32_
             if (!cut_inside_run || run_ends_inside || cnt < kk || kk >= n_rows) break;  // nothing more to learn / fetch
             kk = std::min<uint64_t>(kk * 2, n_rows);
         }
-        for (uint32_t i = 0; i < cnt; i++) tmp_dist[i] = -tmp_dist[i];
+        // (0 - score, not -score: the scan's keys hold a zero distance as +0.0 (score_to_key folds -0.0 into it), and the reference's
+        //  distance of a vector from itself is +0.0, never -0.0 — tests/test_gpu_knobs.py compares the bits)
+        for (uint32_t i = 0; i < cnt; i++) tmp_dist[i] = 0.0f - tmp_dist[i];
         // 3. equal distances keep candidate order: probe order of the cluster, then id (stable sort, ivf.rs:402)
         bool any_tie = false;
         for (uint32_t i = 1; i < cnt && !any_tie; i++) any_tie = tmp_dist[i] == tmp_dist[i - 1];
@@ -1807,11 +1809,11 @@ __global__ __launch_bounds__(256) void ivf_pad_kernel(uint32_t* __restrict__ sco
 }
 
 // slots [0, k) of query blockIdx.y: candidate j (as selected) -> its segment (the last one starting at or before j that holds
-// rows) -> list-major row -> id; distance = -score (Flat: as the host call negates its list scans' scores; PQ / Binary: 0 - score,
-// as codec_search does); the rest id UINT64_MAX, distance +inf.  totals == nullptr: nothing found (empty index, nprobe 0).
+// rows) -> list-major row -> id; distance = 0 - score (as the host call and codec_search form it); the rest id UINT64_MAX, distance +inf.  totals == nullptr: nothing found (empty index, nprobe 0).
 __global__ __launch_bounds__(256) void ivf_idmap_kernel(const uint4* __restrict__ segs, uint32_t np, const uint64_t* __restrict__ totals,
                                                         const uint32_t* __restrict__ perm, uint64_t id_base, int flat, uint32_t k,
                                                         uint64_t* __restrict__ ids, float* __restrict__ dist, uint32_t* __restrict__ counts) {
+    (void)flat;
     const uint32_t q = blockIdx.y;
     const uint32_t cnt = totals ? (uint32_t)min<uint64_t>(k, totals[q]) : 0u;
     ids += (size_t)q * k;
@@ -1829,7 +1831,7 @@ __global__ __launch_bounds__(256) void ivf_idmap_kernel(const uint4* __restrict_
             }
             while (sq[lo].z == 0 || cand - sq[lo].w >= sq[lo].z) lo--;  // (never below 0: cand < total)
             ids[i] = id_base + perm[sq[lo].y + (cand - sq[lo].w)];
-            dist[i] = flat ? -s : 0.0f - s;
+            dist[i] = 0.0f - s;  // (a zero distance comes back as +0.0 whatever the sign of the zero score, as the host call's)
         } else {
             ids[i] = UINT64_MAX;
             dist[i] = __builtin_inff();
