@@ -900,6 +900,32 @@ nmn_status nmn_hnsw_search_tt_device(nmn_hnsw* h, const uint32_t* shape, uint32_
 nmn_status nmn_hnsw_insert_tt(nmn_hnsw* h, const uint32_t* shape, uint32_t n_cores, const uint32_t* ranks, const uint64_t* core_off,
                               const float* cores, uint64_t n, uint64_t* ids_out);
 
+/* ---- EmbeddingStorage::TensorTrain nodes (docs/hnsw.md §24) -------------------------------------------------------------- */
+
+/* HNSWIndex::insert_embedding(EmbeddingStorage::from(tt)) (hnsw.rs:1256-1259, 1913-2051) for each of the n trains in order:
+ * TensorTrain(TTVectorCached) nodes, which keep the train and norm = tt_norm(tt) (276-289) — NOT what nmn_hnsw_insert_tt makes.
+ * The trains cross as they do there; validation, its texts, max_nodes and the all-or-nothing batch are that entry's, and the
+ * product of the shape must be nmn_hnsw_dim(h) (NMN_ERR_DIMENSION_MISMATCH).  Calls may bring different shapes of that product:
+ * every node keeps its own.  Dense handles only: quantized and binary handles are NMN_ERR_CONFIGURATION.  Like nmn_hnsw_insert,
+ * the entry tests no row for finiteness: a train whose reconstruction holds a NaN or an infinity is inserted as it is.
+ * Such a node is scored (a) by a dense or sparse query as a Dense node of its reconstruction, with the cached tt_norm as its
+ * magnitude under Cosine; (b) by a TT query as 1 - tt_dot_product(node, query) / (node.norm * query_norm), 1.0 when a norm is
+ * below 1e-10 or the shapes differ, nothing reconstructed; (c) in pruning, T x T under Cosine by the dot of the reconstructions over
+ * the cached norms (1.0 when one is below 1e-10), every other arm by the Dense / Sparse arithmetic on the reconstruction with
+ * simd::magnitude.  nmn_hnsw_get_vector returns tt_reconstruct; nmn_hnsw_memory_stats counts tt_count and 4 storage_size() bytes;
+ * nmn_hnsw_save refuses such a handle (NMN_ERR_CONFIGURATION) before the file is touched; nmn_hnsw_insert_bulk walks on the host. */
+nmn_status nmn_hnsw_insert_embedding_tt(nmn_hnsw* h, const uint32_t* shape, uint32_t n_cores, const uint32_t* ranks,
+                                        const uint64_t* core_off, const float* cores, uint64_t n, uint64_t* ids_out);
+/* get_embedding of a TensorTrain node: *storage = the floats of its cores, UINT64_MAX for a node that is not a TT node.  Every
+ * array is nullable: shape_out [8], *n_cores_out, ranks_out [9], cores_out [cap] (cap >= *storage: NMN_ERR_BUFFER_TOO_SMALL otherwise). */
+nmn_status nmn_hnsw_tt_row(nmn_hnsw* h, uint64_t node, uint32_t* shape_out, uint32_t* n_cores_out, uint32_t* ranks_out, float* cores_out,
+                           uint64_t cap, uint64_t* storage);
+/* The limits of the device walk of TT queries on a handle with TensorTrain nodes, each output nullable: the largest rank of any TT
+ * node; the TT nodes above nmn_tt_limits (max_rank, max_storage) — with any, every TT query walks on the host; and the floats of
+ * LDS a call with this ef (0: ef_search) may spend on (its largest train's cores + 2 x max_node_rank x its largest rank).  A call
+ * above them: nmn_hnsw_search_tt walks on the host with the same bits, nmn_hnsw_search_tt_device is NMN_ERR_INVALID_ARGUMENT. */
+nmn_status nmn_hnsw_tt_walk_limits(nmn_hnsw* h, uint32_t ef, uint32_t* max_node_rank, uint64_t* nodes_above_limits, uint32_t* lds_floats);
+
 /* ---- tt_decompose: from a dense vector and a TTConfig to a train (docs/hnsw.md §21) --------------------------------------- */
 
 /* A TTConfig (tensor_train.rs:41-49) crosses this interface as its parts: shape[n_cores], max_rank, tolerance.

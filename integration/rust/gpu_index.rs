@@ -394,6 +394,20 @@ impl GpuHnswIndex {
         check(st, self.dim, shape.iter().map(|&x| x as usize).product())
     }
 
+    /// HNSWIndex::insert_embedding(EmbeddingStorage::from(tt)) (nmn_hnsw_insert_embedding_tt): a TensorTrain node, which keeps the
+    /// train and its cached tt_norm and is scored by its own rules (docs/hnsw.md §24) — not the Dense node `insert_tt` makes.
+    /// Returns the node id.
+    pub fn insert_embedding_tt(&self, tt: &tensor_compress::TTVector) -> Result<usize> {
+        let (shape, ranks, cores) = Self::tt_parts(tt);
+        let off = [0u64, cores.len() as u64];
+        let mut id = u64::MAX;
+        let st = unsafe {
+            ffi::nmn_hnsw_insert_embedding_tt(self.raw, shape.as_ptr(), shape.len() as u32, ranks.as_ptr(), off.as_ptr(), cores.as_ptr(), 1, &mut id)
+        };
+        check(st, self.dim, shape.iter().map(|&x| x as usize).product())?;
+        Ok(id as usize)
+    }
+
     /// `search` for several queries in ONE launch, each with its own k and ef (nmn_hnsw_search_multi; ef 0 = ef_search).  Answer i is
     /// bit for bit what `search_with_ef(q_i, k_i, ef_i)` returns alone.  Concurrent callers of `search` / `search_multi` are
     /// coalesced into such launches by the library (docs/hnsw.md §11).

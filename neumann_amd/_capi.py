@@ -264,6 +264,9 @@ SIGNATURES = {
                                        C.POINTER(SearchStats)]),
     "nmn_hnsw_search_tt_device": (C.c_int32, [vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp]),
     "nmn_hnsw_insert_tt": (C.c_int32, [vp, vp, C.c_uint32, vp, vp, vp, C.c_uint64, vp]),
+    "nmn_hnsw_insert_embedding_tt": (C.c_int32, [vp, vp, C.c_uint32, vp, vp, vp, C.c_uint64, vp]),
+    "nmn_hnsw_tt_row": (C.c_int32, [vp, C.c_uint64, vp, vp, vp, vp, C.c_uint64, vp]),
+    "nmn_hnsw_tt_walk_limits": (C.c_int32, [vp, C.c_uint32, vp, vp, vp]),
     "nmn_tt_config_for_dim": (C.c_int32, [C.c_uint64, C.c_uint32, u32p, u32p, u32p, C.POINTER(C.c_float)]),
     "nmn_tt_max_storage": (C.c_uint64, [vp, C.c_uint32, C.c_uint32]),
     "nmn_tt_decompose": (C.c_int32, [vp, C.c_uint64, C.c_uint64, vp, C.c_uint32, C.c_uint32, C.c_float, vp, vp, vp, vp, C.c_uint64]),

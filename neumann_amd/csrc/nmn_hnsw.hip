@@ -207,7 +207,42 @@ struct WalkShape {
     bool sp_only = false;  // qkind 3: every query is kind 1, so the query region need not hold a dense query
     // TT queries (docs/hnsw.md §17): the launch scores under Cosine whatever the handle's metric is (cosine_distance_tt_with_norm)
     bool cosine = false;
+    // TT queries on a handle with TensorTrain nodes (docs/hnsw.md §24): the call's trains in DEVICE memory, the TTN launches
+    const struct TTWalkQueries* tt = nullptr;
 };
+
+// The trains of one TT-query call as the TTN launches read them (SearchArgs' ttq_* fields): ranks_dev [nq][n_cores + 1] or null
+// (ranks_u for every query), off_dev [nq + 1] or null (query i at i * stride); max_rank / max_storage over the call's queries.
+struct TTWalkQueries {
+    const float* cores_dev = nullptr;
+    const uint32_t* ranks_dev = nullptr;
+    const uint64_t* off_dev = nullptr;
+    uint64_t stride = 0;
+    uint32_t n_cores = 0, max_rank = 1, max_storage = 0;
+    uint32_t shape[kTTMaxCores] = {};
+    uint32_t ranks_u[kTTMaxCores + 1] = {};
+};
+
+// The LDS a TTN launch has (docs/hnsw.md §24): the query region, the stage and ctrl, the TT region — the query's ranks and cores
+// and two Gram buffers of (largest node rank x largest query rank) floats — and both heaps, 64 KiB in all.  The candidate heap
+// takes what is left (no answer depends on its size); a call is walked on the device when at least kTTWalkMinCand entries are.
+constexpr uint32_t kTTWalkMinCand = 64;
+constexpr size_t kWalkLdsBytes = 64 * 1024;
+inline size_t walk_fixed_bytes(uint32_t qlds) { return (size_t)qlds * 4 + 32 * 4 + 32 * 4 + 4 * 4; }
+// floats left for (query cores + 2 x node rank x query rank) in a launch of this handle with `ef`; 0: nothing fits
+uint32_t tt_walk_lds_floats(const nmn_hnsw* h, uint32_t ef_eff) {
+    const uint32_t n = (uint32_t)h->level.size(), dim8 = (h->dim + 7u) & ~7u;
+    const uint32_t rmax = h->lds_rcap ? h->lds_rcap : kLdsResultsMax;
+    const bool in_lds = n == 0 || results_need(ef_eff, n) <= rmax + 1;  // (results_fit_lds: otherwise the spill launch alone walks)
+    const size_t used = walk_fixed_bytes(dim8) + 16 * 4 + 4 * 4 + (in_lds ? ((size_t)results_need(ef_eff, n) + kTTWalkMinCand) * sizeof(Ent) : 0);
+    return used >= kWalkLdsBytes ? 0u : (uint32_t)((kWalkLdsBytes - used) / 4);
+}
+// whether the TTN launches serve a call with these trains on this handle
+bool tt_walk_on_device(const nmn_hnsw* h, uint32_t ef_eff, uint32_t q_max_rank, uint64_t q_max_storage) {
+    if (h->n_tt_big) return false;  // a node above nmn_tt_limits
+    const uint64_t need = q_max_storage + 2ull * h->tt_max_rank * q_max_rank;
+    return need <= tt_walk_lds_floats(h, ef_eff);
+}
 
 bool results_fit_lds(const nmn_hnsw* h, uint32_t ef_eff, uint32_t n) {
     const uint32_t rmax = h->lds_rcap ? h->lds_rcap : kLdsResultsMax;
@@ -233,7 +268,7 @@ nmn_status enqueue_walk_locked(nmn_hnsw* h, nmn_hnsw::Scratch* sc, const float* 
     const uint32_t qlds = w.qkind == 1 || (w.qkind == 3 && w.sp_only) ? std::max<uint32_t>(2u * w.sp_max, 2u)
                           : w.qkind == 3                              ? std::max<uint32_t>(dim8, 2u * w.sp_max)
                                                                       : dim8;
-    const uint32_t ccap = cand_cap(w.ef_lds, h->lds_ccap, w.qkind == 1 || w.qkind == 3 ? qlds : h->dim, n);
+    uint32_t ccap = cand_cap(w.ef_lds, h->lds_ccap, w.qkind == 1 || w.qkind == 3 ? qlds : h->dim, n);
     const uint32_t s_rcap = w.rcap_all, s_ccap = std::max<uint32_t>(n, 1);
     const uint64_t region = (uint64_t)s_rcap + s_ccap;
     const uint32_t regions = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint32_t>(chunk, 64), (256ull << 20) / (region * sizeof(Ent))));
@@ -260,6 +295,29 @@ nmn_status enqueue_walk_locked(nmn_hnsw* h, nmn_hnsw::Scratch* sc, const float* 
     a.nrec = mix ? (const uint4*)h->d_nrec.p : nullptr;
     a.nent = mix ? (const uint2*)h->d_nent.p : nullptr;
     a.kind_u = w.qkind == 3 ? 0u : (uint32_t)w.qkind;
+    const bool ttn = w.tt != nullptr;
+    size_t tt_bytes = 0;
+    if (ttn) {  // the caller checked tt_walk_on_device: the TT region and kTTWalkMinCand candidates fit beside the results heap
+        a.tt_slot = (const uint32_t*)h->d_ttslot.p;
+        a.tt_rec = (const TTNodeDev*)h->d_ttrec.p;
+        a.tt_cores = (const float*)h->d_ttcores.p;
+        a.tt_pool = h->tt_cores.size();
+        a.ttq_ncores = w.tt->n_cores;
+        a.ttq_cap = w.tt->max_storage;
+        a.tt_gcap = std::max<uint32_t>(h->tt_max_rank * w.tt->max_rank, 1);
+        a.ttq_stride = w.tt->stride;
+        memcpy(a.ttq_shape, w.tt->shape, sizeof a.ttq_shape);
+        memcpy(a.ttq_ranks_u, w.tt->ranks_u, sizeof a.ttq_ranks_u);
+        tt_bytes = (size_t)tt_region_floats(a.ttq_cap, a.tt_gcap) * 4;
+        if (walk_fixed_bytes(qlds) + tt_bytes > kWalkLdsBytes)
+            return set_error(NMN_ERR_INVALID_ARGUMENT, "HNSW: the query's train does not fit the walk's LDS");
+        const size_t heaps = kWalkLdsBytes - walk_fixed_bytes(qlds) - tt_bytes;
+        if (w.n_lds) {
+            if (heaps < ((size_t)w.rcap_lds + 1) * sizeof(Ent))
+                return set_error(NMN_ERR_INVALID_ARGUMENT, "HNSW: the TT region leaves no LDS for the heaps");
+            ccap = std::min<uint32_t>(ccap, (uint32_t)(heaps / sizeof(Ent) - w.rcap_lds));
+        }
+    }
     for (uint32_t q0 = 0; q0 < nq; q0 += chunk) {
         const uint32_t nb = std::min<uint32_t>(chunk, nq - q0);
         const uint32_t nl = w.n_lds > q0 ? std::min<uint32_t>(w.n_lds - q0, nb) : 0;  // the chunk's queries that start in LDS: its first nl
@@ -276,15 +334,20 @@ nmn_status enqueue_walk_locked(nmn_hnsw* h, nmn_hnsw::Scratch* sc, const float* 
         a.out_ids = o_ids + (size_t)q0 * kstride;
         a.out_scores = o_sc + (size_t)q0 * kstride;
         a.out_counts = o_cnt + q0;
+        if (ttn) {
+            a.ttq_ranks = w.tt->ranks_dev ? w.tt->ranks_dev + (size_t)q0 * (w.tt->n_cores + 1) : nullptr;
+            a.ttq_off = w.tt->off_dev ? w.tt->off_dev + q0 : nullptr;
+            a.ttq_cores = w.tt->off_dev ? w.tt->cores_dev : w.tt->cores_dev + (size_t)q0 * w.tt->stride;
+        }
         HN_TRY(hipMemsetAsync(sc->vis.p, 0, (size_t)nb * vwords * 4, s));
-        const size_t fixed = (size_t)qlds * 4 + 32 * 4 + 32 * 4 + 4 * 4;
+        const size_t fixed = walk_fixed_bytes(qlds) + tt_bytes;
         if (nl) {
             HN_TRY(hipMemsetAsync(a.flags, 0, (size_t)nl * 4, s));
             a.nq = nl;
             a.rcap = w.rcap_lds;
             a.ccap = ccap;
             const size_t lds = fixed + ((size_t)a.rcap + a.ccap) * sizeof(Ent);
-            launch_search(false, q8, bin, perq, w.qkind, mix, nl, lds, s, a);
+            launch_search(false, q8, bin, perq, w.qkind, mix, ttn, nl, lds, s, a);
             HN_TRY(hipGetLastError());
         }
         if (nl < nb)  // results heaps no wave can keep in LDS: these queries go straight to the spill launch
@@ -292,7 +355,7 @@ nmn_status enqueue_walk_locked(nmn_hnsw* h, nmn_hnsw::Scratch* sc, const float* 
         a.nq = nb;
         a.rcap = s_rcap;
         a.ccap = s_ccap;
-        launch_search(true, q8, bin, perq, w.qkind, mix, std::min(regions, nb), fixed, s, a);
+        launch_search(true, q8, bin, perq, w.qkind, mix, ttn, std::min(regions, nb), fixed, s, a);
         HN_TRY(hipGetLastError());
     }
     return NMN_OK;
@@ -575,7 +638,7 @@ extern "C" nmn_status nmn_hnsw_destroy(nmn_hnsw* h) {
         drop(s->ttkind);
         for (DevBuf* b : {&s->sq_off, &s->sq_ent, &s->sq_mag, &s->sq_dup, &s->sq_dense, &s->sq_status}) drop(*b);
     }
-    for (DevBuf* b : {&h->d_l0, &h->d_l0cnt, &h->d_upidx, &h->d_up, &h->d_upcnt, &h->d_nrec, &h->d_nent, &h->d_live, &h->bk_lv, &h->bk_vis, &h->bk_out, &h->bk_patch, &h->hq, &h->hids, &h->hsc, &h->hcnt, &h->hkef,
+    for (DevBuf* b : {&h->d_l0, &h->d_l0cnt, &h->d_upidx, &h->d_up, &h->d_upcnt, &h->d_nrec, &h->d_nent, &h->d_wnorms, &h->d_ttslot, &h->d_ttrec, &h->d_ttcores, &h->d_live, &h->bk_lv, &h->bk_vis, &h->bk_out, &h->bk_patch, &h->hq, &h->hids, &h->hsc, &h->hcnt, &h->hkef,
                        &h->hsp_off, &h->hsp_ent, &h->hqmag,
                        &h->hxmeta, &h->hxsim, &h->hxoids, &h->hxosc, &h->hxocnt, &h->hxsort, &h->htt_cores, &h->htt_ranks, &h->htt_off,
                        &h->htt_skip})
@@ -646,9 +709,12 @@ extern "C" nmn_status nmn_hnsw_memory_stats(nmn_hnsw* h, nmn_hnsw_memstats* out)
     } else {
         // a Sparse node: SparseVector::memory_bytes (sparse_vector.rs:1064-1068) = size_of::<SparseVector>() (56 on a 64-bit
         // target) + 4 capacity + 4 capacity, the capacities taken as the lengths (what a cloned vector has; docs/hnsw.md §15)
+        // a TensorTrain node: 4 storage_size() (hnsw.rs:1230), the sum of its cores' lengths
+        const uint64_t n_tt = h->tt_nodes.size();
         out->sparse_count = h->n_sparse;
-        out->dense_count = n - h->n_sparse;
-        out->embedding_bytes = (n - h->n_sparse) * 4ull * h->dim + h->n_sparse * 56ull + 8ull * h->sp_pos.size();
+        out->tt_count = n_tt;
+        out->dense_count = n - h->n_sparse - n_tt;
+        out->embedding_bytes = (n - h->n_sparse - n_tt) * 4ull * h->dim + h->n_sparse * 56ull + 8ull * h->sp_pos.size() + 4ull * h->tt_cores.size();
     }
     return NMN_OK;
 }
@@ -690,6 +756,7 @@ extern "C" uint64_t nmn_hnsw_hbm_bytes(nmn_hnsw* h) {
     if (!h) return 0;
     std::shared_lock<std::shared_mutex> g(h->rw);
     uint64_t t = h->d_l0.cap + h->d_l0cnt.cap + h->d_upidx.cap + h->d_up.cap + h->d_upcnt.cap + h->d_nrec.cap + h->d_nent.cap + h->d_live.cap;
+    t += h->d_wnorms.cap + h->d_ttslot.cap + h->d_ttrec.cap + h->d_ttcores.cap;  // (a handle with TensorTrain nodes, docs/hnsw.md §24)
     t += h->bk_lv.cap + h->bk_vis.cap + h->bk_out.cap + h->bk_patch.cap;  // (what nmn_hnsw_insert_bulk keeps between calls)
     uint64_t a = 0, b = 0, c = 0;
     if (h->vectors && nmn_index_hbm_bytes(h->vectors, &a, &b, &c) == NMN_OK) t += a + b + c;
@@ -1765,7 +1832,26 @@ namespace {
 // walk's magnitude of the query (tt_norm, 0.0 when it is below 1e-10: the `== 0.0` tests below then return the reference's 1.0).
 // Dense: simd::dot_product and simd::magnitude; Sparse: dot_dense and SparseVector::magnitude(); Quantized: dot_dense and
 // magnitude_immutable — Cosine on every handle.
-inline float tt_node_distance(const nmn_hnsw* h, uint32_t node, const float* q, float qmag, float qsum) {
+// A TensorTrain node (1201-1209; docs/hnsw.md §24): tt_dot_product(node, query) — node first — over the product of the cached norm
+// and the query's, 1.0 when the shapes differ or the node's norm is below 1e-10; nothing is reconstructed.  (qmag == 0.0 stands
+// for a query norm below 1e-10, which is 1.0 for every node: the first test of the reference.)
+struct TTHostQuery {
+    const uint32_t* shape;
+    uint32_t n_cores;
+    const uint32_t* ranks;
+    const float* cores;
+};
+inline float tt_node_distance(const nmn_hnsw* h, uint32_t node, const float* q, float qmag, float qsum, const TTHostQuery& tq) {
+    if (node_is_tt(h, node)) {
+        if (qmag == 0.0f) return 1.0f;
+        const nmn_hnsw::TTNode& t = node_train(h, node);
+        if (t.n_cores != tq.n_cores || memcmp(t.shape, tq.shape, (size_t)t.n_cores * 4) != 0) return 1.0f;
+        const float dot = tt_dot_host(t.shape, t.n_cores, t.ranks, h->tt_cores.data() + t.off, tq.ranks, tq.cores);
+        if (t.norm < 1e-10f) return 1.0f;
+        const float den = t.norm * qmag;
+        const float sim = dot / den;
+        return 1.0f - sim;
+    }
     if (h->storage == NMN_HNSW_STORAGE_QUANTIZED) {
         HQ hq;
         hq.mag = qmag;
@@ -1785,11 +1871,11 @@ inline float tt_node_distance(const nmn_hnsw* h, uint32_t node, const float* q, 
 }
 
 // search_tt_with_ef of one prepared train on the host
-void host_search_one_tt(const nmn_hnsw* h, const float* q, float norm, uint32_t k, uint64_t ef, HostVisited& vis, uint64_t* ids,
-                        float* scores, uint32_t* count, uint64_t* evals) {
+void host_search_one_tt(const nmn_hnsw* h, const float* q, float norm, const TTHostQuery& tq, uint32_t k, uint64_t ef, HostVisited& vis,
+                        uint64_t* ids, float* scores, uint32_t* count, uint64_t* evals) {
     const float qmag = tt_walk_magnitude(norm);
     const float qsum = h->storage == NMN_HNSW_STORAGE_QUANTIZED ? h_sum8(q, h->dim) : 0.0f;
-    host_walk_one(h, [&](uint32_t node) { return tt_node_distance(h, node, q, qmag, qsum); }, k, ef, vis, ids, scores, count, evals,
+    host_walk_one(h, [&](uint32_t node) { return tt_node_distance(h, node, q, qmag, qsum, tq); }, k, ef, vis, ids, scores, count, evals,
                   NMN_METRIC_COSINE);
 }
 
@@ -1797,13 +1883,16 @@ void host_search_one_tt(const nmn_hnsw* h, const float* q, float norm, uint32_t 
 // knows "a dense query whose Cosine magnitude is given": kind 2.  A quantized handle takes the QK = 2 launch; a handle with Sparse
 // nodes the MIX launch with kind 2 for every query (mix_dense_query with the given magnitude), under every metric of the handle;
 // a dense handle the per-query form QK = 3 on dense rows with a kind array of 2s (entries = false, mag_given = true) — no
-// instantiation is added.  Caller holds rw (shared) and sc->mu.
+// instantiation is added.  A handle with TensorTrain nodes (tt set; the caller checked tt_walk_on_device): the same per-query form
+// with the TTN launches, sparse nodes or not (docs/hnsw.md §24).  Caller holds rw (shared) and sc->mu.
 nmn_status enqueue_tt_walk_locked(nmn_hnsw* h, nmn_hnsw::Scratch* sc, const float* q_dev, const float* mag_dev, uint32_t nq, uint32_t k,
-                                  uint32_t ef, uint64_t* o_ids, float* o_sc, uint32_t* o_cnt, hipStream_t s) {
+                                  uint32_t ef, uint64_t* o_ids, float* o_sc, uint32_t* o_cnt, hipStream_t s,
+                                  const TTWalkQueries* tt = nullptr) {
     WalkShape w = uniform_shape(h, nq, k, ef);
     w.cosine = true;
     w.qmag = mag_dev;
-    if (h->storage == NMN_HNSW_STORAGE_QUANTIZED || h->n_sparse > 0) {
+    w.tt = tt;
+    if (!tt && (h->storage == NMN_HNSW_STORAGE_QUANTIZED || h->n_sparse > 0)) {
         w.qkind = 2;
     } else {
         bool synced = false;
@@ -1846,7 +1935,7 @@ extern "C" nmn_status nmn_hnsw_search_tt(nmn_hnsw* h, const uint32_t* shape, uin
     if (core_off[nq] > core_off[0] && !cores) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
     if ((st = tt_dim_check(h, b)) != NMN_OK) return st;
     b.cores = cores;
-    const bool on_host = host_search_forced();
+    bool on_host = host_search_forced();
     const uint32_t dim = h->dim;
     uint64_t evals = 0;
     uint32_t spilled = 0;
@@ -1855,10 +1944,29 @@ extern "C" nmn_status nmn_hnsw_search_tt(nmn_hnsw* h, const uint32_t* shape, uin
     auto host_one = [&](uint32_t q) {  // preparation and walk of train q on the host, into the caller's row
         tt_reconstruct_host(shape, n_cores, b.ranks_of(q), cores + core_off[q], hrow.data());
         const float norm = tt_norm_host(shape, n_cores, b.ranks_of(q), cores + core_off[q]);
-        host_search_one_tt(h, hrow.data(), norm, k, ef ? ef : h->cfg.ef_search, vis, out_ids + (size_t)q * k, out_scores + (size_t)q * k,
-                           out_counts + q, &evals);
+        const TTHostQuery tq{shape, n_cores, b.ranks_of(q), cores + core_off[q]};
+        host_search_one_tt(h, hrow.data(), norm, tq, k, ef ? ef : h->cfg.ef_search, vis, out_ids + (size_t)q * k,
+                           out_scores + (size_t)q * k, out_counts + q, &evals);
     };
     std::shared_lock<std::shared_mutex> g(h->rw);
+    // a handle with TensorTrain nodes (docs/hnsw.md §24): the TTN launches when every node and every train of the call is within the
+    // walk's LDS, the host walk — same bits — otherwise
+    TTWalkQueries tw;
+    const bool tt_nodes = !h->tt_nodes.empty();
+    if (tt_nodes && !on_host) {
+        tw.n_cores = n_cores;
+        memcpy(tw.shape, b.shape, sizeof tw.shape);
+        uint64_t smax = 0;
+        for (uint32_t q = 0; q < nq; q++) {
+            smax = std::max(smax, b.storage_of(q));
+            for (uint32_t c = 0; c <= n_cores; c++) tw.max_rank = std::max(tw.max_rank, b.ranks_of(q)[c]);
+        }
+        const uint32_t ef_eff = std::max<uint32_t>(ef ? ef : h->cfg.ef_search, k);
+        if (tt_walk_on_device(h, ef_eff, tw.max_rank, smax))
+            tw.max_storage = (uint32_t)smax;
+        else
+            on_host = true;
+    }
     if (on_host) {
         for (uint32_t q = 0; q < nq; q++) host_one(q);
     } else {
@@ -1904,8 +2012,13 @@ extern "C" nmn_status nmn_hnsw_search_tt(nmn_hnsw* h, const uint32_t* shape, uin
                     HN_TRY(hipMemcpyAsync((float*)sc->ttmag.p + q, &mags[q], 4, hipMemcpyHostToDevice, s));
                 }
             }
+            if (tt_nodes) {  // the trains as they were sent for the preparation: the kernel reads them again
+                tw.cores_dev = (const float*)h->htt_cores.p;
+                tw.ranks_dev = (const uint32_t*)h->htt_ranks.p;
+                tw.off_dev = (const uint64_t*)h->htt_off.p;
+            }
             st = enqueue_tt_walk_locked(h, sc, (const float*)sc->ttq.p, (const float*)sc->ttmag.p, nq, k, ef, (uint64_t*)h->hids.p,
-                                        (float*)h->hsc.p, (uint32_t*)h->hcnt.p, s);
+                                        (float*)h->hsc.p, (uint32_t*)h->hcnt.p, s, tt_nodes ? &tw : nullptr);
             if (st != NMN_OK) return st;
             HN_TRY(hipMemcpyAsync(out_ids, h->hids.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost, s));
             HN_TRY(hipMemcpyAsync(out_scores, h->hsc.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, s));
@@ -1953,6 +2066,21 @@ extern "C" nmn_status nmn_hnsw_search_tt_device(nmn_hnsw* h, const uint32_t* sha
                          "TT: the train is above the LDS limits of the device path (nmn_tt_limits); nmn_hnsw_search_tt prepares it on the host");
     if ((st = tt_dim_check(h, b)) != NMN_OK) return st;
     std::shared_lock<std::shared_mutex> g(h->rw);
+    TTWalkQueries tw;
+    const bool tt_nodes = !h->tt_nodes.empty();
+    if (tt_nodes) {  // docs/hnsw.md §24: the TTN launches, or a refusal — there is no host to fall back to
+        tw.n_cores = n_cores;
+        memcpy(tw.shape, b.shape, sizeof tw.shape);
+        memcpy(tw.ranks_u, ranks, (size_t)(n_cores + 1) * 4);
+        for (uint32_t c = 0; c <= n_cores; c++) tw.max_rank = std::max(tw.max_rank, ranks[c]);
+        tw.stride = b.storage_of(0);
+        tw.max_storage = (uint32_t)tw.stride;
+        tw.cores_dev = cores_dev;
+        if (!tt_walk_on_device(h, std::max<uint32_t>(ef ? ef : h->cfg.ef_search, k), tw.max_rank, tw.stride))
+            return set_error(NMN_ERR_INVALID_ARGUMENT,
+                             "TT: the index holds TensorTrain nodes and the call is above the LDS limits of their device walk "
+                             "(nmn_hnsw_tt_walk_limits); nmn_hnsw_search_tt walks it on the host");
+    }
     HN_TRY(hipSetDevice(h->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     nmn_hnsw::Scratch* sc = scratch_of(h, s);
@@ -1963,7 +2091,7 @@ extern "C" nmn_status nmn_hnsw_search_tt_device(nmn_hnsw* h, const uint32_t* sha
         HN_TRY(grow(sc->ttmag, (size_t)nq * 4, s, &synced));
         HN_TRY(launch_tt_prepare(b, cores_dev, nullptr, nullptr, nullptr, (float*)sc->ttq.p, nullptr, (float*)sc->ttmag.p, s));
         st = enqueue_tt_walk_locked(h, sc, (const float*)sc->ttq.p, (const float*)sc->ttmag.p, nq, k, ef, out_ids_dev, out_scores_dev,
-                                    out_counts_dev, s);
+                                    out_counts_dev, s, tt_nodes ? &tw : nullptr);
         if (st != NMN_OK) return st;
     }
     return record_search(h, s);
@@ -1988,6 +2116,68 @@ extern "C" nmn_status nmn_hnsw_insert_tt(nmn_hnsw* h, const uint32_t* shape, uin
     st = nmn_tt_reconstruct(shape, n_cores, ranks, core_off, cores, (uint32_t)n, rows.data());
     if (st != NMN_OK) return st;
     return insert_rows(h, rows.data(), n, nullptr, nullptr, ids_out);
+}
+
+// insert_embedding(EmbeddingStorage::from(tt)) (hnsw.rs:1256-1259, 1913-2051) for each of the n trains in order: TensorTrain nodes.
+// The reconstruction (the row of the flat index, the insert-time query) and the raw tt_norm come from nmn_tt_reconstruct /
+// nmn_tt_norm — the preparation kernel, the host restatement above nmn_tt_limits.  Like nmn_hnsw_insert, no row is tested for
+// finiteness: a train whose reconstruction holds a NaN or an infinity is inserted as it is.
+extern "C" nmn_status nmn_hnsw_insert_embedding_tt(nmn_hnsw* h, const uint32_t* shape, uint32_t n_cores, const uint32_t* ranks,
+                                                   const uint64_t* core_off, const float* cores, uint64_t n, uint64_t* ids_out) {
+    if (!h || (!core_off && n)) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (const nmn_status sb = refuse_binary(h, "nmn_hnsw_insert_embedding_tt", kBinNodes); sb != NMN_OK) return sb;
+    if (h->storage != NMN_HNSW_STORAGE_DENSE)
+        return set_error(NMN_ERR_CONFIGURATION,
+                         "HNSW: TensorTrain nodes are served on a dense handle only (the Quantized x TensorTrain arms are out of scope)");
+    if (n == 0) return NMN_OK;
+    if (n >= (uint64_t)kNone) return set_error(NMN_ERR_CAPACITY, "HNSW: node ids are 32 bits on the device");
+    TTBatch b;
+    nmn_status st = tt_check(shape, n_cores, ranks, true, core_off, (uint32_t)n, true, &b);
+    if (st != NMN_OK) return st;
+    if ((st = tt_dim_check(h, b)) != NMN_OK) return st;
+    HN_TRY(hipSetDevice(h->device));
+    std::vector<float> rows((size_t)n * h->dim), norms(n);
+    st = nmn_tt_reconstruct(shape, n_cores, ranks, core_off, cores, (uint32_t)n, rows.data());
+    if (st == NMN_OK) st = nmn_tt_norm(shape, n_cores, ranks, core_off, cores, (uint32_t)n, norms.data());
+    if (st != NMN_OK) return st;
+    b.cores = cores;
+    return insert_rows(h, rows.data(), n, nullptr, nullptr, ids_out, false, &b, norms.data());
+}
+
+// get_embedding of a TensorTrain node: *storage = its core floats, UINT64_MAX for a node of another kind; every array nullable,
+// shape_out [8], ranks_out [9], cores_out [cap] (cap >= *storage: NMN_ERR_BUFFER_TOO_SMALL otherwise)
+extern "C" nmn_status nmn_hnsw_tt_row(nmn_hnsw* h, uint64_t node, uint32_t* shape_out, uint32_t* n_cores_out, uint32_t* ranks_out,
+                                      float* cores_out, uint64_t cap, uint64_t* storage) {
+    if (!h || !storage) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    std::shared_lock<std::shared_mutex> g(h->rw);
+    if (node >= h->level.size()) return set_error(NMN_ERR_NOT_FOUND, "HNSW: no such node");
+    if (!node_is_tt(h, (uint32_t)node)) {
+        *storage = UINT64_MAX;
+        return NMN_OK;
+    }
+    const nmn_hnsw::TTNode& t = node_train(h, (uint32_t)node);
+    *storage = t.storage;
+    if (n_cores_out) *n_cores_out = t.n_cores;
+    if (shape_out) memcpy(shape_out, t.shape, (size_t)t.n_cores * 4);
+    if (ranks_out) memcpy(ranks_out, t.ranks, (size_t)(t.n_cores + 1) * 4);
+    if (cores_out) {
+        if (cap < t.storage) return set_error(NMN_ERR_BUFFER_TOO_SMALL, "nmn_hnsw_tt_row");
+        if (t.storage) memcpy(cores_out, h->tt_cores.data() + t.off, (size_t)t.storage * 4);
+    }
+    return NMN_OK;
+}
+
+// The limits of the device walk of TT queries on a handle with TensorTrain nodes (docs/hnsw.md §24), each output nullable: the
+// largest rank of any TT node, the TT nodes above nmn_tt_limits (any: TT queries walk on the host), and the floats a call with this
+// ef (0: the config's ef_search) may spend on its largest train's cores + 2 x max_node_rank x its largest rank.
+extern "C" nmn_status nmn_hnsw_tt_walk_limits(nmn_hnsw* h, uint32_t ef, uint32_t* max_node_rank, uint64_t* nodes_above_limits,
+                                              uint32_t* lds_floats) {
+    if (!h) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    std::shared_lock<std::shared_mutex> g(h->rw);
+    if (max_node_rank) *max_node_rank = h->tt_max_rank;
+    if (nodes_above_limits) *nodes_above_limits = h->n_tt_big;
+    if (lds_floats) *lds_floats = tt_walk_lds_floats(h, ef ? ef : h->cfg.ef_search);
+    return NMN_OK;
 }
 
 namespace {

@@ -253,6 +253,36 @@ nmn_status upload_graph(nmn_hnsw* h, size_t reserve_n, uint32_t reserve_upper, u
         HN_TRY(hipMemcpy(h->d_nrec.p, rec.data(), n * sizeof(uint4), hipMemcpyHostToDevice));
         if (!ent.empty()) HN_TRY(hipMemcpy(h->d_nent.p, ent.data(), ent.size() * sizeof(uint2), hipMemcpyHostToDevice));
     }
+    if (!h->tt_nodes.empty()) {  // docs/hnsw.md §24: the walk's norms, the slot per node, the record per TT node, the pool of cores
+        std::vector<float> wn(n);
+        HN_TRY(hipMemcpy(wn.data(), h->vectors->norms, n * 4, hipMemcpyDeviceToHost));  // simd::magnitude of every row
+        std::vector<uint32_t> slot(n, kNone);
+        std::vector<TTNodeDev> rec(h->tt_nodes.size());
+        for (size_t i = 0; i < n; i++) {
+            if (!node_is_tt(h, (uint32_t)i)) continue;
+            slot[i] = h->tt_slot[i];
+            wn[i] = h->mags[i];  // the cached tt_norm: what cosine_distance_dense / _sparse divide by
+        }
+        for (size_t t = 0; t < rec.size(); t++) {
+            const nmn_hnsw::TTNode& tn = h->tt_nodes[t];
+            TTNodeDev& r = rec[t];
+            memset(&r, 0, sizeof r);
+            r.off_lo = (uint32_t)tn.off;
+            r.off_hi = (uint32_t)(tn.off >> 32);
+            r.n_cores = tn.n_cores;
+            memcpy(&r.norm_bits, &tn.norm, 4);
+            memcpy(r.modes, tn.shape, sizeof r.modes);
+            memcpy(r.ranks, tn.ranks, sizeof r.ranks);
+        }
+        HN_TRY(grow(h->d_wnorms, n * 4, none, &synced));
+        HN_TRY(grow(h->d_ttslot, n * 4, none, &synced));
+        HN_TRY(grow(h->d_ttrec, rec.size() * sizeof(TTNodeDev), none, &synced));
+        HN_TRY(grow(h->d_ttcores, std::max<size_t>(h->tt_cores.size(), 1) * 4, none, &synced));
+        HN_TRY(hipMemcpy(h->d_wnorms.p, wn.data(), n * 4, hipMemcpyHostToDevice));
+        HN_TRY(hipMemcpy(h->d_ttslot.p, slot.data(), n * 4, hipMemcpyHostToDevice));
+        HN_TRY(hipMemcpy(h->d_ttrec.p, rec.data(), rec.size() * sizeof(TTNodeDev), hipMemcpyHostToDevice));
+        if (!h->tt_cores.empty()) HN_TRY(hipMemcpy(h->d_ttcores.p, h->tt_cores.data(), h->tt_cores.size() * 4, hipMemcpyHostToDevice));
+    }
     return NMN_OK;
 }
 
@@ -362,7 +392,7 @@ double ms_since(const std::chrono::steady_clock::time_point& t0) {
 // Whether the device walks for this handle at all, and with which heaps (the search kernel's LDS rule with ef = ef_construction)
 bool bulk_eligible(const nmn_hnsw* h) {
     const uint32_t efc = h->cfg.ef_construction;
-    if (h->storage != NMN_HNSW_STORAGE_DENSE || h->n_sparse || !h->vectors) return false;
+    if (h->storage != NMN_HNSW_STORAGE_DENSE || h->n_sparse || !h->tt_nodes.empty() || !h->vectors) return false;
     if (efc == 0 || efc > kLdsResultsMax) return false;
     if (h->lds_rcap && h->lds_rcap < efc + 1) return false;
     return true;
@@ -610,8 +640,10 @@ namespace hnsw {
 // nmn_hnsw_insert, nmn_hnsw_insert_sparse and nmn_hnsw_insert_auto behind their argument checks.  rows_host: the n rows as the
 // flat index keeps them (to_dense() of a Sparse node).  sp / sp_row (dense handle only, nullable): row i is EmbeddingStorage::Sparse
 // with the entries of sp's vector sp_row[i] when sp_row[i] >= 0, Dense otherwise.
+// tt / tt_norms (dense handle only, nullable): row i is EmbeddingStorage::TensorTrain with train i of the batch, rows_host its
+// tt_reconstruct() and tt_norms[i] its raw tt_norm.
 nmn_status insert_rows(nmn_hnsw* h, const float* rows_host, uint64_t n, const SparseQueries* sp, const int64_t* sp_row,
-                       uint64_t* ids_out, bool bulk) {
+                       uint64_t* ids_out, bool bulk, const TTBatch* tt, const float* tt_norms) {
     std::unique_lock<std::shared_mutex> g(h->rw);
     const uint64_t have = h->level.size();
     if (h->cfg.max_nodes > 0 && have + n > h->cfg.max_nodes) {  // hnsw.rs:1947-1955, text of 102-107; the batch is all or nothing
@@ -699,6 +731,30 @@ nmn_status insert_rows(nmn_hnsw* h, const float* rows_host, uint64_t n, const Sp
             h->mags.push_back(sp->mag[r]);  // SparseVector::magnitude(): what distance_dense / distance_sparse divide by
             h->n_sparse++;
             if (sp->dup[r]) h->n_sparse_dup++;
+        } else if (tt) {  // TTVectorCached::new (hnsw.rs:276-289): the train and norm = tt_norm(tt), the raw value
+            const uint32_t q = (uint32_t)i;
+            nmn_hnsw::TTNode tn;
+            tn.n_cores = tt->n_cores;
+            memcpy(tn.shape, tt->shape, sizeof tn.shape);
+            const uint32_t* r = tt->ranks_of(q);
+            bool big = false;
+            for (uint32_t c = 0; c <= tt->n_cores; c++) {
+                tn.ranks[c] = r[c];
+                h->tt_max_rank = std::max(h->tt_max_rank, r[c]);
+                big = big || r[c] > kTTMaxRank;
+            }
+            tn.storage = tt->storage_of(q);
+            tn.off = h->tt_cores.size();
+            const float* src = tt->cores + tt->offset_of(q);
+            h->tt_cores.insert(h->tt_cores.end(), src, src + tn.storage);
+            tn.norm = tt_norms[i];
+            const float* v = h->rows.data() + (have + i) * dim;
+            tn.row_mag = sqrtf(h_dot8(v, v, dim));  // simd::magnitude of the reconstruction: the T x D pruning arms
+            if (big || tn.storage > kTTMaxStorage) h->n_tt_big++;
+            h->tt_slot.resize(have + i + 1, kNone);
+            h->tt_slot[have + i] = (uint32_t)h->tt_nodes.size();
+            h->tt_nodes.push_back(tn);
+            h->mags.push_back(tn.norm);  // what cosine_distance_dense / _sparse divide by (hnsw.rs:976, 1023)
         } else if (!q8 && !bin) {
             const float* v = h->rows.data() + (have + i) * dim;
             h->mags.push_back(sqrtf(h_dot8(v, v, dim)));  // simd::magnitude, hnsw.rs:198-229

@@ -30,6 +30,9 @@ static_assert(sizeof(nmn_hnsw_config) == 48, "nmn_hnsw_config is part of the fil
 static const char* const kSaveSparseRefusal =
     "HNSW: the index holds sparse nodes (nmn_hnsw_insert_sparse / nmn_hnsw_insert_auto) and index file format version 1 has no place "
     "for their stored entries; saving it would lose them";
+static const char* const kSaveTTRefusal =
+    "HNSW: the index holds TensorTrain nodes (nmn_hnsw_insert_embedding_tt) and index file format version 1 has no place for their "
+    "trains and cached norms; saving it would lose them";
 
 namespace {
 
@@ -88,6 +91,7 @@ namespace nmn {
 nmn_status persist_write_hnsw(nmn_hnsw* h, FILE* fp, const char* path) {
     std::shared_lock<std::shared_mutex> g(h->rw);  // searches may run, inserts wait
     if (h->n_sparse) return set_error(NMN_ERR_CONFIGURATION, kSaveSparseRefusal);
+    if (!h->tt_nodes.empty()) return set_error(NMN_ERR_CONFIGURATION, kSaveTTRefusal);
     const uint64_t n = h->level.size();
     const uint32_t dim = h->dim;
     const bool q8 = h->storage == NMN_HNSW_STORAGE_QUANTIZED;
@@ -332,6 +336,7 @@ extern "C" nmn_status nmn_hnsw_save(nmn_hnsw* h, const char* path) {
     {
         std::shared_lock<std::shared_mutex> g(h->rw);
         if (h->n_sparse) return set_error(NMN_ERR_CONFIGURATION, kSaveSparseRefusal);  // before the file is touched
+        if (!h->tt_nodes.empty()) return set_error(NMN_ERR_CONFIGURATION, kSaveTTRefusal);
     }
     FILE* fp = fopen(path, "wb");
     if (!fp) return persist_io_error("cannot create", path);

@@ -11,6 +11,7 @@
 #include "nmn_internal.h"
 #include "nmn_hnsw_queue.h"
 #include "nmn_hnsw_kernels.h"
+#include "nmn_tt.h"
 
 namespace nmn {
 namespace hnsw {
@@ -70,6 +71,22 @@ struct nmn_hnsw {
     std::vector<uint32_t> sp_pos;
     std::vector<float> sp_val;
     uint64_t n_sparse = 0, n_sparse_dup = 0;  // sparse nodes; those of them with a duplicated position
+    // EmbeddingStorage::TensorTrain nodes of a dense handle (docs/hnsw.md §24).  Empty until the first one is inserted; from then on
+    // one slot per node: tt_slot (kNone: not a TT node) into tt_nodes, whose cores sit back to back in tt_cores.  rows holds
+    // tt_reconstruct() of such a node, mags its cached tt_norm — the RAW norm, what the query side divides by — and the record
+    // keeps simd::magnitude of the row beside it: what the T x D pruning arms divide by.
+    struct TTNode {
+        uint64_t off = 0, storage = 0;  // into tt_cores, in floats
+        uint32_t n_cores = 0;
+        uint32_t shape[nmn::kTTMaxCores] = {};
+        uint32_t ranks[nmn::kTTMaxCores + 1] = {};
+        float norm = 0.0f, row_mag = 0.0f;
+    };
+    std::vector<uint32_t> tt_slot;
+    std::vector<TTNode> tt_nodes;
+    std::vector<float> tt_cores;
+    uint64_t n_tt_big = 0;     // TT nodes above nmn_tt_limits (a rank above max_rank, more than max_storage core floats)
+    uint32_t tt_max_rank = 0;  // the largest rank of any TT node
     std::vector<uint8_t> level;
     std::vector<std::vector<std::vector<uint32_t>>> nbr;  // [node][layer], id-ascending
     uint64_t entry = ~0ull;
@@ -78,6 +95,9 @@ struct nmn_hnsw {
     // device side
     DevBuf d_l0, d_l0cnt, d_upidx, d_up, d_upcnt;
     DevBuf d_nrec, d_nent;  // a handle with sparse nodes: the record per node and the entries of all sparse nodes (SearchArgs)
+    // a handle with TT nodes: the norms the walk divides by (the flat index's, the TT nodes' entries replaced by their tt_norm), the
+    // slot per node, the record per TT node and the pool of their cores (SearchArgs)
+    DevBuf d_wnorms, d_ttslot, d_ttrec, d_ttcores;
     // the live mask (docs/hnsw.md §16): one bit per node, here and in HBM beside the adjacency.  A new node is live;
     // nmn_hnsw_set_node_mask flips bits.  Only nmn_hnsw_cache_search* read it.  live_n: the nodes that have their bit.
     std::vector<uint32_t> live;
@@ -191,7 +211,7 @@ nmn_status upload_graph(nmn_hnsw* h, size_t reserve_n = 0, uint32_t reserve_uppe
 nmn_status upload_codes(nmn_hnsw* h, uint64_t first, uint64_t count);
 nmn_status alloc_codes(nmn_hnsw* h, uint64_t cap, uint64_t have);
 nmn_status insert_rows(nmn_hnsw* h, const float* rows_host, uint64_t n, const SparseQueries* sp, const int64_t* sp_row,
-                       uint64_t* ids_out, bool bulk = false);
+                       uint64_t* ids_out, bool bulk = false, const TTBatch* tt = nullptr, const float* tt_norms = nullptr);
 
 }  // namespace hnsw
 
@@ -217,7 +237,7 @@ struct HostVisited {
 inline SearchArgs graph_args(const nmn_hnsw* h, uint32_t n) {
     SearchArgs a{};
     a.g.corpus = h->vectors ? h->vectors->corpus : nullptr;
-    a.g.norms = h->vectors ? h->vectors->norms : nullptr;
+    a.g.norms = !h->tt_nodes.empty() ? (const float*)h->d_wnorms.p : h->vectors ? h->vectors->norms : nullptr;
     a.g.l0 = (const uint32_t*)h->d_l0.p;
     a.g.l0cnt = (const uint32_t*)h->d_l0cnt.p;
     a.g.up_idx = (const uint32_t*)h->d_upidx.p;

@@ -91,8 +91,13 @@ inline SpView node_entries(const nmn_hnsw* h, uint32_t node) {
     return SpView{h->sp_pos.data() + h->sp_off[node], h->sp_val.data() + h->sp_off[node], h->sp_nnz[node]};
 }
 
+inline bool node_is_tt(const nmn_hnsw* h, uint32_t node) { return node < h->tt_slot.size() && h->tt_slot[node] != kNone; }
+inline const nmn_hnsw::TTNode& node_train(const nmn_hnsw* h, uint32_t node) { return h->tt_nodes[h->tt_slot[node]]; }
+
 // the query side: distance_dense(stored row `node`, q).  A Sparse node (hnsw.rs:1035-1045, 1084-1091, 1136-1138): s.dot_dense(q)
 // with s.magnitude() under Cosine / DotProduct, simd::euclidean_distance(s.to_dense(), q) — the row kept here — under Euclidean.
+// A TensorTrain node (793-796, 1035-1045, 1093-1096; docs/hnsw.md §24): the Dense arithmetic on tt_reconstruct() — the row kept
+// here — with the cached tt_norm as mag_self under Cosine: h->mags holds that norm, so the last line below is the rule.
 inline float node_distance(const nmn_hnsw* h, uint32_t node, const float* q, const HQ& hq) {
     if (h->storage == NMN_HNSW_STORAGE_QUANTIZED)
         return h_q8_distance(h->cfg.distance_metric, h->codes.data() + (size_t)node * h->dim, h->qscale[node], h->qmin[node],
@@ -173,8 +178,24 @@ inline float pair_of_nodes_distance(const nmn_hnsw* h, uint32_t a, uint32_t b) {
         const double c = r < -1.0 ? -1.0 : (r > 1.0 ? 1.0 : r);
         return (float)(1.0 - c);
     }
-    return h_distance(metric, h->rows.data() + (size_t)b * h->dim, h->mags[b], h->rows.data() + (size_t)a * h->dim, h->mags[a],
-                      h->dim);
+    // A TensorTrain node in the pair (docs/hnsw.md §24).  T x T under Cosine (hnsw.rs:2460-2468): 1.0 when a cached norm is below
+    // 1e-10, else simd::dot_product of the two reconstructions over the product of the cached norms, no `== 0.0` test.  T x D under
+    // Cosine (2469-2480): the Dense arm with simd::magnitude of the reconstruction, NOT the cached norm.  T x S was the arm above
+    // (2481-2485: cosine_distance_dense on the reconstruction); Euclidean and DotProduct read no magnitude (2566-2581, 2644-2658).
+    float mag_a = h->mags[a], mag_b = h->mags[b];
+    if (metric == NMN_METRIC_COSINE && !h->tt_slot.empty()) {
+        const bool ta = node_is_tt(h, a), tb = node_is_tt(h, b);
+        if (ta && tb) {
+            if (mag_a < 1e-10f || mag_b < 1e-10f) return 1.0f;
+            const float dot = h_dot8(h->rows.data() + (size_t)a * h->dim, h->rows.data() + (size_t)b * h->dim, h->dim);
+            const float den = mag_a * mag_b;
+            const float sim = dot / den;
+            return 1.0f - sim;
+        }
+        if (ta) mag_a = node_train(h, a).row_mag;
+        if (tb) mag_b = node_train(h, b).row_mag;
+    }
+    return h_distance(metric, h->rows.data() + (size_t)b * h->dim, mag_b, h->rows.data() + (size_t)a * h->dim, mag_a, h->dim);
 }
 HQ host_query(const nmn_hnsw* h, const float* q) {
     HQ hq;

@@ -22,6 +22,15 @@ struct GraphDev {
     int metric;
 };
 
+// The record of one EmbeddingStorage::TensorTrain node in HBM (docs/hnsw.md §24): where its cores start in the pool, its shape and
+// ranks (ranks[0] == ranks[n_cores] == 1), the bits of its cached tt_norm.  96 bytes.
+struct TTNodeDev {
+    uint32_t off_lo, off_hi, n_cores, norm_bits;
+    uint32_t modes[8];
+    uint32_t ranks[9];
+    uint32_t pad[3];
+};
+
 struct SearchArgs {
     GraphDev g;
     const float* queries;  // [nq][dim]
@@ -60,7 +69,25 @@ struct SearchArgs {
     const uint4* nrec;
     const uint2* nent;
     uint32_t kind_u;
+    // hnsw_search_kernel<.., TTN = true> (a TT-query call on a handle with EmbeddingStorage::TensorTrain nodes, docs/hnsw.md §24):
+    // the slot of every node (kNone: not a TT node), the record per TT node and the pool of their cores, tt_pool floats long; the
+    // call's trains — one shape, ttq_shape[ttq_ncores]; query i's ranks at ttq_ranks + i * (ttq_ncores + 1), or ttq_ranks_u for
+    // every query when ttq_ranks is null; its cores at ttq_cores + ttq_off[i], or at i * ttq_stride when ttq_off is null — and the
+    // floats of the two LDS regions: ttq_cap for a query's cores, tt_gcap for each of the two Gram buffers.
+    const uint32_t* tt_slot;
+    const TTNodeDev* tt_rec;
+    const float* tt_cores;
+    uint64_t tt_pool;
+    const float* ttq_cores;
+    const uint32_t* ttq_ranks;
+    const uint64_t* ttq_off;
+    uint64_t ttq_stride;
+    uint32_t ttq_ncores, ttq_cap, tt_gcap;
+    uint32_t ttq_shape[8], ttq_ranks_u[9];
 };
+
+// The LDS a TTN launch adds in front of the heaps, in floats: the query's ranks (16 slots), its cores, two Gram buffers
+__host__ __device__ inline uint32_t tt_region_floats(uint32_t qcap, uint32_t gcap) { return 16u + ((qcap + 1u) & ~1u) + 2u * ((gcap + 1u) & ~1u); }
 
 // hnsw_insert_walk_kernel: the build walk of one batch (nmn_hnsw_insert_bulk, docs/hnsw.md §19)
 struct InsertArgs {
@@ -100,7 +127,7 @@ struct PatchArgs {
 // the kernels' mangled names), and a type without linkage cannot stand in a signature that crosses translation units: the
 // structs cross by address, and the typed wrappers below are what the host code calls.  Geometry: one wave per workgroup.
 namespace hnsw {
-void launch_search_args(bool spill, bool q8, bool bin, bool perq, int qkind, bool mix, uint32_t grid, size_t lds, hipStream_t s,
+void launch_search_args(bool spill, bool q8, bool bin, bool perq, int qkind, bool mix, bool ttn, uint32_t grid, size_t lds, hipStream_t s,
                         const void* search_args);
 void launch_insert_walk_args(uint32_t grid, size_t lds, hipStream_t s, const void* insert_args);
 void launch_patch_args(uint32_t grid, hipStream_t s, const void* patch_args);
@@ -108,9 +135,9 @@ void launch_patch_args(uint32_t grid, hipStream_t s, const void* patch_args);
 
 namespace {
 // hnsw_search_kernel<spill, ...>: launch_walk<spill> of nmn_hnsw_kernels.hip picks the instantiation
-inline void launch_search(bool spill, bool q8, bool bin, bool perq, int qkind, bool mix, uint32_t grid, size_t lds, hipStream_t s,
-                          const SearchArgs& a) {
-    hnsw::launch_search_args(spill, q8, bin, perq, qkind, mix, grid, lds, s, &a);
+inline void launch_search(bool spill, bool q8, bool bin, bool perq, int qkind, bool mix, bool ttn, uint32_t grid, size_t lds,
+                          hipStream_t s, const SearchArgs& a) {
+    hnsw::launch_search_args(spill, q8, bin, perq, qkind, mix, ttn, grid, lds, s, &a);
 }
 inline void launch_insert_walk(uint32_t grid, size_t lds, hipStream_t s, const InsertArgs& a) {
     hnsw::launch_insert_walk_args(grid, lds, s, &a);

@@ -5,6 +5,7 @@
 // every distance restates the reference's unfused f32 arithmetic and must give its bits (docs/hnsw.md, "Source layout").
 #include "nmn_hnsw_kernels.h"
 #include "nmn_internal.h"
+#include "nmn_tt.h"
 
 #pragma clang fp contract(off)
 
@@ -416,12 +417,21 @@ __device__ __forceinline__ float bin_distance(const uint8_t* __restrict__ row, c
 // (a.qk / a.qef / a.qkind / a.qccap null).  MIX is a template parameter so that every other instantiation stays the code it was.
 // BIN (dense queries only: QK == 0): the rows are BinaryVectors — g.codes holds their words, g.ld8 apart — scored by bin_distance;
 // nothing else of the walk changes.  BIN is a template parameter for the same reason.
-template <bool SPILL, bool Q8, bool PERQ, int QK = 0, bool MIX = false, bool BIN = false>
+// TTN (dense rows, PERQ, QK == 3, every query of kind 2; docs/hnsw.md §24): the queries are TTVectors and the handle holds
+// EmbeddingStorage::TensorTrain nodes.  Such a node is scored by cosine_distance_tt_with_norm's first arm (hnsw.rs:1201-1209):
+// tt_dot_product(node, query) — node first — over the product of the cached norms, nothing reconstructed.  The query's ranks and
+// cores sit in LDS in front of the heaps, beside its reconstruction (which every other node is still scored with), with two Gram
+// buffers.  Pair-of-lanes scoring leaves a TT node's stage slot empty; the staged TT nodes of a pass are then taken ONE AT A TIME
+// by the whole wave (tt_node_distance: the 64 lanes share out the outputs of each core step, tt_gram_step's unsplit chains, a
+// barrier between steps).  Which slots hold TT nodes is read from LDS and the slot array by every lane alike, so the loop and its
+// barriers are wave-uniform.  The visited bitmap, both heaps, lane 0's decision loop and the final order are untouched.
+template <bool SPILL, bool Q8, bool PERQ, int QK = 0, bool MIX = false, bool BIN = false, bool TTN = false>
 __global__ __launch_bounds__(64) void hnsw_search_kernel(SearchArgs a) {
     static_assert(QK == 0 || (QK == 1 && !Q8 && !PERQ) || (QK == 2 && Q8 && !PERQ) || (QK == 3 && PERQ),
                   "query kinds: 1 on dense rows, 2 on quantized rows, 3 = a kind per query of a per-query launch");
     static_assert(!MIX || (!Q8 && PERQ && QK == 3), "sparse nodes: dense storage, the per-query form");
     static_assert(!BIN || (!Q8 && QK == 0 && !MIX), "binary rows: dense queries, a storage of their own");
+    static_assert(!TTN || (!Q8 && PERQ && QK == 3 && !BIN), "TT nodes: dense storage, the per-query form");
     extern __shared__ float4 smem4[];
     const GraphDev& g = a.g;
     const uint32_t lane = threadIdx.x, p = lane >> 1, h = lane & 1u;
@@ -429,13 +439,18 @@ __global__ __launch_bounds__(64) void hnsw_search_kernel(SearchArgs a) {
     uint32_t* stage_id = reinterpret_cast<uint32_t*>(qs + a.qlds);
     float* stage_d = reinterpret_cast<float*>(stage_id + 32);
     uint32_t* ctrl = reinterpret_cast<uint32_t*>(stage_d + 32);  // [0] done, [1] current node, [2] overflow, [3] results
+    // TTN: [16] the query's ranks, [ttq_cap rounded up to 2] its cores, two Gram buffers of tt_gcap (rounded up to 2) floats
+    uint32_t* tq_rank = ctrl + 4;
+    float* tq_core = reinterpret_cast<float*>(tq_rank + 16);
+    float* tt_gram = tq_core + ((a.ttq_cap + 1u) & ~1u);
+    const uint32_t tt_gstride = (a.tt_gcap + 1u) & ~1u;
     Ent* R;
     Ent* Cn;
     if (SPILL) {
         R = a.spill + (size_t)blockIdx.x * ((size_t)a.rcap + a.ccap);
         Cn = R + a.rcap;
     } else {
-        R = reinterpret_cast<Ent*>(ctrl + 4);
+        R = reinterpret_cast<Ent*>(ctrl + 4 + (TTN ? tt_region_floats(a.ttq_cap, a.tt_gcap) : 0u));
         Cn = R + a.rcap;
     }
     const float ninf = __int_as_float(0xFF800000u);
@@ -459,6 +474,16 @@ __global__ __launch_bounds__(64) void hnsw_search_kernel(SearchArgs a) {
             for (uint32_t i = lane; i < nnz; i += 64) el[i] = a.sp_ent[e0 + i];
         } else {
             for (uint32_t i = lane; i < a.qlds; i += 64) qs[i] = i < g.dim ? qg[i] : 0.0f;
+        }
+        if constexpr (TTN) {  // the query's ranks (checked by the host before the launch), then its cores, ttq_cap floats at most
+            if (lane <= a.ttq_ncores)
+                tq_rank[lane] = a.ttq_ranks ? a.ttq_ranks[(size_t)q * (a.ttq_ncores + 1u) + lane] : a.ttq_ranks_u[lane];
+            __syncthreads();
+            uint32_t storage = 0;
+            for (uint32_t c = 0; c < a.ttq_ncores; c++) storage += tq_rank[c] * a.ttq_shape[c] * tq_rank[c + 1];
+            storage = min(storage, a.ttq_cap);
+            const float* src = a.ttq_cores + (a.ttq_off ? a.ttq_off[q] : (uint64_t)q * a.ttq_stride);
+            for (uint32_t i = lane; i < storage; i += 64) tq_core[i] = src[i];
         }
         uint32_t* vis = a.visited + (size_t)q * a.vwords;
         if (SPILL) {
@@ -501,6 +526,9 @@ __global__ __launch_bounds__(64) void hnsw_search_kernel(SearchArgs a) {
         if constexpr (BIN) sqrt_dim = d_sqrt((float)g.dim);  // (dimension as f32).sqrt(), hnsw.rs:981-984
         auto row_distance = [&](uint32_t node) -> float {
             if constexpr (BIN) return bin_distance(g.codes + (size_t)node * g.ld8, qv, qmag, sqrt_dim, g.dim, g.metric, h);
+            if constexpr (TTN) {
+                if (a.tt_slot[node] != kNone) return 0.0f;  // (the whole wave scores it from the stage, tt_node_distance)
+            }
             if constexpr (MIX) {
                 const uint4 rec = a.nrec[node];
                 if (rec.z != kNone) {
@@ -518,6 +546,53 @@ __global__ __launch_bounds__(64) void hnsw_search_kernel(SearchArgs a) {
             else
                 return pair_distance(g.corpus + (size_t)node * g.ld, g.norms[node], qv, qmag, g.dim, g.metric, h);
         };
+        // cosine_distance_tt_with_norm on a TensorTrain node (hnsw.rs:1196-1209), by the whole wave, `slot` the same in every lane.
+        // qmag is the query's norm with a norm below 1e-10 written as 0.0 (tt_walk_magnitude): the first test.  A node of another
+        // shape is tt_dot_product's Err: 1.0.  Then the Gram chain, node first; then the node's own `< 1e-10` test and the quotient.
+        auto tt_node_distance = [&](uint32_t slot) -> float {
+            const TTNodeDev& r = a.tt_rec[slot];
+            const uint32_t nc = r.n_cores;
+            bool same = nc == a.ttq_ncores && nc <= 8u;
+            uint64_t need = 0;
+            for (uint32_t c = 0; c < 8u; c++)
+                if (same && c < nc) {
+                    same = r.modes[c] == a.ttq_shape[c];
+                    need += (uint64_t)r.ranks[c] * r.modes[c] * r.ranks[c + 1];
+                    same = same && r.ranks[c] * tq_rank[c] <= a.tt_gcap && r.ranks[c + 1] * tq_rank[c + 1] <= a.tt_gcap;
+                }
+            const uint64_t off = ((uint64_t)r.off_hi << 32) | r.off_lo;
+            if (qmag == 0.0f || !same || off > a.tt_pool || need > a.tt_pool - off) return 1.0f;  // (the bounds: the host's own)
+            const float* A = a.tt_cores + off;
+            __syncthreads();  // the readers of the previous node's Gram buffers are done
+            if (lane == 0) tt_gram[0] = 1.0f;  // gram = [1.0]
+            uint32_t ca = 0, cb = 0;
+            for (uint32_t c = 0; c < nc; c++) {
+                __syncthreads();
+                const uint32_t r1a = r.ranks[c], r2a = r.ranks[c + 1], r1b = tq_rank[c], r2b = tq_rank[c + 1], m = r.modes[c];
+                const uint32_t cur = c & 1u;
+                tt_gram_step(A + ca, tq_core + cb, tt_gram + cur * tt_gstride, tt_gram + (cur ^ 1u) * tt_gstride, r1a, r2a, r1b, r2b, m,
+                             lane);
+                ca += r1a * m * r2a;
+                cb += r1b * m * r2b;
+            }
+            __syncthreads();
+            const float dot = tt_gram[(nc & 1u) * tt_gstride];
+            const float nnorm = __uint_as_float(r.norm_bits);
+            if (nnorm < 1e-10f) return 1.0f;
+            return 1.0f - dot / (nnorm * qmag);
+        };
+        // the staged neighbours of one pass that are TT nodes, one at a time; every lane reads the same slots: wave-uniform
+        auto tt_stage_pass = [&](uint32_t lim) {
+            for (uint32_t t = 0; t < lim; t++) {
+                const uint32_t id = stage_id[t];
+                if (id == kNone) continue;
+                const uint32_t slot = a.tt_slot[id];
+                if (slot == kNone) continue;
+                const float d = tt_node_distance(slot);
+                if (lane == 0) stage_d[t] = d;
+            }
+            __syncthreads();
+        };
         // distance evaluations.  The reference scores the entry of every search_layer* call again (one per greedy layer, one for
         // search_layer); this kernel carries the distance along.  A quantized or binary handle counts the evaluations the reference makes,
         // as the host walk does; a dense handle keeps the count it has always reported.
@@ -525,6 +600,10 @@ __global__ __launch_bounds__(64) void hnsw_search_kernel(SearchArgs a) {
         // greedy descent, hnsw.rs:2086-2092 / 2170-2200
         uint32_t cur = g.entry;
         float cur_d = row_distance(cur);
+        if constexpr (TTN) {
+            const uint32_t slot = a.tt_slot[cur];
+            if (slot != kNone) cur_d = tt_node_distance(slot);
+        }
         for (uint32_t layer = g.max_layer; layer >= 1; layer--) {
             for (;;) {
                 const uint32_t ui = g.up_idx[cur];
@@ -548,6 +627,7 @@ __global__ __launch_bounds__(64) void hnsw_search_kernel(SearchArgs a) {
                     }
                     __syncthreads();
                     const uint32_t lim = min(32u, cnt - j0);
+                    if constexpr (TTN) tt_stage_pass(lim);
                     for (uint32_t t = 0; t < lim; t++) {  // every lane, the same reads: the list in id order
                         const float dt = stage_d[t];
                         if (dt < best_d) {
@@ -609,6 +689,7 @@ __global__ __launch_bounds__(64) void hnsw_search_kernel(SearchArgs a) {
                     stage_d[p] = d;
                 }
                 __syncthreads();
+                if constexpr (TTN) tt_stage_pass(min(32u, cnt - j0));
                 if (lane == 0) {
                     const uint32_t lim = min(32u, cnt - j0);
                     for (uint32_t t = 0; t < lim; t++) {
@@ -898,8 +979,13 @@ __global__ __launch_bounds__(64) void hnsw_patch_kernel(PatchArgs a) {
 }
 
 template <bool SPILL>
-void launch_walk(bool q8, bool bin, bool perq, int qkind, bool mix, uint32_t grid, size_t lds, hipStream_t s, const SearchArgs& a) {
-    if (bin && perq)  // binary rows: dense queries only (every other query form is refused before it gets here)
+void launch_walk(bool q8, bool bin, bool perq, int qkind, bool mix, bool ttn, uint32_t grid, size_t lds, hipStream_t s,
+                 const SearchArgs& a) {
+    if (ttn && mix)  // TT queries on a handle with TT nodes (and sparse ones): the per-query form, every query of kind 2
+        hipLaunchKernelGGL((hnsw_search_kernel<SPILL, false, true, 3, true, false, true>), dim3(grid), dim3(64), lds, s, a);
+    else if (ttn)
+        hipLaunchKernelGGL((hnsw_search_kernel<SPILL, false, true, 3, false, false, true>), dim3(grid), dim3(64), lds, s, a);
+    else if (bin && perq)  // binary rows: dense queries only (every other query form is refused before it gets here)
         hipLaunchKernelGGL((hnsw_search_kernel<SPILL, false, true, 0, false, true>), dim3(grid), dim3(64), lds, s, a);
     else if (bin)
         hipLaunchKernelGGL((hnsw_search_kernel<SPILL, false, false, 0, false, true>), dim3(grid), dim3(64), lds, s, a);
@@ -927,13 +1013,13 @@ void launch_walk(bool q8, bool bin, bool perq, int qkind, bool mix, uint32_t gri
 
 namespace hnsw {
 
-void launch_search_args(bool spill, bool q8, bool bin, bool perq, int qkind, bool mix, uint32_t grid, size_t lds, hipStream_t s,
+void launch_search_args(bool spill, bool q8, bool bin, bool perq, int qkind, bool mix, bool ttn, uint32_t grid, size_t lds, hipStream_t s,
                         const void* search_args) {
     const SearchArgs& a = *static_cast<const SearchArgs*>(search_args);
     if (spill)
-        launch_walk<true>(q8, bin, perq, qkind, mix, grid, lds, s, a);
+        launch_walk<true>(q8, bin, perq, qkind, mix, ttn, grid, lds, s, a);
     else
-        launch_walk<false>(q8, bin, perq, qkind, mix, grid, lds, s, a);
+        launch_walk<false>(q8, bin, perq, qkind, mix, ttn, grid, lds, s, a);
 }
 void launch_insert_walk_args(uint32_t grid, size_t lds, hipStream_t s, const void* insert_args) {
     hipLaunchKernelGGL(hnsw_insert_walk_kernel, dim3(grid), dim3(64), lds, s, *static_cast<const InsertArgs*>(insert_args));

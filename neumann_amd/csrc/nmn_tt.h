@@ -110,6 +110,29 @@ constexpr uint32_t kTTSimMaxLdsFloats = 16368;  // (16 floats short of 64 KiB: t
 constexpr uint32_t kTTSimGridMax = 2048;        // workgroups of one launch (NMN_TT_SIMILARITY_GRID), the work beyond in a stride loop
 constexpr uint32_t kTTSimMinDefault = 32;       // NMN_TT_SIMILARITY_MIN: calls of fewer pairs are the host's (measured, docs/hnsw.md §23)
 
+// One core step of tt_dot_product (tensor_train.rs:480-516) for one pair by one wave: the lanes share out the r2a * r2b outputs,
+// each output one sequential chain from +0.0 over k, then ia, then ib of (gram[ia * r1b + ib] * A[ia, k, x]) * B[ib, k, y].  A, B:
+// the pair's k-th cores, in global memory or LDS; gram: r1a * r1b floats in LDS; nxt: r2a * r2b floats in LDS.  Shared by
+// tt_similarity_kernel / tt_self_dot_kernel (nmn_tt.hip) and the TTN walk (nmn_hnsw_kernels.hip): both translation units are built
+// with -ffp-contract=off, so no product is fused into its addition in either.
+__device__ __forceinline__ void tt_gram_step(const float* __restrict__ A, const float* __restrict__ B, const float* gram, float* nxt,
+                                             uint32_t r1a, uint32_t r2a, uint32_t r1b, uint32_t r2b, uint32_t n, uint32_t lane) {
+    for (uint32_t o = lane; o < r2a * r2b; o += 64) {
+        const uint32_t x = o / r2b, y = o - x * r2b;
+        float sum = 0.0f;
+        for (uint32_t kk = 0; kk < n; kk++)
+            for (uint32_t ia = 0; ia < r1a; ia++) {
+                const float ga = A[(ia * n + kk) * r2a + x];
+                for (uint32_t ib = 0; ib < r1b; ib++) {
+                    const float t = gram[ia * r1b + ib] * ga;
+                    const float p = t * B[(ib * n + kk) * r2b + y];
+                    sum = sum + p;
+                }
+            }
+        nxt[o] = sum;
+    }
+}
+
 // tt_dot_product of two trains of one shape on the host, the reference's loops restated; with a == b the chain of tt_norm
 float tt_dot_host(const uint32_t* shape, uint32_t n_cores, const uint32_t* ranks_a, const float* cores_a, const uint32_t* ranks_b,
                   const float* cores_b);

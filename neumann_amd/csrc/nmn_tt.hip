@@ -1111,25 +1111,7 @@ __device__ bool tt_train_ok(const TTSet& s, uint32_t i, uint32_t n_cores, const 
     return ok;
 }
 
-// One core step of one pair by one wave: the lanes share out the r2a * r2b outputs, each output one sequential chain.  A, B: the
-// pair's k-th cores; gram: r1a * r1b floats in LDS; nxt: r2a * r2b floats in LDS.
-__device__ __forceinline__ void tt_gram_step(const float* __restrict__ A, const float* __restrict__ B, const float* gram, float* nxt,
-                                             uint32_t r1a, uint32_t r2a, uint32_t r1b, uint32_t r2b, uint32_t n, uint32_t lane) {
-    for (uint32_t o = lane; o < r2a * r2b; o += 64) {
-        const uint32_t x = o / r2b, y = o - x * r2b;
-        float sum = 0.0f;
-        for (uint32_t kk = 0; kk < n; kk++)
-            for (uint32_t ia = 0; ia < r1a; ia++) {
-                const float ga = A[(ia * n + kk) * r2a + x];
-                for (uint32_t ib = 0; ib < r1b; ib++) {
-                    const float t = gram[ia * r1b + ib] * ga;
-                    const float p = t * B[(ib * n + kk) * r2b + y];
-                    sum = sum + p;
-                }
-            }
-        nxt[o] = sum;
-    }
-}
+// (tt_gram_step, one core step of one pair by one wave, is nmn_tt.h's: the HNSW walk restates tt_dot_product with the same text)
 
 // Dynamic LDS of both kernels, in floats: [qcap] the query's cores (tt_similarity_kernel only), then per wave two Gram matrices of
 // gcap floats and the wave's train's ranks.

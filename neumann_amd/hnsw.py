@@ -595,6 +595,49 @@ class GpuHnsw:
                                                  C.c_void_p(ids.ctypes.data)))
         return ids
 
+    def insert_embedding_tt(self, tts):
+        """HNSWIndex::insert_embedding(EmbeddingStorage::from(tt)) for each train in order (nmn_hnsw_insert_embedding_tt):
+        TensorTrain nodes, which keep the train and its cached tt_norm and are scored by their own rules (docs/hnsw.md §24) —
+        not the Dense nodes `insert_tt` makes.  `tts`: one neumann_amd.tt.TTVector or several of one shape whose product is the
+        index's dimension; another call may bring another shape of that product.  Returns the node ids.  Dense handles only."""
+        from . import tt as _tt
+        shape, ranks, off, cores = _tt.pack(tts)
+        n = ranks.shape[0]
+        ids = np.empty(n, dtype=np.uint64)
+        _capi.check(self._lib.nmn_hnsw_insert_embedding_tt(self._h, C.c_void_p(shape.ctypes.data), shape.size,
+                                                           C.c_void_p(ranks.ctypes.data), C.c_void_p(off.ctypes.data),
+                                                           C.c_void_p(cores.ctypes.data), n, C.c_void_p(ids.ctypes.data)))
+        return ids
+
+    def tt_row(self, node):
+        """the train of a TensorTrain node as a neumann_amd.tt.TTVector (nmn_hnsw_tt_row); None for a node of another kind"""
+        from . import tt as _tt
+        storage, nc = C.c_uint64(), C.c_uint32()
+        shape = np.zeros(8, dtype=np.uint32)
+        ranks = np.zeros(9, dtype=np.uint32)
+        _capi.check(self._lib.nmn_hnsw_tt_row(self._h, int(node), C.c_void_p(shape.ctypes.data), C.byref(nc),
+                                              C.c_void_p(ranks.ctypes.data), None, 0, C.byref(storage)))
+        if storage.value == 0xFFFFFFFFFFFFFFFF:
+            return None
+        cores = np.empty(storage.value, dtype=np.float32)
+        _capi.check(self._lib.nmn_hnsw_tt_row(self._h, int(node), None, None, None, C.c_void_p(cores.ctypes.data), cores.size,
+                                              C.byref(storage)))
+        d = nc.value
+        sh, rk = [int(x) for x in shape[:d]], [int(x) for x in ranks[:d + 1]]
+        parts, at = [], 0
+        for c in range(d):
+            size = rk[c] * sh[c] * rk[c + 1]
+            parts.append(cores[at:at + size].reshape(rk[c], sh[c], rk[c + 1]))
+            at += size
+        return _tt.TTVector(sh, rk, parts)
+
+    def tt_walk_limits(self, ef=None):
+        """-> (max_node_rank, nodes_above_limits, lds_floats): the limits of the device walk of TT queries on an index with
+        TensorTrain nodes (nmn_hnsw_tt_walk_limits, docs/hnsw.md §24)"""
+        r, n, f = C.c_uint32(), C.c_uint64(), C.c_uint32()
+        _capi.check(self._lib.nmn_hnsw_tt_walk_limits(self._h, 0 if ef is None else int(ef), C.byref(r), C.byref(n), C.byref(f)))
+        return r.value, n.value, f.value
+
     def search_tt_dense(self, queries, k, config, with_stats=False):
         """HNSWIndex::search_tt per query (nmn_hnsw_search_tt_dense): the query is decomposed under `config` (a
         neumann_amd.tt.TTConfig); an Ok train is answered as `search_tt` answers it (Cosine, ef_search), an Err of any kind as

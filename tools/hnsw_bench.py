@@ -92,7 +92,14 @@ with --bulk-leg) under --leg-timeout that builds the same rows with nmn_hnsw_ins
 handles in 50 000-row calls — the order of the two alternating leg by leg — saves both and ends the run unless the two files are
 byte-equal.  One JSON line per leg: insert_build_s and bulk_build_s, the seconds of every call of either (the graph grows from call
 to call), nmn_hnsw_get_bulk_stats, the accepted share, the batch-size trace (a histogram, and its first runs run-length coded)
-and the split of the bulk build into walk launches, validation plus commits, and patches; then one line with medians and spreads."""
+and the split of the bulk build into walk launches, validation plus commits, and patches; then one line with medians and spreads.
+
+  timeout -k 10 1100 python tools/hnsw_bench.py --rows 200000 --dim 128 --tt-queries 4,4,8:8 --tt-node-fraction 0.5   # once per repetition
+--tt-node-fraction F (docs/hnsw.md §24): Gaussian trains of --tt-queries' SHAPE:RANK, a share F of them inserted as TensorTrain
+nodes (nmn_hnsw_insert_embedding_tt) and the others as Dense(reconstruction), beside a second handle over the same reconstructions
+as Dense nodes only — the yardstick, built in the same process.  search_tt_device and search_device alternate call by call on both
+handles between events at 1, 64 and 1 024 queries; the device, host-buffer and host-walk answers of the handle with TT nodes must
+be the same bits.  One JSON line."""
 import argparse
 import json
 import os
@@ -637,6 +644,97 @@ def time_tt(g, k, args):
     return r
 
 
+def time_tt_nodes(n, d, cfg, k, args, out):
+    """--tt-node-fraction F (docs/hnsw.md §24): n Gaussian trains of --tt-queries' SHAPE:RANK (its product must be --dim).  ONE
+    process builds a handle where a share F of them — drawn per run of 500 trains, each run one insert call — is inserted as
+    TensorTrain nodes (insert_embedding_tt) and the others as Dense(reconstruction), and a handle over the same reconstructions as Dense nodes only — the yardstick.  search_tt_device and
+    search_device then alternate call by call on both handles, each call between two events, at 1, 64 and 1 024 queries, ef 50.
+    The device, host-buffer and host-walk answers of the TT-node handle to the first 64 trains must be the same bits."""
+    import torch
+    from neumann_amd import GpuHnsw, TTVector, tt_reconstruct
+    shape_s, rank_s = (args.tt_queries or "4,4,8:8").split(":")
+    shape = [int(x) for x in shape_s.split(",")]
+    if int(np.prod(shape)) != d:
+        raise SystemExit(f"--tt-queries {shape_s}: the product of the shape must be --dim {d}")
+    ranks = [1] + [int(rank_s)] * (len(shape) - 1) + [1]
+    sizes = [ranks[i] * shape[i] * ranks[i + 1] for i in range(len(shape))]
+    cuts = np.cumsum([0] + sizes)
+    rng = np.random.default_rng(0x77C)
+
+    def trains(cores):
+        return [TTVector(shape, ranks, [row[cuts[i]:cuts[i + 1]] for i in range(len(shape))]) for row in cores]
+
+    F = args.tt_node_fraction
+    r = dict(out, tt_shape=shape, tt_ranks=ranks, core_floats=int(sum(sizes)), tt_node_fraction=F)
+    with GpuHnsw(d, cfg, capacity_hint=n) as gt, GpuHnsw(d, cfg, capacity_hint=n) as gd:
+        t0 = time.perf_counter()
+        step, n_tt = 2_000, 0
+        for r0 in range(0, n, step):
+            cores = rng.standard_normal((min(step, n - r0), sum(sizes))).astype(np.float32)
+            ts = trains(cores)
+            rows = tt_reconstruct(ts)
+            as_tt = np.repeat(rng.random(-(-len(ts) // 500)) < F, 500)[:len(ts)]   # the kind is drawn per run of 500 trains
+            i = 0
+            while i < len(ts):          # runs of one kind, each one call, in row order
+                j = i
+                while j < len(ts) and as_tt[j] == as_tt[i]:
+                    j += 1
+                gt.insert_embedding_tt(ts[i:j]) if as_tt[i] else gt.insert(rows[i:j])
+                i = j
+            gd.insert(rows)
+            n_tt += int(as_tt.sum())
+            print(f"built {min(r0 + step, n)} nodes of both handles in {time.perf_counter() - t0:.1f} s", file=sys.stderr, flush=True)
+        r["build_both_s"] = round(time.perf_counter() - t0, 3)
+        r["tt_nodes"], r["walk_limits"] = n_tt, list(gt.tt_walk_limits(50))
+        r["hbm_bytes_tt_handle"], r["hbm_bytes_dense_handle"] = gt.hbm_bytes, gd.hbm_bytes
+        qcores = rng.standard_normal((1024, sum(sizes))).astype(np.float32)
+        tq = trains(qcores)
+        Q = tt_reconstruct(tq)
+        s = torch.cuda.Stream()
+        cd, qd = torch.from_numpy(qcores).cuda(), torch.from_numpy(Q).cuda()
+        bufs = {nq: tuple((torch.empty((nq, k), dtype=torch.int64, device="cuda"), torch.empty((nq, k), dtype=torch.float32, device="cuda"),
+                           torch.empty((nq,), dtype=torch.int32, device="cuda")) for _ in range(4)) for nq in (1, 64, 1024)}
+        legs = (("tt_nodes_tt", gt, True), ("tt_nodes_dense", gt, False), ("dense_nodes_tt", gd, True), ("dense_nodes_dense", gd, False))
+
+        def call(g, tt_query, nq, buf):
+            if tt_query:
+                g.search_tt_device(shape, ranks, cd[:nq], k, 50, out=buf, stream=s)
+            else:
+                g.search_device(qd[:nq], k, 50, out=buf, stream=s)
+        for nq in bufs:
+            for (_, g, tt_query), buf in zip(legs, bufs[nq]):
+                call(g, tt_query, nq, buf)
+        s.synchronize()
+        ids, sc, _ = gt.search_tt(tq[:64], k, 50)
+        same = np.array_equal(bufs[64][0][0].cpu().numpy().view(np.uint64), ids) and \
+            np.array_equal(bufs[64][0][1].cpu().numpy().view(np.uint32), sc.view(np.uint32))
+        os.environ["NMN_HNSW_HOST_SEARCH"] = "1"
+        try:
+            hids, hsc, _ = gt.search_tt(tq[:64], k, 50)
+        finally:
+            del os.environ["NMN_HNSW_HOST_SEARCH"]
+        same = same and np.array_equal(hids, ids) and np.array_equal(hsc.view(np.uint32), sc.view(np.uint32))
+        r["device_host_buffer_and_host_walk_agree"] = bool(same)
+        if not same:
+            raise SystemExit("search_tt_device, search_tt and the host walk disagree on the handle with TT nodes")
+        for nq, calls in ((1, args.calls), (64, args.calls), (1024, max(args.calls // 5, 5))):
+            ev = {name: [] for name, _, _ in legs}
+            for _ in range(calls):
+                for (name, g, tt_query), buf in zip(legs, bufs[nq]):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record(s)
+                    call(g, tt_query, nq, buf)
+                    e1.record(s)
+                    ev[name].append((e0, e1))
+            s.synchronize()
+            r[f"nq{nq}"] = {"calls": calls}
+            for name in ev:
+                t = np.array([a.elapsed_time(b) for a, b in ev[name]])
+                r[f"nq{nq}"][name + "_call_ms"] = round(float(np.median(t)), 5)
+                r[f"nq{nq}"][name + "_call_ms_p10_p90"] = [round(float(x), 5) for x in np.percentile(t, [10, 90])]
+    return r
+
+
 def time_sparse_device(g, Q, k, args):
     """--sparse-device (docs/hnsw.md §22): the queries of --sparse-queries' recipe (--sparse-fraction of every entry zeroed) as a CSR
     in device memory.  Three calls alternate call by call on the same handle: search_sparse_device between two events, search_device
@@ -745,6 +843,10 @@ def main():
                     help="build the same rows with nmn_hnsw_insert and with nmn_hnsw_insert_bulk on fresh handles, check the saved files "
                          "byte-equal, and report both build_s, the bulk counters and the batch-size trace (docs/hnsw.md §19); "
                          "--repeats legs, each a fresh child process under --leg-timeout")
+    ap.add_argument("--tt-node-fraction", type=float, default=None,
+                    help="build a handle with that share of --tt-queries' trains (default 4,4,8:8) inserted as TensorTrain nodes beside a "
+                         "handle of their reconstructions as Dense nodes, and time search_tt_device / search_device on both, alternating "
+                         "(docs/hnsw.md §24); one repetition per process")
     ap.add_argument("--bulk-leg", action="store_true", help="(one leg of --bulk-build, in this process)")
     ap.add_argument("--bulk-first", action="store_true", help="(--bulk-leg: the bulk build before the sequential one)")
     ap.add_argument("--bulk-policy", default="0,0", help="--bulk-build: batch,min_nodes of nmn_hnsw_set_bulk_policy (0 = default)")
@@ -818,6 +920,9 @@ def main():
         return
     if args.sparse_node_fraction is not None:
         print(json.dumps(time_mixed(n, d, cfg, Q, k, args, out)), flush=True)
+        return
+    if args.tt_node_fraction is not None:
+        print(json.dumps(time_tt_nodes(n, d, cfg, k, args, out)), flush=True)
         return
     if args.tt_queries is not None:
         out["storage"] = args.storage
