@@ -1224,6 +1224,109 @@ nmn_status nmn_hnsw_save(nmn_hnsw* h, const char* path);
 nmn_status nmn_hnsw_load(const char* path, int32_t device, uint64_t capacity_hint, uint64_t max_file_bytes, uint64_t max_entries,
                          nmn_hnsw** out);
 
+/* ---- delta vectors (docs/delta.md) --------------------------------------------------------- */
+
+/* DeltaVector and ArchetypeRegistry (tensor_store/src/delta_vector.rs:72-643), bit for bit: a row stored as its difference from an
+ * archetype.  Every sum is the reference's strictly sequential f32 chain (an iterator's `.sum()` folds from -0.0, the explicit
+ * accumulators from +0.0, products rounded before they are added, one correctly rounded square root and division per score); the
+ * device kernels (nmn_delta.hip) and the host restatement in the same file run the same chains, so which of them answers a call
+ * never shows in a bit.  A call of fewer than nmn_delta_options.min_device_rows rows (of a set: the set's rows; of pairs: the
+ * pairs) is the host's. */
+typedef struct nmn_archetypes nmn_archetypes;
+typedef struct nmn_delta_set nmn_delta_set;
+#define NMN_DELTA_MAX_DIMENSION 65535u /* MAX_DIMENSION: positions are u16 (delta_vector.rs:39) */
+#define NMN_DELTA_VECTOR_BYTES 72u     /* size_of::<DeltaVector>() on a 64-bit target: 2 usize + 2 Vec headers + Option<f32> */
+typedef struct nmn_delta_options {
+    uint64_t min_device_rows; /* calls of fewer rows run on the host; 0: always the device, UINT64_MAX: never */
+} nmn_delta_options;
+/* the default: above the largest measured crossover of a device call against the host path (docs/delta.md, Measurements) */
+#define NMN_DELTA_DEFAULT_MIN_DEVICE_ROWS 4096ull
+void nmn_delta_options_default(nmn_delta_options* opt);
+/* CoverageStats (delta_vector.rs:677-687) without archetype_usage, which is an output array of its own */
+typedef struct nmn_coverage_stats {
+    float avg_similarity;
+    float avg_compression_ratio;
+    float avg_delta_nnz;
+    uint32_t reserved;
+} nmn_coverage_stats;
+/* What the device path serves, each output nullable: the largest dimension a delta row can have; the largest dimension whose query
+ * nmn_delta_set_dot_dense keeps in LDS (above it the gather reads the query from global memory, same bits); the archetypes of one
+ * register tile of find_best; the rows of one block of the offset scan of encode_batch. */
+nmn_status nmn_delta_limits(uint32_t* max_dimension, uint32_t* lds_query_dim, uint32_t* archetype_tile, uint32_t* scan_block);
+
+/* ArchetypeRegistry::new(max_archetypes) for rows of `dim` floats (dim >= 1).  device: HIP ordinal, -1 = the current one; nothing
+ * is allocated on it before the first call that takes the device path. */
+nmn_status nmn_archetypes_create(uint32_t dim, uint64_t max_archetypes, int32_t device, nmn_archetypes** out);
+nmn_status nmn_archetypes_destroy(nmn_archetypes* a);
+nmn_status nmn_archetypes_set_options(nmn_archetypes* a, const nmn_delta_options* opt);
+/* register (442-452) for n rows (HOST, n x dim) in order: ids_out[i] is the new id, -1 where the reference returns None. */
+nmn_status nmn_archetypes_register(nmn_archetypes* a, const float* rows, uint64_t n, int64_t* ids_out);
+/* discover_archetypes (566-592): k.min(n).min(max - len) centroids of KMeans::fit (the GPU k-means of nmn_ivf_build, which sets
+ * the shapes this call takes: anything it refuses is refused here with its text) appended in order.  *added_out is the return.
+ * The k-means has no host restatement: this call always needs the device, whatever min_device_rows says (a call that returns 0
+ * before the fit — no vectors, k == 0, a full registry — touches none). */
+nmn_status nmn_archetypes_discover(nmn_archetypes* a, const float* rows, uint64_t n, uint64_t k, const nmn_kmeans_options* opt,
+                                   uint64_t* added_out);
+uint64_t nmn_archetypes_len(nmn_archetypes* a);
+uint32_t nmn_archetypes_dim(nmn_archetypes* a);
+uint64_t nmn_archetypes_max(nmn_archetypes* a);
+nmn_status nmn_archetypes_get(nmn_archetypes* a, uint64_t id, float* out);          /* NMN_ERR_NOT_FOUND: None */
+nmn_status nmn_archetypes_magnitude_sq(nmn_archetypes* a, uint64_t id, float* out); /* NMN_ERR_NOT_FOUND: None */
+/* find_best_archetype (480-513) of n rows (HOST): ids_out[i] = -1 and sims_out[i] untouched on an empty registry (None). */
+nmn_status nmn_archetypes_find_best(nmn_archetypes* a, const float* rows, uint64_t n, int64_t* ids_out, float* sims_out);
+/* analyze_coverage (614-643): usage_out holds nmn_archetypes_len counters.  An empty registry or n == 0 is CoverageStats::default. */
+nmn_status nmn_archetypes_analyze_coverage(nmn_archetypes* a, const float* rows, uint64_t n, float threshold,
+                                           nmn_coverage_stats* stats_out, uint64_t* usage_out);
+/* encode_batch (598-607): every row against its best archetype (try_from_dense_with_reference, 113-147); with_magnitude != 0 caches
+ * sqrt(sum x * x) of the dense row as from_dense_with_reference_and_magnitude (151-161) does.  An empty registry gives an empty set.
+ * A dimension above 65535 is NMN_ERR_INVALID_ARGUMENT with DeltaVectorError's Display — unless the registry is empty or n == 0: the
+ * reference's `encode` is None before any DeltaVector is built, so the set is empty at any dimension. */
+nmn_status nmn_archetypes_encode_batch(nmn_archetypes* a, const float* rows, uint64_t n, float threshold, int32_t with_magnitude,
+                                       nmn_delta_set** out);
+/* from_parts (170-205) for n rows: row i holds positions / deltas [indptr[i], indptr[i + 1]) against archetype_ids[i].  cached is
+ * nullable; has_cached (nullable: every row of `cached` counts) marks the rows whose cached_magnitude is Some.  Refused with texts
+ * of their own: an archetype id that is not registered, an indptr that does not start at 0 or does not ascend, a position that is
+ * not below the dimension.  Unsorted and repeated positions are kept as they are. */
+nmn_status nmn_delta_set_from_parts(nmn_archetypes* a, uint64_t n, const uint64_t* archetype_ids, const uint64_t* indptr,
+                                    const uint16_t* positions, const float* deltas, const float* cached, const uint8_t* has_cached,
+                                    nmn_delta_set** out);
+/* A set is immutable and tied to the registry it was made against, which must outlive it. */
+nmn_status nmn_delta_set_destroy(nmn_delta_set* s);
+uint64_t nmn_delta_set_len(nmn_delta_set* s);
+uint64_t nmn_delta_set_nnz(nmn_delta_set* s);
+/* copies out, each output nullable: [n], [n + 1], [nnz], [nnz], [n], [n]; sorted_out[i] = 1 where row i's positions strictly ascend */
+nmn_status nmn_delta_set_arrays(nmn_delta_set* s, uint64_t* archetype_ids, uint64_t* indptr, uint16_t* positions, float* deltas,
+                                float* cached, uint8_t* has_cached, uint8_t* sorted_out);
+/* compression_ratio (410-416) and memory_bytes (276-280) per row */
+nmn_status nmn_delta_set_compression_ratio(nmn_delta_set* s, float* out);
+nmn_status nmn_delta_set_memory_bytes(nmn_delta_set* s, uint64_t* out);
+/* to_dense (209-217) per row: out [n][dim].  magnitude (260-267) per row: out [n]. */
+nmn_status nmn_delta_set_decode(nmn_delta_set* s, float* out);
+nmn_status nmn_delta_set_magnitudes(nmn_delta_set* s, float* out);
+/* dot_dense (309-312) and cosine_similarity_dense (374-388) of every row with every query (HOST, nq x dim): out [nq][n];
+ * query_magnitude is sqrt(sum q * q), the sequential chain. */
+nmn_status nmn_delta_set_dot_dense(nmn_delta_set* s, const float* queries, uint32_t nq, float* out);
+nmn_status nmn_delta_set_cosine_dense(nmn_delta_set* s, const float* queries, uint32_t nq, float* out);
+/* dot_deltas_same_archetype (544-552; dot_same_archetype, 321-349): pairs [n_pairs][2] = (row of a, row of b); ok_out[i] = 0 and
+ * out[i] untouched where the archetype ids differ (None).  Both sets belong to one registry. */
+nmn_status nmn_delta_set_dot_same_archetype(nmn_delta_set* a, nmn_delta_set* b, const uint64_t* pairs, uint64_t n_pairs, float* out,
+                                            uint8_t* ok_out);
+/* Stream-ordered forms: DEVICE pointers on the handle's device, enqueued on `stream`, not waited for, nothing read back, nothing
+ * allocated.  The handle must be resident: nmn_archetypes_to_device / nmn_delta_set_to_device (which do block) after the last
+ * register; a handle that is not is NMN_ERR_INVALID_ARGUMENT with a text that says so, as is an empty registry (its answer is no
+ * array).  ids_dev [n] int64, sims_dev [n]; scratch_dev: nq x (nmn_archetypes_len + 1) floats the call may overwrite.  The
+ * residency flags are atomic, the mirrors behind them are not: nmn_archetypes_register, nmn_archetypes_to_device and
+ * nmn_delta_set_to_device (and any host-buffer call that takes the device path after a register, which uploads the registry again)
+ * must not run concurrently with a stream-ordered call on the same handles, nor while one is still in flight. */
+nmn_status nmn_archetypes_to_device(nmn_archetypes* a);
+nmn_status nmn_delta_set_to_device(nmn_delta_set* s);
+nmn_status nmn_archetypes_find_best_device(nmn_archetypes* a, const float* rows_dev, uint64_t n, int64_t* ids_dev, float* sims_dev,
+                                           void* stream);
+nmn_status nmn_delta_set_dot_dense_device(nmn_delta_set* s, const float* queries_dev, uint32_t nq, float* scratch_dev, float* out_dev,
+                                          void* stream);
+nmn_status nmn_delta_set_cosine_dense_device(nmn_delta_set* s, const float* queries_dev, uint32_t nq, float* scratch_dev,
+                                             float* out_dev, void* stream);
+
 /* ---- synthetic data (bench / tests) ------------------------------------------------------- */
 
 /* value(seed,row,col): a counter-based generator that is bit-identical on host and device

@@ -568,3 +568,116 @@ impl Drop for GpuHnswIndex {
         unsafe { ffi::nmn_hnsw_destroy(self.raw) };
     }
 }
+
+/// `tensor_store::ArchetypeRegistry` (delta_vector.rs:421-643) behind nmn_archetypes (docs/delta.md): archetypes and their
+/// magnitude_sq in HBM, find_best_archetype and encode_batch for whole batches, bit for bit.
+pub struct GpuArchetypeRegistry {
+    raw: *mut ffi::nmn_archetypes,
+    dim: usize,
+}
+unsafe impl Send for GpuArchetypeRegistry {}
+unsafe impl Sync for GpuArchetypeRegistry {}
+
+impl GpuArchetypeRegistry {
+    pub fn new(dim: usize, max_archetypes: usize, device: i32) -> Result<Self> {
+        let mut raw = std::ptr::null_mut();
+        check(unsafe { ffi::nmn_archetypes_create(dim as u32, max_archetypes as u64, device, &mut raw) }, dim, dim)?;
+        Ok(Self { raw, dim })
+    }
+
+    /// Calls of fewer rows than this run on the library's host restatement, same bits (nmn_delta_options).
+    pub fn set_min_device_rows(&self, rows: u64) -> Result<()> {
+        let opt = ffi::nmn_delta_options { min_device_rows: rows };
+        check(unsafe { ffi::nmn_archetypes_set_options(self.raw, &opt) }, self.dim, self.dim)
+    }
+
+    pub fn len(&self) -> usize {
+        unsafe { ffi::nmn_archetypes_len(self.raw) as usize }
+    }
+
+    /// ArchetypeRegistry::register for one archetype: None at max_archetypes.
+    pub fn register(&self, archetype: &[f32]) -> Result<Option<usize>> {
+        let mut id = -1i64;
+        check(unsafe { ffi::nmn_archetypes_register(self.raw, archetype.as_ptr(), 1, &mut id) }, self.dim, archetype.len())?;
+        Ok(if id < 0 { None } else { Some(id as usize) })
+    }
+
+    /// ArchetypeRegistry::discover_archetypes: the centroids of the exact GPU k-means, appended in order.
+    pub fn discover_archetypes(&self, rows: &[f32], k: usize, opt: &ffi::nmn_kmeans_options) -> Result<usize> {
+        let n = (rows.len() / self.dim.max(1)) as u64;
+        let mut added = 0u64;
+        check(unsafe { ffi::nmn_archetypes_discover(self.raw, rows.as_ptr(), n, k as u64, opt, &mut added) }, self.dim, self.dim)?;
+        Ok(added as usize)
+    }
+
+    /// ArchetypeRegistry::find_best_archetype of every row: None on an empty registry.
+    pub fn find_best(&self, rows: &[f32]) -> Result<Vec<Option<(usize, f32)>>> {
+        let n = rows.len() / self.dim.max(1);
+        let (mut ids, mut sims) = (vec![-1i64; n], vec![0f32; n]);
+        check(unsafe { ffi::nmn_archetypes_find_best(self.raw, rows.as_ptr(), n as u64, ids.as_mut_ptr(), sims.as_mut_ptr()) }, self.dim, self.dim)?;
+        Ok(ids.iter().zip(&sims).map(|(&i, &s)| if i < 0 { None } else { Some((i as usize, s)) }).collect())
+    }
+
+    /// ArchetypeRegistry::encode_batch: the delta rows stay together in one set; DimensionExceeded arrives as a StorageError with
+    /// DeltaVectorError's Display.
+    pub fn encode_batch(&self, rows: &[f32], threshold: f32, with_magnitude: bool) -> Result<GpuDeltaSet<'_>> {
+        let n = (rows.len() / self.dim.max(1)) as u64;
+        let mut raw = std::ptr::null_mut();
+        check(unsafe { ffi::nmn_archetypes_encode_batch(self.raw, rows.as_ptr(), n, threshold, with_magnitude as i32, &mut raw) }, self.dim, self.dim)?;
+        Ok(GpuDeltaSet { raw, registry: self })
+    }
+}
+
+impl Drop for GpuArchetypeRegistry {
+    fn drop(&mut self) {
+        unsafe { ffi::nmn_archetypes_destroy(self.raw) };
+    }
+}
+
+/// N `DeltaVector`s against one registry (nmn_delta_set); the borrow keeps the registry alive for as long as the set.
+pub struct GpuDeltaSet<'a> {
+    raw: *mut ffi::nmn_delta_set,
+    registry: &'a GpuArchetypeRegistry,
+}
+unsafe impl Send for GpuDeltaSet<'_> {}
+unsafe impl Sync for GpuDeltaSet<'_> {}
+
+impl GpuDeltaSet<'_> {
+    pub fn len(&self) -> usize {
+        unsafe { ffi::nmn_delta_set_len(self.raw) as usize }
+    }
+
+    pub fn nnz(&self) -> usize {
+        unsafe { ffi::nmn_delta_set_nnz(self.raw) as usize }
+    }
+
+    /// DeltaVector::compression_ratio of every row, the second half of encode_batch's pairs.
+    pub fn compression_ratios(&self) -> Result<Vec<f32>> {
+        let mut out = vec![0f32; self.len()];
+        check(unsafe { ffi::nmn_delta_set_compression_ratio(self.raw, out.as_mut_ptr()) }, self.registry.dim, self.registry.dim)?;
+        Ok(out)
+    }
+
+    /// ArchetypeRegistry::dot_delta_dense of every row with every query: out[q * len + row].
+    pub fn dot_dense(&self, queries: &[f32]) -> Result<Vec<f32>> {
+        let dim = self.registry.dim;
+        let nq = queries.len() / dim.max(1);
+        let mut out = vec![0f32; nq * self.len()];
+        check(unsafe { ffi::nmn_delta_set_dot_dense(self.raw, queries.as_ptr(), nq as u32, out.as_mut_ptr()) }, dim, dim)?;
+        Ok(out)
+    }
+
+    /// ArchetypeRegistry::decode of every row: out[row * dim ..].
+    pub fn decode(&self) -> Result<Vec<f32>> {
+        let dim = self.registry.dim;
+        let mut out = vec![0f32; self.len() * dim];
+        check(unsafe { ffi::nmn_delta_set_decode(self.raw, out.as_mut_ptr()) }, dim, dim)?;
+        Ok(out)
+    }
+}
+
+impl Drop for GpuDeltaSet<'_> {
+    fn drop(&mut self) {
+        unsafe { ffi::nmn_delta_set_destroy(self.raw) };
+    }
+}

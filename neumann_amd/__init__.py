@@ -15,5 +15,6 @@ from .cache_index import CacheIndex  # noqa: F401,E402
 from .tt import TTConfig, TTVector, tt_decompose, tt_norm, tt_reconstruct  # noqa: F401,E402
 from .tt import (tt_cosine_similarity, tt_cosine_similarity_batch, tt_dot_product, tt_dot_product_batch,  # noqa: F401,E402
                  tt_euclidean_distance, tt_euclidean_distance_batch, tt_self_dot, tt_similarity, tt_similarity_device)
+from .delta import ArchetypeRegistry, CoverageStats, DeltaSet, DeltaVectorError  # noqa: F401,E402
 
 __version__ = "0.3.0"

@@ -78,6 +78,17 @@ class KMeansOptions(C.Structure):
                 ("init_method", C.c_int32)]
 
 
+class DeltaOptions(C.Structure):
+    """nmn_delta_options: which calls of the delta-vector family take the device path (docs/delta.md)."""
+    _fields_ = [("min_device_rows", C.c_uint64)]
+
+
+class CoverageStats(C.Structure):
+    """nmn_coverage_stats (CoverageStats, tensor_store/src/delta_vector.rs:677-687, without archetype_usage)."""
+    _fields_ = [("avg_similarity", C.c_float), ("avg_compression_ratio", C.c_float), ("avg_delta_nnz", C.c_float),
+                ("reserved", C.c_uint32)]
+
+
 class IvfStorage(C.Structure):
     """nmn_ivf_storage (IVFStorage, tensor_store/src/ivf.rs:150-157; PQConfig, pq.rs:40-85; BinaryThreshold)."""
     _fields_ = [("kind", C.c_int32), ("pq_num_subspaces", C.c_uint32), ("pq_num_centroids", C.c_uint32),
@@ -304,6 +315,38 @@ SIGNATURES = {
     "nmn_hnsw_cache_search_device": (C.c_int32, [vp, vp, C.c_uint32, C.c_uint32, C.c_float, C.POINTER(XMetric), vp, vp, vp, vp]),
     "nmn_hnsw_cache_search_sparse_device": (C.c_int32, [vp, vp, vp, vp, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_float,
                                                         C.POINTER(XMetric), vp, vp, vp, vp, vp]),
+    "nmn_delta_options_default": (None, [C.POINTER(DeltaOptions)]),
+    "nmn_delta_limits": (C.c_int32, [u32p, u32p, u32p, u32p]),
+    "nmn_archetypes_create": (C.c_int32, [C.c_uint32, C.c_uint64, C.c_int32, C.POINTER(vp)]),
+    "nmn_archetypes_destroy": (C.c_int32, [vp]),
+    "nmn_archetypes_set_options": (C.c_int32, [vp, C.POINTER(DeltaOptions)]),
+    "nmn_archetypes_register": (C.c_int32, [vp, vp, C.c_uint64, vp]),
+    "nmn_archetypes_discover": (C.c_int32, [vp, vp, C.c_uint64, C.c_uint64, C.POINTER(KMeansOptions), u64p]),
+    "nmn_archetypes_len": (C.c_uint64, [vp]),
+    "nmn_archetypes_dim": (C.c_uint32, [vp]),
+    "nmn_archetypes_max": (C.c_uint64, [vp]),
+    "nmn_archetypes_get": (C.c_int32, [vp, C.c_uint64, vp]),
+    "nmn_archetypes_magnitude_sq": (C.c_int32, [vp, C.c_uint64, f32p]),
+    "nmn_archetypes_find_best": (C.c_int32, [vp, vp, C.c_uint64, vp, vp]),
+    "nmn_archetypes_analyze_coverage": (C.c_int32, [vp, vp, C.c_uint64, C.c_float, C.POINTER(CoverageStats), vp]),
+    "nmn_archetypes_encode_batch": (C.c_int32, [vp, vp, C.c_uint64, C.c_float, C.c_int32, C.POINTER(vp)]),
+    "nmn_delta_set_from_parts": (C.c_int32, [vp, C.c_uint64, vp, vp, vp, vp, vp, vp, C.POINTER(vp)]),
+    "nmn_delta_set_destroy": (C.c_int32, [vp]),
+    "nmn_delta_set_len": (C.c_uint64, [vp]),
+    "nmn_delta_set_nnz": (C.c_uint64, [vp]),
+    "nmn_delta_set_arrays": (C.c_int32, [vp, vp, vp, vp, vp, vp, vp, vp]),
+    "nmn_delta_set_compression_ratio": (C.c_int32, [vp, vp]),
+    "nmn_delta_set_memory_bytes": (C.c_int32, [vp, vp]),
+    "nmn_delta_set_decode": (C.c_int32, [vp, vp]),
+    "nmn_delta_set_magnitudes": (C.c_int32, [vp, vp]),
+    "nmn_delta_set_dot_dense": (C.c_int32, [vp, vp, C.c_uint32, vp]),
+    "nmn_delta_set_cosine_dense": (C.c_int32, [vp, vp, C.c_uint32, vp]),
+    "nmn_delta_set_dot_same_archetype": (C.c_int32, [vp, vp, vp, C.c_uint64, vp, vp]),
+    "nmn_archetypes_to_device": (C.c_int32, [vp]),
+    "nmn_delta_set_to_device": (C.c_int32, [vp]),
+    "nmn_archetypes_find_best_device": (C.c_int32, [vp, vp, C.c_uint64, vp, vp, vp]),
+    "nmn_delta_set_dot_dense_device": (C.c_int32, [vp, vp, C.c_uint32, vp, vp, vp]),
+    "nmn_delta_set_cosine_dense_device": (C.c_int32, [vp, vp, C.c_uint32, vp, vp, vp]),
     "nmn_index_save": (C.c_int32, [vp, C.c_char_p]),
     "nmn_index_load": (C.c_int32, [C.c_char_p, C.POINTER(IndexDesc), C.c_uint64, C.c_uint64, C.POINTER(vp)]),
     "nmn_ivf_save": (C.c_int32, [vp, C.c_char_p]),
