@@ -1327,6 +1327,42 @@ nmn_status nmn_delta_set_dot_dense_device(nmn_delta_set* s, const float* queries
 nmn_status nmn_delta_set_cosine_dense_device(nmn_delta_set* s, const float* queries_dev, uint32_t nq, float* scratch_dev,
                                              float* out_dev, void* stream);
 
+/* Top-k over a delta set (docs/delta.md, section 8).  The answer of query q is the first min(k, n) rows of all n rows sorted by the
+ * project's order (docs/exactness.md): score descending, row ascending, -0.0 and +0.0 equal, every NaN equal to every other NaN and
+ * below -inf.  The score is what nmn_delta_set_dot_dense (cosine = 0) or nmn_delta_set_cosine_dense (cosine != 0) returns for that
+ * row, and the score returned is the row's own bits: a -0.0 stays -0.0, a NaN keeps its payload.  rows_out / scores_out are [nq][k],
+ * counts_out[q] = min(k, n); the unused slots hold row UINT64_MAX and score -inf.  k == 0 and a set of 4294967295 rows or more are
+ * NMN_ERR_INVALID_ARGUMENT.  Below min_device_rows the host scores and sorts: same bits.  On the device a k up to select_max_k is
+ * served by one select workgroup per query, a larger k by the sort of the large-k path, one query at a time; so is a call of ONE
+ * query over sort_single_query_rows rows or more, which one workgroup would serve more slowly.  The host-buffer form
+ * takes its queries in blocks whose score words [queries][n] stay within block_budget_bytes. */
+nmn_status nmn_deltaset_limits(uint32_t* select_chunk_rows, uint32_t* select_max_k, uint64_t* block_budget_bytes,
+                               uint64_t* sort_single_query_rows);
+nmn_status nmn_deltaset_search(nmn_delta_set* s, const float* queries, uint32_t nq, uint32_t k, int32_t cosine, uint64_t* rows_out,
+                               float* scores_out, uint32_t* counts_out);
+/* The stream-ordered form: DEVICE pointers, enqueued on `stream`, not waited for, nothing allocated, no mutex taken; the handles must
+ * be resident as for the stream-ordered scores above.  scratch_dev: nmn_deltaset_search_scratch_bytes bytes (for the same nq and k,
+ * asked after the last register), aligned to 16 bytes, which the call may overwrite. */
+uint64_t nmn_deltaset_search_scratch_bytes(nmn_delta_set* s, uint32_t nq, uint32_t k);
+nmn_status nmn_deltaset_search_device(nmn_delta_set* s, const float* queries_dev, uint32_t nq, uint32_t k, int32_t cosine,
+                                      void* scratch_dev, uint64_t scratch_bytes, uint64_t* rows_dev, float* scores_dev,
+                                      uint32_t* counts_dev, void* stream);
+
+/* A delta set made where the rows are (docs/delta.md, section 9): encode_batch of n rows that are already on the device (rows_dev,
+ * n x dim, DEVICE), into a resident set that holds NO host copy of its arrays.  Enqueues on `stream`: find_best, count and scan,
+ * the slice lengths and their scan; then WAITS once on that stream for two u64 (the entry total and the slice total), allocates, and
+ * enqueues the entry write, the 64-row entry-major slices and the magnitudes.  It returns with those enqueued and not waited for; the
+ * set records an event at their end, and the library's own host-buffer calls on the set wait for it.  Stream-ordered callers order
+ * themselves (same stream, or their own event).  ids_dev [n] int64 / sims_dev [n] (nullable, DEVICE) receive find_best's answers.
+ * Refused with NMN_ERR_INVALID_ARGUMENT and a text of its own: an empty registry; a registry that is not resident or not current;
+ * a dimension above 65535 (DeltaVectorError's Display).  n == 0 gives an empty set.  The host arrays (nmn_delta_set_arrays,
+ * the compression ratios and memory bytes, any host-path call) are downloaded on first need, each once, under a lock of the set's;
+ * nmn_deltaset_host_arrays_present says whether that has happened (1) or not (0).  The host-buffer encode_batch on its device path
+ * returns such a set too. */
+nmn_status nmn_deltaset_encode_device(nmn_archetypes* a, const float* rows_dev, uint64_t n, float threshold, int32_t with_magnitude,
+                                      int64_t* ids_dev, float* sims_dev, void* stream, nmn_delta_set** out);
+int32_t nmn_deltaset_host_arrays_present(nmn_delta_set* s);
+
 /* ---- synthetic data (bench / tests) ------------------------------------------------------- */
 
 /* value(seed,row,col): a counter-based generator that is bit-identical on host and device

@@ -626,6 +626,23 @@ impl GpuArchetypeRegistry {
         check(unsafe { ffi::nmn_archetypes_encode_batch(self.raw, rows.as_ptr(), n, threshold, with_magnitude as i32, &mut raw) }, self.dim, self.dim)?;
         Ok(GpuDeltaSet { raw, registry: self })
     }
+
+    /// encode_batch of `n` rows that are already on the device (docs/delta.md §9): a resident set without host arrays.  `rows_dev`
+    /// is a DEVICE pointer to n x dim floats, `stream` a hipStream_t; the registry must be resident (nmn_archetypes_to_device).
+    ///
+    /// # Safety
+    /// `rows_dev` must point to n x dim floats on the registry's device and stay unchanged until `stream` has run the call.
+    pub unsafe fn encode_batch_device(&self, rows_dev: *const f32, n: usize, threshold: f32, with_magnitude: bool, stream: *mut std::ffi::c_void)
+                                      -> Result<GpuDeltaSet<'_>> {
+        let mut raw = std::ptr::null_mut();
+        check(
+            ffi::nmn_deltaset_encode_device(self.raw, rows_dev, n as u64, threshold, with_magnitude as i32, std::ptr::null_mut(), std::ptr::null_mut(),
+                                            stream, &mut raw),
+            self.dim,
+            self.dim,
+        )?;
+        Ok(GpuDeltaSet { raw, registry: self })
+    }
 }
 
 impl Drop for GpuArchetypeRegistry {
@@ -665,6 +682,23 @@ impl GpuDeltaSet<'_> {
         let mut out = vec![0f32; nq * self.len()];
         check(unsafe { ffi::nmn_delta_set_dot_dense(self.raw, queries.as_ptr(), nq as u32, out.as_mut_ptr()) }, dim, dim)?;
         Ok(out)
+    }
+
+    /// Top-k over the set (docs/delta.md §8): per query the first min(k, len) rows by (score descending, row ascending), the score
+    /// being dot_dense's (`cosine` false) or cosine_similarity_dense's; each pair carries the row's own score bits.
+    pub fn search(&self, queries: &[f32], k: usize, cosine: bool) -> Result<Vec<Vec<(usize, f32)>>> {
+        let dim = self.registry.dim;
+        let nq = queries.len() / dim.max(1);
+        let (mut rows, mut scores, mut counts) = (vec![u64::MAX; nq * k], vec![f32::NEG_INFINITY; nq * k], vec![0u32; nq]);
+        check(
+            unsafe {
+                ffi::nmn_deltaset_search(self.raw, queries.as_ptr(), nq as u32, k as u32, cosine as i32, rows.as_mut_ptr(), scores.as_mut_ptr(),
+                                         counts.as_mut_ptr())
+            },
+            dim,
+            dim,
+        )?;
+        Ok((0..nq).map(|q| (0..counts[q] as usize).map(|i| (rows[q * k + i] as usize, scores[q * k + i])).collect()).collect())
     }
 
     /// ArchetypeRegistry::decode of every row: out[row * dim ..].

@@ -347,6 +347,12 @@ SIGNATURES = {
     "nmn_archetypes_find_best_device": (C.c_int32, [vp, vp, C.c_uint64, vp, vp, vp]),
     "nmn_delta_set_dot_dense_device": (C.c_int32, [vp, vp, C.c_uint32, vp, vp, vp]),
     "nmn_delta_set_cosine_dense_device": (C.c_int32, [vp, vp, C.c_uint32, vp, vp, vp]),
+    "nmn_deltaset_encode_device": (C.c_int32, [vp, vp, C.c_uint64, C.c_float, C.c_int32, vp, vp, vp, C.POINTER(vp)]),
+    "nmn_deltaset_host_arrays_present": (C.c_int32, [vp]),
+    "nmn_deltaset_limits": (C.c_int32, [u32p, u32p, u64p, u64p]),
+    "nmn_deltaset_search": (C.c_int32, [vp, vp, C.c_uint32, C.c_uint32, C.c_int32, vp, vp, vp]),
+    "nmn_deltaset_search_scratch_bytes": (C.c_uint64, [vp, C.c_uint32, C.c_uint32]),
+    "nmn_deltaset_search_device": (C.c_int32, [vp, vp, C.c_uint32, C.c_uint32, C.c_int32, vp, C.c_uint64, vp, vp, vp, vp]),
     "nmn_index_save": (C.c_int32, [vp, C.c_char_p]),
     "nmn_index_load": (C.c_int32, [C.c_char_p, C.POINTER(IndexDesc), C.c_uint64, C.c_uint64, C.POINTER(vp)]),
     "nmn_ivf_save": (C.c_int32, [vp, C.c_char_p]),

@@ -7,6 +7,7 @@
 #include <atomic>
 #include <cmath>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <shared_mutex>
 #include <string>
@@ -14,6 +15,7 @@
 #include <vector>
 
 #include "nmn_internal.h"
+#include "nmn_select_dev.h"
 
 #pragma clang fp contract(off)
 
@@ -27,6 +29,10 @@ constexpr uint32_t kScanBlock = 256;   // rows per step of the single-workgroup 
 constexpr uint32_t kLdsQueryDim = 8192;  // a query up to this dimension sits in LDS (32 KiB) while a slice is scored
 constexpr uint32_t kQueryBlock = 32768;  // queries per launch of the score kernels (gridDim.y is 16 bits wide)
 constexpr uint64_t kChunkBytes = 256ull << 20;  // dense rows on the device per step of a host-buffer call
+constexpr uint32_t kSelectMaxK = 4096;                // the largest k deltaset_select_kernel serves: its composites fill 32 KiB of LDS
+constexpr uint32_t kSelectChunk = kSelThreads * 4;    // score words one step of its workgroup reads: 16 bytes per lane
+constexpr uint64_t kSearchBudget = 256ull << 20;      // score words [queries][n] on the device per step of a host-buffer search
+constexpr uint64_t kSortSingleRows = 1ull << 18;      // a single query over this many rows is ranked by the sort, not by one workgroup
 
 #define HD __host__ __device__ inline
 
@@ -343,6 +349,228 @@ __global__ void __launch_bounds__(256) delta_pair_kernel(const uint32_t* __restr
                       ptr_b[rb + 1] - ptr_b[rb], arch + (uint64_t)id * dim, msq[id]);
 }
 
+// ---- top-k over a set's scores (docs/delta.md §8) -----------------------------------------------------------------------------
+
+// four score words of one query from the 16-byte aligned word v0 of `al`: the words [a0, vend) are the query's, a word outside
+// them is never read and gives kKeyMasked (score_to_key itself never returns it); one 16-byte load where all four are the query's
+__device__ __forceinline__ void load_keys4(const uint32_t* __restrict__ al, uint64_t v0, uint32_t a0, uint64_t vend, uint32_t key[4]) {
+    if (v0 >= a0 && v0 + 4 <= vend) {
+        const uint4 w = *reinterpret_cast<const uint4*>(al + v0);
+        key[0] = score_to_key(u2f(w.x));
+        key[1] = score_to_key(u2f(w.y));
+        key[2] = score_to_key(u2f(w.z));
+        key[3] = score_to_key(u2f(w.w));
+    } else {
+#pragma unroll
+        for (uint32_t u = 0; u < 4; u++) {
+            const uint64_t v = v0 + u;
+            key[u] = v >= a0 && v < vend ? score_to_key(u2f(al[v])) : kKeyMasked;
+        }
+    }
+}
+
+// The first min(k, n) rows of one query's n scores under (key descending, row ascending), k <= kSelectMaxK: a workgroup per query
+// (the grid's x).  Three histogram passes over the key bits 31-21, 20-10 and 9-0, each within the bin found before, give the exact
+// k-th key T, the keys above it and the keys equal to it; a fourth pass collects every row above T in any order and the first
+// (k - above) rows AT T in row order (the chunks ascend, a thread's four rows ascend, and a block-wide prefix of the tie counts
+// ranks them; where every tie is wanted no rank is needed); then a bitonic sort of the composites key << 32 | ~row in LDS.  The
+// score written is the row's own word, not key_to_score of its key: a -0.0 stays -0.0 and a NaN keeps its payload.
+__global__ void __launch_bounds__(kSelThreads) deltaset_select_kernel(const uint32_t* __restrict__ scores, uint64_t n, uint32_t k,
+                                                                      uint64_t* __restrict__ out_rows, uint32_t* __restrict__ out_scores,
+                                                                      uint32_t* __restrict__ out_counts) {
+    __shared__ uint32_t hist[kBins];
+    __shared__ unsigned long long list[kSelectMaxK];
+    __shared__ PickResult pick;
+    __shared__ uint32_t n_list;
+    __shared__ uint32_t wsum[kSelThreads / 64];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint64_t q = blockIdx.x;
+    const uint32_t* sc = scores + q * n;
+    const uint32_t a0 = (uint32_t)((reinterpret_cast<uintptr_t>(sc) >> 2) & 3u);  // words between the 16-byte border below and sc
+    const uint32_t* al = sc - a0;
+    const uint64_t vend = (uint64_t)a0 + n;
+    const uint32_t kk = (uint32_t)(n < (uint64_t)k ? n : (uint64_t)k);  // the rows that answer
+    uint32_t prefix = 0, need = kk, above = 0, eq_total = 0;
+    uint32_t key[4];
+    if (kk) {
+        for (int pass = 0; pass < 3; pass++) {
+            for (uint32_t i = tid; i < (uint32_t)kBins; i += kSelThreads) hist[i] = 0;
+            __syncthreads();
+            for (uint64_t c0 = 0; c0 < vend; c0 += kSelectChunk) {
+                load_keys4(al, c0 + tid * 4, a0, vend, key);
+#pragma unroll
+                for (uint32_t u = 0; u < 4; u++) {
+                    bool in = key[u] != kKeyMasked;
+                    uint32_t bin = key[u] >> 21;
+                    if (pass == 1) in = in && (key[u] >> 21) == prefix, bin = (key[u] >> 10) & 2047u;
+                    if (pass == 2) in = in && (key[u] >> 10) == prefix, bin = key[u] & 1023u;
+                    hist_add_wave(hist, in, bin);
+                }
+            }
+            __syncthreads();
+            pick_bin(hist, pass == 2 ? 1024 : kBins, need, &pick);
+            const uint32_t bin = pick.bin;
+            if (pass == 2) eq_total = hist[bin];  // the bin of the last pass is one key: the rows that hold T
+            prefix = pass == 0 ? bin : (prefix << (pass == 1 ? 11 : 10)) | bin;
+            above += pick.above;
+            need -= pick.above;
+            __syncthreads();
+        }
+    }
+    const uint32_t T = prefix;
+    if (tid == 0) n_list = 0;
+    __syncthreads();
+    if (kk) {
+        const bool ranked = eq_total > need;  // more rows at T than are wanted: the lowest rows win
+        uint32_t running = 0;                 // rows at T in the chunks before this one
+        for (uint64_t c0 = 0; c0 < vend; c0 += kSelectChunk) {
+            const uint64_t v0 = c0 + tid * 4;
+            load_keys4(al, v0, a0, vend, key);
+            uint32_t ties = 0;
+#pragma unroll
+            for (uint32_t u = 0; u < 4; u++) {
+                const bool tie = key[u] == T;
+                ties += tie ? 1u : 0u;
+                const uint32_t slot = wave_append(key[u] > T || (tie && !ranked), &n_list);
+                if (slot < kSelectMaxK)
+                    list[slot] = ((unsigned long long)key[u] << 32) | (uint32_t)~(uint32_t)(v0 + u - a0);
+            }
+            if (ranked && running < need) {  // (uniform: `running` is the same in every thread)
+                uint32_t incl = ties;
+                for (int off = 1; off < 64; off <<= 1) {
+                    const uint32_t t = __shfl_up(incl, off);
+                    if (lane >= (uint32_t)off) incl += t;
+                }
+                if (lane == 63) wsum[wave] = incl;
+                __syncthreads();
+                uint32_t before = 0, total = 0;
+                for (uint32_t w = 0; w < kSelThreads / 64; w++) {
+                    before += w < wave ? wsum[w] : 0u;
+                    total += wsum[w];
+                }
+                uint32_t rank = running + before + incl - ties;
+#pragma unroll
+                for (uint32_t u = 0; u < 4; u++) {
+                    if (key[u] == T) {
+                        if (rank < need) list[above + rank] = ((unsigned long long)T << 32) | (uint32_t)~(uint32_t)(v0 + u - a0);
+                        rank++;
+                    }
+                }
+                running += total;
+                __syncthreads();
+            }
+        }
+    }
+    uint32_t P = 2;
+    while (P < kk) P <<= 1;
+    __syncthreads();
+    for (uint32_t i = kk + tid; i < P; i += kSelThreads) list[i] = 0ull;  // padding sorts last
+    __syncthreads();
+    for (uint32_t stage = 2; stage <= P; stage <<= 1) {
+        for (uint32_t j = stage >> 1; j > 0; j >>= 1) {
+            for (uint32_t p = tid; p < P / 2; p += kSelThreads) {
+                const uint32_t i = ((p & ~(j - 1)) << 1) | (p & (j - 1));
+                const unsigned long long x = list[i], y = list[i + j];
+                if ((i & stage) == 0 ? x < y : x > y) {
+                    list[i] = y;
+                    list[i + j] = x;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    for (uint32_t i = tid; i < k; i += kSelThreads) {
+        uint64_t row = UINT64_MAX;
+        uint32_t word = 0xFF800000u;  // -inf
+        if (i < kk) {
+            const uint32_t r = ~(uint32_t)list[i];
+            row = r;
+            word = sc[r];
+        }
+        out_rows[q * k + i] = row;
+        out_scores[q * k + i] = word;
+    }
+    if (tid == 0) out_counts[q] = kk;
+}
+
+// the large-k path reads a word of all ones as "this row does not take part"; as a score it is one more NaN.  Any other NaN takes
+// its place in the copy that is ranked (every NaN ranks alike); the scores that are returned are gathered from the original.
+__global__ void __launch_bounds__(256) deltaset_rank_words_kernel(const uint32_t* __restrict__ in, uint64_t n, uint32_t* __restrict__ out) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
+        out[i] = in[i] == kScoreSentinelBits ? 0x7FC00000u : in[i];
+}
+
+__global__ void __launch_bounds__(256) deltaset_gather_kernel(const uint32_t* __restrict__ scores, const uint64_t* __restrict__ rows, uint32_t k,
+                                                              uint32_t* __restrict__ out_scores) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < k; i += (uint64_t)gridDim.x * blockDim.x)
+        if (rows[i] != UINT64_MAX) out_scores[i] = scores[rows[i]];
+}
+
+// ---- sets made on the device (docs/delta.md §9) -------------------------------------------------------------------------------
+
+// exclusive scan of u32 counts into u64 offsets, off[n] = the total, for the whole of a set at once: one 1024-thread workgroup,
+// the scan inside a wave by shuffles, one LDS hop across the 16 waves, the running total carried across the blocks of 1024
+__global__ void __launch_bounds__(kSelThreads) deltaset_scan_kernel(const uint32_t* __restrict__ counts, uint64_t n, uint64_t* __restrict__ off) {
+    __shared__ unsigned long long wtot[kSelThreads / 64];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    unsigned long long carry = 0;
+    for (uint64_t base = 0; base < n; base += kSelThreads) {
+        const uint64_t i = base + tid;
+        const unsigned long long v = i < n ? counts[i] : 0;
+        unsigned long long incl = v;
+        for (int d = 1; d < 64; d <<= 1) {
+            const unsigned long long t = __shfl_up(incl, d);
+            if (lane >= (uint32_t)d) incl += t;
+        }
+        if (lane == 63) wtot[wave] = incl;
+        __syncthreads();
+        unsigned long long before = 0, total = 0;
+        for (uint32_t w = 0; w < kSelThreads / 64; w++) {
+            before += w < wave ? wtot[w] : 0ull;
+            total += wtot[w];
+        }
+        if (i < n) off[i] = carry + before + incl - v;
+        carry += total;
+        __syncthreads();
+    }
+    if (tid == 0) off[n] = carry;
+}
+
+// a wave per 64-row slice: 64 x the longest of its rows, the entries the slice takes in the entry-major copy (<= 64 x 65535)
+__global__ void __launch_bounds__(256) deltaset_slice_len_kernel(const uint64_t* __restrict__ indptr, uint64_t n, uint64_t nslices,
+                                                                 uint32_t* __restrict__ out) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t slice = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (slice >= nslices) return;  // a whole wave leaves together
+    const uint64_t row = slice * 64 + lane;
+    uint32_t len = row < n ? (uint32_t)(indptr[row + 1] - indptr[row]) : 0u;
+    for (int d = 32; d > 0; d >>= 1) len = max(len, (uint32_t)__shfl_xor((int)len, d));
+    if (lane == 0) out[slice] = len * 64u;
+}
+
+// a wave per row: entry e of row r goes to slice_off[r / 64] + e * 64 + r % 64; the padding was zeroed before
+__global__ void __launch_bounds__(256) deltaset_slice_write_kernel(const uint64_t* __restrict__ indptr, const uint16_t* __restrict__ pos,
+                                                                   const float* __restrict__ del, const uint64_t* __restrict__ slice_off,
+                                                                   uint64_t n, uint16_t* __restrict__ spos, float* __restrict__ sdel) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t row = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= n) return;
+    const uint64_t p0 = indptr[row], len = indptr[row + 1] - p0, base = slice_off[row >> 6] + (row & 63u);
+    for (uint64_t e = lane; e < len; e += 64) {  // (base + e * 64 < slice_off[r / 64 + 1]: the slice is as long as its longest row)
+        spos[base + e * 64] = pos[p0 + e];
+        sdel[base + e * 64] = del[p0 + e];
+    }
+}
+
+__global__ void __launch_bounds__(256) deltaset_aid_kernel(const int64_t* __restrict__ ids, uint64_t n, uint32_t* __restrict__ aid) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) aid[i] = (uint32_t)ids[i];
+}
+
+// a chunk's offsets into the set's: indptr[i] = base + off[i] for i <= m
+__global__ void __launch_bounds__(256) deltaset_rebase_kernel(const uint64_t* __restrict__ off, uint64_t m, uint64_t base, uint64_t* __restrict__ indptr) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= m; i += (uint64_t)gridDim.x * blockDim.x) indptr[i] = base + off[i];
+}
+
 // ---- host helpers -----------------------------------------------------------------------------------------------------------
 
 template <class F>
@@ -430,7 +658,21 @@ struct nmn_delta_set {
     uint16_t* d_spos = nullptr;
     float* d_sdel = nullptr;
     float* d_mag = nullptr;
+    // a set made on the device (docs/delta.md §9) holds no host copy of the seven arrays above until something asks for one:
+    // ensure_host downloads each once, at its final size, under host_mx.  nnz is stored; `ready` is recorded on the stream that
+    // built the mirror, and the library's own calls wait for it; temps are the builder's device temporaries, freed once it is done
+    uint64_t nnz = 0;
+    bool with_magnitude = false;
+    std::atomic<bool> host_present{true};
+    std::mutex host_mx;
+    hipEvent_t ready = nullptr;
+    std::vector<void*> temps;
+    void free_temps() {
+        for (void* p : temps) (void)hipFree(p);
+        temps.clear();
+    }
     void free_device() {
+        free_temps();
         for (void* p : {(void*)d_aid, (void*)d_indptr, (void*)d_pos, (void*)d_del, (void*)d_has, (void*)d_sorted, (void*)d_slice_off,
                         (void*)d_spos, (void*)d_sdel, (void*)d_mag})
             if (p) (void)hipFree(p);
@@ -634,7 +876,10 @@ hipError_t upload(T** dst, const std::vector<T>& v) {
 
 // the set's mirror; caller holds reg->rw (shared) and reg->gpu, and the registry's mirror is current
 nmn_status set_to_device(nmn_delta_set* s) {
-    if (s->resident) return NMN_OK;
+    if (s->resident) {  // a set made on the device, perhaps on a stream of the caller's: a host-buffer call waits for its end
+        if (s->ready) D_TRY(hipEventSynchronize(s->ready));
+        return NMN_OK;
+    }
     nmn_archetypes* a = s->reg;
     const uint64_t n = s->n;
     const uint32_t dim = a->dim;
@@ -703,6 +948,177 @@ nmn_status mirrors(nmn_delta_set* s) {
     return st == NMN_OK ? set_to_device(s) : st;
 }
 
+// the host arrays of a set made on the device, on first need: each array once, at its final size, under the set's lock (two
+// threads asking together get one download).  The values are those encode_batch has always returned: cached = 0.0 and has = 0
+// without with_magnitude, sorted = 1 throughout.
+nmn_status ensure_host(nmn_delta_set* s) {
+    if (s->host_present.load(std::memory_order_acquire)) return NMN_OK;
+    std::lock_guard<std::mutex> g(s->host_mx);
+    if (s->host_present.load(std::memory_order_acquire)) return NMN_OK;
+    nmn_archetypes* a = s->reg;
+    if (a->device >= 0) D_TRY(hipSetDevice(a->device));
+    if (s->ready) D_TRY(hipEventSynchronize(s->ready));
+    s->free_temps();
+    const uint64_t n = s->n;
+    s->aid.resize(n);
+    s->indptr.resize(n + 1);
+    s->pos.resize(s->nnz);
+    s->del.resize(s->nnz);
+    s->cached.assign(n, 0.0f);
+    s->has.assign(n, s->with_magnitude ? 1 : 0);
+    s->sorted.assign(n, 1);
+    D_TRY(hipMemcpy(s->aid.data(), s->d_aid, n * 4, hipMemcpyDeviceToHost));
+    D_TRY(hipMemcpy(s->indptr.data(), s->d_indptr, (n + 1) * 8, hipMemcpyDeviceToHost));
+    if (s->nnz) {
+        D_TRY(hipMemcpy(s->pos.data(), s->d_pos, s->nnz * 2, hipMemcpyDeviceToHost));
+        D_TRY(hipMemcpy(s->del.data(), s->d_del, s->nnz * 4, hipMemcpyDeviceToHost));
+    }
+    if (s->with_magnitude) D_TRY(hipMemcpy(s->cached.data(), s->d_mag, n * 4, hipMemcpyDeviceToHost));  // every row's magnitude is its cached one
+    s->host_present.store(true, std::memory_order_release);
+    return NMN_OK;
+}
+
+uint32_t stream_grid(uint64_t n) { return (uint32_t)std::min<uint64_t>(std::max<uint64_t>((n + 255) / 256, 1), 8192); }
+
+template <class T>
+hipError_t dev_alloc(T** p, uint64_t count) {
+    return hipMalloc(reinterpret_cast<void**>(p), std::max<uint64_t>(count, 1) * sizeof(T));
+}
+
+// encode n rows into a resident set without a host copy (docs/delta.md §9).  rows_host: the rows go up in chunks on `st`;
+// rows_dev: they are where they are.  Enqueues find_best, count and scan per chunk, the slice lengths and their scan, then WAITS once
+// for two u64 — the entry total and the slice total — (with more than one chunk: once per chunk for its entry total, then once
+// for the slice total), allocates, and enqueues the entry write, the slice write and the magnitudes; the set's event ends it.
+// Caller holds a->rw; the registry's mirror is current and not empty; n >= 1, dim <= 65535.
+nmn_status encode_resident(nmn_archetypes* a, const float* rows_host, const float* rows_dev, uint64_t n, float threshold, bool with_magnitude,
+                           int64_t* ids_out_dev, float* sims_out_dev, hipStream_t st, nmn_delta_set* s) {
+    const uint32_t dim = a->dim;
+    const uint64_t ch = rows_dev ? n : std::min(chunk_rows(dim), n);
+    const uint64_t nslices = (n + 63) / 64;
+    auto fail = [&](hipError_t e, const char* what) {
+        (void)hipStreamSynchronize(st);
+        s->free_device();
+        return set_error_hip(e, what);
+    };
+#define E_TRY(expr)                                   \
+    do {                                              \
+        hipError_t _e = (expr);                       \
+        if (_e != hipSuccess) return fail(_e, #expr); \
+    } while (0)
+    float* d_x = nullptr;
+    int64_t* d_ids = ids_out_dev;
+    uint32_t *d_counts = nullptr, *d_slen = nullptr;
+    uint64_t* d_off = nullptr;
+    auto temp = [&](auto** p, uint64_t count) {
+        hipError_t e = dev_alloc(p, count);
+        if (e == hipSuccess) s->temps.push_back(*p);
+        return e;
+    };
+    if (rows_host) E_TRY(temp(&d_x, ch * dim));
+    if (!d_ids) E_TRY(temp(&d_ids, n));
+    E_TRY(temp(&d_counts, ch));
+    E_TRY(temp(&d_slen, nslices));
+    E_TRY(dev_alloc(&s->d_mag, n));
+    E_TRY(dev_alloc(&s->d_indptr, n + 1));
+    E_TRY(dev_alloc(&s->d_slice_off, nslices + 1));
+    E_TRY(dev_alloc(&s->d_aid, n));
+    E_TRY(dev_alloc(&s->d_has, n));
+    E_TRY(dev_alloc(&s->d_sorted, n));
+    const bool one = ch >= n;  // one chunk: its offsets are the set's, and the one wait brings both totals
+    if (!one) E_TRY(temp(&d_off, ch + 1));
+    struct Piece {
+        uint16_t* pos;
+        float* del;
+        uint64_t total;
+    };
+    std::vector<Piece> pieces;
+    uint64_t totals[2] = {0, 0}, base = 0;
+    auto slices = [&]() {
+        hipLaunchKernelGGL(deltaset_slice_len_kernel, dim3((uint32_t)((nslices + 3) / 4)), dim3(256), 0, st, s->d_indptr, n, nslices, d_slen);
+        hipLaunchKernelGGL(deltaset_scan_kernel, dim3(1), dim3(kSelThreads), 0, st, d_slen, nslices, s->d_slice_off);
+    };
+    for (uint64_t r0 = 0; r0 < n; r0 += ch) {
+        const uint64_t m = std::min(ch, n - r0);
+        const uint32_t wave_blocks = (uint32_t)((m + 3) / 4);
+        const float* x = rows_dev ? rows_dev : d_x;
+        if (rows_host) E_TRY(hipMemcpyAsync(d_x, rows_host + r0 * dim, m * dim * 4, hipMemcpyHostToDevice, st));
+        launch_find_best(a, x, m, d_ids + r0, sims_out_dev ? sims_out_dev + r0 : nullptr, s->d_mag + r0, st);
+        hipLaunchKernelGGL(delta_count_kernel, dim3(wave_blocks), dim3(256), 0, st, x, m, dim, a->d_rows, d_ids + r0, threshold, d_counts);
+        uint64_t* off = one ? s->d_indptr : d_off;
+        hipLaunchKernelGGL(deltaset_scan_kernel, dim3(1), dim3(kSelThreads), 0, st, d_counts, m, off);
+        if (one) slices();
+        E_TRY(hipGetLastError());
+        E_TRY(hipMemcpyAsync(&totals[0], off + m, 8, hipMemcpyDeviceToHost, st));
+        if (one) E_TRY(hipMemcpyAsync(&totals[1], s->d_slice_off + nslices, 8, hipMemcpyDeviceToHost, st));
+        E_TRY(hipStreamSynchronize(st));  // the one wait (per chunk)
+        Piece p{nullptr, nullptr, totals[0]};
+        E_TRY(dev_alloc(&p.pos, p.total));
+        pieces.push_back(p);
+        E_TRY(dev_alloc(&pieces.back().del, p.total));
+        p = pieces.back();
+        hipLaunchKernelGGL(delta_write_kernel, dim3(wave_blocks), dim3(256), 0, st, x, m, dim, a->d_rows, d_ids + r0, threshold, off, p.total, p.pos,
+                           p.del);
+        if (!one) hipLaunchKernelGGL(deltaset_rebase_kernel, dim3(stream_grid(m + 1)), dim3(256), 0, st, off, m, base, s->d_indptr + r0);
+        E_TRY(hipGetLastError());
+        base += p.total;
+    }
+    s->nnz = base;
+    if (one) {
+        s->d_pos = pieces[0].pos, s->d_del = pieces[0].del;
+        pieces.clear();
+    } else {  // join the pieces device to device
+        hipError_t e = dev_alloc(&s->d_pos, base);
+        if (e == hipSuccess) e = dev_alloc(&s->d_del, base);
+        uint64_t at = 0;
+        for (const Piece& p : pieces) {
+            if (e == hipSuccess && p.total) e = hipMemcpyAsync(s->d_pos + at, p.pos, p.total * 2, hipMemcpyDeviceToDevice, st);
+            if (e == hipSuccess && p.total) e = hipMemcpyAsync(s->d_del + at, p.del, p.total * 4, hipMemcpyDeviceToDevice, st);
+            at += p.total;
+            s->temps.push_back(p.pos);
+            s->temps.push_back(p.del);
+        }
+        pieces.clear();
+        if (e != hipSuccess) return fail(e, "nmn_delta_set: joining the chunks");
+        slices();
+        E_TRY(hipGetLastError());
+        E_TRY(hipMemcpyAsync(&totals[1], s->d_slice_off + nslices, 8, hipMemcpyDeviceToHost, st));
+        E_TRY(hipStreamSynchronize(st));
+    }
+    const uint64_t slice_total = totals[1];
+    E_TRY(dev_alloc(&s->d_spos, slice_total));
+    E_TRY(dev_alloc(&s->d_sdel, slice_total));
+    if (slice_total) {  // padding is zero, as the host builder leaves it
+        E_TRY(hipMemsetAsync(s->d_spos, 0, slice_total * 2, st));
+        E_TRY(hipMemsetAsync(s->d_sdel, 0, slice_total * 4, st));
+    }
+    E_TRY(hipMemsetAsync(s->d_has, with_magnitude ? 1 : 0, n, st));
+    E_TRY(hipMemsetAsync(s->d_sorted, 1, n, st));
+    hipLaunchKernelGGL(deltaset_aid_kernel, dim3(stream_grid(n)), dim3(256), 0, st, d_ids, n, s->d_aid);
+    hipLaunchKernelGGL(deltaset_slice_write_kernel, dim3((uint32_t)((n + 3) / 4)), dim3(256), 0, st, s->d_indptr, s->d_pos, s->d_del, s->d_slice_off, n,
+                       s->d_spos, s->d_sdel);
+    E_TRY(hipGetLastError());
+    if (!with_magnitude) {  // sqrt(sum) over the reconstruction, not over the input: decode a tile of rows, then one chain per row
+        const uint64_t tile = std::min<uint64_t>(n, std::max<uint64_t>(64, (64ull << 20) / 4 / dim));
+        float* dense = nullptr;
+        E_TRY(temp(&dense, tile * dim));
+        for (uint64_t r0 = 0; r0 < n; r0 += tile) {
+            const uint64_t m = std::min(tile, n - r0);
+            hipLaunchKernelGGL(delta_decode_kernel, dim3((uint32_t)m), dim3(64), 0, st, s->d_aid, s->d_indptr, s->d_pos, s->d_del, s->d_sorted, a->d_rows,
+                               dim, r0, dense);
+            hipLaunchKernelGGL(delta_magnitude_kernel, dim3((uint32_t)((m + 255) / 256)), dim3(256), 0, st, dense, m, dim, r0, s->d_has, s->d_mag);
+        }
+        E_TRY(hipGetLastError());
+    }
+    E_TRY(hipEventCreateWithFlags(&s->ready, hipEventDisableTiming));
+    E_TRY(hipEventRecord(s->ready, st));
+#undef E_TRY
+    s->n = n;
+    s->with_magnitude = with_magnitude;
+    s->host_present.store(false, std::memory_order_release);
+    s->resident = true;
+    return NMN_OK;
+}
+
 void host_decode_row(const nmn_delta_set* s, uint64_t r, float* out) {
     const uint32_t dim = s->reg->dim;
     memcpy(out, s->reg->rows.data() + (uint64_t)s->aid[r] * dim, (size_t)dim * 4);
@@ -748,6 +1164,7 @@ nmn_status score(nmn_delta_set* s, const float* queries, uint32_t nq, int cosine
     if (n == 0 || nq == 0) return NMN_OK;
     std::shared_lock<std::shared_mutex> lk(a->rw);
     if (!on_device(a, n)) {
+        { nmn_status hs = ensure_host(s); if (hs != NMN_OK) return hs; }
         const uint64_t K = a->len();
         std::vector<float> arch_dot((size_t)nq * (K + 1));
         parallel_rows((uint64_t)nq * (K + 1), dim, [&](uint64_t b, uint64_t e) {
@@ -801,6 +1218,163 @@ nmn_status score_device(nmn_delta_set* s, const float* q_dev, uint32_t nq, float
     if (a->device >= 0) D_TRY(hipSetDevice(a->device));
     launch_score(s, q_dev, nq, scratch, cosine, out, static_cast<hipStream_t>(stream));
     D_TRY(hipGetLastError());
+    return NMN_OK;
+}
+
+// ---- top-k search -----------------------------------------------------------------------------------------------------------
+
+uint64_t align256(uint64_t bytes) { return (bytes + 255) & ~255ull; }
+
+// Which of the two selections answers.  The select kernel is one workgroup per query, so a single query over a large set keeps
+// one CU busy while the sort of the large-k path uses the whole device: measured (docs/delta.md §7), one query over 200 000 rows
+// costs the same either way and over 1M rows the sort is 2.3 times faster.  Two queries over 1M rows are still 27 % faster
+// through two sorts and are NOT routed: the rule is one query, as measured, not a model of queries x sort time.
+bool search_sorts(uint64_t n, uint32_t nq, uint32_t k) { return k > kSelectMaxK || (nq == 1 && n >= kSortSingleRows); }
+
+// the device scratch of a search of nq queries at once over n rows against K archetypes: the archetype dots, the score words, and
+// where the sort answers the ranked copy of one query's words and the sort keys of the large-k path
+struct SearchScratch {
+    uint64_t arch_dot = 0, scores = 0, words = 0, keys = 0, bytes = 0;
+    SearchScratch(uint64_t n, uint64_t K, uint32_t nq, uint32_t k) {
+        const bool sorts = search_sorts(n, nq, k);
+        scores = arch_dot + align256((uint64_t)nq * (K + 1) * 4);
+        words = scores + align256((uint64_t)nq * n * 4);
+        keys = words + (sorts ? align256(n * 4) : 0);
+        bytes = keys + (sorts ? largek_sort_len(n) * 8 : 0);
+    }
+};
+
+nmn_status search_refusals(const nmn_delta_set* s, uint32_t k) {
+    if (k == 0) return set_error(NMN_ERR_INVALID_ARGUMENT, "a top-k search needs k of at least 1");
+    if (s->n >= 0xFFFFFFFFull)
+        return set_error(NMN_ERR_INVALID_ARGUMENT, "a top-k search serves a delta set of at most 4294967294 rows: the row is the low half of a sort key");
+    return NMN_OK;
+}
+
+// score and select nq <= nq_laid queries (DEVICE) on `st`; the set and its registry are resident.  base: scratch of
+// SearchScratch(n, K, nq_laid, k), and nq_laid chooses the selection with it: the scratch of the sort is there or it is not
+hipError_t launch_search(nmn_delta_set* s, const float* q_dev, uint32_t nq, uint32_t nq_laid, uint32_t k, int cosine, char* base,
+                         uint64_t* rows_dev, float* scores_dev, uint32_t* counts_dev, hipStream_t st) {
+    const uint64_t n = s->n;
+    const SearchScratch sc(n, s->reg->d_count, nq_laid, k);
+    uint32_t* words = reinterpret_cast<uint32_t*>(base + sc.scores);
+    if (n) launch_score(s, q_dev, nq, reinterpret_cast<float*>(base + sc.arch_dot), cosine, reinterpret_cast<float*>(words), st);
+    if (!search_sorts(n, nq_laid, k) || n == 0) {  // (no rows: the kernel reads none and writes the unused slots)
+        hipLaunchKernelGGL(deltaset_select_kernel, dim3(nq), dim3(kSelThreads), 0, st, words, n, k, rows_dev, reinterpret_cast<uint32_t*>(scores_dev),
+                           counts_dev);
+        return hipGetLastError();
+    }
+    uint32_t* ranked = reinterpret_cast<uint32_t*>(base + sc.words);
+    const uint32_t grid_n = (uint32_t)std::min<uint64_t>((n + 255) / 256, 8192), grid_k = (uint32_t)std::min<uint64_t>(((uint64_t)k + 255) / 256, 8192);
+    for (uint32_t q = 0; q < nq; q++) {  // the sort of the large-k path, one query at a time: the same order by construction
+        const uint32_t* w = words + (uint64_t)q * n;
+        hipLaunchKernelGGL(deltaset_rank_words_kernel, dim3(grid_n), dim3(256), 0, st, w, n, ranked);
+        hipError_t e = launch_largek(ranked, n, reinterpret_cast<uint64_t*>(base + sc.keys), k, 0, rows_dev + (uint64_t)q * k,
+                                     scores_dev + (uint64_t)q * k, counts_dev + q, st);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(deltaset_gather_kernel, dim3(grid_k), dim3(256), 0, st, w, rows_dev + (uint64_t)q * k, k,
+                           reinterpret_cast<uint32_t*>(scores_dev + (uint64_t)q * k));
+    }
+    return hipGetLastError();
+}
+
+// the queries one step of a host-buffer search takes: their score words and their answers each stay within kSearchBudget
+uint32_t search_block(uint64_t n, uint32_t nq, uint32_t k) {
+    const uint64_t by_scores = kSearchBudget / std::max<uint64_t>(n * 4, 1), by_answers = kSearchBudget / ((uint64_t)k * 12);
+    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(nq, std::min(by_scores, by_answers)));
+}
+
+nmn_status search(nmn_delta_set* s, const float* queries, uint32_t nq, uint32_t k, int cosine, uint64_t* rows_out, float* scores_out,
+                  uint32_t* counts_out) {
+    if (!s) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    nmn_status st = search_refusals(s, k);
+    if (st != NMN_OK) return st;
+    if (nq && (!queries || !rows_out || !scores_out || !counts_out)) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    if (nq == 0) return NMN_OK;
+    nmn_archetypes* a = s->reg;
+    const uint64_t n = s->n;
+    const uint32_t dim = a->dim;
+    const uint32_t kk = (uint32_t)std::min<uint64_t>(k, n);
+    const uint32_t qb = search_block(n, nq, k);
+    if (n == 0 || !on_device(a, n)) {
+        // the host scores, then a partial sort of the composites key << 32 | ~row: the same key and the same tie rule
+        std::vector<float> sc((size_t)qb * n);
+        for (uint32_t q0 = 0; q0 < nq; q0 += qb) {
+            const uint32_t m = std::min(qb, nq - q0);
+            if (n) {
+                st = score(s, queries + (uint64_t)q0 * dim, m, cosine, sc.data());
+                if (st != NMN_OK) return st;
+            }
+            parallel_rows(m, n * 8, [&](uint64_t b, uint64_t e) {
+                std::vector<uint64_t> comp(n);
+                for (uint64_t q = b; q < e; q++) {
+                    const float* row_scores = sc.data() + q * n;
+                    for (uint64_t r = 0; r < n; r++) comp[r] = ((uint64_t)score_to_key(row_scores[r]) << 32) | (uint32_t)~(uint32_t)r;
+                    std::partial_sort(comp.begin(), comp.begin() + kk, comp.end(), std::greater<uint64_t>());
+                    uint64_t* ro = rows_out + (q0 + q) * k;
+                    float* so = scores_out + (q0 + q) * k;
+                    for (uint32_t i = 0; i < k; i++) {
+                        const uint32_t unused = 0xFF800000u;  // -inf
+                        if (i < kk) {
+                            const uint32_t r = ~(uint32_t)comp[i];
+                            ro[i] = r;
+                            memcpy(so + i, row_scores + r, 4);  // the row's own bits
+                        } else {
+                            ro[i] = UINT64_MAX;
+                            memcpy(so + i, &unused, 4);
+                        }
+                    }
+                    counts_out[q0 + q] = kk;
+                }
+            });
+        }
+        return NMN_OK;
+    }
+    std::shared_lock<std::shared_mutex> lk(a->rw);
+    std::lock_guard<std::mutex> g(a->gpu);
+    st = mirrors(s);
+    if (st != NMN_OK) return st;
+    const SearchScratch lay(n, a->d_count, qb, k);
+    DevBuf d_q, d_scratch, d_rows, d_sc, d_counts;
+    D_TRY(d_q.alloc((size_t)qb * dim * 4));
+    D_TRY(d_scratch.alloc(lay.bytes));
+    D_TRY(d_rows.alloc((size_t)qb * k * 8));
+    D_TRY(d_sc.alloc((size_t)qb * k * 4));
+    D_TRY(d_counts.alloc((size_t)qb * 4));
+    for (uint32_t q0 = 0; q0 < nq; q0 += qb) {
+        const uint32_t m = std::min(qb, nq - q0);
+        D_TRY(hipMemcpyAsync(d_q.p, queries + (uint64_t)q0 * dim, (size_t)m * dim * 4, hipMemcpyHostToDevice, a->stream));
+        // (the layout of qb queries serves a last, shorter block too: launch_search lays out m queries within it)
+        D_TRY(launch_search(s, d_q.as<float>(), m, qb, k, cosine, d_scratch.as<char>(), d_rows.as<uint64_t>(), d_sc.as<float>(), d_counts.as<uint32_t>(),
+                            a->stream));
+        D_TRY(hipMemcpyAsync(rows_out + (uint64_t)q0 * k, d_rows.p, (size_t)m * k * 8, hipMemcpyDeviceToHost, a->stream));
+        D_TRY(hipMemcpyAsync(scores_out + (uint64_t)q0 * k, d_sc.p, (size_t)m * k * 4, hipMemcpyDeviceToHost, a->stream));
+        D_TRY(hipMemcpyAsync(counts_out + q0, d_counts.p, (size_t)m * 4, hipMemcpyDeviceToHost, a->stream));
+        D_TRY(hipStreamSynchronize(a->stream));
+    }
+    return NMN_OK;
+}
+
+nmn_status search_device(nmn_delta_set* s, const float* q_dev, uint32_t nq, uint32_t k, int cosine, void* scratch, uint64_t scratch_bytes,
+                         uint64_t* rows_dev, float* scores_dev, uint32_t* counts_dev, void* stream) {
+    if (!s) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    nmn_status st = search_refusals(s, k);
+    if (st != NMN_OK) return st;
+    if (!q_dev || !scratch || !rows_dev || !scores_dev || !counts_dev) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    nmn_archetypes* a = s->reg;
+    std::shared_lock<std::shared_mutex> lk(a->rw);
+    if (!a->d_valid || a->d_count != a->len())
+        return set_error(NMN_ERR_INVALID_ARGUMENT, "the registry is not resident on the device: call nmn_archetypes_to_device after the last register");
+    if (!s->resident) return set_error(NMN_ERR_INVALID_ARGUMENT, "the delta set is not resident on the device: call nmn_delta_set_to_device first");
+    if (reinterpret_cast<uintptr_t>(scratch) & 15u) return set_error(NMN_ERR_INVALID_ARGUMENT, "the search scratch must be aligned to 16 bytes");
+    const uint64_t want = SearchScratch(s->n, a->d_count, nq, k).bytes;
+    if (scratch_bytes < want)
+        return set_error(NMN_ERR_INVALID_ARGUMENT, ("the search scratch holds " + std::to_string(scratch_bytes) + " bytes, the search needs " +
+                                                    std::to_string(want) + " (nmn_deltaset_search_scratch_bytes)")
+                                                       .c_str());
+    if (nq == 0) return NMN_OK;
+    if (a->device >= 0) D_TRY(hipSetDevice(a->device));
+    D_TRY(launch_search(s, q_dev, nq, nq, k, cosine, static_cast<char*>(scratch), rows_dev, scores_dev, counts_dev, static_cast<hipStream_t>(stream)));
     return NMN_OK;
 }
 
@@ -983,7 +1557,16 @@ extern "C" nmn_status nmn_archetypes_encode_batch(nmn_archetypes* a, const float
     nmn_delta_set* s = new nmn_delta_set();
     s->reg = a;
     s->indptr.assign(1, 0);
-    if (a->len() != 0 && n != 0) {
+    if (a->len() != 0 && n != 0 && on_device(a, n)) {
+        // the device path: the chunks go up as before, every piece of the CSR stays in HBM and the set is finished there
+        std::lock_guard<std::mutex> g(a->gpu);
+        nmn_status st = registry_to_device(a);
+        if (st == NMN_OK) st = encode_resident(a, rows, nullptr, n, threshold, with_magnitude != 0, nullptr, nullptr, a->stream, s);
+        if (st != NMN_OK) {
+            delete s;
+            return st;
+        }
+    } else if (a->len() != 0 && n != 0) {
         std::vector<int64_t> ids;
         std::vector<float> sims, mags;
         nmn_status st = encode_rows(a, rows, n, threshold, ids, sims, mags, s->indptr, true, s->pos, s->del);
@@ -992,6 +1575,7 @@ extern "C" nmn_status nmn_archetypes_encode_batch(nmn_archetypes* a, const float
             return st;
         }
         s->n = n;
+        s->nnz = s->pos.size();
         s->aid.resize(n);
         for (uint64_t i = 0; i < n; i++) s->aid[i] = (uint32_t)ids[i];
         s->has.assign(n, with_magnitude ? 1 : 0);
@@ -1040,6 +1624,7 @@ extern "C" nmn_status nmn_delta_set_from_parts(nmn_archetypes* a, uint64_t n, co
     s->aid.resize(n);
     for (uint64_t i = 0; i < n; i++) s->aid[i] = (uint32_t)archetype_ids[i];
     s->indptr.assign(indptr, indptr + n + 1);
+    s->nnz = nnz;
     s->pos.assign(positions, positions + nnz);
     s->del.assign(deltas, deltas + nnz);
     s->has.assign(n, 0);
@@ -1058,6 +1643,10 @@ extern "C" nmn_status nmn_delta_set_destroy(nmn_delta_set* s) {
     if (s->d_aid) {
         std::lock_guard<std::mutex> g(s->reg->gpu);
         if (s->reg->device >= 0) (void)hipSetDevice(s->reg->device);
+        if (s->ready) {  // a set made on a stream of the caller's: its last kernel has run before its arrays go
+            (void)hipEventSynchronize(s->ready);
+            (void)hipEventDestroy(s->ready);
+        }
         if (s->reg->stream) (void)hipStreamSynchronize(s->reg->stream);
         s->free_device();
     }
@@ -1066,11 +1655,12 @@ extern "C" nmn_status nmn_delta_set_destroy(nmn_delta_set* s) {
 }
 
 extern "C" uint64_t nmn_delta_set_len(nmn_delta_set* s) { return s ? s->n : 0; }
-extern "C" uint64_t nmn_delta_set_nnz(nmn_delta_set* s) { return s ? s->pos.size() : 0; }
+extern "C" uint64_t nmn_delta_set_nnz(nmn_delta_set* s) { return s ? s->nnz : 0; }
 
 extern "C" nmn_status nmn_delta_set_arrays(nmn_delta_set* s, uint64_t* archetype_ids, uint64_t* indptr, uint16_t* positions, float* deltas,
                                            float* cached, uint8_t* has_cached, uint8_t* sorted_out) {
     if (!s) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    { nmn_status hs = ensure_host(s); if (hs != NMN_OK) return hs; }
     for (uint64_t i = 0; archetype_ids && i < s->n; i++) archetype_ids[i] = s->aid[i];
     if (indptr) memcpy(indptr, s->indptr.data(), (s->n + 1) * 8);
     if (positions && !s->pos.empty()) memcpy(positions, s->pos.data(), s->pos.size() * 2);
@@ -1083,12 +1673,14 @@ extern "C" nmn_status nmn_delta_set_arrays(nmn_delta_set* s, uint64_t* archetype
 
 extern "C" nmn_status nmn_delta_set_compression_ratio(nmn_delta_set* s, float* out) {
     if (!s || (!out && s->n)) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    { nmn_status hs = ensure_host(s); if (hs != NMN_OK) return hs; }
     for (uint64_t i = 0; i < s->n; i++) out[i] = ratio_of(s->reg->dim, s->indptr[i + 1] - s->indptr[i]);
     return NMN_OK;
 }
 
 extern "C" nmn_status nmn_delta_set_memory_bytes(nmn_delta_set* s, uint64_t* out) {
     if (!s || (!out && s->n)) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    { nmn_status hs = ensure_host(s); if (hs != NMN_OK) return hs; }
     for (uint64_t i = 0; i < s->n; i++) out[i] = NMN_DELTA_VECTOR_BYTES + (s->indptr[i + 1] - s->indptr[i]) * 6;
     return NMN_OK;
 }
@@ -1100,6 +1692,7 @@ extern "C" nmn_status nmn_delta_set_decode(nmn_delta_set* s, float* out) {
     const uint32_t dim = a->dim;
     std::shared_lock<std::shared_mutex> lk(a->rw);
     if (!on_device(a, s->n)) {
+        { nmn_status hs = ensure_host(s); if (hs != NMN_OK) return hs; }
         parallel_rows(s->n, dim, [&](uint64_t b, uint64_t e) {
             for (uint64_t r = b; r < e; r++) host_decode_row(s, r, out + r * dim);
         });
@@ -1128,6 +1721,7 @@ extern "C" nmn_status nmn_delta_set_magnitudes(nmn_delta_set* s, float* out) {
     nmn_archetypes* a = s->reg;
     std::shared_lock<std::shared_mutex> lk(a->rw);
     if (!on_device(a, s->n)) {
+        { nmn_status hs = ensure_host(s); if (hs != NMN_OK) return hs; }
         host_magnitudes(s, out);
         return NMN_OK;
     }
@@ -1157,6 +1751,10 @@ extern "C" nmn_status nmn_delta_set_dot_same_archetype(nmn_delta_set* sa, nmn_de
     const uint32_t dim = a->dim;
     std::shared_lock<std::shared_mutex> lk(a->rw);
     if (!on_device(a, n_pairs)) {
+        for (nmn_delta_set* s : {sa, sb}) {
+            nmn_status hs = ensure_host(s);
+            if (hs != NMN_OK) return hs;
+        }
         parallel_rows(n_pairs, 64, [&](uint64_t b, uint64_t e) {
             for (uint64_t i = b; i < e; i++) {
                 const uint64_t ra = pairs[2 * i], rb = pairs[2 * i + 1];
@@ -1226,3 +1824,59 @@ extern "C" nmn_status nmn_delta_set_cosine_dense_device(nmn_delta_set* s, const 
                                                         float* out_dev, void* stream) {
     return score_device(s, queries_dev, nq, scratch_dev, out_dev, 1, stream);
 }
+
+// ---- top-k over a delta set (docs/delta.md §8) --------------------------------------------------------------------------------
+
+extern "C" nmn_status nmn_deltaset_limits(uint32_t* select_chunk_rows, uint32_t* select_max_k, uint64_t* block_budget_bytes,
+                                          uint64_t* sort_single_query_rows) {
+    if (sort_single_query_rows) *sort_single_query_rows = kSortSingleRows;
+    if (select_chunk_rows) *select_chunk_rows = kSelectChunk;
+    if (select_max_k) *select_max_k = kSelectMaxK;
+    if (block_budget_bytes) *block_budget_bytes = kSearchBudget;
+    return NMN_OK;
+}
+
+extern "C" uint64_t nmn_deltaset_search_scratch_bytes(nmn_delta_set* s, uint32_t nq, uint32_t k) {
+    if (!s) return 0;
+    std::shared_lock<std::shared_mutex> lk(s->reg->rw);
+    return SearchScratch(s->n, s->reg->len(), nq, k).bytes;
+}
+
+extern "C" nmn_status nmn_deltaset_search(nmn_delta_set* s, const float* queries, uint32_t nq, uint32_t k, int32_t cosine, uint64_t* rows_out,
+                                          float* scores_out, uint32_t* counts_out) {
+    return search(s, queries, nq, k, cosine != 0, rows_out, scores_out, counts_out);
+}
+
+extern "C" nmn_status nmn_deltaset_search_device(nmn_delta_set* s, const float* queries_dev, uint32_t nq, uint32_t k, int32_t cosine,
+                                                 void* scratch_dev, uint64_t scratch_bytes, uint64_t* rows_dev, float* scores_dev,
+                                                 uint32_t* counts_dev, void* stream) {
+    return search_device(s, queries_dev, nq, k, cosine != 0, scratch_dev, scratch_bytes, rows_dev, scores_dev, counts_dev, stream);
+}
+
+// ---- sets made on the device (docs/delta.md §9) -------------------------------------------------------------------------------
+
+extern "C" nmn_status nmn_deltaset_encode_device(nmn_archetypes* a, const float* rows_dev, uint64_t n, float threshold, int32_t with_magnitude,
+                                                 int64_t* ids_dev, float* sims_dev, void* stream, nmn_delta_set** out) {
+    if (!a || (!rows_dev && n) || !out) return set_error(NMN_ERR_INVALID_ARGUMENT, "null argument");
+    *out = nullptr;
+    std::shared_lock<std::shared_mutex> lk(a->rw);
+    if (a->len() == 0) return set_error(NMN_ERR_INVALID_ARGUMENT, "the registry is empty: encode is None for every row");
+    if (!a->d_valid || a->d_count != a->len())
+        return set_error(NMN_ERR_INVALID_ARGUMENT, "the registry is not resident on the device: call nmn_archetypes_to_device after the last register");
+    if (a->dim > NMN_DELTA_MAX_DIMENSION) return set_error(NMN_ERR_INVALID_ARGUMENT, dimension_exceeded(a->dim).c_str());
+    nmn_delta_set* s = new nmn_delta_set();
+    s->reg = a;
+    s->indptr.assign(1, 0);
+    if (n) {
+        if (a->device >= 0) D_TRY(hipSetDevice(a->device));
+        nmn_status st = encode_resident(a, nullptr, rows_dev, n, threshold, with_magnitude != 0, ids_dev, sims_dev, static_cast<hipStream_t>(stream), s);
+        if (st != NMN_OK) {
+            delete s;
+            return st;
+        }
+    }
+    *out = s;
+    return NMN_OK;
+}
+
+extern "C" int32_t nmn_deltaset_host_arrays_present(nmn_delta_set* s) { return s && s->host_present.load(std::memory_order_acquire) ? 1 : 0; }

@@ -65,6 +65,22 @@ def limits():
     return tuple(int(x.value) for x in v)
 
 
+def search_limits():
+    """(select_chunk_rows, select_max_k, block_budget_bytes, sort_single_query_rows) of DeltaSet.search on the device
+    (nmn_deltaset_limits): the rows a step of the select workgroup reads, the largest k it serves (above: the sort of the large-k
+    path), the bytes of score words a block of queries of the host-buffer form may fill, and the rows from which a call of one
+    query takes the sort as well"""
+    a, b, c, d = C.c_uint32(), C.c_uint32(), C.c_uint64(), C.c_uint64()
+    _capi.check(_capi.load().nmn_deltaset_limits(C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+    return int(a.value), int(b.value), int(c.value), int(d.value)
+
+
+def _metric(metric):
+    if metric not in ("dot", "cosine"):
+        raise DeltaVectorError(f"metric must be \"dot\" or \"cosine\", got {metric!r}")
+    return int(metric == "cosine")
+
+
 class CoverageStats:
     """CoverageStats (delta_vector.rs:677-687)"""
 
@@ -217,6 +233,23 @@ class ArchetypeRegistry:
                                                          C.c_void_p(sims.data_ptr()), _stream(stream)))
         return ids, sims
 
+    def encode_batch_device(self, vectors, threshold, with_magnitude=False, stream=None, return_assignments=False):
+        """nmn_deltaset_encode_device on an f32 tensor [n][dim] of the registry's device (the registry resident: to_device) -> a
+        resident DeltaSet without host arrays; with return_assignments (DeltaSet, ids int64 tensor [n], sims f32 tensor [n]).  The
+        call waits once on the stream, for the two totals that size the set, and returns with the rest enqueued.  The rows must stay
+        as they are until the stream has run the call"""
+        import torch
+        assert vectors.dtype == torch.float32 and vectors.is_contiguous() and vectors.shape[-1] == self.dim
+        n = vectors.numel() // self.dim
+        ids = torch.empty(n, dtype=torch.int64, device=vectors.device) if return_assignments else None
+        sims = torch.empty(n, dtype=torch.float32, device=vectors.device) if return_assignments else None
+        h = C.c_void_p()
+        _check(self._lib.nmn_deltaset_encode_device(self._h, C.c_void_p(vectors.data_ptr()), n, C.c_float(threshold), int(bool(with_magnitude)),
+                                                    None if ids is None else C.c_void_p(ids.data_ptr()),
+                                                    None if sims is None else C.c_void_p(sims.data_ptr()), _stream(stream), C.byref(h)))
+        s = DeltaSet(self, h)
+        return (s, ids, sims) if return_assignments else s
+
 
 class DeltaSet:
     """N DeltaVectors (delta_vector.rs:72-417) against one registry: archetype id per row, CSR offsets, u16 positions, f32 deltas
@@ -261,6 +294,11 @@ class DeltaSet:
     @property
     def nnz(self):
         return int(self._lib.nmn_delta_set_nnz(self._h))
+
+    @property
+    def host_arrays_present(self):
+        """False while a set made on the device holds no host copy of its arrays (nmn_deltaset_host_arrays_present)"""
+        return bool(self._lib.nmn_deltaset_host_arrays_present(self._h))
 
     @property
     def dimension(self):
@@ -356,3 +394,41 @@ class DeltaSet:
 
     def cosine_similarity_dense_device(self, queries, out=None, stream=None, scratch=None):
         return self._score_device(self._lib.nmn_delta_set_cosine_dense_device, queries, out, stream, scratch)
+
+    # -- top-k (docs/delta.md §8) --------------------------------------------------------------------------------------------------
+    def search(self, queries, k, metric="dot"):
+        """the first min(k, n) rows per query under (score descending, row ascending; -0.0 = +0.0; every NaN alike, below -inf), the
+        score being dot_dense's ("dot") or cosine_similarity_dense's ("cosine") -> (rows int64 [nq][k], scores f32 [nq][k], counts
+        uint32 [nq]); the unused slots hold row -1 and score -inf.  The scores are the rows' own bits."""
+        q = _rows(queries, self.registry.dim, "queries")
+        nq, k = q.shape[0], int(k)
+        rows = np.full((nq, max(k, 0)), 2 ** 64 - 1, dtype=np.uint64)
+        scores = np.full((nq, max(k, 0)), -np.inf, dtype=np.float32)
+        counts = np.zeros(nq, dtype=np.uint32)
+        _check(self._lib.nmn_deltaset_search(self._h, _p(q), nq, max(k, 0), _metric(metric), _p(rows), _p(scores), _p(counts)))
+        return rows.view(np.int64), scores, counts
+
+    def search_scratch_bytes(self, nq, k):
+        """the bytes of scratch a stream-ordered search of nq queries overwrites (nmn_deltaset_search_scratch_bytes)"""
+        return int(self._lib.nmn_deltaset_search_scratch_bytes(self._h, int(nq), int(k)))
+
+    def search_device(self, queries, k, metric="dot", stream=None, scratch=None):
+        """nmn_deltaset_search_device on an f32 tensor [nq][dim]: enqueued, not waited for -> (rows int64 tensor [nq][k], scores f32
+        tensor [nq][k], counts int32 tensor [nq]).  scratch: a uint8 tensor of search_scratch_bytes(nq, k) the caller keeps alive until
+        the kernels have run; None allocates one per call, as the stream-ordered scores do"""
+        import torch
+        assert queries.dtype == torch.float32 and queries.is_contiguous() and queries.shape[-1] == self.registry.dim
+        nq, k = queries.numel() // self.registry.dim, int(k)
+        need = self.search_scratch_bytes(nq, k)
+        if scratch is None:
+            scratch = torch.empty(max(need, 16), dtype=torch.uint8, device=queries.device)
+            if stream is not None:
+                scratch.record_stream(torch.cuda.ExternalStream(int(stream), device=queries.device))
+        assert scratch.dtype == torch.uint8 and scratch.is_contiguous()
+        rows = torch.empty((nq, max(k, 0)), dtype=torch.int64, device=queries.device)
+        scores = torch.empty((nq, max(k, 0)), dtype=torch.float32, device=queries.device)
+        counts = torch.empty(nq, dtype=torch.int32, device=queries.device)
+        _check(self._lib.nmn_deltaset_search_device(self._h, C.c_void_p(queries.data_ptr()), nq, max(k, 0), _metric(metric),
+                                                    C.c_void_p(scratch.data_ptr()), scratch.numel(), C.c_void_p(rows.data_ptr()),
+                                                    C.c_void_p(scores.data_ptr()), C.c_void_p(counts.data_ptr()), _stream(stream)))
+        return rows, scores, counts

@@ -45,8 +45,58 @@ def timed(fn, reps):
     return float(np.median(t)), float(min(t)), float(max(t))
 
 
+def search_bench(a, reg, x, q_all, threshold, res):
+    """--search: DeltaSet.search (docs/delta.md §8) at k = --top-k over --rows rows, per --search-nq: the call with host buffers, the
+    stream-ordered call on resident tensors (enqueue to synchronize), the score kernels alone on resident tensors, and the same
+    search at k = select_max_k + 1, which takes the sort of the large-k path — the only way the score array could be ranked before
+    the select kernel.  First the host path and the device path are compared bit for bit on --host-rows rows."""
+    import torch
+    max_k = nd.search_limits()[1]
+    hx = x[:min(a.host_rows, a.rows)]
+    reg.set_min_device_rows(nd.NEVER_DEVICE)
+    h_set = reg.encode_batch(hx, threshold, True)
+    host_answers = [h_set.search(q_all[:8], k, m) for k in (a.top_k, max_k + 1) for m in ("dot", "cosine")]
+    res["host_search_s"] = timed(lambda: h_set.search(q_all[:8], a.top_k), a.reps)[0]
+    reg.set_min_device_rows(nd.ALWAYS_DEVICE)
+    d_set = reg.encode_batch(hx, threshold, True)
+    dev_answers = [d_set.search(q_all[:8], k, m) for k in (a.top_k, max_k + 1) for m in ("dot", "cosine")]
+    same = all(np.array_equal(h[0], d[0]) and np.array_equal(h[1].view(np.uint32), d[1].view(np.uint32)) and np.array_equal(h[2], d[2])
+               for h, d in zip(host_answers, dev_answers))
+    res["paths_agree_bit_for_bit"] = bool(same)
+    if not same:
+        return 1
+    s = reg.encode_batch(x, threshold, True).to_device()
+    n = len(s)
+    res["search_top_k"], res["large_k"] = a.top_k, max_k + 1
+
+    def resident(fn):
+        def run():
+            fn()
+            torch.cuda.synchronize()
+        return run
+    for nq in a.search_nq:
+        q = q_all[:nq]
+        tq = torch.from_numpy(q).cuda()
+        scratch = torch.empty(s.search_scratch_bytes(nq, max_k + 1), dtype=torch.uint8, device="cuda")
+        fscratch = torch.empty(s.scratch_floats(nq), dtype=torch.float32, device="cuda")
+        out = torch.empty((nq, n), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        for name, fn in (("host_buffers", lambda: s.search(q, a.top_k)),
+                         ("resident", resident(lambda: s.search_device(tq, a.top_k, scratch=scratch))),
+                         ("resident_scores_only", resident(lambda: s.dot_dense_device(tq, out=out, scratch=fscratch))),
+                         ("resident_large_k_path", resident(lambda: s.search_device(tq, max_k + 1, scratch=scratch)))):
+            med, lo, hi = timed(fn, a.reps)
+            res[f"search_nq{nq}_{name}_s"] = med
+            res[f"search_nq{nq}_{name}_min_max_s"] = [lo, hi]
+        res[f"search_nq{nq}_select_bytes_read"] = 4 * n * 4 * nq          # the yardstick: 4 passes x n x 4 bytes per query
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--search", action="store_true", help="time DeltaSet.search instead of find_best / encode_batch / dot_dense")
+    ap.add_argument("--top-k", type=int, default=10)
+    ap.add_argument("--search-nq", type=int, nargs="+", default=[1, 8, 64])
     ap.add_argument("--rows", type=int, default=200000)
     ap.add_argument("--dim", type=int, default=128)
     ap.add_argument("--k", type=int, default=16)
@@ -65,6 +115,15 @@ def main():
     hx = x[:min(a.host_rows, a.rows)]
     res = dict(rows=a.rows, dim=a.dim, k=a.k, keep=a.keep, nq=a.nq, host_rows=int(hx.shape[0]), small_rows=a.small_rows, threshold=threshold,
                reps=a.reps)
+    if a.search:
+        q_all = np.random.default_rng(a.seed + 1).standard_normal((max(a.search_nq + [8]), a.dim)).astype(np.float32)
+        rc = search_bench(a, reg, x, q_all, threshold, res)
+        line = json.dumps(res)
+        print(line)
+        if a.out and rc == 0:
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        return rc
 
     # the two paths on the host's rows: the same bits, or nothing below means anything
     reg.set_min_device_rows(nd.NEVER_DEVICE)
@@ -95,6 +154,34 @@ def main():
             res[f"{name}_{op}_s"] = med
             res[f"{name}_{op}_min_max_s"] = [lo, hi]
             res[f"{name}_{op}_us_per_row"] = med / n * 1e6
+    # a set made where the rows are (docs/delta.md §9): the rows resident, the call up to a device synchronize; and, apart, the first
+    # arrays() of such a set — the download the host-buffer encode_batch used to include
+    import torch
+    reg.set_min_device_rows(nd.ALWAYS_DEVICE)
+    reg.to_device()
+    tx = torch.from_numpy(x).cuda()
+    torch.cuda.synchronize()
+
+    def born():
+        s = reg.encode_batch_device(tx, threshold, True)
+        torch.cuda.synchronize()
+        return s
+    med, lo, hi = timed(born, a.reps)
+    res["device_encode_batch_device_s"], res["device_encode_batch_device_min_max_s"] = med, [lo, hi]
+    first = []
+    for _ in range(a.reps):
+        s = born()
+        t0 = time.perf_counter()
+        s.arrays()
+        first.append(time.perf_counter() - t0)
+    res["device_first_arrays_s"], res["device_first_arrays_min_max_s"] = float(np.median(first)), [float(min(first)), float(max(first))]
+    h = reg.encode_batch(x[:a.host_rows], threshold, True)
+    d = reg.encode_batch_device(tx[:a.host_rows], threshold, True)
+    res["device_born_equals_host_buffer_set"] = bool(all(np.array_equal(h.arrays()[k].view(np.uint8), d.arrays()[k].view(np.uint8)) for k in h.arrays()))
+    # the whole batch through the host-buffer call (above 256 MiB of rows: several chunks, joined on the device) against the same
+    # rows encoded where they are
+    full_h, full_d = reg.encode_batch(x, threshold, True).arrays(), born().arrays()
+    res["chunked_equals_device_born"] = bool(all(np.array_equal(full_h[k].view(np.uint8), full_d[k].view(np.uint8)) for k in full_h))
     for op in ("find_best", "encode_batch", "dot_dense"):
         per_dev, per_host = res[f"device_{op}_us_per_row"], res[f"host_{op}_us_per_row"]
         res[f"{op}_host_over_device"] = per_host / per_dev
